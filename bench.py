@@ -21,6 +21,9 @@ communicator set-up never returns, naming the stage.
 After the timed region the run verifies itself (sampled planes of one more step, bit for bit
 against the CPU oracle) and, on one GPU, times the other single-GPU BASELINE configurations.
 
+--dump-outputs DIR writes what the last timed step computed (whole planes and a seeded sample of
+cells, at most 64 MiB) as .npy files, so that two builds can be compared output for output.
+
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how every field is derived.
 """
 import argparse
@@ -103,7 +106,16 @@ def parse_args():
     ap.add_argument("--cpu-sample-planes", type=int, default=0, help="dim-0 extent of the CPU sample (0 = auto)")
     ap.add_argument("--hbm-traffic-bytes", type=float, default=None,
                     help="per-launch HBM bytes from a separate rocprofv3 --pmc pass (reported as roofline.traffic)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the field the last timed step produced to DIR as .npy files in its "
+                         "own dtype: field_planes.npy (up to 5 whole dim-0 planes: both ends, their neighbours, the middle) "
+                         "and field_sample.npy (a fixed, seeded sample of cells), at most 64 MiB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 class Watchdog:
@@ -613,6 +625,14 @@ def main():
     assert bool(torch.isfinite(mid).all()), "non-finite values in the result"
     assert float(mid.abs().max()) > 0.0, "result is identically zero"
 
+    # ---- what the last timed step computed, before anything below reuses the buffers ------------------------------------
+    if args.dump_outputs:
+        dog.stage("dump of the outputs", 300)
+        result = bufs[1] if args.fixed_input else bufs[(args.warmup + args.steps) % 2]
+        dump_outputs(args.dump_outputs, torch, dist, world, rank, sl, emu, result, gbox, coll_dev)
+        barrier()
+        dog.done()
+
     # ---- where a sharded step's time goes (untimed-for-the-result extra steps; C-ABI transports only) -----------------
     breakdown = None
     if (world > 1 or emu is not None) and hasattr(op, "rccl") and op.rccl is not None:
@@ -800,6 +820,67 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     dog.done()
+
+
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_PLANES_BYTES = 40 << 20      # ... of which whole planes
+DUMP_SAMPLE_CELLS = 1 << 21       # ... and this many sampled cells (16 MiB in fp64)
+
+
+def dump_outputs(directory, torch, dist, world, rank, sl, emu, result, gbox, coll_dev):
+    """--dump-outputs: write what the last timed step computed.  field_planes.npy holds whole dim-0 planes of the global field
+    (both ends, their neighbours and the middle, as many as fit in DUMP_PLANES_BYTES); field_sample.npy holds
+    DUMP_SAMPLE_CELLS cells drawn with a fixed seed (sorted row-major indices, with repeats).  Both are in the field's dtype.
+    Which planes and cells are written depends on the shape alone, so runs with the same arguments write the same cells.
+    Under --emulate-rank the emulated rank's slab stands for the field.  N > 1: every rank contributes the cells it owns and
+    rank 0 writes the files."""
+    import numpy as np
+    from neptune_hip import slab as slab_mod
+    gshape = [u - l for l, u in zip(*gbox)]
+    plane_cells = int(np.prod(gshape[1:], dtype=np.int64))
+    t = result.tensor
+    esize = t.element_size()
+    p0, p1 = (sl.start, sl.stop) if emu is not None else (gbox[0][0], gbox[1][0])
+    fit = DUMP_PLANES_BYTES // (plane_cells * esize)
+    planes = []
+    for p in (p0, p1 - 1, p0 + 1, p1 - 2, (p0 + p1) // 2):
+        if p0 <= p < p1 and p not in planes and len(planes) < fit:
+            planes.append(p)
+    planes.sort()
+    n_cells = (p1 - p0) * plane_cells
+    m = min(DUMP_SAMPLE_CELLS, n_cells)
+    idx = np.sort(np.random.default_rng(SEED).integers(0, n_cells, size=m, dtype=np.int64)) + p0 * plane_cells
+    assert (len(planes) * plane_cells + m) * esize <= DUMP_BUDGET_BYTES
+
+    # this process's part: the cells of its owned planes, zeros elsewhere
+    flat = t.reshape(-1)
+    lo = sl.owned_planes()[0]
+    base = (lo - sl.start) * plane_cells            # local flat index = global flat index + base
+    packed = torch.zeros(len(planes) * plane_cells + m, dtype=t.dtype, device=t.device)
+    for i, p in enumerate(planes):
+        if sl.start <= p < sl.stop:
+            packed[i * plane_cells:(i + 1) * plane_cells] = flat[p * plane_cells + base:(p + 1) * plane_cells + base]
+    mine = (idx >= sl.start * plane_cells) & (idx < sl.stop * plane_cells)
+    if mine.any():
+        at = torch.from_numpy(np.nonzero(mine)[0] + len(planes) * plane_cells).to(t.device)
+        packed[at] = flat[torch.from_numpy(idx[mine] + base).to(t.device)]
+    if world == 1:
+        values = packed.cpu().numpy()
+    else:
+        packed = packed.to(coll_dev)
+        parts = [torch.empty_like(packed) for _ in range(world)]
+        dist.all_gather(parts, packed)
+        starts = np.array([slab_mod.decompose(gbox, sl.radius, r, world).start for r in range(world)])
+        owner = np.searchsorted(starts, np.concatenate([np.repeat(np.array(planes, dtype=np.int64), plane_cells),
+                                                        idx // plane_cells]), side="right") - 1
+        parts = np.stack([x.cpu().numpy() for x in parts])
+        values = parts[owner, np.arange(owner.size)]
+    if rank == 0:
+        os.makedirs(directory, exist_ok=True)
+        np.save(os.path.join(directory, "field_planes.npy"), values[:len(planes) * plane_cells].reshape([len(planes)] + gshape[1:]))
+        np.save(os.path.join(directory, "field_sample.npy"), values[len(planes) * plane_cells:])
+        print(f"[bench] outputs of the last timed step written to {directory}: planes {planes} and {m} sampled cells "
+              f"({values.nbytes / 2**20:.1f} MiB, {values.dtype})", file=sys.stderr, flush=True)
 
 
 def verify_against_oracle(args, torch, dist, world, rank, sl, bufs, refill, step, body_name, gshape, esize, plane_cells, chunk,

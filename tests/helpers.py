@@ -116,6 +116,19 @@ def load_kats():
     return json.loads((GOLDEN_DIR / "kat_reference_smoke.json").read_text())
 
 
+def old_style_region_text() -> str:
+    """kat_smoke_1d.mlir with @kat_lap's apply region in the old style: the block takes the index only and the body
+    reads the opdef's own argument %x, captured from outside the region.  ApplyOp::verify rejects such a region
+    (block arg count != bounds rank + number of inputs)."""
+    text = (GOLDEN_DIR / "kat_smoke_1d.mlir").read_text()
+    new_style = ("^bb0(%i: index, %a: !t16):\n      %m = neptune_ir.access %a[-1] : !t16 -> f64\n"
+                 "      %z = neptune_ir.access %a[0] : !t16 -> f64\n      %p = neptune_ir.access %a[1] : !t16 -> f64\n      %k2")
+    old_style = ("^bb0(%i: index):\n      %m = neptune_ir.access %x[-1] : !t16 -> f64\n"
+                 "      %z = neptune_ir.access %x[0] : !t16 -> f64\n      %p = neptune_ir.access %x[1] : !t16 -> f64\n      %k2")
+    assert text.count(new_style) == 1
+    return text.replace(new_style, old_style)
+
+
 def prefetch_modules(texts, workers=None):
     """compile (lower + hipcc) a batch of module texts into the current module cache with a pool of host threads, so
     that the tests that follow load them as cache hits: hipcc takes 3-10 s per module on one core and the GPU box has

@@ -10,7 +10,6 @@ import helpers
 from helpers import FIXTURE_DIR, GOLDEN_DIR
 from neptune_hip import lowering
 
-REFERENCE = Path("/root/reference/test")
 NEPTUNE_OPT = helpers.REPO / "neptune-pde-solver_amd" / "bin" / "neptune-opt"
 
 
@@ -108,23 +107,24 @@ def test_known_answer_module_lowers_with_scf_if_and_multiple_inputs():
     assert "a.template idx<0>()" in src
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="reference tree not mounted (GPU box)")
 def test_reference_inputs_lower_or_fail_like_the_reference():
-    for name, lowered in (("smoke_time_advance.mlir", ["ac_lap", "ac_A"]), ("smoke_time_advance_bs.mlir", ["bs_A"]),
-                          ("smoke_time_advance_nonlinear.mlir", ["ac_residual"])):
-        _, report = lowering.to_hip((REFERENCE / "smoke_tests" / name).read_text())
-        # @entry holds neptune_ir.time_advance: solver surface, stays on the host path ...
-        assert report["skipped"][0]["symbol"] == "entry" and "time_advance" in report["skipped"][0]["reason"]
-        # ... but the stencil value it hands to the solver op (smoke_time_advance.mlir:59-70: %ustar) is outlined
-        outlined = [o["symbol"] for o in report["outlined"]]
-        assert report["lowered"] == lowered + outlined
-        if name == "smoke_time_advance.mlir":
-            assert report["outlined"] == [{"symbol": "entry__stencil_0", "function": "entry", "value": "%ustar", "line": 59}]
-    # old-style regions (^bb0(%i0: index) capturing the outer temp) fail ApplyOp::verify in the
+    """the golden restatements of the reference's smoke inputs (tests/golden/README.md): every stand-alone apply body
+    lowers; a function around an implicit time_advance stays on the host path with its stencil value outlined; an
+    old-style region fails verification with the reference verifier's diagnostic"""
+    _, report = lowering.to_hip((GOLDEN_DIR / "kat_smoke_1d.mlir").read_text())
+    assert report["lowered"] == ["kat_lap", "kat_react", "kat_bs", "kat_resid", "kat_axpy"]
+    assert report["skipped"] == [] and report["outlined"] == []
+    _, report = lowering.to_hip((GOLDEN_DIR / "kat_outline_1d.mlir").read_text())
+    # @entry holds neptune_ir.time_advance: solver surface, stays on the host path ...
+    assert report["skipped"][0]["symbol"] == "entry" and "time_advance" in report["skipped"][0]["reason"]
+    # ... but the stencil value it hands to the solver op (%ustar) is outlined
+    outlined = [o["symbol"] for o in report["outlined"]]
+    assert report["lowered"] == ["ol_lap", "ol_A"] + outlined
+    assert report["outlined"] == [{"symbol": "entry__stencil_0", "function": "entry", "value": "%ustar", "line": 47}]
+    # old-style regions (^bb0(%i: index) capturing the outer temp) fail ApplyOp::verify in the
     # reference too (NeptuneIRVerifier.cpp:150-168); same diagnostic text
-    for name in ("smoke.mlir", "smoke_apply.mlir", "smoke_assemble_matrix.mlir"):
-        with pytest.raises(lowering.LoweringError, match=r"block arg count must be \(bounds rank \+ number of inputs\) = 2, but got 1"):
-            lowering.to_hip((REFERENCE / "smoke_tests" / name).read_text())
+    with pytest.raises(lowering.LoweringError, match=r"block arg count must be \(bounds rank \+ number of inputs\) = 2, but got 1"):
+        lowering.to_hip(helpers.old_style_region_text())
 
 
 def test_stencil_part_of_a_function_with_a_solver_op_is_outlined():

@@ -1,15 +1,12 @@
-"""Pin the oracle (test infrastructure): known-answer vectors, the reference's own input files
-(when the reference tree is present), C restatement vs numpy restatement, and its guard rails."""
+"""Pin the oracle (test infrastructure): known-answer vectors, C restatement vs numpy restatement,
+and its guard rails."""
 import ctypes as C
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import helpers
 from helpers import bits_equal, mismatch_report, oracle
-
-REFERENCE = Path("/root/reference/test/smoke_tests")
 
 
 def _vec(hexes):
@@ -48,31 +45,26 @@ def test_known_answers_spelled_out():
     assert F[0] == 0.5 and F[15] == 8.0
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="reference tree not mounted (GPU box)")
-def test_oracle_on_the_reference_input_files_themselves(kat_doc):
-    """same vectors, but parsed from the reference's own smoke inputs: pins the oracle's parser to
-    the reference's textual format (aliases, comments, opdef/func syntax, time_advance skipped)"""
-    by_symbol = {}
-    for k in kat_doc["kats"]:
-        by_symbol.setdefault(k["symbol"], []).append(k)
-    for ksym, (fname, refsym) in kat_doc["reference_symbol_of"].items():
-        m = oracle.Module.parse((REFERENCE / fname).read_text())
-        for k in by_symbol[ksym]:
-            got = m.call(refsym, *[_vec(v) for v in k["inputs"]])
-            assert bits_equal(got, _vec(k["expected"])), f"{fname} @{refsym}: {k['name']}"
-        # the solver/time-stepping ops around them are outside the hot path
-        with pytest.raises(oracle.Unsupported):
-            n = 32 if "bs" in fname else 16
-            m.call("entry", np.zeros(n), np.arange(1, n + 1, dtype=np.float64))
+def test_oracle_evaluates_the_stencils_of_a_module_with_solver_ops(kat_doc):
+    """kat_outline_1d.mlir: opdefs beside an @entry that hands a stencil value to an implicit time_advance, the shape
+    of every current-style reference input.  The opdefs evaluate to the known answers; the solver/time-stepping op
+    is outside the hot path and raises Unsupported instead of being skipped silently."""
+    m = oracle.Module.parse((helpers.GOLDEN_DIR / "kat_outline_1d.mlir").read_text())
+    laps = [k for k in kat_doc["kats"] if k["symbol"] == "kat_lap"]
+    assert laps
+    for k in laps:
+        got = m.call("ol_lap", *[_vec(v) for v in k["inputs"]])
+        assert bits_equal(got, _vec(k["expected"])), k["name"]
+    with pytest.raises(oracle.Unsupported, match="time_advance"):
+        m.call("entry", np.zeros(16), np.arange(1, 17, dtype=np.float64))
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="reference tree not mounted (GPU box)")
 def test_old_style_region_is_rejected_like_the_reference_verifier_does():
-    # smoke_apply.mlir uses ^bb0(%i0: index) capturing the outer temp: fails ApplyOp::verify
-    # (lib/Dialect/NeptuneIR/NeptuneIRVerifier.cpp:150-168)
-    m = oracle.Module.parse((REFERENCE / "smoke_apply.mlir").read_text())
+    # ^bb0(%i: index) capturing the outer temp, as the reference's older smoke inputs write it: fails
+    # ApplyOp::verify (lib/Dialect/NeptuneIR/NeptuneIRVerifier.cpp:150-168)
+    m = oracle.Module.parse(helpers.old_style_region_text())
     with pytest.raises(oracle.OracleError, match="block arg count"):
-        m.call("A", np.arange(1, 5, dtype=np.float64))
+        m.call("kat_lap", np.arange(1, 17, dtype=np.float64))
 
 
 def test_out_of_bounds_access_raises():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Mutation fuzzing of the NeptuneIR front end (parser, verifier, emitter) on the CPU: every fixture, the reference's
-own .mlir inputs when mounted, and random generator modules are truncated / spliced / bit-flipped / number-swapped and
+"""Mutation fuzzing of the NeptuneIR front end (parser, verifier, emitter) on the CPU: every fixture of the
+repository and random generator modules are truncated / spliced / bit-flipped / number-swapped and
 fed to neptune-opt.  A run may accept or reject an input (exit 0 / 1 / 2) but must terminate quickly and cleanly;
 with an AddressSanitizer/UBSan build of neptune-opt (see the recipe printed by --help) it also must not trip a sanitizer.
 usage: tools/fuzz_frontend.py [--opt PATH] [--mutants-per-input N] [--seed S] [--asan-build DIR]"""
@@ -29,7 +29,7 @@ def asan_build(directory: Path) -> Path:
 
 def corpus(generator_seeds=range(7000, 7030)):
     import test_fuzz_gpu as fz
-    files = glob.glob(str(REPO / "tests/**/*.mlir"), recursive=True) + glob.glob("/root/reference/test/**/*.mlir", recursive=True)
+    files = glob.glob(str(REPO / "tests/**/*.mlir"), recursive=True)
     import test_batched_gpu as tb
     import test_ownbox_gpu as ob
     extra = [ob.case_text(n) for n in ob.CASES] + [tb.rank5_text(), tb.stencil4d_text(), tb.stencil5d_text()] + list(tb.step4_texts().values())
