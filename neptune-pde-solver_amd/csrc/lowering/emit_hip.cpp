@@ -51,13 +51,28 @@ std::string ctype(const std::string& elem) {
   if (elem == "i1") return "bool";
   return "void";
 }
+// the unsigned type integer arithmetic of `elem` is done in (MLIR addi / subi / muli wrap; signed C overflow would be
+// undefined), and that unsigned-compares / uitofp read the source's bits through
+std::string utype(const std::string& elem) { return (elem == "index" || elem == "i64") ? "uint64_t" : "uint32_t"; }
+// the value of an integer operand sign-extended to 64 bits: i1 `true` is -1 (a one-bit two's complement integer)
+std::string sext(const std::string& v, const std::string& elem) {
+  return elem == "i1" ? "(-(int64_t)" + v + ")" : "(int64_t)" + v;
+}
 int esize(const std::string& elem) { return elem == "f32" ? 4 : 8; }
 std::string dtype_macro(const std::string& elem) { return elem == "f32" ? "NEPTUNE_HIP_F32" : "NEPTUNE_HIP_F64"; }
 
 std::string float_literal(const std::string& lit, const std::string& elem, bool& ok) {
   ok = true;
-  if (lit.size() > 2 && (lit.compare(0, 2, "0x") == 0 || lit.compare(0, 3, "-0x") == 0)) { ok = false; return ""; }
   char buf[64];
+  if (lit.size() > 2 && (lit.compare(0, 2, "0x") == 0 || lit.compare(0, 3, "-0x") == 0)) {
+    // MLIR prints infinities, NaNs and -0.0 as the bit pattern in hex, one digit per nibble of the type
+    const size_t digits = elem == "f32" ? 8 : 16;
+    if (lit[0] != '0' || lit.size() != 2 + digits ||
+        lit.find_first_not_of("0123456789abcdefABCDEF", 2) != std::string::npos) { ok = false; return ""; }
+    snprintf(buf, sizeof(buf), "__builtin_bit_cast(%s, (%s)0x%sull)", elem == "f32" ? "float" : "double",
+             elem == "f32" ? "uint32_t" : "uint64_t", lit.c_str() + 2);
+    return buf;
+  }
   const double d = std::strtod(lit.c_str(), nullptr);
   if (elem == "f32") {
     const float f = (float)d;  // MLIR parses the literal as a double and rounds it to f32
@@ -170,19 +185,33 @@ struct Emitter {
         if (t.elem == "f64" || t.elem == "f32") {
           bool ok;
           std::string lit = float_literal(op.literal, t.elem, ok);
-          if (!ok) { diag.fail(op.line, "unsupported floating-point constant '" + op.literal + "'"); return false; }
+          if (!ok) {
+            const bool hex = op.literal.find("0x") != std::string::npos;
+            diag.fail(op.line, "unsupported floating-point constant '" + op.literal + "'" +
+                                   (hex ? std::string(" (a hex constant is the bit pattern: 0x and exactly ") +
+                                              (t.elem == "f32" ? "8" : "16") + " hex digits for " + t.elem + ")"
+                                        : std::string()));
+            return false;
+          }
           o << ind << "const " << ctype(t.elem) << " " << res() << " = " << lit << ";  // " << op.literal << "\n";
         } else if (t.elem == "i1") {
           o << ind << "const bool " << res() << " = " << ((op.literal == "true" || op.literal == "1") ? "true" : "false") << ";\n";
         } else {
           o << ind << "const " << ctype(t.elem) << " " << res() << " = (" << ctype(t.elem) << ")" << op.literal << "LL;\n";
         }
-      } else if (n == "arith.addf" || n == "arith.subf" || n == "arith.mulf" || n == "arith.divf" || n == "arith.addi" ||
-                 n == "arith.subi" || n == "arith.muli") {
+      } else if (n == "arith.addf" || n == "arith.subf" || n == "arith.mulf" || n == "arith.divf") {
         const char* sym = (n.find("add") != std::string::npos) ? "+" : (n.find("sub") != std::string::npos) ? "-"
                           : (n.find("mul") != std::string::npos) ? "*" : "/";
         o << ind << "const " << ctype(op.types[0].elem) << " " << res() << " = " << val(op.operands[0]) << " " << sym << " "
           << val(op.operands[1]) << ";\n";
+      } else if (n == "arith.addi" || n == "arith.subi" || n == "arith.muli") {
+        // wrapping integer arithmetic: in the unsigned type of the width, then back (i1: the low bit)
+        const std::string& e = op.types[0].elem;
+        const std::string u = utype(e);
+        const char* sym = n == "arith.addi" ? "+" : n == "arith.subi" ? "-" : "*";
+        const std::string x = "(" + u + ")" + val(op.operands[0]) + " " + sym + " (" + u + ")" + val(op.operands[1]);
+        o << ind << "const " << ctype(e) << " " << res() << " = "
+          << (e == "i1" ? "((" + x + ") & 1u) != 0" : "(" + ctype(e) + ")(" + u + ")(" + x + ")") << ";\n";
       } else if (n == "arith.andi" || n == "arith.ori" || n == "arith.xori") {
         const bool b1 = op.types[0].elem == "i1";
         const char* sym = n == "arith.andi" ? (b1 ? "&&" : "&") : n == "arith.ori" ? (b1 ? "||" : "|") : (b1 ? "!=" : "^");
@@ -218,25 +247,37 @@ struct Emitter {
         else if (p == "une") e = a + " != " + b; else e = "(" + a + " != " + a + " || " + b + " != " + b + ")";
         o << ind << "const bool " << res() << " = " << e << ";\n";
       } else if (n == "arith.cmpi") {
-        const std::string &p = op.predicate;
-        const bool uns = p[0] == 'u';
-        const std::string ct = ctype(op.types[0].elem);
-        const std::string cast = uns ? "(uint64_t)" : "";
+        // unsigned predicates compare the operands' bits (of their own width), signed ones their two's complement
+        // values (i1 true = -1)
+        const std::string &p = op.predicate, &e = op.types[0].elem;
+        const bool uns = p[0] == 'u', sgn = p[0] == 's';
         std::string sym = (p == "eq") ? "==" : (p == "ne") ? "!=" : (p.substr(1) == "lt") ? "<" : (p.substr(1) == "le") ? "<="
                           : (p.substr(1) == "gt") ? ">" : ">=";
-        o << ind << "const bool " << res() << " = " << cast << val(op.operands[0]) << " " << sym << " " << cast
-          << val(op.operands[1]) << ";\n";
-        (void)ct;
+        auto operand = [&](const std::string& v) {
+          return uns ? "(" + utype(e) + ")" + v : (sgn && e == "i1") ? sext(v, e) : v;
+        };
+        o << ind << "const bool " << res() << " = " << operand(val(op.operands[0])) << " " << sym << " "
+          << operand(val(op.operands[1])) << ";\n";
       } else if (n == "arith.select") {
         o << ind << "const " << ctype(op.types[0].elem) << " " << res() << " = " << val(op.operands[0]) << " ? "
           << val(op.operands[1]) << " : " << val(op.operands[2]) << ";\n";
       } else if (n == "arith.index_cast" || n == "arith.sitofp" || n == "arith.fptosi" || n == "arith.extf" ||
                  n == "arith.truncf" || n == "arith.extsi" || n == "arith.trunci") {
-        o << ind << "const " << ctype(op.types[1].elem) << " " << res() << " = (" << ctype(op.types[1].elem) << ")"
-          << val(op.operands[0]) << ";\n";
+        // integer sources are read sign-extended (i1 true = -1); an i1 destination keeps the low bit
+        const std::string &from = op.types[0].elem, &to = op.types[1].elem;
+        const bool int_from = from != "f64" && from != "f32";
+        std::string x = val(op.operands[0]);
+        if (int_from && from == "i1") x = sext(x, from);
+        if (to == "i1")
+          x = "((" + (int_from ? "(uint64_t)" + x : "(int64_t)" + x) + ") & 1u) != 0";
+        else
+          x = "(" + ctype(to) + ")" + x;
+        o << ind << "const " << ctype(to) << " " << res() << " = " << x << ";\n";
       } else if (n == "arith.uitofp") {
-        o << ind << "const " << ctype(op.types[1].elem) << " " << res() << " = (" << ctype(op.types[1].elem) << ")(uint64_t)"
-          << val(op.operands[0]) << ";\n";
+        // the source's bits read as an unsigned integer of the source's width
+        const std::string& from = op.types[0].elem;
+        o << ind << "const " << ctype(op.types[1].elem) << " " << res() << " = (" << ctype(op.types[1].elem) << ")("
+          << (from == "i1" ? std::string("bool") : utype(from)) << ")" << val(op.operands[0]) << ";\n";
       } else if (n == "scf.if") {
         for (size_t r = 0; r < op.results.size(); ++r) o << ind << ctype(op.types[r].elem) << " " << cname(op.results[r]) << ";\n";
         o << ind << "if (" << val(op.operands[0]) << ") {\n";

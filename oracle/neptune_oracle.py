@@ -731,18 +731,88 @@ class PointSet:
         return buf.data[tuple(idx)]
 
 
-_CMPI = {
-    "eq": np.equal, "ne": np.not_equal, "slt": np.less, "sle": np.less_equal, "sgt": np.greater,
-    "sge": np.greater_equal,
-}
-_CMPF = {
-    "oeq": np.equal, "ogt": np.greater, "oge": np.greater_equal, "olt": np.less, "ole": np.less_equal,
-    "one": lambda a, b: np.logical_and(np.not_equal(a, b), ~(np.isnan(a) | np.isnan(b))),
-    "une": np.not_equal,
-}
+# Integers: numpy int64 (index, i64), int32 (i32) and bool (i1) arrays.  Integer arithmetic wraps (MLIR addi / subi /
+# muli carry no overflow flags in these bodies); i1 is a one-bit integer whose signed value of `true` is -1.
+_IWIDTH = {"i1": 1, "i32": 32, "i64": 64, "index": 64}
+
+
+def _signed64(a, ity: str) -> np.ndarray:
+    a = np.asarray(a)
+    if ity == "i1":
+        return np.where(a, np.int64(-1), np.int64(0))
+    return a.astype(np.int64)
+
+
+def _unsigned64(a, ity: str) -> np.ndarray:
+    a = np.asarray(a)
+    if ity == "i32":
+        a = a.astype(np.uint32)          # the source width's bits, not a sign extension
+    return a.astype(np.uint64)
+
+
+def _narrow(v64: np.ndarray, ity: str) -> np.ndarray:
+    """keep the low bits of a 64-bit two's complement value: the result of trunci / extsi / index_cast / wrapping ops"""
+    if ity == "i1":
+        return (np.asarray(v64) & 1).astype(np.bool_)
+    return np.asarray(v64).astype(np_dtype(ity))
+
+
+def _int_binop(n: str, a, b, ity: str) -> np.ndarray:
+    if n in ("arith.andi", "arith.ori", "arith.xori"):
+        return {"arith.andi": np.bitwise_and, "arith.ori": np.bitwise_or, "arith.xori": np.bitwise_xor}[n](
+            np.asarray(a), np.asarray(b))
+    ua, ub = _unsigned64(a, ity), _unsigned64(b, ity)
+    with np.errstate(all="ignore"):
+        r = {"arith.addi": np.add, "arith.subi": np.subtract, "arith.muli": np.multiply}[n](ua, ub)
+    return _narrow(r.astype(np.int64), ity)
+
+
+def _cmpi(pred: str, a, b, ity: str) -> np.ndarray:
+    if pred in ("eq", "ne"):
+        a, b = _unsigned64(a, ity), _unsigned64(b, ity)
+        return np.equal(a, b) if pred == "eq" else np.not_equal(a, b)
+    if pred[0] == "s":
+        a, b = _signed64(a, ity), _signed64(b, ity)
+    elif pred[0] == "u":
+        a, b = _unsigned64(a, ity), _unsigned64(b, ity)
+    else:
+        raise Unsupported(f"cmpi predicate {pred}")
+    rel = {"lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal}.get(pred[1:])
+    if rel is None:
+        raise Unsupported(f"cmpi predicate {pred}")
+    return rel(a, b)
+
+
+_REL = {"eq": np.equal, "gt": np.greater, "ge": np.greater_equal, "lt": np.less, "le": np.less_equal,
+        "ne": np.not_equal}
+
+
+def _cmpf(pred: str, a, b) -> np.ndarray:
+    """the 14 predicates: `o..` is false, `u..` true when either operand is NaN"""
+    uno = np.isnan(a) | np.isnan(b)
+    if pred == "ord":
+        return ~uno
+    if pred == "uno":
+        return uno
+    rel = _REL.get(pred[1:])
+    if rel is None or pred[0] not in "ou":
+        raise Unsupported(f"cmpf predicate {pred}")
+    return (~uno & rel(a, b)) if pred[0] == "o" else (uno | rel(a, b))
+
+
+def _maximumf(a, b):
+    """arith.maximumf (llvm.maximum): NaN if either operand is NaN, -0.0 < +0.0"""
+    a, b = np.asarray(a), np.asarray(b)
+    return np.where(a == b, np.where(np.signbit(a), b, a), np.maximum(a, b))
+
+
+def _minimumf(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return np.where(a == b, np.where(np.signbit(a), a, b), np.minimum(a, b))
+
+
 _BINF = {"arith.addf": np.add, "arith.subf": np.subtract, "arith.mulf": np.multiply, "arith.divf": np.divide}
-_BINI = {"arith.addi": np.add, "arith.subi": np.subtract, "arith.muli": np.multiply,
-         "arith.andi": np.bitwise_and, "arith.ori": np.bitwise_or, "arith.xori": np.bitwise_xor}
+_BINI = ("arith.addi", "arith.subi", "arith.muli", "arith.andi", "arith.ori", "arith.xori")
 
 
 def _const(op: Op):
@@ -752,7 +822,10 @@ def _const(op: Op):
     lit = op.attrs["literal"]
     dt = np_dtype(ty.name)
     if ty.name in ("f64", "f32"):
-        return dt(float(lit)) if not lit.startswith("0x") else dt(np.array(int(lit, 16)).view(dt))
+        if not lit.startswith("0x"):
+            return dt(float(lit))
+        ut = np.uint64 if ty.name == "f64" else np.uint32           # a hex literal is the bit pattern
+        return np.array(int(lit, 16), dtype=ut).view(dt)[()]
     return dt(int(lit, 0))
 
 
@@ -973,10 +1046,12 @@ class Module:
                 env[op.results[0]] = np.negative(self._value(env, op.operands[0], pts))
             elif n in ("arith.maximumf", "arith.minimumf"):
                 a, b = (self._value(env, o, pts) for o in op.operands)
-                env[op.results[0]] = (np.maximum if n == "arith.maximumf" else np.minimum)(a, b)
+                env[op.results[0]] = (_maximumf if n == "arith.maximumf" else _minimumf)(a, b)
             elif n in ("arith.maxnumf", "arith.minnumf"):
-                a, b = (self._value(env, o, pts) for o in op.operands)
-                env[op.results[0]] = (np.fmax if n == "arith.maxnumf" else np.fmin)(a, b)
+                # the non-NaN operand if one is NaN; a (+0, -0) tie may give either zero: b, as the kernels do
+                a, b = (np.asarray(self._value(env, o, pts)) for o in op.operands)
+                pick = np.greater(a, b) if n == "arith.maxnumf" else np.less(a, b)
+                env[op.results[0]] = np.where(np.isnan(a), b, np.where(np.isnan(b) | pick, a, b))
             elif n == "math.sqrt":
                 with np.errstate(all="ignore"):
                     env[op.results[0]] = np.sqrt(self._value(env, op.operands[0], pts))
@@ -993,31 +1068,38 @@ class Module:
                     env[op.results[0]] = _ELEMENTARY[n](*[self._value(env, o, pts) for o in op.operands])
             elif n in _BINI:
                 a, b = (self._value(env, o, pts) for o in op.operands)
-                env[op.results[0]] = _BINI[n](a, b)
+                env[op.results[0]] = _int_binop(n, a, b, op.types[0].name)
             elif n == "arith.cmpi":
                 a, b = (self._value(env, o, pts) for o in op.operands)
-                pred = op.attrs["predicate"]
-                if pred not in _CMPI:
-                    raise Unsupported(f"cmpi predicate {pred}")
-                env[op.results[0]] = _CMPI[pred](a, b)
+                env[op.results[0]] = _cmpi(op.attrs["predicate"], a, b, op.types[0].name)
             elif n == "arith.cmpf":
                 a, b = (self._value(env, o, pts) for o in op.operands)
-                pred = op.attrs["predicate"]
-                if pred not in _CMPF:
-                    raise Unsupported(f"cmpf predicate {pred}")
-                env[op.results[0]] = _CMPF[pred](a, b)
+                env[op.results[0]] = _cmpf(op.attrs["predicate"], a, b)
             elif n == "arith.select":
                 c, a, b = (self._value(env, o, pts) for o in op.operands)
                 env[op.results[0]] = np.where(c, a, b)
-            elif n == "arith.index_cast":
-                dst = op.types[1] if len(op.types) > 1 else op.types[0]
-                env[op.results[0]] = np.asarray(self._value(env, op.operands[0], pts)).astype(np_dtype(dst.name))
-            elif n in ("arith.sitofp", "arith.uitofp"):
-                dst = op.types[1]
-                env[op.results[0]] = np.asarray(self._value(env, op.operands[0], pts)).astype(np_dtype(dst.name))
+            elif n in ("arith.index_cast", "arith.extsi", "arith.trunci"):
+                # sign-extend to 64 bits, keep the destination's low bits
+                src, dst = op.types[0], op.types[1] if len(op.types) > 1 else op.types[0]
+                env[op.results[0]] = _narrow(_signed64(self._value(env, op.operands[0], pts), src.name), dst.name)
+            elif n == "arith.sitofp":
+                src, dst = op.types
+                env[op.results[0]] = _signed64(self._value(env, op.operands[0], pts), src.name).astype(np_dtype(dst.name))
+            elif n == "arith.uitofp":
+                src, dst = op.types                  # the source width's bits read as an unsigned integer
+                env[op.results[0]] = _unsigned64(self._value(env, op.operands[0], pts), src.name).astype(np_dtype(dst.name))
+            elif n == "arith.fptosi":
+                # truncation toward zero; NaN, infinities and out-of-range values are poison (any value will do)
+                src, dst = op.types
+                x = np.asarray(self._value(env, op.operands[0], pts))
+                with np.errstate(all="ignore"):
+                    w = _IWIDTH[dst.name]
+                    ok = np.isfinite(x) & (x >= -(2.0 ** (w - 1))) & (x < 2.0 ** (w - 1))
+                    env[op.results[0]] = _narrow(np.where(ok, x, 0).astype(np.int64), dst.name)
             elif n in ("arith.extf", "arith.truncf"):
                 dst = op.types[1]
-                env[op.results[0]] = np.asarray(self._value(env, op.operands[0], pts)).astype(np_dtype(dst.name))
+                with np.errstate(all="ignore"):         # truncf: overflow to infinity is the defined result
+                    env[op.results[0]] = np.asarray(self._value(env, op.operands[0], pts)).astype(np_dtype(dst.name))
             elif n == "scf.if":
                 env_res = self._eval_if(op, env, pts, elem)
                 for r, v in zip(op.results, env_res):

@@ -233,3 +233,95 @@ def test_random_applies_match_the_oracle(env, monkeypatch, seed):
             got = g_out.cpu().numpy() if device else g_out
             assert bits_equal(got, h_out), f"seed={seed} entry inplace={inplace} device={device} shape={shape} {elem}\n" + \
                 mismatch_report(got, h_out) + "\n" + text
+
+
+# ---- IEEE group: every cmpf predicate, maxnumf / minnumf / negf, index arithmetic with unsigned compares, and input
+# fields salted with the edge values of scalar_spec.FLOAT_TABLE (NaN compared by position).  Seeds of its own: the
+# cases above generate unchanged.
+IEEE_SEEDS = [9001, 9002, 9003, 9004, 9005, 9006]
+
+
+def gen_ieee_module(seed):
+    import scalar_spec
+    rng = np.random.default_rng(seed)
+    rank = int(rng.choice([2, 3]))
+    elem = str(rng.choice(["f64", "f32"]))
+    shape = [int(rng.integers(6, 10)) for _ in range(rank - 1)] + [256]
+    b = ", ".join(map(str, shape))
+    L = [f"%x = neptune_ir.access %in0[{', '.join(['0'] * rank)}] : !t -> {elem}",
+         f"%y = neptune_ir.access %in1[{', '.join(['0'] * (rank - 1) + ['1'])}] : !t -> {elem}",
+         f"%z = neptune_ir.access %in0[{', '.join(['1'] + ['0'] * (rank - 1))}] : !t -> {elem}"]
+    vals, cnt = ["%x", "%y", "%z"], 0
+    binf = ["arith.addf", "arith.subf", "arith.mulf", "arith.maximumf", "arith.minimumf", "arith.maxnumf", "arith.minnumf",
+            "math.copysign"]
+    for _ in range(int(rng.integers(4, 8))):
+        cnt += 1
+        a, c = (vals[int(rng.integers(0, len(vals)))] for _ in range(2))
+        kind = rng.random()
+        if kind < 0.45:
+            L.append(f"%v{cnt} = {rng.choice(binf)} {a}, {c} : {elem}")
+        elif kind < 0.55:
+            L.append(f"%v{cnt} = arith.negf {a} : {elem}")
+        elif kind < 0.85:
+            p = rng.choice(scalar_spec.CMPF_PREDICATES)
+            L.append(f"%p{cnt} = arith.cmpf {p}, {a}, {c} : {elem}")
+            L.append(f"%v{cnt} = arith.select %p{cnt}, {a}, {c} : {elem}")
+        else:                       # index arithmetic with an unsigned compare (negative values compare as huge)
+            d = int(rng.integers(0, rank))
+            k1, k2 = int(rng.integers(-5, 6)), int(rng.integers(0, 6))
+            p = rng.choice(["ult", "ule", "ugt", "uge", "slt", "eq"])
+            L += [f"%w{cnt} = arith.index_cast %i{d} : index to i64", f"%k{cnt} = arith.constant {k1} : i64",
+                  f"%m{cnt} = arith.muli %w{cnt}, %k{cnt} : i64", f"%j{cnt} = arith.constant {k2} : i64",
+                  f"%s{cnt} = arith.subi %m{cnt}, %j{cnt} : i64", f"%p{cnt} = arith.cmpi {p}, %s{cnt}, %j{cnt} : i64",
+                  f"%v{cnt} = arith.select %p{cnt}, {a}, {c} : {elem}"]
+        vals.append(f"%v{cnt}")
+    L.append(f"neptune_ir.yield {vals[-1]} : {elem}")
+    ub = ", ".join(str(n - 1) for n in shape)
+    idx = ", ".join(f"%i{d}: index" for d in range(rank))
+    text = "\n".join(['#l = #neptune_ir.location<"cell">', f"#b = #neptune_ir.bounds<lb = [{', '.join(['0'] * rank)}], ub = [{b}]>",
+                      f"!t = !neptune_ir.temp<element = {elem}, bounds = #b, location = #l>", "module {",
+                      "  neptune_ir.nonlinear_opdef @op : (!t, !t) -> !t {", "  ^bb0(%u0: !t, %u1: !t):",
+                      "    %r = neptune_ir.apply(%u0, %u1) attributes {bounds = #neptune_ir.bounds<lb = "
+                      f"[{', '.join(['0'] * rank)}], ub = [{ub}]>}} : (!t, !t) -> !t {{",
+                      f"      ^bb0({idx}, %in0: !t, %in1: !t):"] + ["        " + l for l in L] +
+                     ["    }", "    neptune_ir.return %r : !t", "  }", "}"]) + "\n"
+    dt = np.float64 if elem == "f64" else np.float32
+    table = np.array(scalar_spec.FLOAT_TABLE[elem], dtype=np.float64).astype(dt)
+    ins = []
+    for k in range(2):
+        u = helpers.hash_field(tuple(shape), dt, seed=seed + 13 * k)
+        salt = rng.random(u.shape) < 0.1
+        u[salt] = table[rng.integers(0, len(table), int(salt.sum()))]
+        ins.append(u)
+    return text, ins
+
+
+def _same_with_nan_by_position(a, b):
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb)) and bits_equal(np.where(na, 0, a).astype(a.dtype), np.where(nb, 0, b).astype(b.dtype))
+
+
+@pytest.fixture(scope="module")
+def env_ieee(built_libs, tmp_path_factory):
+    import torch
+    assert torch.cuda.is_available()
+    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache_fuzz_ieee"))
+    from neptune_hip import lowering
+    helpers.prefetch_modules([gen_ieee_module(seed)[0] for seed in IEEE_SEEDS])
+    return lowering, torch
+
+
+@pytest.mark.parametrize("seed", IEEE_SEEDS)
+def test_random_ieee_bodies_match_the_oracle(env_ieee, monkeypatch, seed):
+    lowering, torch = env_ieee
+    text, ins = gen_ieee_module(seed)
+    want = oracle.Module.parse(text).call("op", *ins)
+    mod = lowering.compile_module(text)
+    d_ins = [torch.from_numpy(a).cuda() for a in ins]
+    for s in [{}, {"NEPTUNE_HIP_KERNEL": "direct"}, {"NEPTUNE_HIP_KERNEL": "direct-flat"}]:
+        for k in ("NEPTUNE_HIP_KERNEL", "NEPTUNE_HIP_VARIANT", "NEPTUNE_HIP_CHUNK"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in s.items():
+            monkeypatch.setenv(k, v)
+        got = mod.call("op", *d_ins).cpu().numpy()
+        assert _same_with_nan_by_position(got, want), f"seed={seed} {s}\n" + mismatch_report(got, want) + "\n" + text
