@@ -139,7 +139,10 @@ __global__ __launch_bounds__(256) void neptune_count_mismatch(const U* __restric
 // per workgroup -> second kernel adds the partials in index order), so the result is bit-for-bit
 // reproducible from run to run and independent of scheduling (no atomics), but differs from the
 // serial sum by rounding: |gpu - serial| <= 2 (n-1) eps sum|x_i| (each order is within (n-1) eps
-// sum|x_i| of the exact sum).  Accumulation is in the element type, like the reference.
+// sum|x_i| of the exact sum).  Every kernel accumulates in the element type, like the reference.  One host path
+// adds more: a bounded reduce beyond rank 3 (run_reduce_sum, lowered_runtime.hpp) adds its per-leading-index box
+// sums in double and rounds to the element type once, which only removes rounding
+// (tests/test_reduce_exact_gpu.py::test_rank4_bounded_f32_reduce_adds_slab_sums_in_double).
 constexpr int kReduceBlocks = 2048;  // partials of the first pass; the workspace holds kReduceBlocks + 1 elements
 
 struct ReduceBoxParams {

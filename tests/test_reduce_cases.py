@@ -1,0 +1,151 @@
+"""The exact-sum generators, references and tree heights of tests/reduce_cases.py keep their promises (no GPU).
+
+Exact data must sum to the same bits in every order -- serial, reversed, numpy's pairwise, a random permutation, and
+for f32 an f64 sum cast down -- and the oracle's serial _reduce must return that exact sum over whole, bounded, empty
+and backwards boxes.  The tree heights must grow with n and give a bound far below the 2 (n - 1) eps of the older
+tests for every shape the GPU tests bound with them."""
+import math
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import reduce_cases as rc
+from helpers import oracle
+
+DTYPES = [np.float64, np.float32]
+
+
+def _exact_cases():
+    for dt in DTYPES:
+        sub = -1074 if dt == np.float64 else -149
+        yield dt, (1,), {}
+        yield dt, (1000,), {}
+        yield dt, (37, 129), {}
+        yield dt, (9, 7, 300), {}
+        yield dt, (5, 3, 4, 7), {}
+        yield dt, (20_000,), {"sparse": 0.01}
+        yield dt, (4096, 3), {"scale_exp": -3}
+        yield dt, (3000,), {"scale_exp": sub}                       # all subnormal
+        yield dt, (2, 3, 4, 5, 6), {"scale_exp": 7}
+    yield np.float64, (100_000,), {"max_abs": 1 << 20}              # needs 37 significant bits
+
+
+def _orders(x):
+    dt = x.dtype.type
+    flat = x.reshape(-1)
+    z = np.zeros(1, dt)
+    perm = np.random.default_rng(5).permutation(flat.size)
+    out = {
+        "serial": np.cumsum(np.concatenate([z, flat]), dtype=dt)[-1],
+        "reversed": np.cumsum(np.concatenate([z, flat[::-1]]), dtype=dt)[-1],
+        "pairwise": flat.sum(dtype=dt),
+        "permuted": np.cumsum(np.concatenate([z, flat[perm]]), dtype=dt)[-1],
+    }
+    if dt == np.float32:
+        out["f64 cast down"] = np.float32(flat.astype(np.float64).sum())
+    return out
+
+
+def _bits(v):
+    v = np.asarray(v)
+    return v.view({8: np.uint64, 4: np.uint32}[v.dtype.itemsize]).item()
+
+
+@pytest.mark.parametrize("dt,shape,kw", list(_exact_cases()))
+def test_exact_data_sums_to_the_same_bits_in_every_order(dt, shape, kw):
+    x = rc.exact_field(shape, dt, seed=hash(shape) & 0xFFFF, **kw)
+    assert x.dtype == dt and x.shape == shape
+    want = rc.exact_sum(x)
+    assert type(want) is dt
+    for name, got in _orders(x).items():
+        assert _bits(got) == _bits(want), (name, got, want)
+    if kw.get("scale_exp", 0) in (-1074, -149):
+        nz = x[x != 0]
+        assert nz.size > 0 and (np.abs(nz) < np.finfo(dt).tiny).all()          # every non-zero cell is subnormal
+    if kw.get("max_abs") == 1 << 20:
+        # the partial sums need more than 24 significant bits: an f32 accumulator rounds
+        assert float(np.cumsum(x.astype(np.float32), dtype=np.float32)[-1]) != float(want)
+
+
+def test_exact_sum_refuses_a_sum_it_cannot_represent():
+    with pytest.raises(AssertionError):
+        rc.exact_sum(np.array([2.0 ** 24, 1.0], np.float32))
+    assert _bits(rc.exact_sum(np.array([2.0 ** 53, 1.0, -1.0]))) == _bits(np.float64(2.0 ** 53))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape,lb,box", [
+    ((1000,), (0,), None),
+    ((37, 129), (3, -2), ((5, 0), (30, 100))),
+    ((9, 7, 300), (0, 0, 0), ((0, 1, 1), (9, 5, 298))),
+    ((2, 3, 9, 11), (0, 0, 0, 0), ((0, 1, 2, 3), (2, 3, 9, 11))),
+    ((8, 8), (0, 0), ((3, 3), (3, 8))),                     # empty
+    ((8, 8), (0, 0), ((5, 5), (2, 2))),                     # backwards along both axes
+    ((8, 8, 4), (0, 0, 0), ((5, 1, 0), (2, 4, 4))),         # backwards along one axis
+])
+def test_oracle_reduce_returns_the_exact_sum(dt, shape, lb, box):
+    elem = "f64" if dt == np.float64 else "f32"
+    ub = tuple(l + n for l, n in zip(lb, shape))
+    x = rc.exact_field(shape, dt, seed=17)
+    text = rc.plain_module(elem, (lb, ub), box)
+    got = oracle.Module.parse(text).call("red", x)
+    abox = None if box is None else (tuple(l - o for l, o in zip(box[0], lb)), tuple(h - o for h, o in zip(box[1], lb)))
+    want = rc.exact_sum(x, abox)
+    assert type(got) is dt and _bits(got) == _bits(want), (got, want)
+    if box is not None and any(h <= l for l, h in zip(*box)):
+        assert _bits(got) == 0
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_oracle_sum_of_negative_zeros_is_positive_zero(dt):
+    elem = "f64" if dt == np.float64 else "f32"
+    x = np.full((6, 10), -0.0, dt)
+    got = oracle.Module.parse(rc.plain_module(elem, ((0, 0), (6, 10)), ((1, 2), (5, 9)))).call("red", x)
+    assert _bits(got) == 0 and _bits(rc.exact_sum(x)) == 0
+
+
+def test_fused_sentinel_masks_keep_exactly_the_cells_used():
+    # 1-D: result [0, 10), apply.bounds [2, 8), reduced box [1, 9); input 1 in [-1, 12) read at 0 and +1
+    res, b, r = ((0,), (10,)), ((2,), (8,)), ((1,), (9,))
+    m0, m1 = rc.fused_sentinel_masks(res, b, r, [res, ((-1,), (12,))], [[(0,), (-1,)], [(0,), (1,)]])
+    assert np.flatnonzero(~m0).tolist() == list(range(1, 9))              # R (copy-through) and [1, 8) for offset -1
+    assert (np.flatnonzero(~m1) - 1).tolist() == list(range(2, 9))       # [2, 8) + {0, 1}, logical coordinates
+    assert rc.plain_sentinel_mask((4, 5), ((1, 1), (3, 4))).sum() == 20 - 6
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("path", ["flat", "box", "fused_scalar", "fused_vec"])
+def test_tree_height_is_monotone_in_n(dt, path):
+    hs = []
+    for n in [1, 2, 3, 255, 256, 257, 1023, 1024, 1025, 4096, 10**5, 524_288, 524_289, 10**6, 2 * 10**6 + 3, 10**8, 3 * 10**9]:
+        ext = (n,) if path in ("flat",) else (max(1, n // 1000), min(n, 1000))
+        if path == "flat" or n < 1000:
+            ext = (n,)
+        hs.append((int(np.prod(ext)), rc.tree_height(path, dt, ext)))
+    hs.sort()
+    assert all(h1 <= h2 for (_, h1), (_, h2) in zip(hs, hs[1:])), hs
+    assert hs[-1][1] < 3 * 10**9 // 2048                         # the tree: a few levels per workgroup of cells
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_gamma_bound_is_far_tighter_than_the_serial_bound_on_every_gpu_shape(dt):
+    cases = [(p, rc.box_ext(s, b)) for p, lst in rc.GAMMA_PLAIN.items() for s, b in lst]
+    cases += [(p, rc.box_ext(s, b)) for p, lst in rc.GAMMA_FUSED.items() for s, b in lst]
+    for path, ext in cases:
+        n = int(np.prod(ext))
+        g = rc.gamma(rc.tree_height(path, dt, ext), dt)
+        assert 0 < g < rc.serial_bound(n, dt) / 8, (path, ext, g, rc.serial_bound(n, dt))
+    assert math.isclose(rc.gamma(1, np.float64), 2.0 ** -53, rel_tol=1e-15)
+
+
+def test_the_mirrored_host_and_kernel_lines_are_unchanged():
+    """fused_path, plain_path, launch_blocks and tree_height restate the host's kernel choice and grid and the kernels'
+    loop structure; the GPU tests rely on them to know which kernel a case runs.  Each restated line must still be
+    there, verbatim, or the mirror in reduce_cases.py is out of date."""
+    csrc = Path(__file__).resolve().parent.parent / "neptune-pde-solver_amd" / "csrc"
+    texts = {}
+    for rel, line in rc.MIRRORED:
+        if rel not in texts:
+            texts[rel] = " ".join((csrc / rel).read_text().split())
+        assert " ".join(line.split()) in texts[rel], (rel, line)
