@@ -18,8 +18,12 @@ transport is CHECKED at start-up (ghost planes poisoned, exchanged, compared), t
 pass are timed for a few steps and the fastest is used; a start-up watchdog ends a run whose
 communicator set-up never returns, naming the stage.
 
-After the timed region the run verifies itself (sampled planes of one more step, bit for bit
-against the CPU oracle) and, on one GPU, times the other single-GPU BASELINE configurations.
+A plain run does only what the headline needs: set-up (lowering + hipcc of the module, plan-time
+tuning, halo transport choice for N > 1, clock ramp), the W warm-up and K timed steps, the
+--dump-outputs arrays, and the JSON line.  --full adds what takes runs of its own after the timed
+region: the self-check (sampled planes of one more step, bit for bit against the CPU oracle), the
+per-step breakdown of a sharded step, the copy ceiling, and, on one GPU, the other single-GPU
+BASELINE configurations and the CPU baseline.  The fields of what did not run are null.
 
 --dump-outputs DIR writes what the last timed step computed (whole planes and a seeded sample of
 cells, at most 64 MiB) as .npy files, so that two builds can be compared output for output.
@@ -52,7 +56,7 @@ WORKLOADS = {
 KIND = {"lap3d7_f64": "3d7", "lap2d5_f64": "2d5", "lap3d27_f32": "3d27"}
 FIXTURE = {"lap3d7_f64": "apply-3d-7pt.mlir", "lap2d5_f64": "apply-2d-5pt.mlir", "lap3d27_f32": "apply-3d-27pt.mlir"}
 ORACLE_FN = {"lap3d7_f64": "lap3d7_f64", "lap2d5_f64": "lap2d5_f64", "lap3d27_f32": "lap3d27_f32"}
-# the other single-GPU configurations of BASELINE.json, timed after the headline on one GPU (config.configs)
+# the other single-GPU configurations of BASELINE.json, timed after the headline on one GPU with --full (config.configs)
 EXTRA_CONFIGS = ["3d7_512", "2d5_8192", "3d27_512"]
 SEED = 2024
 
@@ -96,10 +100,16 @@ def parse_args():
     ap.add_argument("--full-variants", action="store_true",
                     help="build the lowered module with every march tile of the library (NEPTUNE_HIP_FULL_VARIANTS=1: "
                          "a longer hipcc run) so that the plan-time tuning can choose among all of them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the self-check against the oracle (config.verified), the per-step "
+                         "breakdown of a sharded step (config.step_breakdown_ms), the copy ceiling (roofline.copy_ceiling) and, "
+                         "on one GPU, the other single-GPU BASELINE configurations (config.configs) and the CPU baseline "
+                         "(cpu_baseline); a plain run leaves them null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="N=1, default workload: skip the other single-GPU BASELINE configurations (config.configs)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the self-check against the oracle after the timed region")
+                    help="--full, N=1, default workload: skip the other single-GPU BASELINE configurations (config.configs)")
+    ap.add_argument("--no-verify", action="store_true",
+                    help="--full: skip the self-check against the oracle and the copy ceiling after the timed region")
     ap.add_argument("--compile-only", action="store_true",
                     help="lower + hipcc the module(s) this command line needs into the cache and exit without touching the GPU "
                          "(run before profiling: a profiled run must be a pure cache hit)")
@@ -249,7 +259,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    extra = (world == 1 and args.workload == "3d7_1024" and not args.emulate_rank and not args.no_extra_configs
+    extra = (args.full and world == 1 and args.workload == "3d7_1024" and not args.emulate_rank and not args.no_extra_configs
              and args.kernel == "auto" and args.variant < 0 and args.chunk == 0 and args.lowered)
 
     if args.compile_only:
@@ -635,7 +645,7 @@ def main():
 
     # ---- where a sharded step's time goes (untimed-for-the-result extra steps; C-ABI transports only) -----------------
     breakdown = None
-    if (world > 1 or emu is not None) and hasattr(op, "rccl") and op.rccl is not None:
+    if args.full and (world > 1 or emu is not None) and hasattr(op, "rccl") and op.rccl is not None:
         dog.stage("per-step timing breakdown", 300)
         op.timing(True)
         for s in range(20):
@@ -664,7 +674,7 @@ def main():
 
     # ---- the run verifies itself: one more step from the freshly filled field, sampled planes against the oracle -------
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         dog.stage("self-check against the oracle", 600)
         verified = verify_against_oracle(args, torch, dist, world, rank, sl, bufs, refill, step, body_name, gshape, esize,
                                          plane_cells, int(launched.chunk) if have_launch else 0, ranks_agree)
@@ -678,7 +688,7 @@ def main():
     # ---- a plain copy of the same field, same process, same clocks: the measured ceiling the roofline fraction sits under ----
     # ("also report vs the measured-copy ceiling"; outside the timed region, N = 1 only)
     copy_ceiling = None
-    if world == 1 and emu is None and not args.no_verify:
+    if args.full and world == 1 and emu is None and not args.no_verify:
         dog.stage("copy ceiling", 120)
         src_t, dst_t = bufs[0].tensor, bufs[1].tensor
         nbytes2 = 2.0 * src_t.numel() * src_t.element_size()
@@ -777,6 +787,7 @@ def main():
                 "step_breakdown_ms": breakdown,
                 "host_enqueue_us_per_step": t_enqueued * 1e6 / args.steps,
                 "body": "lowered module (NeptuneIR text -> emitter -> hipcc)" if args.lowered else "library built-in (same statements)",
+                "full": args.full,
                 "verified": verified,
                 "watchdog_stages_s": dog.history,
                 "configs": configs,
@@ -797,7 +808,7 @@ def main():
                 "frac_of_copy": (achieved / copy_ceiling["GBps"]) if copy_ceiling else None,
             },
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(body_name, gshape, esize, args.cpu_sample_planes)
         else:
             out["cpu_baseline"] = None

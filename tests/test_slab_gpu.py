@@ -106,19 +106,47 @@ print("NOT_REACHED")
     assert p.returncode != 0 and "slab mode: neptune_ir.apply reads neighbouring planes" in p.stderr
 
 
+BENCH_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline")
+
+
+def _bench_line(args):
+    import json
+    p = subprocess.run([sys.executable, str(HERE.parent / "bench.py")] + args, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in BENCH_KEYS:
+        assert key in d, key
+    assert d["value"] > 0 and d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1.2
+    return d
+
+
 def test_bench_diagnostic_modes(built_libs):
     """bench.py's single-process diagnostics keep working: --emulate-rank (the launches one rank of W would issue, no
-    exchange) and a small workload end to end; both print exactly one JSON line with the contract's keys"""
-    import json
-    bench = str(HERE.parent / "bench.py")
+    exchange) and a small workload end to end, with --full's self-check against the oracle; both print exactly one JSON
+    line with the contract's keys"""
     for extra in (["--emulate-rank", "1/4", "--workload", "3d7_512"], ["--workload", "2d5_1024"]):
-        p = subprocess.run([sys.executable, bench, "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra,
-                           capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-3000:]
-        lines = [l for l in p.stdout.splitlines() if l.strip()]
-        assert len(lines) == 1
-        d = json.loads(lines[0])
-        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                    "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
-            assert key in d, key
-        assert d["value"] > 0 and d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1.2
+        d = _bench_line(["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra)
+        assert d["config"]["full"] is True and d["config"]["verified"]
+
+
+def test_bench_plain_run_is_lean(built_libs, tmp_path):
+    """a plain run times the steps and stops: everything --full adds is null, and the last timed step's outputs are the
+    same bits as a --full run of the same command line writes"""
+    import numpy as np
+    common = ["--workload", "2d5_1024", "--steps", "3", "--warmup", "1"]
+    d = _bench_line(common + ["--dump-outputs", str(tmp_path / "plain")])
+    cfg = d["config"]
+    assert cfg["full"] is False
+    assert cfg["verified"] is None and cfg["configs"] is None and cfg["step_breakdown_ms"] is None
+    assert d["roofline"]["copy_ceiling"] is None and d["cpu_baseline"] is None
+    assert [name for name, _ in cfg["watchdog_stages_s"]] == ["import torch", "lowering + hipcc of the module", "clock ramp",
+                                                            "warm-up and timed steps", "dump of the outputs"]
+    full = _bench_line(common + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert full["config"]["verified"] and full["roofline"]["copy_ceiling"] is not None
+    for name in ("field_planes.npy", "field_sample.npy"):
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == b.dtype == np.float64 and a.shape == b.shape and a.size > 0
+        assert a.tobytes() == b.tobytes(), name
