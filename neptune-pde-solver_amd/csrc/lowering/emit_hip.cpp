@@ -404,28 +404,34 @@ struct Emitter {
     return true;
   }
 
-  // reach of a fused explicit time step: the rhs body's unconditional accesses of the state, and the axpy's read of the centre
-  static std::string fused_reach(const Footprint& cfp, int rank) {
+  // a reach table: {{most negative offset per input and dimension}, {most positive}} (hi < lo: not accessed)
+  template <int D>
+  static std::string reach_table(const int (&lo)[4][D], const int (&hi)[4][D]) {
     std::ostringstream o;
     o << "{";
     for (int side = 0; side < 2; ++side) {
       o << (side ? ", {" : "{");
       for (int k = 0; k < 4; ++k) {
         o << (k ? ", {" : "{");
-        for (int d = 0; d < 3; ++d) {
-          int v = side ? -1 : 1;   // not accessed
-          if (k == 0 && d < rank) {
-            const bool any = cfp.top_hi[0][d] >= cfp.top_lo[0][d];
-            v = side ? std::max(any ? cfp.top_hi[0][d] : 0, 0) : std::min(any ? cfp.top_lo[0][d] : 0, 0);
-          }
-          o << (d ? ", " : "") << v;
-        }
+        for (int d = 0; d < D; ++d) o << (d ? ", " : "") << (side ? hi[k][d] : lo[k][d]);
         o << "}";
       }
       o << "}";
     }
     o << "}";
     return o.str();
+  }
+
+  // reach of a fused explicit time step: the rhs body's unconditional accesses of the state, and the axpy's read of the centre
+  static std::string fused_reach(const Footprint& cfp, int rank) {
+    int lo[4][3], hi[4][3];
+    for (int k = 0; k < 4; ++k)
+      for (int d = 0; d < 3; ++d) {
+        const bool state = k == 0 && d < rank;
+        lo[k][d] = state ? std::min(cfp.top_lo[0][d], 0) : 1;   // an unread dimension (1, -1) widens to (0, 0)
+        hi[k][d] = state ? std::max(cfp.top_hi[0][d], 0) : -1;
+      }
+    return reach_table(lo, hi);
   }
 
   // reach of an apply along dim 0 (the slab axis), over all of its accesses
@@ -442,10 +448,6 @@ struct Emitter {
     const Type& res = apply.types[nin];
     std::map<std::string, int> temp_index, index_arg;
     if (!analyze_apply(apply, fp, temp_index, index_arg)) return false;
-    const int* R = fp.R;
-    const int halo_inputs = fp.halo_inputs;
-    const unsigned halo_mask = fp.halo_mask;
-
     std::ostringstream& o = bodies;
     o << "// " << tag << ": region of the neptune_ir.apply at line " << apply.line << "\n";
     o << "struct Body_" << tag << " {\n";
@@ -458,46 +460,20 @@ struct Emitter {
     if (!body_ok) return false;
     fp.exact = !saw_elementary;
     o << "  }\n};\n";
-    o << "using FP_" << tag << " = neptune_hip::Footprint<" << fp.halo_input << ", " << R[0] << ", " << R[1] << ", " << R[2] << ", "
+    o << "using FP_" << tag << " = neptune_hip::Footprint<" << fp.halo_input << ", " << fp.R[0] << ", " << fp.R[1] << ", " << fp.R[2] << ", "
       << ((fp.box && fp.march_ok) ? "true" : "false") << ", " << (fp.march_ok ? "true" : "false");
-    if (halo_inputs > 1 && fp.march_ok) o << ", 0x" << std::hex << halo_mask << std::dec << "u";
+    if (fp.halo_inputs > 1 && fp.march_ok) o << ", 0x" << std::hex << fp.halo_mask << std::dec << "u";
     o << ">;\n";
-    // what the unconditional accesses reach, per input and dimension: {most negative offsets}, {most positive} (hi < lo: none)
-    o << "static const neptune_hip::Reach kTopRadius_" << tag << " = {";
-    for (int side = 0; side < 2; ++side) {
-      o << (side ? ", {" : "{");
-      for (int k = 0; k < 4; ++k) {
-        o << (k ? ", {" : "{");
-        for (int d = 0; d < 3; ++d)
-          o << (d ? ", " : "") << (k < nin && d < fp.rank ? (side ? fp.top_hi[k][d] : fp.top_lo[k][d]) : (side ? -1 : 1));
-        o << "}";
-      }
-      o << "}";
-    }
-    o << "};\n";
-    if (fp.nd) {
-      o << "static const neptune_hip::ReachN kNdReach_" << tag << " = {";
-      for (int side = 0; side < 2; ++side) {
-        o << (side ? ", {" : "{");
-        for (int k = 0; k < 4; ++k) {
-          o << (k ? ", {" : "{");
-          for (int d = 0; d < 6; ++d)
-            o << (d ? ", " : "") << (k < nin && d < rank ? (side ? fp.nd_hi[k][d] : fp.nd_lo[k][d]) : (side ? -1 : 1));
-          o << "}";
-        }
-        o << "}";
-      }
-      o << "};\n";
-    }
+    // what the unconditional accesses reach, per input and dimension (analyze_apply leaves hi < lo where nothing is read)
+    o << "static const neptune_hip::Reach kTopRadius_" << tag << " = " << reach_table(fp.top_lo, fp.top_hi) << ";\n";
+    if (fp.nd) o << "static const neptune_hip::ReachN kNdReach_" << tag << " = " << reach_table(fp.nd_lo, fp.nd_hi) << ";\n";
     o << "\n";
     return true;
   }
 
   // ---- functions -----------------------------------------------------------------------
   struct ValueInfo {
-    Type type;
     int root_arg = -1;  // >= 0: aliases function argument #root_arg
-    int def_index = -1;
     int uses = 0;
   };
 
@@ -532,440 +508,376 @@ struct Emitter {
     int rank = 0, nin = 0, halo0 = 0;
   };
 
-  bool emit_function(const Function& f) {
+  // what the emitters of one function's ops share
+  struct FnState {
+    const Function& f;
+    std::ostringstream o;
     std::map<std::string, ValueInfo> vals;
     std::map<std::string, FusedReduce> fused_reduce;  // apply result -> how the consuming reduce evaluates it
     std::map<std::string, int> scalar_kind;           // function-level scalars: 0 uniform, 1 bare reduce result, 2 derived from one
     int returned_scalar_kind = -1;
-    const int nargs = (int)f.arg_types.size();
-    for (int i = 0; i < nargs; ++i) {
-      ValueInfo vi;
-      vi.type = f.arg_types[i];
-      vi.root_arg = i;
-      vals[f.body.args[i].name] = vi;
-    }
-    // use counts + definitions
-    for (size_t oi = 0; oi < f.body.ops.size(); ++oi)
-      for (auto& v : f.body.ops[oi]->operands) vals[v].uses++;
-    // which producer may write straight into which destination
     std::map<int, std::string> dest_of;  // producer op index -> C expression of the destination Val*
     int returned_producer = -1;
     std::map<std::string, int> def_at;
-    for (size_t oi = 0; oi < f.body.ops.size(); ++oi)
-      for (auto& r : f.body.ops[oi]->results) def_at[r] = (int)oi;
-    for (size_t oi = 0; oi < f.body.ops.size(); ++oi) {
-      const Op& op = *f.body.ops[oi];
-      auto producer_of = [&](const std::string& v) -> int {
-        auto it = def_at.find(v);
-        if (it == def_at.end()) return -1;
-        const Op& p = *f.body.ops[it->second];
-        if (p.name == "neptune_ir.apply" || !p.callee.empty()) return it->second;
-        return -1;
-      };
+    int apply_counter = 0;
+    explicit FnState(const Function& fn) : f(fn) {}
+    std::string dest_for(int oi) const {
+      auto it = dest_of.find(oi);
+      if (it != dest_of.end()) return it->second;
+      return oi == returned_producer ? "dest" : "nullptr";
+    }
+  };
+
+  // only aliases and constants lie between producer p and op oi: nothing there can observe the field p would write
+  static bool nothing_observes_between(const Function& f, int p, int oi) {
+    for (int j = p + 1; j < oi; ++j) {
+      const std::string& nm = f.body.ops[j]->name;
+      if (!is_alias_op(nm) && nm != "arith.constant") return false;
+    }
+    return true;
+  }
+
+  bool emit_function(const Function& f) {
+    FnState s(f);
+    const auto& ops = f.body.ops;
+    const int nargs = (int)f.arg_types.size();
+    for (int i = 0; i < nargs; ++i) s.vals[f.body.args[i].name].root_arg = i;
+    for (size_t oi = 0; oi < ops.size(); ++oi) {
+      for (auto& v : ops[oi]->operands) s.vals[v].uses++;
+      for (auto& r : ops[oi]->results) s.def_at[r] = (int)oi;
+    }
+    // which producer may write straight into which destination
+    auto producer_of = [&](const std::string& v) -> int {
+      auto it = s.def_at.find(v);
+      if (it == s.def_at.end()) return -1;
+      const Op& p = *ops[it->second];
+      return (p.name == "neptune_ir.apply" || !p.callee.empty()) ? it->second : -1;
+    };
+    for (size_t oi = 0; oi < ops.size(); ++oi) {
+      const Op& op = *ops[oi];
       if (op.name == "neptune_ir.store" && !op.attrs.count("bounds")) {
         const int p = producer_of(op.operands[0]);
         const std::string& field = op.operands[1];
-        const bool field_before = !def_at.count(field) || def_at[field] < p;  // function args precede everything
-        if (p >= 0 && vals[op.operands[0]].uses == 1 && field_before) {
-          bool clean = true;  // nothing between producer and store may observe the field
-          for (int j = p + 1; j < (int)oi; ++j) {
-            const std::string& nm = f.body.ops[j]->name;
-            if (!(nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" || nm == "neptune_ir.as_tensor" ||
-                  nm == "neptune_ir.from_tensor" || nm == "arith.constant")) clean = false;
-          }
-          if (clean) dest_of[p] = "&" + cname(field);
-        }
+        const bool field_before = !s.def_at.count(field) || s.def_at[field] < p;  // function args precede everything
+        if (p >= 0 && s.vals[op.operands[0]].uses == 1 && field_before && nothing_observes_between(f, p, (int)oi))
+          s.dest_of[p] = "&" + cname(field);
       }
-      if ((op.name == "neptune_ir.return" || op.name == "func.return" || op.name == "return") && op.operands.size() == 1) {
-        // the caller's destination may only be handed down to a producer that is the LAST thing the function
-        // computes: an op between it and the return could still read an argument that aliases that destination
-        // (the reference gives every apply a private result, DataflowLowering.cpp:281)
+      // the caller's destination may only be handed down to a producer that is the LAST thing the function
+      // computes: an op between it and the return could still read an argument that aliases that destination
+      // (the reference gives every apply a private result, DataflowLowering.cpp:281)
+      if (is_return_op(op.name) && op.operands.size() == 1) {
         const int p = producer_of(op.operands[0]);
-        bool clean = p >= 0 && vals[op.operands[0]].uses == 1;
-        for (int j = p + 1; clean && j < (int)oi; ++j) {
-          const std::string& nm = f.body.ops[j]->name;
-          if (!(nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" || nm == "neptune_ir.as_tensor" ||
-                  nm == "neptune_ir.from_tensor" || nm == "arith.constant")) clean = false;
-        }
-        if (clean) returned_producer = p;
+        if (p >= 0 && s.vals[op.operands[0]].uses == 1 && nothing_observes_between(f, p, (int)oi)) s.returned_producer = p;
       }
     }
 
-    std::ostringstream o;
-    const std::string impl = f.name + "__impl";
+    std::ostringstream& o = s.o;
     o << "// ---- @" << f.name << " (line " << f.line << ") ----\n";
-    o << "static nl::Val " << impl << "(nl::Scope& sc";
+    o << "static nl::Val " << f.name << "__impl(nl::Scope& sc";
     for (int i = 0; i < nargs; ++i) o << ", const nl::Val& " << cname(f.body.args[i].name);
     o << ", const nl::Val* dest, int* ret_arg, double* sret) {\n";
     o << "  (void)dest; (void)sret; if (ret_arg) *ret_arg = -1;\n";
-    if (returned_producer >= 0 && nargs > 0) {
+    if (s.returned_producer >= 0 && nargs > 0) {
       // ... and never when it overlaps one of this function's own arguments (checked on the actual pointers): the
       // producer would overwrite data the function was given to read
       o << "  if (dest && (";
       for (int i = 0; i < nargs; ++i) o << (i ? " || " : "") << "nl::overlaps(*dest, " << cname(f.body.args[i].name) << ")";
       o << ")) dest = nullptr;\n";
     }
-    int apply_counter = 0;
-    for (size_t oi = 0; oi < f.body.ops.size(); ++oi) {
-      const Op& op = *f.body.ops[oi];
+    for (size_t oi = 0; oi < ops.size(); ++oi) {
+      const Op& op = *ops[oi];
       const std::string& n = op.name;
-      if (n == "neptune_ir.wrap" || n == "neptune_ir.unwrap" || n == "neptune_ir.load" || n == "neptune_ir.as_tensor" ||
-          n == "neptune_ir.from_tensor") {
-        ValueInfo vi;
-        vi.type = op.types[1];
-        vi.root_arg = vals[op.operands[0]].root_arg;
-        vi.uses = vals[op.results[0]].uses;
-        vals[op.results[0]] = vi;
-        Bounds b;
-        if (op.types[1].is_tempish()) b = op.types[1].bounds;
-        o << "  // " << n << " " << op.operands[0] << "\n";
-        if (op.types[1].is_tempish()) {
-          o << "  const nl::Val " << cname(op.results[0]) << " = sc.alias(" << cname(op.operands[0]) << ", " << new_box(b)
-            << ", \"" << n << "\");\n";
-        } else {  // unwrap -> memref: same buffer, zero-based box
-          Bounds zb = op.types[0].bounds;
-          for (int d = 0; d < zb.rank(); ++d) { zb.ub[d] -= zb.lb[d]; zb.lb[d] = 0; }
-          o << "  const nl::Val " << cname(op.results[0]) << " = sc.alias(" << cname(op.operands[0]) << ", " << new_box(zb)
-            << ", \"" << n << "\");\n";
-        }
-      } else if (n == "neptune_ir.apply") {
-        const std::string tag = f.name + "_" + std::to_string(apply_counter++);
-        Footprint fp;
-        if (!emit_body(op, tag, fp)) return false;
-        const int nin = (int)op.operands.size();
-        const Type& res = op.types[nin];
-        ValueInfo vi;
-        vi.type = res;
-        vi.uses = vals[op.results[0]].uses;
-        vals[op.results[0]] = vi;
-        // single-use result consumed by a reduce a few scalar/alias ops later: the apply is evaluated
-        // inside the reduction kernel (run_apply_reduce_sum), the temp never exists
-        {
-          int consumer = -1;
-          if (vi.uses == 1 && fp.lead == 0)
-            for (size_t j = oi + 1; j < f.body.ops.size(); ++j) {
-              const Op& c = *f.body.ops[j];
-              if (c.name == "neptune_ir.reduce" && c.operands.at(0) == op.results[0]) { consumer = (int)j; break; }
-              const std::string& nm = c.name;
-              const bool harmless = nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" ||
-                                    ((nm.compare(0, 6, "arith.") == 0 || nm.compare(0, 5, "math.") == 0) && c.regions.empty());
-              if (!harmless) break;
-            }
-          if (consumer >= 0) {
-            FusedReduce fr;
-            fr.tag = tag;
-            fr.elem = ctype(res.elem);
-            fr.rank = res.bounds.rank();
-            fr.nin = nin;
-            fr.result_box = new_box(res.bounds);
-            fr.bounds_box = new_box(op.attrs.at("bounds").bounds);
-            fr.halo0 = halo0_of(fp);
-            o << "  // neptune_ir.apply -> " << op.results[0] << "   (evaluated inside the reduce below)\n";
-            o << "  const nl::Val* in_" << tag << "[] = {";
-            for (int k = 0; k < nin; ++k) o << (k ? ", " : "") << "&" << cname(op.operands[k]);
-            o << "};\n";
-            fused_reduce[op.results[0]] = fr;
-            ApplyInfo ai;
-            ai.function = f.name;
-            ai.tag = tag;
-            ai.rank = fp.rank;
-            ai.num_inputs = fp.nin;
-            ai.march = false;
-            ai.box = fp.box;
-            ai.halo_input = fp.halo_inputs > 0 ? std::max(fp.halo_input, 0) : -1;  // report: star/box also when the direct kernel runs it
-            ai.fused_reduce = true;
-            ai.exact = fp.exact;
-            info.applies.push_back(ai);
-            continue;
-          }
-        }
-        std::string dest = "nullptr";
-        if (dest_of.count((int)oi)) dest = dest_of[(int)oi];
-        else if ((int)oi == returned_producer) dest = "dest";
-        o << "  // neptune_ir.apply -> " << op.results[0] << "   (kernel + fused copy-through)\n";
-        o << "  const nl::Val* in_" << tag << "[] = {";
-        for (int k = 0; k < nin; ++k) o << (k ? ", " : "") << "&" << cname(op.operands[k]);
-        o << "};\n";
-        if (fp.nd) {
-          // rank 4..6 with offsets along a leading dimension: the rank-generic kernel (lowered_runtime.hpp run_apply_nd)
-          o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply_nd<Body_" << tag << ", " << ctype(res.elem) << ", "
-            << res.bounds.rank() << ", " << nin << ">(sc, Body_" << tag << "{}, " << new_box(res.bounds) << ", "
-            << new_box(op.attrs.at("bounds").bounds) << ", in_" << tag << ", kNdReach_" << tag << ", " << dest << ", " << fp.nd_halo0 << ");\n";
-          ApplyInfo ai;
-          ai.function = f.name;
-          ai.tag = tag;
-          ai.rank = res.bounds.rank();
-          ai.num_inputs = fp.nin;
-          ai.march = false;
-          ai.box = true;
-          ai.halo_input = 0;
-          ai.elem = res.elem;
-          ai.halo0 = fp.nd_halo0;
-          ai.geom_symbol = "";     // no geometry-level entry: neptune_hip_apply_geom_t is rank 1..3
-          ai.exact = fp.exact;
-          info.applies.push_back(ai);
-          continue;
-        }
-        if (fp.lead > 0) {
-          // rank 4..6: one rank-3 apply per index of the leading dimensions (lowered_runtime.hpp run_apply_batched)
-          o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply_batched<Body_" << tag << ", " << ctype(res.elem) << ", "
-            << res.bounds.rank() << ", " << nin << ", FP_" << tag << ">(sc, Body_" << tag << "{}, " << new_box(res.bounds) << ", "
-            << new_box(op.attrs.at("bounds").bounds) << ", in_" << tag << ", kTopRadius_" << tag << ", " << dest << ");\n";
-          ApplyInfo ai;
-          ai.function = f.name;
-          ai.tag = tag;
-          ai.rank = res.bounds.rank();
-          ai.num_inputs = fp.nin;
-          ai.march = fp.march_ok;
-          ai.box = fp.box;
-          ai.halo_input = fp.halo_inputs > 0 ? std::max(fp.halo_input, 0) : -1;
-          ai.elem = res.elem;
-          ai.halo0 = 0;
-          ai.geom_symbol = "";     // no geometry-level entry: neptune_hip_apply_geom_t is rank 1..3
-          ai.exact = fp.exact;
-          info.applies.push_back(ai);
-          continue;
-        }
-        o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply<Body_" << tag << ", " << ctype(res.elem) << ", "
-          << res.bounds.rank() << ", " << nin << ", FP_" << tag << ">(sc, Body_" << tag << "{}, " << new_box(res.bounds) << ", "
-          << new_box(op.attrs.at("bounds").bounds) << ", in_" << tag << ", kTopRadius_" << tag << ", " << dest << ", "
-          << halo0_of(fp) << ");\n";
-        ApplyInfo ai;
-        ai.function = f.name;
-        ai.tag = tag;
-        ai.rank = fp.rank;
-        ai.num_inputs = fp.nin;
-        ai.march = fp.march_ok;
-        ai.box = fp.box;
-        ai.halo_input = fp.halo_inputs > 0 ? std::max(fp.halo_input, 0) : -1;  // report: star/box also when the direct kernel runs it
-        ai.elem = res.elem;
-        ai.halo0 = halo0_of(fp);
-        ai.geom_symbol = tag + "__geom";
-        ai.exact = fp.exact;
-        // Geometry-level entry of this apply's body: what neptune_hip_apply_builtin is for the library's own
-        // bodies (caller-supplied boxes, bounds, region, stream and launch configuration; no allocation,
-        // no synchronisation).  The slab decomposition drives user stencils through it.
-        geom_entries << "extern \"C\" int " << ai.geom_symbol
-                     << "(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* stream,\n"
-                     << "    const neptune_hip_launch_cfg_t* cfg) {\n"
-                     << "  if (!g || !in || !out) return NEPTUNE_HIP_EINVAL;\n"
-                     << "  const int rc = neptune_hip::geom_check_radius(g, kTopRadius_" << tag << ");\n"
-                     << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
-                     << "  return neptune_hip::launch_apply<Body_" << tag << ", " << ctype(res.elem) << ", " << res.bounds.rank() << ", " << nin
-                     << ", FP_" << tag << ">(Body_" << tag << "{}, g, in, out, (hipStream_t)stream, cfg);\n}\n"
-                     << "// two chained applies of this body in one pass over HBM (csrc/kernels/apply_march2.hpp): out = A(A(in)), or\n"
-                     << "// NEPTUNE_HIP_EUNSUPPORTED when the footprint / geometry does not qualify (neptune_hip_step_loop_pairs)\n"
-                     << "extern \"C\" int " << ai.geom_symbol << "2"
-                     << "(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* stream,\n"
-                     << "    const neptune_hip_launch_cfg_t* cfg) {\n"
-                     << "  if (!g || !in || !out) return NEPTUNE_HIP_EINVAL;\n"
-                     << "  const int rc = neptune_hip::geom_check_radius(g, kTopRadius_" << tag << ");\n"
-                     << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
-                     << "  return neptune_hip::launch_apply_twice<Body_" << tag << ", " << ctype(res.elem) << ", " << res.bounds.rank() << ", " << nin
-                     << ", FP_" << tag << ">(Body_" << tag << "{}, g, in, out, (hipStream_t)stream, cfg);\n}\n"
-                     << "extern \"C\" int " << ai.geom_symbol << "3"
-                     << "(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* stream,\n"
-                     << "    const neptune_hip_launch_cfg_t* cfg) {\n"
-                     << "  if (!g || !in || !out) return NEPTUNE_HIP_EINVAL;\n"
-                     << "  const int rc = neptune_hip::geom_check_radius(g, kTopRadius_" << tag << ");\n"
-                     << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
-                     << "  return neptune_hip::launch_apply_thrice<Body_" << tag << ", " << ctype(res.elem) << ", " << res.bounds.rank() << ", " << nin
-                     << ", FP_" << tag << ">(Body_" << tag << "{}, g, in, out, (hipStream_t)stream, cfg);\n}\n"
-                     << "// march tiles this module holds for that entry (plan-time tuning: neptune_hip_autotune_fn)\n"
-                     << "extern \"C\" int " << ai.geom_symbol << "_variants(int rank) { return neptune_hip::march_variant_count(rank); }\n\n";
-        info.applies.push_back(ai);
-      } else if (n == "neptune_ir.time_advance") {
-        // explicit Euler step: k = rhs(state); result = state + dt * k, over the whole box.  The
-        // reference's own explicit lowering (HighLevelConvertion.cpp:77-120) builds exactly this
-        // apply_{linear,nonlinear} + axpy apply pair (its version is 1-D-only and ill-formed).
-        const Type& st = op.types[0];
-        ValueInfo vi;
-        vi.type = st;
-        vi.uses = vals[op.results[0]].uses;
-        vals[op.results[0]] = vi;
-        std::string dest = "nullptr";
-        if (dest_of.count((int)oi)) dest = dest_of[(int)oi];
-        else if ((int)oi == returned_producer) dest = "dest";
-        const std::string tag = f.name + "_ta" + std::to_string(apply_counter++);
-        const std::string bx = new_box(st.bounds);
-        const std::string T = ctype(st.elem);
-        // Fusable: the rhs opdef is exactly "apply(state) ; return" with result box == state box.  Then
-        // one kernel computes state + dt * rhs(state) (ops::EulerFused); anything else takes the
-        // two-kernel form below.  Both produce the same bits.
-        const Function* c = m.find(op.callee);
-        const Op* rhs_apply = nullptr;
-        if (st.rank() <= 3 && c && c->arg_types.size() == 1 && c->body.ops.size() == 2 && c->body.ops[0]->name == "neptune_ir.apply" &&
-            c->body.ops[1]->name == "neptune_ir.return" && c->body.ops[1]->operands.size() == 1 &&
-            c->body.ops[1]->operands[0] == c->body.ops[0]->results.at(0) && c->body.ops[0]->operands.size() == 1 &&
-            c->body.ops[0]->operands[0] == c->body.args[0].name) {
-          const Op& a = *c->body.ops[0];
-          const Type& rt = a.types[1];
-          bool same = a.types[0].is_tempish() && rt.elem == st.elem && rt.bounds.rank() == st.rank() && a.types[0].elem == st.elem;
-          for (int d = 0; same && d < st.rank(); ++d)
-            same = rt.bounds.lb[d] == st.bounds.lb[d] && rt.bounds.ub[d] == st.bounds.ub[d] &&
-                   a.types[0].bounds.lb[d] == st.bounds.lb[d] && a.types[0].bounds.ub[d] == st.bounds.ub[d];
-          if (same) rhs_apply = &a;
-        }
-        if (rhs_apply) {
-          Footprint cfp;
-          std::map<std::string, int> ti, ia;
-          if (!analyze_apply(*rhs_apply, cfp, ti, ia)) return false;
-          const std::string ctag = op.callee + "_0";  // the tag emit_function gives the opdef's only apply
-          o << "  // neptune_ir.time_advance {method = 0 (explicit), rhs = @" << op.callee
-            << "}: state + dt * rhs(state), rhs apply and axpy fused into one kernel\n";
-          o << "  static const neptune_hip::Reach kTopRadius_" << tag << " = " << fused_reach(cfp, st.rank()) << ";\n";
-          o << "  const nl::Val* in_" << tag << "[] = {&" << cname(op.operands[0]) << "};\n";
-          const std::string body = "neptune_hip::ops::EulerFused<Body_" + ctag + ", " + T + ", " + std::to_string(st.rank()) + ">";
-          o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply<" << body << ", " << T << ", " << st.rank() << ", 1, FP_"
-            << ctag << ">(sc, " << body << "{(" << T << ")" << cname(op.operands[1]) << "}, " << bx << ", "
-            << new_box(rhs_apply->attrs.at("bounds").bounds) << ", in_" << tag << ", kTopRadius_" << tag << ", " << dest << ", "
-            << halo0_of(cfp) << ");\n";
-          ApplyInfo ai;
-          ai.function = f.name;
-          ai.tag = tag;
-          ai.rank = st.rank();
-          ai.num_inputs = 1;
-          ai.march = cfp.march_ok;
-          ai.box = cfp.box;
-          ai.halo_input = cfp.halo_inputs > 0 ? std::max(cfp.halo_input, 0) : -1;
-          ai.elem = st.elem;
-          ai.halo0 = halo0_of(cfp);
-          ai.exact = cfp.exact;
-          // With a constant time step the fused step is a self-contained apply: give it geometry-level entries too
-          // (single step, two steps per pass, tile count), so step loops and slab decompositions can drive `u + dt*rhs(u)`
-          // exactly like a plain operator.
-          {
-            auto dit = def_at.find(op.operands[1]);
-            const Op* dtdef = dit == def_at.end() ? nullptr : f.body.ops[dit->second].get();
-            bool lit_ok = false;
-            std::string lit;
-            if (dtdef && dtdef->name == "arith.constant") lit = float_literal(dtdef->literal, st.elem, lit_ok);
-            if (lit_ok) {
-              ai.geom_symbol = tag + "__geom";
-              std::ostringstream& ge = geom_entries;
-              ge << "static const neptune_hip::Reach kTopRadiusG_" << tag << " = " << fused_reach(cfp, st.rank()) << ";\n";
-              const char* names[3] = {"", "2", "3"};
-              const char* fns[3] = {"launch_apply", "launch_apply_twice", "launch_apply_thrice"};
-              for (int v = 0; v < 3; ++v)
-                ge << "extern \"C\" int " << ai.geom_symbol << names[v]
+      bool ok = true;
+      if (is_alias_op(n)) emit_alias(s, op);
+      else if (n == "neptune_ir.apply") ok = emit_apply(s, op, (int)oi);
+      else if (n == "neptune_ir.time_advance") ok = emit_time_advance(s, op, (int)oi);
+      else if (!op.callee.empty()) emit_call(s, op, (int)oi);
+      else if (n == "neptune_ir.store") emit_store(s, op);
+      else if (n == "neptune_ir.reduce") emit_reduce(s, op);
+      else if (is_scalar_op(op)) ok = emit_scalar(s, op);
+      else if (is_return_op(n)) emit_return(s, op);
+      if (!ok) return false;
+    }
+    o << "}\n";
+    emit_abi(s);
+    return true;
+  }
+
+  // the report entry of an apply; halo_input is star / box also when the direct kernel runs it
+  ApplyInfo apply_info(const FnState& s, const std::string& tag, const Footprint& fp, int rank, const std::string& elem, int halo0) {
+    ApplyInfo ai;
+    ai.function = s.f.name;
+    ai.tag = tag;
+    ai.rank = rank;
+    ai.num_inputs = fp.nin;
+    ai.march = fp.march_ok;
+    ai.box = fp.box;
+    ai.halo_input = fp.halo_inputs > 0 ? std::max(fp.halo_input, 0) : -1;
+    ai.elem = elem;
+    ai.halo0 = halo0;
+    ai.exact = fp.exact;
+    return ai;
+  }
+
+  // const nl::Val* in_<tag>[] = {...}: the inputs of one run_apply*, as C expressions of nl::Val
+  static void emit_inputs(std::ostream& o, const std::string& tag, const std::vector<std::string>& ins) {
+    o << "  const nl::Val* in_" << tag << "[] = {";
+    for (size_t k = 0; k < ins.size(); ++k) o << (k ? ", " : "") << "&" << ins[k];
+    o << "};\n";
+  }
+
+  // Geometry-level entries of an apply body: what neptune_hip_apply_builtin is for the library's own bodies
+  // (caller-supplied boxes, bounds, region, stream and launch configuration; no allocation, no synchronisation).
+  // The slab decomposition drives user stencils through them.
+  void emit_geom_entries(const std::string& sym, const std::string& reach, const std::string& body, const std::string& init,
+                         const std::string& T, int rank, int nin, const std::string& fp) {
+    static const char* const suffix[3] = {"", "2", "3"};
+    static const char* const launch[3] = {"launch_apply", "launch_apply_twice", "launch_apply_thrice"};
+    for (int v = 0; v < 3; ++v) {
+      if (v == 1)
+        geom_entries << "// two chained applies of this body in one pass over HBM (csrc/kernels/apply_march2.hpp): out = A(A(in)), or\n"
+                     << "// NEPTUNE_HIP_EUNSUPPORTED when the footprint / geometry does not qualify (neptune_hip_step_loop_pairs)\n";
+      geom_entries << "extern \"C\" int " << sym << suffix[v]
                    << "(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* stream,\n"
                    << "    const neptune_hip_launch_cfg_t* cfg) {\n"
                    << "  if (!g || !in || !out) return NEPTUNE_HIP_EINVAL;\n"
-                   << "  const int rc = neptune_hip::geom_check_radius(g, kTopRadiusG_" << tag << ");\n"
+                   << "  const int rc = neptune_hip::geom_check_radius(g, " << reach << ");\n"
                    << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
-                   << "  return neptune_hip::" << fns[v] << "<" << body << ", " << T << ", " << st.rank() << ", 1, FP_" << ctag << ">(" << body
-                   << "{(" << T << ")" << lit << "}, g, in, out, (hipStream_t)stream, cfg);\n}\n";
-              ge << "extern \"C\" int " << ai.geom_symbol << "_variants(int rank) { return neptune_hip::march_variant_count(rank); }\n\n";
-            }
-          }
-          info.applies.push_back(ai);
-        } else {
-          o << "  // neptune_ir.time_advance {method = 0 (explicit), rhs = @" << op.callee << "}: state + dt * rhs(state)\n";
-          o << "  const nl::Val k_" << tag << " = " << op.callee << "__impl(sc, " << cname(op.operands[0]) << ", nullptr, nullptr, nullptr);\n";
-          if (st.rank() > 3) {
-            // rank 4..6: the rhs through its own lowering (leading dimensions peeled off, or the rank-generic kernel), the
-            // axpy as one flat pointwise pass
-            o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_euler_axpy_flat<" << T << ">(sc, (" << T << ")" << cname(op.operands[1])
-              << ", " << cname(op.operands[0]) << ", k_" << tag << ", " << dest << ");\n";
-            ApplyInfo ai;
-            ai.function = f.name;
-            ai.tag = tag;
-            ai.rank = st.rank();
-            ai.num_inputs = 2;
-            ai.march = true;
-            ai.halo_input = -1;
-            info.applies.push_back(ai);
-            continue;
-          }
-          o << "  const nl::Val* in_" << tag << "[] = {&" << cname(op.operands[0]) << ", &k_" << tag << "};\n";
-          o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply<neptune_hip::ops::EulerAxpy<" << T << ", " << st.rank()
-            << ">, " << T << ", " << st.rank() << ", 2, nl::PointwiseFP>(sc, neptune_hip::ops::EulerAxpy<" << T << ", " << st.rank() << ">{(" << T << ")"
-            << cname(op.operands[1]) << "}, " << bx << ", " << bx << ", in_" << tag << ", nl::kPointwiseRadius2, " << dest << ");\n";
-          ApplyInfo ai;
-          ai.function = f.name;
-          ai.tag = tag;
-          ai.rank = st.rank();
-          ai.num_inputs = 2;
-          ai.march = true;
-          ai.halo_input = -1;
-          info.applies.push_back(ai);
-        }
-      } else if (!op.callee.empty()) {
-        const Function* c = m.find(op.callee);
-        ValueInfo vi;
-        vi.type = c->result_types.at(0);
-        vi.uses = vals[op.results[0]].uses;
-        vals[op.results[0]] = vi;
-        std::string dest = "nullptr";
-        if (dest_of.count((int)oi)) dest = dest_of[(int)oi];
-        else if ((int)oi == returned_producer) dest = "dest";
-        o << "  // " << n << " @" << op.callee << "\n";
-        o << "  const nl::Val " << cname(op.results[0]) << " = " << op.callee << "__impl(sc";
-        for (auto& a : op.operands) o << ", " << cname(a);
-        o << ", " << dest << ", nullptr, nullptr);\n";
-      } else if (n == "neptune_ir.store") {
-        const Type& vt = op.types[0];
-        o << "  // neptune_ir.store " << op.operands[0] << " to " << op.operands[1] << "\n";
-        if (op.attrs.count("bounds")) {
-          std::string bx = new_box(op.attrs.at("bounds").bounds);
-          o << "  nl::run_store(sc, " << cname(op.operands[0]) << ", " << cname(op.operands[1]) << ", &" << bx << ", "
-            << dtype_macro(vt.elem) << ");\n";
-        } else {
-          o << "  nl::run_store(sc, " << cname(op.operands[0]) << ", " << cname(op.operands[1]) << ", nullptr, "
-            << dtype_macro(vt.elem) << ");\n";
-        }
-      } else if (n == "neptune_ir.reduce") {
-        scalar_kind[op.results[0]] = 1;   // under a slab view: this rank's partial sum
-        const Type& in = op.types[0];
-        std::string bx = "nullptr";
-        if (op.attrs.count("bounds")) bx = "&" + new_box(op.attrs.at("bounds").bounds);
-        auto fit = fused_reduce.find(op.operands[0]);
-        if (fit != fused_reduce.end()) {
-          const FusedReduce& fr = fit->second;
-          o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"sum\"}   (apply + fixed-tree device sum in one kernel, blocking)\n";
-          o << "  const " << fr.elem << " " << cname(op.results[0]) << " = (" << fr.elem << ")nl::run_apply_reduce_sum<Body_" << fr.tag
-            << ", " << fr.elem << ", " << fr.rank << ", " << fr.nin << ", FP_" << fr.tag << ">(sc, Body_" << fr.tag << "{}, "
-            << fr.result_box << ", " << fr.bounds_box << ", in_" << fr.tag << ", kTopRadius_" << fr.tag << ", " << fr.halo0 << ", "
-            << bx << ");\n";
-          continue;
-        }
-        o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"sum\"}   (fixed-tree device sum, blocking)\n";
-        o << "  const " << ctype(in.elem) << " " << cname(op.results[0]) << " = (" << ctype(in.elem) << ")nl::run_reduce_sum(sc, "
-          << cname(op.operands[0]) << ", " << bx << ", " << dtype_macro(in.elem) << ");\n";
-      } else if ((n.compare(0, 6, "arith.") == 0 || n.compare(0, 5, "math.") == 0) && op.regions.empty()) {
-        // scalar arithmetic at function level (constants, reduce results): plain host statements
-        static const std::map<std::string, int> none;
-        if (!emit_op(op, o, "  ", none, none, nullptr)) return false;
-        // what a scalar means when the function runs on one slab of a decomposed field: 0 = the same on every rank
-        // (constants and arithmetic on them), 1 = a bare reduce result (ranks add up), 2 = computed FROM a partial sum
-        // (sqrt of it, a product of two, ...): not recoverable from the per-rank values
-        int kind = 0;
-        for (auto& a : op.operands) {
-          auto it = scalar_kind.find(a);
-          if (it != scalar_kind.end() && it->second != 0) kind = 2;
-        }
-        for (auto& r : op.results) scalar_kind[r] = kind;
-      } else if (n == "neptune_ir.return" || n == "func.return" || n == "return") {
-        if (op.operands.empty()) {
-          o << "  return nl::Val{};\n";
-        } else if (f.result_types[0].is_scalar()) {
-          auto it = scalar_kind.find(op.operands[0]);
-          const int kind = it == scalar_kind.end() ? 0 : it->second;
-          returned_scalar_kind = (returned_scalar_kind < 0 || returned_scalar_kind == kind) ? kind : 2;
-          if (kind == 2)
-            o << "  if (sc.has_ghosts()) nl::die(\"" << f.name << "\", \"slab mode: the returned scalar is computed from a reduce result, "
-              << "which is only this rank's partial sum -- return the bare reduce and finish the arithmetic after the ranks' sums are added\");\n";
-          o << "  if (sret) *sret = (double)" << cname(op.operands[0]) << ";\n  return nl::Val{};\n";
-        } else {
-          const int root = vals[op.operands[0]].root_arg;
-          if (root >= 0) o << "  if (ret_arg) *ret_arg = " << root << ";\n";
-          o << "  return " << cname(op.operands[0]) << ";\n";
-        }
-      }
+                   << "  return neptune_hip::" << launch[v] << "<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
+                   << ">(" << body << "{" << init << "}, g, in, out, (hipStream_t)stream, cfg);\n}\n";
     }
-    o << "}\n";
+    geom_entries << "// march tiles this module holds for that entry (plan-time tuning: neptune_hip_autotune_fn)\n"
+                 << "extern \"C\" int " << sym << "_variants(int rank) { return neptune_hip::march_variant_count(rank); }\n\n";
+  }
 
-    // exported symbol with the expanded-memref ABI
+  void emit_alias(FnState& s, const Op& op) {
+    s.vals[op.results[0]].root_arg = s.vals[op.operands[0]].root_arg;
+    const bool temp = op.types[1].is_tempish();
+    Bounds b = op.types[temp ? 1 : 0].bounds;
+    if (!temp)  // unwrap -> memref: same buffer, zero-based box
+      for (int d = 0; d < b.rank(); ++d) { b.ub[d] -= b.lb[d]; b.lb[d] = 0; }
+    s.o << "  // " << op.name << " " << op.operands[0] << "\n";
+    s.o << "  const nl::Val " << cname(op.results[0]) << " = sc.alias(" << cname(op.operands[0]) << ", " << new_box(b) << ", \""
+        << op.name << "\");\n";
+  }
+
+  bool emit_apply(FnState& s, const Op& op, int oi) {
+    const auto& ops = s.f.body.ops;
+    const std::string tag = s.f.name + "_" + std::to_string(s.apply_counter++);
+    Footprint fp;
+    if (!emit_body(op, tag, fp)) return false;
+    const int nin = (int)op.operands.size();
+    const Type& res = op.types[nin];
+    ValueInfo& vi = s.vals[op.results[0]];
+    vi.root_arg = -1;
+    // single-use result consumed by a reduce a few scalar/alias ops later: the apply is evaluated
+    // inside the reduction kernel (run_apply_reduce_sum), the temp never exists
+    bool fused = false;
+    if (vi.uses == 1 && fp.lead == 0)
+      for (size_t j = oi + 1; j < ops.size(); ++j) {
+        const Op& c = *ops[j];
+        if (c.name == "neptune_ir.reduce" && c.operands.at(0) == op.results[0]) { fused = true; break; }
+        const std::string& nm = c.name;
+        if (!(nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" || is_scalar_op(c))) break;
+      }
+    const std::string res_box = new_box(res.bounds), bounds_box = new_box(op.attrs.at("bounds").bounds);
+    std::vector<std::string> ins;
+    for (auto& v : op.operands) ins.push_back(cname(v));
+    s.o << "  // neptune_ir.apply -> " << op.results[0]
+        << (fused ? "   (evaluated inside the reduce below)\n" : "   (kernel + fused copy-through)\n");
+    emit_inputs(s.o, tag, ins);
+    if (fused) {
+      s.fused_reduce[op.results[0]] = {tag, ctype(res.elem), res_box, bounds_box, res.bounds.rank(), nin, halo0_of(fp)};
+      ApplyInfo ai = apply_info(s, tag, fp, fp.rank, "", 0);
+      ai.march = false;
+      ai.fused_reduce = true;
+      info.applies.push_back(ai);
+      return true;
+    }
+    // the run_apply* template arguments and call arguments the three forms share
+    const std::string targs = "<Body_" + tag + ", " + ctype(res.elem) + ", " + std::to_string(res.bounds.rank()) + ", " +
+                              std::to_string(nin);
+    const std::string args = "(sc, Body_" + tag + "{}, " + res_box + ", " + bounds_box + ", in_" + tag + ", ";
+    const std::string dest = s.dest_for(oi);
+    s.o << "  const nl::Val " << cname(op.results[0]) << " = ";
+    // rank 4..6: no geometry-level entry (neptune_hip_apply_geom_t is rank 1..3)
+    if (fp.nd) {
+      // offsets along a leading dimension: the rank-generic kernel (lowered_runtime.hpp run_apply_nd)
+      s.o << "nl::run_apply_nd" << targs << ">" << args << "kNdReach_" << tag << ", " << dest << ", " << fp.nd_halo0 << ");\n";
+      ApplyInfo ai = apply_info(s, tag, fp, res.bounds.rank(), res.elem, fp.nd_halo0);
+      ai.march = false;
+      ai.box = true;
+      ai.halo_input = 0;
+      info.applies.push_back(ai);
+    } else if (fp.lead > 0) {
+      // one rank-3 apply per index of the leading dimensions (lowered_runtime.hpp run_apply_batched)
+      s.o << "nl::run_apply_batched" << targs << ", FP_" << tag << ">" << args << "kTopRadius_" << tag << ", " << dest << ");\n";
+      info.applies.push_back(apply_info(s, tag, fp, res.bounds.rank(), res.elem, 0));
+    } else {
+      s.o << "nl::run_apply" << targs << ", FP_" << tag << ">" << args << "kTopRadius_" << tag << ", " << dest << ", "
+          << halo0_of(fp) << ");\n";
+      ApplyInfo ai = apply_info(s, tag, fp, fp.rank, res.elem, halo0_of(fp));
+      ai.geom_symbol = tag + "__geom";
+      emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
+      info.applies.push_back(ai);
+    }
+    return true;
+  }
+
+  // the rhs apply of a time_advance that one kernel can fuse with the axpy: the opdef is exactly "apply(state) ; return"
+  // with result box == state box (nullptr: two kernels)
+  const Op* fusable_rhs(const Op& op) const {
+    const Type& st = op.types[0];
+    const Function* c = m.find(op.callee);
+    if (!(st.rank() <= 3 && c && c->arg_types.size() == 1 && c->body.ops.size() == 2 && c->body.ops[0]->name == "neptune_ir.apply" &&
+          c->body.ops[1]->name == "neptune_ir.return" && c->body.ops[1]->operands.size() == 1 &&
+          c->body.ops[1]->operands[0] == c->body.ops[0]->results.at(0) && c->body.ops[0]->operands.size() == 1 &&
+          c->body.ops[0]->operands[0] == c->body.args[0].name))
+      return nullptr;
+    const Op& a = *c->body.ops[0];
+    const Type &in = a.types[0], &rt = a.types[1];
+    const bool same = in.is_tempish() && in.elem == st.elem && rt.elem == st.elem && in.bounds == st.bounds && rt.bounds == st.bounds;
+    return same ? &a : nullptr;
+  }
+
+  // explicit Euler step: k = rhs(state); result = state + dt * k, over the whole box.  The
+  // reference's own explicit lowering (HighLevelConvertion.cpp:77-120) builds exactly this
+  // apply_{linear,nonlinear} + axpy apply pair (its version is 1-D-only and ill-formed).
+  // A fusable rhs runs as one kernel computing state + dt * rhs(state) (ops::EulerFused); both forms produce the same bits.
+  bool emit_time_advance(FnState& s, const Op& op, int oi) {
+    const Type& st = op.types[0];
+    s.vals[op.results[0]].root_arg = -1;
+    const std::string dest = s.dest_for(oi);
+    const std::string tag = s.f.name + "_ta" + std::to_string(s.apply_counter++);
+    const std::string bx = new_box(st.bounds);
+    const std::string T = ctype(st.elem);
+    const std::string state = cname(op.operands[0]), dt = "(" + T + ")" + cname(op.operands[1]);
+    std::ostringstream& o = s.o;
+    const Op* rhs_apply = fusable_rhs(op);
+    if (!rhs_apply) {
+      o << "  // neptune_ir.time_advance {method = 0 (explicit), rhs = @" << op.callee << "}: state + dt * rhs(state)\n";
+      o << "  const nl::Val k_" << tag << " = " << op.callee << "__impl(sc, " << state << ", nullptr, nullptr, nullptr);\n";
+      if (st.rank() > 3) {
+        // rank 4..6: the rhs through its own lowering (leading dimensions peeled off, or the rank-generic kernel), the
+        // axpy as one flat pointwise pass
+        o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_euler_axpy_flat<" << T << ">(sc, " << dt << ", " << state
+          << ", k_" << tag << ", " << dest << ");\n";
+      } else {
+        emit_inputs(o, tag, {state, "k_" + tag});
+        const std::string axpy = "neptune_hip::ops::EulerAxpy<" + T + ", " + std::to_string(st.rank()) + ">";
+        o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply<" << axpy << ", " << T << ", " << st.rank()
+          << ", 2, nl::PointwiseFP>(sc, " << axpy << "{" << dt << "}, " << bx << ", " << bx << ", in_" << tag
+          << ", nl::kPointwiseRadius2, " << dest << ");\n";
+      }
+      Footprint pointwise;  // the axpy reads state and k at the centre
+      pointwise.nin = 2;
+      info.applies.push_back(apply_info(s, tag, pointwise, st.rank(), "", 0));
+      return true;
+    }
+    Footprint cfp;
+    std::map<std::string, int> ti, ia;
+    if (!analyze_apply(*rhs_apply, cfp, ti, ia)) return false;
+    const std::string ctag = op.callee + "_0";  // the tag emit_apply gives the opdef's only apply
+    o << "  // neptune_ir.time_advance {method = 0 (explicit), rhs = @" << op.callee
+      << "}: state + dt * rhs(state), rhs apply and axpy fused into one kernel\n";
+    o << "  static const neptune_hip::Reach kTopRadius_" << tag << " = " << fused_reach(cfp, st.rank()) << ";\n";
+    emit_inputs(o, tag, {state});
+    const std::string body = "neptune_hip::ops::EulerFused<Body_" + ctag + ", " + T + ", " + std::to_string(st.rank()) + ">";
+    o << "  const nl::Val " << cname(op.results[0]) << " = nl::run_apply<" << body << ", " << T << ", " << st.rank() << ", 1, FP_"
+      << ctag << ">(sc, " << body << "{" << dt << "}, " << bx << ", " << new_box(rhs_apply->attrs.at("bounds").bounds) << ", in_"
+      << tag << ", kTopRadius_" << tag << ", " << dest << ", " << halo0_of(cfp) << ");\n";
+    ApplyInfo ai = apply_info(s, tag, cfp, st.rank(), st.elem, halo0_of(cfp));
+    // With a constant time step the fused step is a self-contained apply: give it geometry-level entries too
+    // (single step, two steps per pass, tile count), so step loops and slab decompositions can drive `u + dt*rhs(u)`
+    // exactly like a plain operator.
+    auto dit = s.def_at.find(op.operands[1]);
+    const Op* dtdef = dit == s.def_at.end() ? nullptr : s.f.body.ops[dit->second].get();
+    bool lit_ok = false;
+    std::string lit;
+    if (dtdef && dtdef->name == "arith.constant") lit = float_literal(dtdef->literal, st.elem, lit_ok);
+    if (lit_ok) {
+      ai.geom_symbol = tag + "__geom";
+      geom_entries << "static const neptune_hip::Reach kTopRadiusG_" << tag << " = " << fused_reach(cfp, st.rank()) << ";\n";
+      emit_geom_entries(ai.geom_symbol, "kTopRadiusG_" + tag, body, "(" + T + ")" + lit, T, st.rank(), 1, "FP_" + ctag);
+    }
+    info.applies.push_back(ai);
+    return true;
+  }
+
+  // apply_linear / apply_nonlinear @A(x): a call of A__impl, which may write straight into this op's destination
+  void emit_call(FnState& s, const Op& op, int oi) {
+    s.vals[op.results.at(0)].root_arg = -1;   // at(): a call of an opdef without a result is refused (malformed module)
+    s.o << "  // " << op.name << " @" << op.callee << "\n";
+    s.o << "  const nl::Val " << cname(op.results[0]) << " = " << op.callee << "__impl(sc";
+    for (auto& a : op.operands) s.o << ", " << cname(a);
+    s.o << ", " << s.dest_for(oi) << ", nullptr, nullptr);\n";
+  }
+
+  void emit_store(FnState& s, const Op& op) {
+    s.o << "  // neptune_ir.store " << op.operands[0] << " to " << op.operands[1] << "\n";
+    const std::string bx = op.attrs.count("bounds") ? "&" + new_box(op.attrs.at("bounds").bounds) : "nullptr";
+    s.o << "  nl::run_store(sc, " << cname(op.operands[0]) << ", " << cname(op.operands[1]) << ", " << bx << ", "
+        << dtype_macro(op.types[0].elem) << ");\n";
+  }
+
+  void emit_reduce(FnState& s, const Op& op) {
+    s.scalar_kind[op.results[0]] = 1;   // under a slab view: this rank's partial sum
+    const std::string bx = op.attrs.count("bounds") ? "&" + new_box(op.attrs.at("bounds").bounds) : "nullptr";
+    auto fit = s.fused_reduce.find(op.operands[0]);
+    if (fit != s.fused_reduce.end()) {
+      const FusedReduce& fr = fit->second;
+      s.o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"sum\"}   (apply + fixed-tree device sum in one kernel, blocking)\n";
+      s.o << "  const " << fr.elem << " " << cname(op.results[0]) << " = (" << fr.elem << ")nl::run_apply_reduce_sum<Body_" << fr.tag
+          << ", " << fr.elem << ", " << fr.rank << ", " << fr.nin << ", FP_" << fr.tag << ">(sc, Body_" << fr.tag << "{}, "
+          << fr.result_box << ", " << fr.bounds_box << ", in_" << fr.tag << ", kTopRadius_" << fr.tag << ", " << fr.halo0 << ", "
+          << bx << ");\n";
+      return;
+    }
+    const std::string& elem = op.types[0].elem;
+    s.o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"sum\"}   (fixed-tree device sum, blocking)\n";
+    s.o << "  const " << ctype(elem) << " " << cname(op.results[0]) << " = (" << ctype(elem) << ")nl::run_reduce_sum(sc, "
+        << cname(op.operands[0]) << ", " << bx << ", " << dtype_macro(elem) << ");\n";
+  }
+
+  // scalar arithmetic at function level (constants, reduce results): plain host statements
+  bool emit_scalar(FnState& s, const Op& op) {
+    static const std::map<std::string, int> none;
+    if (!emit_op(op, s.o, "  ", none, none, nullptr)) return false;
+    // what a scalar means when the function runs on one slab of a decomposed field: 0 = the same on every rank
+    // (constants and arithmetic on them), 1 = a bare reduce result (ranks add up), 2 = computed FROM a partial sum
+    // (sqrt of it, a product of two, ...): not recoverable from the per-rank values
+    int kind = 0;
+    for (auto& a : op.operands) {
+      auto it = s.scalar_kind.find(a);
+      if (it != s.scalar_kind.end() && it->second != 0) kind = 2;
+    }
+    for (auto& r : op.results) s.scalar_kind[r] = kind;
+    return true;
+  }
+
+  void emit_return(FnState& s, const Op& op) {
+    if (op.operands.empty()) {
+      s.o << "  return nl::Val{};\n";
+    } else if (s.f.result_types[0].is_scalar()) {
+      auto it = s.scalar_kind.find(op.operands[0]);
+      const int kind = it == s.scalar_kind.end() ? 0 : it->second;
+      s.returned_scalar_kind = (s.returned_scalar_kind < 0 || s.returned_scalar_kind == kind) ? kind : 2;
+      if (kind == 2)
+        s.o << "  if (sc.has_ghosts()) nl::die(\"" << s.f.name << "\", \"slab mode: the returned scalar is computed from a reduce result, "
+            << "which is only this rank's partial sum -- return the bare reduce and finish the arithmetic after the ranks' sums are added\");\n";
+      s.o << "  if (sret) *sret = (double)" << cname(op.operands[0]) << ";\n  return nl::Val{};\n";
+    } else {
+      const int root = s.vals[op.operands[0]].root_arg;
+      if (root >= 0) s.o << "  if (ret_arg) *ret_arg = " << root << ";\n";
+      s.o << "  return " << cname(op.operands[0]) << ";\n";
+    }
+  }
+
+  // the exported symbol with the expanded-memref ABI, and its signature in the report
+  void emit_abi(FnState& s) {
+    const Function& f = s.f;
+    const int nargs = (int)f.arg_types.size();
+    std::ostringstream& o = s.o;
     const bool has_res = !f.result_types.empty();
     const bool scalar_res = has_res && f.result_types[0].is_scalar();
     const int rrank = (has_res && !scalar_res) ? f.result_types[0].rank() : 0;
@@ -1003,7 +915,7 @@ struct Emitter {
       }
     }
     o << "  int ret_arg = -1;\n  double sret = 0.0;\n";
-    o << "  " << ((has_res && !scalar_res) ? "const nl::Val r = " : "") << impl << "(sc";
+    o << "  " << ((has_res && !scalar_res) ? "const nl::Val r = " : "") << f.name << "__impl(sc";
     for (int i = 0; i < nargs; ++i) o << ", m" << i;
     o << ", nullptr, &ret_arg, &sret);\n";
     o << "  sc.finish();\n";
@@ -1046,9 +958,8 @@ struct Emitter {
     for (auto& t : f.arg_types) sig.args.push_back(conv(t));
     sig.has_result = has_res;
     if (has_res) sig.result = conv(f.result_types[0]);
-    if (scalar_res) sig.result.scalar = returned_scalar_kind <= 0 ? "uniform" : (returned_scalar_kind == 1 ? "partial_sum" : "derived");
+    if (scalar_res) sig.result.scalar = s.returned_scalar_kind <= 0 ? "uniform" : (s.returned_scalar_kind == 1 ? "partial_sum" : "derived");
     info.signatures.push_back(sig);
-    return true;
   }
 
   // ---- outlining: the stencil part of a function that also holds solver ops ----------------------------------
@@ -1088,7 +999,7 @@ struct Emitter {
     for (size_t oi = 0; oi < ops.size(); ++oi) {
       const Op& op = *ops[oi];
       const std::string& n = op.name;
-      if (n == "neptune_ir.wrap" || n == "neptune_ir.unwrap" || n == "neptune_ir.load" || n == "neptune_ir.as_tensor" || n == "neptune_ir.from_tensor")
+      if (is_alias_op(n))
         if (!op.results.empty() && !op.operands.empty()) root[op.results[0]] = root_of(op.operands[0]);
       bool t = op.opaque;
       for (auto& v : op.operands) t = t || tainted[v] || dirty_root[root_of(v)];

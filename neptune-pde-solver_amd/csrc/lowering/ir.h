@@ -73,6 +73,17 @@ struct Op {
   int line = 0;
 };
 
+// ops whose result is their operand's buffer under another type or box (DataflowLowering.cpp:131-159)
+inline bool is_alias_op(const std::string& n) {
+  return n == "neptune_ir.wrap" || n == "neptune_ir.unwrap" || n == "neptune_ir.load" || n == "neptune_ir.as_tensor" ||
+         n == "neptune_ir.from_tensor";
+}
+inline bool is_return_op(const std::string& n) { return n == "neptune_ir.return" || n == "func.return" || n == "return"; }
+// arith / math op on scalars (no scf-style regions)
+inline bool is_scalar_op(const Op& op) {
+  return (op.name.compare(0, 6, "arith.") == 0 || op.name.compare(0, 5, "math.") == 0) && op.regions.empty();
+}
+
 struct BlockArg {
   std::string name;
   Type type;

@@ -395,8 +395,7 @@ struct Parser {
       op.types = {a, b};
       return true;
     }
-    if (n == "neptune_ir.wrap" || n == "neptune_ir.unwrap" || n == "neptune_ir.load" || n == "neptune_ir.as_tensor" ||
-        n == "neptune_ir.from_tensor") {
+    if (is_alias_op(n)) {
       // $x attr-dict `:` type($x) `->` type($result)   (NeptuneIROps.td:31-33, 55-57, 79-81, 553-556, 588-591)
       op.operands.push_back(next().text);
       if (is("{")) { if (!parse_attr_dict(op.attrs)) return false; }
@@ -459,7 +458,7 @@ struct Parser {
       for (auto& r : res) op.types.push_back(r);
       return true;
     }
-    if (n == "neptune_ir.yield" || n == "neptune_ir.return" || n == "func.return" || n == "return" || n == "scf.yield") {
+    if (n == "neptune_ir.yield" || is_return_op(n) || n == "scf.yield") {
       parse_operands(op.operands);
       if (!op.operands.empty()) {
         if (!expect(":")) return false;

@@ -249,7 +249,7 @@ struct Verifier {
         }
         if (unknown) {
           for (auto& r : op.results) { Type t; sc[r] = t; }
-          if (n == "neptune_ir.return" || n == "func.return" || n == "return") returned = true;
+          if (is_return_op(n)) returned = true;
           continue;
         }
       }
@@ -356,9 +356,9 @@ struct Verifier {
         }
         if (!op.types.at(1).is_scalar() || op.types[1].elem != in.elem) { diag.fail(op.line, "'neptune_ir.reduce' op result type must equal the input's element type"); return false; }
         sc[op.results.at(0)] = op.types[1];
-      } else if ((n.compare(0, 6, "arith.") == 0 || n.compare(0, 5, "math.") == 0) && op.regions.empty()) {
+      } else if (is_scalar_op(op)) {
         if (!check_arith(op, sc)) return false;   // scalar arithmetic on reduce results / constants
-      } else if (n == "neptune_ir.return" || n == "func.return" || n == "return") {
+      } else if (is_return_op(n)) {
         if (oi + 1 != f.body.ops.size()) { diag.fail(op.line, "return must be the last operation of @" + f.name); return false; }
         if (opdef && n != "neptune_ir.return") { diag.fail(op.line, "@" + f.name + ": body must terminate with neptune_ir.return"); return false; }
         if (op.operands.size() != f.result_types.size()) { diag.fail(op.line, "@" + f.name + ": return operand count must match function results"); return false; }
