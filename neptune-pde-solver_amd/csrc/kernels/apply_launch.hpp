@@ -112,6 +112,27 @@ inline int geom_check_radius(const neptune_hip_apply_geom_t* g,
   return NEPTUNE_HIP_OK;
 }
 
+// out must not overlap an input: every wave reads neighbours other waves may already have
+// overwritten.  (The reference materialises a fresh buffer per apply, DataflowLowering.cpp:281.)
+// Shared by neptune_hip_apply_builtin and the geometry-level entries of every lowered module.
+inline bool buffers_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+inline size_t geom_box_bytes(const int64_t* lb, const int64_t* ub, int rank, size_t elem) {
+  size_t n = elem;
+  for (int d = 0; d < rank; ++d) n *= (size_t)(ub[d] - lb[d]);
+  return n;
+}
+inline int check_no_alias(const neptune_hip_apply_geom_t* g, const void* const* in, const void* out, size_t elem) {
+  const size_t ob = geom_box_bytes(g->out_lb, g->out_ub, g->rank, elem);
+  for (int k = 0; k < g->num_inputs; ++k) {
+    const size_t ib = geom_box_bytes(g->in_lb[k], g->in_ub[k], g->rank, elem);
+    if (buffers_overlap(in[k], ib, out, ob)) return NEPTUNE_HIP_EINVAL;
+  }
+  return NEPTUNE_HIP_OK;
+}
+
 // logical-dim arrays -> kernel axis order (I,J,K); absent axes get `fill`
 template <int RANK>
 inline void to_axes(const int64_t* src, int64_t dst[3], int64_t fill) {
@@ -857,10 +878,12 @@ inline int launch_apply(const Body& body, const neptune_hip_apply_geom_t* g, con
   const bool free_choice = !cfg || (cfg->kernel == NEPTUNE_HIP_KERNEL_AUTO && cfg->variant < 0 && cfg->chunk == 0 && cfg->flags == 0);
   if (free_choice && tune_mode() != 0 && g && FP::MARCH_OK) {
     // one table per body (this function is instantiated per Body); key: everything of the geometry that the
-    // launcher looks at, plus the 16-byte alignment of the buffers
+    // launcher looks at -- each input's box relative to the result's included: whether it contains the result's box
+    // decides march or direct (plan_apply) -- plus the 16-byte alignment of the buffers
+    constexpr int kKeyLen = 5 * 3 + 1 + 2 * 3 * kMaxInputs;
     static std::mutex mu;
-    static std::map<std::array<int64_t, 20>, neptune_hip_launch_cfg_t> table;
-    std::array<int64_t, 20> key{};
+    static std::map<std::array<int64_t, kKeyLen>, neptune_hip_launch_cfg_t> table;
+    std::array<int64_t, kKeyLen> key{};
     int n = 0;
     int64_t cells = 1;
     for (int d = 0; d < 3; ++d) {
@@ -872,11 +895,13 @@ inline int launch_apply(const Body& body, const neptune_hip_apply_geom_t* g, con
       if (d < RANK) cells *= (g->region_ub[d] > g->region_lb[d] ? g->region_ub[d] - g->region_lb[d] : 0);
     }
     int64_t align = ((uintptr_t)out % 16 == 0);
-    for (int k = 0; k < NIN; ++k) {
-      align = align * 2 + ((uintptr_t)in[k] % 16 == 0);
-      for (int d = 0; d < RANK; ++d) align = align * 2 + (g->in_lb[k][d] == g->out_lb[d] && g->in_ub[k][d] == g->out_ub[d]);
-    }
+    for (int k = 0; k < NIN; ++k) align = align * 2 + ((uintptr_t)in[k] % 16 == 0);
     key[n++] = align;
+    for (int k = 0; k < NIN; ++k)
+      for (int d = 0; d < RANK; ++d) {
+        key[n++] = g->in_lb[k][d] - g->out_lb[d];
+        key[n++] = g->in_ub[k][d] - g->out_ub[d];
+      }
     const neptune_hip_launch_cfg_t untuned = {NEPTUNE_HIP_KERNEL_AUTO, -1, 0, 0};
     neptune_hip_launch_cfg_t tuned = untuned;
     bool have = false;
@@ -895,7 +920,12 @@ inline int launch_apply(const Body& body, const neptune_hip_apply_geom_t* g, con
         for (int i = 0; i < n; ++i) wkey += (i ? "," : "|") + std::to_string(key[i]);
         if (neptune_hip_wisdom_lookup(wkey.c_str(), &tuned) &&
             (tuned.kernel != NEPTUNE_HIP_KERNEL_MARCH || (tuned.variant >= 0 && tuned.variant < march_variant_count(RANK)))) {
-          // (a choice this translation unit cannot run -- a tile index beyond its table -- is measured again)
+          // (a choice this translation unit cannot run -- a tile index beyond its table -- is measured again; one the plan
+          // refuses for this geometry is neither used nor remembered)
+          if (tuned.kernel == NEPTUNE_HIP_KERNEL_MARCH && plan_apply<T, RANK, NIN, FP>(g, in, out, &tuned) != NEPTUNE_HIP_KERNEL_MARCH) {
+            tuned = untuned;
+            decided = false;
+          }
         } else {
           tuned = untuned;
           // measuring synchronises the stream: not possible while it is being captured into a graph (the step
@@ -917,7 +947,10 @@ inline int launch_apply(const Body& body, const neptune_hip_apply_geom_t* g, con
       }
     }
     const bool is_tuned = tuned.kernel != NEPTUNE_HIP_KERNEL_AUTO || tuned.variant >= 0 || tuned.chunk != 0;
-    if (is_tuned) return launch_apply_impl<Body, T, RANK, NIN, FP>(body, g, in, out, stream, &tuned);
+    // a remembered choice this geometry cannot take (a march tile where the plan says direct) is not used: the free
+    // choice runs instead
+    const bool takes = tuned.kernel != NEPTUNE_HIP_KERNEL_MARCH || plan_apply<T, RANK, NIN, FP>(g, in, out, &tuned) == NEPTUNE_HIP_KERNEL_MARCH;
+    if (is_tuned && takes) return launch_apply_impl<Body, T, RANK, NIN, FP>(body, g, in, out, stream, &tuned);
   }
   return launch_apply_impl<Body, T, RANK, NIN, FP>(body, g, in, out, stream, cfg);
 }

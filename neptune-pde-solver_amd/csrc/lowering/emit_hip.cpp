@@ -643,6 +643,8 @@ struct Emitter {
                    << "  if (!g || !in || !out) return NEPTUNE_HIP_EINVAL;\n"
                    << "  const int rc = neptune_hip::geom_check_radius(g, " << reach << ");\n"
                    << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
+                   << "  // an output that overlaps an input is refused, as neptune_hip_apply_builtin does\n"
+                   << "  if (neptune_hip::check_no_alias(g, in, out, sizeof(" << T << ")) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;\n"
                    << "  return neptune_hip::" << launch[v] << "<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
                    << ">(" << body << "{" << init << "}, g, in, out, (hipStream_t)stream, cfg);\n}\n";
     }

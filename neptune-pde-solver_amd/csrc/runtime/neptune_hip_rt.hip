@@ -68,26 +68,6 @@ const rtbody::Entry* body_entry(int body) {
   return nullptr;
 }
 
-// out must not overlap an input: every wave reads neighbours other waves may already have
-// overwritten.  (The reference materialises a fresh buffer per apply, DataflowLowering.cpp:281.)
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-size_t geom_bytes(const int64_t* lb, const int64_t* ub, int rank, size_t elem) {
-  size_t n = elem;
-  for (int d = 0; d < rank; ++d) n *= (size_t)(ub[d] - lb[d]);
-  return n;
-}
-int check_no_alias(const neptune_hip_apply_geom_t* g, const void* const* in, const void* out, size_t elem) {
-  const size_t ob = geom_bytes(g->out_lb, g->out_ub, g->rank, elem);
-  for (int k = 0; k < g->num_inputs; ++k) {
-    const size_t ib = geom_bytes(g->in_lb[k], g->in_ub[k], g->rank, elem);
-    if (overlaps(in[k], ib, out, ob)) return NEPTUNE_HIP_EINVAL;
-  }
-  return NEPTUNE_HIP_OK;
-}
-
 size_t body_elem_size(int body) { return body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? 4 : 8; }
 
 }  // namespace
@@ -177,7 +157,7 @@ int vec_update(int dtype, int64_t n, double a, const void* x, void* y, void* str
   if (n == 0) return NEPTUNE_HIP_OK;
   if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
   // the kernel reads x and writes y through __restrict__ pointers: overlapping ranges would be undefined behaviour
-  if (overlaps(x, (size_t)n * (dtype == NEPTUNE_HIP_F64 ? 8 : 4), y, (size_t)n * (dtype == NEPTUNE_HIP_F64 ? 8 : 4))) return NEPTUNE_HIP_EINVAL;
+  if (buffers_overlap(x, (size_t)n * (dtype == NEPTUNE_HIP_F64 ? 8 : 4), y, (size_t)n * (dtype == NEPTUNE_HIP_F64 ? 8 : 4))) return NEPTUNE_HIP_EINVAL;
   ensure_init();
   if (((uintptr_t)x | (uintptr_t)y) % 16 == 0) {   // 16-byte vectors, exact grid
     const int vk = dtype == NEPTUNE_HIP_F64 ? 2 : 4;
