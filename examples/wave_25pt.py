@@ -4,7 +4,9 @@
     u_next = 2 u - u_prev + (c dt / h)^2 * L8(u)
 
 written with the Python DSL as ONE two-input apply per step: `u` is read at 25 offsets (radius 4, the march
-kernel's widest 3-D footprint), `u_prev` at the centre only.  Three device fields rotate, nothing else is
+kernel's widest 3-D footprint), `u_prev` at the centre only.  Three device fields rotate inside
+neptune_hip_step_loop_leapfrog -- no per-step synchronisation, long runs replay a hipGraph; radius 4 is beyond the
+two-steps-per-pass kernel (examples/wave_leapfrog.py shows that one), so every step is one launch.  Nothing else is
 allocated or copied; the energy-like diagnostic sum(u^2) is a fused reduce(apply).
 
 usage: examples/wave_25pt.py [N] [STEPS]        (default 256^3, 100 steps)"""
@@ -60,19 +62,26 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     import torch
+    from neptune_hip import apply, fields
     mod = build(n, 0.1)
     kernels = [(a["function"], a["kernel"]) for a in mod.report["applies"]]
     print("kernels:", kernels)
     g = torch.arange(n, dtype=torch.float64, device="cuda") - n / 2
     pulse = torch.exp(-(g[:, None, None] ** 2 + g[None, :, None] ** 2 + g[None, None, :] ** 2) / 18.0)   # centred Gaussian
-    prev, cur, nxt = pulse.clone(), pulse.clone(), torch.zeros_like(pulse)        # starts at rest
-    e0 = mod.call("norm2", cur)
+    fs = [pulse.clone(), pulse.clone(), torch.zeros_like(pulse)]                  # u(0), u(-1): starts at rest; scratch
+    entry = mod.geom_entry("step")                                                # the leapfrog apply, callable with a geometry
+    f0 = fields.DeviceField((0, 0, 0), (n, n, n), tensor=fs[0])
+    geom = apply.geom_for([f0, f0], f0, ([R] * 3, [n - R] * 3))
+    e0 = mod.call("norm2", fs[0])
+    warm = [f.clone() for f in fs]                                                # settles the launch's tile choice off the clock
+    apply.step_loop_leapfrog(entry, geom, warm, steps=steps)
+    torch.cuda.synchronize()
+    del warm
     t0 = time.perf_counter()
-    for s in range(steps):
-        mod.call("step", nxt, cur, prev)
-        prev, cur, nxt = cur, nxt, prev
+    cur, prev = apply.step_loop_leapfrog(entry, geom, fs, steps=steps)            # -> which fields hold u(steps), u(steps - 1)
     torch.cuda.synchronize()
     per = (time.perf_counter() - t0) / steps
+    cur = fs[cur]
     e1 = mod.call("norm2", cur)
     rim_quiet = bool(cur[:R].abs().max() < 1e-6)           # the pulse has not reached the (fixed) rim
     finite = bool(torch.isfinite(cur).all())

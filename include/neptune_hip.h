@@ -283,6 +283,36 @@ int neptune_hip_step_loop_chain(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn
                                 const neptune_hip_apply_geom_t *g, void *const fields[2], const void *const *in,
                                 int64_t steps, void *stream, const neptune_hip_launch_cfg_t *cfg);
 
+/* Two-level (leapfrog) schemes: u(n+1) = F(u(n), u(n-1), c...), e.g. the second-order wave equation.
+ * A lowered apply whose input 0 is a star of radius <= 2, whose input 1 is read at the centre only and has input 0's element
+ * type, and whose further inputs are read at the centre only exports <function>_<k>__geomL2 next to __geom: ONE pair,
+ *   in[0] = u(n), in[1] = u(n-1), in[2..] = centre-only inputs; out_v = u(n+1), out_w = u(n+2)
+ * in one pass over HBM (csrc/kernels/apply_march2.hpp: 4.4 field passes instead of 6), bit-identical to two __geom
+ * launches.  Both results are stored.  out_v and out_w must be buffers distinct from every input and from each other; the
+ * geometry must qualify as for __geom2 (all boxes equal, rows a whole number of 64-byte granules, launch region
+ * restricted along dim 0 only).  Anything else returns NEPTUNE_HIP_EUNSUPPORTED and nothing is launched. */
+typedef int (*neptune_hip_leapfrog2_fn)(const neptune_hip_apply_geom_t *g, const void *const *in, void *out_v,
+                                        void *out_w, void *stream, const neptune_hip_launch_cfg_t *cfg);
+
+/* `steps` steps of a two-level scheme on rotating fields.  fields[0] = u(0), fields[1] = u(-1), fields[2] = scratch,
+ * fields[3] = second scratch or NULL.  fn = the apply's ordinary geometry-level entry (inputs: state, previous state,
+ * extra[0 .. n_extra-1]); fn2 = its leapfrog pair entry or NULL.  On return *cur / *prev are the indices into fields[]
+ * that hold u(steps) and u(steps-1): BOTH are defined, whatever the grouping.  Asynchronous on `stream`.
+ *   single launches: next <- F(cur, prev), then (prev, cur, next) <- (cur, next, prev): three fields, period 3;
+ *   pairs (fn2 and fields[3] present): (v, w) go into the two free buffers and (prev, cur) <- (v, w): four fields, period
+ *   two pair launches; an odd step count ends with one single launch.
+ * Long runs replay a cached hipGraph (one linear chain of 18 single or 8 pair launches).  Whether pairs pay is measured
+ * once per (entry, geometry) and process, as neptune_hip_step_loop_chain does (a pair must win by 3 %; the trial launches
+ * write only into the free buffers); NEPTUNE_HIP_NO_PAIRS, NEPTUNE_HIP_TUNE=0 and NEPTUNE_HIP_CHAIN_MIN_CELLS apply
+ * as there.  NEPTUNE_HIP_EUNSUPPORTED from fn2 is not an error: that (entry, geometry) runs single launches from then on. */
+int neptune_hip_step_loop_leapfrog(neptune_hip_apply_fn fn, neptune_hip_leapfrog2_fn fn2,
+                                   const neptune_hip_apply_geom_t *g, void *const fields[4], const void *const *extra,
+                                   int n_extra, int64_t steps, void *stream, const neptune_hip_launch_cfg_t *cfg,
+                                   int *cur, int *prev);
+/* how many single and pair launches the last neptune_hip_step_loop_leapfrog call of this process issued or replayed
+ * (its trial launches not counted) */
+void neptune_hip_leapfrog_launch_counts(int64_t *singles, int64_t *pairs);
+
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t *g,

@@ -25,7 +25,8 @@ int neptune_lowering_verify(const char *mlir_text, char **diag_out);
  *   applies     per neptune_ir.apply (and per explicit time_advance): rank, inputs, element type, kernel family
  *               (march | direct | reduce = evaluated inside the consuming reduce's kernel), stencil shape,
  *               halo0 (reach along dim 0: the ghost planes a slab decomposition must hold) and geom_symbol,
- *               the exported geometry-level entry of that apply (neptune_hip_apply_fn, include/neptune_hip.h)
+ *               the exported geometry-level entry of that apply (neptune_hip_apply_fn, include/neptune_hip.h);
+ *               leapfrog_symbol, the pair entry <geom_symbol>L2 of a two-level scheme (neptune_hip_leapfrog2_fn), or ""
  * Set NEPTUNE_HIP_FULL_VARIANTS=1 in the environment of neptune_lowering_compile to build every march tile
  * into the module instead of the defaults (for NEPTUNE_HIP_TUNE=1). */
 int neptune_lowering_to_hip(const char *mlir_text, char **source_out, char **report_out, char **diag_out);

@@ -27,6 +27,15 @@
 //     from u(i..i+2) and w(i) from v(i-1..i+1), stores w(i).  A chunk starts two planes early (results discarded)
 //     to fill the v ring: 4 redundant plane reads per chunk.
 //   * one barrier per step: the waves publish the edge rows of u(i+1) AND of v(i) together.
+//
+// Leapfrog form (LF, two stages only): two steps of a TWO-LEVEL scheme u(n+1) = B(u(n), u(n-1), c...) in one pass,
+//     v = B(u, p, c...)      w = B(v, u, c...)
+// with input 1 of the body the previous state (read at the centre only).  Stage 2's input 1 is not a field in memory: it is
+// the centre plane of stage 1's input ring.  p is needed at stage 1's plane only (one plane in flight, no queue), and BOTH
+// v and w are stored (the next pair reads (w, v); the caller is entitled to both states), v with the predicates of w, so
+// whole 64-byte granules too.  Two steps cost 1.2 x (u + p) + v + w = 4.4 field passes instead of 6.
+// The two outputs must be buffers distinct from BOTH inputs and from each other: w may not go into p's buffer -- windows
+// overlap, so another workgroup still reads p cells on its discarded rim after their owner has stored w there.
 #pragma once
 #include "apply_march.hpp"
 
@@ -65,12 +74,21 @@ struct March2Geom {
 // Star footprints of input 0 up to radius 2 per axis (7-point family, 13-point 4th-order operators); inputs 1.. are read at
 // the centre only and are the same field at every stage (coefficient fields): each keeps a queue of the (NS-1) R0 + 1 planes
 // between the first stage's plane and the last one's.
-template <class Body, class T, int NIN, class FP, int NS, int RJ, int WJ, int MINW>
-__global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Params<T, NIN> P, Body body) {
+// leapfrog form: March2Params plus the buffer of stage 1's result
+template <class T, int NIN>
+struct Leapfrog2Params : March2Params<T, NIN> {
+  T* out_v;
+};
+
+// LF = the leapfrog form described at the top of this file (P is then a Leapfrog2Params)
+template <class Body, class T, int NIN, class FP, int NS, int RJ, int WJ, int MINW, bool LF = false>
+__global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(
+    std::conditional_t<LF, Leapfrog2Params<T, NIN>, March2Params<T, NIN>> P, Body body) {
   using V = typename Vec16<T>::type;
   using GM = March2Geom<T, FP, NS>;
   constexpr int VK = GM::VK, R0 = GM::R0, R1 = GM::R1, R2 = GM::R2, NP = 2 * R0 + 1;
   static_assert(NS >= 2 && NS <= 3, "two or three applies per pass");
+  static_assert(!LF || (NS == 2 && NIN >= 2), "leapfrog: two stages, input 1 = the previous state");
   constexpr int TJ = RJ * WJ;                 // window rows
   constexpr int MK = GM::MK, SPAN = GM::SPAN;
   static_assert(R0 >= 1 && R0 <= 2 && R1 >= 1 && R1 <= 2 && R2 >= 1 && R2 <= 2 && !FP::BOX && FP::HALO_MASK == 1u, "star of input 0, radius 1..2");
@@ -131,9 +149,10 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
   const bool lane_keep = k0 >= kw + MK && k0 < kw + SPAN - MK && k0 >= 0 && k0 < P.N2;
 
   // one stage: `pl` = the 2 R0 + 1 planes of the stage's input (own rows), centre at pl[R0]; `above` / `below` the R1 rows
-  // outside the wave's own rows on the centre plane; `fx` the centre-only inputs' rows on the stage's plane
-  auto stage = [&](const V(&pl)[NP][RJ], const V(&above)[R1], const V(&below)[R1], const V(&fx)[NF][NQ][RJ], auto qc, int32_t ip,
-                   V(&res)[RJ]) {
+  // outside the wave's own rows on the centre plane; `fx` the centre-only inputs' rows on the stage's plane; `xp` (leapfrog
+  // form only) the previous state's rows on the stage's plane, which take input 1's place
+  auto stage = [&](const V(&pl)[NP][RJ], const V(&above)[R1], const V(&below)[R1], const V(&fx)[NF][NQ][RJ], const V(&xp)[RJ],
+                   auto qc, int32_t ip, V(&res)[RJ]) {
     constexpr int q = decltype(qc)::value;
     V ring[1][NP][RJ + 2 * R1];
     T lft[1][1][RJ + 2 * R1][R2], rgt[1][1][RJ + 2 * R1][R2];
@@ -149,7 +168,11 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
         lft[0][0][r + R1][x] = from_prev<true>(pl[R0][r][VK - dl], pl[R0][r][0], lane);
         rgt[0][0][r + R1][x] = from_next<true>(pl[R0][r][dr - 1], pl[R0][r][VK - 1], lane);
       });
-      static_for<NIN>([&](auto nc) { constexpr int n = nc; if constexpr (n > 0) pt[n][r] = fx[n - 1][q][r]; });
+      static_for<NIN>([&](auto nc) {
+        constexpr int n = nc;
+        if constexpr (LF && n == 1) pt[n][r] = xp[r];
+        else if constexpr (n > 0) pt[n][r] = fx[n - 1][q][r];
+      });
     });
     static_for<R1>([&](auto xc) {
       constexpr int x = xc;
@@ -175,7 +198,8 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
   // ---- register state.  ring[k] holds the 2 R0 + 1 newest planes of v_k that stage k+1 reads: at step i planes
   // i + (NS-k) R0 - 2 R0 .. i + (NS-k) R0, the centre of stage k+1 in the middle; ring[k][2 R0] is written by stage k in the
   // same step (k = 0: by the load issued one step earlier).  fx[n][q]: plane i + q R0 ... of centre-only input n+1: slot q is
-  // the plane of the stage that works q R0 planes ahead of the last one.
+  // the plane of the stage that works q R0 planes ahead of the last one.  Leapfrog form: input 1 (the previous state p) is
+  // read by stage 1 only, so of its queue only the newest slot fx[0][NQ - 1] = p(i + R0) and the plane in flight exist.
   V ring[NS][NP][RJ];
   V un[RJ];                                // u(i + NS R0 + 1) in flight
   V fx[NF][NQ][RJ], fn[NF][RJ];            // centre-only inputs: queue and the plane in flight
@@ -186,7 +210,8 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
   if constexpr (NIN > 1) {
     static_for<NIN - 1>([&](auto nc) {
       constexpr int n = nc;
-      static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; load_plane(P.in[n + 1], i0 + q, fx[n][q]); });
+      if constexpr (!(LF && n == 0))
+        static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; load_plane(P.in[n + 1], i0 + q, fx[n][q]); });
       load_plane(P.in[n + 1], i0 + NQ - 1, fn[n]);
     });
   }
@@ -228,8 +253,10 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
     static_for<NS>([&](auto kc) {
       constexpr int k = kc;                // stage k + 1: v_{k+1}(i + (NS - k - 1) R0) from ring[k]
       constexpr int q = (NS - k - 1) * R0;
-      if constexpr (k + 1 < NS) stage(ring[k], above[k], below[k], fx, std::integral_constant<int, q>{}, i + q, ring[k + 1][NP - 1]);
-      else stage(ring[k], above[k], below[k], fx, std::integral_constant<int, 0>{}, i, wres);
+      // leapfrog: stage 1 reads p(i + R0); stage 2's previous state is stage 1's input 0 on its own plane: u(i) = ring[0][0]
+      const V(&xp)[RJ] = (LF && k == 0) ? fx[0][NQ - 1] : ring[0][0];
+      if constexpr (k + 1 < NS) stage(ring[k], above[k], below[k], fx, xp, std::integral_constant<int, q>{}, i + q, ring[k + 1][NP - 1]);
+      else stage(ring[k], above[k], below[k], fx, xp, std::integral_constant<int, 0>{}, i, wres);
     });
     if (i >= ib && lane_keep) {
       char* obase = reinterpret_cast<char*>(P.out) + (int64_t)i * plane_b;
@@ -238,6 +265,17 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
         if (row_keep[r]) __builtin_nontemporal_store(wres[r], reinterpret_cast<V*>(obase + (rowb[r] + lane_b)));
       });
     }
+    if constexpr (LF) {
+      // v(i + R0), this step's stage-1 result: valid R cells inside the window, so on every kept cell (2 R inside); the
+      // warm-up steps cover planes ib .. ib + R0 - 1
+      if (i + R0 >= ib && i + R0 < ie && lane_keep) {
+        char* obase = reinterpret_cast<char*>(P.out_v) + (int64_t)(i + R0) * plane_b;
+        static_for<RJ>([&](auto rc) {
+          constexpr int r = rc;
+          if (row_keep[r]) __builtin_nontemporal_store(ring[1][NP - 1][r], reinterpret_cast<V*>(obase + (rowb[r] + lane_b)));
+        });
+      }
+    }
     static_for<NS>([&](auto kc) {
       constexpr int k = kc;
       static_for<NP - 1>([&](auto pc) { constexpr int pp = pc; static_for<RJ>([&](auto rc) { constexpr int r = rc; ring[k][pp][r] = ring[k][pp + 1][r]; }); });
@@ -245,10 +283,12 @@ __global__ __launch_bounds__(kWave* WJ, MINW) void neptune_apply_march2(March2Pa
     if constexpr (NIN > 1)
       static_for<NIN - 1>([&](auto nc) {
         constexpr int n = nc;
-        static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; static_for<RJ>([&](auto rc) { constexpr int r = rc; fx[n][q][r] = fx[n][q + 1][r]; }); });
+        if constexpr (!(LF && n == 0))
+          static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; static_for<RJ>([&](auto rc) { constexpr int r = rc; fx[n][q][r] = fx[n][q + 1][r]; }); });
       });
   }
 }
+
 
 // ---- rank 2 ------------------------------------------------------------------------------------------------
 // The same idea for 2-D fields (d0, d1) -> (I, K): a wave marches DOWN THE ROWS of its column window (one wave span wide,
@@ -273,12 +313,17 @@ constexpr bool march2_rank2_footprint() {
   return FP::MARCH_OK && !FP::BOX && FP::HALO_MASK == 1u && FP::R0 >= 1 && FP::R0 <= 2 && FP::R1 == 0 && FP::R2 >= 1 && FP::R2 <= 2;
 }
 
-template <class Body, class T, int NIN, class FP, int NS, int PF>
-__global__ __launch_bounds__(256) void neptune_apply_march2_rank2(March2R2Params P, Body body) {
+struct Leapfrog2R2Params : March2R2Params {
+  void* out_v;             // leapfrog form: where stage 1's result goes
+};
+
+template <class Body, class T, int NIN, class FP, int NS, int PF, bool LF = false>
+__global__ __launch_bounds__(256) void neptune_apply_march2_rank2(std::conditional_t<LF, Leapfrog2R2Params, March2R2Params> P, Body body) {
   using V = typename Vec16<T>::type;
   using GM = March2Geom<T, FP, NS>;
   constexpr int VK = GM::VK, R0 = GM::R0, R2 = GM::R2, NP = 2 * R0 + 1, MK = GM::MK, SPAN = GM::SPAN, KEEPK = GM::KEEPK;
   static_assert(NS >= 2 && NS <= 3 && march2_rank2_footprint<FP>() && R2 <= VK, "window constants");
+  static_assert(!LF || (NS == 2 && NIN >= 2), "leapfrog: two stages, input 1 = the previous state");
   constexpr int NQ = (NS - 1) * R0 + 1;       // rows of a centre-only input between the first stage's row and the last one's
   constexpr int NF = NIN > 1 ? NIN - 1 : 1;
   const int lane = threadIdx.x & (kWave - 1);
@@ -299,7 +344,7 @@ __global__ __launch_bounds__(256) void neptune_apply_march2_rank2(March2R2Params
   static_for<VK>([&](auto ec) { constexpr int e = ec; in_k[e] = (k0 + e) >= P.plb[1] && (k0 + e) < P.pub[1]; });
   const bool lane_keep = k0 >= kw + MK && k0 < kw + SPAN - MK && k0 >= 0 && k0 < P.N1;
 
-  auto stage = [&](const V(&pl)[NP], const V(&fx)[NF][NQ], auto qc, int32_t ip) -> V {
+  auto stage = [&](const V(&pl)[NP], const V(&fx)[NF][NQ], const V& xp, auto qc, int32_t ip) -> V {
     constexpr int q = decltype(qc)::value;
     V ring[1][NP][1];
     T lft[1][1][1][R2], rgt[1][1][1][R2];
@@ -311,7 +356,11 @@ __global__ __launch_bounds__(256) void neptune_apply_march2_rank2(March2R2Params
       lft[0][0][0][x] = from_prev<true>(pl[R0][VK - dl], pl[R0][0], lane);
       rgt[0][0][0][x] = from_next<true>(pl[R0][dr - 1], pl[R0][VK - 1], lane);
     });
-    static_for<NIN>([&](auto nc) { constexpr int n = nc; if constexpr (n > 0) pt[n][0] = fx[n - 1][q]; });
+    static_for<NIN>([&](auto nc) {
+      constexpr int n = nc;
+      if constexpr (LF && n == 1) pt[n][0] = xp;       // leapfrog: the previous state on the stage's row
+      else if constexpr (n > 0) pt[n][0] = fx[n - 1][q];
+    });
     const bool in_i = ip >= P.plb[0] && ip < P.pub[0];
     const int64_t li = (int64_t)ip + P.olb[0];
     V res;
@@ -336,7 +385,7 @@ __global__ __launch_bounds__(256) void neptune_apply_march2_rank2(March2R2Params
   if constexpr (NIN > 1) {
     static_for<NIN - 1>([&](auto nc) {
       constexpr int n = nc;
-      static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; fx[n][q] = load_row(n + 1, i0 + q); });
+      if constexpr (!(LF && n == 0)) static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; fx[n][q] = load_row(n + 1, i0 + q); });
       static_for<PF>([&](auto dc) { constexpr int d = dc; fn[n][d] = load_row(n + 1, i0 + NQ - 1 + d); });
     });
   }
@@ -353,13 +402,21 @@ __global__ __launch_bounds__(256) void neptune_apply_march2_rank2(March2R2Params
     static_for<NS>([&](auto kc2) {
       constexpr int k = kc2;
       constexpr int q = (NS - k - 1) * R0;
-      if constexpr (k + 1 < NS) ring[k + 1][NP - 1] = stage(ring[k], fx, std::integral_constant<int, q>{}, i + q);
-      else w = stage(ring[k], fx, std::integral_constant<int, 0>{}, i);
+      const V& xp = (LF && k == 0) ? fx[0][NQ - 1] : ring[0][0];   // leapfrog: p(i + R0) for stage 1, u(i) for stage 2
+      if constexpr (k + 1 < NS) ring[k + 1][NP - 1] = stage(ring[k], fx, xp, std::integral_constant<int, q>{}, i + q);
+      else w = stage(ring[k], fx, xp, std::integral_constant<int, 0>{}, i);
     });
     if (i >= ib && lane_keep) __builtin_nontemporal_store(w, reinterpret_cast<V*>(out + (int64_t)i * P.N1 + kc));
+    if constexpr (LF) {
+      if (i + R0 >= ib && i + R0 < ie && lane_keep)
+        __builtin_nontemporal_store(ring[1][NP - 1], reinterpret_cast<V*>(static_cast<T*>(P.out_v) + (int64_t)(i + R0) * P.N1 + kc));
+    }
     static_for<NS>([&](auto kc2) { constexpr int k = kc2; static_for<NP - 1>([&](auto pc) { constexpr int pp = pc; ring[k][pp] = ring[k][pp + 1]; }); });
     if constexpr (NIN > 1)
-      static_for<NIN - 1>([&](auto nc) { constexpr int n = nc; static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; fx[n][q] = fx[n][q + 1]; }); });
+      static_for<NIN - 1>([&](auto nc) {
+        constexpr int n = nc;
+        if constexpr (!(LF && n == 0)) static_for<NQ - 1>([&](auto qc) { constexpr int q = qc; fx[n][q] = fx[n][q + 1]; });
+      });
   };
   for (int32_t i = i0; i < ie; i += PF) {
     static_for<PF>([&](auto phc) {
@@ -368,6 +425,7 @@ __global__ __launch_bounds__(256) void neptune_apply_march2_rank2(March2R2Params
     });
   }
 }
+
 
 template <class T, int NIN, class FP>
 inline bool march2_rank2_eligible(const neptune_hip_apply_geom_t* g, const void* const* in, const void* out) {
@@ -390,12 +448,14 @@ inline bool march2_rank2_eligible(const neptune_hip_apply_geom_t* g, const void*
   return true;
 }
 
-template <class Body, class T, int NIN, class FP, int NS>
+// out_v != nullptr: the leapfrog form (NS = 2; out = w, out_v = v), see leapfrog2_eligible
+template <class Body, class T, int NIN, class FP, int NS, bool LF = false>
 inline int launch_march2_rank2(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, hipStream_t stream,
-                               int chunk_req) {
+                               int chunk_req, void* out_v = nullptr) {
   if (!march2_rank2_eligible<T, NIN, FP>(g, in, out) || geom_bounds_empty(g)) return NEPTUNE_HIP_EUNSUPPORTED;
   constexpr int KEEPK = March2Geom<T, FP, NS>::KEEPK, PF = 4;
-  March2R2Params P{};
+  std::conditional_t<LF, Leapfrog2R2Params, March2R2Params> P{};
+  if constexpr (LF) P.out_v = out_v;
   for (int k = 0; k < NIN; ++k) P.in[k] = in[k];
   P.out = out;
   P.N0 = (int32_t)(g->out_ub[0] - g->out_lb[0]);
@@ -418,7 +478,7 @@ inline int launch_march2_rank2(const Body& body, const neptune_hip_apply_geom_t*
   const int64_t waves = (int64_t)P.nK * ((rows + chunk - 1) / chunk);
   const int64_t blocks = (waves + 3) / 4;
   if (blocks <= 0 || blocks > 0x7fffffffLL) return NEPTUNE_HIP_EUNSUPPORTED;
-  hipLaunchKernelGGL((neptune_apply_march2_rank2<Body, T, NIN, FP, NS, PF>), dim3((uint32_t)blocks), dim3(256), 0, stream, P, body);
+  hipLaunchKernelGGL((neptune_apply_march2_rank2<Body, T, NIN, FP, NS, PF, LF>), dim3((uint32_t)blocks), dim3(256), 0, stream, P, body);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   return NEPTUNE_HIP_OK;
 }
@@ -453,12 +513,13 @@ inline bool march2_eligible(const neptune_hip_apply_geom_t* g, const void* const
   return true;
 }
 
-template <class Body, class T, int NIN, class FP, int NS, int RJ, int WJ, int MINW>
+template <class Body, class T, int NIN, class FP, int NS, int RJ, int WJ, int MINW, bool LF = false>
 inline int launch_march2_shape(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, hipStream_t stream,
-                               int chunk_req) {
+                               int chunk_req, void* out_v = nullptr) {
   using GM = March2Geom<T, FP, NS>;
   constexpr int KEEPJ = RJ * WJ - 2 * GM::MJ, KEEPK = GM::KEEPK;
-  March2Params<T, NIN> P{};
+  std::conditional_t<LF, Leapfrog2Params<T, NIN>, March2Params<T, NIN>> P{};
+  if constexpr (LF) P.out_v = static_cast<T*>(out_v);
   for (int k = 0; k < NIN; ++k) P.in[k] = static_cast<const T*>(in[k]);
   P.out = static_cast<T*>(out);
   P.N0 = (int32_t)(g->out_ub[0] - g->out_lb[0]);
@@ -482,8 +543,8 @@ inline int launch_march2_shape(const Body& body, const neptune_hip_apply_geom_t*
   P.chunk = (int32_t)chunk;
   const int64_t blocks = (int64_t)P.nJ * P.nK * ((planes + chunk - 1) / chunk);
   if (blocks <= 0 || blocks > 0x7fffffffLL) return NEPTUNE_HIP_EUNSUPPORTED;
-  hipLaunchKernelGGL((neptune_apply_march2<Body, T, NIN, FP, NS, RJ, WJ, MINW>), dim3((uint32_t)blocks), dim3(kWave * WJ), 0, stream, P,
-                     body);
+  hipLaunchKernelGGL((neptune_apply_march2<Body, T, NIN, FP, NS, RJ, WJ, MINW, LF>), dim3((uint32_t)blocks), dim3(kWave * WJ), 0, stream,
+                     P, body);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   return NEPTUNE_HIP_OK;
 }
@@ -579,6 +640,68 @@ template <class Body, class T, int RANK, int NIN, class FP>
 inline int launch_apply_thrice(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out,
                                hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
   return launch_apply_chain<Body, T, RANK, NIN, FP, 3>(body, g, in, out, stream, cfg);
+}
+
+// ---- leapfrog pairs ----------------------------------------------------------------------------------------
+// in[0] = u(n), in[1] = u(n-1), in[2..] = centre-only inputs; out_v = u(n+1), out_w = u(n+2).  On top of what the chain
+// kernel asks of a geometry: the two outputs are buffers of their own -- none of (in[0], in[1], out_v, out_w) and none of
+// the further inputs overlaps an output (see the header comment: w may not go into p's buffer).
+// footprints the leapfrog form is built for.  Rank 3 stops where the window needs scratch memory: radius 2 with a coefficient
+// field, radius 1 with more than one (rank 2 keeps rows, not planes, per lane: 170 VGPRs at radius 2 with a coefficient).
+// csrc/lowering/emit_hip.cpp (leapfrog_capable) exports <tag>__geomL2 for exactly these.
+template <int RANK, int NIN, class FP>
+constexpr bool leapfrog2_footprint() {
+  if constexpr (RANK == 3) return march2_footprint<FP>() && NIN <= ((FP::R0 > 1 || FP::R1 > 1 || FP::R2 > 1) ? 2 : 3);
+  else if constexpr (RANK == 2) return march2_rank2_footprint<FP>();
+  else return false;
+}
+template <class T, int NIN>
+inline bool leapfrog2_buffers_ok(const neptune_hip_apply_geom_t* g, const void* const* in, const void* out_v, const void* out_w) {
+  if (!out_v || !out_w || (uintptr_t)out_v % 64 != 0) return false;
+  const size_t bytes = geom_box_bytes(g->out_lb, g->out_ub, g->rank, sizeof(T));
+  if (buffers_overlap(out_v, bytes, out_w, bytes)) return false;
+  for (int k = 0; k < NIN; ++k)
+    if (buffers_overlap(in[k], bytes, out_v, bytes) || buffers_overlap(in[k], bytes, out_w, bytes)) return false;
+  return true;
+}
+
+// what a lowered apply's <tag>__geomL2 calls: two steps of the two-level scheme `body` in one pass, or
+// NEPTUNE_HIP_EUNSUPPORTED -- nothing launched -- when the footprint or the geometry does not qualify.  `FP` is the apply's
+// footprint: input 0 a star up to radius 2, every other input read at the centre only (FP::HALO_MASK == 1).
+template <class Body, class T, int RANK, int NIN, class FP>
+inline int launch_apply_leapfrog2(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out_v, void* out_w,
+                                  hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
+  static_assert(NIN >= 2, "a two-level scheme has the previous state as input 1");
+  if constexpr (leapfrog2_footprint<RANK, NIN, FP>()) {
+    if (!g || !in || !out_v || !out_w) return NEPTUNE_HIP_EINVAL;
+    for (int k = 0; k < NIN; ++k)
+      if (!in[k]) return NEPTUNE_HIP_EINVAL;
+    if (cfg && (cfg->kernel == NEPTUNE_HIP_KERNEL_DIRECT || cfg->variant >= 0)) return NEPTUNE_HIP_EUNSUPPORTED;   // an explicit tile was asked for
+    const int rc = geom_validate(g);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    if (g->num_inputs != NIN || !leapfrog2_buffers_ok<T, NIN>(g, in, out_v, out_w)) return NEPTUNE_HIP_EUNSUPPORTED;
+    const int chunk = cfg ? cfg->chunk : 0;
+    if constexpr (RANK == 3) {
+      if (!march2_eligible<T, NIN, FP>(g, in, out_w) || geom_bounds_empty(g)) return NEPTUNE_HIP_EUNSUPPORTED;
+      // Windows (rows per lane x waves) by what a gfx950 cross-compile of the 7- / 13-point wave step allocates
+      // (-Rpass-analysis=kernel-resource-usage, fp64 and fp32): the chain kernel's 3x16 window spills here (128 VGPRs +
+      // 100 bytes of scratch per lane: the previous state adds two planes of rows), so
+      //   radius 1, no further input: 3x12 (154 VGPRs; 2x16: 110, 4x8: 196, 5x8: 238, 6x8 spills)
+      //   radius 1, one coefficient:  4x8  (242 VGPRs; 2x16, 3x12 and 5x8 spill)
+      //   radius 2, no further input: 3x8  (216 VGPRs; with a coefficient field it needs scratch: refused, see
+      //                                     leapfrog2_footprint)
+      if constexpr (FP::R0 > 1 || FP::R1 > 1 || FP::R2 > 1)
+        return launch_march2_shape<Body, T, NIN, FP, 2, 3, 8, 1, true>(body, g, in, out_w, stream, chunk, out_v);
+      else if constexpr (NIN == 2)
+        return launch_march2_shape<Body, T, NIN, FP, 2, 3, 12, 1, true>(body, g, in, out_w, stream, chunk, out_v);
+      else
+        return launch_march2_shape<Body, T, NIN, FP, 2, 4, 8, 1, true>(body, g, in, out_w, stream, chunk, out_v);
+    } else {
+      return launch_march2_rank2<Body, T, NIN, FP, 2, true>(body, g, in, out_w, stream, chunk, out_v);
+    }
+  } else {
+    return NEPTUNE_HIP_EUNSUPPORTED;
+  }
 }
 
 }  // namespace neptune_hip

@@ -70,7 +70,8 @@ std::string report_json(const LowerInfo& info) {
       << ", \"inputs\": " << a.num_inputs << ", \"kernel\": \"" << (a.fused_reduce ? "reduce" : (a.march ? "march" : "direct"))
       << "\", \"shape\": \""
       << (a.halo_input < 0 ? "pointwise" : (a.box ? "box" : "star")) << "\", \"elem\": \"" << a.elem << "\", \"halo0\": " << a.halo0
-      << ", \"geom_symbol\": \"" << a.geom_symbol << "\", \"exact\": " << (a.exact ? "true" : "false") << "}";
+      << ", \"geom_symbol\": \"" << a.geom_symbol << "\", \"exact\": " << (a.exact ? "true" : "false")
+      << ", \"leapfrog_symbol\": \"" << a.leapfrog_symbol << "\"}";
   }
   o << "]}";
   return o.str();

@@ -652,6 +652,37 @@ struct Emitter {
                  << "extern \"C\" int " << sym << "_variants(int rank) { return neptune_hip::march_variant_count(rank); }\n\n";
   }
 
+  // A two-level scheme u(n+1) = B(u(n), u(n-1), c...) the chain kernel can step twice per pass: input 0 a star of radius
+  // 1..2 per axis (what march2_footprint / march2_rank2_footprint of csrc/kernels/apply_march2.hpp take), input 1 -- the
+  // previous state -- of input 0's and the result's element type, every input but input 0 read at the centre only.
+  static bool leapfrog_capable(const Footprint& fp, const Op& op) {
+    const int nin = (int)op.operands.size();
+    if (nin < 2 || fp.lead > 0 || fp.nd || !fp.march_ok || fp.box || fp.halo_mask != 1u) return false;
+    const Type& res = op.types[nin];
+    if (op.types[0].elem != res.elem || op.types[1].elem != res.elem) return false;
+    auto in12 = [](int r) { return r >= 1 && r <= 2; };
+    // rank 3 stops where the kernel's window would need scratch memory (leapfrog2_footprint): radius 2 takes no further
+    // input, radius 1 one
+    if (fp.rank == 3) return in12(fp.R[0]) && in12(fp.R[1]) && in12(fp.R[2]) && nin <= (std::max(fp.R[0], std::max(fp.R[1], fp.R[2])) > 1 ? 2 : 3);
+    if (fp.rank == 2) return in12(fp.R[0]) && fp.R[1] == 0 && in12(fp.R[2]);
+    return false;
+  }
+
+  // <sym>L2: one leapfrog pair of that apply (neptune_hip_leapfrog2_fn, include/neptune_hip.h)
+  void emit_leapfrog_entry(const std::string& sym, const std::string& reach, const std::string& body, const std::string& T, int rank,
+                           int nin, const std::string& fp) {
+    geom_entries << "// two steps of this two-level scheme in one pass over HBM (csrc/kernels/apply_march2.hpp, leapfrog form):\n"
+                 << "// out_v = B(in[0], in[1], in[2..]), out_w = B(out_v, in[0], in[2..]); NEPTUNE_HIP_EUNSUPPORTED when the geometry or\n"
+                 << "// the buffers do not qualify (neptune_hip_step_loop_leapfrog)\n"
+                 << "extern \"C\" int " << sym << "L2(const neptune_hip_apply_geom_t* g, const void* const* in, void* out_v, void* out_w,\n"
+                 << "    void* stream, const neptune_hip_launch_cfg_t* cfg) {\n"
+                 << "  if (!g || !in || !out_v || !out_w) return NEPTUNE_HIP_EINVAL;\n"
+                 << "  const int rc = neptune_hip::geom_check_radius(g, " << reach << ");\n"
+                 << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
+                 << "  return neptune_hip::launch_apply_leapfrog2<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
+                 << ">(" << body << "{}, g, in, out_v, out_w, (hipStream_t)stream, cfg);\n}\n\n";
+  }
+
   void emit_alias(FnState& s, const Op& op) {
     s.vals[op.results[0]].root_arg = s.vals[op.operands[0]].root_arg;
     const bool temp = op.types[1].is_tempish();
@@ -721,6 +752,10 @@ struct Emitter {
       ApplyInfo ai = apply_info(s, tag, fp, fp.rank, res.elem, halo0_of(fp));
       ai.geom_symbol = tag + "__geom";
       emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
+      if (leapfrog_capable(fp, op)) {
+        ai.leapfrog_symbol = ai.geom_symbol + "L2";
+        emit_leapfrog_entry(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
+      }
       info.applies.push_back(ai);
     }
     return true;

@@ -77,6 +77,48 @@ def step_loop(body, a: DeviceField, b: DeviceField, bounds: Box, steps: int, oth
     return b if steps % 2 else a
 
 
+def _as_field(x) -> DeviceField:
+    """a DeviceField as it is; a contiguous torch CUDA tensor as a field with a zero-based box"""
+    if isinstance(x, DeviceField):
+        return x
+    import torch
+    dtype = {torch.float64: _capi.F64, torch.float32: _capi.F32}[x.dtype]
+    return DeviceField((0,) * x.dim(), tuple(x.shape), dtype, x)
+
+
+def leapfrog_launch_counts():
+    """(single launches, pair launches) of the last step_loop_leapfrog call, replays of its cached graph included"""
+    singles, pairs = C.c_int64(0), C.c_int64(0)
+    _capi.load().neptune_hip_leapfrog_launch_counts(C.byref(singles), C.byref(pairs))
+    return singles.value, pairs.value
+
+
+def step_loop_leapfrog(entry, geom, fields: Sequence, extra: Sequence = (), steps: int = 0,
+                       cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
+    """`steps` steps of the two-level scheme u(n+1) = F(u(n), u(n-1), extra...) that `entry` computes (a lowered apply's
+    geometry-level entry whose inputs are: state, previous state, extra...), on rotating fields (torch CUDA tensors or
+    DeviceFields): fields[0] = u(0), fields[1] = u(-1), fields[2] = scratch, and optionally fields[3] = a second scratch,
+    which lets the loop take two steps per pass over HBM where the entry has a pair form (GeomEntry.fn_leapfrog2) and
+    pairs measure faster.  `geom`: the apply's geometry (geom_for([u, u_prev, *extra], scratch, bounds)).  Long runs replay
+    a cached hipGraph.  Asynchronous; -> (cur, prev): the indices into `fields` that hold u(steps) and u(steps - 1).
+    leapfrog_launch_counts() tells which grouping ran."""
+    lib = _capi.load()
+    fs = [_as_field(f) for f in fields]
+    ex = [_as_field(f) for f in extra]
+    if len(fs) not in (3, 4):
+        raise ValueError("step_loop_leapfrog: three fields (single launches) or four (pairs)")
+    farr = (C.c_void_p * 4)(*([f.ptr for f in fs] + [None] * (4 - len(fs))))
+    earr = (C.c_void_p * max(len(ex), 1))(*[f.ptr for f in ex])
+    st = current_stream_ptr() if stream is None else stream
+    fn2 = getattr(entry, "fn_leapfrog2", None)
+    cur, prev = C.c_int(0), C.c_int(1)
+    rc = lib.neptune_hip_step_loop_leapfrog(C.cast(entry.fn, C.c_void_p), C.cast(fn2, C.c_void_p) if fn2 is not None else None,
+                                            C.byref(geom), farr, earr, len(ex), steps, st,
+                                            C.byref(cfg) if cfg is not None else None, C.byref(cur), C.byref(prev))
+    _capi.check(rc, "neptune_hip_step_loop_leapfrog")
+    return cur.value, prev.value
+
+
 def apply_twice(body, inp: DeviceField, out: DeviceField, bounds: Box, region: Optional[Box] = None,
                 cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None, applies: int = 2) -> bool:
     """out = A(A(inp)) -- or A(A(A(inp))) with applies=3 -- in ONE pass over HBM for apply A (a built-in body id or a

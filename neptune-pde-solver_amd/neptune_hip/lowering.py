@@ -173,6 +173,14 @@ class GeomEntry:
             if f is not None:
                 f.restype, f.argtypes = C.c_int, self.fn.argtypes
 
+        # a two-level scheme's pair entry (neptune_hip_leapfrog2_fn: two steps per pass, both states stored), or None
+        sym = info.get("leapfrog_symbol") or ""
+        self.fn_leapfrog2 = getattr(module.lib, sym) if sym else None
+        if self.fn_leapfrog2 is not None:
+            self.fn_leapfrog2.restype = C.c_int
+            self.fn_leapfrog2.argtypes = [C.POINTER(_capi.ApplyGeom), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(_capi.LaunchCfg)]
+
     def __call__(self, geom, in_array, out_ptr, stream, cfg=None) -> int:
         return self.fn(C.byref(geom), in_array, out_ptr, stream, C.byref(cfg) if cfg is not None else None)
 

@@ -33,9 +33,9 @@ def short(name):
         return ("neptune_apply_planes[" if "apply_planes<" in name else "neptune_apply_plane[") + f"pln_rj{a[0]}_wj{a[1]}_wk{a[2]}_pf{a[5]}]"
     if "neptune_apply_plane" in name:
         return "neptune_apply_plane" + ("s" if "apply_planes<" in name else "")
-    m = re.search(r"neptune_apply_march2<.*?, (\d+), (\d+), \d+>", name)
-    if m:
-        return f"neptune_apply_march2[rows{m.group(1)}x{m.group(2)}]"
+    m = re.search(r"neptune_apply_march2<.*?, (\d+), (\d+), \d+, (\w+)>", name)
+    if m:   # the last argument: the leapfrog form (two steps of a two-level scheme, both stored)
+        return f"neptune_apply_march2[rows{m.group(1)}x{m.group(2)}{'_leapfrog' if m.group(3) in ('true', '1') else ''}]"
     for key in ("neptune_apply_direct", "neptune_apply_rows", "neptune_reduce_apply_vec", "neptune_reduce_apply", "neptune_fill_hash",
                 "neptune_copy16", "neptune_store_box", "neptune_vec_update"):
         if key in name:
