@@ -427,6 +427,12 @@ void neptune_hip_tune_stats(int64_t out[3]);
  * (chunk as launched, never 0 for the march kernel).  Launchers call _note_launch; returns 0 if nothing was launched yet. */
 void neptune_hip_note_launch(int kernel, int variant, int chunk);
 int neptune_hip_last_launch(neptune_hip_launch_cfg_t *out);
+/* Groups of sibling applies over shared inputs: counters of this process.  *fused = groups that ran as ONE
+ * multi-output launch; *members_single = member applies of a group that ran as launches of their own (the plan has no
+ * group form for the union footprint, a slab view is in force, or NEPTUNE_HIP_NO_GROUPS=1).  Lowered modules call
+ * _note_group(fused, members) once per group they run. */
+void neptune_hip_note_group(int fused, int members);
+void neptune_hip_group_launch_counts(int64_t *fused, int64_t *members_single);
 
 /* Plain 16-byte-per-lane device copy, timed the same way: the measured HBM ceiling.
  * mode selects the copy kernel shape (0 .. neptune_hip_copy_mode_count()-1: grid-stride, or

@@ -86,6 +86,59 @@ struct OutsideOf<Body, T, std::void_t<decltype(std::declval<const Body&>().outsi
   static __device__ __forceinline__ T apply(const Body& b, T through) { return b.outside(through); }
 };
 
+// ---- groups: sibling applies over shared inputs, one launch, one result per member --------------------
+// A kernel asks ResultsOf<Body> how many results a body has (1 unless the body says NOUT).  A GroupBody carries the
+// member bodies, one result pointer per member and, per member, the map from the member's input indices to the
+// group's (the union of the members' operands): member bodies stay exactly what the lowering emits for a single
+// apply, MappedAcc renumbers their accesses.  Member m's copy-through source is ITS input 0 -- group input
+// THROUGH -- whose box equals the result's, so "input 0 at the same physical index" is that input's centre access.
+template <class Body, class = void>
+struct ResultsOf { static constexpr int value = 1; };
+template <class Body>
+struct ResultsOf<Body, std::void_t<decltype(Body::NOUT)>> { static constexpr int value = Body::NOUT; };
+
+template <class A, class G>
+struct MappedAcc {
+  const A& a;
+  template <int IN, int... O>
+  __device__ __forceinline__ auto get() const { return a.template get<G::map(IN), O...>(); }
+  template <int D>
+  __device__ __forceinline__ int64_t idx() const { return a.template idx<D>(); }
+};
+template <class Body_, class FP_, int NIN_, int M0 = 0, int M1 = 1, int M2 = 2, int M3 = 3>
+struct GroupMember {
+  using Body = Body_;
+  using FP = FP_;
+  static constexpr int NIN = NIN_, THROUGH = M0;
+  static constexpr int map(int k) { return k == 0 ? M0 : (k == 1 ? M1 : (k == 2 ? M2 : M3)); }
+  Body body;
+};
+struct NoMember {};
+template <class T, class G0, class G1, class G2 = NoMember, class G3 = NoMember>
+struct GroupBody {
+  static constexpr int NOUT = 2 + (std::is_same<G2, NoMember>::value ? 0 : 1) + (std::is_same<G3, NoMember>::value ? 0 : 1);
+  static_assert(!std::is_same<G2, NoMember>::value || std::is_same<G3, NoMember>::value, "members are listed without gaps");
+  G0 m0;
+  G1 m1;
+  G2 m2;
+  G3 m3;
+  T* out[4];
+  template <int M> using Member = std::conditional_t<M == 0, G0, std::conditional_t<M == 1, G1, std::conditional_t<M == 2, G2, G3>>>;
+  template <int M>
+  __host__ __device__ __forceinline__ const Member<M>& member() const {
+    if constexpr (M == 0) return m0;
+    else if constexpr (M == 1) return m1;
+    else if constexpr (M == 2) return m2;
+    else return m3;
+  }
+  template <int M, class A>
+  __device__ __forceinline__ T eval(const A& a) const { return member<M>().body(MappedAcc<A, Member<M>>{a}); }
+  template <int M, class A>
+  __device__ __forceinline__ T through(const A& a) const { return a.template get<Member<M>::THROUGH>(); }
+  template <int M>
+  __device__ __forceinline__ T outside(T thr) const { return OutsideOf<typename Member<M>::Body, T>::apply(member<M>().body, thr); }
+};
+
 // Rank mapping onto the kernel's (I, J, K) axes.  K is always the contiguous last dim, I the
 // slowest.  rank 3: (d0,d1,d2) -> (I,J,K); rank 2: (d0,d1) -> (I,K), J has extent 1;
 // rank 1: (d0) -> (K), I and J have extent 1.

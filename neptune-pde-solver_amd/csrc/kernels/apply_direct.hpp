@@ -73,11 +73,21 @@ __global__ __launch_bounds__(256) void neptune_apply_direct(DirectParams<T, NIN>
     const int64_t p = acc.q[a] + P.olb[a];
     inside = inside && p >= P.lb[a] && p < P.ub[a];
   }
+  if constexpr (ResultsOf<Body>::value > 1) {
+    // a group (apply_common.hpp GroupBody): one result per member, each against its own copy-through source
+    static_for<ResultsOf<Body>::value>([&](auto mc) {
+      constexpr int m = mc;
+      const T through = body.template through<m>(acc);
+      const T val = body.template eval<m>(acc);
+      __builtin_nontemporal_store(inside ? val : body.template outside<m>(through), body.out[m] + o);
+    });
+  } else {
   const T through = P.in[0][o];  // copy-through: physical-index-wise (DataflowLowering.cpp:283-287)
   const T val = body(acc);
   // (non-temporal: the result is not read again by this launch, and keeping it out of L2 leaves the neighbours' lines there --
   //  rows form 1024^3 7-point 2.52 -> 2.84 TB/s)
   __builtin_nontemporal_store(inside ? val : OutsideOf<Body, T>::apply(body, through), P.out + o);
+  }
 }
 
 // wave-uniform pointer -> SGPR pair, so the load takes the "scalar base + 32-bit lane offset" form
@@ -150,11 +160,21 @@ __global__ __launch_bounds__(256) void neptune_apply_rows(DirectParams<T, NIN> P
   RowAcc<T, RANK, NIN> a{P, (int32_t)P.rlb[0] + i, (int32_t)P.rlb[1] + j, (int32_t)P.rlb[2] + k};
   const int64_t pi = a.qi + P.olb[0], pj = a.qj + P.olb[1], pk = a.qk + P.olb[2];
   const bool inside = pi >= P.lb[0] && pi < P.ub[0] && pj >= P.lb[1] && pj < P.ub[1] && pk >= P.lb[2] && pk < P.ub[2];
+  if constexpr (ResultsOf<Body>::value > 1) {
+    static_for<ResultsOf<Body>::value>([&](auto mc) {
+      constexpr int m = mc;
+      T* out = const_cast<T*>(RowAcc<T, RANK, NIN>::row_ptr(body.out[m], a.qi, a.qj, P.n));
+      const T through = body.template through<m>(a);
+      const T val = body.template eval<m>(a);
+      __builtin_nontemporal_store(inside ? val : body.template outside<m>(through), out + (uint32_t)a.qk);
+    });
+  } else {
   const T* in0 = RowAcc<T, RANK, NIN>::row_ptr(P.in[0], a.qi, a.qj, P.n);
   T* out = const_cast<T*>(RowAcc<T, RANK, NIN>::row_ptr(P.out, a.qi, a.qj, P.n));
   const T through = in0[(uint32_t)a.qk];  // copy-through: physical-index-wise (DataflowLowering.cpp:283-287)
   const T val = body(a);
   __builtin_nontemporal_store(inside ? val : OutsideOf<Body, T>::apply(body, through), out + (uint32_t)a.qk);
+  }
 }
 
 }  // namespace neptune_hip

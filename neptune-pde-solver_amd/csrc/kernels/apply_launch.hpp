@@ -327,6 +327,12 @@ struct TileFor {
                std::conditional_t<canon, Tile<rows, wj, 1, true, true, pf_star, false, true, false, true, 1, true>,
                                   Tile<rows, WJ, WK, DPP, NT, (pln && PF < pf_star) ? pf_star : PF, NTL, LDSJ, (JK) && RANK == 2, JHL, KD, pln>>>;
 };
+// ... for a body: a group (ResultsOf<Body> > 1) has no plane-in-LDS form, so every table row -- the PLN rows too -- is that
+// shape of the march kernel for it; footprints only the LDS kernels hold never get here (launch_apply_group)
+template <class Body, class T, class FP, int RANK, int RJ, int WJ, int WK, bool DPP, bool NT, int PF, bool NTL, bool LDSJ, bool JK, bool JHL, int KD, bool PLN>
+using TileOf = std::conditional_t<(ResultsOf<Body>::value > 1),
+                                  Tile<march_rows<FP, RANK>(RJ), WJ, WK, DPP, NT, PF, NTL, LDSJ, (JK) && RANK == 2, JHL, KD, false>,
+                                  typename TileFor<T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN>::type>;
 // star footprints: the centre plane in LDS, the ring of own cells in registers; box footprints: every live plane in LDS
 template <class Body, class T, int RANK, int NIN, class FP, class TL>
 constexpr auto march_kernel_fn() {
@@ -422,7 +428,7 @@ inline void launch_march(int variant, MarchParams<T, NIN>& P, const Body& body, 
 #define NEPTUNE_MV_CASE(idx, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN, name)                        \
   case idx:                                                                                                     \
     launch_march_variant<Body, T, RANK, NIN, FP,                                                                \
-                         typename TileFor<T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN>::type>( \
+                         TileOf<Body, T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN>>(         \
         P, body, planes, chunk, stream);                                                                        \
     break;
   if constexpr (RANK == 3) {
@@ -600,7 +606,7 @@ inline int march3_variant_scratch(int variant) {
     if (it != cache.end()) return it->second;
     const void* fn = nullptr;
 #define NEPTUNE_MV_FN(idx, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN, name) \
-  case idx: fn = (const void*)march_kernel_fn<Body, T, RANK, NIN, FP, typename TileFor<T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, false, JHL, KD, PLN>::type>(); break;
+  case idx: fn = (const void*)march_kernel_fn<Body, T, RANK, NIN, FP, TileOf<Body, T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, false, JHL, KD, PLN>>(); break;
     switch (variant) { NEPTUNE_MARCH3_VARIANTS(NEPTUNE_MV_FN) default: break; }
 #undef NEPTUNE_MV_FN
     int bytes = -1;
@@ -610,6 +616,49 @@ inline int march3_variant_scratch(int variant) {
     cache[variant] = bytes;
     return bytes;
   }
+}
+
+// ---- groups (apply_common.hpp GroupBody): which march tile a multi-output launch takes ----------------------------
+// scratch bytes per lane of a group's kernel on one tile of its rank's table; -1 if unknown
+template <class Body, class T, int RANK, int NIN, class FP>
+inline int group_variant_scratch(int variant) {
+  if constexpr (!FP::MARCH_OK) {
+    return -1;
+  } else {
+    static std::mutex mu;
+    static std::map<int, int> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(variant);
+    if (it != cache.end()) return it->second;
+    const void* fn = nullptr;
+#define NEPTUNE_MV_FN(idx, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN, name) \
+  case idx: fn = (const void*)march_kernel_fn<Body, T, RANK, NIN, FP, TileOf<Body, T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN>>(); break;
+    if constexpr (RANK == 3) { switch (variant) { NEPTUNE_MARCH3_VARIANTS(NEPTUNE_MV_FN) default: break; } }
+    else if constexpr (RANK == 2) { switch (variant) { NEPTUNE_MARCH2_VARIANTS(NEPTUNE_MV_FN) default: break; } }
+    else fn = (const void*)march_kernel_fn<Body, T, RANK, NIN, FP, Tile<1, 1, 4, true, true, 1, false, false, false, false>>();
+#undef NEPTUNE_MV_FN
+    int bytes = -1;
+    hipFuncAttributes attr;
+    if (fn && hipFuncGetAttributes(&attr, fn) == hipSuccess) bytes = (int)attr.localSizeBytes;
+    else (void)hipGetLastError();
+    cache[variant] = bytes;
+    return bytes;
+  }
+}
+// A group instantiation is heavier than any of its members: the tile an automatic choice lands on is kept only if the
+// group's kernel needs no scratch there; otherwise the smaller tiles of the rank are tried in turn (fewer rows per lane,
+// then fewer planes in flight).  -1: every tile spills -- the caller runs the members one by one.  PLN rows stand for
+// their shape of the march kernel (TileOf); an automatic choice that only named one for the plane-in-LDS kernel's sake
+// takes the wide-state tile the march kernel has for such footprints.
+template <class Body, class T, int RANK, int NIN, class FP>
+inline int group_auto_variant(int picked) {
+  if (RANK == 3 && picked >= 0 && picked < kNumMarch3 && kMarch3[picked].pln) picked = FP::R0 > 3 ? 5 : 2;
+  const int order3[] = {picked, 2, 3, 5}, order2[] = {picked, 2, 1}, order1[] = {0};
+  const int* order = RANK == 3 ? order3 : (RANK == 2 ? order2 : order1);
+  const int n = RANK == 3 ? 4 : (RANK == 2 ? 3 : 1);
+  for (int c = 0; c < n; ++c)
+    if (group_variant_scratch<Body, T, RANK, NIN, FP>(order[c]) <= 0) return order[c];   // 0, or unknown (no device query)
+  return -1;
 }
 
 // the direct kernel on g's region: rows form when all coordinates fit 31 bits (see apply_direct.hpp),
@@ -662,6 +711,13 @@ inline int launch_apply_impl(const Body& body, const neptune_hip_apply_geom_t* g
     int variant = pick_march_variant<T, RANK, FP>(g, cfg);
     if (RANK == 3 && variant == 6 && !(cfg && cfg->variant == 6) && march3_variant_scratch<Body, T, RANK, NIN, FP>(6) > 0)
       variant = 4;  // automatic choice only: this body spills on the 8-rows-per-lane tile
+    if constexpr (ResultsOf<Body>::value > 1) {
+      // a group: an automatic choice never lands on a tile its kernel spills on (an explicit tile is taken as asked)
+      if (!(cfg && cfg->variant >= 0 && cfg->variant < march_variant_count(RANK))) {
+        variant = group_auto_variant<Body, T, RANK, NIN, FP>(variant);
+        if (variant < 0) return NEPTUNE_HIP_EUNSUPPORTED;
+      }
+    }
     // rank-2 tile form: (d0,d1) -> (J,K), one plane (the LDS tile kernel is a tile form whatever the table row says)
     const bool jk = RANK == 2 && (march_variant(RANK, variant)->jk || tile2_only<T, FP, RANK>());
     auto axes = [&](const int64_t* src, int64_t dst[3], int64_t fill) {
@@ -829,6 +885,8 @@ inline neptune_hip_launch_cfg_t tune_apply(const Body& body, const neptune_hip_a
   int top[2] = {-1, -1};
   float top_ms[2] = {-1.f, -1.f};
   for (int v = 0; v < nv; ++v) {
+    if constexpr (ResultsOf<Body>::value > 1)
+      if (group_variant_scratch<Body, T, RANK, NIN, FP>(v) > 0) continue;   // a group is never given a tile it spills on
     const float ms = try_cfg({NEPTUNE_HIP_KERNEL_MARCH, v, 0, 0});
     if (ms <= 0) continue;
     if (top_ms[0] < 0 || ms < top_ms[0]) { top[1] = top[0]; top_ms[1] = top_ms[0]; top[0] = v; top_ms[0] = ms; }
@@ -953,6 +1011,58 @@ inline int launch_apply(const Body& body, const neptune_hip_apply_geom_t* g, con
     if (is_tuned && takes) return launch_apply_impl<Body, T, RANK, NIN, FP>(body, g, in, out, stream, &tuned);
   }
   return launch_apply_impl<Body, T, RANK, NIN, FP>(body, g, in, out, stream, cfg);
+}
+
+// ---- a group of sibling applies as ONE multi-output launch ---------------------------------------------------------
+// `body` is a GroupBody whose out[] are set; g / in describe the UNION of the members' inputs, FP their union footprint.
+// The fused kernel exists for the march kernel and the direct kernels only.  Returns NEPTUNE_HIP_EUNSUPPORTED -- and
+// launches nothing -- when the union footprint is one that only the LDS kernels hold, when the plan is the direct kernel
+// although a member alone would take the march kernel (fusing would then trade a fast launch for a slow one), when a
+// result buffer is not 16-byte aligned, or when every march tile spills for this group.  plan_only: decide, launch nothing.
+// Measured choices are kept per body type like any launch's, and a GroupBody is a type of its own: its table and its
+// wisdom keys (typeid of the body) never meet its members'.
+template <class GB, class T, int RANK, int NIN, class FP, int M = 0>
+inline bool group_members_all_direct(const neptune_hip_apply_geom_t* g, const void* const* in, const void* out) {
+  if constexpr (M >= GB::NOUT) {
+    return true;
+  } else {
+    using G = typename GB::template Member<M>;
+    neptune_hip_apply_geom_t gm = *g;
+    const void* inm[kMaxInputs];
+    gm.num_inputs = G::NIN;
+    for (int k = 0; k < G::NIN; ++k) {
+      inm[k] = in[G::map(k)];
+      for (int d = 0; d < RANK; ++d) { gm.in_lb[k][d] = g->in_lb[G::map(k)][d]; gm.in_ub[k][d] = g->in_ub[G::map(k)][d]; }
+    }
+    if (plan_apply<T, RANK, G::NIN, typename G::FP>(&gm, inm, out, nullptr) != NEPTUNE_HIP_KERNEL_DIRECT) return false;
+    return group_members_all_direct<GB, T, RANK, NIN, FP, M + 1>(g, in, out);
+  }
+}
+template <class GB, class T, int RANK, int NIN, class FP>
+inline int launch_apply_group(const GB& body, const neptune_hip_apply_geom_t* g, const void* const* in, hipStream_t stream,
+                              const neptune_hip_launch_cfg_t* cfg, bool plan_only = false) {
+  static_assert(ResultsOf<GB>::value > 1, "launch_apply_group takes a GroupBody");
+  for (int m = 0; m < GB::NOUT; ++m)
+    if (!body.out[m]) return NEPTUNE_HIP_EINVAL;
+  const int kernel = plan_apply<T, RANK, NIN, FP>(g, in, body.out[0], cfg);
+  if (kernel < 0) return kernel;
+  const int want = cfg ? cfg->kernel : NEPTUNE_HIP_KERNEL_AUTO;
+  if (kernel == NEPTUNE_HIP_KERNEL_MARCH) {
+    if constexpr (!FP::MARCH_OK) {
+      return NEPTUNE_HIP_EUNSUPPORTED;
+    } else {
+      if (plane_only<T, FP, RANK>() || tile2_only<T, FP, RANK>()) return NEPTUNE_HIP_EUNSUPPORTED;
+      for (int m = 1; m < GB::NOUT; ++m)
+        if ((uintptr_t)body.out[m] % 16 != 0) return NEPTUNE_HIP_EUNSUPPORTED;
+      if (!(cfg && cfg->variant >= 0 && cfg->variant < march_variant_count(RANK)) &&
+          group_auto_variant<GB, T, RANK, NIN, FP>(pick_march_variant<T, RANK, FP>(g, cfg)) < 0)
+        return NEPTUNE_HIP_EUNSUPPORTED;
+    }
+  } else if (want == NEPTUNE_HIP_KERNEL_AUTO) {
+    if (!group_members_all_direct<GB, T, RANK, NIN, FP>(g, in, body.out[0])) return NEPTUNE_HIP_EUNSUPPORTED;
+  }
+  if (plan_only) return NEPTUNE_HIP_OK;
+  return launch_apply<GB, T, RANK, NIN, FP>(body, g, in, body.out[0], stream, cfg);
 }
 
 }  // namespace neptune_hip

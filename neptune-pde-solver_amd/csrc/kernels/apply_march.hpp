@@ -706,6 +706,28 @@ __global__ __launch_bounds__(kWave* TL::WJ* TL::WK) void neptune_apply_march(Mar
       constexpr int r = rc;
       const int64_t lj = (int64_t)(j0 + r) + P.olb[1];
       const bool in_ij = in_i && in_j[r];
+      if constexpr (ResultsOf<Body>::value > 1) {
+        // a group (apply_common.hpp GroupBody): member by member on the same neighbourhood, so that one result vector is
+        // live besides the shared rings; each member selects against ITS copy-through source and stores into ITS buffer
+        static_for<ResultsOf<Body>::value>([&](auto mc) {
+          constexpr int m = mc;
+          V res;
+          static_for<VK>([&](auto ec) {
+            constexpr int e = ec;
+            const int64_t lk = (int64_t)(k0 + e) + P.olb[2];
+            const bool inside = in_ij && in_k[e];
+            MarchAcc<T, RANK, NIN, FP, RJ, r, e, JK> acc{ring, lft, rgt, pt, li, lj, lk};
+            const T val = body.template eval<m>(acc);
+            const T through = body.template through<m>(acc);   // the member's input 0 at the centre
+            res[e] = inside ? val : body.template outside<m>(through);
+          });
+          if (row_ok[r] && lane_ok) {
+            V* dst = reinterpret_cast<V*>(reinterpret_cast<char*>(body.out[m]) + (int64_t)i * plane_b + (rowb[0][r + R1] + lane_b));
+            if constexpr (NT) __builtin_nontemporal_store(res, dst);
+            else *dst = res;
+          }
+        });
+      } else {
       V res;
       static_for<VK>([&](auto ec) {
         constexpr int e = ec;
@@ -723,6 +745,7 @@ __global__ __launch_bounds__(kWave* TL::WJ* TL::WK) void neptune_apply_march(Mar
         V* dst = reinterpret_cast<V*>(obase + (rowb[0][r + R1] + lane_b));
         if constexpr (NT) __builtin_nontemporal_store(res, dst);
         else *dst = res;
+      }
       }
     });
   };

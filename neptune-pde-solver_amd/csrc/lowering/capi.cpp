@@ -71,7 +71,18 @@ std::string report_json(const LowerInfo& info) {
       << "\", \"shape\": \""
       << (a.halo_input < 0 ? "pointwise" : (a.box ? "box" : "star")) << "\", \"elem\": \"" << a.elem << "\", \"halo0\": " << a.halo0
       << ", \"geom_symbol\": \"" << a.geom_symbol << "\", \"exact\": " << (a.exact ? "true" : "false")
-      << ", \"leapfrog_symbol\": \"" << a.leapfrog_symbol << "\"}";
+      << ", \"leapfrog_symbol\": \"" << a.leapfrog_symbol << "\"";
+    if (a.group >= 0) o << ", \"group\": " << a.group;
+    o << "}";
+  }
+  o << "], \"groups\": [";
+  for (size_t i = 0; i < info.groups.size(); ++i) {
+    const GroupInfo& g = info.groups[i];
+    o << (i ? ", " : "") << "{\"function\": \"" << g.function << "\", \"members\": [";
+    for (size_t k = 0; k < g.members.size(); ++k) o << (k ? ", " : "") << "\"" << g.members[k] << "\"";
+    o << "], \"inputs\": [";
+    for (size_t k = 0; k < g.inputs.size(); ++k) o << (k ? ", " : "") << "\"" << g.inputs[k] << "\"";
+    o << "], \"kernel\": \"" << g.kernel << "\", \"rank\": " << g.rank << ", \"elem\": \"" << g.elem << "\"}";
   }
   o << "]}";
   return o.str();

@@ -355,6 +355,14 @@ struct Emitter {
     }
     // inputs never read unconditionally keep top_radius -1 ("not accessed": nothing to check)
     scan_accesses(blk, temp_index, fp, true);
+    finish_footprint(fp, res.elem);
+    return true;
+  }
+
+  // from the per-input radii (fp.radius, fp.box, fp.nin, fp.rank) to what the kernels are told: which inputs get a ring,
+  // the shared radii, whether a march-class kernel holds it.  Also run on the union footprint of a group of applies.
+  static void finish_footprint(Footprint& fp, const std::string& elem) {
+    const int nin = fp.nin;
     // rank mapping onto the kernel's (I,J,K) axes, see apply_common.hpp AxisMap.
     // every input read at a non-zero offset gets a register ring in the march kernel; the rings share
     // the largest radii
@@ -374,7 +382,7 @@ struct Emitter {
       else { m[2] = r[0]; }
       for (int a = 0; a < 3; ++a) R[a] = std::max(R[a], m[a]);
     }
-    const int vk = 16 / esize(res.elem);
+    const int vk = 16 / esize(elem);
     // the march kernel keeps 2*R0+1 planes of RJ+2*R1 rows per halo input in registers.  3-D: radius 1 for box
     // stencils, up to 4 for stars (4th/6th/8th-order 13-, 19- and 25-point operators; the 2-row late-J-halo tile
     // holds a radius-3 ring in 209 VGPRs without scratch, a radius-4 ring in 229 with one plane in flight), at most
@@ -401,7 +409,6 @@ struct Emitter {
     // 3-D boxes of one halo input up to radius 2 (125 points): every live plane in LDS (neptune_apply_planes)
     if (!fp.march_ok && krank == 3 && fp.box && fp.halo_inputs == 1 && rbig <= 2 && R[0] >= 1) fp.march_ok = true;
     if (!fp.march_ok) { fp.halo_input = -1; fp.halo_mask = 0; R[0] = R[1] = R[2] = 0; }
-    return true;
   }
 
   // a reach table: {{most negative offset per input and dimension}, {most positive}} (hi < lo: not accessed)
@@ -441,6 +448,15 @@ struct Emitter {
     return h;
   }
 
+  static std::string footprint_type(const Footprint& fp) {
+    std::ostringstream o;
+    o << "neptune_hip::Footprint<" << fp.halo_input << ", " << fp.R[0] << ", " << fp.R[1] << ", " << fp.R[2] << ", "
+      << ((fp.box && fp.march_ok) ? "true" : "false") << ", " << (fp.march_ok ? "true" : "false");
+    if (fp.halo_inputs > 1 && fp.march_ok) o << ", 0x" << std::hex << fp.halo_mask << std::dec << "u";
+    o << ">";
+    return o.str();
+  }
+
   bool emit_body(const Op& apply, const std::string& tag, Footprint& fp) {
     const Block& blk = *apply.regions[0];
     const int nin = (int)apply.operands.size();
@@ -460,10 +476,7 @@ struct Emitter {
     if (!body_ok) return false;
     fp.exact = !saw_elementary;
     o << "  }\n};\n";
-    o << "using FP_" << tag << " = neptune_hip::Footprint<" << fp.halo_input << ", " << fp.R[0] << ", " << fp.R[1] << ", " << fp.R[2] << ", "
-      << ((fp.box && fp.march_ok) ? "true" : "false") << ", " << (fp.march_ok ? "true" : "false");
-    if (fp.halo_inputs > 1 && fp.march_ok) o << ", 0x" << std::hex << fp.halo_mask << std::dec << "u";
-    o << ">;\n";
+    o << "using FP_" << tag << " = " << footprint_type(fp) << ";\n";
     // what the unconditional accesses reach, per input and dimension (analyze_apply leaves hi < lo where nothing is read)
     o << "static const neptune_hip::Reach kTopRadius_" << tag << " = " << reach_table(fp.top_lo, fp.top_hi) << ";\n";
     if (fp.nd) o << "static const neptune_hip::ReachN kNdReach_" << tag << " = " << reach_table(fp.nd_lo, fp.nd_hi) << ";\n";
@@ -589,7 +602,15 @@ struct Emitter {
       const std::string& n = op.name;
       bool ok = true;
       if (is_alias_op(n)) emit_alias(s, op);
-      else if (n == "neptune_ir.apply") ok = emit_apply(s, op, (int)oi);
+      else if (n == "neptune_ir.apply") {
+        Group grp;
+        if (find_group(s, (int)oi, grp)) {
+          ok = emit_group(s, grp);
+          oi = (size_t)grp.members.back();   // the aliases and constants between the members were emitted with the group
+        } else {
+          ok = emit_apply(s, op, (int)oi);
+        }
+      }
       else if (n == "neptune_ir.time_advance") ok = emit_time_advance(s, op, (int)oi);
       else if (!op.callee.empty()) emit_call(s, op, (int)oi);
       else if (n == "neptune_ir.store") emit_store(s, op);
@@ -694,25 +715,44 @@ struct Emitter {
         << op.name << "\");\n";
   }
 
-  bool emit_apply(FnState& s, const Op& op, int oi) {
+  // single-use result consumed by a reduce a few scalar/alias ops later: the apply is evaluated
+  // inside the reduction kernel (run_apply_reduce_sum), the temp never exists
+  static bool feeds_fused_reduce(FnState& s, const Op& op, int oi) {
     const auto& ops = s.f.body.ops;
+    if (s.vals[op.results[0]].uses != 1) return false;
+    for (size_t j = oi + 1; j < ops.size(); ++j) {
+      const Op& c = *ops[j];
+      if (c.name == "neptune_ir.reduce" && c.operands.at(0) == op.results[0]) return true;
+      const std::string& nm = c.name;
+      if (!(nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" || is_scalar_op(c))) break;
+    }
+    return false;
+  }
+
+  // group >= 0: the apply is a member of that group -- its body functor, geometry-level entries and report entry are
+  // what they are for an apply on its own; the launch itself is emitted by emit_group
+  bool emit_apply(FnState& s, const Op& op, int oi, int group = -1, std::string* tag_out = nullptr) {
     const std::string tag = s.f.name + "_" + std::to_string(s.apply_counter++);
+    if (tag_out) *tag_out = tag;
     Footprint fp;
     if (!emit_body(op, tag, fp)) return false;
     const int nin = (int)op.operands.size();
     const Type& res = op.types[nin];
     ValueInfo& vi = s.vals[op.results[0]];
     vi.root_arg = -1;
-    // single-use result consumed by a reduce a few scalar/alias ops later: the apply is evaluated
-    // inside the reduction kernel (run_apply_reduce_sum), the temp never exists
-    bool fused = false;
-    if (vi.uses == 1 && fp.lead == 0)
-      for (size_t j = oi + 1; j < ops.size(); ++j) {
-        const Op& c = *ops[j];
-        if (c.name == "neptune_ir.reduce" && c.operands.at(0) == op.results[0]) { fused = true; break; }
-        const std::string& nm = c.name;
-        if (!(nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" || is_scalar_op(c))) break;
+    const bool fused = group < 0 && fp.lead == 0 && feeds_fused_reduce(s, op, oi);
+    if (group >= 0) {
+      ApplyInfo ai = apply_info(s, tag, fp, fp.rank, res.elem, halo0_of(fp));
+      ai.group = group;
+      ai.geom_symbol = tag + "__geom";
+      emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
+      if (leapfrog_capable(fp, op)) {
+        ai.leapfrog_symbol = ai.geom_symbol + "L2";
+        emit_leapfrog_entry(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
       }
+      info.applies.push_back(ai);
+      return true;
+    }
     const std::string res_box = new_box(res.bounds), bounds_box = new_box(op.attrs.at("bounds").bounds);
     std::vector<std::string> ins;
     for (auto& v : op.operands) ins.push_back(cname(v));
@@ -758,6 +798,186 @@ struct Emitter {
       }
       info.applies.push_back(ai);
     }
+    return true;
+  }
+
+  // ---- groups: sibling applies over shared inputs -> one multi-output launch (csrc/kernels/apply_common.hpp GroupBody) ----
+  struct Group {
+    std::vector<int> members;            // op indices of the member applies, in order
+    std::vector<std::string> inputs;     // union of their operands (SSA names), in order of first use
+    Footprint fp;                        // union footprint over `inputs`
+    bool no_group_form = false;          // the union is planned onto a kernel without a group form: runs member by member
+  };
+
+  // A group starting at the apply ops[first]: consecutive applies with nothing between them but aliases and scalar
+  // constants (no store: a load does not snapshot, a store in between could feed a later member through memory), none
+  // reading another's result, same rank (1..3) / element type / result box / apply.bounds, every member's input 0 in the
+  // result's box, at most 4 distinct operands of which one at least is read by two members, 2..4 members, none feeding a
+  // fused reduce, none with batch dimensions or an n-D footprint.  The longest such prefix is taken.
+  bool find_group(FnState& s, int first, Group& grp) {
+    const auto& ops = s.f.body.ops;
+    const Op& a0 = *ops[first];
+    const int nin0 = (int)a0.operands.size();
+    const Type& res0 = a0.types[nin0];
+    const Bounds& bnd0 = a0.attrs.at("bounds").bounds;
+    std::set<std::string> tainted;                 // member results and their aliases
+    std::vector<Footprint> fps;
+    std::vector<std::string> inputs;
+    bool shared = false;
+    std::vector<int> members;
+    for (int j = first; j < (int)ops.size() && members.size() < 4; ++j) {
+      const Op& op = *ops[j];
+      if (is_alias_op(op.name) || op.name == "arith.constant") {
+        bool reads_member = false;
+        for (auto& v : op.operands) reads_member = reads_member || tainted.count(v);
+        if (reads_member) break;
+        continue;
+      }
+      if (op.name != "neptune_ir.apply") break;
+      const int nin = (int)op.operands.size();
+      if (nin < 1 || nin > 4) break;
+      const Type& res = op.types[nin];
+      const Bounds& bnd = op.attrs.at("bounds").bounds;
+      if (bnd.rank() < 1 || bnd.rank() > 3 || res.elem != res0.elem || !(res.bounds == res0.bounds) || !(bnd == bnd0)) break;
+      if (!(op.types[0].bounds == res.bounds) || !op.types[0].is_tempish()) break;
+      if (res.elem != "f64" && res.elem != "f32") break;
+      bool bad = false;
+      for (int k = 0; k < nin; ++k) bad = bad || tainted.count(op.operands[k]) || op.types[k].elem != res.elem;
+      if (bad || feeds_fused_reduce(s, op, j)) break;
+      Footprint fp;
+      std::map<std::string, int> ti, ia;
+      if (!analyze_apply(op, fp, ti, ia)) return false;   // the same diagnostic emit_apply would give
+      if (fp.lead > 0 || fp.nd) break;
+      std::vector<std::string> next = inputs;
+      bool shares = false;
+      for (auto& v : op.operands) {
+        if (std::find(next.begin(), next.end(), v) == next.end()) next.push_back(v);
+        else if (std::find(inputs.begin(), inputs.end(), v) != inputs.end()) shares = true;
+      }
+      if (next.size() > 4) break;
+      inputs = next;
+      shared = shared || shares;
+      members.push_back(j);
+      fps.push_back(fp);
+      tainted.insert(op.results[0]);
+    }
+    // a member that shares nothing with the ones before it may still be followed by one that does; a group needs one
+    // shared value in all
+    if (members.size() < 2 || !shared) return false;
+    // union footprint: per group input the largest radius any member reads it at, a box if any member's is
+    Footprint u;
+    u.nin = (int)inputs.size();
+    u.rank = fps[0].rank;
+    for (int k = 0; k < 4; ++k)
+      for (int d = 0; d < 3; ++d) { u.radius[k][d] = 0; u.top_radius[k][d] = -1; u.top_lo[k][d] = 1; u.top_hi[k][d] = -1; }
+    bool any_march = false;
+    for (size_t m = 0; m < members.size(); ++m) {
+      const Op& op = *ops[members[m]];
+      any_march = any_march || fps[m].march_ok;
+      u.box = u.box || fps[m].box;
+      for (size_t k = 0; k < op.operands.size(); ++k) {
+        const int gi = (int)(std::find(inputs.begin(), inputs.end(), op.operands[k]) - inputs.begin());
+        for (int d = 0; d < 3; ++d) u.radius[gi][d] = std::max(u.radius[gi][d], fps[m].radius[k][d]);
+      }
+    }
+    finish_footprint(u, res0.elem);
+    // a union no march-class kernel holds while a member alone runs on one: fusing would trade a fast launch for a slow one
+    if (!u.march_ok && any_march) return false;
+    // what the march kernel's registers do not hold runs on the LDS kernels, which have no group form
+    // (apply_launch.hpp plane_only / tile2_only): the runtime then runs the members one by one
+    const int rbig = std::max(u.R[0], std::max(u.R[1], u.R[2]));
+    if (u.march_ok)
+      grp.no_group_form = u.rank == 3 ? (rbig > 1 || u.halo_inputs > 2) : (u.rank == 2 ? (rbig > 2 || (u.box && rbig > 1)) : false);
+    grp.members = members;
+    grp.inputs = inputs;
+    grp.fp = u;
+    return true;
+  }
+
+  bool emit_group(FnState& s, const Group& grp) {
+    const auto& ops = s.f.body.ops;
+    const int gidx = (int)info.groups.size();
+    const int first = grp.members.front(), last = grp.members.back();
+    const Op& a0 = *ops[first];
+    const Type& res = a0.types[a0.operands.size()];
+    const std::string T = ctype(res.elem);
+    const int rank = res.bounds.rank(), M = (int)grp.members.size(), NU = (int)grp.inputs.size();
+    // the aliases and constants between the members first: none of them reads a member's result
+    std::vector<std::string> tags(M);
+    for (int j = first, m = 0; j <= last; ++j) {
+      const Op& op = *ops[j];
+      if (is_alias_op(op.name)) emit_alias(s, op);
+      else if (op.name == "arith.constant") { if (!emit_scalar(s, op)) return false; }
+      else { if (!emit_apply(s, op, j, gidx, &tags[m])) return false; ++m; }
+    }
+    const std::string gtag = tags[0] + "_group";
+    // destinations: member m may write straight into the field its single consumer stores it to when only aliases,
+    // constants and the other members' own such stores lie between the group and that store (the runtime checks the
+    // actual pointers against every input and every other destination); else what the apply on its own would get
+    std::vector<std::string> dest(M), dest_single(M);
+    for (int m = 0; m < M; ++m) dest[m] = dest_single[m] = s.dest_for(grp.members[m]);
+    for (int j = last + 1; j < (int)ops.size(); ++j) {
+      const Op& op = *ops[j];
+      if (is_alias_op(op.name) || op.name == "arith.constant") continue;
+      if (op.name != "neptune_ir.store" || op.attrs.count("bounds")) break;
+      int m = -1;
+      for (int k = 0; k < M; ++k)
+        if (ops[grp.members[k]]->results[0] == op.operands[0]) m = k;
+      const std::string& field = op.operands[1];
+      const bool field_before = !s.def_at.count(field) || s.def_at[field] < first;
+      if (m < 0 || s.vals[op.operands[0]].uses != 1 || !field_before) break;
+      dest[m] = "&" + cname(field);
+    }
+    // the group body: members with their footprints and the map from member input to group input
+    std::ostringstream gb, init;
+    gb << "neptune_hip::GroupBody<" << T;
+    for (int m = 0; m < M; ++m) {
+      const Op& op = *ops[grp.members[m]];
+      gb << ", neptune_hip::GroupMember<Body_" << tags[m] << ", FP_" << tags[m] << ", " << op.operands.size();
+      for (auto& v : op.operands) gb << ", " << (std::find(grp.inputs.begin(), grp.inputs.end(), v) - grp.inputs.begin());
+      gb << ">";
+    }
+    gb << ">";
+    std::ostringstream& o = s.o;
+    o << "  // group of " << M << " sibling applies over " << NU << " shared inputs -> one multi-output launch (members:";
+    for (int m = 0; m < M; ++m) o << " " << ops[grp.members[m]]->results[0];
+    o << ")\n";
+    o << "  using Group_" << gtag << " = " << gb.str() << ";\n";
+    o << "  using FP_" << gtag << " = " << footprint_type(grp.fp) << ";\n";
+    std::vector<std::string> ins;
+    for (auto& v : grp.inputs) ins.push_back(cname(v));
+    emit_inputs(o, gtag, ins);
+    auto list = [&](const char* type, const std::string& name, const std::vector<std::string>& items) {
+      o << "  " << type << " " << name << "_" << gtag << "[] = {";
+      for (size_t k = 0; k < items.size(); ++k) o << (k ? ", " : "") << items[k];
+      o << "};\n";
+    };
+    std::vector<std::string> reach, halo0;
+    for (int m = 0; m < M; ++m) {
+      reach.push_back("&kTopRadius_" + tags[m]);
+      Footprint fp;
+      std::map<std::string, int> ti, ia;
+      if (!analyze_apply(*ops[grp.members[m]], fp, ti, ia)) return false;
+      halo0.push_back(std::to_string(halo0_of(fp)));
+    }
+    list("const neptune_hip::Reach* const", "reach", reach);
+    list("const int", "halo0", halo0);
+    list("const nl::Val* const", "dest", dest);
+    list("const nl::Val* const", "dest1", dest_single);
+    o << "  nl::Val out_" << gtag << "[" << M << "];\n";
+    o << "  nl::run_apply_group<Group_" << gtag << ", " << T << ", " << rank << ", " << NU << ", FP_" << gtag << ">(sc, Group_" << gtag
+      << "{}, " << new_box(res.bounds) << ", " << new_box(a0.attrs.at("bounds").bounds) << ", in_" << gtag << ", reach_" << gtag
+      << ", halo0_" << gtag << ", dest_" << gtag << ", dest1_" << gtag << ", out_" << gtag << ");\n";
+    for (int m = 0; m < M; ++m)
+      o << "  const nl::Val " << cname(ops[grp.members[m]]->results[0]) << " = out_" << gtag << "[" << m << "];\n";
+    GroupInfo gi;
+    gi.function = s.f.name;
+    gi.members = tags;
+    gi.inputs = grp.inputs;
+    gi.kernel = grp.no_group_form ? "members" : (grp.fp.march_ok ? "march" : "direct");
+    gi.rank = rank;
+    gi.elem = res.elem;
+    info.groups.push_back(gi);
     return true;
   }
 

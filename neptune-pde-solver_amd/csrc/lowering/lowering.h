@@ -18,6 +18,16 @@ struct ApplyInfo {
   std::string geom_symbol;    // exported geometry-level entry (empty: none)
   std::string leapfrog_symbol;  // exported leapfrog pair entry <geom_symbol>L2 of a two-level scheme (empty: none)
   bool exact = true;          // false: the body uses elementary functions (exp, log, ...): a few ulp, not bit-exact
+  int group = -1;             // index into LowerInfo::groups when this apply is a member of a group
+};
+// a run of sibling applies over shared inputs that one multi-output launch can compute
+struct GroupInfo {
+  std::string function;
+  std::vector<std::string> members;   // the members' apply tags, in order
+  std::vector<std::string> inputs;    // SSA names of the union of their operands, in group-input order
+  std::string kernel;                 // what the union footprint is planned onto: march | direct | members (no group form)
+  int rank = 0;
+  std::string elem;
 };
 struct SigType {
   std::string kind, elem;  // kind: memref | temp | field
@@ -40,6 +50,7 @@ struct LowerInfo {
   std::vector<std::string> lowered;                            // exported symbols
   std::vector<std::pair<std::string, std::string>> skipped;    // (symbol, reason)
   std::vector<ApplyInfo> applies;
+  std::vector<GroupInfo> groups;
   // stencil parts of functions that are not lowered as a whole (they hold solver ops): each is an exported symbol that
   // computes one value the solver op consumes, from the function's own arguments
   struct Outlined { std::string symbol, function, value; int line = 0; };

@@ -403,6 +403,108 @@ inline Val run_apply(Scope& sc, const Body& body, const Box& result_decl, const 
   return out;
 }
 
+// A GROUP of sibling neptune_ir.apply ops over shared inputs (csrc/kernels/apply_common.hpp GroupBody): ONE launch reads
+// the union of the members' inputs once and stores one result per member.  `in`: the union inputs; member m reads
+// in[map_m(k)] as its input k and copies in[THROUGH_m] through outside the bounds.  reach / halo0: per member, as run_apply
+// takes them.  dest: per member, the field its single consumer (a whole-buffer store) copies it into, or nullptr; a member
+// writes straight into it only if that field overlaps NO input of ANY member and no other member's destination (actual
+// pointers) -- the launch reads every input while it writes every result.  dest_single: what each member's run_apply
+// would be given were the group not recognised; used under a slab view, where the members run exactly as they did before
+// groups existed.  The members run one by one through run_apply when the launch has no group form
+// (launch_apply_group: NEPTUNE_HIP_EUNSUPPORTED), under a slab view, or with NEPTUNE_HIP_NO_GROUPS=1 (read at each call).
+inline bool groups_disabled() {
+  const char* e = getenv("NEPTUNE_HIP_NO_GROUPS");
+  return e && *e && *e != '0';
+}
+template <class GB, class T, int RANK, int NIN, int M = 0>
+inline void run_group_members(Scope& sc, const GB& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
+                              const neptune_hip::Reach* const* reach, const int* halo0, const Val* const* dest, Val* out) {
+  if constexpr (M < GB::NOUT) {
+    using G = typename GB::template Member<M>;
+    const Val* inm[G::NIN];
+    for (int k = 0; k < G::NIN; ++k) inm[k] = in[G::map(k)];
+    out[M] = run_apply<typename G::Body, T, RANK, G::NIN, typename G::FP>(sc, body.template member<M>().body, result_decl, bounds_decl, inm,
+                                                                       *reach[M], dest[M], halo0[M]);
+    run_group_members<GB, T, RANK, NIN, M + 1>(sc, body, result_decl, bounds_decl, in, reach, halo0, dest, out);
+  }
+}
+template <class GB, class T, int RANK, int NIN, int M = 0>
+inline void check_group_members(Scope& sc, const Box& result_box, const Box& bounds, const Val* const* in,
+                                const neptune_hip::Reach* const* reach, bool& through_ok) {
+  if constexpr (M < GB::NOUT) {
+    using G = typename GB::template Member<M>;
+    const Val* inm[G::NIN];
+    for (int k = 0; k < G::NIN; ++k) inm[k] = in[G::map(k)];
+    neptune_hip_apply_geom_t gm;
+    fill_geom(gm, result_box, bounds, inm, G::NIN);
+    const int rc = geom_check_radius(&gm, *reach[M]);
+    if (rc == NEPTUNE_HIP_EOOB)
+      die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
+                     "DataflowLowering.cpp:380-410); refusing to run it");
+    if (rc != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
+    // the copy-through source is read at the centre of the group input: its box must BE the result's
+    for (int d = 0; d < RANK; ++d)
+      through_ok = through_ok && inm[0]->box.lb[d] == result_box.lb[d] && inm[0]->box.ub[d] == result_box.ub[d];
+    check_group_members<GB, T, RANK, NIN, M + 1>(sc, result_box, bounds, in, reach, through_ok);
+  }
+}
+template <class GB, class T, int RANK, int NIN, class FP>
+inline void run_apply_group(Scope& sc, GB body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
+                            const neptune_hip::Reach* const* reach, const int* halo0, const Val* const* dest,
+                            const Val* const* dest_single, Val* out) {
+  constexpr int M = GB::NOUT;
+  if (sc.slab()) {   // multi-GPU: member by member, as before groups existed (ghost planes, pending exchanges: run_apply)
+    run_group_members<GB, T, RANK, NIN>(sc, body, result_decl, bounds_decl, in, reach, halo0, dest_single, out);
+    neptune_hip_note_group(0, M);
+    return;
+  }
+  const Box result_box = result_decl, bounds = Scope::zero_trip(bounds_decl);
+  bool through_ok = true;
+  check_group_members<GB, T, RANK, NIN>(sc, result_box, bounds, in, reach, through_ok);
+  // destination forwarding, decided for the group as a whole: holds for the fused launch and for the members run in turn
+  // (member m's direct write happens before member m+1 reads ITS inputs)
+  const Val* fwd[M];
+  for (int m = 0; m < M; ++m) {
+    bool direct = dest[m] != nullptr && dest[m]->count == result_box.count();
+    for (int k = 0; direct && k < NIN; ++k) direct = !overlaps(*dest[m], *in[k]);
+    for (int o = 0; direct && o < M; ++o) direct = o == m || dest[o] == nullptr || !overlaps(*dest[m], *dest[o]);
+    fwd[m] = direct ? dest[m] : nullptr;
+  }
+  neptune_hip_apply_geom_t g;
+  fill_geom(g, result_box, bounds, in, NIN);
+  const void* ptrs[NIN];
+  for (int k = 0; k < NIN; ++k) ptrs[k] = in[k]->dev;
+  bool fused = through_ok && !groups_disabled();
+  if (fused) {
+    // plan first (a result that will be a pool block is 16-byte aligned: stands in as such), allocate only what runs
+    for (int m = 0; m < M; ++m) body.out[m] = fwd[m] ? static_cast<T*>(fwd[m]->dev) : reinterpret_cast<T*>((uintptr_t)16);
+    const int rc = launch_apply_group<GB, T, RANK, NIN, FP>(body, &g, ptrs, sc.stream(), launch_override(), true);
+    if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
+    else if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply group launch rejected");
+  }
+  if (!fused) {
+    run_group_members<GB, T, RANK, NIN>(sc, body, result_decl, bounds_decl, in, reach, halo0, fwd, out);
+    neptune_hip_note_group(0, M);
+    return;
+  }
+  for (int m = 0; m < M; ++m) {
+    if (fwd[m]) {
+      out[m] = *fwd[m];
+      out[m].box = result_box;
+    } else {
+      out[m] = sc.alloc(result_box, (int)sizeof(T));
+    }
+    out[m].stale_ghosts = false;
+    body.out[m] = static_cast<T*>(out[m].dev);
+  }
+  sc.wait_pending();
+  const int rc = launch_apply_group<GB, T, RANK, NIN, FP>(body, &g, ptrs, sc.stream(), launch_override());
+  if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply group launch rejected");
+  for (int m = 0; m < M; ++m)
+    if (fwd[m]) sc.mark_dirty(*fwd[m]);
+  neptune_hip_note_group(1, M);
+}
+
 // One neptune_ir.apply of rank R = 4..6 whose accesses have no offset along the leading R-3 dimensions (batch / component
 // dimensions; the reference's lowering is rank-generic, DataflowLowering.cpp:268-270, 301-308): for every leading index one
 // rank-3 apply on the contiguous sub-field -- inside the leading bounds the body (which sees the leading indices as members

@@ -138,6 +138,18 @@ void neptune_hip_tune_stats(int64_t out[3]) {
 
 void neptune_hip_note_launch(int kernel, int variant, int chunk) { t_last = {kernel, variant, chunk, 0}; }
 
+// groups of sibling applies (lowered_runtime.hpp run_apply_group): how many ran as one multi-output launch, and how many
+// member applies of a group ran as launches of their own
+static std::atomic<int64_t> g_groups_fused{0}, g_group_members_single{0};
+void neptune_hip_note_group(int fused, int members) {
+  if (fused) g_groups_fused += 1;
+  else g_group_members_single += members;
+}
+void neptune_hip_group_launch_counts(int64_t* fused, int64_t* members_single) {
+  if (fused) *fused = g_groups_fused.load();
+  if (members_single) *members_single = g_group_members_single.load();
+}
+
 int neptune_hip_last_launch(neptune_hip_launch_cfg_t* out) {
   if (!out || t_last.kernel < 0) return 0;
   *out = t_last;

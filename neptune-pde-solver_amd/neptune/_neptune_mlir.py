@@ -60,6 +60,21 @@ class _Scope:
         self.indent = indent
 
 
+def _backward_slice(lines: List[str], root: str) -> List[str]:
+    """the straight-line ops of `lines` ("%name = op %a, %b : type") that `root` depends on, in their order"""
+    import re
+    need, keep = {root}, []
+    for line in reversed(lines):
+        m = re.match(r"\s*(%[\w.$-]+)\s*=", line)
+        if m is None:
+            keep.append(line)            # not a single-result op: leave it alone
+            continue
+        if m.group(1) in need:
+            need.update(re.findall(r"%[\w.$-]+", line[m.end():]))
+            keep.append(line)
+    return keep[::-1]
+
+
 class Compiler:
     def __init__(self):
         self._top: List[str] = []          # module-level ops, in creation order
@@ -156,7 +171,9 @@ class Compiler:
 
     # ---- DSL core (NeptuneModule.cpp:21-27) -----------------------------------------------
     def create_apply(self, inputs: Sequence[Value], lb: Sequence[int], ub: Sequence[int],
-                     body_builder: Callable[[List[Value]], Value]) -> Value:
+                     body_builder: Callable[[List[Value]], Value], prune: Optional[Callable[[], bool]] = None) -> Value:
+        """`prune` (extension), asked after the body was built: keep only the region ops the yielded value depends on
+        (a kernel traced for one element of a tuple result also emitted the other elements' ops)"""
         if not inputs:
             raise ValueError("apply needs at least one input (it is the copy-through source)")
         for v in inputs:
@@ -181,6 +198,8 @@ class Compiler:
         out = body_builder(list(args))
         if not isinstance(out, Value) or out.type != _Type("scalar", res_t.elem):
             raise TypeError("apply body must return a scalar Value of the result's element type")
+        if prune is not None and prune():
+            self._scopes[-1].lines[:] = _backward_slice(self._scopes[-1].lines, out.name)
         self._emit(f"neptune_ir.yield {out.name} : {res_t.elem}")
         inner = self._scopes.pop()
         outer.lines.extend(inner.lines)

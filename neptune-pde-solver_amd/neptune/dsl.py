@@ -3,20 +3,57 @@ from .core import get_compiler
 from .expr import Expr
 
 
-def apply(inputs, bounds):
+def apply(inputs, bounds, through=None):
     """@neptune.apply(inputs=[u, v], bounds=([1], [9]))
-    def kernel(u, v): ...        -> Expr wrapping the apply's result temp"""
+    def kernel(u, v): ...        -> Expr wrapping the apply's result temp
+
+    A kernel that returns a tuple or list of Exprs (a system: `return res_h, res_q`) creates one apply per element, all
+    over the same inputs and bounds, in order, and the decorator returns a tuple of result Exprs.  The function is traced
+    once per element and each region keeps only what its own value needs.  `through=(i0, i1, ...)` names, per element,
+    which input is that apply's input 0 -- its copy-through source outside `bounds` and its result type; the function
+    still receives its arguments in the declared order.  Default: input 0 for every element.  The HIP lowering runs such
+    sibling applies as one multi-output kernel where it can."""
     lb, ub = bounds
     compiler = get_compiler()
+    handles = [i._handle for i in inputs]
 
     def decorator(func):
-        def body(arg_handles):
-            result = func(*[Expr(h) for h in arg_handles])
-            if not isinstance(result, Expr):
-                raise TypeError(f"Kernel must return a Neptune Expr, got {type(result)}")
-            return result._handle
+        state = {"count": None}
 
-        return Expr(compiler.create_apply([i._handle for i in inputs], lb, ub, body))
+        def order(first):          # the apply's operand order when declared input `first` is its input 0
+            return [first] + [k for k in range(len(handles)) if k != first]
+
+        def member(m, first):
+            perm = order(first)
+
+            def body(arg_handles):
+                declared = [None] * len(perm)
+                for pos, k in enumerate(perm):
+                    declared[k] = Expr(arg_handles[pos])
+                result = func(*declared)
+                if isinstance(result, Expr):
+                    if m != 0 or through is not None:
+                        raise TypeError("Kernel returned a single Expr where a tuple was expected")
+                    return result._handle
+                if not isinstance(result, (tuple, list)) or not result or not all(isinstance(r, Expr) for r in result):
+                    raise TypeError(f"Kernel must return a Neptune Expr, got {type(result)}")
+                if state["count"] is None:
+                    state["count"] = len(result)
+                elif state["count"] != len(result):
+                    raise TypeError("Kernel returned a different number of values when traced again")
+                return result[m]._handle
+
+            # a single Expr keeps the region exactly as traced; a member of a tuple drops the other members' ops
+            return Expr(compiler.create_apply([handles[k] for k in perm], lb, ub, body, prune=lambda: state["count"] is not None))
+
+        if through is not None and any(not 0 <= int(t) < len(handles) for t in through):
+            raise ValueError("through: input index out of range")
+        first = member(0, int(through[0]) if through is not None else 0)
+        if state["count"] is None:
+            return first
+        if through is not None and len(through) != state["count"]:
+            raise ValueError(f"through names {len(through)} inputs for a kernel that returns {state['count']} values")
+        return (first,) + tuple(member(m, int(through[m]) if through is not None else 0) for m in range(1, state["count"]))
 
     return decorator
 

@@ -136,6 +136,8 @@ SIGNATURES = {
     "neptune_hip_tune_stats": (None, [_i64p]),
     "neptune_hip_note_launch": (None, [_i, _i, _i]),
     "neptune_hip_last_launch": (_i, [_cfg_p]),
+    "neptune_hip_note_group": (None, [_i, _i]),
+    "neptune_hip_group_launch_counts": (None, [_i64p, _i64p]),
     "neptune_hip_time_copy": (_dbl, [_vp, _vp, _sz, _vp, _i, _i, _i]),
     "neptune_hip_copy_mode_count": (_i, []),
     "neptune_hip_event_create": (_vp, []),

@@ -93,6 +93,14 @@ def leapfrog_launch_counts():
     return singles.value, pairs.value
 
 
+def group_launch_counts():
+    """(groups of sibling applies run as ONE multi-output launch, member applies of a group run as launches of their
+    own) since the process started"""
+    fused, single = C.c_int64(0), C.c_int64(0)
+    _capi.load().neptune_hip_group_launch_counts(C.byref(fused), C.byref(single))
+    return fused.value, single.value
+
+
 def step_loop_leapfrog(entry, geom, fields: Sequence, extra: Sequence = (), steps: int = 0,
                        cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
     """`steps` steps of the two-level scheme u(n+1) = F(u(n), u(n-1), extra...) that `entry` computes (a lowered apply's
