@@ -184,6 +184,12 @@ int vec_update(int dtype, int64_t n, double a, const void* x, void* y, void* str
 }
 }  // namespace
 
+// step_loop.hip: destroys the cached graphs of the step loops (declared here rather than in a header: the headers of this
+// directory are hashed into NEPTUNE_HIP_BUILD_ID)
+namespace neptune_hip {
+__attribute__((visibility("hidden"))) void step_loop_destroy_graphs();
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------- runtime
@@ -207,38 +213,6 @@ void neptune_hip_init(int device) {
   s.inited = true;
 }
 
-// state of neptune_hip_step_loop (defined further down)
-namespace {
-struct LoopKey {
-  int applies, from0;         // (graph cache only) what one node of the cached graph is, and which field the loop started in
-  neptune_hip_apply_fn fn3;   // three chained applies in one launch (<tag>__geom3), or nullptr
-  neptune_hip_apply_fn fn2;   // two chained applies in one launch (a lowered apply's <tag>__geom2), or nullptr
-  neptune_hip_apply_fn fn;
-  int body;
-  neptune_hip_apply_geom_t g;
-  void* fields[2];
-  const void* in[NEPTUNE_HIP_MAX_INPUTS];
-  neptune_hip_launch_cfg_t cfg;
-  hipStream_t stream;
-  // neptune_hip_step_loop_leapfrog only (zero otherwise): the pair entry and fields[2..3]; `from0` then encodes which field
-  // plays which part when the graph starts
-  neptune_hip_leapfrog2_fn fnl;
-  void* more[2];
-};
-struct LoopGraph {
-  LoopKey key;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  uint64_t stamp = 0;
-};
-constexpr int kLoopGraphs = 8;
-LoopGraph g_loops[kLoopGraphs];
-uint64_t g_loop_clock = 0;
-
-hipStream_t g_loop_stream = nullptr;   // stands in for the legacy default stream, which cannot be captured
-hipEvent_t g_loop_ev[2] = {nullptr, nullptr};
-}  // namespace
-
 void neptune_hip_finalize(void) {
   RuntimeState& s = rt();
   std::lock_guard<std::mutex> lk(s.mu);
@@ -251,14 +225,7 @@ void neptune_hip_finalize(void) {
     (void)hipFree(s.reduce_ws);
     s.reduce_ws = nullptr;
   }
-  for (auto& e : g_loops)
-    if (e.exec) {
-      (void)hipGraphExecDestroy(e.exec);
-      (void)hipGraphDestroy(e.graph);
-      e.exec = nullptr;
-      e.graph = nullptr;
-      e.stamp = 0;
-    }
+  step_loop_destroy_graphs();
   for (auto& b : s.pool) (void)hipFree(b.p);
   s.pool.clear();
   s.pool_bytes = 0;
@@ -467,414 +434,6 @@ int neptune_hip_apply_chain_builtin(int body, int applies, const neptune_hip_app
 int neptune_hip_apply2_builtin(int body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out,
                                void* stream, const neptune_hip_launch_cfg_t* cfg) {
   return neptune_hip_apply_chain_builtin(body, 2, g, in, out, stream, cfg);
-}
-
-// ---------------------------------------------------------------- hipGraph step loop
-namespace {
-// `applies` (2 or 3) chained applies in one launch when the body and the geometry allow it (else NEPTUNE_HIP_EUNSUPPORTED)
-int loop_launch_chain(const LoopKey& k, int applies, int from, int to) {
-  // inputs 1.. (centre-only inputs of a lowered apply: the same field at every stage) ride along unchanged
-  const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-  for (int i = 0; i < k.g.num_inputs; ++i) ins[i] = k.in[i];
-  ins[0] = k.fields[from];
-  const neptune_hip_launch_cfg_t* cfg = (k.cfg.kernel || k.cfg.variant >= 0 || k.cfg.chunk || k.cfg.flags) ? &k.cfg : nullptr;
-  if (cfg && (cfg->kernel == NEPTUNE_HIP_KERNEL_DIRECT || cfg->variant >= 0)) return NEPTUNE_HIP_EUNSUPPORTED;  // an explicit tile was asked for
-  if (k.fn) {
-    neptune_hip_apply_fn f = applies == 2 ? k.fn2 : k.fn3;
-    return f ? f(&k.g, ins, k.fields[to], (void*)k.stream, cfg) : NEPTUNE_HIP_EUNSUPPORTED;
-  }
-  return neptune_hip_apply_chain_builtin(k.body, applies, &k.g, ins, k.fields[to], (void*)k.stream, cfg);
-}
-// The cached graph of `gkey`, captured on `stream` at first use: record() issues the launches of one period (a sequence
-// that leaves the state where it found it, so the graph can be replayed any number of times) and returns their first
-// error.  Graphs are cached by geometry, pointers, configuration and kind; the least recently used one makes room.
-// nullptr and *rc on failure.  The caller holds rt().mu.
-extern "C++" template <class R>
-LoopGraph* loop_graph(const LoopKey& gkey, hipStream_t stream, R&& record, int* rc) {
-  LoopGraph* slot = nullptr;
-  for (auto& e : g_loops)
-    if (e.exec && memcmp(&e.key, &gkey, sizeof(gkey)) == 0) slot = &e;
-  if (!slot) {
-    slot = &g_loops[0];
-    for (auto& e : g_loops)
-      if (e.stamp < slot->stamp) slot = &e;  // least recently used (empty slots have stamp 0)
-    if (slot->exec) {
-      (void)hipGraphExecDestroy(slot->exec);
-      (void)hipGraphDestroy(slot->graph);
-      slot->exec = nullptr;
-      slot->graph = nullptr;
-    }
-    NEPTUNE_HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
-    const int r = record();
-    hipGraph_t graph = nullptr;
-    NEPTUNE_HIP_CHECK(hipStreamEndCapture(stream, &graph));
-    if (r != NEPTUNE_HIP_OK || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      *rc = r != NEPTUNE_HIP_OK ? r : NEPTUNE_HIP_EINVAL;
-      return nullptr;
-    }
-    NEPTUNE_HIP_CHECK(hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0));
-    slot->graph = graph;
-    slot->key = gkey;
-  }
-  slot->stamp = ++g_loop_clock;
-  return slot;
-}
-int loop_launch(const LoopKey& k, int from, int to) {
-  const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-  for (int i = 0; i < k.g.num_inputs; ++i) ins[i] = k.in[i];
-  ins[0] = k.fields[from];
-  const neptune_hip_launch_cfg_t* cfg = (k.cfg.kernel || k.cfg.variant >= 0 || k.cfg.chunk || k.cfg.flags) ? &k.cfg : nullptr;
-  return k.fn ? k.fn(&k.g, ins, k.fields[to], (void*)k.stream, cfg)
-              : neptune_hip_apply_builtin(k.body, &k.g, ins, k.fields[to], (void*)k.stream, cfg);
-}
-}  // namespace
-
-int neptune_hip_step_loop(neptune_hip_apply_fn fn, int body, const neptune_hip_apply_geom_t* g, void* const fields[2],
-                          const void* const* in, int64_t steps, void* stream, const neptune_hip_launch_cfg_t* cfg) {
-  return neptune_hip_step_loop_pairs(fn, nullptr, body, g, fields, in, steps, stream, cfg);
-}
-
-int neptune_hip_step_loop_pairs(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, int body, const neptune_hip_apply_geom_t* g,
-                                void* const fields[2], const void* const* in, int64_t steps, void* stream,
-                                const neptune_hip_launch_cfg_t* cfg) {
-  return neptune_hip_step_loop_chain(fn, fn2, nullptr, body, g, fields, in, steps, stream, cfg);
-}
-
-int neptune_hip_step_loop_chain(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, neptune_hip_apply_fn fn3, int body,
-                                const neptune_hip_apply_geom_t* g, void* const fields[2], const void* const* in, int64_t steps,
-                                void* stream, const neptune_hip_launch_cfg_t* cfg) {
-  if (!g || !fields || !fields[0] || !fields[1] || fields[0] == fields[1] || steps < 0) return NEPTUNE_HIP_EINVAL;
-  if (g->num_inputs < 1 || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
-  if (g->num_inputs > 1 && !in) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  LoopKey key;
-  memset(&key, 0, sizeof(key));  // padding too: keys are compared with memcmp
-  key.fn = fn;
-  key.fn2 = fn ? fn2 : nullptr;
-  key.fn3 = fn ? fn3 : nullptr;
-  key.body = fn ? -1 : body;
-  key.g = *g;
-  key.fields[0] = fields[0];
-  key.fields[1] = fields[1];
-  for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in[i];
-  if (cfg) key.cfg = *cfg; else key.cfg.variant = -1;
-  key.stream = as_stream(stream);
-  if (steps == 0) return NEPTUNE_HIP_OK;
-  hipStream_t user = key.stream;
-  if (!user) {
-    // the legacy default stream cannot be captured: run the loop on an internal stream ordered after
-    // everything already queued on the default stream, and order the default stream after the loop
-    if (!g_loop_stream) {
-      NEPTUNE_HIP_CHECK(hipStreamCreateWithFlags(&g_loop_stream, hipStreamNonBlocking));
-      NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[0], hipEventDisableTiming));
-      NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[1], hipEventDisableTiming));
-    }
-    NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[0], nullptr));
-    NEPTUNE_HIP_CHECK(hipStreamWaitEvent(g_loop_stream, g_loop_ev[0], 0));
-    key.stream = g_loop_stream;
-  }
-  auto finish = [&](int rc) {
-    if (!user) {
-      NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[1], g_loop_stream));
-      NEPTUNE_HIP_CHECK(hipStreamWaitEvent(nullptr, g_loop_ev[1], 0));
-    }
-    return rc;
-  };
-
-  // `count` launches of `applies` chained applies each (1 = the plain apply), the first one reading fields[from0], every launch
-  // moving the state to the other field.  The first launch is a plain one (it validates the request and warms the
-  // launcher's one-time queries outside of stream capture); from 16 more on, a ping-pong pair of launches is captured
-  // once into a hipGraph of 16 kernel nodes and replayed (graphs cached by geometry, pointers, configuration and kind), so
-  // that small fields are not bound by launch overhead.  Returns NEPTUNE_HIP_EUNSUPPORTED from the FIRST launch untouched
-  // (nothing has run then).
-  auto run_launches = [&](int applies, int64_t count, int from0) -> int {
-    if (count <= 0) return NEPTUNE_HIP_OK;
-    auto launch = [&](int from, int to) { return applies == 1 ? loop_launch(key, from, to) : loop_launch_chain(key, applies, from, to); };
-    const int b0 = from0, b1 = from0 ^ 1;
-    int rc = launch(b0, b1);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    int64_t done = 1;
-    constexpr int kPairs = 8;  // ping-pong pairs per graph: 16 kernel nodes amortise one graph launch
-    if (count - done >= 2 * kPairs) {
-      LoopKey gkey = key;
-      gkey.applies = applies;
-      gkey.from0 = from0;
-      RuntimeState& s = rt();
-      std::lock_guard<std::mutex> lk(s.mu);
-      // the pair (b1 -> b0, b0 -> b1) leaves the state where it found it, so it can be replayed any number of times
-      LoopGraph* slot = loop_graph(gkey, key.stream, [&] {
-        int r1 = NEPTUNE_HIP_OK, r2 = NEPTUNE_HIP_OK;
-        for (int p = 0; p < kPairs && r1 == NEPTUNE_HIP_OK && r2 == NEPTUNE_HIP_OK; ++p) {
-          r1 = launch(b1, b0);
-          r2 = launch(b0, b1);
-        }
-        return r1 != NEPTUNE_HIP_OK ? r1 : r2;
-      }, &rc);
-      if (!slot) return rc;
-      for (; count - done >= 2 * kPairs; done += 2 * kPairs) NEPTUNE_HIP_CHECK(hipGraphLaunch(slot->exec, key.stream));
-    }
-    for (; done < count; ++done) {
-      rc = launch((int)((from0 + done) % 2), (int)((from0 + done + 1) % 2));
-      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-    }
-    return NEPTUNE_HIP_OK;
-  };
-
-  // Several steps per pass over HBM.  Every launch -- of one, two or three chained applies -- moves the state to the other
-  // field, and the newest state has to end in fields[steps % 2]:
-  //   * triples: steps = 3 T + r needs T + r launches, and T + r = steps (mod 2) always: T triples, then r < 3 single steps;
-  //   * pairs (when the triple entry does not exist or refuses): an EVEN number of pair launches brings the state back to
-  //     fields[0], the remaining < 4 steps run as single launches.
-  // The grouping does not change a bit: the same apply is evaluated, cell by cell, the same number of times on the same
-  // operands.  NEPTUNE_HIP_NO_PAIRS=1 keeps one apply per pass, NEPTUNE_HIP_NO_TRIPLES=1 stops at two.
-  // Chaining pays where a step is bound by HBM: a field that stays in the 256 MiB memory-side cache between steps gains
-  // nothing from saved passes and loses to the chain kernels' longer dependent march (measured, profiles/r02_twostep.txt:
-  // 128^3 and 1024^2 fp64 are faster one apply per launch, 256^3 and 2048^2 are faster chained: the line is 4e6 cells).
-  int64_t cells = 1;
-  for (int d = 0; d < g->rank; ++d) cells *= g->ub[d] > g->lb[d] ? g->ub[d] - g->lb[d] : 0;
-  const char* min_cells_env = getenv("NEPTUNE_HIP_CHAIN_MIN_CELLS");
-  const int64_t min_cells = min_cells_env ? atoll(min_cells_env) : (int64_t)4000000;
-  const bool chain_ok = cells >= min_cells && !getenv("NEPTUNE_HIP_NO_PAIRS");
-  // ... and whether chaining pays for THIS body is measured, once per (entry, geometry) and process: a Laplacian gains
-  // 1.7-2.4x, a 13-point operator 1.1x on its 3x8 window, a body heavy enough to be bound by its arithmetic loses (the
-  // windows overlap: every stage computes 1.3-1.8x the cells it keeps).  Each grouping the entry offers runs once to warm
-  // and twice under HIP events, from fields[0] into fields[1] -- exactly what the loop's first step overwrites anyway.
-  // Skipped for short loops, under stream capture and with NEPTUNE_HIP_TUNE=0 (then: the largest grouping offered).
-  int best = 3;
-  if (chain_ok && steps >= 8 && tune_mode() != 0) {
-    struct Choice { neptune_hip_apply_fn fn, fn2, fn3; int body; neptune_hip_apply_geom_t g; int best; };
-    static std::vector<Choice> choices;
-    static std::mutex cmu;
-    bool known = false;
-    {
-      std::lock_guard<std::mutex> lk(cmu);
-      for (const Choice& c : choices)
-        if (c.fn == key.fn && c.fn2 == key.fn2 && c.fn3 == key.fn3 && c.body == key.body && memcmp(&c.g, &key.g, sizeof(key.g)) == 0) {
-          best = c.best;
-          known = true;
-        }
-    }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(key.stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (!known && cs == hipStreamCaptureStatusNone) {
-      hipEvent_t e0, e1;
-      NEPTUNE_HIP_CHECK(hipEventCreate(&e0));
-      NEPTUNE_HIP_CHECK(hipEventCreate(&e1));
-      double best_ms = -1;
-      for (int applies = 1; applies <= 3; ++applies) {
-        if (applies == 3 && getenv("NEPTUNE_HIP_NO_TRIPLES")) continue;
-        auto one = [&] { return applies == 1 ? loop_launch(key, 0, 1) : loop_launch_chain(key, applies, 0, 1); };
-        if (one() != NEPTUNE_HIP_OK) continue;              // a grouping this entry / geometry does not offer
-        NEPTUNE_HIP_CHECK(hipEventRecord(e0, key.stream));
-        (void)one();
-        (void)one();
-        NEPTUNE_HIP_CHECK(hipEventRecord(e1, key.stream));
-        NEPTUNE_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0;
-        NEPTUNE_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        const double per_step = ms / (2.0 * applies);
-        if (best_ms < 0 || per_step < 0.97 * best_ms) { best_ms = per_step; best = applies; }   // a larger grouping must win by 3 %
-      }
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      std::lock_guard<std::mutex> lk(cmu);
-      choices.push_back({key.fn, key.fn2, key.fn3, key.body, key.g, best});
-    }
-  }
-  if (steps >= 3 && chain_ok && best >= 3 && !getenv("NEPTUNE_HIP_NO_TRIPLES")) {
-    const int64_t triples = steps / 3;
-    const int rc3 = run_launches(3, triples, 0);
-    if (rc3 == NEPTUNE_HIP_OK) return finish(run_launches(1, steps - 3 * triples, (int)(triples % 2)));
-    if (rc3 != NEPTUNE_HIP_EUNSUPPORTED) return finish(rc3);
-  }
-  if (steps >= 4 && chain_ok && best >= 2) {
-    const int64_t pairs = (steps / 2) & ~(int64_t)1;
-    const int rc2 = run_launches(2, pairs, 0);
-    if (rc2 == NEPTUNE_HIP_OK) return finish(run_launches(1, steps - 2 * pairs, 0));
-    if (rc2 != NEPTUNE_HIP_EUNSUPPORTED) return finish(rc2);
-  }
-  return finish(run_launches(1, steps, 0));
-}
-
-// ---------------------------------------------------------------- leapfrog step loop (two-level schemes)
-namespace {
-// which of the (up to) four fields plays which part: cur = u(n), prev = u(n-1), f1 / f2 = the free buffers
-struct LeapState { int cur, prev, f1, f2; };
-int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last loop
-}  // namespace
-
-void neptune_hip_leapfrog_launch_counts(int64_t* singles, int64_t* pairs) {
-  if (singles) *singles = g_leap_counts[0];
-  if (pairs) *pairs = g_leap_counts[1];
-}
-
-int neptune_hip_step_loop_leapfrog(neptune_hip_apply_fn fn, neptune_hip_leapfrog2_fn fn2, const neptune_hip_apply_geom_t* g,
-                                   void* const fields[4], const void* const* extra, int n_extra, int64_t steps, void* stream,
-                                   const neptune_hip_launch_cfg_t* cfg, int* cur, int* prev) {
-  if (!fn || !g || !fields || !fields[0] || !fields[1] || !fields[2] || steps < 0 || n_extra < 0) return NEPTUNE_HIP_EINVAL;
-  if (g->num_inputs != 2 + n_extra || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS || (n_extra > 0 && !extra)) return NEPTUNE_HIP_EINVAL;
-  const int nf = fields[3] ? 4 : 3;
-  for (int a = 0; a < nf; ++a)
-    for (int b = a + 1; b < nf; ++b)
-      if (fields[a] == fields[b]) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  LoopKey key;
-  memset(&key, 0, sizeof(key));  // padding too: keys are compared with memcmp
-  key.fn = fn;
-  key.fnl = fn2;
-  key.body = -1;
-  key.g = *g;
-  key.fields[0] = fields[0];
-  key.fields[1] = fields[1];
-  key.more[0] = fields[2];
-  key.more[1] = fields[3];
-  for (int i = 0; i < n_extra; ++i) key.in[2 + i] = extra[i];
-  if (cfg) key.cfg = *cfg; else key.cfg.variant = -1;
-  key.stream = as_stream(stream);
-  g_leap_counts[0] = g_leap_counts[1] = 0;
-  if (cur) *cur = 0;
-  if (prev) *prev = 1;
-  if (steps == 0) return NEPTUNE_HIP_OK;
-  hipStream_t user = key.stream;
-  if (!user) {   // the legacy default stream cannot be captured: as neptune_hip_step_loop_chain does
-    if (!g_loop_stream) {
-      NEPTUNE_HIP_CHECK(hipStreamCreateWithFlags(&g_loop_stream, hipStreamNonBlocking));
-      NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[0], hipEventDisableTiming));
-      NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[1], hipEventDisableTiming));
-    }
-    NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[0], nullptr));
-    NEPTUNE_HIP_CHECK(hipStreamWaitEvent(g_loop_stream, g_loop_ev[0], 0));
-    key.stream = g_loop_stream;
-  }
-  auto finish = [&](int rc, const LeapState& s) {
-    if (!user) {
-      NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[1], g_loop_stream));
-      NEPTUNE_HIP_CHECK(hipStreamWaitEvent(nullptr, g_loop_ev[1], 0));
-    }
-    if (cur) *cur = s.cur;
-    if (prev) *prev = s.prev;
-    return rc;
-  };
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(key.stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-  const bool capturing = cs != hipStreamCaptureStatusNone;
-
-  void* const F[4] = {fields[0], fields[1], fields[2], fields[3]};
-  const neptune_hip_launch_cfg_t* cfgp = (key.cfg.kernel || key.cfg.variant >= 0 || key.cfg.chunk || key.cfg.flags) ? &key.cfg : nullptr;
-  // one launch of `kind` steps (1: the apply itself into f1; 2: the pair entry into (f1, f2)) and the rotation after it:
-  //   single: (prev, cur, f1) <- (cur, f1, prev)                 -- period 3
-  //   pair:   (prev, cur) <- (v, w) = (f1, f2), (f1, f2) <- (old prev, old cur)   -- period 2
-  auto launch = [&](int kind, LeapState& s) -> int {
-    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    ins[0] = F[s.cur];
-    ins[1] = F[s.prev];
-    for (int i = 0; i < n_extra; ++i) ins[2 + i] = extra[i];
-    if (kind == 1) {
-      const int rc = fn(&key.g, ins, F[s.f1], (void*)key.stream, cfgp);
-      if (rc == NEPTUNE_HIP_OK) s = {s.f1, s.cur, s.prev, s.f2};
-      return rc;
-    }
-    const int rc = fn2(&key.g, ins, F[s.f1], F[s.f2], (void*)key.stream, cfgp);
-    if (rc == NEPTUNE_HIP_OK) s = {s.f2, s.f1, s.prev, s.cur};
-    return rc;
-  };
-  // `count` launches of one kind from state `s`: the first one plain (it validates the request outside of stream capture; its
-  // NEPTUNE_HIP_EUNSUPPORTED comes back untouched: nothing has run then), then whole periods as replays of a cached graph --
-  // ONE linear chain of 18 single or 8 pair launches, a multiple of the rotation's period -- then the rest plain.
-  auto run_launches = [&](int kind, int64_t count, LeapState& s) -> int {
-    if (count <= 0) return NEPTUNE_HIP_OK;
-    int rc = launch(kind, s);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    int64_t done = 1;
-    const int per_graph = kind == 1 ? 18 : 8;
-    if (!capturing && count - done >= per_graph) {
-      LoopKey gkey = key;
-      gkey.applies = kind;
-      gkey.from0 = 0x100 | s.cur | s.prev << 2 | s.f1 << 4 | (s.f2 & 3) << 6;
-      std::lock_guard<std::mutex> lk(rt().mu);
-      LoopGraph* slot = loop_graph(gkey, key.stream, [&] {
-        LeapState t = s;
-        int r = NEPTUNE_HIP_OK;
-        for (int i = 0; i < per_graph && r == NEPTUNE_HIP_OK; ++i) r = launch(kind, t);
-        return r;
-      }, &rc);
-      if (!slot) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-      for (; count - done >= per_graph; done += per_graph) NEPTUNE_HIP_CHECK(hipGraphLaunch(slot->exec, key.stream));
-    }
-    for (; done < count; ++done) {
-      rc = launch(kind, s);
-      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-    }
-    g_leap_counts[kind - 1] += count;
-    return NEPTUNE_HIP_OK;
-  };
-
-  // Pairs pay where a step is bound by HBM, and whether they pay for THIS body is measured: the rules of
-  // neptune_hip_step_loop_chain (field size, NEPTUNE_HIP_NO_PAIRS, 3 % margin, short loops, stream capture, NEPTUNE_HIP_TUNE=0
-  // -- read per call here).  best: 2 = pairs, 1 = singles, 0 = the pair entry refused this geometry (singles from then on).
-  int64_t cells = 1;
-  for (int d = 0; d < g->rank; ++d) cells *= g->ub[d] > g->lb[d] ? g->ub[d] - g->lb[d] : 0;
-  const char* min_cells_env = getenv("NEPTUNE_HIP_CHAIN_MIN_CELLS");
-  const int64_t min_cells = min_cells_env ? atoll(min_cells_env) : (int64_t)4000000;
-  const bool pairs_ok = fn2 && fields[3] && steps >= 2 && cells >= min_cells && !getenv("NEPTUNE_HIP_NO_PAIRS");
-  const char* tune_env = getenv("NEPTUNE_HIP_TUNE");
-  const bool tune = !(tune_env && *tune_env == '0');
-  struct Choice { neptune_hip_apply_fn fn; neptune_hip_leapfrog2_fn fn2; neptune_hip_apply_geom_t g; int best; };
-  static std::vector<Choice> choices;
-  static std::mutex cmu;
-  auto remember = [&](int best) {
-    std::lock_guard<std::mutex> lk(cmu);
-    for (Choice& c : choices)
-      if (c.fn == fn && c.fn2 == fn2 && memcmp(&c.g, &key.g, sizeof(key.g)) == 0) { c.best = best; return; }
-    choices.push_back({fn, fn2, key.g, best});
-  };
-  int best = 2;
-  LeapState st = {0, 1, 2, fields[3] ? 3 : -1};
-  if (pairs_ok) {
-    int known = -1;
-    {
-      std::lock_guard<std::mutex> lk(cmu);
-      for (const Choice& c : choices)
-        if (c.fn == fn && c.fn2 == fn2 && memcmp(&c.g, &key.g, sizeof(key.g)) == 0) known = c.best;
-    }
-    if (known == 0) best = 1;
-    else if (steps >= 8 && tune && known > 0) best = known;
-    else if (steps >= 8 && tune && !capturing) {
-      // each grouping once to warm and twice under HIP events, from (fields[0], fields[1]) into the free buffers -- which
-      // the loop's first steps overwrite
-      hipEvent_t e0, e1;
-      NEPTUNE_HIP_CHECK(hipEventCreate(&e0));
-      NEPTUNE_HIP_CHECK(hipEventCreate(&e1));
-      double best_ms = -1;
-      bool refused = false;
-      for (int kind = 1; kind <= 2; ++kind) {
-        auto one = [&] { LeapState t = st; return launch(kind, t); };
-        const int rc = one();
-        if (rc != NEPTUNE_HIP_OK) { refused = kind == 2 && rc == NEPTUNE_HIP_EUNSUPPORTED; continue; }
-        NEPTUNE_HIP_CHECK(hipEventRecord(e0, key.stream));
-        (void)one();
-        (void)one();
-        NEPTUNE_HIP_CHECK(hipEventRecord(e1, key.stream));
-        NEPTUNE_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0;
-        NEPTUNE_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        const double per_step = ms / (2.0 * kind);
-        if (best_ms < 0 || per_step < 0.97 * best_ms) { best_ms = per_step; best = kind; }   // pairs must win by 3 %
-      }
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      remember(refused ? 0 : best);
-    }
-  }
-  if (pairs_ok && best >= 2) {
-    const int64_t pairs = steps / 2;
-    const int rc2 = run_launches(2, pairs, st);
-    if (rc2 == NEPTUNE_HIP_OK) return finish(run_launches(1, steps - 2 * pairs, st), st);
-    if (rc2 != NEPTUNE_HIP_EUNSUPPORTED) return finish(rc2, st);
-    remember(0);   // nothing has run: single launches, now and for the rest of the process
-  }
-  return finish(run_launches(1, steps, st), st);
 }
 
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t* g, const void* const* in,

@@ -1,0 +1,430 @@
+// step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (stream scope, graph cache, replay,
+// grouping choice) that knows nothing about ping-pong or leapfrog, and the two loops built on it: neptune_hip_step_loop_chain
+// (one-level schemes, two fields) and neptune_hip_step_loop_leapfrog (two-level schemes, three or four fields).  Host code
+// only (its own translation unit: builds in seconds, linked into libneptune_hip.so); it launches through the public C API.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../../include/neptune_hip.h"
+#include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no kernel is instantiated here)
+
+using namespace neptune_hip;
+
+namespace {
+
+// what neptune_hip_rt.hip's ensure_init does (device 0 unless the runtime is up already), through the public API
+void ensure_init() { (void)neptune_hip_cu_count(); }
+
+// ---------------------------------------------------------------- what a loop is: the key of both caches
+using group_fn = void (*)();   // an entry of a larger grouping, untyped: the caches only compare it
+struct LoopKey {
+  neptune_hip_apply_fn fn;     // the single-step entry (launch kind 1), or nullptr: built-in body `body`
+  int body;
+  // the optional entries of launch kinds 2 and 3, nullptr = none: <tag>__geom2 / __geom3 in the one-level loop,
+  // <tag>__geomL2 / nothing in the leapfrog loop (two loops cannot meet in a cache: their entry types differ)
+  group_fn more[2];
+  neptune_hip_apply_geom_t g;
+  void* fields[4];             // the rotating fields, nullptr beyond the loop's own two, three or four
+  const void* in[NEPTUNE_HIP_MAX_INPUTS];   // the inputs that are no state (centre-only inputs: the same field at every stage)
+  neptune_hip_launch_cfg_t cfg;
+  hipStream_t stream;
+  int kind, state;             // (graph cache only) what one node of the graph is, and the rotation state at graph start
+};
+// the part of a key that is common to every loop; padding too: keys are compared with memcmp
+void init_key(LoopKey& k, neptune_hip_apply_fn fn, int body, const neptune_hip_apply_geom_t* g, const neptune_hip_launch_cfg_t* cfg,
+              hipStream_t stream) {
+  memset(&k, 0, sizeof(k));
+  k.fn = fn;
+  k.body = body;
+  k.g = *g;
+  if (cfg) k.cfg = *cfg; else k.cfg.variant = -1;
+  k.stream = stream;
+}
+// the cfg to launch with: nullptr unless the caller set anything
+const neptune_hip_launch_cfg_t* loop_cfg(const LoopKey& k) {
+  return (k.cfg.kernel || k.cfg.variant >= 0 || k.cfg.chunk || k.cfg.flags) ? &k.cfg : nullptr;
+}
+// the inputs of one launch: the state in fields[cur], a two-level scheme's previous state in fields[prev] (-1: none), the rest
+// riding along unchanged
+void loop_inputs(const LoopKey& k, const void** ins, int cur, int prev) {
+  for (int i = 0; i < k.g.num_inputs; ++i) ins[i] = k.in[i];
+  ins[0] = k.fields[cur];
+  if (prev >= 0) ins[1] = k.fields[prev];
+}
+
+// ---------------------------------------------------------------- stream scope
+hipStream_t g_loop_stream = nullptr;   // stands in for the legacy default stream, which cannot be captured
+hipEvent_t g_loop_ev[2] = {nullptr, nullptr};
+
+// The stream a loop body runs on, and whether the caller is capturing it.  The legacy default stream cannot be captured: the
+// loop then runs on an internal stream ordered after everything already queued on the default stream, and the destructor
+// orders the default stream after the loop -- on every exit path.
+struct StreamScope {
+  hipStream_t stream;
+  bool capturing;
+  const bool bridged;
+  explicit StreamScope(hipStream_t user) : stream(user), bridged(!user) {
+    if (bridged) {
+      if (!g_loop_stream) {
+        NEPTUNE_HIP_CHECK(hipStreamCreateWithFlags(&g_loop_stream, hipStreamNonBlocking));
+        NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[0], hipEventDisableTiming));
+        NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[1], hipEventDisableTiming));
+      }
+      NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[0], nullptr));
+      NEPTUNE_HIP_CHECK(hipStreamWaitEvent(g_loop_stream, g_loop_ev[0], 0));
+      stream = g_loop_stream;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    capturing = cs != hipStreamCaptureStatusNone;
+  }
+  ~StreamScope() {
+    if (bridged) {
+      NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[1], g_loop_stream));
+      NEPTUNE_HIP_CHECK(hipStreamWaitEvent(nullptr, g_loop_ev[1], 0));
+    }
+  }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+};
+
+// ---------------------------------------------------------------- graph cache
+struct LoopGraph {
+  LoopKey key;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  uint64_t stamp = 0;
+};
+constexpr int kLoopGraphs = 8;
+LoopGraph g_loops[kLoopGraphs];
+uint64_t g_loop_clock = 0;
+std::mutex g_loop_mu;
+
+void destroy_graph(LoopGraph& e) {
+  if (!e.exec) return;
+  (void)hipGraphExecDestroy(e.exec);
+  (void)hipGraphDestroy(e.graph);
+  e.exec = nullptr;
+  e.graph = nullptr;
+}
+
+// The cached graph of `gkey`, captured on `stream` at first use: record() issues the launches of one period (a sequence
+// that leaves the state where it found it, so the graph can be replayed any number of times) and returns their first
+// error.  Graphs are cached by geometry, pointers, configuration and kind; the least recently used one makes room.
+// nullptr and *rc on failure.  The caller holds g_loop_mu.
+template <class R>
+LoopGraph* loop_graph(const LoopKey& gkey, hipStream_t stream, R&& record, int* rc) {
+  LoopGraph* slot = nullptr;
+  for (auto& e : g_loops)
+    if (e.exec && memcmp(&e.key, &gkey, sizeof(gkey)) == 0) slot = &e;
+  if (!slot) {
+    slot = &g_loops[0];
+    for (auto& e : g_loops)
+      if (e.stamp < slot->stamp) slot = &e;  // least recently used (empty slots have stamp 0)
+    destroy_graph(*slot);
+    NEPTUNE_HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
+    const int r = record();
+    hipGraph_t graph = nullptr;
+    NEPTUNE_HIP_CHECK(hipStreamEndCapture(stream, &graph));
+    if (r != NEPTUNE_HIP_OK || !graph) {
+      if (graph) (void)hipGraphDestroy(graph);
+      *rc = r != NEPTUNE_HIP_OK ? r : NEPTUNE_HIP_EINVAL;
+      return nullptr;
+    }
+    NEPTUNE_HIP_CHECK(hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0));
+    slot->graph = graph;
+    memcpy(&slot->key, &gkey, sizeof(gkey));
+  }
+  slot->stamp = ++g_loop_clock;
+  return slot;
+}
+
+// ---------------------------------------------------------------- replay
+// which of the one-level loop's two fields holds the state
+int state_code(int from) { return from; }
+// which of the leapfrog loop's (up to) four fields plays which part: cur = u(n), prev = u(n-1), f1 / f2 = the free buffers
+struct LeapState { int cur, prev, f1, f2; };
+int state_code(const LeapState& s) { return s.cur | s.prev << 2 | s.f1 << 4 | (s.f2 & 3) << 6; }
+
+// `count` launches of one kind from state `s`; launch(kind, s) issues one and, when it succeeds, rotates `s`.  The first
+// launch is a plain one: it validates the request and warms the launcher's one-time queries outside of stream capture, and
+// its code comes back untouched -- NEPTUNE_HIP_EUNSUPPORTED from the FIRST launch means that nothing has run, and the caller
+// may fall back to another grouping.  Then whole graphs of `per_graph` launches, captured once and replayed from the cache, so
+// that small fields are not bound by launch overhead; per_graph is a multiple of the rotation's period, so a graph leaves
+// the state where it found it.  Not inside a caller's capture: a capturing stream cannot begin another one.  Then the rest
+// plain.  After the first launch the state has moved, so a late NEPTUNE_HIP_EUNSUPPORTED is an error: NEPTUNE_HIP_EINVAL.
+template <class State, class Launch>
+int replay(LoopKey& key, const StreamScope& sc, int kind, int64_t count, State& s, int per_graph, Launch&& launch) {
+  if (count <= 0) return NEPTUNE_HIP_OK;
+  int rc = launch(kind, s);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  int64_t done = 1;
+  if (!sc.capturing && count - done >= per_graph) {
+    key.kind = kind;
+    key.state = state_code(s);
+    std::lock_guard<std::mutex> lk(g_loop_mu);
+    LoopGraph* slot = loop_graph(key, sc.stream, [&] {
+      State t = s;
+      int r = NEPTUNE_HIP_OK;
+      for (int i = 0; i < per_graph && r == NEPTUNE_HIP_OK; ++i) r = launch(kind, t);
+      return r;
+    }, &rc);
+    if (!slot) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+    for (; count - done >= per_graph; done += per_graph) NEPTUNE_HIP_CHECK(hipGraphLaunch(slot->exec, sc.stream));
+  }
+  for (; done < count; ++done) {
+    rc = launch(kind, s);
+    if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+  }
+  return NEPTUNE_HIP_OK;
+}
+
+// ---------------------------------------------------------------- grouping choice
+// Several steps per launch pay where a step is bound by HBM: a field that stays in the 256 MiB memory-side cache between
+// steps gains nothing from saved passes and loses to the chain kernels' longer dependent march (measured,
+// profiles/r02_twostep.txt: 128^3 and 1024^2 fp64 are faster one apply per launch, 256^3 and 2048^2 are faster chained: the
+// line is 4e6 cells).  NEPTUNE_HIP_NO_PAIRS=1 keeps one step per launch.  Both are read on every call.
+bool grouping_allowed(const neptune_hip_apply_geom_t* g) {
+  int64_t cells = 1;
+  for (int d = 0; d < g->rank; ++d) cells *= g->ub[d] > g->lb[d] ? g->ub[d] - g->lb[d] : 0;
+  const char* min_cells_env = getenv("NEPTUNE_HIP_CHAIN_MIN_CELLS");
+  const int64_t min_cells = min_cells_env ? atoll(min_cells_env) : (int64_t)4000000;
+  return cells >= min_cells && !getenv("NEPTUNE_HIP_NO_PAIRS");
+}
+
+// the grouping to start with, per (entries, geometry) and process; 0 = the largest grouping's entry refused this geometry:
+// single launches from now on
+struct Choice { neptune_hip_apply_fn fn; int body; group_fn more[2]; neptune_hip_apply_geom_t g; int best; };
+std::vector<Choice> g_choices;
+std::mutex g_choice_mu;
+// caller holds g_choice_mu
+Choice* find_choice(const LoopKey& k) {
+  for (Choice& c : g_choices)
+    if (c.fn == k.fn && c.body == k.body && c.more[0] == k.more[0] && c.more[1] == k.more[1] && memcmp(&c.g, &k.g, sizeof(k.g)) == 0)
+      return &c;
+  return nullptr;
+}
+void remember_grouping(const LoopKey& k, int best) {
+  std::lock_guard<std::mutex> lk(g_choice_mu);
+  if (Choice* c = find_choice(k)) c->best = best;
+  else g_choices.push_back({k.fn, k.body, {k.more[0], k.more[1]}, k.g, best});
+}
+
+// How many steps per launch (1 .. largest) the loop should try first, where grouping_allowed().  Whether grouping pays for
+// THIS body is measured, once per (entries, geometry) and process: a Laplacian gains 1.7-2.4x from chaining, a 13-point
+// operator 1.1x on its 3x8 window, a body heavy enough to be bound by its arithmetic loses (the windows overlap: every stage
+// computes 1.3-1.8x the cells it keeps).  Each grouping the entries offer runs once to warm and twice under HIP events, from
+// state `s0` into the buffers that the loop's first launch overwrites anyway.  Not measured (then: the largest grouping)
+// unless `measure` -- the loop is long enough and tuning is on -- and not under stream capture.
+// measure: the caller's business because the two loops read NEPTUNE_HIP_TUNE differently on purpose -- the one-level loop
+// through the process-wide cached tune_mode(), the leapfrog loop on every call (its callers flip it within one process).
+// refusal_is_final: NEPTUNE_HIP_EUNSUPPORTED from the largest grouping's trial is remembered as 0 (the leapfrog loop; the
+// one-level loop has a middle grouping left to try).
+template <class State, class Launch>
+int choose_grouping(const LoopKey& key, const StreamScope& sc, bool measure, int largest, bool refusal_is_final, const State& s0,
+                    Launch&& launch) {
+  int known = -1;
+  {
+    std::lock_guard<std::mutex> lk(g_choice_mu);
+    if (const Choice* c = find_choice(key)) known = c->best;
+  }
+  if (known == 0) return 1;
+  if (!measure) return largest;
+  if (known > 0) return known;
+  if (sc.capturing) return largest;
+  hipEvent_t e0, e1;
+  NEPTUNE_HIP_CHECK(hipEventCreate(&e0));
+  NEPTUNE_HIP_CHECK(hipEventCreate(&e1));
+  int best = largest;
+  double best_ms = -1;
+  bool refused = false;
+  for (int kind = 1; kind <= largest; ++kind) {
+    auto one = [&] { State t = s0; return launch(kind, t); };
+    const int rc = one();
+    if (rc != NEPTUNE_HIP_OK) {   // a grouping these entries / this geometry do not offer
+      refused = refusal_is_final && kind == largest && rc == NEPTUNE_HIP_EUNSUPPORTED;
+      continue;
+    }
+    NEPTUNE_HIP_CHECK(hipEventRecord(e0, sc.stream));
+    (void)one();
+    (void)one();
+    NEPTUNE_HIP_CHECK(hipEventRecord(e1, sc.stream));
+    NEPTUNE_HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    NEPTUNE_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    const double per_step = ms / (2.0 * kind);
+    if (best_ms < 0 || per_step < 0.97 * best_ms) { best_ms = per_step; best = kind; }   // a larger grouping must win by 3 %
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  remember_grouping(key, refused ? 0 : best);
+  return best;
+}
+
+int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last leapfrog loop
+
+}  // namespace
+
+namespace neptune_hip {
+// for neptune_hip_finalize (declared in neptune_hip_rt.hip; not exported)
+__attribute__((visibility("hidden"))) void step_loop_destroy_graphs() {
+  std::lock_guard<std::mutex> lk(g_loop_mu);
+  for (auto& e : g_loops) {
+    destroy_graph(e);
+    e.stamp = 0;
+  }
+}
+}  // namespace neptune_hip
+
+extern "C" {
+
+// ---------------------------------------------------------------- one-level loop: two fields, ping-pong
+int neptune_hip_step_loop(neptune_hip_apply_fn fn, int body, const neptune_hip_apply_geom_t* g, void* const fields[2],
+                          const void* const* in, int64_t steps, void* stream, const neptune_hip_launch_cfg_t* cfg) {
+  return neptune_hip_step_loop_pairs(fn, nullptr, body, g, fields, in, steps, stream, cfg);
+}
+
+int neptune_hip_step_loop_pairs(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, int body, const neptune_hip_apply_geom_t* g,
+                                void* const fields[2], const void* const* in, int64_t steps, void* stream,
+                                const neptune_hip_launch_cfg_t* cfg) {
+  return neptune_hip_step_loop_chain(fn, fn2, nullptr, body, g, fields, in, steps, stream, cfg);
+}
+
+int neptune_hip_step_loop_chain(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, neptune_hip_apply_fn fn3, int body,
+                                const neptune_hip_apply_geom_t* g, void* const fields[2], const void* const* in, int64_t steps,
+                                void* stream, const neptune_hip_launch_cfg_t* cfg) {
+  if (!g || !fields || !fields[0] || !fields[1] || fields[0] == fields[1] || steps < 0) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs < 1 || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs > 1 && !in) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  if (steps == 0) return NEPTUNE_HIP_OK;
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  const neptune_hip_apply_fn chain[2] = {fn ? fn2 : nullptr, fn ? fn3 : nullptr};
+  LoopKey key;
+  init_key(key, fn, fn ? -1 : body, g, cfg, sc.stream);
+  key.more[0] = (group_fn)chain[0];
+  key.more[1] = (group_fn)chain[1];
+  key.fields[0] = fields[0];
+  key.fields[1] = fields[1];
+  for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in[i];
+
+  // one launch of `applies` chained applies (1 = the plain apply) from fields[from] into the other field, which then holds
+  // the state; a grouping the body or the geometry does not allow returns NEPTUNE_HIP_EUNSUPPORTED
+  auto launch = [&](int applies, int& from) -> int {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    loop_inputs(key, ins, from, -1);
+    const neptune_hip_launch_cfg_t* c = loop_cfg(key);
+    void* out = key.fields[from ^ 1];
+    int rc;
+    if (applies == 1)
+      rc = fn ? fn(&key.g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(key.body, &key.g, ins, out, (void*)sc.stream, c);
+    else if (c && (c->kernel == NEPTUNE_HIP_KERNEL_DIRECT || c->variant >= 0))
+      rc = NEPTUNE_HIP_EUNSUPPORTED;   // an explicit tile was asked for
+    else if (fn)
+      rc = chain[applies - 2] ? chain[applies - 2](&key.g, ins, out, (void*)sc.stream, c) : NEPTUNE_HIP_EUNSUPPORTED;
+    else
+      rc = neptune_hip_apply_chain_builtin(key.body, applies, &key.g, ins, out, (void*)sc.stream, c);
+    if (rc == NEPTUNE_HIP_OK) from ^= 1;
+    return rc;
+  };
+  int from = 0;
+  // graphs of 8 ping-pong pairs (the rotation's period is 2): 16 kernel nodes amortise one graph launch
+  auto run = [&](int applies, int64_t count) { return replay(key, sc, applies, count, from, 16, launch); };
+
+  // Several steps per pass over HBM.  Every launch -- of one, two or three chained applies -- moves the state to the other
+  // field, and the newest state has to end in fields[steps % 2]:
+  //   * triples: steps = 3 T + r needs T + r launches, and T + r = steps (mod 2) always: T triples, then r < 3 single steps;
+  //   * pairs (when the triple entry does not exist or refuses): an EVEN number of pair launches brings the state back to
+  //     fields[0], the remaining < 4 steps run as single launches.
+  // The grouping does not change a bit: the same apply is evaluated, cell by cell, the same number of times on the same
+  // operands.  NEPTUNE_HIP_NO_TRIPLES=1 stops at two applies per launch.
+  const bool chain_ok = grouping_allowed(g), triples_ok = !getenv("NEPTUNE_HIP_NO_TRIPLES");
+  const int best = chain_ok ? choose_grouping(key, sc, steps >= 8 && tune_mode() != 0, triples_ok ? 3 : 2, false, from, launch) : 1;
+  if (steps >= 3 && best >= 3 && triples_ok) {
+    const int64_t triples = steps / 3;
+    const int rc3 = run(3, triples);
+    if (rc3 == NEPTUNE_HIP_OK) return run(1, steps - 3 * triples);
+    if (rc3 != NEPTUNE_HIP_EUNSUPPORTED) return rc3;
+  }
+  if (steps >= 4 && best >= 2) {
+    const int64_t pairs = (steps / 2) & ~(int64_t)1;
+    const int rc2 = run(2, pairs);
+    if (rc2 == NEPTUNE_HIP_OK) return run(1, steps - 2 * pairs);
+    if (rc2 != NEPTUNE_HIP_EUNSUPPORTED) return rc2;
+  }
+  return run(1, steps);
+}
+
+// ---------------------------------------------------------------- leapfrog loop (two-level schemes): three or four fields
+void neptune_hip_leapfrog_launch_counts(int64_t* singles, int64_t* pairs) {
+  if (singles) *singles = g_leap_counts[0];
+  if (pairs) *pairs = g_leap_counts[1];
+}
+
+int neptune_hip_step_loop_leapfrog(neptune_hip_apply_fn fn, neptune_hip_leapfrog2_fn fn2, const neptune_hip_apply_geom_t* g,
+                                   void* const fields[4], const void* const* extra, int n_extra, int64_t steps, void* stream,
+                                   const neptune_hip_launch_cfg_t* cfg, int* cur, int* prev) {
+  if (!fn || !g || !fields || !fields[0] || !fields[1] || !fields[2] || steps < 0 || n_extra < 0) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs != 2 + n_extra || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS || (n_extra > 0 && !extra)) return NEPTUNE_HIP_EINVAL;
+  const int nf = fields[3] ? 4 : 3;
+  for (int a = 0; a < nf; ++a)
+    for (int b = a + 1; b < nf; ++b)
+      if (fields[a] == fields[b]) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  g_leap_counts[0] = g_leap_counts[1] = 0;
+  LeapState st = {0, 1, 2, fields[3] ? 3 : -1};
+  auto result = [&](int rc) {
+    if (cur) *cur = st.cur;
+    if (prev) *prev = st.prev;
+    return rc;
+  };
+  if (steps == 0) return result(NEPTUNE_HIP_OK);
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  LoopKey key;
+  init_key(key, fn, -1, g, cfg, sc.stream);
+  key.more[0] = (group_fn)fn2;
+  for (int a = 0; a < 4; ++a) key.fields[a] = fields[a];
+  for (int i = 0; i < n_extra; ++i) key.in[2 + i] = extra[i];
+
+  // one launch of `kind` steps (1: the apply itself into f1; 2: the pair entry into (f1, f2)) and the rotation after it:
+  //   single: (prev, cur, f1) <- (cur, f1, prev)                 -- period 3
+  //   pair:   (prev, cur) <- (v, w) = (f1, f2), (f1, f2) <- (old prev, old cur)   -- period 2
+  auto launch = [&](int kind, LeapState& s) -> int {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    loop_inputs(key, ins, s.cur, s.prev);
+    if (kind == 1) {
+      const int rc = fn(&key.g, ins, key.fields[s.f1], (void*)sc.stream, loop_cfg(key));
+      if (rc == NEPTUNE_HIP_OK) s = {s.f1, s.cur, s.prev, s.f2};
+      return rc;
+    }
+    const int rc = fn2(&key.g, ins, key.fields[s.f1], key.fields[s.f2], (void*)sc.stream, loop_cfg(key));
+    if (rc == NEPTUNE_HIP_OK) s = {s.f2, s.f1, s.prev, s.cur};
+    return rc;
+  };
+  // ONE linear chain per graph, a multiple of the rotation's period: 18 single or 8 pair launches
+  auto run = [&](int kind, int64_t count) {
+    const int rc = replay(key, sc, kind, count, st, kind == 1 ? 18 : 8, launch);
+    if (rc == NEPTUNE_HIP_OK && count > 0) g_leap_counts[kind - 1] += count;
+    return rc;
+  };
+
+  // steps / 2 pairs, then at most one single launch -- where pairs are allowed and chosen; single launches otherwise.
+  // NEPTUNE_HIP_TUNE is read on every call here.
+  const char* tune_env = getenv("NEPTUNE_HIP_TUNE");
+  const bool tune = !(tune_env && *tune_env == '0');
+  const bool pairs_ok = fn2 && fields[3] && steps >= 2 && grouping_allowed(g);
+  if (pairs_ok && choose_grouping(key, sc, steps >= 8 && tune, 2, true, st, launch) >= 2) {
+    const int64_t pairs = steps / 2;
+    const int rc2 = run(2, pairs);
+    if (rc2 == NEPTUNE_HIP_OK) return result(run(1, steps - 2 * pairs));
+    if (rc2 != NEPTUNE_HIP_EUNSUPPORTED) return result(rc2);
+    remember_grouping(key, 0);   // nothing has run: single launches, now and for the rest of the process
+  }
+  return result(run(1, steps));
+}
+
+}  // extern "C"
