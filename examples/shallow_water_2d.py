@@ -9,8 +9,10 @@
 The front end makes one apply per returned value over the same three inputs (`through`: each unknown is its own
 copy-through source on the boundary), and the HIP lowering runs the three sibling applies as one multi-output launch:
 every field is read once per step instead of three times.  A Lax-Friedrichs step (centred fluxes, neighbour average), so
-the plain scheme is stable.  The step is timed with the group launch and with NEPTUNE_HIP_NO_GROUPS=1 (one launch per
-member), each in a fresh child process: the variable is read per call, but measured tile choices are cached per process.
+the plain scheme is stable.  The step is timed three ways, each in a fresh child process (NEPTUNE_HIP_NO_GROUPS is read per
+call, but measured tile choices are cached per process): a host loop of `mod.call("step", ...)` with the group launch, the
+same with NEPTUNE_HIP_NO_GROUPS=1 (one launch per member), and the whole run through neptune_hip.apply.step_loop_system
+on the group's geometry-level entry -- no per-step binding, checking or synchronising, long runs replayed from a hipGraph.
 
 usage: examples/shallow_water_2d.py [N] [STEPS]        (default 4096^2, 50 steps)"""
 import json
@@ -63,22 +65,32 @@ def build(n, lam=0.2, g=1.0):
     return mod
 
 
-def child(n, steps):
+def child(n, steps, mode):
     import torch
     from neptune_hip import apply
     mod = build(n)
     x = torch.arange(n, dtype=torch.float64, device="cuda") - n / 2
     bump = torch.exp(-(x[:, None] ** 2 + x[None, :] ** 2) / (n / 16) ** 2)
-    cur = [1.0 + 0.1 * bump, torch.zeros_like(bump), torch.zeros_like(bump)]
+    start = [1.0 + 0.1 * bump, torch.zeros_like(bump), torch.zeros_like(bump)]
+    cur = [t.clone() for t in start]
     nxt = [t.clone() for t in cur]                      # boundary cells keep their values (copy-through)
     mass0 = float(cur[0][1:-1, 1:-1].sum())
+    bounds = ([1, 1], [n - 1, n - 1])
+    entry = mod.group_entry("step") if mode == "loop" else None
     for _ in range(3):                                  # warm-up: the first launch measures its tile
         mod.call("step", *nxt, *cur)
+    if entry is not None:                               # ... and the loop captures the graph of these buffers
+        apply.step_loop_system(entry, bounds, cur, nxt, steps=34)
+        for t, u in zip(cur, start):
+            t.copy_(u)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        mod.call("step", *nxt, *cur)
-        cur, nxt = nxt, cur
+    if entry is not None:
+        cur = apply.step_loop_system(entry, bounds, cur, nxt, steps=steps)
+    else:
+        for _ in range(steps):
+            mod.call("step", *nxt, *cur)
+            cur, nxt = nxt, cur
     torch.cuda.synchronize()
     per = (time.perf_counter() - t0) / steps
     fused, single = apply.group_launch_counts()
@@ -90,19 +102,21 @@ def child(n, steps):
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        return child(int(sys.argv[2]), int(sys.argv[3]))
+        return child(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4])
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
     res = {}
-    for label, extra in (("one group launch", {}), ("one launch per member", {"NEPTUNE_HIP_NO_GROUPS": "1"})):
+    for label, extra, mode in (("one group launch", {}, "host"), ("one launch per member", {"NEPTUNE_HIP_NO_GROUPS": "1"}, "host"),
+                               ("system step loop", {}, "loop")):
         env = dict(os.environ, **extra)
-        p = subprocess.run([sys.executable, __file__, "--child", str(n), str(steps)], env=env, capture_output=True, text=True, check=True)
+        p = subprocess.run([sys.executable, __file__, "--child", str(n), str(steps), mode], env=env, capture_output=True, text=True, check=True)
         res[label] = r = json.loads(p.stdout.strip().splitlines()[-1])
         print(f"{label:>22}: {r['ms_per_step']:.3f} ms/step, {r['tb_s_over_6_fields']:.2f} TB/s over 3 + 3 fields, "
               f"{r['fused_launches']} group / {r['member_launches']} member launches, finite: {r['finite']}, mass drift {r['mass_drift']:.1e}")
     g = res["one group launch"]["groups"]
     print("group:", g[0]["members"] if g else "none", "planned on", g[0]["kernel"] if g else "-",
-          f"-> {res['one launch per member']['ms_per_step'] / res['one group launch']['ms_per_step']:.2f}x")
+          f"-> {res['one launch per member']['ms_per_step'] / res['one group launch']['ms_per_step']:.2f}x;",
+          f"step loop against the host loop: {res['one group launch']['ms_per_step'] / res['system step loop']['ms_per_step']:.2f}x")
 
 
 if __name__ == "__main__":

@@ -313,6 +313,35 @@ int neptune_hip_step_loop_leapfrog(neptune_hip_apply_fn fn, neptune_hip_leapfrog
  * (its trial launches not counted) */
 void neptune_hip_leapfrog_launch_counts(int64_t *singles, int64_t *pairs);
 
+/* Systems of equations: a GROUP of sibling applies over shared inputs (2..4 members over at most 4 union inputs, e.g. the
+ * (h, qx, qy) updates of a shallow-water step) that a lowered module computes in one multi-output launch exports
+ * <function>_<k0>_group__geom next to its members' <function>_<k>__geom.  `g` describes the UNION inputs -- num_inputs of
+ * them, in the order of the lowering report's groups[i]["inputs"] -- and the result box, apply.bounds and launch region as
+ * for neptune_hip_apply_fn; out[m] is member m's result buffer.  No allocation, no synchronisation.  Every member's result
+ * is always computed: in ONE launch where that form exists, else by the members' own launches (no group form for the union
+ * footprint, a result not 16-byte aligned, a member's copy-through input in another box than the result,
+ * NEPTUNE_HIP_NO_GROUPS=1) -- the same bits either way, members never read each other's results.  Refused, nothing
+ * launched: a null pointer, or a result that overlaps an input or another result (NEPTUNE_HIP_EINVAL); a member reaching
+ * outside an input's box (NEPTUNE_HIP_EOOB). */
+typedef int (*neptune_hip_group_fn)(const neptune_hip_apply_geom_t *g, const void *const *in, void *const *out,
+                                    void *stream, const neptune_hip_launch_cfg_t *cfg);
+
+/* `steps` steps of a system on two SETS of fields.  Member m advances union input through[m] (the report's
+ * groups[i]["through"]); fields_a[m] / fields_b[m] are that unknown's two buffers, n_out = 2..4 of them.  Step s reads set
+ * s % 2 (0 = a) at the inputs through[m] and writes the other set; union inputs that are nobody's unknown (a bathymetry, a
+ * coefficient field) are fixed: in[k] supplies them, the other slots of `in` are ignored (in may be NULL when there are
+ * none).  After the call the newest state is in set steps % 2; every launch is one step, so the OTHER set holds state
+ * steps - 1.  Asynchronous on `stream`; long runs replay a cached hipGraph (one linear chain of 16 launches), as
+ * neptune_hip_step_loop does; one launch kind, no trial launches; inside a caller's stream capture plain launches.
+ * NEPTUNE_HIP_EINVAL before anything runs: n_out outside 2..4, a through[] out of range or repeated, two of the 2 n_out
+ * buffers equal, a fixed input missing.  steps = 0 touches nothing. */
+int neptune_hip_step_loop_system(neptune_hip_group_fn fn, const neptune_hip_apply_geom_t *g, int n_out, const int *through,
+                                 void *const *fields_a, void *const *fields_b, const void *const *in, int64_t steps,
+                                 void *stream, const neptune_hip_launch_cfg_t *cfg);
+/* the last neptune_hip_step_loop_system call of this process: steps issued or replayed, and how many hipGraphLaunch calls
+ * carried them */
+void neptune_hip_system_loop_counts(int64_t *launches, int64_t *graph_launches);
+
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t *g,

@@ -1021,19 +1021,25 @@ inline int launch_apply(const Body& body, const neptune_hip_apply_geom_t* g, con
 // result buffer is not 16-byte aligned, or when every march tile spills for this group.  plan_only: decide, launch nothing.
 // Measured choices are kept per body type like any launch's, and a GroupBody is a type of its own: its table and its
 // wisdom keys (typeid of the body) never meet its members'.
+// member G's view of a group's geometry: its own inputs, in its own order, out of the union's
+template <class G, int RANK>
+inline void group_member_geom(const neptune_hip_apply_geom_t* g, const void* const* in, neptune_hip_apply_geom_t& gm, const void** inm) {
+  gm = *g;
+  gm.num_inputs = G::NIN;
+  for (int k = 0; k < G::NIN; ++k) {
+    inm[k] = in[G::map(k)];
+    for (int d = 0; d < RANK; ++d) { gm.in_lb[k][d] = g->in_lb[G::map(k)][d]; gm.in_ub[k][d] = g->in_ub[G::map(k)][d]; }
+  }
+}
 template <class GB, class T, int RANK, int NIN, class FP, int M = 0>
 inline bool group_members_all_direct(const neptune_hip_apply_geom_t* g, const void* const* in, const void* out) {
   if constexpr (M >= GB::NOUT) {
     return true;
   } else {
     using G = typename GB::template Member<M>;
-    neptune_hip_apply_geom_t gm = *g;
+    neptune_hip_apply_geom_t gm;
     const void* inm[kMaxInputs];
-    gm.num_inputs = G::NIN;
-    for (int k = 0; k < G::NIN; ++k) {
-      inm[k] = in[G::map(k)];
-      for (int d = 0; d < RANK; ++d) { gm.in_lb[k][d] = g->in_lb[G::map(k)][d]; gm.in_ub[k][d] = g->in_ub[G::map(k)][d]; }
-    }
+    group_member_geom<G, RANK>(g, in, gm, inm);
     if (plan_apply<T, RANK, G::NIN, typename G::FP>(&gm, inm, out, nullptr) != NEPTUNE_HIP_KERNEL_DIRECT) return false;
     return group_members_all_direct<GB, T, RANK, NIN, FP, M + 1>(g, in, out);
   }
@@ -1063,6 +1069,91 @@ inline int launch_apply_group(const GB& body, const neptune_hip_apply_geom_t* g,
   }
   if (plan_only) return NEPTUNE_HIP_OK;
   return launch_apply<GB, T, RANK, NIN, FP>(body, g, in, body.out[0], stream, cfg);
+}
+
+// ---- a group on a geometry: the rules the lowered function (lowered_runtime.hpp run_apply_group) and the group's
+// geometry-level entry <gtag>__geom share ----
+inline bool groups_disabled() {   // NEPTUNE_HIP_NO_GROUPS=1, read at each call
+  const char* e = getenv("NEPTUNE_HIP_NO_GROUPS");
+  return e && *e && *e != '0';
+}
+// every member's reach (its Reach table, on ITS view of the geometry) stays inside its inputs' boxes: the first code that
+// is not NEPTUNE_HIP_OK
+template <class GB, int RANK, int M = 0>
+inline int group_check_radius(const neptune_hip_apply_geom_t* g, const Reach* const* reach) {
+  if constexpr (M >= GB::NOUT) {
+    return NEPTUNE_HIP_OK;
+  } else {
+    neptune_hip_apply_geom_t gm;
+    const void* unused[kMaxInputs] = {};
+    const void* inm[kMaxInputs];
+    group_member_geom<typename GB::template Member<M>, RANK>(g, unused, gm, inm);
+    const int rc = geom_check_radius(&gm, *reach[M]);
+    return rc != NEPTUNE_HIP_OK ? rc : group_check_radius<GB, RANK, M + 1>(g, reach);
+  }
+}
+// a member's copy-through source is read at the centre of the group input: its box must BE the result's
+template <class GB, int RANK, int M = 0>
+inline bool group_through_ok(const neptune_hip_apply_geom_t* g) {
+  if constexpr (M >= GB::NOUT) {
+    return true;
+  } else {
+    constexpr int t = GB::template Member<M>::THROUGH;
+    for (int d = 0; d < RANK; ++d)
+      if (g->in_lb[t][d] != g->out_lb[d] || g->in_ub[t][d] != g->out_ub[d]) return false;
+    return group_through_ok<GB, RANK, M + 1>(g);
+  }
+}
+// 1: the group runs as ONE launch (launch_apply_group); 0: member by member -- launch_apply_group has no form for it, a
+// copy-through source lies in another box than the result, or NEPTUNE_HIP_NO_GROUPS=1; < 0: an error.  body.out[] set
+// (a stand-in of the same alignment will do); nothing is launched.
+template <class GB, class T, int RANK, int NIN, class FP>
+inline int plan_apply_group(const GB& body, const neptune_hip_apply_geom_t* g, const void* const* in, const neptune_hip_launch_cfg_t* cfg) {
+  if (!group_through_ok<GB, RANK>(g) || groups_disabled()) return 0;
+  const int rc = launch_apply_group<GB, T, RANK, NIN, FP>(body, g, in, nullptr, cfg, true);
+  return rc == NEPTUNE_HIP_EUNSUPPORTED ? 0 : (rc == NEPTUNE_HIP_OK ? 1 : rc);
+}
+// the members one by one into body.out[]: no member reads another's result, so the same bits as the one launch
+template <class GB, class T, int RANK, int M = 0>
+inline int launch_group_members(const GB& body, const neptune_hip_apply_geom_t* g, const void* const* in, hipStream_t stream,
+                                const neptune_hip_launch_cfg_t* cfg) {
+  if constexpr (M >= GB::NOUT) {
+    return NEPTUNE_HIP_OK;
+  } else {
+    using G = typename GB::template Member<M>;
+    neptune_hip_apply_geom_t gm;
+    const void* inm[kMaxInputs];
+    group_member_geom<G, RANK>(g, in, gm, inm);
+    const int rc = launch_apply<typename G::Body, T, RANK, G::NIN, typename G::FP>(body.template member<M>().body, &gm, inm, body.out[M], stream, cfg);
+    return rc != NEPTUNE_HIP_OK ? rc : launch_group_members<GB, T, RANK, M + 1>(body, g, in, stream, cfg);
+  }
+}
+// What a group's geometry-level entry does (neptune_hip_group_fn, include/neptune_hip.h): g describes the NIN union inputs,
+// out[m] is member m's result.  Refused, nothing launched: a null pointer, a result that overlaps an input or another
+// result (NEPTUNE_HIP_EINVAL), a member reaching outside an input's box (NEPTUNE_HIP_EOOB).
+template <class GB, class T, int RANK, int NIN, class FP>
+inline int apply_group_geom(GB body, const neptune_hip_apply_geom_t* g, const void* const* in, void* const* out, hipStream_t stream,
+                            const neptune_hip_launch_cfg_t* cfg, const Reach* const* reach) {
+  constexpr int M = GB::NOUT;
+  if (!g || !in || !out || g->num_inputs != NIN || g->rank != RANK) return NEPTUNE_HIP_EINVAL;
+  for (int k = 0; k < NIN; ++k)
+    if (!in[k]) return NEPTUNE_HIP_EINVAL;
+  for (int m = 0; m < M; ++m)
+    if (!out[m]) return NEPTUNE_HIP_EINVAL;
+  int rc = group_check_radius<GB, RANK>(g, reach);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  const size_t ob = geom_box_bytes(g->out_lb, g->out_ub, RANK, sizeof(T));
+  for (int m = 0; m < M; ++m) {
+    if (check_no_alias(g, in, out[m], sizeof(T)) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;
+    for (int o = 0; o < m; ++o)
+      if (buffers_overlap(out[o], ob, out[m], ob)) return NEPTUNE_HIP_EINVAL;
+    body.out[m] = static_cast<T*>(out[m]);
+  }
+  const int fused = plan_apply_group<GB, T, RANK, NIN, FP>(body, g, in, cfg);
+  if (fused < 0) return fused;
+  rc = fused ? launch_apply_group<GB, T, RANK, NIN, FP>(body, g, in, stream, cfg) : launch_group_members<GB, T, RANK>(body, g, in, stream, cfg);
+  if (rc == NEPTUNE_HIP_OK) neptune_hip_note_group(fused, M);
+  return rc;
 }
 
 }  // namespace neptune_hip

@@ -82,7 +82,10 @@ std::string report_json(const LowerInfo& info) {
     for (size_t k = 0; k < g.members.size(); ++k) o << (k ? ", " : "") << "\"" << g.members[k] << "\"";
     o << "], \"inputs\": [";
     for (size_t k = 0; k < g.inputs.size(); ++k) o << (k ? ", " : "") << "\"" << g.inputs[k] << "\"";
-    o << "], \"kernel\": \"" << g.kernel << "\", \"rank\": " << g.rank << ", \"elem\": \"" << g.elem << "\"}";
+    o << "], \"kernel\": \"" << g.kernel << "\", \"rank\": " << g.rank << ", \"elem\": \"" << g.elem << "\", \"geom_symbol\": \""
+      << g.geom_symbol << "\", \"through\": [";
+    for (size_t k = 0; k < g.through.size(); ++k) o << (k ? ", " : "") << g.through[k];
+    o << "]}";
   }
   o << "]}";
   return o.str();

@@ -942,8 +942,14 @@ struct Emitter {
     o << "  // group of " << M << " sibling applies over " << NU << " shared inputs -> one multi-output launch (members:";
     for (int m = 0; m < M; ++m) o << " " << ops[grp.members[m]]->results[0];
     o << ")\n";
-    o << "  using Group_" << gtag << " = " << gb.str() << ";\n";
-    o << "  using FP_" << gtag << " = " << footprint_type(grp.fp) << ";\n";
+    // the group's types and its members' reach tables at file scope: the lowered function and the group's geometry-level
+    // entry launch the same instantiations
+    bodies << "// " << gtag << ": " << M << " sibling applies over " << NU << " shared inputs as one GroupBody\n"
+           << "using Group_" << gtag << " = " << gb.str() << ";\n"
+           << "using FP_" << gtag << " = " << footprint_type(grp.fp) << ";\n"
+           << "static const neptune_hip::Reach* const reach_" << gtag << "[] = {";
+    for (int m = 0; m < M; ++m) bodies << (m ? ", " : "") << "&kTopRadius_" << tags[m];
+    bodies << "};\n\n";
     std::vector<std::string> ins;
     for (auto& v : grp.inputs) ins.push_back(cname(v));
     emit_inputs(o, gtag, ins);
@@ -952,15 +958,13 @@ struct Emitter {
       for (size_t k = 0; k < items.size(); ++k) o << (k ? ", " : "") << items[k];
       o << "};\n";
     };
-    std::vector<std::string> reach, halo0;
+    std::vector<std::string> halo0;
     for (int m = 0; m < M; ++m) {
-      reach.push_back("&kTopRadius_" + tags[m]);
       Footprint fp;
       std::map<std::string, int> ti, ia;
       if (!analyze_apply(*ops[grp.members[m]], fp, ti, ia)) return false;
       halo0.push_back(std::to_string(halo0_of(fp)));
     }
-    list("const neptune_hip::Reach* const", "reach", reach);
     list("const int", "halo0", halo0);
     list("const nl::Val* const", "dest", dest);
     list("const nl::Val* const", "dest1", dest_single);
@@ -977,7 +981,20 @@ struct Emitter {
     gi.kernel = grp.no_group_form ? "members" : (grp.fp.march_ok ? "march" : "direct");
     gi.rank = rank;
     gi.elem = res.elem;
+    gi.geom_symbol = gtag + "__geom";
+    for (int m = 0; m < M; ++m) {
+      const std::string& own = ops[grp.members[m]]->operands[0];
+      gi.through.push_back((int)(std::find(grp.inputs.begin(), grp.inputs.end(), own) - grp.inputs.begin()));
+    }
     info.groups.push_back(gi);
+    // The group's geometry-level entry (neptune_hip_group_fn, include/neptune_hip.h): what <tag>__geom is for one apply.
+    // One fused launch, or the members' own launches where the fused form does not apply (apply_launch.hpp
+    // apply_group_geom); it instantiates no kernel the lowered function does not.
+    geom_entries << "// group of " << M << " applies over " << NU << " inputs: g describes the union inputs, out[m] is member m's result\n"
+                 << "extern \"C\" int " << gi.geom_symbol << "(const neptune_hip_apply_geom_t* g, const void* const* in, void* const* out,\n"
+                 << "    void* stream, const neptune_hip_launch_cfg_t* cfg) {\n"
+                 << "  return neptune_hip::apply_group_geom<Group_" << gtag << ", " << T << ", " << rank << ", " << NU << ", FP_" << gtag
+                 << ">(Group_" << gtag << "{}, g, in, out, (hipStream_t)stream, cfg, reach_" << gtag << ");\n}\n\n";
     return true;
   }
 

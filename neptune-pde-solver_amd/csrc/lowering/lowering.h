@@ -28,6 +28,8 @@ struct GroupInfo {
   std::string kernel;                 // what the union footprint is planned onto: march | direct | members (no group form)
   int rank = 0;
   std::string elem;
+  std::string geom_symbol;            // exported geometry-level entry of the group, <fn>_<k0>_group__geom
+  std::vector<int> through;           // per member: the group input it lists first (its unknown and copy-through source)
 };
 struct SigType {
   std::string kind, elem;  // kind: memref | temp | field

@@ -411,11 +411,9 @@ inline Val run_apply(Scope& sc, const Body& body, const Box& result_decl, const 
 // pointers) -- the launch reads every input while it writes every result.  dest_single: what each member's run_apply
 // would be given were the group not recognised; used under a slab view, where the members run exactly as they did before
 // groups existed.  The members run one by one through run_apply when the launch has no group form
-// (launch_apply_group: NEPTUNE_HIP_EUNSUPPORTED), under a slab view, or with NEPTUNE_HIP_NO_GROUPS=1 (read at each call).
-inline bool groups_disabled() {
-  const char* e = getenv("NEPTUNE_HIP_NO_GROUPS");
-  return e && *e && *e != '0';
-}
+// (launch_apply_group: NEPTUNE_HIP_EUNSUPPORTED), under a slab view, or with NEPTUNE_HIP_NO_GROUPS=1 (read at each call):
+// apply_launch.hpp plan_apply_group and group_check_radius hold those rules, for this function and for the group's
+// geometry-level entry alike.
 template <class GB, class T, int RANK, int NIN, int M = 0>
 inline void run_group_members(Scope& sc, const GB& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
                               const neptune_hip::Reach* const* reach, const int* halo0, const Val* const* dest, Val* out) {
@@ -426,26 +424,6 @@ inline void run_group_members(Scope& sc, const GB& body, const Box& result_decl,
     out[M] = run_apply<typename G::Body, T, RANK, G::NIN, typename G::FP>(sc, body.template member<M>().body, result_decl, bounds_decl, inm,
                                                                        *reach[M], dest[M], halo0[M]);
     run_group_members<GB, T, RANK, NIN, M + 1>(sc, body, result_decl, bounds_decl, in, reach, halo0, dest, out);
-  }
-}
-template <class GB, class T, int RANK, int NIN, int M = 0>
-inline void check_group_members(Scope& sc, const Box& result_box, const Box& bounds, const Val* const* in,
-                                const neptune_hip::Reach* const* reach, bool& through_ok) {
-  if constexpr (M < GB::NOUT) {
-    using G = typename GB::template Member<M>;
-    const Val* inm[G::NIN];
-    for (int k = 0; k < G::NIN; ++k) inm[k] = in[G::map(k)];
-    neptune_hip_apply_geom_t gm;
-    fill_geom(gm, result_box, bounds, inm, G::NIN);
-    const int rc = geom_check_radius(&gm, *reach[M]);
-    if (rc == NEPTUNE_HIP_EOOB)
-      die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
-                     "DataflowLowering.cpp:380-410); refusing to run it");
-    if (rc != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
-    // the copy-through source is read at the centre of the group input: its box must BE the result's
-    for (int d = 0; d < RANK; ++d)
-      through_ok = through_ok && inm[0]->box.lb[d] == result_box.lb[d] && inm[0]->box.ub[d] == result_box.ub[d];
-    check_group_members<GB, T, RANK, NIN, M + 1>(sc, result_box, bounds, in, reach, through_ok);
   }
 }
 template <class GB, class T, int RANK, int NIN, class FP>
@@ -459,8 +437,13 @@ inline void run_apply_group(Scope& sc, GB body, const Box& result_decl, const Bo
     return;
   }
   const Box result_box = result_decl, bounds = Scope::zero_trip(bounds_decl);
-  bool through_ok = true;
-  check_group_members<GB, T, RANK, NIN>(sc, result_box, bounds, in, reach, through_ok);
+  neptune_hip_apply_geom_t g;
+  fill_geom(g, result_box, bounds, in, NIN);
+  const int rcr = group_check_radius<GB, RANK>(&g, reach);
+  if (rcr == NEPTUNE_HIP_EOOB)
+    die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
+                   "DataflowLowering.cpp:380-410); refusing to run it");
+  if (rcr != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
   // destination forwarding, decided for the group as a whole: holds for the fused launch and for the members run in turn
   // (member m's direct write happens before member m+1 reads ITS inputs)
   const Val* fwd[M];
@@ -470,18 +453,12 @@ inline void run_apply_group(Scope& sc, GB body, const Box& result_decl, const Bo
     for (int o = 0; direct && o < M; ++o) direct = o == m || dest[o] == nullptr || !overlaps(*dest[m], *dest[o]);
     fwd[m] = direct ? dest[m] : nullptr;
   }
-  neptune_hip_apply_geom_t g;
-  fill_geom(g, result_box, bounds, in, NIN);
   const void* ptrs[NIN];
   for (int k = 0; k < NIN; ++k) ptrs[k] = in[k]->dev;
-  bool fused = through_ok && !groups_disabled();
-  if (fused) {
-    // plan first (a result that will be a pool block is 16-byte aligned: stands in as such), allocate only what runs
-    for (int m = 0; m < M; ++m) body.out[m] = fwd[m] ? static_cast<T*>(fwd[m]->dev) : reinterpret_cast<T*>((uintptr_t)16);
-    const int rc = launch_apply_group<GB, T, RANK, NIN, FP>(body, &g, ptrs, sc.stream(), launch_override(), true);
-    if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
-    else if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply group launch rejected");
-  }
+  // plan first (a result that will be a pool block is 16-byte aligned: stands in as such), allocate only what runs
+  for (int m = 0; m < M; ++m) body.out[m] = fwd[m] ? static_cast<T*>(fwd[m]->dev) : reinterpret_cast<T*>((uintptr_t)16);
+  const int fused = plan_apply_group<GB, T, RANK, NIN, FP>(body, &g, ptrs, launch_override());
+  if (fused < 0) die(sc.name(), "neptune_ir.apply group launch rejected");
   if (!fused) {
     run_group_members<GB, T, RANK, NIN>(sc, body, result_decl, bounds_decl, in, reach, halo0, fwd, out);
     neptune_hip_note_group(0, M);

@@ -1,6 +1,7 @@
 // step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (stream scope, graph cache, replay,
-// grouping choice) that knows nothing about ping-pong or leapfrog, and the two loops built on it: neptune_hip_step_loop_chain
-// (one-level schemes, two fields) and neptune_hip_step_loop_leapfrog (two-level schemes, three or four fields).  Host code
+// grouping choice) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
+// neptune_hip_step_loop_chain (one-level schemes, two fields), neptune_hip_step_loop_leapfrog (two-level schemes, three or
+// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields).  Host code
 // only (its own translation unit: builds in seconds, linked into libneptune_hip.so); it launches through the public C API.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -29,6 +30,11 @@ struct LoopKey {
   group_fn more[2];
   neptune_hip_apply_geom_t g;
   void* fields[4];             // the rotating fields, nullptr beyond the loop's own two, three or four
+  // the system loop: fields[] is set A of its n_out unknowns, fields_b[] set B, through[m] the union input member m advances;
+  // n_out = 0 and the rest zero in the other loops
+  void* fields_b[4];
+  int through[4];
+  int n_out;
   const void* in[NEPTUNE_HIP_MAX_INPUTS];   // the inputs that are no state (centre-only inputs: the same field at every stage)
   neptune_hip_launch_cfg_t cfg;
   hipStream_t stream;
@@ -157,8 +163,10 @@ int state_code(const LeapState& s) { return s.cur | s.prev << 2 | s.f1 << 4 | (s
 // that small fields are not bound by launch overhead; per_graph is a multiple of the rotation's period, so a graph leaves
 // the state where it found it.  Not inside a caller's capture: a capturing stream cannot begin another one.  Then the rest
 // plain.  After the first launch the state has moved, so a late NEPTUNE_HIP_EUNSUPPORTED is an error: NEPTUNE_HIP_EINVAL.
+// *graph_launches (optional): how many hipGraphLaunch calls carried launches of this run.
 template <class State, class Launch>
-int replay(LoopKey& key, const StreamScope& sc, int kind, int64_t count, State& s, int per_graph, Launch&& launch) {
+int replay(LoopKey& key, const StreamScope& sc, int kind, int64_t count, State& s, int per_graph, Launch&& launch,
+           int64_t* graph_launches = nullptr) {
   if (count <= 0) return NEPTUNE_HIP_OK;
   int rc = launch(kind, s);
   if (rc != NEPTUNE_HIP_OK) return rc;
@@ -174,7 +182,10 @@ int replay(LoopKey& key, const StreamScope& sc, int kind, int64_t count, State& 
       return r;
     }, &rc);
     if (!slot) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-    for (; count - done >= per_graph; done += per_graph) NEPTUNE_HIP_CHECK(hipGraphLaunch(slot->exec, sc.stream));
+    for (; count - done >= per_graph; done += per_graph) {
+      NEPTUNE_HIP_CHECK(hipGraphLaunch(slot->exec, sc.stream));
+      if (graph_launches) ++*graph_launches;
+    }
   }
   for (; done < count; ++done) {
     rc = launch(kind, s);
@@ -266,6 +277,7 @@ int choose_grouping(const LoopKey& key, const StreamScope& sc, bool measure, int
 }
 
 int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last leapfrog loop
+int64_t g_system_counts[2] = {0, 0}; // steps / graph launches of the last system loop
 
 }  // namespace
 
@@ -425,6 +437,68 @@ int neptune_hip_step_loop_leapfrog(neptune_hip_apply_fn fn, neptune_hip_leapfrog
     remember_grouping(key, 0);   // nothing has run: single launches, now and for the rest of the process
   }
   return result(run(1, steps));
+}
+
+// ---------------------------------------------------------------- system loop: a group's n_out unknowns, two sets of fields
+void neptune_hip_system_loop_counts(int64_t* launches, int64_t* graph_launches) {
+  if (launches) *launches = g_system_counts[0];
+  if (graph_launches) *graph_launches = g_system_counts[1];
+}
+
+int neptune_hip_step_loop_system(neptune_hip_group_fn fn, const neptune_hip_apply_geom_t* g, int n_out, const int* through,
+                                 void* const* fields_a, void* const* fields_b, const void* const* in, int64_t steps, void* stream,
+                                 const neptune_hip_launch_cfg_t* cfg) {
+  g_system_counts[0] = g_system_counts[1] = 0;
+  if (!fn || !g || !through || !fields_a || !fields_b || steps < 0 || n_out < 2 || n_out > 4) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs < n_out || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
+  bool advanced[NEPTUNE_HIP_MAX_INPUTS] = {};
+  for (int m = 0; m < n_out; ++m) {
+    // two members advancing the same unknown is not a time step
+    if (through[m] < 0 || through[m] >= g->num_inputs || advanced[through[m]]) return NEPTUNE_HIP_EINVAL;
+    advanced[through[m]] = true;
+  }
+  const void* bufs[8];
+  for (int m = 0; m < n_out; ++m) { bufs[m] = fields_a[m]; bufs[n_out + m] = fields_b[m]; }
+  for (int a = 0; a < 2 * n_out; ++a) {
+    if (!bufs[a]) return NEPTUNE_HIP_EINVAL;
+    for (int b = 0; b < a; ++b)
+      if (bufs[a] == bufs[b]) return NEPTUNE_HIP_EINVAL;
+  }
+  for (int k = 0; k < g->num_inputs; ++k)
+    if (!advanced[k] && (!in || !in[k])) return NEPTUNE_HIP_EINVAL;   // a fixed input is missing
+  ensure_init();
+  if (steps == 0) return NEPTUNE_HIP_OK;
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  LoopKey key;
+  init_key(key, nullptr, -1, g, cfg, sc.stream);
+  key.more[0] = (group_fn)fn;
+  key.n_out = n_out;
+  for (int m = 0; m < n_out; ++m) {
+    key.fields[m] = fields_a[m];
+    key.fields_b[m] = fields_b[m];
+    key.through[m] = through[m];
+  }
+  for (int k = 0; k < g->num_inputs; ++k)
+    if (!advanced[k]) key.in[k] = in[k];
+
+  // one step: every member reads set `from` (0 = A) at its unknown's input and writes the other set
+  auto launch = [&](int, int& from) -> int {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    void* outs[4];
+    for (int k = 0; k < key.g.num_inputs; ++k) ins[k] = key.in[k];
+    for (int m = 0; m < key.n_out; ++m) {
+      ins[key.through[m]] = from ? key.fields_b[m] : key.fields[m];
+      outs[m] = from ? key.fields[m] : key.fields_b[m];
+    }
+    const int rc = fn(&key.g, ins, outs, (void*)sc.stream, loop_cfg(key));
+    if (rc == NEPTUNE_HIP_OK) from ^= 1;
+    return rc;
+  };
+  // one launch kind, no grouping to choose: graphs of 8 ping-pong pairs, as the one-level loop's
+  int from = 0;
+  const int rc = replay(key, sc, 1, steps, from, 16, launch, &g_system_counts[1]);
+  if (rc == NEPTUNE_HIP_OK) g_system_counts[0] = steps;
+  return rc;
 }
 
 }  // extern "C"

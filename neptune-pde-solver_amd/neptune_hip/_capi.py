@@ -114,6 +114,8 @@ SIGNATURES = {
     "neptune_hip_step_loop_leapfrog": (_i, [_vp, _vp, _geom_p, _vpp, _vpp, _i, _i64, _vp, _cfg_p, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int)]),
     "neptune_hip_leapfrog_launch_counts": (None, [_i64p, _i64p]),
+    "neptune_hip_step_loop_system": (_i, [_vp, _geom_p, _i, C.POINTER(C.c_int), _vpp, _vpp, _vpp, _i64, _vp, _cfg_p]),
+    "neptune_hip_system_loop_counts": (None, [_i64p, _i64p]),
     "neptune_hip_kernel_name": (C.c_char_p, [_i]),
     "neptune_hip_apply_builtin_variant": (_i, [_i, _geom_p, _cfg_p]),
     "neptune_hip_march_variant_count": (_i, [_i]),

@@ -127,6 +127,54 @@ def step_loop_leapfrog(entry, geom, fields: Sequence, extra: Sequence = (), step
     return cur.value, prev.value
 
 
+def apply_group(entry, inputs: Sequence, outs: Sequence, bounds: Box, region: Optional[Box] = None,
+                cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None) -> None:
+    """outs[m] = member m's apply over `inputs` {bounds}, for every member of the group `entry`
+    (LoweredModule.group_entry) in one call -- one multi-output launch where the group has that form.  `inputs`: the
+    group's union inputs in the order of entry.inputs; DeviceFields or torch CUDA tensors.  Asynchronous on `stream`."""
+    ins, os_ = [_as_field(f) for f in inputs], [_as_field(f) for f in outs]
+    if len(ins) != entry.num_inputs or len(os_) != entry.num_outputs:
+        raise ValueError(f"{entry.symbol}: {entry.num_inputs} inputs and {entry.num_outputs} results")
+    g = geom_for(ins, os_[0], bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    _capi.check(entry(g, _in_array(ins), _in_array(os_), st, cfg), entry.symbol)
+
+
+def system_loop_counts():
+    """(steps issued or replayed, hipGraphLaunch calls that carried them) of the last step_loop_system call"""
+    launches, graphs = C.c_int64(0), C.c_int64(0)
+    _capi.load().neptune_hip_system_loop_counts(C.byref(launches), C.byref(graphs))
+    return launches.value, graphs.value
+
+
+def step_loop_system(entry, bounds: Box, cur: Sequence, nxt: Sequence, fixed: Sequence = (), steps: int = 0,
+                     cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
+    """`steps` steps of the system that the group `entry` (LoweredModule.group_entry) computes: member m advances the
+    unknown in cur[m] (DeviceFields or torch CUDA tensors, in member order), nxt[m] is that unknown's second buffer; step s
+    reads one set and writes the other.  `fixed`: the group's union inputs that are nobody's unknown (coefficient fields),
+    in the order they have in entry.inputs.  Long runs replay a cached hipGraph.  Asynchronous; returns whichever of `cur`
+    and `nxt` holds the newest state -- the other one then holds the state one step earlier."""
+    lib = _capi.load()
+    a, b, fx = [_as_field(f) for f in cur], [_as_field(f) for f in nxt], [_as_field(f) for f in fixed]
+    n = entry.num_outputs
+    fixed_slots = [k for k in range(entry.num_inputs) if k not in entry.through]
+    if len(a) != n or len(b) != n or len(fx) != len(fixed_slots):
+        raise ValueError(f"{entry.symbol}: {n} unknowns in cur and in nxt, {len(fixed_slots)} fixed inputs")
+    ins = [None] * entry.num_inputs
+    for m, k in enumerate(entry.through):
+        ins[k] = a[m]
+    for f, k in zip(fx, fixed_slots):
+        ins[k] = f
+    g = geom_for(ins, b[0], bounds)
+    in_arr = (C.c_void_p * entry.num_inputs)(*[ins[k].ptr if k in fixed_slots else None for k in range(entry.num_inputs)])
+    st = current_stream_ptr() if stream is None else stream
+    rc = lib.neptune_hip_step_loop_system(C.cast(entry.fn, C.c_void_p), C.byref(g), n, (C.c_int * n)(*entry.through),
+                                          _in_array(a), _in_array(b), in_arr, steps, st,
+                                          C.byref(cfg) if cfg is not None else None)
+    _capi.check(rc, "neptune_hip_step_loop_system")
+    return list(nxt) if steps % 2 else list(cur)
+
+
 def apply_twice(body, inp: DeviceField, out: DeviceField, bounds: Box, region: Optional[Box] = None,
                 cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None, applies: int = 2) -> bool:
     """out = A(A(inp)) -- or A(A(A(inp))) with applies=3 -- in ONE pass over HBM for apply A (a built-in body id or a

@@ -185,6 +185,28 @@ class GeomEntry:
         return self.fn(C.byref(geom), in_array, out_ptr, stream, C.byref(cfg) if cfg is not None else None)
 
 
+class GroupEntry:
+    """a group of sibling applies of a lowered module (a system of equations: one multi-output launch), callable with an
+    explicit geometry over the group's union inputs (see LoweredModule.group_entry; neptune_hip_group_fn)"""
+
+    def __init__(self, module: "LoweredModule", info: dict):
+        self.module = module            # keeps the shared object loaded
+        self.info = info
+        self.symbol = info["geom_symbol"]
+        self.rank = info["rank"]
+        self.dtype = _capi.F64 if info["elem"] == "f64" else _capi.F32
+        self.inputs: List[str] = list(info["inputs"])      # SSA names of the union inputs, in the order `geom` lists them
+        self.through: List[int] = list(info["through"])    # per member: the union input it advances (its input 0)
+        self.num_inputs, self.num_outputs = len(self.inputs), len(info["members"])
+        self.fn = getattr(module.lib, self.symbol)
+        self.fn.restype = C.c_int
+        self.fn.argtypes = [C.POINTER(_capi.ApplyGeom), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,
+                            C.POINTER(_capi.LaunchCfg)]
+
+    def __call__(self, geom, in_array, out_array, stream, cfg=None) -> int:
+        return self.fn(C.byref(geom), in_array, out_array, stream, C.byref(cfg) if cfg is not None else None)
+
+
 class LoweredModule:
     """a compiled module: call exported symbols with numpy arrays (host buffers: staged through the
     device, result comes back in malloc'ed host memory) or with DeviceField / torch CUDA tensors
@@ -221,6 +243,15 @@ class LoweredModule:
         if index >= len(cands):
             raise KeyError(f"@{function} has no apply #{index} with a geometry-level entry")
         return GeomEntry(self, cands[index])
+
+    def group_entry(self, function: str, index: int = 0) -> "GroupEntry":
+        """geometry-level entry of the `index`-th group of sibling applies of @function: every member's result from one
+        call, on caller-supplied boxes / bounds / region / stream / launch cfg (neptune_hip.apply.apply_group), and what
+        neptune_hip.apply.step_loop_system steps"""
+        cands = [g for g in self.report["groups"] if g["function"] == function]
+        if index >= len(cands):
+            raise KeyError(f"@{function} has no group #{index}")
+        return GroupEntry(self, cands[index])
 
     def call(self, name: str, *args):
         sig = self.signatures[name]
