@@ -17,34 +17,10 @@ pytestmark = pytest.mark.gpu
 CONSTS = [0.5, -0.25, 1.5, 0.125, -0.75, 2.0, -1.25, 0.375, 3.0, -0.0625, 1.75, 0.3125]
 
 
-def gen_apply(rng, name, rank, elem, shape, origin):
-    nin = int(rng.integers(1, 4))
-    radius = int(rng.choice([1, 1, 2]))
-    if rank < 3 and min(shape) >= 11 and rng.random() < 0.3:       # high-order stars (march kernel up to radius 4)
-        radius = int(rng.choice([3, 4, 5]))
-    elif rank == 3 and min(shape) >= 9 and rng.random() < 0.25:    # 3-D: up to radius 3
-        radius = int(rng.choice([3, 3, 4]))
-    box = (radius == 1 and rank > 1 and rng.random() < 0.35) or (radius == 2 and rank == 2 and rng.random() < 0.4)
-    accesses = []                       # (input, offsets)
-    for k in range(nin):
-        style = rng.choice(["centre", "halo"]) if k > 0 else "halo"
-        accesses.append((k, (0,) * rank))
-        if style == "centre":
-            continue
-        n_off = int(rng.integers(2, 7))
-        for _ in range(n_off):
-            if box:
-                off = tuple(int(rng.integers(-radius, radius + 1)) for _ in range(rank))
-            else:
-                d = int(rng.integers(0, rank))
-                off = tuple(int(rng.choice([-radius, -1, 1, radius])) if a == d else 0 for a in range(rank))
-            if any(off) and (k, off) not in accesses:
-                accesses.append((k, off))
-    L = []
-    vals = []
-    for n, (k, off) in enumerate(accesses):
-        L.append(f"%a{n} = neptune_ir.access %in{k}[{', '.join(map(str, off))}] : !t -> {elem}")
-        vals.append(f"%a{n}")
+def gen_chain(rng, L, vals, elem):
+    """a random expression over the accessed values `vals`, appended to the region's lines L: IEEE-exact operations only
+    (add / sub / mul / max / min, abs, division by a constant, floor / ceil / copysign, sqrt(|x|), cmpf + select).
+    -> (the SSA name of its value, the last counter used in a name).  Also the body of the group fuzz cases."""
     cnt = 0
 
     def const():
@@ -96,6 +72,38 @@ def gen_apply(rng, name, rank, elem, shape, origin):
         L.append(f"%p{cnt} = arith.cmpf {rng.choice(['olt', 'oge', 'une', 'ogt'])}, {vals[0]}, {z} : {elem}")
         L.append(f"%v{cnt} = arith.select %p{cnt}, {acc}, {vals[-1]} : {elem}")
         acc = f"%v{cnt}"
+    return acc, cnt
+
+
+def gen_apply(rng, name, rank, elem, shape, origin):
+    nin = int(rng.integers(1, 4))
+    radius = int(rng.choice([1, 1, 2]))
+    if rank < 3 and min(shape) >= 11 and rng.random() < 0.3:       # high-order stars (march kernel up to radius 4)
+        radius = int(rng.choice([3, 4, 5]))
+    elif rank == 3 and min(shape) >= 9 and rng.random() < 0.25:    # 3-D: up to radius 3
+        radius = int(rng.choice([3, 3, 4]))
+    box = (radius == 1 and rank > 1 and rng.random() < 0.35) or (radius == 2 and rank == 2 and rng.random() < 0.4)
+    accesses = []                       # (input, offsets)
+    for k in range(nin):
+        style = rng.choice(["centre", "halo"]) if k > 0 else "halo"
+        accesses.append((k, (0,) * rank))
+        if style == "centre":
+            continue
+        n_off = int(rng.integers(2, 7))
+        for _ in range(n_off):
+            if box:
+                off = tuple(int(rng.integers(-radius, radius + 1)) for _ in range(rank))
+            else:
+                d = int(rng.integers(0, rank))
+                off = tuple(int(rng.choice([-radius, -1, 1, radius])) if a == d else 0 for a in range(rank))
+            if any(off) and (k, off) not in accesses:
+                accesses.append((k, off))
+    L = []
+    vals = []
+    for n, (k, off) in enumerate(accesses):
+        L.append(f"%a{n} = neptune_ir.access %in{k}[{', '.join(map(str, off))}] : !t -> {elem}")
+        vals.append(f"%a{n}")
+    acc, cnt = gen_chain(rng, L, vals, elem)
     margin = radius
     if rng.random() < 0.6:                      # scf.if on an index argument, with a conditional access
         d = int(rng.integers(0, rank))
