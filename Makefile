@@ -33,13 +33,13 @@ build/obj/neptune_hip_rt.o: $(CSRC)/runtime/neptune_hip_rt.hip $(KERNEL_HDRS)
 build/obj/rt_body_%.o: $(CSRC)/runtime/rt_body_%.hip $(KERNEL_HDRS)
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-build/obj/slab_rccl.o: $(CSRC)/runtime/slab_rccl.hip $(CSRC)/runtime/slab_rccl.hpp $(CSRC)/kernels/apply_launch.hpp include/neptune_hip.h
+build/obj/slab_rccl.o: $(CSRC)/runtime/slab_rccl.hip $(KERNEL_HDRS)
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 build/obj/wisdom.o: $(CSRC)/runtime/wisdom.hip include/neptune_hip.h
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-build/obj/step_loop.o: $(CSRC)/runtime/step_loop.hip $(CSRC)/kernels/apply_launch.hpp include/neptune_hip.h
+build/obj/step_loop.o: $(CSRC)/runtime/step_loop.hip $(KERNEL_HDRS)
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 RT_BODIES := lap2d5 lap3d7 lap3d27 lap1d3

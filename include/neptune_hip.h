@@ -342,6 +342,58 @@ int neptune_hip_step_loop_system(neptune_hip_group_fn fn, const neptune_hip_appl
  * carried them */
 void neptune_hip_system_loop_counts(int64_t *launches, int64_t *graph_launches);
 
+/* Iteration to a tolerance: the update norm out of the apply's own launch.
+ * A MONITORED launch computes exactly what neptune_hip_apply_builtin computes -- the same result, bit for bit -- and
+ * additionally S = sum (new - old)^2 in the field's element type T over the cells of apply.bounds that lie in the launch
+ * region: `old` is input 0 at the same physical index, d = new - old is one rounding, d * d is one rounding, no FMA.
+ * Cells outside apply.bounds (copy-through), clamped or predicated-off cells and cells outside the launch region
+ * contribute nothing; empty bounds give +0.  Every workgroup stores one partial at its linear index (the ragged-row and
+ * row-tail launches' partials follow the march launch's), a second kernel adds the partials in index order: no atomics, the
+ * same bits run after run for one launch configuration (tile, chunk), rounding-level differences between configurations.
+ * sum_out is a DEVICE pointer to one T, written in stream order; the call is asynchronous.  Errors as
+ * neptune_hip_apply_builtin; sum_out overlapping a field is NEPTUNE_HIP_EINVAL.  Monitored forms exist for the march kernel
+ * (rank 3, both rank-2 forms, rank 1) and both direct forms; a request planned onto the plane-in-LDS kernels (or one that
+ * would have to grow the partials workspace inside a stream capture) returns NEPTUNE_HIP_EUNSUPPORTED with nothing
+ * launched.  The several-steps-per-pass kernels, rank 4-6 and groups have no monitored form.  No first-use measuring:
+ * the automatic tile or cfg's; a tile whose monitored kernel needs scratch memory is never chosen automatically.
+ * The partials workspace is the process's (like neptune_hip_reduce_workspace): monitored launches on two streams at once
+ * are not supported.  Lowered applies export the same as <function>_<k>__geomN on request (include/neptune_lowering.h). */
+int neptune_hip_apply_builtin_norm(int body, const neptune_hip_apply_geom_t *g, const void *const *in, void *out,
+                                   void *sum_out, void *stream, const neptune_hip_launch_cfg_t *cfg);
+typedef int (*neptune_hip_apply_norm_fn)(const neptune_hip_apply_geom_t *g, const void *const *in, void *out,
+                                         void *sum_out, void *stream, const neptune_hip_launch_cfg_t *cfg);
+/* device buffer of at least `bytes` bytes for the partials of one monitored launch: grown on demand (which waits for
+ * the device), released by neptune_hip_finalize; NULL when it would have to grow while `stream` is being captured */
+void *neptune_hip_monitor_workspace(size_t bytes, void *stream);
+/* The same S from two fields, in one read-only pass: *sum_out = sum (a - b)^2 over apply.bounds x launch region of `g`
+ * (a = a field in the result's box -- the new state --, b = one in input 0's box -- the old state), the two roundings
+ * above, summed by the fixed tree of the reduce(apply) kernels (another order than a monitored launch's: the two agree
+ * within 2 (n - 1) eps sum |x_i|).  dtype: NEPTUNE_HIP_F64 / _F32.  sum_out: DEVICE pointer; asynchronous. */
+int neptune_hip_update_norm(int dtype, const neptune_hip_apply_geom_t *g, const void *a, const void *b, void *sum_out,
+                            void *stream);
+
+/* Iterate u <- A(u) on two ping-pong fields until S = sum (A(u) - u)^2 <= tol2 or max_steps steps have run.
+ * The loop runs in blocks of check_every steps (the last block shorter, so that max_steps is never exceeded): the first
+ * steps of a block go through neptune_hip_step_loop_chain's loop (fn2 / fn3 = NULL: graphs as there), the LAST step of
+ * every block is a monitored launch through fn_norm (fn = NULL: built-in body `body` through
+ * neptune_hip_apply_builtin_norm).  After each block the scalar is read back -- one stream synchronise, sizeof(T) bytes --
+ * and the loop stops when S <= tol2.  tol2 is the threshold on S itself: no square root anywhere.  A NaN sum never
+ * satisfies the test, so such a loop runs to max_steps.  On return *steps_done steps have run, the newest state is in
+ * fields[*steps_done % 2] and -- the last launch always being a single step -- the other field holds state
+ * *steps_done - 1; *last_sum is the last S read (0 when no step ran).  steps_done / last_sum may be NULL.
+ * Fallback: when fn_norm is NULL (with fn set) or the monitored entry answers NEPTUNE_HIP_EUNSUPPORTED, the checked step
+ * is a plain launch followed by neptune_hip_update_norm over both fields: the same S, another summation order.
+ * Synchronous by nature.  NEPTUNE_HIP_EINVAL, nothing launched: a call while `stream` is being captured, check_every < 1,
+ * max_steps < 0, equal or null fields.  Element type: the built-in body's, or `dtype_of_fn` for fn (NEPTUNE_HIP_F64 /
+ * NEPTUNE_HIP_F32; ignored for built-in bodies). */
+int neptune_hip_step_loop_until(neptune_hip_apply_fn fn, neptune_hip_apply_norm_fn fn_norm, int body, int dtype_of_fn,
+                                const neptune_hip_apply_geom_t *g, void *const fields[2], const void *const *in,
+                                int64_t max_steps, int64_t check_every, double tol2, void *stream,
+                                const neptune_hip_launch_cfg_t *cfg, int64_t *steps_done, double *last_sum);
+/* the last neptune_hip_step_loop_until call of this process: checked steps that ran as monitored launches, checked steps
+ * that ran the fallback, and checks (read-backs) in all */
+void neptune_hip_until_loop_counts(int64_t *fused, int64_t *fallback, int64_t *checks);
+
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t *g,

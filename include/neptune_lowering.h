@@ -27,6 +27,13 @@ int neptune_lowering_verify(const char *mlir_text, char **diag_out);
  *               halo0 (reach along dim 0: the ghost planes a slab decomposition must hold) and geom_symbol,
  *               the exported geometry-level entry of that apply (neptune_hip_apply_fn, include/neptune_hip.h);
  *               leapfrog_symbol, the pair entry <geom_symbol>L2 of a two-level scheme (neptune_hip_leapfrog2_fn), or ""
+ *               norm_symbol (only with the option below), the monitored launch <geom_symbol>N (neptune_hip_apply_norm_fn)
+ * Lowering options travel in the module text, one comment line each: "// neptune-hip-option: <name>".
+ *   norm-entries   every apply whose input 0 has the result's element type and a box equal to the result's (a fused
+ *                  explicit Euler step included) also exports its monitored launch <function>_<k>__geomN: the apply and
+ *                  the update norm sum (new - old)^2 from one launch (include/neptune_hip.h).  Without it
+ *                  source and report are what they are without this feature.  neptune-opt: --norm-entries; Python:
+ *                  compile_module(..., norm_entries=True).
  * Set NEPTUNE_HIP_FULL_VARIANTS=1 in the environment of neptune_lowering_compile to build every march tile
  * into the module instead of the defaults (for NEPTUNE_HIP_TUNE=1). */
 int neptune_lowering_to_hip(const char *mlir_text, char **source_out, char **report_out, char **diag_out);

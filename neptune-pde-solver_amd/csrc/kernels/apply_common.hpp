@@ -139,6 +139,70 @@ struct GroupBody {
   __device__ __forceinline__ T outside(T thr) const { return OutsideOf<typename Member<M>::Body, T>::apply(member<M>().body, thr); }
 };
 
+// ---- monitored applies: the update norm S = sum (new - old)^2 out of the same launch ------------------
+// A kernel asks IsMonitored<Body> whether the body is a MonitoredBody.  It then keeps one accumulator per lane, updated at
+// the store site under the store's own predicates plus `inside` (cells outside apply.bounds, clamped or predicated-off
+// cells and cells outside the launch region contribute nothing), reduces it over the workgroup after its last store and
+// writes ONE partial at the workgroup's linear index; the host adds the partials in index order with a second kernel
+// (apply_launch.hpp launch_apply_norm).  `old` is input 0 at the same physical index -- the copy-through source the store
+// site holds anyway.  The wrapped body is evaluated exactly as on its own, so the result is the plain launch's, bit for bit.
+struct MonitorPlan {     // host side of one monitored call: a counting pass sizes the partials, the launching pass fills them
+  bool counting;         // true: launch nothing, add up the workgroups every launch of the call would have
+  int64_t blocks;        // workgroups so far: where the next launch's partials start
+  void* base;            // the partials buffer (launching pass)
+};
+template <class Body, class T>
+struct MonitoredBody {
+  static constexpr bool MONITORED = true;
+  Body body;
+  T* partials;           // this launch's partials, one per workgroup
+  MonitorPlan* plan;     // host only
+  template <class A>
+  __device__ __forceinline__ T operator()(const A& a) const { return body(a); }
+};
+template <class Body, class = void>
+struct IsMonitored { static constexpr bool value = false; };
+template <class Body>
+struct IsMonitored<Body, std::void_t<decltype(Body::MONITORED)>> { static constexpr bool value = true; };
+template <class Body, class T>
+struct OutsideOf<MonitoredBody<Body, T>, T, void> {
+  static __device__ __forceinline__ T apply(const MonitoredBody<Body, T>& b, T through) { return OutsideOf<Body, T>::apply(b.body, through); }
+};
+// one term of S: two roundings (the difference, then the square), no FMA; a cell that does not count adds +0
+template <class T>
+__device__ __forceinline__ T monitor_term(bool counts, T fresh, T old) {
+  const T d = fresh - old;
+  const T q = d * d;
+  return counts ? q : (T)0;
+}
+
+// The workgroup's sum of `v`, valid in thread 0: wave shuffle tree, one slot per wave in `lds` (>= blockDim.x / 64 entries),
+// the waves' sums added in wave order -- the same fixed tree as util_kernels.hpp's block_sum, which this header cannot
+// include (that file holds a non-template kernel: one translation unit per library).  Every wave of the workgroup calls it.
+template <class T>
+__device__ __forceinline__ T monitor_block_sum(T v, T* lds) {
+  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o);
+  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T r = 0;
+  if (threadIdx.x == 0) {
+    const int nw = blockDim.x / kWave;
+    for (int i = 0; i < nw; ++i) r += lds[i];
+  }
+  return r;
+}
+// The second kernel of a monitored call: ONE workgroup adds the n partials into *out.  Lane t adds a contiguous run of
+// partials in index order, the 256 runs are added by the tree above in lane order: a fixed order, no atomics.
+template <class T>
+__global__ __launch_bounds__(256) void neptune_monitor_final(const T* __restrict__ partials, int64_t n, T* __restrict__ out) {
+  __shared__ T lds[4];
+  const int64_t per = (n + 255) / 256, lo = (int64_t)threadIdx.x * per, hi = lo + per < n ? lo + per : n;
+  T acc = 0;
+  for (int64_t i = lo; i < hi; ++i) acc += partials[i];
+  const T r = monitor_block_sum(acc, lds);
+  if (threadIdx.x == 0) *out = r;
+}
+
 // Rank mapping onto the kernel's (I, J, K) axes.  K is always the contiguous last dim, I the
 // slowest.  rank 3: (d0,d1,d2) -> (I,J,K); rank 2: (d0,d1) -> (I,K), J has extent 1;
 // rank 1: (d0) -> (K), I and J have extent 1.

@@ -59,7 +59,11 @@ __global__ __launch_bounds__(256) void neptune_apply_direct(DirectParams<T, NIN>
   const int64_t eK = P.rub[2] - P.rlb[2], eJ = P.rub[1] - P.rlb[1], eI = P.rub[0] - P.rlb[0];
   const int64_t total = eI * eJ * eK;
   const int64_t flat = linear_block() * blockDim.x + threadIdx.x;
-  if (flat >= total) return;
+  // a monitored launch (apply_common.hpp MonitoredBody) keeps every lane for the workgroup reduction at the end
+  constexpr bool MON = IsMonitored<Body>::value;
+  [[maybe_unused]] T mon_term = (T)0;
+  if constexpr (!MON) { if (flat >= total) return; }
+  if (!MON || flat < total) {
   DirectAcc<T, RANK, NIN> acc{P, {0, 0, 0}};
   const int64_t row = flat / eK;
   acc.q[2] = P.rlb[2] + (flat - row * eK);
@@ -87,6 +91,13 @@ __global__ __launch_bounds__(256) void neptune_apply_direct(DirectParams<T, NIN>
   // (non-temporal: the result is not read again by this launch, and keeping it out of L2 leaves the neighbours' lines there --
   //  rows form 1024^3 7-point 2.52 -> 2.84 TB/s)
   __builtin_nontemporal_store(inside ? val : OutsideOf<Body, T>::apply(body, through), P.out + o);
+  if constexpr (MON) mon_term = monitor_term(inside, val, through);
+  }
+  }
+  if constexpr (MON) {
+    __shared__ T mon_red[4];
+    const T sum = monitor_block_sum(mon_term, mon_red);
+    if (threadIdx.x == 0) body.partials[linear_block()] = sum;
   }
 }
 
@@ -152,11 +163,17 @@ template <class Body, class T, int RANK, int NIN>
 __global__ __launch_bounds__(256) void neptune_apply_rows(DirectParams<T, NIN> P, Body body, uint32_t nchunk) {
   const int64_t b = linear_block();
   const int32_t eJ = (int32_t)(P.rub[1] - P.rlb[1]), eK = (int32_t)(P.rub[2] - P.rlb[2]);
-  if (b >= (P.rub[0] - P.rlb[0]) * (int64_t)eJ * nchunk) return;  // the folded grid's last row of workgroups
+  constexpr bool MON = IsMonitored<Body>::value;   // as in neptune_apply_direct
+  [[maybe_unused]] T mon_term = (T)0;
+  if (b >= (P.rub[0] - P.rlb[0]) * (int64_t)eJ * nchunk) {  // the folded grid's last row of workgroups
+    if constexpr (MON) { if (threadIdx.x == 0) body.partials[b] = (T)0; }
+    return;
+  }
   const uint32_t row = (uint32_t)(b / nchunk), c = (uint32_t)(b - (int64_t)row * nchunk);
   const int32_t i = (int32_t)(row / (uint32_t)eJ), j = (int32_t)(row - (uint32_t)i * (uint32_t)eJ);
   const int32_t k = (int32_t)c * 256 + (int32_t)threadIdx.x;
-  if (k >= eK) return;
+  if constexpr (!MON) { if (k >= eK) return; }
+  if (!MON || k < eK) {
   RowAcc<T, RANK, NIN> a{P, (int32_t)P.rlb[0] + i, (int32_t)P.rlb[1] + j, (int32_t)P.rlb[2] + k};
   const int64_t pi = a.qi + P.olb[0], pj = a.qj + P.olb[1], pk = a.qk + P.olb[2];
   const bool inside = pi >= P.lb[0] && pi < P.ub[0] && pj >= P.lb[1] && pj < P.ub[1] && pk >= P.lb[2] && pk < P.ub[2];
@@ -174,6 +191,13 @@ __global__ __launch_bounds__(256) void neptune_apply_rows(DirectParams<T, NIN> P
   const T through = in0[(uint32_t)a.qk];  // copy-through: physical-index-wise (DataflowLowering.cpp:283-287)
   const T val = body(a);
   __builtin_nontemporal_store(inside ? val : OutsideOf<Body, T>::apply(body, through), out + (uint32_t)a.qk);
+  if constexpr (MON) mon_term = monitor_term(inside, val, through);
+  }
+  }
+  if constexpr (MON) {
+    __shared__ T mon_red[4];
+    const T sum = monitor_block_sum(mon_term, mon_red);
+    if (threadIdx.x == 0) body.partials[b] = sum;
   }
 }
 

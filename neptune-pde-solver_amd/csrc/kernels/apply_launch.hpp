@@ -330,7 +330,7 @@ struct TileFor {
 // ... for a body: a group (ResultsOf<Body> > 1) has no plane-in-LDS form, so every table row -- the PLN rows too -- is that
 // shape of the march kernel for it; footprints only the LDS kernels hold never get here (launch_apply_group)
 template <class Body, class T, class FP, int RANK, int RJ, int WJ, int WK, bool DPP, bool NT, int PF, bool NTL, bool LDSJ, bool JK, bool JHL, int KD, bool PLN>
-using TileOf = std::conditional_t<(ResultsOf<Body>::value > 1),
+using TileOf = std::conditional_t<(ResultsOf<Body>::value > 1 || IsMonitored<Body>::value),   // (a monitored body likewise: launch_apply_norm)
                                   Tile<march_rows<FP, RANK>(RJ), WJ, WK, DPP, NT, PF, NTL, LDSJ, (JK) && RANK == 2, JHL, KD, false>,
                                   typename TileFor<T, FP, RANK, RJ, WJ, WK, DPP, NT, PF, NTL, LDSJ, JK, JHL, KD, PLN>::type>;
 // star footprints: the centre plane in LDS, the ring of own cells in registers; box footprints: every live plane in LDS
@@ -415,8 +415,17 @@ inline void launch_march_variant(MarchParams<T, NIN>& P, const Body& body, int64
   }
   P.chunk = (int32_t)chunk;
   const auto kern = march_kernel_fn<Body, T, RANK, NIN, FP, TL>();
+  if constexpr (IsMonitored<Body>::value) {
+    // one partial per workgroup, after those of the call's earlier launches (launch_apply_norm)
+    if (body.plan->counting) { body.plan->blocks += blocks; return; }
+    Body mb = body;
+    mb.partials = static_cast<T*>(body.plan->base) + body.plan->blocks;
+    body.plan->blocks += blocks;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(kWave * WJ * WK), 0, stream, P, mb);
+  } else {
   hipLaunchKernelGGL(kern, dim3((uint32_t)blocks),
                      dim3(kWave * WJ * WK), 0, stream, P, body);
+  }
   NEPTUNE_HIP_CHECK(hipGetLastError());
 }
 
@@ -678,8 +687,19 @@ inline int launch_direct(const Body& body, const neptune_hip_apply_geom_t* g, co
     }
     const int64_t nchunk = (eK + 255) / 256;
     if (narrow && rows * nchunk < lim) {
+      const dim3 grid = grid_for_blocks(rows * nchunk);
+      if constexpr (IsMonitored<Body>::value) {
+        // one partial per workgroup of the (possibly folded) grid, after those of the call's earlier launches
+        const int64_t nb = (int64_t)grid.x * grid.y;
+        if (body.plan->counting) { body.plan->blocks += nb; return NEPTUNE_HIP_OK; }
+        Body mb = body;
+        mb.partials = static_cast<T*>(body.plan->base) + body.plan->blocks;
+        body.plan->blocks += nb;
+        hipLaunchKernelGGL((neptune_apply_rows<Body, T, RANK, NIN>), grid, dim3(256), 0, stream, P, mb, (uint32_t)nchunk);
+      } else {
       hipLaunchKernelGGL((neptune_apply_rows<Body, T, RANK, NIN>), grid_for_blocks(rows * nchunk), dim3(256), 0, stream, P,
                          body, (uint32_t)nchunk);
+      }
       NEPTUNE_HIP_CHECK(hipGetLastError());
       return NEPTUNE_HIP_OK;
     }
@@ -690,10 +710,35 @@ inline int launch_direct(const Body& body, const neptune_hip_apply_geom_t* g, co
     fprintf(stderr, "[NeptuneRT][HIP] direct grid of %lld workgroups is not launchable\n", (long long)blocks);
     abort();
   }
+  if constexpr (IsMonitored<Body>::value) {
+    const dim3 grid = grid_for_blocks(blocks);
+    const int64_t nb = (int64_t)grid.x * grid.y;
+    if (body.plan->counting) { body.plan->blocks += nb; return NEPTUNE_HIP_OK; }
+    Body mb = body;
+    mb.partials = static_cast<T*>(body.plan->base) + body.plan->blocks;
+    body.plan->blocks += nb;
+    hipLaunchKernelGGL((neptune_apply_direct<Body, T, RANK, NIN>), grid, dim3(256), 0, stream, P, mb);
+  } else {
   hipLaunchKernelGGL((neptune_apply_direct<Body, T, RANK, NIN>), grid_for_blocks(blocks), dim3(256), 0, stream, P,
                      body);
+  }
   NEPTUNE_HIP_CHECK(hipGetLastError());
   return NEPTUNE_HIP_OK;
+}
+
+// whether tile `variant` of the rank's table stands for one of the LDS kernels (apply_plane.hpp) for this footprint: what
+// TileFor::pln says at compile time
+template <class T, class FP, int RANK>
+inline bool tile_is_lds_kernel(int variant) {
+  const MarchVariant* mv = march_variant(RANK, variant);
+  return tile2_only<T, FP, RANK>() ||
+         ((plane_capable<FP, RANK>() || planes_capable<T, FP, RANK>()) && ((mv && mv->pln) || plane_only<T, FP, RANK>()));
+}
+// the counting pass of a monitored call (launch_apply_norm below) launches nothing and leaves no launch note
+template <class Body>
+inline bool monitor_counting(const Body& body) {
+  if constexpr (IsMonitored<Body>::value) return body.plan->counting;
+  else return false;
 }
 
 template <class Body, class T, int RANK, int NIN, class FP>
@@ -704,15 +749,23 @@ inline int launch_apply_impl(const Body& body, const neptune_hip_apply_geom_t* g
   for (int d = 0; d < RANK; ++d)
     if (g->region_lb[d] == g->region_ub[d]) return NEPTUNE_HIP_OK;  // empty region: nothing to do
 
-  if constexpr (FP::MARCH_OK) if (kernel == NEPTUNE_HIP_KERNEL_MARCH) {
+  // a monitored body on a footprint only the LDS kernels hold: no march instantiation exists (or could be compiled) for it
+  constexpr bool kMonitoredLdsOnly = IsMonitored<Body>::value && FP::MARCH_OK && (plane_only<T, FP, RANK>() || tile2_only<T, FP, RANK>());
+  if constexpr (kMonitoredLdsOnly) { if (kernel == NEPTUNE_HIP_KERNEL_MARCH) return NEPTUNE_HIP_EUNSUPPORTED; }
+  if constexpr (FP::MARCH_OK && !kMonitoredLdsOnly) if (kernel == NEPTUNE_HIP_KERNEL_MARCH) {
     MarchParams<T, NIN> P{};
     for (int k = 0; k < NIN; ++k) P.in[k] = static_cast<const T*>(in[k]);
     P.out = static_cast<T*>(out);
     int variant = pick_march_variant<T, RANK, FP>(g, cfg);
     if (RANK == 3 && variant == 6 && !(cfg && cfg->variant == 6) && march3_variant_scratch<Body, T, RANK, NIN, FP>(6) > 0)
       variant = 4;  // automatic choice only: this body spills on the 8-rows-per-lane tile
-    if constexpr (ResultsOf<Body>::value > 1) {
-      // a group: an automatic choice never lands on a tile its kernel spills on (an explicit tile is taken as asked)
+    if constexpr (IsMonitored<Body>::value) {
+      // no monitored form of the plane-in-LDS kernels: a request planned onto one is refused, nothing launched
+      if (tile_is_lds_kernel<T, FP, RANK>(variant)) return NEPTUNE_HIP_EUNSUPPORTED;
+    }
+    if constexpr (ResultsOf<Body>::value > 1 || IsMonitored<Body>::value) {
+      // a group or a monitored body: an automatic choice never lands on a tile its kernel spills on (an explicit tile is
+      // taken as asked)
       if (!(cfg && cfg->variant >= 0 && cfg->variant < march_variant_count(RANK))) {
         variant = group_auto_variant<Body, T, RANK, NIN, FP>(variant);
         if (variant < 0) return NEPTUNE_HIP_EUNSUPPORTED;
@@ -779,7 +832,7 @@ inline int launch_apply_impl(const Body& body, const neptune_hip_apply_geom_t* g
       P.rI0 = (int32_t)rlb[0]; P.rI1 = (int32_t)rub[0];
     }
     launch_march<Body, T, RANK, NIN, FP>(variant, P, body, P.rI1 - P.rI0, cfg ? cfg->chunk : 0, stream);
-    neptune_hip_note_launch(NEPTUNE_HIP_KERNEL_MARCH, variant, P.chunk);
+    if (!monitor_counting(body)) neptune_hip_note_launch(NEPTUNE_HIP_KERNEL_MARCH, variant, P.chunk);
     int rc = NEPTUNE_HIP_OK;
     if (P.N2 % (16 / (int)sizeof(T)) != 0) {
       // ragged rows: cells [Ks, N2) of every row the march launch stored -- fewer than 3*VK per row -- through the
@@ -798,8 +851,44 @@ inline int launch_apply_impl(const Body& body, const neptune_hip_apply_geom_t* g
     return rc;
   }
 
-  neptune_hip_note_launch(NEPTUNE_HIP_KERNEL_DIRECT, -1, 0);
+  if (!monitor_counting(body)) neptune_hip_note_launch(NEPTUNE_HIP_KERNEL_DIRECT, -1, 0);
   return launch_direct<Body, T, RANK, NIN>(body, g, in, out, stream, cfg && (cfg->flags & NEPTUNE_HIP_FLAG_DIRECT_FLAT));
+}
+
+// ---- a monitored launch: the apply and S = sum (new - old)^2 over apply.bounds x launch region --------
+// Everything launch_apply_impl does for `body`, through the MonitoredBody instantiations of the march and direct kernels
+// (apply_common.hpp): a counting pass walks the same plan without launching and adds up the workgroups of the march launch
+// and of the ragged-row / row-tail launches behind it, the partials buffer is sized by that, the launching pass hands
+// every launch its slice, and neptune_monitor_final adds the partials in index order into *sum_out.  No atomics; the bits
+// of S depend on the launch configuration (tile, chunk) only.  Asynchronous.  No first-use measuring: the automatic tile,
+// or cfg's.  NEPTUNE_HIP_EUNSUPPORTED, nothing launched: a plan onto the plane-in-LDS kernels, every tile spilling, a
+// workspace that would have to grow while the stream is being captured.  sum_out overlapping a field: NEPTUNE_HIP_EINVAL.
+template <class Body, class T, int RANK, int NIN, class FP>
+inline int launch_apply_norm(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* sum_out,
+                             hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
+  if (!g || !in || !out || !sum_out) return NEPTUNE_HIP_EINVAL;
+  int rc = geom_validate(g);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  if (g->rank != RANK || g->num_inputs != NIN) return NEPTUNE_HIP_EINVAL;
+  if ((uintptr_t)sum_out % sizeof(T) != 0) return NEPTUNE_HIP_EINVAL;
+  if (buffers_overlap(sum_out, sizeof(T), out, geom_box_bytes(g->out_lb, g->out_ub, RANK, sizeof(T)))) return NEPTUNE_HIP_EINVAL;
+  for (int k = 0; k < NIN; ++k)
+    if (in[k] && buffers_overlap(sum_out, sizeof(T), in[k], geom_box_bytes(g->in_lb[k], g->in_ub[k], RANK, sizeof(T)))) return NEPTUNE_HIP_EINVAL;
+  using MB = MonitoredBody<Body, T>;
+  MonitorPlan mp = {true, 0, nullptr};
+  const MB mb = {body, nullptr, &mp};
+  rc = launch_apply_impl<MB, T, RANK, NIN, FP>(mb, g, in, out, stream, cfg);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  const int64_t blocks = mp.blocks;
+  if (blocks > 0x7fffffffLL) return NEPTUNE_HIP_EUNSUPPORTED;
+  void* ws = neptune_hip_monitor_workspace((size_t)(blocks > 0 ? blocks : 1) * sizeof(T), (void*)stream);
+  if (!ws) return NEPTUNE_HIP_EUNSUPPORTED;
+  mp = {false, 0, ws};
+  rc = launch_apply_impl<MB, T, RANK, NIN, FP>(mb, g, in, out, stream, cfg);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  hipLaunchKernelGGL(neptune_monitor_final<T>, dim3(1), dim3(256), 0, stream, static_cast<const T*>(ws), (int64_t)mp.blocks, static_cast<T*>(sum_out));
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  return NEPTUNE_HIP_OK;
 }
 
 // ---- measured launch choice at first use, remembered as wisdom -----------------------------------------------

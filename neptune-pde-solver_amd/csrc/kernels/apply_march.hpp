@@ -371,8 +371,13 @@ __global__ __launch_bounds__(kWave* TL::WJ* TL::WK) void neptune_apply_march(Mar
 
   const int32_t ib = P.rI0 + (int32_t)ct * P.chunk;
   const int32_t ie = (ib + P.chunk < P.rI1) ? ib + P.chunk : P.rI1;
-  if (ib >= ie) return;
+  if (ib >= ie) {
+    if constexpr (IsMonitored<Body>::value) { if (threadIdx.x == 0) body.partials[blockIdx.x] = (T)0; }
+    return;
+  }
   const int64_t plane_b = (int64_t)P.N1 * P.N2 * (int64_t)sizeof(T);
+  // a monitored launch (apply_common.hpp MonitoredBody): this lane's share of S = sum (new - old)^2
+  [[maybe_unused]] T mon_acc = (T)0;
 
   // byte offsets of the rows this wave touches (halo rows clamped into the field: a clamped
   // row is only ever read for cells outside apply.bounds, whose body value is discarded).  One set for the result and
@@ -739,6 +744,8 @@ __global__ __launch_bounds__(kWave* TL::WJ* TL::WK) void neptune_apply_march(Mar
         if constexpr (HMASK & 1u) through = ring[0][R0][r + R1][e];  // input 0 owns ring slot 0
         else through = pt[0][r][e];
         res[e] = inside ? val : OutsideOf<Body, T>::apply(body, through);
+        // the store's own predicates plus `inside`: copy-through, clamped and predicated-off cells add nothing
+        if constexpr (IsMonitored<Body>::value) mon_acc += monitor_term(inside && row_ok[r] && lane_ok, val, through);
       });
       if (row_ok[r] && lane_ok) {
         // rowb[0][r+R1] is this own row's offset in the result (own rows are never clamped when row_ok)
@@ -755,6 +762,21 @@ __global__ __launch_bounds__(kWave* TL::WJ* TL::WK) void neptune_apply_march(Mar
       constexpr int ph = phc;
       if (i + ph < ie) step(i + ph, phc);
     });
+  }
+  if constexpr (IsMonitored<Body>::value) {
+    // one partial per workgroup, at its linear index.  The tiles with an LDS exchange declare up to 64 KiB already: the
+    // reduction reuses the exchange buffer once every wave is past its last read of it (waves outside the field are still
+    // here: they took part in every barrier above and add +0); the other tiles get a slot per wave of their own.
+    T* red;
+    if constexpr (LDSJ) {
+      __syncthreads();
+      red = reinterpret_cast<T*>(&lds_rows[0][0][0][0][0]);
+    } else {
+      __shared__ T mon_red[WJ * WK];
+      red = mon_red;
+    }
+    const T sum = monitor_block_sum(mon_acc, red);
+    if (threadIdx.x == 0) body.partials[blockIdx.x] = sum;
   }
 }
 

@@ -72,6 +72,7 @@ std::string report_json(const LowerInfo& info) {
       << (a.halo_input < 0 ? "pointwise" : (a.box ? "box" : "star")) << "\", \"elem\": \"" << a.elem << "\", \"halo0\": " << a.halo0
       << ", \"geom_symbol\": \"" << a.geom_symbol << "\", \"exact\": " << (a.exact ? "true" : "false")
       << ", \"leapfrog_symbol\": \"" << a.leapfrog_symbol << "\"";
+    if (!a.norm_symbol.empty()) o << ", \"norm_symbol\": \"" << a.norm_symbol << "\"";
     if (a.group >= 0) o << ", \"group\": " << a.group;
     o << "}";
   }
@@ -170,6 +171,30 @@ int guarded(char** diag_out, F&& body) {
 }
 }  // namespace
 
+namespace neptune_lowering {
+// option lines of a module text: "// neptune-hip-option: <name>" at the start of a line (leading blanks allowed)
+LowerOptions options_in_text(const char* mlir_text) {
+  LowerOptions opt;
+  if (!mlir_text) return opt;
+  static const char kPrefix[] = "// neptune-hip-option:";
+  const std::string text = mlir_text;
+  size_t pos = 0;
+  while (pos < text.size()) {
+    size_t eol = text.find('\n', pos);
+    if (eol == std::string::npos) eol = text.size();
+    size_t b = text.find_first_not_of(" \t", pos);
+    if (b != std::string::npos && b < eol && text.compare(b, sizeof(kPrefix) - 1, kPrefix) == 0) {
+      std::string name = text.substr(b + sizeof(kPrefix) - 1, eol - b - (sizeof(kPrefix) - 1));
+      const size_t f = name.find_first_not_of(" \t"), l = name.find_last_not_of(" \t\r");
+      name = f == std::string::npos ? "" : name.substr(f, l - f + 1);
+      if (name == "norm-entries") opt.norm_entries = true;
+    }
+    pos = eol + 1;
+  }
+  return opt;
+}
+}  // namespace neptune_lowering
+
 extern "C" {
 
 const char* neptune_lowering_version(void) { return "neptune-lowering 0.1 (NeptuneIR hot-path subset -> HIP, gfx950)"; }
@@ -196,7 +221,7 @@ int neptune_lowering_to_hip(const char* mlir_text, char** source_out, char** rep
     Diag d;
     std::string src;
     LowerInfo info;
-    if (!front(mlir_text, m, d) || !lower_to_hip(m, src, info, d)) {
+    if (!front(mlir_text, m, d) || !lower_to_hip(m, src, info, d, options_in_text(mlir_text))) {
       if (diag_out) *diag_out = dup(d.message);
       return -1;
     }

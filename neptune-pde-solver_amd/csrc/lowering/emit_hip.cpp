@@ -651,7 +651,7 @@ struct Emitter {
   // (caller-supplied boxes, bounds, region, stream and launch configuration; no allocation, no synchronisation).
   // The slab decomposition drives user stencils through them.
   void emit_geom_entries(const std::string& sym, const std::string& reach, const std::string& body, const std::string& init,
-                         const std::string& T, int rank, int nin, const std::string& fp) {
+                         const std::string& T, int rank, int nin, const std::string& fp, bool norm = false) {
     static const char* const suffix[3] = {"", "2", "3"};
     static const char* const launch[3] = {"launch_apply", "launch_apply_twice", "launch_apply_thrice"};
     for (int v = 0; v < 3; ++v) {
@@ -669,8 +669,28 @@ struct Emitter {
                    << "  return neptune_hip::" << launch[v] << "<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
                    << ">(" << body << "{" << init << "}, g, in, out, (hipStream_t)stream, cfg);\n}\n";
     }
+    if (norm)
+      geom_entries << "// the monitored launch (lowering option norm-entries; neptune_hip_apply_norm_fn, include/neptune_hip.h): the apply and\n"
+                   << "// S = sum (new - old)^2 over apply.bounds x launch region into *sum_out, or NEPTUNE_HIP_EUNSUPPORTED, nothing launched\n"
+                   << "extern \"C\" int " << sym << "N(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* sum_out,\n"
+                   << "    void* stream, const neptune_hip_launch_cfg_t* cfg) {\n"
+                   << "  if (!g || !in || !out || !sum_out) return NEPTUNE_HIP_EINVAL;\n"
+                   << "  const int rc = neptune_hip::geom_check_radius(g, " << reach << ");\n"
+                   << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
+                   << "  if (neptune_hip::check_no_alias(g, in, out, sizeof(" << T << ")) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;\n"
+                   << "  return neptune_hip::launch_apply_norm<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
+                   << ">(" << body << "{" << init << "}, g, in, out, sum_out, (hipStream_t)stream, cfg);\n}\n";
     geom_entries << "// march tiles this module holds for that entry (plan-time tuning: neptune_hip_autotune_fn)\n"
                  << "extern \"C\" int " << sym << "_variants(int rank) { return neptune_hip::march_variant_count(rank); }\n\n";
+  }
+
+  // Lowering option norm-entries: an apply whose input 0 has the result's element type and a box equal to the result's --
+  // the old state of an iteration u <- A(u) -- also exports its monitored launch <geom_symbol>N
+  bool norm_entries = false;
+  bool wants_norm_entry(const Op& op) const {
+    const int nin = (int)op.operands.size();
+    const Type& res = op.types[nin];
+    return norm_entries && op.types[0].elem == res.elem && op.types[0].bounds == res.bounds;
   }
 
   // A two-level scheme u(n+1) = B(u(n), u(n-1), c...) the chain kernel can step twice per pass: input 0 a star of radius
@@ -745,7 +765,9 @@ struct Emitter {
       ApplyInfo ai = apply_info(s, tag, fp, fp.rank, res.elem, halo0_of(fp));
       ai.group = group;
       ai.geom_symbol = tag + "__geom";
-      emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
+      if (wants_norm_entry(op)) ai.norm_symbol = ai.geom_symbol + "N";
+      emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag,
+                        !ai.norm_symbol.empty());
       if (leapfrog_capable(fp, op)) {
         ai.leapfrog_symbol = ai.geom_symbol + "L2";
         emit_leapfrog_entry(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
@@ -791,7 +813,9 @@ struct Emitter {
           << halo0_of(fp) << ");\n";
       ApplyInfo ai = apply_info(s, tag, fp, fp.rank, res.elem, halo0_of(fp));
       ai.geom_symbol = tag + "__geom";
-      emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
+      if (wants_norm_entry(op)) ai.norm_symbol = ai.geom_symbol + "N";
+      emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag,
+                        !ai.norm_symbol.empty());
       if (leapfrog_capable(fp, op)) {
         ai.leapfrog_symbol = ai.geom_symbol + "L2";
         emit_leapfrog_entry(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
@@ -1072,7 +1096,8 @@ struct Emitter {
     if (lit_ok) {
       ai.geom_symbol = tag + "__geom";
       geom_entries << "static const neptune_hip::Reach kTopRadiusG_" << tag << " = " << fused_reach(cfp, st.rank()) << ";\n";
-      emit_geom_entries(ai.geom_symbol, "kTopRadiusG_" + tag, body, "(" + T + ")" + lit, T, st.rank(), 1, "FP_" + ctag);
+      if (norm_entries) ai.norm_symbol = ai.geom_symbol + "N";   // the state is input 0 and the result: always eligible
+      emit_geom_entries(ai.geom_symbol, "kTopRadiusG_" + tag, body, "(" + T + ")" + lit, T, st.rank(), 1, "FP_" + ctag, norm_entries);
     }
     info.applies.push_back(ai);
     return true;
@@ -1394,8 +1419,9 @@ struct Emitter {
 
 }  // namespace
 
-bool lower_to_hip(const Module& m, std::string& out_source, LowerInfo& info, Diag& diag) {
+bool lower_to_hip(const Module& m, std::string& out_source, LowerInfo& info, Diag& diag, const LowerOptions& options) {
   Emitter e(m, diag, info);
+  e.norm_entries = options.norm_entries;
   return e.run(out_source) && diag.ok;
 }
 

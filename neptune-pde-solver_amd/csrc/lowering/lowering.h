@@ -17,6 +17,7 @@ struct ApplyInfo {
   int halo0 = 0;              // reach along dim 0 (what a slab decomposition must hold as ghost planes)
   std::string geom_symbol;    // exported geometry-level entry (empty: none)
   std::string leapfrog_symbol;  // exported leapfrog pair entry <geom_symbol>L2 of a two-level scheme (empty: none)
+  std::string norm_symbol;    // exported monitored launch <geom_symbol>N (lowering option norm-entries; empty: none)
   bool exact = true;          // false: the body uses elementary functions (exp, log, ...): a few ulp, not bit-exact
   int group = -1;             // index into LowerInfo::groups when this apply is a member of a group
 };
@@ -59,8 +60,16 @@ struct LowerInfo {
   std::vector<Outlined> outlined;
 };
 
+// What a caller may ask for beyond the default lowering.  The C ABI carries the options inside the module text, one comment
+// line each -- "// neptune-hip-option: <name>" (include/neptune_lowering.h) -- so that a module's text still says everything
+// about its artefact.
+struct LowerOptions {
+  bool norm_entries = false;   // "norm-entries": eligible applies also export their monitored launch <fn>_<k>__geomN
+};
+LowerOptions options_in_text(const char* mlir_text);   // capi.cpp
+
 // emit_hip.cpp
-bool lower_to_hip(const Module& m, std::string& out_source, LowerInfo& info, Diag& diag);
+bool lower_to_hip(const Module& m, std::string& out_source, LowerInfo& info, Diag& diag, const LowerOptions& options = LowerOptions());
 
 }  // namespace neptune_lowering
 

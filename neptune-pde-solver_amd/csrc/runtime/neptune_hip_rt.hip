@@ -18,6 +18,7 @@
 
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"
+#include "../kernels/reduce_apply.hpp"
 #include "../kernels/util_kernels.hpp"
 #include "rt_bodies.hpp"
 
@@ -33,6 +34,8 @@ struct RuntimeState {
   int cus = 0;
   unsigned long long* counter = nullptr;  // device word for count_mismatch
   void* reduce_ws = nullptr;              // kReduceBlocks partials + 1 result (8 B each)
+  void* monitor_ws = nullptr;             // partials of one monitored launch (neptune_hip_monitor_workspace), grown on demand
+  size_t monitor_bytes = 0;
   // idle device blocks kept for the temporaries of lowered functions (neptune_hip_pool_*)
   struct PoolBlock { void* p; size_t bytes; };
   std::vector<PoolBlock> pool;
@@ -184,6 +187,68 @@ int vec_update(int dtype, int64_t n, double a, const void* x, void* y, void* str
 }
 }  // namespace
 
+namespace {
+// (a - b) * (a - b): the term of S, as a two-input pointwise body for the reduce(apply) kernels
+template <class T>
+struct DiffSquared {
+  template <class A>
+  __device__ __forceinline__ T operator()(const A& acc) const {
+    const T d = acc.template get<0, 0, 0, 0>() - acc.template get<1, 0, 0, 0>();
+    return d * d;
+  }
+};
+template <class T>
+int update_norm(const neptune_hip_apply_geom_t* g, const void* a, const void* b, void* sum_out, hipStream_t st) {
+  // a two-input apply geometry: input 0 = a in the result's box, input 1 = b in input 0's box; reduced box = bounds x region
+  neptune_hip_apply_geom_t g2 = *g;
+  g2.num_inputs = 2;
+  bool empty = false;
+  for (int d = 0; d < g->rank; ++d) {
+    g2.in_lb[0][d] = g->out_lb[d]; g2.in_ub[0][d] = g->out_ub[d];
+    g2.in_lb[1][d] = g->in_lb[0][d]; g2.in_ub[1][d] = g->in_ub[0][d];
+    const int64_t lo = std::max(g->lb[d] - g->out_lb[d], g->region_lb[d]), hi = std::min(g->ub[d] - g->out_lb[d], g->region_ub[d]);
+    g2.region_lb[d] = lo;
+    g2.region_ub[d] = hi;
+    empty = empty || lo >= hi;
+  }
+  if (empty || geom_bounds_empty(g)) {
+    NEPTUNE_HIP_CHECK(hipMemsetAsync(sum_out, 0, sizeof(T), st));   // +0
+    return NEPTUNE_HIP_OK;
+  }
+  const void* ptrs[2] = {a, b};
+  DirectParams<T, 2> P{};
+  switch (g->rank) {   // the kernels below are the rank-3 instantiations: absent axes have extent 1
+    case 1: fill_direct_params<T, 1, 2>(&g2, ptrs, nullptr, P); break;
+    case 2: fill_direct_params<T, 2, 2>(&g2, ptrs, nullptr, P); break;
+    default: fill_direct_params<T, 3, 2>(&g2, ptrs, nullptr, P); break;
+  }
+  const int64_t lim = 0x7fffff00LL;
+  bool narrow = P.n[0] * P.n[1] < lim && P.n[2] < lim;
+  for (int k = 0; k < 2; ++k) {
+    narrow = narrow && P.m[k][0] * P.m[k][1] < lim && P.m[k][2] < lim;
+    for (int ax = 0; ax < 3; ++ax) narrow = narrow && P.sh[k][ax] > -lim && P.sh[k][ax] < lim;
+  }
+  if (!narrow) return NEPTUNE_HIP_EUNSUPPORTED;   // the kernels keep coordinates and row indices in 32 bits
+  constexpr int VK = 16 / (int)sizeof(T);
+  const int64_t eK = P.rub[2] - P.rlb[2];
+  bool vec = eK % VK == 0 && P.rlb[2] % VK == 0 && P.n[2] % VK == 0;
+  for (int k = 0; k < 2; ++k) {
+    vec = vec && ((uintptr_t)ptrs[k] % 16 == 0);
+    for (int ax = 0; ax < 3; ++ax) vec = vec && P.sh[k][ax] == 0 && P.m[k][ax] == P.n[ax];
+  }
+  const int cells_per_chunk = 256 * (vec ? VK : 1), iter = vec ? kReduceApplyIter / 2 : kReduceApplyIter;
+  const int64_t nchunk = (eK + cells_per_chunk - 1) / cells_per_chunk;
+  const int64_t trips = ((P.rub[0] - P.rlb[0]) * (P.rub[1] - P.rlb[1]) * nchunk + iter - 1) / iter;
+  const int blocks = (int)(trips < kReduceBlocks ? trips : kReduceBlocks);
+  T* part = static_cast<T*>(rt().reduce_ws);
+  if (vec) hipLaunchKernelGGL((neptune_reduce_apply_vec<DiffSquared<T>, T, 3, 2>), dim3(blocks), dim3(256), 0, st, P, DiffSquared<T>{}, nchunk, part);
+  else hipLaunchKernelGGL((neptune_reduce_apply<DiffSquared<T>, T, 3, 2>), dim3(blocks), dim3(256), 0, st, P, DiffSquared<T>{}, nchunk, part);
+  hipLaunchKernelGGL(neptune_reduce_final<T>, dim3(1), dim3(256), 0, st, part, blocks, static_cast<T*>(sum_out));
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  return NEPTUNE_HIP_OK;
+}
+}  // namespace
+
 // step_loop.hip: destroys the cached graphs of the step loops (declared here rather than in a header: the headers of this
 // directory are hashed into NEPTUNE_HIP_BUILD_ID)
 namespace neptune_hip {
@@ -224,6 +289,11 @@ void neptune_hip_finalize(void) {
   if (s.reduce_ws) {
     (void)hipFree(s.reduce_ws);
     s.reduce_ws = nullptr;
+  }
+  if (s.monitor_ws) {
+    (void)hipFree(s.monitor_ws);
+    s.monitor_ws = nullptr;
+    s.monitor_bytes = 0;
   }
   step_loop_destroy_graphs();
   for (auto& b : s.pool) (void)hipFree(b.p);
@@ -413,6 +483,49 @@ int neptune_hip_apply_builtin(int body, const neptune_hip_apply_geom_t* g, const
   if (rc != NEPTUNE_HIP_OK) return rc;
   ensure_init();
   return body_entry(body)->apply(g, in, out, as_stream(stream), cfg);
+}
+
+// ---------------------------------------------------------------- monitored applies
+int neptune_hip_apply_builtin_norm(int body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* sum_out,
+                                   void* stream, const neptune_hip_launch_cfg_t* cfg) {
+  if (!g || !in || !out || !sum_out) return NEPTUNE_HIP_EINVAL;
+  if (body < 0 || body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
+  int rc = geom_validate(g);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  for (int k = 0; k < g->num_inputs; ++k)
+    if (!in[k]) return NEPTUNE_HIP_EINVAL;
+  rc = check_no_alias(g, in, out, body_elem_size(body));
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  ensure_init();
+  return body_entry(body)->apply_norm(g, in, out, sum_out, as_stream(stream), cfg);
+}
+
+void* neptune_hip_monitor_workspace(size_t bytes, void* stream) {
+  ensure_init();
+  RuntimeState& s = rt();
+  std::lock_guard<std::mutex> lk(s.mu);
+  if (bytes <= s.monitor_bytes) return s.monitor_ws;
+  // growing frees the old block, which waits for the launches that may still write it: not inside a stream capture
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(as_stream(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+  if (cs != hipStreamCaptureStatusNone) return nullptr;
+  size_t want = s.monitor_bytes ? s.monitor_bytes : (size_t)1 << 16;
+  while (want < bytes) want *= 2;
+  if (s.monitor_ws) NEPTUNE_HIP_CHECK(hipFree(s.monitor_ws));
+  s.monitor_ws = nullptr;
+  s.monitor_bytes = 0;
+  NEPTUNE_HIP_CHECK(hipMalloc(&s.monitor_ws, want));
+  s.monitor_bytes = want;
+  return s.monitor_ws;
+}
+
+int neptune_hip_update_norm(int dtype, const neptune_hip_apply_geom_t* g, const void* a, const void* b, void* sum_out, void* stream) {
+  if (!g || !a || !b || !sum_out) return NEPTUNE_HIP_EINVAL;
+  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
+  const int rc = geom_validate(g);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  ensure_init();
+  return dtype == NEPTUNE_HIP_F64 ? update_norm<double>(g, a, b, sum_out, as_stream(stream)) : update_norm<float>(g, a, b, sum_out, as_stream(stream));
 }
 
 // two or three chained applies of a built-in body in one pass over HBM (csrc/kernels/apply_march2.hpp)

@@ -13,6 +13,8 @@ struct Entry {
   int (*variant)(const neptune_hip_apply_geom_t*, const neptune_hip_launch_cfg_t*);
   // two / three chained applies in one launch (apply_march2.hpp); nullptr for bodies without that form
   int (*chain)(int applies, const neptune_hip_apply_geom_t*, const void* const*, void*, hipStream_t, const neptune_hip_launch_cfg_t*);
+  // the monitored launch (apply_launch.hpp launch_apply_norm): the apply and the update norm into a device scalar
+  int (*apply_norm)(const neptune_hip_apply_geom_t*, const void* const*, void*, void* sum_out, hipStream_t, const neptune_hip_launch_cfg_t*);
 };
 const Entry& lap2d5();
 const Entry& lap3d7();

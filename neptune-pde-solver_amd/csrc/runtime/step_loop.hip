@@ -278,43 +278,16 @@ int choose_grouping(const LoopKey& key, const StreamScope& sc, bool measure, int
 
 int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last leapfrog loop
 int64_t g_system_counts[2] = {0, 0}; // steps / graph launches of the last system loop
+void* g_until_sum = nullptr;            // the until loop's device scalar (one element), released with the graphs
+int64_t g_until_counts[3] = {0, 0, 0};  // monitored checked steps / fallback checked steps / checks of the last until loop
 
-}  // namespace
-
-namespace neptune_hip {
-// for neptune_hip_finalize (declared in neptune_hip_rt.hip; not exported)
-__attribute__((visibility("hidden"))) void step_loop_destroy_graphs() {
-  std::lock_guard<std::mutex> lk(g_loop_mu);
-  for (auto& e : g_loops) {
-    destroy_graph(e);
-    e.stamp = 0;
-  }
-}
-}  // namespace neptune_hip
-
-extern "C" {
-
-// ---------------------------------------------------------------- one-level loop: two fields, ping-pong
-int neptune_hip_step_loop(neptune_hip_apply_fn fn, int body, const neptune_hip_apply_geom_t* g, void* const fields[2],
-                          const void* const* in, int64_t steps, void* stream, const neptune_hip_launch_cfg_t* cfg) {
-  return neptune_hip_step_loop_pairs(fn, nullptr, body, g, fields, in, steps, stream, cfg);
-}
-
-int neptune_hip_step_loop_pairs(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, int body, const neptune_hip_apply_geom_t* g,
-                                void* const fields[2], const void* const* in, int64_t steps, void* stream,
-                                const neptune_hip_launch_cfg_t* cfg) {
-  return neptune_hip_step_loop_chain(fn, fn2, nullptr, body, g, fields, in, steps, stream, cfg);
-}
-
-int neptune_hip_step_loop_chain(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, neptune_hip_apply_fn fn3, int body,
-                                const neptune_hip_apply_geom_t* g, void* const fields[2], const void* const* in, int64_t steps,
-                                void* stream, const neptune_hip_launch_cfg_t* cfg) {
-  if (!g || !fields || !fields[0] || !fields[1] || fields[0] == fields[1] || steps < 0) return NEPTUNE_HIP_EINVAL;
-  if (g->num_inputs < 1 || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
-  if (g->num_inputs > 1 && !in) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
+// ---------------------------------------------------------------- the one-level loop on a stream scope
+// `steps` applies from fields[0] (the state) into fields[steps % 2]: what neptune_hip_step_loop_chain is once its arguments
+// are checked, and what neptune_hip_step_loop_until runs between two checks.
+int one_level_loop(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, neptune_hip_apply_fn fn3, int body,
+                   const neptune_hip_apply_geom_t* g, void* const fields[2], const void* const* in, int64_t steps,
+                   const neptune_hip_launch_cfg_t* cfg) {
   if (steps == 0) return NEPTUNE_HIP_OK;
-  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
   const neptune_hip_apply_fn chain[2] = {fn ? fn2 : nullptr, fn ? fn3 : nullptr};
   LoopKey key;
   init_key(key, fn, fn ? -1 : body, g, cfg, sc.stream);
@@ -369,6 +342,139 @@ int neptune_hip_step_loop_chain(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn
     if (rc2 != NEPTUNE_HIP_EUNSUPPORTED) return rc2;
   }
   return run(1, steps);
+}
+
+}  // namespace
+
+namespace neptune_hip {
+// for neptune_hip_finalize (declared in neptune_hip_rt.hip; not exported)
+__attribute__((visibility("hidden"))) void step_loop_destroy_graphs() {
+  std::lock_guard<std::mutex> lk(g_loop_mu);
+  for (auto& e : g_loops) {
+    destroy_graph(e);
+    e.stamp = 0;
+  }
+  if (g_until_sum) {
+    (void)hipFree(g_until_sum);
+    g_until_sum = nullptr;
+  }
+}
+}  // namespace neptune_hip
+
+extern "C" {
+
+// ---------------------------------------------------------------- one-level loop: two fields, ping-pong
+int neptune_hip_step_loop(neptune_hip_apply_fn fn, int body, const neptune_hip_apply_geom_t* g, void* const fields[2],
+                          const void* const* in, int64_t steps, void* stream, const neptune_hip_launch_cfg_t* cfg) {
+  return neptune_hip_step_loop_pairs(fn, nullptr, body, g, fields, in, steps, stream, cfg);
+}
+
+int neptune_hip_step_loop_pairs(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, int body, const neptune_hip_apply_geom_t* g,
+                                void* const fields[2], const void* const* in, int64_t steps, void* stream,
+                                const neptune_hip_launch_cfg_t* cfg) {
+  return neptune_hip_step_loop_chain(fn, fn2, nullptr, body, g, fields, in, steps, stream, cfg);
+}
+
+int neptune_hip_step_loop_chain(neptune_hip_apply_fn fn, neptune_hip_apply_fn fn2, neptune_hip_apply_fn fn3, int body,
+                                const neptune_hip_apply_geom_t* g, void* const fields[2], const void* const* in, int64_t steps,
+                                void* stream, const neptune_hip_launch_cfg_t* cfg) {
+  if (!g || !fields || !fields[0] || !fields[1] || fields[0] == fields[1] || steps < 0) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs < 1 || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs > 1 && !in) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  if (steps == 0) return NEPTUNE_HIP_OK;
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  return one_level_loop(sc, fn, fn2, fn3, body, g, fields, in, steps, cfg);
+}
+
+// ---------------------------------------------------------------- iteration to a tolerance: the one-level loop in blocks
+void neptune_hip_until_loop_counts(int64_t* fused, int64_t* fallback, int64_t* checks) {
+  if (fused) *fused = g_until_counts[0];
+  if (fallback) *fallback = g_until_counts[1];
+  if (checks) *checks = g_until_counts[2];
+}
+
+int neptune_hip_step_loop_until(neptune_hip_apply_fn fn, neptune_hip_apply_norm_fn fn_norm, int body, int dtype_of_fn,
+                                const neptune_hip_apply_geom_t* g, void* const fields[2], const void* const* in, int64_t max_steps,
+                                int64_t check_every, double tol2, void* stream, const neptune_hip_launch_cfg_t* cfg,
+                                int64_t* steps_done, double* last_sum) {
+  g_until_counts[0] = g_until_counts[1] = g_until_counts[2] = 0;
+  if (steps_done) *steps_done = 0;
+  if (last_sum) *last_sum = 0.0;
+  if (!g || !fields || !fields[0] || !fields[1] || fields[0] == fields[1] || max_steps < 0 || check_every < 1) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs < 1 || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs > 1 && !in) return NEPTUNE_HIP_EINVAL;
+  int dtype = dtype_of_fn;
+  if (!fn) {
+    if (body < 0 || body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
+    dtype = body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64;
+  }
+  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
+  {
+    // the scalar is read back after every block: not while the caller's stream is being captured
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return NEPTUNE_HIP_EINVAL;
+  }
+  ensure_init();
+  if (max_steps == 0) return NEPTUNE_HIP_OK;
+  if (!g_until_sum) NEPTUNE_HIP_CHECK(hipMalloc(&g_until_sum, 8));
+  void* const sum_dev = g_until_sum;
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
+  bool fused_ok = fn ? fn_norm != nullptr : true;   // false once the monitored entry has refused this geometry
+  int64_t done = 0;
+  int cur = 0;   // fields[cur] holds the state
+  double sum = 0.0;
+  while (done < max_steps) {
+    const int64_t block = check_every < max_steps - done ? check_every : max_steps - done;
+    // the block's first steps: intermediate states are not needed, so graphs and chained launches apply as in any loop
+    if (block > 1) {
+      void* const fl[2] = {fields[cur], fields[cur ^ 1]};
+      const int rc = one_level_loop(sc, fn, nullptr, nullptr, body, g, fl, in, block - 1, cfg);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+      cur ^= (int)((block - 1) & 1);
+      done += block - 1;
+      if (steps_done) *steps_done = done;
+    }
+    // the block's last step, checked
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    for (int i = 1; i < g->num_inputs; ++i) ins[i] = in[i];
+    ins[0] = fields[cur];
+    void* const out = fields[cur ^ 1];
+    int rc = NEPTUNE_HIP_EUNSUPPORTED;
+    if (fused_ok) {
+      rc = fn ? fn_norm(g, ins, out, sum_dev, (void*)sc.stream, c) : neptune_hip_apply_builtin_norm(body, g, ins, out, sum_dev, (void*)sc.stream, c);
+      if (rc == NEPTUNE_HIP_OK) ++g_until_counts[0];
+      else if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused_ok = false;   // nothing was launched: the fallback, now and for the rest of the call
+      else return rc;
+    }
+    if (rc == NEPTUNE_HIP_EUNSUPPORTED) {
+      rc = fn ? fn(g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(body, g, ins, out, (void*)sc.stream, c);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+      rc = neptune_hip_update_norm(dtype, g, out, ins[0], sum_dev, (void*)sc.stream);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+      ++g_until_counts[1];
+    }
+    cur ^= 1;
+    ++done;
+    if (steps_done) *steps_done = done;
+    if (dtype == NEPTUNE_HIP_F64) {
+      double h = 0;
+      NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, sum_dev, sizeof(h), hipMemcpyDeviceToHost, sc.stream));
+      NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+      sum = h;
+    } else {
+      float h = 0;
+      NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, sum_dev, sizeof(h), hipMemcpyDeviceToHost, sc.stream));
+      NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+      sum = (double)h;
+    }
+    ++g_until_counts[2];
+    if (last_sum) *last_sum = sum;
+    if (sum <= tol2) break;   // false for a NaN sum: such a loop runs to max_steps
+  }
+  return NEPTUNE_HIP_OK;
 }
 
 // ---------------------------------------------------------------- leapfrog loop (two-level schemes): three or four fields

@@ -77,6 +77,72 @@ def step_loop(body, a: DeviceField, b: DeviceField, bounds: Box, steps: int, oth
     return b if steps % 2 else a
 
 
+def apply_norm(body, inputs: Sequence[DeviceField], out: DeviceField, bounds: Box, sum_out=None,
+               region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
+    """a monitored launch: out = apply(inputs) {bounds} exactly as apply_builtin computes it, and S = sum (new - old)^2 over
+    the cells of `bounds` in the launch region (old = inputs[0] at the same physical index) in the field's element type.
+    `body`: a built-in body id, or the norm entry of a lowered apply (LoweredModule.norm_entry).  `sum_out`: a one-element
+    torch CUDA tensor of the field's element type that receives S in stream order (asynchronous; returns it), or None:
+    one is allocated, the call synchronises and returns S as a float.  Returns None -- having launched nothing -- when
+    the request has no monitored form (a plan onto the plane-in-LDS kernels: NEPTUNE_HIP_EUNSUPPORTED)."""
+    import torch
+    lib = _capi.load()
+    g = geom_for(inputs, out, bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    dst = sum_out if sum_out is not None else torch.empty(1, dtype=out.tensor.dtype, device=out.tensor.device)
+    cfg_p = C.byref(cfg) if cfg is not None else None
+    if hasattr(body, "fn"):
+        if body.fn_norm is None:
+            raise ValueError(f"{body.symbol}: no monitored launch (compile the module with norm_entries=True)")
+        rc, what = body.fn_norm(C.byref(g), _in_array(inputs), out.ptr, dst.data_ptr(), st, cfg_p), body.symbol
+    else:
+        rc = lib.neptune_hip_apply_builtin_norm(body, C.byref(g), _in_array(inputs), out.ptr, dst.data_ptr(), st, cfg_p)
+        what = "neptune_hip_apply_builtin_norm"
+    if rc == _capi.EUNSUPPORTED:
+        return None
+    _capi.check(rc, what)
+    if sum_out is not None:
+        return sum_out
+    torch.cuda.synchronize()
+    return float(dst.item())
+
+
+def until_loop_counts():
+    """(checked steps run as monitored launches, checked steps run as plain launch + two-field reduction, checks) of the
+    last step_loop_until call"""
+    fused, fallback, checks = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _capi.load().neptune_hip_until_loop_counts(C.byref(fused), C.byref(fallback), C.byref(checks))
+    return fused.value, fallback.value, checks.value
+
+
+def step_loop_until(body, a: DeviceField, b: DeviceField, bounds: Box, max_steps: int, tol2: float, check_every: int = 1,
+                    others: Sequence[DeviceField] = (), norm="auto", cfg: Optional[_capi.LaunchCfg] = None,
+                    stream: Optional[int] = None):
+    """iterate u <- A(u), ping-ponging between fields a and b (step 0 reads a), until S = sum (A(u) - u)^2 <= tol2 -- the
+    threshold is on S itself, no square root -- or max_steps steps have run.  S is taken every `check_every` steps, out of
+    the checked step's own launch where a monitored form exists.  `body`: a built-in body id or a lowered apply's
+    geometry-level entry (LoweredModule.geom_entry); `norm`: that apply's norm entry (LoweredModule.norm_entry), None for
+    the fallback (plain launch + one read-only pass over both fields), "auto": body's own (built-in bodies have one).
+    Blocking; -> (steps_done, last_sum).  The newest state is in (a, b)[steps_done % 2]; the other field holds state
+    steps_done - 1.  A NaN sum never satisfies the test.  until_loop_counts() tells which path the checks took."""
+    lib = _capi.load()
+    g = geom_for([a] + list(others), b, bounds)
+    fields2 = (C.c_void_p * 2)(a.ptr, b.ptr)
+    ins = _in_array([a] + list(others))
+    st = current_stream_ptr() if stream is None else stream
+    is_entry = hasattr(body, "fn")
+    fn = C.cast(body.fn, C.c_void_p) if is_entry else None
+    if isinstance(norm, str):   # "auto"
+        norm = body if is_entry else None
+    fn_norm = C.cast(norm.fn_norm, C.c_void_p) if (is_entry and norm is not None and norm.fn_norm is not None) else None
+    done, last = C.c_int64(0), C.c_double(0.0)
+    rc = lib.neptune_hip_step_loop_until(fn, fn_norm, -1 if is_entry else body, a.dtype, C.byref(g), fields2, ins, max_steps,
+                                         check_every, tol2, st, C.byref(cfg) if cfg is not None else None, C.byref(done),
+                                         C.byref(last))
+    _capi.check(rc, "neptune_hip_step_loop_until")
+    return done.value, last.value
+
+
 def _as_field(x) -> DeviceField:
     """a DeviceField as it is; a contiguous torch CUDA tensor as a field with a zero-based box"""
     if isinstance(x, DeviceField):

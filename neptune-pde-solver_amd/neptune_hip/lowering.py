@@ -63,9 +63,22 @@ def verify(text: str) -> None:
         raise LoweringError(_take(lib, diag))
 
 
-def to_hip(text: str):
-    """-> (HIP source, report dict)"""
+NORM_ENTRIES_LINE = "// neptune-hip-option: norm-entries\n"
+
+
+def with_options(text: str, norm_entries: bool = False) -> str:
+    """the module text with its lowering options: they travel in the text, one comment line each
+    (include/neptune_lowering.h), so the cache key of a module covers them"""
+    if norm_entries and NORM_ENTRIES_LINE.strip() not in text:
+        text = NORM_ENTRIES_LINE + text
+    return text
+
+
+def to_hip(text: str, norm_entries: bool = False):
+    """-> (HIP source, report dict).  norm_entries: lowering option norm-entries (eligible applies also export their
+    monitored launch <fn>_<k>__geomN; the report names it as "norm_symbol")"""
     lib = _load()
+    text = with_options(text, norm_entries)
     src, rep, diag = C.c_void_p(), C.c_void_p(), C.c_void_p()
     if lib.neptune_lowering_to_hip(text.encode(), C.byref(src), C.byref(rep), C.byref(diag)) != 0:
         raise LoweringError(_take(lib, diag))
@@ -123,12 +136,14 @@ def module_hash(text: str) -> str:
 
 
 def compile_module(text: str, so_path: Optional[os.PathLike] = None, use_cache: bool = True,
-                   cache_directory: Optional[os.PathLike] = None, load: bool = True) -> Optional["LoweredModule"]:
+                   cache_directory: Optional[os.PathLike] = None, load: bool = True,
+                   norm_entries: bool = False) -> Optional["LoweredModule"]:
     """lower + hipcc (gfx950) + load.  Compiling needs no GPU; loading needs libneptune_hip.so.  Without an explicit
     so_path the object lives in `cache_directory` (default: cache_dir()) under its module_hash.  load=False only fills
     the cache (what the profiling scripts do before they start rocprofv3: hipcc is started with an environment scrubbed
     of LD_PRELOAD / ROCP* / HSA_TOOLS_*, csrc/lowering/capi.cpp, but a profiled run should be a pure cache hit)."""
     lib = _load()
+    text = with_options(text, norm_entries)   # lowering option norm-entries: see to_hip
     if so_path is None:
         directory = Path(cache_directory) if cache_directory else cache_dir()
         directory.mkdir(parents=True, exist_ok=True)
@@ -180,6 +195,14 @@ class GeomEntry:
             self.fn_leapfrog2.restype = C.c_int
             self.fn_leapfrog2.argtypes = [C.POINTER(_capi.ApplyGeom), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(_capi.LaunchCfg)]
+
+        # the monitored launch (lowering option norm-entries; neptune_hip_apply_norm_fn), or None
+        sym = info.get("norm_symbol") or ""
+        self.fn_norm = getattr(module.lib, sym) if sym else None
+        if self.fn_norm is not None:
+            self.fn_norm.restype = C.c_int
+            self.fn_norm.argtypes = [C.POINTER(_capi.ApplyGeom), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(_capi.LaunchCfg)]
 
     def __call__(self, geom, in_array, out_ptr, stream, cfg=None) -> int:
         return self.fn(C.byref(geom), in_array, out_ptr, stream, C.byref(cfg) if cfg is not None else None)
@@ -242,6 +265,14 @@ class LoweredModule:
         cands = [a for a in self.report["applies"] if a["function"] == function and a.get("geom_symbol")]
         if index >= len(cands):
             raise KeyError(f"@{function} has no apply #{index} with a geometry-level entry")
+        return GeomEntry(self, cands[index])
+
+    def norm_entry(self, function: str, index: int = 0) -> "GeomEntry":
+        """the `index`-th apply of @function that exports a monitored launch (module compiled with norm_entries=True): a
+        GeomEntry whose fn_norm is set -- what neptune_hip.apply.apply_norm launches and step_loop_until checks with"""
+        cands = [a for a in self.report["applies"] if a["function"] == function and a.get("norm_symbol")]
+        if index >= len(cands):
+            raise KeyError(f"@{function} has no apply #{index} with a monitored launch (compile with norm_entries=True)")
         return GeomEntry(self, cands[index])
 
     def group_entry(self, function: str, index: int = 0) -> "GroupEntry":
