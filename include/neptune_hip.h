@@ -433,6 +433,29 @@ int neptune_hip_store_box(int dtype, int rank, const void *src, const int64_t *s
 int neptune_hip_reduce_sum(int dtype, int rank, const void *src, const int64_t *src_lb,
                            const int64_t *src_ub, const int64_t *lb, const int64_t *ub,
                            double *result, void *stream);
+/* reduce {kind = "sum" | "max" | "min" | "l1" | "l2"}: the same domain rules, error codes, blocking behaviour and
+ * fixed tree as neptune_hip_reduce_sum, for every kind of the op (NeptuneIROps.td:266-288; the reference lowers only
+ * "sum", so the other four are defined here).  Result in the element type T, widened to double (NaN,
+ * +-inf and -0 survive the widening):
+ *   SUM  sum x              empty domain: +0     the bits of neptune_hip_reduce_sum
+ *   MAX  arith.maximumf     empty domain: -inf   NaN if any cell is NaN, -0 < +0; exact in any order
+ *   MIN  arith.minimumf     empty domain: +inf   likewise
+ *   L1   sum |x|            empty domain: +0     |x| exact, summed in T by the tree of SUM
+ *   L2   sqrt(sum x*x)      empty domain: +0     x*x one rounding (no FMA), summed in T by the tree of SUM, one sqrt in T
+ *                                                on the device, applied to the final sum
+ * kind | NEPTUNE_HIP_REDUCE_RAW leaves the finishing step out (L2 returns sum x*x; the other kinds have none), for a
+ * caller that combines the results of several boxes itself.  Any other kind: NEPTUNE_HIP_EINVAL, nothing launched. */
+enum {
+  NEPTUNE_HIP_REDUCE_SUM = 0,
+  NEPTUNE_HIP_REDUCE_MAX = 1,
+  NEPTUNE_HIP_REDUCE_MIN = 2,
+  NEPTUNE_HIP_REDUCE_L1 = 3,
+  NEPTUNE_HIP_REDUCE_L2 = 4,
+  NEPTUNE_HIP_REDUCE_RAW = 0x100
+};
+int neptune_hip_reduce(int kind, int dtype, int rank, const void *src, const int64_t *src_lb,
+                       const int64_t *src_ub, const int64_t *lb, const int64_t *ub,
+                       double *result, void *stream);
 /* device scratch of the reductions: (2048 + 1) elements of 8 bytes, owned by the library.  Used by the
  * fused apply+reduce kernels a lowered module carries (csrc/kernels/reduce_apply.hpp); calls that use it
  * are serialised by the stream they run on. */

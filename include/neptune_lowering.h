@@ -34,6 +34,13 @@ int neptune_lowering_verify(const char *mlir_text, char **diag_out);
  *                  the update norm sum (new - old)^2 from one launch (include/neptune_hip.h).  Without it
  *                  source and report are what they are without this feature.  neptune-opt: --norm-entries; Python:
  *                  compile_module(..., norm_entries=True).
+ *   reduce-kinds   neptune_ir.reduce kinds "max" | "min" | "l1" | "l2" verify and lower (semantics: DESIGN.md 3.3; any other
+ *                  kind: 'neptune_ir.reduce' op unsupported reduce kind "<k>"); every reduce then goes through the kind-taking
+ *                  runtime forms, and the report entry of an apply fused into a reduce carries "reduce_kind".  Without it a
+ *                  kind other than "sum" fails verification with the reference's diagnostic, and source and report are what
+ *                  they are without this feature.  neptune-opt: --reduce-kinds; Python: to_hip / verify /
+ *                  compile_module(..., reduce_kinds=True); modules built with neptune.reduce_max / _min / _l1 / _l2 carry
+ *                  the line themselves.
  * Set NEPTUNE_HIP_FULL_VARIANTS=1 in the environment of neptune_lowering_compile to build every march tile
  * into the module instead of the defaults (for NEPTUNE_HIP_TUNE=1). */
 int neptune_lowering_to_hip(const char *mlir_text, char **source_out, char **report_out, char **diag_out);

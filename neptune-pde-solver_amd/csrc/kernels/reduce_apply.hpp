@@ -1,5 +1,5 @@
-// reduce_apply.hpp -- `neptune_ir.reduce {kind = "sum"}` of a single-use `neptune_ir.apply` result in
-// ONE pass: the apply's value at every cell of the reduced box is computed in registers and summed,
+// reduce_apply.hpp -- `neptune_ir.reduce` of a single-use `neptune_ir.apply` result in
+// ONE pass: the apply's value at every cell of the reduced box is computed in registers and reduced,
 // the intermediate temp never exists in memory.  This is the shape of the dot products and norms a
 // Krylov iteration needs (reduce(apply(u*v)), reduce(apply(u*u))): the inputs are read once, nothing
 // is written -- 2 field passes for a dot product instead of the 4 of apply-then-reduce.
@@ -10,6 +10,8 @@
 // runs of 256-cell row chunks, lanes take consecutive cells (coalesced), per-lane serial sum, wave
 // shuffle tree, LDS, then neptune_reduce_final adds the per-workgroup partials in index order.  Reproducible
 // run to run; differs from the reference's serial sum by rounding within 2(n-1) eps sum|x_i|.
+// The kind is a reduction-op policy Op (util_kernels.hpp; the default is the sum): a counted cell contributes the term
+// of the value above, a lane or slot that does not count contributes the kind's identity, never 0 or a loaded value.
 #pragma once
 #include "apply_direct.hpp"
 #include "util_kernels.hpp"
@@ -22,22 +24,23 @@ constexpr int kReduceApplyIter = 8;  // row chunks per lane per trip, all their 
 // Workgroups own contiguous runs of row chunks; the (row, chunk) -> (i, j, k) bookkeeping is
 // workgroup-uniform, i.e. scalar work.  P.rlb / P.rub hold the REDUCED box in result-physical
 // coordinates; P.out is unused.
-template <class Body, class T, int RANK, int NIN>
+template <class Body, class T, int RANK, int NIN, class Op = RedSum<T>>
 __global__ __launch_bounds__(256) void neptune_reduce_apply(DirectParams<T, NIN> P, Body body, int64_t nchunk,
                                                              T* __restrict__ partials) {
-  __shared__ T lds[4];
+  typedef RedNode<Op, T> Node;
+  __shared__ Node lds[4];
   const int32_t eJ = (int32_t)(P.rub[1] - P.rlb[1]), eK = (int32_t)(P.rub[2] - P.rlb[2]);
   const int32_t r0 = (int32_t)P.rlb[0], r1 = (int32_t)P.rlb[1], r2 = (int32_t)P.rlb[2];
   const int64_t total = (P.rub[0] - P.rlb[0]) * eJ * nchunk;
   const int64_t per = (total + gridDim.x - 1) / gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * per;
   const int64_t hi = lo + per < total ? lo + per : total;
-  T acc = 0;
+  Node acc = Node::none();
   for (int64_t rc0 = lo; rc0 < hi; rc0 += kReduceApplyIter) {
     const int64_t row0 = rc0 / nchunk;
     const int32_t c0 = (int32_t)(rc0 - row0 * nchunk), i0 = (int32_t)(row0 / eJ), j0 = (int32_t)(row0 - (int64_t)i0 * eJ);
     int32_t i = i0, j = j0, c = c0;
-    T v[kReduceApplyIter];
+    Node v[kReduceApplyIter];
 #pragma unroll
     for (int it = 0; it < kReduceApplyIter; ++it) {
       const bool live = rc0 + it < hi;  // uniform; a dead slot re-reads the first chunk and is discarded
@@ -49,7 +52,7 @@ __global__ __launch_bounds__(256) void neptune_reduce_apply(DirectParams<T, NIN>
       const bool inside = pi >= P.lb[0] && pi < P.ub[0] && pj >= P.lb[1] && pj < P.ub[1] && pk >= P.lb[2] && pk < P.ub[2];
       const T through = RowAcc<T, RANK, NIN>::row_ptr(P.in[0], a.qi, a.qj, P.n)[(uint32_t)a.qk];
       const T val = body(a);
-      v[it] = valid ? (inside ? val : OutsideOf<Body, T>::apply(body, through)) : (T)0;
+      v[it] = valid ? Node::term(inside ? val : OutsideOf<Body, T>::apply(body, through)) : Node::none();
       if (++c == (int32_t)nchunk) {
         c = 0;
         if (++j == eJ) { j = 0; ++i; }
@@ -90,21 +93,22 @@ struct PointVecAcc {
   }
 };
 
-template <class Body, class T, int RANK, int NIN>
+template <class Body, class T, int RANK, int NIN, class Op = RedSum<T>>
 __global__ __launch_bounds__(256) void neptune_reduce_apply_vec(DirectParams<T, NIN> P, Body body, int64_t nchunk,
                                                                  T* __restrict__ partials) {
   constexpr int VK = 16 / sizeof(T);
   constexpr int ITER = kReduceApplyIter / 2;
   static_assert(ITER == 4, "the accessor array below is spelled out for 4 slots");
   typedef typename PointVecAcc<T, RANK, NIN>::vec vec;
-  __shared__ T lds[4];
+  typedef RedNode<Op, T> Node;
+  __shared__ Node lds[4];
   const int32_t eJ = (int32_t)(P.rub[1] - P.rlb[1]), eK = (int32_t)(P.rub[2] - P.rlb[2]);
   const int32_t r0 = (int32_t)P.rlb[0], r1 = (int32_t)P.rlb[1], r2 = (int32_t)P.rlb[2];
   const int64_t total = (P.rub[0] - P.rlb[0]) * eJ * nchunk;
   const int64_t per = (total + gridDim.x - 1) / gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * per;
   const int64_t hi = lo + per < total ? lo + per : total;
-  T acc = 0;
+  Node acc = Node::none();
   for (int64_t rc0 = lo; rc0 < hi; rc0 += ITER) {
     const int64_t row0 = rc0 / nchunk;
     const int32_t c0 = (int32_t)(rc0 - row0 * nchunk), i0 = (int32_t)(row0 / eJ), j0 = (int32_t)(row0 - (int64_t)i0 * eJ);
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(256) void neptune_reduce_apply_vec(DirectParams<T, 
         const int64_t pk = (int64_t)a[it].qk + e + P.olb[2];
         const bool inside = inside_ij[it] && pk >= P.lb[2] && pk < P.ub[2];
         const T val = body(a[it]);
-        const T v = valid[it] ? (inside ? val : OutsideOf<Body, T>::apply(body, a[it].x[0][e])) : (T)0;
+        const Node v = valid[it] ? Node::term(inside ? val : OutsideOf<Body, T>::apply(body, a[it].x[0][e])) : Node::none();
         acc += v;
       }
     }

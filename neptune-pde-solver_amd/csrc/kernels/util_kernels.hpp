@@ -2,6 +2,7 @@
 // compare kernels around the apply kernels.
 #pragma once
 #include "apply_common.hpp"
+#include "body_ops.hpp"
 
 namespace neptune_hip {
 
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(256) void neptune_count_mismatch(const U* __restric
   if ((threadIdx.x & (kWave - 1)) == 0 && local) atomicAdd(out, local);
 }
 
-// ---- neptune_ir.reduce {kind = "sum"} (lib/Passes/DataflowLowering.cpp:589-698) ------------------
+// ---- neptune_ir.reduce (lib/Passes/DataflowLowering.cpp:589-698) ------------------
 // The reference sums serially in row-major order.  A GPU cannot keep that order; this reduction
 // uses a FIXED tree instead (lane-strided partial sums -> wave shuffle tree -> LDS -> one partial
 // per workgroup -> second kernel adds the partials in index order), so the result is bit-for-bit
@@ -145,50 +146,100 @@ __global__ __launch_bounds__(256) void neptune_count_mismatch(const U* __restric
 // (tests/test_reduce_exact_gpu.py::test_rank4_bounded_f32_reduce_adds_slab_sums_in_double).
 constexpr int kReduceBlocks = 2048;  // partials of the first pass; the workspace holds kReduceBlocks + 1 elements
 
+// ---- reduce kinds ----
+// kind = "max" | "min" | "l1" | "l2" run on the kernels and the fixed tree of "sum".  A kernel is instantiated on a
+// reduction-op policy that names the four places a kind differs in:
+//   identity()    what anything that does not count contributes -- a dead unroll slot, a lane past the row's end, a workgroup
+//                 whose run is empty, the start of every accumulator: never a loaded value, and 0 only where 0 is it
+//   map(x)        a counted cell's term:   sum x | max x | min x | l1 |x| (exact) | l2 x*x (one rounding: -ffp-contract=off)
+//   combine(a,b)  one node of the tree:    a + b | ops::maximumf | ops::minimumf (NaN if either is NaN, -0 < +0)
+//   finish(x)     applied once to the root of the tree, by thread 0 of neptune_reduce_final: l2 takes its sqrt there
+// The first-pass kernels run on the kind's op; neptune_reduce_final combines PARTIALS, so it runs on an op whose map is
+// the identity function: RedSum for l1 and for l2 without its finish, RedSqrtSum for l2.
+template <class T> struct RedSum {
+  static __device__ __forceinline__ T identity() { return (T)0; }
+  static __device__ __forceinline__ T map(T x) { return x; }
+  static __device__ __forceinline__ T combine(T a, T b) { return a + b; }
+  static __device__ __forceinline__ T finish(T x) { return x; }
+};
+template <class T> struct RedMax : RedSum<T> {
+  static __device__ __forceinline__ T identity() { return (T)-__builtin_huge_val(); }
+  static __device__ __forceinline__ T combine(T a, T b) { return ops::maximumf(a, b); }
+};
+template <class T> struct RedMin : RedSum<T> {
+  static __device__ __forceinline__ T identity() { return (T)__builtin_huge_val(); }
+  static __device__ __forceinline__ T combine(T a, T b) { return ops::minimumf(a, b); }
+};
+template <class T> struct RedL1 : RedSum<T> {
+  static __device__ __forceinline__ T map(T x) { return ops::absf(x); }
+};
+template <class T> struct RedSumSq : RedSum<T> {
+  static __device__ __forceinline__ T map(T x) { return x * x; }
+};
+template <class T> struct RedSqrtSum : RedSum<T> {
+  static __device__ __forceinline__ T finish(T x) { return ops::sqrt(x); }
+};
+
+// A value of the tree.  The kernels below are written as the sum they were before the kinds existed -- `acc += x` -- and
+// the types say what `+=` is: node += node is one combine; node += cell (a T: a loaded or computed value that counts) is the
+// combine with the cell's term map(cell).  For RedSum both are the plain addition, op for op.
+template <class Op, class T>
+struct RedNode {
+  T v;
+  static __device__ __forceinline__ RedNode none() { return {Op::identity()}; }     // what does not count
+  static __device__ __forceinline__ RedNode term(T cell) { return {Op::map(cell)}; }
+  __device__ __forceinline__ RedNode& operator+=(RedNode o) { v = Op::combine(v, o.v); return *this; }
+  __device__ __forceinline__ RedNode& operator+=(T cell) { v = Op::combine(v, Op::map(cell)); return *this; }
+};
+using ::__shfl_down;   // the overload below must not hide the builtin-typed ones from the rest of this namespace
+template <class Op, class T>
+__device__ __forceinline__ RedNode<Op, T> __shfl_down(RedNode<Op, T> n, int delta) { return {::__shfl_down(n.v, delta)}; }
+
 struct ReduceBoxParams {
   int64_t ext[3];     // reduced box extents (I,J,K order, absent axes 1)
   int64_t off[3];     // box origin - buffer origin
   int64_t shape[3];   // buffer extents
 };
 
-template <class T>
-__device__ __forceinline__ T block_sum(T v, T* lds /* >= blockDim.x / 64 entries */) {
+template <class Op, class T>
+__device__ __forceinline__ T block_sum(RedNode<Op, T> v, RedNode<Op, T>* lds /* >= blockDim.x / 64 entries */) {
   for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o);
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
   if (lane == 0) lds[w] = v;
   __syncthreads();
-  T r = 0;
+  RedNode<Op, T> r = RedNode<Op, T>::none();
   if (threadIdx.x == 0) {
     const int nw = blockDim.x / kWave;
     for (int i = 0; i < nw; ++i) r += lds[i];  // fixed order
   }
-  return r;  // valid in thread 0
+  return r.v;  // valid in thread 0
 }
 
 // contiguous buffer: every workgroup owns one contiguous slice, lanes stride through it with
 // 16-byte loads (VK cells per lane per load, VK independent partial sums per lane)
-template <class T>
+template <class T, class Op = RedSum<T>>
 __global__ __launch_bounds__(256) void neptune_reduce_partial_flat(const T* __restrict__ src, int64_t count,
                                                                     T* __restrict__ partials) {
   constexpr int VK = 16 / sizeof(T);
   typedef T vec __attribute__((ext_vector_type(VK)));
-  __shared__ T lds[4];
+  typedef RedNode<Op, T> Node;
+  __shared__ Node lds[4];
   // slices are whole numbers of 16-byte words; the last workgroup also takes the scalar tail
   const int64_t nvec = count / VK;
   const int64_t per = (nvec + gridDim.x - 1) / gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * per;
   const int64_t hi = lo + per < nvec ? lo + per : nvec;
   const vec* __restrict__ sv = reinterpret_cast<const vec*>(src);
-  T part[VK];
+  Node part[VK];
 #pragma unroll
-  for (int e = 0; e < VK; ++e) part[e] = 0;
+  for (int e = 0; e < VK; ++e) part[e] = Node::none();
 #pragma unroll 4
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     const vec x = sv[i];
 #pragma unroll
     for (int e = 0; e < VK; ++e) part[e] += x[e];
   }
-  T acc = 0;
+  Node acc = Node::none();
 #pragma unroll
   for (int e = 0; e < VK; ++e) acc += part[e];
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
@@ -201,25 +252,26 @@ __global__ __launch_bounds__(256) void neptune_reduce_partial_flat(const T* __re
 // 256*VK consecutive cells of one row of the box, VK adjacent cells per lane in one 16-byte load (rows of a sub-box
 // start anywhere: unaligned loads) -- so the (row, chunk) -> (i, j, k) bookkeeping is workgroup-uniform scalar work
 // instead of a 64-bit division per cell.  Four chunks per trip keep their loads in flight together.
-template <class T>
+template <class T, class Op = RedSum<T>>
 __global__ __launch_bounds__(256) void neptune_reduce_partial_box(const T* __restrict__ src, ReduceBoxParams P,
                                                                    T* __restrict__ partials) {
   constexpr int VK = 16 / sizeof(T), ITER = 4;
   typedef T uvec __attribute__((ext_vector_type(VK), aligned(sizeof(T))));
-  __shared__ T lds[4];
+  typedef RedNode<Op, T> Node;
+  __shared__ Node lds[4];
   const int64_t cells_per_chunk = 256 * VK;
   const int64_t nchunk = (P.ext[2] + cells_per_chunk - 1) / cells_per_chunk;
   const int64_t total = P.ext[0] * P.ext[1] * nchunk;
   const int64_t per = (total + gridDim.x - 1) / gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * per;
   const int64_t hi = lo + per < total ? lo + per : total;
-  T part[VK];
+  Node part[VK];
 #pragma unroll
-  for (int e = 0; e < VK; ++e) part[e] = 0;
+  for (int e = 0; e < VK; ++e) part[e] = Node::none();
   for (int64_t rc0 = lo; rc0 < hi; rc0 += ITER) {
     const int64_t row0 = rc0 / nchunk;
     int64_t c = rc0 - row0 * nchunk, i = row0 / P.ext[1], j = row0 - i * P.ext[1];
-    T v[ITER][VK];
+    Node v[ITER][VK];
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
       const bool live = rc0 + it < hi;  // uniform
@@ -228,10 +280,10 @@ __global__ __launch_bounds__(256) void neptune_reduce_partial_box(const T* __res
       if (live && k0 + VK <= P.ext[2]) {
         const uvec x = *reinterpret_cast<const uvec*>(p);
 #pragma unroll
-        for (int e = 0; e < VK; ++e) v[it][e] = x[e];
+        for (int e = 0; e < VK; ++e) v[it][e] = Node::term(x[e]);
       } else {
 #pragma unroll
-        for (int e = 0; e < VK; ++e) v[it][e] = (live && k0 + e < P.ext[2]) ? p[e] : (T)0;  // the row's last, partial vector
+        for (int e = 0; e < VK; ++e) v[it][e] = (live && k0 + e < P.ext[2]) ? Node::term(p[e]) : Node::none();  // the row's last, partial vector
       }
       if (live && ++c == nchunk) {
         c = 0;
@@ -243,20 +295,23 @@ __global__ __launch_bounds__(256) void neptune_reduce_partial_box(const T* __res
 #pragma unroll
       for (int e = 0; e < VK; ++e) part[e] += v[it][e];
   }
-  T acc = 0;
+  Node acc = Node::none();
 #pragma unroll
   for (int e = 0; e < VK; ++e) acc += part[e];
   const T r = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-template <class T>
+// the root of the tree: the partials of the first pass combined in index order, then the kind's finish.  Op: one whose
+// map is the identity function (see above)
+template <class T, class Op = RedSum<T>>
 __global__ __launch_bounds__(256) void neptune_reduce_final(const T* __restrict__ partials, int n, T* __restrict__ out) {
-  __shared__ T lds[4];
-  T acc = 0;
+  typedef RedNode<Op, T> Node;
+  __shared__ Node lds[4];
+  Node acc = Node::none();
   for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];
   const T r = block_sum(acc, lds);
-  if (threadIdx.x == 0) *out = r;
+  if (threadIdx.x == 0) *out = Op::finish(r);
 }
 
 }  // namespace neptune_hip

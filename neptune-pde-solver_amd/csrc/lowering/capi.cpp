@@ -73,6 +73,7 @@ std::string report_json(const LowerInfo& info) {
       << ", \"geom_symbol\": \"" << a.geom_symbol << "\", \"exact\": " << (a.exact ? "true" : "false")
       << ", \"leapfrog_symbol\": \"" << a.leapfrog_symbol << "\"";
     if (!a.norm_symbol.empty()) o << ", \"norm_symbol\": \"" << a.norm_symbol << "\"";
+    if (!a.reduce_kind.empty()) o << ", \"reduce_kind\": \"" << a.reduce_kind << "\"";
     if (a.group >= 0) o << ", \"group\": " << a.group;
     o << "}";
   }
@@ -152,7 +153,7 @@ std::string kernel_build_id(const std::string& root) {
 }
 bool front(const char* text, Module& m, Diag& d) {
   if (!text) { d.fail(0, "null module text"); return false; }
-  return parse_module(text, m, d) && verify_module(m, d);
+  return parse_module(text, m, d) && verify_module(m, d, options_in_text(text).reduce_kinds);
 }
 // Nothing may leave the C ABI as a C++ exception: malformed text that slips past a structural check (an op with
 // fewer types or operands than its kind implies) surfaces as std::out_of_range from a checked access -- report
@@ -188,6 +189,7 @@ LowerOptions options_in_text(const char* mlir_text) {
       const size_t f = name.find_first_not_of(" \t"), l = name.find_last_not_of(" \t\r");
       name = f == std::string::npos ? "" : name.substr(f, l - f + 1);
       if (name == "norm-entries") opt.norm_entries = true;
+      if (name == "reduce-kinds") opt.reduce_kinds = true;
     }
     pos = eol + 1;
   }

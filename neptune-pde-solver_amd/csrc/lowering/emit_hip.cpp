@@ -687,6 +687,7 @@ struct Emitter {
   // Lowering option norm-entries: an apply whose input 0 has the result's element type and a box equal to the result's --
   // the old state of an iteration u <- A(u) -- also exports its monitored launch <geom_symbol>N
   bool norm_entries = false;
+  bool reduce_kinds = false;   // lowering option reduce-kinds: reduces go through the kind-taking runtime forms
   bool wants_norm_entry(const Op& op) const {
     const int nin = (int)op.operands.size();
     const Type& res = op.types[nin];
@@ -737,17 +738,18 @@ struct Emitter {
 
   // single-use result consumed by a reduce a few scalar/alias ops later: the apply is evaluated
   // inside the reduction kernel (run_apply_reduce_sum), the temp never exists
-  static bool feeds_fused_reduce(FnState& s, const Op& op, int oi) {
+  static const Op* fused_reduce_consumer(FnState& s, const Op& op, int oi) {
     const auto& ops = s.f.body.ops;
-    if (s.vals[op.results[0]].uses != 1) return false;
+    if (s.vals[op.results[0]].uses != 1) return nullptr;
     for (size_t j = oi + 1; j < ops.size(); ++j) {
       const Op& c = *ops[j];
-      if (c.name == "neptune_ir.reduce" && c.operands.at(0) == op.results[0]) return true;
+      if (c.name == "neptune_ir.reduce" && c.operands.at(0) == op.results[0]) return &c;
       const std::string& nm = c.name;
       if (!(nm == "neptune_ir.wrap" || nm == "neptune_ir.unwrap" || nm == "neptune_ir.load" || is_scalar_op(c))) break;
     }
-    return false;
+    return nullptr;
   }
+  static bool feeds_fused_reduce(FnState& s, const Op& op, int oi) { return fused_reduce_consumer(s, op, oi) != nullptr; }
 
   // group >= 0: the apply is a member of that group -- its body functor, geometry-level entries and report entry are
   // what they are for an apply on its own; the launch itself is emitted by emit_group
@@ -786,6 +788,7 @@ struct Emitter {
       ApplyInfo ai = apply_info(s, tag, fp, fp.rank, "", 0);
       ai.march = false;
       ai.fused_reduce = true;
+      if (reduce_kinds) ai.reduce_kind = fused_reduce_consumer(s, op, oi)->attrs.at("kind").s;
       info.applies.push_back(ai);
       return true;
     }
@@ -1120,6 +1123,7 @@ struct Emitter {
   }
 
   void emit_reduce(FnState& s, const Op& op) {
+    if (reduce_kinds) return emit_reduce_kind(s, op);
     s.scalar_kind[op.results[0]] = 1;   // under a slab view: this rank's partial sum
     const std::string bx = op.attrs.count("bounds") ? "&" + new_box(op.attrs.at("bounds").bounds) : "nullptr";
     auto fit = s.fused_reduce.find(op.operands[0]);
@@ -1135,6 +1139,32 @@ struct Emitter {
     const std::string& elem = op.types[0].elem;
     s.o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"sum\"}   (fixed-tree device sum, blocking)\n";
     s.o << "  const " << ctype(elem) << " " << cname(op.results[0]) << " = (" << ctype(elem) << ")nl::run_reduce_sum(sc, "
+        << cname(op.operands[0]) << ", " << bx << ", " << dtype_macro(elem) << ");\n";
+  }
+
+  // lowering option reduce-kinds: every kind, "sum" included, through the kind-taking runtime forms (lowered_runtime.hpp
+  // run_reduce / run_apply_reduce)
+  void emit_reduce_kind(FnState& s, const Op& op) {
+    const std::string& kind = op.attrs.at("kind").s;
+    static const char* const macros[] = {"NEPTUNE_HIP_REDUCE_SUM", "NEPTUNE_HIP_REDUCE_MAX", "NEPTUNE_HIP_REDUCE_MIN", "NEPTUNE_HIP_REDUCE_L1",
+                                         "NEPTUNE_HIP_REDUCE_L2"};
+    const std::string macro = macros[reduce_kind_id(kind)];
+    // under a slab view a sum is this rank's partial sum; the ranks' values of any other kind do not add up (they refuse to run)
+    s.scalar_kind[op.results[0]] = kind == "sum" ? 1 : 2;
+    const std::string bx = op.attrs.count("bounds") ? "&" + new_box(op.attrs.at("bounds").bounds) : "nullptr";
+    auto fit = s.fused_reduce.find(op.operands[0]);
+    if (fit != s.fused_reduce.end()) {
+      const FusedReduce& fr = fit->second;
+      s.o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"" << kind << "\"}   (apply + fixed-tree device reduction in one kernel, blocking)\n";
+      s.o << "  const " << fr.elem << " " << cname(op.results[0]) << " = (" << fr.elem << ")nl::run_apply_reduce<" << macro << ", Body_" << fr.tag
+          << ", " << fr.elem << ", " << fr.rank << ", " << fr.nin << ", FP_" << fr.tag << ">(sc, Body_" << fr.tag << "{}, "
+          << fr.result_box << ", " << fr.bounds_box << ", in_" << fr.tag << ", kTopRadius_" << fr.tag << ", " << fr.halo0 << ", "
+          << bx << ");\n";
+      return;
+    }
+    const std::string& elem = op.types[0].elem;
+    s.o << "  // neptune_ir.reduce " << op.operands[0] << " {kind = \"" << kind << "\"}   (fixed-tree device reduction, blocking)\n";
+    s.o << "  const " << ctype(elem) << " " << cname(op.results[0]) << " = (" << ctype(elem) << ")nl::run_reduce(sc, " << macro << ", "
         << cname(op.operands[0]) << ", " << bx << ", " << dtype_macro(elem) << ");\n";
   }
 
@@ -1422,6 +1452,7 @@ struct Emitter {
 bool lower_to_hip(const Module& m, std::string& out_source, LowerInfo& info, Diag& diag, const LowerOptions& options) {
   Emitter e(m, diag, info);
   e.norm_entries = options.norm_entries;
+  e.reduce_kinds = options.reduce_kinds;
   return e.run(out_source) && diag.ok;
 }
 

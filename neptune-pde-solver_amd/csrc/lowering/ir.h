@@ -129,6 +129,9 @@ bool parse_module(const std::string& text, Module& out, Diag& diag);
 // verify.cpp: the checks of ApplyOp::verify (lib/Dialect/NeptuneIR/NeptuneIRVerifier.cpp:141-171),
 // checkApplyLike (lib/Passes/VerifyAndAnnotate.cpp:87-214) and the linear_opdef body whitelist
 // (NeptuneIRVerifier.cpp:34-118), with the reference's diagnostics.
-bool verify_module(const Module& m, Diag& diag);
+// reduce_kinds: the lowering option of that name (lowering.h) -- neptune_ir.reduce kinds max | min | l1 | l2 verify
+bool verify_module(const Module& m, Diag& diag, bool reduce_kinds = false);
+// the NEPTUNE_HIP_REDUCE_* value (include/neptune_hip.h) of a reduce kind: sum 0, max 1, min 2, l1 3, l2 4; -1: none of them
+int reduce_kind_id(const std::string& kind);
 
 }  // namespace neptune_lowering

@@ -24,6 +24,7 @@ bool is_intlike(const Type& t) { return t.is_scalar() && (t.elem == "index" || t
 struct Verifier {
   const Module& m;
   Diag& diag;
+  bool reduce_kinds = false;   // lowering option reduce-kinds
   Verifier(const Module& mm, Diag& d) : m(mm), diag(d) {}
 
   bool lookup(const Scope& sc, const Op& op, const std::string& v, Type& out) {
@@ -345,8 +346,14 @@ struct Verifier {
         if (!lookup(sc, op, op.operands[0], in)) return false;
         if (in.kind != TypeKind::Temp || in != op.types.at(0)) { diag.fail(op.line, "'neptune_ir.reduce' op reduce input must be TempType"); return false; }
         auto kit = op.attrs.find("kind");
-        if (kit == op.attrs.end() || kit->second.kind != AttrValue::String || kit->second.s != "sum") {
-          diag.fail(op.line, "'neptune_ir.reduce' op MVP reduce only supports kind=\"sum\"");
+        const bool has_kind = kit != op.attrs.end() && kit->second.kind == AttrValue::String;
+        if (!reduce_kinds || !has_kind) {
+          if (!has_kind || kit->second.s != "sum") {
+            diag.fail(op.line, "'neptune_ir.reduce' op MVP reduce only supports kind=\"sum\"");
+            return false;
+          }
+        } else if (reduce_kind_id(kit->second.s) < 0) {   // the kinds of NeptuneIROps.td:266-288
+          diag.fail(op.line, "'neptune_ir.reduce' op unsupported reduce kind \"" + kit->second.s + "\"");
           return false;
         }
         auto bit = op.attrs.find("bounds");
@@ -380,8 +387,16 @@ struct Verifier {
 
 }  // namespace
 
-bool verify_module(const Module& m, Diag& diag) {
+int reduce_kind_id(const std::string& kind) {
+  static const char* const names[] = {"sum", "max", "min", "l1", "l2"};
+  for (int i = 0; i < 5; ++i)
+    if (kind == names[i]) return i;
+  return -1;
+}
+
+bool verify_module(const Module& m, Diag& diag, bool reduce_kinds) {
   Verifier v(m, diag);
+  v.reduce_kinds = reduce_kinds;
   for (auto& f : m.funcs)
     if (!v.check_function(*f)) return false;
   return diag.ok;

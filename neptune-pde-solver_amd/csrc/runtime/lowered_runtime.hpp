@@ -763,9 +763,30 @@ inline Val run_euler_axpy_flat(Scope& sc, T dt, const Val& state, const Val& k, 
   return out;
 }
 
-// neptune_ir.reduce {kind = "sum"} (DataflowLowering.cpp:589-698): blocking, result on the host
-// slab mode: this rank's partial sum over its owned planes (the caller adds the ranks' results)
-inline double run_reduce_sum(Scope& sc, const Val& src, const Box* bounds_decl, int dtype) {
+// ---- neptune_ir.reduce (DataflowLowering.cpp:589-698): blocking, result on the host ----
+// kind: NEPTUNE_HIP_REDUCE_* (neptune_hip.h; the reference lowers "sum" only, the others are DESIGN 3.3)
+inline const char* reduce_kind_name(int kind) {
+  static const char* const names[] = {"sum", "max", "min", "l1", "l2"};
+  return kind >= 0 && kind < 5 ? names[kind] : "?";
+}
+// what a reduce over no cells returns: the kind's identity
+inline double reduce_identity(int kind) {
+  return kind == NEPTUNE_HIP_REDUCE_MAX ? -__builtin_huge_val() : (kind == NEPTUNE_HIP_REDUCE_MIN ? __builtin_huge_val() : 0.0);
+}
+// Slab mode combines the ranks' results by adding them (neptune_hip.slab): right for "sum" alone -- max and min need
+// another combine and l2 is not additive at all -- so every other kind refuses to run on a slab.
+inline void refuse_slab_reduce(Scope& sc, int kind) {
+  if (kind != NEPTUNE_HIP_REDUCE_SUM && sc.slab()) {
+    char msg[192];
+    snprintf(msg, sizeof msg, "slab mode: neptune_ir.reduce {kind = \"%s\"} is not supported (the ranks' results are combined by "
+                              "adding them, which is only right for kind = \"sum\")", reduce_kind_name(kind));
+    die(sc.name(), msg);
+  }
+}
+
+// slab mode (kind sum only): this rank's partial sum over its owned planes (the caller adds the ranks' results)
+inline double run_reduce(Scope& sc, int kind, const Val& src, const Box* bounds_decl, int dtype) {
+  refuse_slab_reduce(sc, kind);
   sc.wait_pending();
   double r = 0.0;
   Box clipped;
@@ -773,44 +794,57 @@ inline double run_reduce_sum(Scope& sc, const Val& src, const Box* bounds_decl, 
   if (sc.slab() || bounds_decl) {
     clipped = sc.owned_bounds(bounds_decl ? *bounds_decl : src.box);
     bounds = &clipped;
-    if (clipped.count() == 0) return 0.0;
+    if (clipped.count() == 0) return reduce_identity(kind);
   }
   if (src.box.rank > NEPTUNE_HIP_MAX_RANK) {
-    // a whole-buffer sum of a field with leading batch dimensions: the same fixed tree over the flat buffer
+    // a whole-buffer reduce of a field with leading batch dimensions: the same fixed tree over the flat buffer
     if (bounds) {
-      // one rank-3 box sum per leading index of the reduced box, added up in index order
+      // one rank-3 box reduce per leading index of the reduced box, combined in index order: sums (sum, l1, and l2's
+      // sums of squares, which take their one sqrt at the end) are added in double and rounded to the element type
+      // once; max and min fold with their own combine
       const Box s3 = last3(src.box), b3 = last3(*bounds);
+      const bool additive = kind != NEPTUNE_HIP_REDUCE_MAX && kind != NEPTUNE_HIP_REDUCE_MIN;
+      r = reduce_identity(kind);
       for_each_lead(*bounds, [&](const int64_t* idx) {
         const int64_t so = lead_offset_cells(src.box, idx);
         if (so < 0) die(sc.name(), "neptune_ir.reduce bounds leave the input buffer");
         double part = 0.0;
-        const int r1 = neptune_hip_reduce_sum(dtype, 3, static_cast<char*>(src.dev) + so * src.esize, s3.lb, s3.ub, b3.lb, b3.ub, &part,
-                                              sc.stream());
+        const int r1 = neptune_hip_reduce(kind | NEPTUNE_HIP_REDUCE_RAW, dtype, 3, static_cast<char*>(src.dev) + so * src.esize, s3.lb,
+                                          s3.ub, b3.lb, b3.ub, &part, sc.stream());
         if (r1 == NEPTUNE_HIP_EOOB) die(sc.name(), "neptune_ir.reduce bounds leave the input buffer");
         if (r1 != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.reduce rejected");
-        r += part;
+        if (additive) r += part;
+        else if (kind == NEPTUNE_HIP_REDUCE_MAX) r = neptune_hip::ops::maximumf(r, part);
+        else r = neptune_hip::ops::minimumf(r, part);
       });
+      if (kind == NEPTUNE_HIP_REDUCE_L2)   // one sqrt, in the element type, of the sum rounded to it
+        r = dtype == NEPTUNE_HIP_F32 ? (double)neptune_hip::ops::sqrt((float)r) : neptune_hip::ops::sqrt(r);
       return r;
     }
     const int64_t flat_lb[1] = {0}, flat_ub[1] = {src.count};
-    const int rc1 = neptune_hip_reduce_sum(dtype, 1, src.dev, flat_lb, flat_ub, nullptr, nullptr, &r, sc.stream());
+    const int rc1 = neptune_hip_reduce(kind, dtype, 1, src.dev, flat_lb, flat_ub, nullptr, nullptr, &r, sc.stream());
     if (rc1 != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.reduce rejected");
     return r;
   }
-  const int rc = neptune_hip_reduce_sum(dtype, src.box.rank, src.dev, src.box.lb, src.box.ub, bounds ? bounds->lb : nullptr,
-                                        bounds ? bounds->ub : nullptr, &r, sc.stream());
+  const int rc = neptune_hip_reduce(kind, dtype, src.box.rank, src.dev, src.box.lb, src.box.ub, bounds ? bounds->lb : nullptr,
+                                    bounds ? bounds->ub : nullptr, &r, sc.stream());
   if (rc == NEPTUNE_HIP_EOOB) die(sc.name(), "neptune_ir.reduce bounds leave the input buffer");
   if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.reduce rejected");
   return r;
 }
+inline double run_reduce_sum(Scope& sc, const Val& src, const Box* bounds_decl, int dtype) {
+  return run_reduce(sc, NEPTUNE_HIP_REDUCE_SUM, src, bounds_decl, dtype);
+}
 
-// neptune_ir.reduce {kind = "sum"} of a single-use neptune_ir.apply result, fused: the apply's values are
-// summed as they are computed (csrc/kernels/reduce_apply.hpp); no intermediate temp, nothing written.
-template <class Body, class T, int RANK, int NIN, class FP>
-inline double run_apply_reduce_sum(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl,
-                                   const Val* const* in,
-                                   const neptune_hip::Reach& top_radius, int halo0,
-                                   const Box* reduce_decl) {
+// neptune_ir.reduce of a single-use neptune_ir.apply result, fused: the apply's values are reduced as they are
+// computed (csrc/kernels/reduce_apply.hpp); no intermediate temp, nothing written.  POp: the reduction-op policy of the
+// first pass (util_kernels.hpp), FOp: that of the root -- POp's combine, the identity map, the kind's finish.
+template <class POp, class FOp, class Body, class T, int RANK, int NIN, class FP>
+inline double run_apply_reduce_op(Scope& sc, int kind, const Body& body, const Box& result_decl, const Box& bounds_decl,
+                                  const Val* const* in,
+                                  const neptune_hip::Reach& top_radius, int halo0,
+                                  const Box* reduce_decl) {
+  refuse_slab_reduce(sc, kind);
   sc.wait_pending();
   for (int k = 0; k < NIN; ++k)
     if (sc.has_ghosts() && halo0 > 0 && in[k]->stale_ghosts)
@@ -835,7 +869,7 @@ inline double run_apply_reduce_sum(Scope& sc, const Body& body, const Box& resul
     g.region_ub[d] = red.ub[d] - result_box.lb[d];
     cells *= e;
   }
-  if (cells == 0) return 0.0;  // the reference's loop never runs, the accumulator stays 0
+  if (cells == 0) return reduce_identity(kind);  // the reference's loop never runs, the accumulator stays at the identity (sum: 0)
   const void* ptrs[NIN];
   for (int k = 0; k < NIN; ++k) ptrs[k] = in[k]->dev;
   DirectParams<T, NIN> P{};
@@ -863,18 +897,47 @@ inline double run_apply_reduce_sum(Scope& sc, const Body& body, const Box& resul
   const int blocks = (int)(trips < kReduceBlocks ? trips : kReduceBlocks);
   if constexpr (FP::MARCH_OK && FP::HALO_MASK == 0u) {
     if (vec)
-      hipLaunchKernelGGL((neptune_reduce_apply_vec<Body, T, RANK, NIN>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
+      hipLaunchKernelGGL((neptune_reduce_apply_vec<Body, T, RANK, NIN, POp>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
   } else {
     vec = false;
   }
-  if (!vec)
-    hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
-  hipLaunchKernelGGL(neptune_reduce_final<T>, dim3(1), dim3(256), 0, sc.stream(), part, blocks, part + kReduceBlocks);
+  // the sum is the kernels' default op: its launch keeps the spelling tests/reduce_cases.py mirrors (MIRRORED), which is
+  // the same specialisation as <..., RedSum<T>>
+  if constexpr (std::is_same<POp, neptune_hip::RedSum<T>>::value) {
+    if (!vec)
+      hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
+  } else {
+    if (!vec)
+      hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN, POp>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
+  }
+  hipLaunchKernelGGL((neptune_reduce_final<T, FOp>), dim3(1), dim3(256), 0, sc.stream(), part, blocks, part + kReduceBlocks);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   T h = 0;
   NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, part + kReduceBlocks, sizeof(T), hipMemcpyDeviceToHost, sc.stream()));
   NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream()));
   return (double)h;
+}
+template <class Body, class T, int RANK, int NIN, class FP>
+inline double run_apply_reduce_sum(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl,
+                                   const Val* const* in,
+                                   const neptune_hip::Reach& top_radius, int halo0,
+                                   const Box* reduce_decl) {
+  return run_apply_reduce_op<neptune_hip::RedSum<T>, neptune_hip::RedSum<T>, Body, T, RANK, NIN, FP>(
+      sc, NEPTUNE_HIP_REDUCE_SUM, body, result_decl, bounds_decl, in, top_radius, halo0, reduce_decl);
+}
+// the kind-taking form: KIND is a NEPTUNE_HIP_REDUCE_* constant (the kernel is instantiated per kind)
+template <int KIND, class Body, class T, int RANK, int NIN, class FP>
+inline double run_apply_reduce(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
+                               const neptune_hip::Reach& top_radius, int halo0, const Box* reduce_decl) {
+  static_assert(KIND >= NEPTUNE_HIP_REDUCE_SUM && KIND <= NEPTUNE_HIP_REDUCE_L2, "unknown reduce kind");
+  using POp = std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_MAX, RedMax<T>,
+              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_MIN, RedMin<T>,
+              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L1, RedL1<T>,
+              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L2, RedSumSq<T>, RedSum<T>>>>>;
+  using FOp = std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L2, RedSqrtSum<T>,
+              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L1, RedSum<T>, POp>>;
+  return run_apply_reduce_op<POp, FOp, Body, T, RANK, NIN, FP>(sc, KIND, body, result_decl, bounds_decl, in, top_radius, halo0,
+                                                                reduce_decl);
 }
 
 template <int RANK> struct MemRefOf;

@@ -8,6 +8,7 @@
 //   it is bit-exact only if the device code does the same.
 #define NEPTUNE_HIP_FULL_VARIANTS 1
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -246,6 +247,85 @@ int update_norm(const neptune_hip_apply_geom_t* g, const void* a, const void* b,
   hipLaunchKernelGGL(neptune_reduce_final<T>, dim3(1), dim3(256), 0, st, part, blocks, static_cast<T*>(sum_out));
   NEPTUNE_HIP_CHECK(hipGetLastError());
   return NEPTUNE_HIP_OK;
+}
+}  // namespace
+
+// ---- neptune_ir.reduce: what neptune_hip_reduce_sum / neptune_hip_reduce share
+namespace {
+// the checks and the launch geometry every kind shares: which first-pass kernel, how many workgroups, the box
+struct ReducePlan {
+  bool whole;
+  int blocks;
+  int64_t total, count;   // cells of the reduced box, cells of the buffer
+  ReduceBoxParams P;
+};
+int reduce_plan(int dtype, int rank, const void* src, const int64_t* src_lb, const int64_t* src_ub, const int64_t* lb,
+                const int64_t* ub, const double* result, ReducePlan& pl) {
+  if (!src || !src_lb || !src_ub || !result) return NEPTUNE_HIP_EINVAL;
+  if (rank < 1 || rank > kMaxRank) return NEPTUNE_HIP_EINVAL;
+  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
+  int64_t ext[3], off[3], shp[3];
+  bool whole = true;
+  int64_t total = 1, count = 1;
+  for (int d = 0; d < rank; ++d) {
+    shp[d] = src_ub[d] - src_lb[d];
+    if (shp[d] <= 0) return NEPTUNE_HIP_EINVAL;
+    const int64_t l = lb ? lb[d] : src_lb[d], u = ub ? ub[d] : src_ub[d];
+    ext[d] = u - l;
+    off[d] = l - src_lb[d];
+    if (ext[d] < 0) return NEPTUNE_HIP_EINVAL;
+    if (ext[d] > 0 && (off[d] < 0 || off[d] + ext[d] > shp[d])) return NEPTUNE_HIP_EOOB;  // memref.load out of range
+    whole = whole && off[d] == 0 && ext[d] == shp[d] && ((uintptr_t)src % 16 == 0);
+    total *= ext[d];
+    count *= shp[d];
+  }
+  int blocks = (int)((total + 255) / 256 < kReduceBlocks ? (total + 255) / 256 : kReduceBlocks);
+  if (!whole) {  // box kernel: one unit of work = 4 row chunks of 256 lanes x 16 bytes
+    const int64_t cells = 256 * (dtype == NEPTUNE_HIP_F64 ? 2 : 4);
+    const int64_t last = ext[rank - 1];
+    const int64_t trips = ((total / (last ? last : 1)) * ((last + cells - 1) / cells) + 3) / 4;
+    blocks = (int)(trips < kReduceBlocks ? (trips < 1 ? 1 : trips) : kReduceBlocks);
+  }
+  auto fill = [&](const int64_t* a, int64_t* o, int64_t f) {
+    o[0] = o[1] = o[2] = f;
+    if (rank == 3) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
+    else if (rank == 2) { o[0] = a[0]; o[2] = a[1]; }
+    else { o[2] = a[0]; }
+  };
+  fill(ext, pl.P.ext, 1);
+  fill(off, pl.P.off, 0);
+  fill(shp, pl.P.shape, 1);
+  pl.whole = whole;
+  pl.blocks = blocks;
+  pl.total = total;
+  pl.count = count;
+  return NEPTUNE_HIP_OK;
+}
+
+// a kind other than "sum": the first pass on POp, the root on FOp (POp's combine, the identity map, the kind's finish)
+template <class T, class POp, class FOp>
+int reduce_launch(const ReducePlan& pl, const void* src, double* result, hipStream_t st) {
+  T* part = static_cast<T*>(rt().reduce_ws);
+  if (pl.whole) hipLaunchKernelGGL((neptune_reduce_partial_flat<T, POp>), dim3(pl.blocks), dim3(256), 0, st, (const T*)src, pl.count, part);
+  else hipLaunchKernelGGL((neptune_reduce_partial_box<T, POp>), dim3(pl.blocks), dim3(256), 0, st, (const T*)src, pl.P, part);
+  hipLaunchKernelGGL((neptune_reduce_final<T, FOp>), dim3(1), dim3(256), 0, st, part, pl.blocks, part + kReduceBlocks);
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  T h = 0;
+  NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, part + kReduceBlocks, sizeof(T), hipMemcpyDeviceToHost, st));
+  NEPTUNE_HIP_CHECK(hipStreamSynchronize(st));
+  *result = (double)h;   // the widening keeps NaN, +-inf and -0
+  return NEPTUNE_HIP_OK;
+}
+template <class T>
+int reduce_kind(int kind, bool raw, const ReducePlan& pl, const void* src, double* result, hipStream_t st) {
+  switch (kind) {
+    case NEPTUNE_HIP_REDUCE_MAX: return reduce_launch<T, RedMax<T>, RedMax<T>>(pl, src, result, st);
+    case NEPTUNE_HIP_REDUCE_MIN: return reduce_launch<T, RedMin<T>, RedMin<T>>(pl, src, result, st);
+    case NEPTUNE_HIP_REDUCE_L1: return reduce_launch<T, RedL1<T>, RedSum<T>>(pl, src, result, st);
+    default: break;
+  }
+  if (raw) return reduce_launch<T, RedSumSq<T>, RedSum<T>>(pl, src, result, st);
+  return reduce_launch<T, RedSumSq<T>, RedSqrtSum<T>>(pl, src, result, st);
 }
 }  // namespace
 
@@ -658,48 +738,20 @@ void* neptune_hip_reduce_workspace(void) {
 
 int neptune_hip_reduce_sum(int dtype, int rank, const void* src, const int64_t* src_lb, const int64_t* src_ub,
                            const int64_t* lb, const int64_t* ub, double* result, void* stream) {
-  if (!src || !src_lb || !src_ub || !result) return NEPTUNE_HIP_EINVAL;
-  if (rank < 1 || rank > kMaxRank) return NEPTUNE_HIP_EINVAL;
-  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
-  int64_t ext[3], off[3], shp[3];
-  bool whole = true;
-  int64_t total = 1, count = 1;
-  for (int d = 0; d < rank; ++d) {
-    shp[d] = src_ub[d] - src_lb[d];
-    if (shp[d] <= 0) return NEPTUNE_HIP_EINVAL;
-    const int64_t l = lb ? lb[d] : src_lb[d], u = ub ? ub[d] : src_ub[d];
-    ext[d] = u - l;
-    off[d] = l - src_lb[d];
-    if (ext[d] < 0) return NEPTUNE_HIP_EINVAL;
-    if (ext[d] > 0 && (off[d] < 0 || off[d] + ext[d] > shp[d])) return NEPTUNE_HIP_EOOB;  // memref.load out of range
-    whole = whole && off[d] == 0 && ext[d] == shp[d] && ((uintptr_t)src % 16 == 0);
-    total *= ext[d];
-    count *= shp[d];
-  }
-  if (total == 0) {  // empty domain: the reference's loop never runs, the accumulator stays 0
+  ReducePlan pl;
+  const int rc = reduce_plan(dtype, rank, src, src_lb, src_ub, lb, ub, result, pl);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  if (pl.total == 0) {  // empty domain: the reference's loop never runs, the accumulator stays 0
     *result = 0.0;
     return NEPTUNE_HIP_OK;
   }
   ensure_init();
   RuntimeState& s = rt();
   hipStream_t st = as_stream(stream);
-  int blocks = (int)((total + 255) / 256 < kReduceBlocks ? (total + 255) / 256 : kReduceBlocks);
-  if (!whole) {  // box kernel: one unit of work = 4 row chunks of 256 lanes x 16 bytes
-    const int64_t cells = 256 * (dtype == NEPTUNE_HIP_F64 ? 2 : 4);
-    const int64_t last = ext[rank - 1];
-    const int64_t trips = ((total / (last ? last : 1)) * ((last + cells - 1) / cells) + 3) / 4;
-    blocks = (int)(trips < kReduceBlocks ? (trips < 1 ? 1 : trips) : kReduceBlocks);
-  }
-  ReduceBoxParams P;
-  auto fill = [&](const int64_t* a, int64_t* o, int64_t f) {
-    o[0] = o[1] = o[2] = f;
-    if (rank == 3) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
-    else if (rank == 2) { o[0] = a[0]; o[2] = a[1]; }
-    else { o[2] = a[0]; }
-  };
-  fill(ext, P.ext, 1);
-  fill(off, P.off, 0);
-  fill(shp, P.shape, 1);
+  const bool whole = pl.whole;
+  const int blocks = pl.blocks;
+  const int64_t count = pl.count;
+  const ReduceBoxParams& P = pl.P;
   if (dtype == NEPTUNE_HIP_F64) {
     double* part = (double*)s.reduce_ws;
     if (whole) hipLaunchKernelGGL(neptune_reduce_partial_flat<double>, dim3(blocks), dim3(256), 0, st, (const double*)src, count, part);
@@ -722,6 +774,25 @@ int neptune_hip_reduce_sum(int dtype, int rank, const void* src, const int64_t* 
     *result = (double)h;
   }
   return NEPTUNE_HIP_OK;
+}
+
+int neptune_hip_reduce(int kind_flags, int dtype, int rank, const void* src, const int64_t* src_lb, const int64_t* src_ub,
+                       const int64_t* lb, const int64_t* ub, double* result, void* stream) {
+  const bool raw = (kind_flags & NEPTUNE_HIP_REDUCE_RAW) != 0;
+  const int kind = kind_flags & ~NEPTUNE_HIP_REDUCE_RAW;
+  if (kind < NEPTUNE_HIP_REDUCE_SUM || kind > NEPTUNE_HIP_REDUCE_L2) return NEPTUNE_HIP_EINVAL;
+  if (kind == NEPTUNE_HIP_REDUCE_SUM) return neptune_hip_reduce_sum(dtype, rank, src, src_lb, src_ub, lb, ub, result, stream);
+  ReducePlan pl;
+  const int rc = reduce_plan(dtype, rank, src, src_lb, src_ub, lb, ub, result, pl);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  if (pl.total == 0) {  // empty domain: the accumulator stays at the kind's identity
+    *result = kind == NEPTUNE_HIP_REDUCE_MAX ? -HUGE_VAL : (kind == NEPTUNE_HIP_REDUCE_MIN ? HUGE_VAL : 0.0);
+    return NEPTUNE_HIP_OK;
+  }
+  ensure_init();
+  hipStream_t st = as_stream(stream);
+  if (dtype == NEPTUNE_HIP_F64) return reduce_kind<double>(kind, raw, pl, src, result, st);
+  return reduce_kind<float>(kind, raw, pl, src, result, st);
 }
 
 // ---------------------------------------------------------------- Krylov vector updates

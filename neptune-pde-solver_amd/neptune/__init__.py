@@ -38,10 +38,38 @@ def reduce_sum(value: Expr, bounds=None) -> Expr:
     return Expr(get_compiler().create_reduce_sum(value._handle, lb, ub))
 
 
+def _reduce(kind: str, value: Expr, bounds) -> Expr:
+    lb, ub = bounds if bounds is not None else (None, None)
+    return Expr(get_compiler().create_reduce(value._handle, kind, lb, ub))
+
+
+def reduce_max(value: Expr, bounds=None) -> Expr:
+    """maximum of a temp over its box (or bounds=(lb, ub)): arith.maximumf semantics -- NaN if any cell is NaN, -0 < +0;
+    -inf over an empty box.  Like reduce_sum, `reduce_max(apply(...)(kernel))` is one read-only kernel (a max-norm
+    residual, a CFL number).  The module then carries the lowering option reduce-kinds."""
+    return _reduce("max", value, bounds)
+
+
+def reduce_min(value: Expr, bounds=None) -> Expr:
+    """minimum (arith.minimumf; +inf over an empty box): a positivity check"""
+    return _reduce("min", value, bounds)
+
+
+def reduce_l1(value: Expr, bounds=None) -> Expr:
+    """sum |x|, summed like reduce_sum"""
+    return _reduce("l1", value, bounds)
+
+
+def reduce_l2(value: Expr, bounds=None) -> Expr:
+    """sqrt(sum x*x): the squares summed like reduce_sum, one sqrt of the total"""
+    return _reduce("l2", value, bounds)
+
+
 def time_advance(state: Expr, dt: float, rhs: str) -> Expr:
     """explicit Euler step state + dt * rhs(state); `rhs` is the symbol a linear_op_def returned"""
     return Expr(get_compiler().create_time_advance_explicit(state._handle, dt, rhs))
 
 
 __all__ = ["Context", "get_compiler", "reset", "Expr", "apply", "stencil", "linear_op_def", "assemble_matrix",
-           "solve_linear", "jit_compile", "jit_class", "wrap", "load", "store", "unwrap", "apply_linear", "reduce_sum", "time_advance"]
+           "solve_linear", "jit_compile", "jit_class", "wrap", "load", "store", "unwrap", "apply_linear", "reduce_sum", "reduce_max", "reduce_min",
+           "reduce_l1", "reduce_l2", "time_advance"]

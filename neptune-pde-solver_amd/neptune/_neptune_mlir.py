@@ -81,6 +81,7 @@ class Compiler:
         self._scopes: List[_Scope] = []
         self._counter = 0
         self._func: Optional[dict] = None
+        self._options: List[str] = []      # lowering options the module needs ("// neptune-hip-option: <name>" lines of dump())
 
     # ---- helpers -----------------------------------------------------------------------
     def _fresh(self, hint: str = "") -> str:
@@ -103,7 +104,8 @@ class Compiler:
     # ---- basic ops (NeptuneModule.cpp:13-20) --------------------------------------------
     def dump(self) -> str:
         body = "\n".join(self._top)
-        return "module {\n" + body + ("\n" if body else "") + "}\n"
+        options = "".join(f"// neptune-hip-option: {name}\n" for name in self._options)
+        return options + "module {\n" + body + ("\n" if body else "") + "}\n"
 
     def create_wrap(self, buffer: Optional[Value], type_hint) -> Value:
         """buffer: a memref Value; type_hint: (lb, ub[, location]) of the field, or anything else for
@@ -250,6 +252,32 @@ class Compiler:
             where = " in #neptune_ir.bounds<lb = [%s], ub = [%s]>" % (", ".join(map(str, lb)), ", ".join(map(str, ub)))
         self._emit(f'{name} = neptune_ir.reduce {temp.name}{where} {{kind = "sum"}} : {temp.type.text()} -> {temp.type.elem}')
         return Value(name, _Type("scalar", temp.type.elem))
+
+    def create_reduce(self, temp: Value, kind: str, lb=None, ub=None) -> Value:
+        """neptune_ir.reduce %t [in bounds] {kind = "sum" | "max" | "min" | "l1" | "l2"}.  The reference lowers "sum" only;
+        the other kinds are this backend's (lowering option reduce-kinds), so a module that uses one carries the option
+        line and compiles unasked.  kind "sum" is create_reduce_sum: the same text, no option."""
+        if kind == "sum":
+            return self.create_reduce_sum(temp, lb, ub)
+        if kind not in ("max", "min", "l1", "l2"):
+            raise ValueError(f"unknown reduce kind {kind!r}")
+        if temp.type.kind != "temp":
+            raise TypeError("create_reduce needs a temp value")
+        if "reduce-kinds" not in self._options:
+            self._options.append("reduce-kinds")
+        name = self._fresh("s")
+        where = ""
+        if lb is not None:
+            where = " in #neptune_ir.bounds<lb = [%s], ub = [%s]>" % (", ".join(map(str, lb)), ", ".join(map(str, ub)))
+        self._emit(f'{name} = neptune_ir.reduce {temp.name}{where} {{kind = "{kind}"}} : {temp.type.text()} -> {temp.type.elem}')
+        return Value(name, _Type("scalar", temp.type.elem))
+
+    def create_math_abs(self, value: Value) -> Value:  # extension: what a max-norm residual needs in a body
+        if value.type.kind != "scalar":
+            raise TypeError("absf needs a scalar value")
+        name = self._fresh("v")
+        self._emit(f"{name} = math.absf {value.name} : {value.type.elem}")
+        return Value(name, value.type)
 
     def create_time_advance_explicit(self, state: Value, dt: float, rhs_symbol: str) -> Value:
         """neptune_ir.time_advance %state, %dt {method = 0, rhs = @symbol}: state + dt * rhs(state), one fused kernel

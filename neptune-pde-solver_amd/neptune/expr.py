@@ -35,6 +35,10 @@ class Expr:
             raise TypeError(f"stencil offsets must be integers, got {offsets!r}")
         return Expr(get_compiler().create_access(self._handle, [int(o) for o in offsets]))
 
+    def __abs__(self):
+        """abs(x): math.absf (an extension, like `/`)"""
+        return Expr(get_compiler().create_math_abs(self._handle))
+
     def __repr__(self):
         return f"Expr({self._handle!r})"
 

@@ -23,6 +23,10 @@ OK, EINVAL, EUNSUPPORTED, EOOB, ECOMM = 0, -1, -2, -3, -4
 SLAB_ID_BYTES = 128
 TRANSPORT_RCCL, TRANSPORT_PEER = 0, 1
 F64, F32 = 0, 1
+# neptune_hip_reduce kinds (NEPTUNE_HIP_REDUCE_*); REDUCE_RAW: or-ed in, leaves the finishing step (l2's sqrt) out
+REDUCE_SUM, REDUCE_MAX, REDUCE_MIN, REDUCE_L1, REDUCE_L2 = range(5)
+REDUCE_RAW = 0x100
+REDUCE_KINDS = {"sum": REDUCE_SUM, "max": REDUCE_MAX, "min": REDUCE_MIN, "l1": REDUCE_L1, "l2": REDUCE_L2}
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_MARCH = 0, 1, 2
 FLAG_DIRECT_FLAT = 1   # direct kernel: flat one-lane-per-cell form instead of the rows form
 BODY_LAP2D5_F64, BODY_LAP3D7_F64, BODY_LAP3D27_F32, BODY_LAP1D3_F64 = 0, 1, 2, 3
@@ -129,6 +133,7 @@ SIGNATURES = {
     "neptune_hip_store_full": (_i, [_i, _vp, _vp, _i64, _vp]),
     "neptune_hip_store_box": (_i, [_i, _i, _vp, _i64p, _i64p, _vp, _i64p, _i64p, _i64p, _i64p, _vp]),
     "neptune_hip_reduce_sum": (_i, [_i, _i, _vp, _i64p, _i64p, _i64p, _i64p, C.POINTER(C.c_double), _vp]),
+    "neptune_hip_reduce": (_i, [_i, _i, _i, _vp, _i64p, _i64p, _i64p, _i64p, C.POINTER(C.c_double), _vp]),
     "neptune_hip_axpy": (_i, [_i, _i64, _dbl, _vp, _vp, _vp]),
     "neptune_hip_xpay": (_i, [_i, _i64, _vp, _dbl, _vp, _vp]),
     "neptune_hip_fill_hash": (_i, [_i, _vp, _i64, _i64, _u64, _vp]),

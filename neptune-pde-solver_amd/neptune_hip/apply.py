@@ -336,6 +336,28 @@ def reduce_sum(src: DeviceField, bounds: Optional[Box] = None, stream: Optional[
     return out.value
 
 
+def reduce(src: DeviceField, kind, bounds: Optional[Box] = None, stream: Optional[int] = None) -> float:
+    """neptune_ir.reduce %src (in bounds)? {kind = "sum" | "max" | "min" | "l1" | "l2"}; blocking.  kind: the name, or a
+    _capi.REDUCE_* value (| _capi.REDUCE_RAW: l2 without its sqrt).  The value is computed in the field's element type
+    and comes back widened to a Python float: max / min fold with arith.maximumf / minimumf (NaN if any cell is NaN,
+    -0 < +0; -inf / +inf over an empty box), l1 = sum |x| and l2 = sqrt(sum x*x) on the fixed tree of reduce_sum
+    (+0 over an empty box); kind "sum" returns the bits of reduce_sum."""
+    lib = _capi.load()
+    if isinstance(kind, str):
+        if kind not in _capi.REDUCE_KINDS:
+            raise ValueError(f"unknown reduce kind {kind!r} (expected one of {', '.join(_capi.REDUCE_KINDS)})")
+        kind = _capi.REDUCE_KINDS[kind]
+    r = src.rank
+    arr = lambda v: (C.c_int64 * r)(*[int(x) for x in v])
+    out = C.c_double(0.0)
+    rc = lib.neptune_hip_reduce(int(kind), src.dtype, r, src.ptr, arr(src.lb), arr(src.ub),
+                                arr(bounds[0]) if bounds is not None else None,
+                                arr(bounds[1]) if bounds is not None else None, C.byref(out),
+                                current_stream_ptr() if stream is None else stream)
+    _capi.check(rc, "neptune_hip_reduce")
+    return out.value
+
+
 def autotune_builtin(body, inputs: Sequence[DeviceField], out: DeviceField, bounds: Box,
                      region: Optional[Box] = None, reps: int = 5, stream: Optional[int] = None):
     """plan-time tuning: -> (LaunchCfg of the fastest tile/chunk for this geometry, its ms per launch).  `body`: a

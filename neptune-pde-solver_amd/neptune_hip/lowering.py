@@ -55,30 +55,36 @@ def _take(lib, p: C.c_void_p) -> Optional[str]:
     return s
 
 
-def verify(text: str) -> None:
-    """raise LoweringError with the reference's diagnostic if the module is ill-formed"""
+def verify(text: str, reduce_kinds: bool = False) -> None:
+    """raise LoweringError with the reference's diagnostic if the module is ill-formed.  reduce_kinds: lowering option
+    reduce-kinds (see to_hip)"""
     lib = _load()
+    text = with_options(text, reduce_kinds=reduce_kinds)
     diag = C.c_void_p()
     if lib.neptune_lowering_verify(text.encode(), C.byref(diag)) != 0:
         raise LoweringError(_take(lib, diag))
 
 
 NORM_ENTRIES_LINE = "// neptune-hip-option: norm-entries\n"
+REDUCE_KINDS_LINE = "// neptune-hip-option: reduce-kinds\n"
 
 
-def with_options(text: str, norm_entries: bool = False) -> str:
+def with_options(text: str, norm_entries: bool = False, reduce_kinds: bool = False) -> str:
     """the module text with its lowering options: they travel in the text, one comment line each
     (include/neptune_lowering.h), so the cache key of a module covers them"""
+    if reduce_kinds and REDUCE_KINDS_LINE.strip() not in text:
+        text = REDUCE_KINDS_LINE + text
     if norm_entries and NORM_ENTRIES_LINE.strip() not in text:
         text = NORM_ENTRIES_LINE + text
     return text
 
 
-def to_hip(text: str, norm_entries: bool = False):
+def to_hip(text: str, norm_entries: bool = False, reduce_kinds: bool = False):
     """-> (HIP source, report dict).  norm_entries: lowering option norm-entries (eligible applies also export their
-    monitored launch <fn>_<k>__geomN; the report names it as "norm_symbol")"""
+    monitored launch <fn>_<k>__geomN; the report names it as "norm_symbol").  reduce_kinds: lowering option reduce-kinds
+    (neptune_ir.reduce kinds max | min | l1 | l2 verify and lower; a fused apply's report entry carries "reduce_kind")"""
     lib = _load()
-    text = with_options(text, norm_entries)
+    text = with_options(text, norm_entries, reduce_kinds)
     src, rep, diag = C.c_void_p(), C.c_void_p(), C.c_void_p()
     if lib.neptune_lowering_to_hip(text.encode(), C.byref(src), C.byref(rep), C.byref(diag)) != 0:
         raise LoweringError(_take(lib, diag))
@@ -137,13 +143,13 @@ def module_hash(text: str) -> str:
 
 def compile_module(text: str, so_path: Optional[os.PathLike] = None, use_cache: bool = True,
                    cache_directory: Optional[os.PathLike] = None, load: bool = True,
-                   norm_entries: bool = False) -> Optional["LoweredModule"]:
+                   norm_entries: bool = False, reduce_kinds: bool = False) -> Optional["LoweredModule"]:
     """lower + hipcc (gfx950) + load.  Compiling needs no GPU; loading needs libneptune_hip.so.  Without an explicit
     so_path the object lives in `cache_directory` (default: cache_dir()) under its module_hash.  load=False only fills
     the cache (what the profiling scripts do before they start rocprofv3: hipcc is started with an environment scrubbed
     of LD_PRELOAD / ROCP* / HSA_TOOLS_*, csrc/lowering/capi.cpp, but a profiled run should be a pure cache hit)."""
     lib = _load()
-    text = with_options(text, norm_entries)   # lowering option norm-entries: see to_hip
+    text = with_options(text, norm_entries, reduce_kinds)   # lowering options: see to_hip
     if so_path is None:
         directory = Path(cache_directory) if cache_directory else cache_dir()
         directory.mkdir(parents=True, exist_ok=True)

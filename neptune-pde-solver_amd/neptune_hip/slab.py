@@ -468,7 +468,8 @@ class ShardedModule:
         slab = self.slab
         res = self.module.signatures[name]["result"]
         if slab.world > 1 and res and res["kind"] == "scalar" and res.get("scalar") == "derived":
-            raise ValueError(f"@{name} returns a scalar computed from a neptune_ir.reduce result; on a slab decomposition that "
+            raise ValueError(f"@{name} returns a scalar computed from a neptune_ir.reduce result (or a reduce of a kind other than "
+                             "\"sum\", whose per-rank values do not add up); on a slab decomposition that "
                              "result is only this rank's partial sum, so the function would be evaluated on it and the "
                              "ranks' values could not be combined.  Return the bare reduce (ShardedModule adds the ranks' sums) "
                              "and finish the arithmetic on the total.")
