@@ -670,6 +670,20 @@ inline int group_auto_variant(int picked) {
   return -1;
 }
 
+// Kernels that keep coordinates and row indices in 32 bits (the rows form of the direct kernel, the reduce(apply)
+// kernels) take a launch only if every extent and shift of its parameter block is narrow
+constexpr int64_t kNarrowLim = 0x7fffff00LL;
+template <class T, int NIN>
+inline bool direct_params_narrow(const DirectParams<T, NIN>& P) {
+  const int64_t lim = kNarrowLim;
+  bool narrow = P.n[0] * P.n[1] < lim && P.n[2] < lim;
+  for (int k = 0; k < NIN; ++k) {
+    narrow = narrow && P.m[k][0] * P.m[k][1] < lim && P.m[k][2] < lim;
+    for (int ax = 0; ax < 3; ++ax) narrow = narrow && P.sh[k][ax] > -lim && P.sh[k][ax] < lim;
+  }
+  return narrow;
+}
+
 // the direct kernel on g's region: rows form when all coordinates fit 31 bits (see apply_direct.hpp),
 // else -- or when `flat` asks for it -- the flat form
 template <class Body, class T, int RANK, int NIN>
@@ -678,15 +692,10 @@ inline int launch_direct(const Body& body, const neptune_hip_apply_geom_t* g, co
   DirectParams<T, NIN> P{};
   fill_direct_params<T, RANK, NIN>(g, in, out, P);
   {
-    const int64_t lim = 0x7fffff00LL;
     const int64_t eK = P.rub[2] - P.rlb[2], rows = (P.rub[0] - P.rlb[0]) * (P.rub[1] - P.rlb[1]);
-    bool narrow = !flat && P.n[0] * P.n[1] < lim && P.n[2] < lim;
-    for (int k = 0; k < NIN; ++k) {
-      narrow = narrow && P.m[k][0] * P.m[k][1] < lim && P.m[k][2] < lim;
-      for (int ax = 0; ax < 3; ++ax) narrow = narrow && P.sh[k][ax] > -lim && P.sh[k][ax] < lim;
-    }
+    const bool narrow = !flat && direct_params_narrow(P);
     const int64_t nchunk = (eK + 255) / 256;
-    if (narrow && rows * nchunk < lim) {
+    if (narrow && rows * nchunk < kNarrowLim) {
       const dim3 grid = grid_for_blocks(rows * nchunk);
       if constexpr (IsMonitored<Body>::value) {
         // one partial per workgroup of the (possibly folded) grid, after those of the call's earlier launches

@@ -1,6 +1,7 @@
 // util_kernels.hpp -- store (box copy), streaming copy, deterministic fill and bitwise
 // compare kernels around the apply kernels.
 #pragma once
+#include "../../../include/neptune_hip.h"
 #include "apply_common.hpp"
 #include "body_ops.hpp"
 
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(256) void neptune_count_mismatch(const U* __restric
 // reproducible from run to run and independent of scheduling (no atomics), but differs from the
 // serial sum by rounding: |gpu - serial| <= 2 (n-1) eps sum|x_i| (each order is within (n-1) eps
 // sum|x_i| of the exact sum).  Every kernel accumulates in the element type, like the reference.  One host path
-// adds more: a bounded reduce beyond rank 3 (run_reduce_sum, lowered_runtime.hpp) adds its per-leading-index box
+// adds more: a bounded reduce beyond rank 3 (run_reduce, lowered_runtime.hpp) adds its per-leading-index box
 // sums in double and rounds to the element type once, which only removes rounding
 // (tests/test_reduce_exact_gpu.py::test_rank4_bounded_f32_reduce_adds_slab_sums_in_double).
 constexpr int kReduceBlocks = 2048;  // partials of the first pass; the workspace holds kReduceBlocks + 1 elements
@@ -179,6 +180,21 @@ template <class T> struct RedSumSq : RedSum<T> {
 template <class T> struct RedSqrtSum : RedSum<T> {
   static __device__ __forceinline__ T finish(T x) { return ops::sqrt(x); }
 };
+
+// The kind table: the first-pass op POp and the root op FOp of NEPTUNE_HIP_REDUCE_<KIND> (neptune_hip.h) -- RAW leaves l2's
+// sqrt out -- and what a reduce over no cells returns, the kind's identity.  Every host path that takes a kind reads them
+// here: neptune_hip_reduce (neptune_hip_rt.hip) and run_reduce / run_apply_reduce (lowered_runtime.hpp).
+template <int KIND, class T, bool RAW = false> struct ReduceOps { using POp = RedSum<T>; using FOp = RedSum<T>; };
+template <class T, bool RAW> struct ReduceOps<NEPTUNE_HIP_REDUCE_MAX, T, RAW> { using POp = RedMax<T>; using FOp = RedMax<T>; };
+template <class T, bool RAW> struct ReduceOps<NEPTUNE_HIP_REDUCE_MIN, T, RAW> { using POp = RedMin<T>; using FOp = RedMin<T>; };
+template <class T, bool RAW> struct ReduceOps<NEPTUNE_HIP_REDUCE_L1, T, RAW> { using POp = RedL1<T>; using FOp = RedSum<T>; };
+template <class T, bool RAW> struct ReduceOps<NEPTUNE_HIP_REDUCE_L2, T, RAW> {
+  using POp = RedSumSq<T>;
+  using FOp = std::conditional_t<RAW, RedSum<T>, RedSqrtSum<T>>;
+};
+inline double reduce_identity(int kind) {
+  return kind == NEPTUNE_HIP_REDUCE_MAX ? -__builtin_huge_val() : (kind == NEPTUNE_HIP_REDUCE_MIN ? __builtin_huge_val() : 0.0);
+}
 
 // A value of the tree.  The kernels below are written as the sum they were before the kinds existed -- `acc += x` -- and
 // the types say what `+=` is: node += node is one combine; node += cell (a T: a loaded or computed value that counts) is the

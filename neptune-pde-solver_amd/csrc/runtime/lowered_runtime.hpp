@@ -35,7 +35,7 @@
 #include "../kernels/apply_march2.hpp"
 #include "../kernels/apply_nd.hpp"
 #include "../kernels/body_ops.hpp"
-#include "../kernels/reduce_apply.hpp"
+#include "../kernels/reduce_launch.hpp"
 
 namespace neptune_hip {
 namespace lowered {
@@ -103,15 +103,7 @@ class Scope {
   bool slab() const { return slab_on_; }
   bool has_ghosts() const { return slab_on_ && (slab_[2] > 0 || slab_[3] > 0); }
   // a declared (global) logical box -> what this rank holds of it
-  Box local_box(const Box& b) const {
-    Box r = b;
-    if (!slab_on_) return r;
-    const int64_t lo = slab_[0] - slab_[2], hi = slab_[1] + slab_[3];
-    if (r.lb[0] < lo) r.lb[0] = lo;
-    if (r.ub[0] > hi) r.ub[0] = hi;
-    if (r.ub[0] < r.lb[0]) r.ub[0] = r.lb[0];
-    return r;
-  }
+  Box local_box(const Box& b) const { return clip_planes(b, true); }
   // loop bounds with lb > ub along a dimension: the reference's scf.for nest (DataflowLowering.cpp:289-310 for
   // apply, :604-611 for reduce) makes zero trips, i.e. the box is empty
   static Box zero_trip(const Box& b) {
@@ -122,15 +114,7 @@ class Scope {
   }
   // a bounds attribute -> the part this rank computes: its owned planes, or (with_ghosts) all the
   // planes it holds
-  Box owned_bounds(const Box& b, bool with_ghosts = false) const {
-    Box r = zero_trip(b);
-    if (!slab_on_) return r;
-    const int64_t lo = slab_[0] - (with_ghosts ? slab_[2] : 0), hi = slab_[1] + (with_ghosts ? slab_[3] : 0);
-    if (r.lb[0] < lo) r.lb[0] = lo;
-    if (r.ub[0] > hi) r.ub[0] = hi;
-    if (r.ub[0] < r.lb[0]) r.ub[0] = r.lb[0];
-    return r;
-  }
+  Box owned_bounds(const Box& b, bool with_ghosts = false) const { return clip_planes(zero_trip(b), with_ghosts); }
   ~Scope() {
     // every exit path has synchronised the stream (finish / export_result), so the blocks are idle
     for (auto& b : owned_) neptune_hip_pool_release(b.p, b.bytes);
@@ -272,6 +256,16 @@ class Scope {
       once = true;
     }
   }
+  // dim 0 of `b` clipped to this rank's owned planes, or (with_ghosts) to all the planes it holds
+  Box clip_planes(const Box& b, bool with_ghosts) const {
+    Box r = b;
+    if (!slab_on_) return r;
+    const int64_t lo = slab_[0] - (with_ghosts ? slab_[2] : 0), hi = slab_[1] + (with_ghosts ? slab_[3] : 0);
+    if (r.lb[0] < lo) r.lb[0] = lo;
+    if (r.ub[0] > hi) r.ub[0] = hi;
+    if (r.ub[0] < r.lb[0]) r.ub[0] = r.lb[0];
+    return r;
+  }
   static bool box_matches(const Val& v, const Box& b) {
     if (v.box.rank != b.rank) return false;
     return v.box.same_shape(b);
@@ -309,6 +303,47 @@ inline void fill_geom(neptune_hip_apply_geom_t& g, const Box& out, const Box& bo
   }
 }
 
+// ---- what every apply path decides before it launches ----
+// Result placement.  `dest`: the field an apply's single consumer (a whole-buffer store) will copy the result into, or
+// nullptr; the kernel may write there directly, and the copy is elided, when the field has the result's size and overlaps
+// no input.
+inline bool writes_direct(const Val* dest, const Box& box, const Val* const* in, int nin) {
+  bool direct = dest != nullptr && dest->count == box.count();
+  for (int k = 0; direct && k < nin; ++k) direct = !overlaps(*dest, *in[k]);
+  return direct;
+}
+// the value the kernel writes, `dest` under the result's box or a fresh temporary, and in *direct which of the two
+inline Val place_result(Scope& sc, const Val* dest, const Box& box, int esize, const Val* const* in, int nin, bool* direct) {
+  *direct = writes_direct(dest, box, in, nin);
+  if (!*direct) return sc.alloc(box, esize);
+  Val out = *dest;
+  out.box = box;
+  return out;
+}
+// Ghost planes (slab mode).  An apply that stays within its plane (halo0 == 0) and reads only values whose ghost planes
+// are good is computed on the ghost planes too, so a stencil apply may follow it without an exchange: returns whether
+// this one is (any other result has stale ghosts).  One that reaches into neighbouring planes of a value whose ghosts are
+// stale cannot run: `refusal` is the caller's diagnostic.
+constexpr const char* kStaleGhostRefusal =
+    "slab mode: neptune_ir.apply reads neighbouring planes of a value computed inside this call; "
+    "its ghost planes would need a halo exchange in the middle of the function (split the function "
+    "or run it on one GPU)";
+inline bool whole_local_or_die(Scope& sc, const Val* const* in, int nin, int halo0, const char* refusal) {
+  bool inputs_fresh = true;
+  for (int k = 0; k < nin; ++k) inputs_fresh = inputs_fresh && !in[k]->stale_ghosts;
+  if (sc.has_ghosts() && halo0 > 0 && !inputs_fresh) die(sc.name(), refusal);
+  return sc.slab() && halo0 == 0 && inputs_fresh;
+}
+// the verdict of geom_check_radius / group_check_radius
+[[noreturn]] inline void die_oob(Scope& sc) {
+  die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
+                 "DataflowLowering.cpp:380-410); refusing to run it");
+}
+inline void check_radius_or_die(Scope& sc, int rc) {
+  if (rc == NEPTUNE_HIP_EOOB) die_oob(sc);
+  if (rc != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
+}
+
 // One neptune_ir.apply.  `dest`: a field the single consumer (a whole-buffer store) will copy the
 // result into; when it aliases no input the kernel writes there directly and the copy is elided.
 // `top_radius`: max |offset| of the UNCONDITIONAL accesses (those not nested under scf.if) -- the
@@ -339,37 +374,21 @@ inline const neptune_hip_launch_cfg_t* launch_override() {
 template <class Body, class T, int RANK, int NIN, class FP>
 inline Val run_apply(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
                      const neptune_hip::Reach& top_radius, const Val* dest, int halo0 = 0) {
-  // slab mode: an apply that stays within its plane (halo0 == 0) and reads only values whose ghost
-  // planes are good is computed on the ghost planes too, so a stencil apply may follow it without an
-  // exchange; any other result has stale ghosts
-  bool inputs_fresh = true;
-  for (int k = 0; k < NIN; ++k) inputs_fresh = inputs_fresh && !in[k]->stale_ghosts;
-  if (sc.has_ghosts() && halo0 > 0 && !inputs_fresh)
-    die(sc.name(), "slab mode: neptune_ir.apply reads neighbouring planes of a value computed inside this call; "
-                   "its ghost planes would need a halo exchange in the middle of the function (split the function "
-                   "or run it on one GPU)");
-  const bool whole_local = sc.slab() && halo0 == 0 && inputs_fresh;
+  const bool whole_local = whole_local_or_die(sc, in, NIN, halo0, kStaleGhostRefusal);
   const Box result_box = sc.local_box(result_decl);
   const Box bounds = sc.owned_bounds(bounds_decl, whole_local);
   neptune_hip_apply_geom_t g;
   fill_geom(g, result_box, bounds, in, NIN);
-  int rc = geom_check_radius(&g, top_radius);
-  if (rc == NEPTUNE_HIP_EOOB)
-    die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
-                   "DataflowLowering.cpp:380-410); refusing to run it");
-  if (rc != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
-  bool direct = dest != nullptr && dest->count == result_box.count();
-  for (int k = 0; direct && k < NIN; ++k) direct = !overlaps(*dest, *in[k]);
-  Val out;
-  if (direct) {
-    out = *dest;
-    out.box = result_box;
-  } else {
-    out = sc.alloc(result_box, (int)sizeof(T));
-  }
+  check_radius_or_die(sc, geom_check_radius(&g, top_radius));
+  bool direct;
+  Val out = place_result(sc, dest, result_box, (int)sizeof(T), in, NIN, &direct);
   out.stale_ghosts = sc.has_ghosts() && !whole_local;
   const void* ptrs[NIN];
   for (int k = 0; k < NIN; ++k) ptrs[k] = in[k]->dev;
+  auto launch = [&](const neptune_hip_apply_geom_t& gl) {
+    if (launch_apply<Body, T, RANK, NIN, FP>(body, &gl, ptrs, out.dev, sc.stream(), launch_override()) != NEPTUNE_HIP_OK)
+      die(sc.name(), "neptune_ir.apply launch rejected");
+  };
   if (sc.pending()) {
     // The inputs' ghost planes are still being exchanged on another stream.  A stencil apply does its interior planes
     // now -- they read owned planes only -- then waits, then does the planes next to the ghosts and the ghost planes
@@ -381,24 +400,21 @@ inline Val run_apply(Scope& sc, const Body& body, const Box& result_decl, const 
       neptune_hip_apply_geom_t gi = g;
       gi.region_lb[0] = a;
       gi.region_ub[0] = b;
-      rc = launch_apply<Body, T, RANK, NIN, FP>(body, &gi, ptrs, out.dev, sc.stream(), launch_override());
-      if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply launch rejected");
+      launch(gi);
       sc.wait_pending();
       const int64_t edges[2][2] = {{0, a}, {b, n0}};
       for (auto& e : edges) {
         if (e[1] <= e[0]) continue;
         gi.region_lb[0] = e[0];
         gi.region_ub[0] = e[1];
-        rc = launch_apply<Body, T, RANK, NIN, FP>(body, &gi, ptrs, out.dev, sc.stream(), launch_override());
-        if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply launch rejected");
+        launch(gi);
       }
       if (direct) sc.mark_dirty(*dest);
       return out;
     }
     sc.wait_pending();
   }
-  rc = launch_apply<Body, T, RANK, NIN, FP>(body, &g, ptrs, out.dev, sc.stream(), launch_override());
-  if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply launch rejected");
+  launch(g);
   if (direct) sc.mark_dirty(*dest);
   return out;
 }
@@ -439,17 +455,12 @@ inline void run_apply_group(Scope& sc, GB body, const Box& result_decl, const Bo
   const Box result_box = result_decl, bounds = Scope::zero_trip(bounds_decl);
   neptune_hip_apply_geom_t g;
   fill_geom(g, result_box, bounds, in, NIN);
-  const int rcr = group_check_radius<GB, RANK>(&g, reach);
-  if (rcr == NEPTUNE_HIP_EOOB)
-    die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
-                   "DataflowLowering.cpp:380-410); refusing to run it");
-  if (rcr != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
+  check_radius_or_die(sc, group_check_radius<GB, RANK>(&g, reach));
   // destination forwarding, decided for the group as a whole: holds for the fused launch and for the members run in turn
   // (member m's direct write happens before member m+1 reads ITS inputs)
   const Val* fwd[M];
   for (int m = 0; m < M; ++m) {
-    bool direct = dest[m] != nullptr && dest[m]->count == result_box.count();
-    for (int k = 0; direct && k < NIN; ++k) direct = !overlaps(*dest[m], *in[k]);
+    bool direct = writes_direct(dest[m], result_box, in, NIN);
     for (int o = 0; direct && o < M; ++o) direct = o == m || dest[o] == nullptr || !overlaps(*dest[m], *dest[o]);
     fwd[m] = direct ? dest[m] : nullptr;
   }
@@ -465,12 +476,8 @@ inline void run_apply_group(Scope& sc, GB body, const Box& result_decl, const Bo
     return;
   }
   for (int m = 0; m < M; ++m) {
-    if (fwd[m]) {
-      out[m] = *fwd[m];
-      out[m].box = result_box;
-    } else {
-      out[m] = sc.alloc(result_box, (int)sizeof(T));
-    }
+    bool direct;
+    out[m] = place_result(sc, fwd[m], result_box, (int)sizeof(T), in, NIN, &direct);
     out[m].stale_ghosts = false;
     body.out[m] = static_cast<T*>(out[m].dev);
   }
@@ -480,173 +487,6 @@ inline void run_apply_group(Scope& sc, GB body, const Box& result_decl, const Bo
   for (int m = 0; m < M; ++m)
     if (fwd[m]) sc.mark_dirty(*fwd[m]);
   neptune_hip_note_group(1, M);
-}
-
-// One neptune_ir.apply of rank R = 4..6 whose accesses have no offset along the leading R-3 dimensions (batch / component
-// dimensions; the reference's lowering is rank-generic, DataflowLowering.cpp:268-270, 301-308): for every leading index one
-// rank-3 apply on the contiguous sub-field -- inside the leading bounds the body (which sees the leading indices as members
-// `lead[]`), outside them the copy-through of input 0 (DataflowLowering.cpp:283-287).  Every input must cover the result's
-// leading extent.  Slab mode: dim 0, the slab axis, is a leading dimension here, so the apply never reaches into a
-// neighbouring plane: every rank runs its own leading indices (and the ghost planes too when its inputs' ghosts are good,
-// like run_apply with halo0 == 0).
-template <class Body, class T, int R, int NIN, class FP>
-inline Val run_apply_batched(Scope& sc, Body body, const Box& result_global, const Box& bounds_decl, const Val* const* in,
-                             const neptune_hip::Reach& top_radius, const Val* dest) {
-  static_assert(R > 3 && R <= kMaxBoxRank, "run_apply_batched: rank 4..6");
-  constexpr int L = R - 3;
-  bool inputs_fresh = true;
-  for (int k = 0; k < NIN; ++k) inputs_fresh = inputs_fresh && !in[k]->stale_ghosts;
-  const bool whole_local = sc.slab() && inputs_fresh;
-  const Box result_decl = sc.local_box(result_global);
-  const Box bounds = sc.owned_bounds(bounds_decl, whole_local);
-  auto sub_box = [](const Box& b) {
-    Box r;
-    r.rank = 3;
-    for (int d = 0; d < 3; ++d) { r.lb[d] = b.lb[L + d]; r.ub[d] = b.ub[L + d]; }
-    return r;
-  };
-  const Box out3 = sub_box(result_decl), bnd3 = sub_box(bounds);
-  for (int k = 0; k < NIN; ++k) {
-    if (in[k]->box.rank != R) die(sc.name(), "neptune_ir.apply: input rank differs from the result's");
-    for (int d = 0; d < L; ++d)
-      if (in[k]->box.lb[d] > result_decl.lb[d] || in[k]->box.ub[d] < result_decl.ub[d])
-        die(sc.name(), "neptune_ir.apply of rank > 3: an input does not cover the result's leading extent");
-  }
-  bool direct = dest != nullptr && dest->count == result_decl.count();
-  for (int k = 0; direct && k < NIN; ++k) direct = !overlaps(*dest, *in[k]);
-  Val out;
-  if (direct) {
-    out = *dest;
-    out.box = result_decl;
-  } else {
-    out = sc.alloc(result_decl, (int)sizeof(T));
-  }
-  out.stale_ghosts = sc.has_ghosts() && !whole_local;
-  sc.wait_pending();
-  const int64_t out_slab = out3.count();
-  int64_t lead_n = 1;
-  for (int d = 0; d < L; ++d) lead_n *= result_decl.ub[d] - result_decl.lb[d];
-  Val sub[NIN];
-  const Val* subp[NIN];
-  const void* ptrs[NIN];
-  for (int64_t flat = 0; flat < lead_n; ++flat) {
-    int64_t idx[3] = {0, 0, 0}, rem = flat;
-    for (int d = L - 1; d >= 0; --d) {
-      const int64_t n = result_decl.ub[d] - result_decl.lb[d];
-      idx[d] = result_decl.lb[d] + rem % n;
-      rem /= n;
-    }
-    bool inside = true;
-    for (int d = 0; d < L; ++d) inside = inside && idx[d] >= bounds.lb[d] && idx[d] < bounds.ub[d];
-    for (int k = 0; k < NIN; ++k) {
-      const Box& ib = in[k]->box;
-      int64_t slab = 1, off = 0;
-      for (int d = 0; d < 3; ++d) slab *= ib.ub[L + d] - ib.lb[L + d];
-      for (int d = 0; d < L; ++d) off = off * (ib.ub[d] - ib.lb[d]) + (idx[d] - ib.lb[d]);
-      sub[k] = *in[k];
-      sub[k].box = sub_box(ib);
-      sub[k].count = slab;
-      sub[k].dev = static_cast<char*>(in[k]->dev) + off * slab * (int64_t)sizeof(T);
-      subp[k] = &sub[k];
-      ptrs[k] = sub[k].dev;
-    }
-    void* outp = static_cast<char*>(out.dev) + flat * out_slab * (int64_t)sizeof(T);
-    neptune_hip_apply_geom_t g;
-    Box b3 = bnd3;
-    if (!inside) { for (int d = 0; d < 3; ++d) b3.ub[d] = b3.lb[d]; }   // zero trips: the kernel writes the copy-through only
-    fill_geom(g, out3, b3, subp, NIN);
-    int rc = inside ? geom_check_radius(&g, top_radius) : geom_validate(&g);
-    if (rc == NEPTUNE_HIP_EOOB)
-      die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
-                     "DataflowLowering.cpp:380-410); refusing to run it");
-    if (rc != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
-    for (int d = 0; d < L; ++d) body.lead[d] = idx[d];
-    rc = launch_apply<Body, T, 3, NIN, FP>(body, &g, ptrs, outp, sc.stream(), launch_override());
-    if (rc != NEPTUNE_HIP_OK) die(sc.name(), "neptune_ir.apply launch rejected");
-  }
-  if (direct) sc.mark_dirty(*dest);
-  return out;
-}
-
-// One neptune_ir.apply of rank R = 4..6 with offsets along its leading dimensions: a stencil in more than three dimensions
-// (kernels/apply_nd.hpp).  Same contract as run_apply, slab mode included (dim 0 is the slab axis whatever the rank); the
-// launch is not split around a pending halo exchange, it waits for it.
-template <class Body, class T, int R, int NIN>
-inline Val run_apply_nd(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
-                        const neptune_hip::ReachN& top_reach, const Val* dest, int halo0 = 0) {
-  static_assert(R > 3 && R <= kMaxBoxRank && R <= neptune_hip::kNdMaxRank, "run_apply_nd: rank 4..6");
-  bool inputs_fresh = true;
-  for (int k = 0; k < NIN; ++k) inputs_fresh = inputs_fresh && !in[k]->stale_ghosts;
-  if (sc.has_ghosts() && halo0 > 0 && !inputs_fresh)
-    die(sc.name(), "slab mode: neptune_ir.apply reads neighbouring planes of a value computed inside this call; "
-                   "its ghost planes would need a halo exchange in the middle of the function (split the function "
-                   "or run it on one GPU)");
-  const bool whole_local = sc.slab() && halo0 == 0 && inputs_fresh;
-  const Box result_box = sc.local_box(result_decl);
-  const Box bounds = sc.owned_bounds(bounds_decl, whole_local);
-  if (result_box.rank != R || bounds.rank != R) die(sc.name(), "malformed neptune_ir.apply geometry");
-  for (int k = 0; k < NIN; ++k)
-    if (in[k]->box.rank != R) die(sc.name(), "neptune_ir.apply: input rank differs from the result's");
-  if (!in[0]->box.same_shape(result_box))
-    die(sc.name(), "neptune_ir.apply: input 0 does not have the result's shape (DataflowLowering.cpp:283-287 copies it whole)");
-  // every unconditional access of every cell inside apply.bounds (and the result) must stay inside its input's box
-  for (int k = 0; k < NIN; ++k)
-    for (int d = 0; d < R; ++d) {
-      if (top_reach.hi[k][d] < top_reach.lo[k][d]) continue;
-      const int64_t p0 = bounds.lb[d] > result_box.lb[d] ? bounds.lb[d] : result_box.lb[d];
-      const int64_t p1 = bounds.ub[d] < result_box.ub[d] ? bounds.ub[d] : result_box.ub[d];
-      bool empty = false;
-      for (int e = 0; e < R; ++e) {
-        const int64_t a = bounds.lb[e] > result_box.lb[e] ? bounds.lb[e] : result_box.lb[e];
-        const int64_t b = bounds.ub[e] < result_box.ub[e] ? bounds.ub[e] : result_box.ub[e];
-        empty = empty || b <= a;
-      }
-      if (empty) continue;
-      if (p0 + top_reach.lo[k][d] < in[k]->box.lb[d] || p1 - 1 + top_reach.hi[k][d] >= in[k]->box.ub[d])
-        die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
-                       "DataflowLowering.cpp:380-410); refusing to run it");
-    }
-  bool direct = dest != nullptr && dest->count == result_box.count();
-  for (int k = 0; direct && k < NIN; ++k) direct = !overlaps(*dest, *in[k]);
-  Val out;
-  if (direct) {
-    out = *dest;
-    out.box = result_box;
-  } else {
-    out = sc.alloc(result_box, (int)sizeof(T));
-  }
-  out.stale_ghosts = sc.has_ghosts() && !whole_local;
-  sc.wait_pending();
-  neptune_hip::NdParams<T, NIN> P{};
-  P.out = static_cast<T*>(out.dev);
-  P.inner = 1;
-  for (int d = 0; d < R; ++d) {
-    P.n[d] = result_box.ub[d] - result_box.lb[d];
-    P.olb[d] = result_box.lb[d];
-    P.lb[d] = bounds.lb[d];
-    P.ub[d] = bounds.ub[d];
-    if (d > 0) P.inner *= P.n[d];
-  }
-  for (int k = 0; k < NIN; ++k) {
-    P.in[k] = static_cast<const T*>(in[k]->dev);
-    for (int d = 0; d < R; ++d) {
-      P.m[k][d] = in[k]->box.ub[d] - in[k]->box.lb[d];
-      P.sh[k][d] = result_box.lb[d] - in[k]->box.lb[d];
-    }
-  }
-  P.r0 = 0;
-  P.r1 = P.n[0];
-  const int64_t total = (P.r1 - P.r0) * P.inner;
-  if (total > 0) {
-    const int64_t blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffLL) die(sc.name(), "neptune_ir.apply of rank > 3: the grid is not launchable");
-    hipLaunchKernelGGL((neptune_hip::neptune_apply_nd<Body, T, R, NIN>), neptune_hip::grid_for_blocks(blocks), dim3(256), 0, sc.stream(), P,
-                       body);
-    NEPTUNE_HIP_CHECK(hipGetLastError());
-    neptune_hip_note_launch(NEPTUNE_HIP_KERNEL_DIRECT, -1, 0);
-  }
-  if (direct) sc.mark_dirty(*dest);
-  return out;
 }
 
 // rank 4..6 helpers: the leading R-3 dimensions of a box as a flat range of multi-indices, and the rank-3 sub-box / offset of
@@ -683,6 +523,126 @@ inline void for_each_lead(const Box& range, F&& f) {   // every leading multi-in
     }
     f(idx);
   }
+}
+
+// One neptune_ir.apply of rank R = 4..6 whose accesses have no offset along the leading R-3 dimensions (batch / component
+// dimensions; the reference's lowering is rank-generic, DataflowLowering.cpp:268-270, 301-308): for every leading index one
+// rank-3 apply on the contiguous sub-field -- inside the leading bounds the body (which sees the leading indices as members
+// `lead[]`), outside them the copy-through of input 0 (DataflowLowering.cpp:283-287).  Every input must cover the result's
+// leading extent.  Slab mode: dim 0, the slab axis, is a leading dimension here, so the apply never reaches into a
+// neighbouring plane: every rank runs its own leading indices (and the ghost planes too when its inputs' ghosts are good,
+// like run_apply with halo0 == 0).
+template <class Body, class T, int R, int NIN, class FP>
+inline Val run_apply_batched(Scope& sc, Body body, const Box& result_global, const Box& bounds_decl, const Val* const* in,
+                             const neptune_hip::Reach& top_radius, const Val* dest) {
+  static_assert(R > 3 && R <= kMaxBoxRank, "run_apply_batched: rank 4..6");
+  constexpr int L = R - 3;
+  const bool whole_local = whole_local_or_die(sc, in, NIN, 0, nullptr);   // no offset along dim 0: nothing to refuse
+  const Box result_decl = sc.local_box(result_global);
+  const Box bounds = sc.owned_bounds(bounds_decl, whole_local);
+  const Box out3 = last3(result_decl), bnd3 = last3(bounds);
+  for (int k = 0; k < NIN; ++k) {
+    if (in[k]->box.rank != R) die(sc.name(), "neptune_ir.apply: input rank differs from the result's");
+    for (int d = 0; d < L; ++d)
+      if (in[k]->box.lb[d] > result_decl.lb[d] || in[k]->box.ub[d] < result_decl.ub[d])
+        die(sc.name(), "neptune_ir.apply of rank > 3: an input does not cover the result's leading extent");
+  }
+  bool direct;
+  Val out = place_result(sc, dest, result_decl, (int)sizeof(T), in, NIN, &direct);
+  out.stale_ghosts = sc.has_ghosts() && !whole_local;
+  sc.wait_pending();
+  Val sub[NIN];
+  const Val* subp[NIN];
+  const void* ptrs[NIN];
+  for_each_lead(result_decl, [&](const int64_t* idx) {
+    bool inside = true;
+    for (int d = 0; d < L; ++d) inside = inside && idx[d] >= bounds.lb[d] && idx[d] < bounds.ub[d];
+    for (int k = 0; k < NIN; ++k) {   // every input covers the result's leading extent (checked above): no offset is -1
+      sub[k] = *in[k];
+      sub[k].box = last3(in[k]->box);
+      sub[k].count = sub[k].box.count();
+      sub[k].dev = static_cast<char*>(in[k]->dev) + lead_offset_cells(in[k]->box, idx) * (int64_t)sizeof(T);
+      subp[k] = &sub[k];
+      ptrs[k] = sub[k].dev;
+    }
+    void* outp = static_cast<char*>(out.dev) + lead_offset_cells(result_decl, idx) * (int64_t)sizeof(T);
+    neptune_hip_apply_geom_t g;
+    Box b3 = bnd3;
+    if (!inside) { for (int d = 0; d < 3; ++d) b3.ub[d] = b3.lb[d]; }   // zero trips: the kernel writes the copy-through only
+    fill_geom(g, out3, b3, subp, NIN);
+    check_radius_or_die(sc, inside ? geom_check_radius(&g, top_radius) : geom_validate(&g));
+    for (int d = 0; d < L; ++d) body.lead[d] = idx[d];
+    if (launch_apply<Body, T, 3, NIN, FP>(body, &g, ptrs, outp, sc.stream(), launch_override()) != NEPTUNE_HIP_OK)
+      die(sc.name(), "neptune_ir.apply launch rejected");
+  });
+  if (direct) sc.mark_dirty(*dest);
+  return out;
+}
+
+// One neptune_ir.apply of rank R = 4..6 with offsets along its leading dimensions: a stencil in more than three dimensions
+// (kernels/apply_nd.hpp).  Same contract as run_apply, slab mode included (dim 0 is the slab axis whatever the rank); the
+// launch is not split around a pending halo exchange, it waits for it.
+template <class Body, class T, int R, int NIN>
+inline Val run_apply_nd(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
+                        const neptune_hip::ReachN& top_reach, const Val* dest, int halo0 = 0) {
+  static_assert(R > 3 && R <= kMaxBoxRank && R <= neptune_hip::kNdMaxRank, "run_apply_nd: rank 4..6");
+  const bool whole_local = whole_local_or_die(sc, in, NIN, halo0, kStaleGhostRefusal);
+  const Box result_box = sc.local_box(result_decl);
+  const Box bounds = sc.owned_bounds(bounds_decl, whole_local);
+  if (result_box.rank != R || bounds.rank != R) die(sc.name(), "malformed neptune_ir.apply geometry");
+  for (int k = 0; k < NIN; ++k)
+    if (in[k]->box.rank != R) die(sc.name(), "neptune_ir.apply: input rank differs from the result's");
+  if (!in[0]->box.same_shape(result_box))
+    die(sc.name(), "neptune_ir.apply: input 0 does not have the result's shape (DataflowLowering.cpp:283-287 copies it whole)");
+  // every unconditional access of every cell inside apply.bounds (and the result) must stay inside its input's box
+  for (int k = 0; k < NIN; ++k)
+    for (int d = 0; d < R; ++d) {
+      if (top_reach.hi[k][d] < top_reach.lo[k][d]) continue;
+      const int64_t p0 = bounds.lb[d] > result_box.lb[d] ? bounds.lb[d] : result_box.lb[d];
+      const int64_t p1 = bounds.ub[d] < result_box.ub[d] ? bounds.ub[d] : result_box.ub[d];
+      bool empty = false;
+      for (int e = 0; e < R; ++e) {
+        const int64_t a = bounds.lb[e] > result_box.lb[e] ? bounds.lb[e] : result_box.lb[e];
+        const int64_t b = bounds.ub[e] < result_box.ub[e] ? bounds.ub[e] : result_box.ub[e];
+        empty = empty || b <= a;
+      }
+      if (empty) continue;
+      if (p0 + top_reach.lo[k][d] < in[k]->box.lb[d] || p1 - 1 + top_reach.hi[k][d] >= in[k]->box.ub[d]) die_oob(sc);
+    }
+  bool direct;
+  Val out = place_result(sc, dest, result_box, (int)sizeof(T), in, NIN, &direct);
+  out.stale_ghosts = sc.has_ghosts() && !whole_local;
+  sc.wait_pending();
+  neptune_hip::NdParams<T, NIN> P{};
+  P.out = static_cast<T*>(out.dev);
+  P.inner = 1;
+  for (int d = 0; d < R; ++d) {
+    P.n[d] = result_box.ub[d] - result_box.lb[d];
+    P.olb[d] = result_box.lb[d];
+    P.lb[d] = bounds.lb[d];
+    P.ub[d] = bounds.ub[d];
+    if (d > 0) P.inner *= P.n[d];
+  }
+  for (int k = 0; k < NIN; ++k) {
+    P.in[k] = static_cast<const T*>(in[k]->dev);
+    for (int d = 0; d < R; ++d) {
+      P.m[k][d] = in[k]->box.ub[d] - in[k]->box.lb[d];
+      P.sh[k][d] = result_box.lb[d] - in[k]->box.lb[d];
+    }
+  }
+  P.r0 = 0;
+  P.r1 = P.n[0];
+  const int64_t total = (P.r1 - P.r0) * P.inner;
+  if (total > 0) {
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) die(sc.name(), "neptune_ir.apply of rank > 3: the grid is not launchable");
+    hipLaunchKernelGGL((neptune_hip::neptune_apply_nd<Body, T, R, NIN>), neptune_hip::grid_for_blocks(blocks), dim3(256), 0, sc.stream(), P,
+                       body);
+    NEPTUNE_HIP_CHECK(hipGetLastError());
+    neptune_hip_note_launch(NEPTUNE_HIP_KERNEL_DIRECT, -1, 0);
+  }
+  if (direct) sc.mark_dirty(*dest);
+  return out;
 }
 
 // neptune_ir.store (DataflowLowering.cpp:165-220)
@@ -737,14 +697,9 @@ template <class T>
 inline Val run_euler_axpy_flat(Scope& sc, T dt, const Val& state, const Val& k, const Val* dest) {
   if (!state.box.same_shape(k.box) || state.count != k.count)
     die(sc.name(), "neptune_ir.time_advance: rhs(state) does not have the state's shape");
-  bool direct = dest != nullptr && dest->count == state.count && !overlaps(*dest, state) && !overlaps(*dest, k);
-  Val out;
-  if (direct) {
-    out = *dest;
-    out.box = state.box;
-  } else {
-    out = sc.alloc(state.box, (int)sizeof(T));
-  }
+  const Val* const operands[2] = {&state, &k};
+  bool direct;
+  Val out = place_result(sc, dest, state.box, (int)sizeof(T), operands, 2, &direct);
   out.stale_ghosts = state.stale_ghosts || k.stale_ghosts;
   sc.wait_pending();
   if (state.count > 0) {
@@ -768,10 +723,6 @@ inline Val run_euler_axpy_flat(Scope& sc, T dt, const Val& state, const Val& k, 
 inline const char* reduce_kind_name(int kind) {
   static const char* const names[] = {"sum", "max", "min", "l1", "l2"};
   return kind >= 0 && kind < 5 ? names[kind] : "?";
-}
-// what a reduce over no cells returns: the kind's identity
-inline double reduce_identity(int kind) {
-  return kind == NEPTUNE_HIP_REDUCE_MAX ? -__builtin_huge_val() : (kind == NEPTUNE_HIP_REDUCE_MIN ? __builtin_huge_val() : 0.0);
 }
 // Slab mode combines the ranks' results by adding them (neptune_hip.slab): right for "sum" alone -- max and min need
 // another combine and l2 is not additive at all -- so every other kind refuses to run on a slab.
@@ -846,19 +797,13 @@ inline double run_apply_reduce_op(Scope& sc, int kind, const Body& body, const B
                                   const Box* reduce_decl) {
   refuse_slab_reduce(sc, kind);
   sc.wait_pending();
-  for (int k = 0; k < NIN; ++k)
-    if (sc.has_ghosts() && halo0 > 0 && in[k]->stale_ghosts)
-      die(sc.name(), "slab mode: neptune_ir.apply reads neighbouring planes of a value computed inside this call");
+  whole_local_or_die(sc, in, NIN, halo0, "slab mode: neptune_ir.apply reads neighbouring planes of a value computed inside this call");
   const Box result_box = sc.local_box(result_decl);
   const Box bounds = sc.owned_bounds(bounds_decl);
   const Box red = sc.owned_bounds(reduce_decl ? *reduce_decl : result_decl);
   neptune_hip_apply_geom_t g;
   fill_geom(g, result_box, bounds, in, NIN);
-  int rc = geom_check_radius(&g, top_radius);
-  if (rc == NEPTUNE_HIP_EOOB)
-    die(sc.name(), "neptune_ir.apply reads outside an input's bounds (undefined behaviour in the reference lowering, "
-                   "DataflowLowering.cpp:380-410); refusing to run it");
-  if (rc != NEPTUNE_HIP_OK) die(sc.name(), "malformed neptune_ir.apply geometry");
+  check_radius_or_die(sc, geom_check_radius(&g, top_radius));
   int64_t cells = 1;
   for (int d = 0; d < RANK; ++d) {
     const int64_t e = red.ub[d] - red.lb[d];
@@ -874,48 +819,13 @@ inline double run_apply_reduce_op(Scope& sc, int kind, const Body& body, const B
   for (int k = 0; k < NIN; ++k) ptrs[k] = in[k]->dev;
   DirectParams<T, NIN> P{};
   fill_direct_params<T, RANK, NIN>(&g, ptrs, nullptr, P);
-  const int64_t eK = P.rub[2] - P.rlb[2];
+  constexpr bool kPointwise = FP::MARCH_OK && FP::HALO_MASK == 0u;
+  const ReduceApplyPlan pl = plan_reduce_apply(P, ptrs, kPointwise);
   // the kernel keeps coordinates and row indices in 32 bits
-  const int64_t lim = 0x7fffff00LL;
-  bool narrow = P.n[0] * P.n[1] < lim && P.n[2] < lim;
-  for (int k = 0; k < NIN; ++k) {
-    narrow = narrow && P.m[k][0] * P.m[k][1] < lim && P.m[k][2] < lim;
-    for (int ax = 0; ax < 3; ++ax) narrow = narrow && P.sh[k][ax] > -lim && P.sh[k][ax] < lim;
-  }
-  if (!narrow) die(sc.name(), "neptune_ir.reduce of an apply: fields with 2^31 rows or 2^31 cells per row are not supported");
+  if (!pl.narrow) die(sc.name(), "neptune_ir.reduce of an apply: fields with 2^31 rows or 2^31 cells per row are not supported");
   T* part = static_cast<T*>(neptune_hip_reduce_workspace());
-  // pointwise body on 16-byte-aligned rows with all inputs in the result's box: the vector kernel
-  constexpr int VK = 16 / (int)sizeof(T);
-  bool vec = FP::MARCH_OK && FP::HALO_MASK == 0u && eK % VK == 0 && P.rlb[2] % VK == 0 && P.n[2] % VK == 0;
-  for (int k = 0; k < NIN; ++k) {
-    vec = vec && ((uintptr_t)ptrs[k] % 16 == 0);
-    for (int ax = 0; ax < 3; ++ax) vec = vec && P.sh[k][ax] == 0 && P.m[k][ax] == P.n[ax];
-  }
-  const int cells_per_chunk = 256 * (vec ? VK : 1), iter = vec ? kReduceApplyIter / 2 : kReduceApplyIter;
-  const int64_t nchunk = (eK + cells_per_chunk - 1) / cells_per_chunk;
-  const int64_t trips = ((P.rub[0] - P.rlb[0]) * (P.rub[1] - P.rlb[1]) * nchunk + iter - 1) / iter;
-  const int blocks = (int)(trips < kReduceBlocks ? trips : kReduceBlocks);
-  if constexpr (FP::MARCH_OK && FP::HALO_MASK == 0u) {
-    if (vec)
-      hipLaunchKernelGGL((neptune_reduce_apply_vec<Body, T, RANK, NIN, POp>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
-  } else {
-    vec = false;
-  }
-  // the sum is the kernels' default op: its launch keeps the spelling tests/reduce_cases.py mirrors (MIRRORED), which is
-  // the same specialisation as <..., RedSum<T>>
-  if constexpr (std::is_same<POp, neptune_hip::RedSum<T>>::value) {
-    if (!vec)
-      hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
-  } else {
-    if (!vec)
-      hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN, POp>), dim3(blocks), dim3(256), 0, sc.stream(), P, body, nchunk, part);
-  }
-  hipLaunchKernelGGL((neptune_reduce_final<T, FOp>), dim3(1), dim3(256), 0, sc.stream(), part, blocks, part + kReduceBlocks);
-  NEPTUNE_HIP_CHECK(hipGetLastError());
-  T h = 0;
-  NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, part + kReduceBlocks, sizeof(T), hipMemcpyDeviceToHost, sc.stream()));
-  NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream()));
-  return (double)h;
+  launch_reduce_apply<POp, FOp, kPointwise, Body, T, RANK, NIN>(pl, P, body, part, part + kReduceBlocks, sc.stream());
+  return read_back(part + kReduceBlocks, sc.stream());
 }
 template <class Body, class T, int RANK, int NIN, class FP>
 inline double run_apply_reduce_sum(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl,
@@ -930,12 +840,9 @@ template <int KIND, class Body, class T, int RANK, int NIN, class FP>
 inline double run_apply_reduce(Scope& sc, const Body& body, const Box& result_decl, const Box& bounds_decl, const Val* const* in,
                                const neptune_hip::Reach& top_radius, int halo0, const Box* reduce_decl) {
   static_assert(KIND >= NEPTUNE_HIP_REDUCE_SUM && KIND <= NEPTUNE_HIP_REDUCE_L2, "unknown reduce kind");
-  using POp = std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_MAX, RedMax<T>,
-              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_MIN, RedMin<T>,
-              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L1, RedL1<T>,
-              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L2, RedSumSq<T>, RedSum<T>>>>>;
-  using FOp = std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L2, RedSqrtSum<T>,
-              std::conditional_t<KIND == NEPTUNE_HIP_REDUCE_L1, RedSum<T>, POp>>;
+  using Ops = neptune_hip::ReduceOps<KIND, T>;
+  using POp = typename Ops::POp;
+  using FOp = typename Ops::FOp;
   return run_apply_reduce_op<POp, FOp, Body, T, RANK, NIN, FP>(sc, KIND, body, result_decl, bounds_decl, in, top_radius, halo0,
                                                                 reduce_decl);
 }

@@ -19,7 +19,7 @@
 
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"
-#include "../kernels/reduce_apply.hpp"
+#include "../kernels/reduce_launch.hpp"
 #include "../kernels/util_kernels.hpp"
 #include "rt_bodies.hpp"
 
@@ -223,35 +223,23 @@ int update_norm(const neptune_hip_apply_geom_t* g, const void* a, const void* b,
     case 2: fill_direct_params<T, 2, 2>(&g2, ptrs, nullptr, P); break;
     default: fill_direct_params<T, 3, 2>(&g2, ptrs, nullptr, P); break;
   }
-  const int64_t lim = 0x7fffff00LL;
-  bool narrow = P.n[0] * P.n[1] < lim && P.n[2] < lim;
-  for (int k = 0; k < 2; ++k) {
-    narrow = narrow && P.m[k][0] * P.m[k][1] < lim && P.m[k][2] < lim;
-    for (int ax = 0; ax < 3; ++ax) narrow = narrow && P.sh[k][ax] > -lim && P.sh[k][ax] < lim;
-  }
-  if (!narrow) return NEPTUNE_HIP_EUNSUPPORTED;   // the kernels keep coordinates and row indices in 32 bits
-  constexpr int VK = 16 / (int)sizeof(T);
-  const int64_t eK = P.rub[2] - P.rlb[2];
-  bool vec = eK % VK == 0 && P.rlb[2] % VK == 0 && P.n[2] % VK == 0;
-  for (int k = 0; k < 2; ++k) {
-    vec = vec && ((uintptr_t)ptrs[k] % 16 == 0);
-    for (int ax = 0; ax < 3; ++ax) vec = vec && P.sh[k][ax] == 0 && P.m[k][ax] == P.n[ax];
-  }
-  const int cells_per_chunk = 256 * (vec ? VK : 1), iter = vec ? kReduceApplyIter / 2 : kReduceApplyIter;
-  const int64_t nchunk = (eK + cells_per_chunk - 1) / cells_per_chunk;
-  const int64_t trips = ((P.rub[0] - P.rlb[0]) * (P.rub[1] - P.rlb[1]) * nchunk + iter - 1) / iter;
-  const int blocks = (int)(trips < kReduceBlocks ? trips : kReduceBlocks);
-  T* part = static_cast<T*>(rt().reduce_ws);
-  if (vec) hipLaunchKernelGGL((neptune_reduce_apply_vec<DiffSquared<T>, T, 3, 2>), dim3(blocks), dim3(256), 0, st, P, DiffSquared<T>{}, nchunk, part);
-  else hipLaunchKernelGGL((neptune_reduce_apply<DiffSquared<T>, T, 3, 2>), dim3(blocks), dim3(256), 0, st, P, DiffSquared<T>{}, nchunk, part);
-  hipLaunchKernelGGL(neptune_reduce_final<T>, dim3(1), dim3(256), 0, st, part, blocks, static_cast<T*>(sum_out));
-  NEPTUNE_HIP_CHECK(hipGetLastError());
+  const ReduceApplyPlan pl = plan_reduce_apply(P, ptrs, true);
+  if (!pl.narrow) return NEPTUNE_HIP_EUNSUPPORTED;   // the kernels keep coordinates and row indices in 32 bits
+  launch_reduce_apply<RedSum<T>, RedSum<T>, true, DiffSquared<T>, T, 3, 2>(pl, P, DiffSquared<T>{}, static_cast<T*>(rt().reduce_ws),
+                                                                          static_cast<T*>(sum_out), st);
   return NEPTUNE_HIP_OK;
 }
 }  // namespace
 
-// ---- neptune_ir.reduce: what neptune_hip_reduce_sum / neptune_hip_reduce share
+// ---- neptune_ir.reduce: the plan and the launch behind neptune_hip_reduce
 namespace {
+// per-rank arrays -> the kernels' (I,J,K) order; absent axes take `f`
+void to_axes3(int rank, const int64_t* a, int64_t* o, int64_t f) {
+  o[0] = o[1] = o[2] = f;
+  if (rank == 3) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
+  else if (rank == 2) { o[0] = a[0]; o[2] = a[1]; }
+  else { o[2] = a[0]; }
+}
 // the checks and the launch geometry every kind shares: which first-pass kernel, how many workgroups, the box
 struct ReducePlan {
   bool whole;
@@ -286,15 +274,9 @@ int reduce_plan(int dtype, int rank, const void* src, const int64_t* src_lb, con
     const int64_t trips = ((total / (last ? last : 1)) * ((last + cells - 1) / cells) + 3) / 4;
     blocks = (int)(trips < kReduceBlocks ? (trips < 1 ? 1 : trips) : kReduceBlocks);
   }
-  auto fill = [&](const int64_t* a, int64_t* o, int64_t f) {
-    o[0] = o[1] = o[2] = f;
-    if (rank == 3) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
-    else if (rank == 2) { o[0] = a[0]; o[2] = a[1]; }
-    else { o[2] = a[0]; }
-  };
-  fill(ext, pl.P.ext, 1);
-  fill(off, pl.P.off, 0);
-  fill(shp, pl.P.shape, 1);
+  to_axes3(rank, ext, pl.P.ext, 1);
+  to_axes3(rank, off, pl.P.off, 0);
+  to_axes3(rank, shp, pl.P.shape, 1);
   pl.whole = whole;
   pl.blocks = blocks;
   pl.total = total;
@@ -302,30 +284,32 @@ int reduce_plan(int dtype, int rank, const void* src, const int64_t* src_lb, con
   return NEPTUNE_HIP_OK;
 }
 
-// a kind other than "sum": the first pass on POp, the root on FOp (POp's combine, the identity map, the kind's finish)
+// the first pass on POp, the root on FOp (POp's combine, the identity map, the kind's finish), the result read back
 template <class T, class POp, class FOp>
 int reduce_launch(const ReducePlan& pl, const void* src, double* result, hipStream_t st) {
   T* part = static_cast<T*>(rt().reduce_ws);
   if (pl.whole) hipLaunchKernelGGL((neptune_reduce_partial_flat<T, POp>), dim3(pl.blocks), dim3(256), 0, st, (const T*)src, pl.count, part);
   else hipLaunchKernelGGL((neptune_reduce_partial_box<T, POp>), dim3(pl.blocks), dim3(256), 0, st, (const T*)src, pl.P, part);
-  hipLaunchKernelGGL((neptune_reduce_final<T, FOp>), dim3(1), dim3(256), 0, st, part, pl.blocks, part + kReduceBlocks);
-  NEPTUNE_HIP_CHECK(hipGetLastError());
-  T h = 0;
-  NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, part + kReduceBlocks, sizeof(T), hipMemcpyDeviceToHost, st));
-  NEPTUNE_HIP_CHECK(hipStreamSynchronize(st));
-  *result = (double)h;   // the widening keeps NaN, +-inf and -0
+  launch_reduce_root<T, FOp>(part, pl.blocks, part + kReduceBlocks, st);
+  *result = read_back(part + kReduceBlocks, st);
   return NEPTUNE_HIP_OK;
+}
+// kind / raw -> the ops of the kind table (ReduceOps, util_kernels.hpp)
+template <class T, int KIND, bool RAW = false>
+int reduce_as(const ReducePlan& pl, const void* src, double* result, hipStream_t st) {
+  using Ops = ReduceOps<KIND, T, RAW>;
+  return reduce_launch<T, typename Ops::POp, typename Ops::FOp>(pl, src, result, st);
 }
 template <class T>
 int reduce_kind(int kind, bool raw, const ReducePlan& pl, const void* src, double* result, hipStream_t st) {
   switch (kind) {
-    case NEPTUNE_HIP_REDUCE_MAX: return reduce_launch<T, RedMax<T>, RedMax<T>>(pl, src, result, st);
-    case NEPTUNE_HIP_REDUCE_MIN: return reduce_launch<T, RedMin<T>, RedMin<T>>(pl, src, result, st);
-    case NEPTUNE_HIP_REDUCE_L1: return reduce_launch<T, RedL1<T>, RedSum<T>>(pl, src, result, st);
+    case NEPTUNE_HIP_REDUCE_SUM: return reduce_as<T, NEPTUNE_HIP_REDUCE_SUM>(pl, src, result, st);
+    case NEPTUNE_HIP_REDUCE_MAX: return reduce_as<T, NEPTUNE_HIP_REDUCE_MAX>(pl, src, result, st);
+    case NEPTUNE_HIP_REDUCE_MIN: return reduce_as<T, NEPTUNE_HIP_REDUCE_MIN>(pl, src, result, st);
+    case NEPTUNE_HIP_REDUCE_L1: return reduce_as<T, NEPTUNE_HIP_REDUCE_L1>(pl, src, result, st);
     default: break;
   }
-  if (raw) return reduce_launch<T, RedSumSq<T>, RedSum<T>>(pl, src, result, st);
-  return reduce_launch<T, RedSumSq<T>, RedSqrtSum<T>>(pl, src, result, st);
+  return raw ? reduce_as<T, NEPTUNE_HIP_REDUCE_L2, true>(pl, src, result, st) : reduce_as<T, NEPTUNE_HIP_REDUCE_L2>(pl, src, result, st);
 }
 }  // namespace
 
@@ -702,17 +686,11 @@ int neptune_hip_store_box(int dtype, int rank, const void* src, const int64_t* s
       return NEPTUNE_HIP_EOOB;
   }
   BoxCopyParams P;
-  auto fill = [&](const int64_t* a, int64_t* o, int64_t f) {
-    o[0] = o[1] = o[2] = f;
-    if (rank == 3) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
-    else if (rank == 2) { o[0] = a[0]; o[2] = a[1]; }
-    else { o[2] = a[0]; }
-  };
-  fill(ext, P.ext, 1);
-  fill(soff, P.soff, 0);
-  fill(doff, P.doff, 0);
-  fill(ss, P.sshape, 1);
-  fill(ds, P.dshape, 1);
+  to_axes3(rank, ext, P.ext, 1);
+  to_axes3(rank, soff, P.soff, 0);
+  to_axes3(rank, doff, P.doff, 0);
+  to_axes3(rank, ss, P.sshape, 1);
+  to_axes3(rank, ds, P.dshape, 1);
   const int64_t total = P.ext[0] * P.ext[1] * P.ext[2];
   if (total == 0) return NEPTUNE_HIP_OK;
   // one workgroup per chunk of 256 lanes x 16 bytes of one row of the box (see the kernel)
@@ -738,42 +716,7 @@ void* neptune_hip_reduce_workspace(void) {
 
 int neptune_hip_reduce_sum(int dtype, int rank, const void* src, const int64_t* src_lb, const int64_t* src_ub,
                            const int64_t* lb, const int64_t* ub, double* result, void* stream) {
-  ReducePlan pl;
-  const int rc = reduce_plan(dtype, rank, src, src_lb, src_ub, lb, ub, result, pl);
-  if (rc != NEPTUNE_HIP_OK) return rc;
-  if (pl.total == 0) {  // empty domain: the reference's loop never runs, the accumulator stays 0
-    *result = 0.0;
-    return NEPTUNE_HIP_OK;
-  }
-  ensure_init();
-  RuntimeState& s = rt();
-  hipStream_t st = as_stream(stream);
-  const bool whole = pl.whole;
-  const int blocks = pl.blocks;
-  const int64_t count = pl.count;
-  const ReduceBoxParams& P = pl.P;
-  if (dtype == NEPTUNE_HIP_F64) {
-    double* part = (double*)s.reduce_ws;
-    if (whole) hipLaunchKernelGGL(neptune_reduce_partial_flat<double>, dim3(blocks), dim3(256), 0, st, (const double*)src, count, part);
-    else hipLaunchKernelGGL(neptune_reduce_partial_box<double>, dim3(blocks), dim3(256), 0, st, (const double*)src, P, part);
-    hipLaunchKernelGGL(neptune_reduce_final<double>, dim3(1), dim3(256), 0, st, part, blocks, part + kReduceBlocks);
-    NEPTUNE_HIP_CHECK(hipGetLastError());
-    double h = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, part + kReduceBlocks, sizeof(double), hipMemcpyDeviceToHost, st));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(st));
-    *result = h;
-  } else {
-    float* part = (float*)s.reduce_ws;
-    if (whole) hipLaunchKernelGGL(neptune_reduce_partial_flat<float>, dim3(blocks), dim3(256), 0, st, (const float*)src, count, part);
-    else hipLaunchKernelGGL(neptune_reduce_partial_box<float>, dim3(blocks), dim3(256), 0, st, (const float*)src, P, part);
-    hipLaunchKernelGGL(neptune_reduce_final<float>, dim3(1), dim3(256), 0, st, part, blocks, part + kReduceBlocks);
-    NEPTUNE_HIP_CHECK(hipGetLastError());
-    float h = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, part + kReduceBlocks, sizeof(float), hipMemcpyDeviceToHost, st));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(st));
-    *result = (double)h;
-  }
-  return NEPTUNE_HIP_OK;
+  return neptune_hip_reduce(NEPTUNE_HIP_REDUCE_SUM, dtype, rank, src, src_lb, src_ub, lb, ub, result, stream);
 }
 
 int neptune_hip_reduce(int kind_flags, int dtype, int rank, const void* src, const int64_t* src_lb, const int64_t* src_ub,
@@ -781,18 +724,16 @@ int neptune_hip_reduce(int kind_flags, int dtype, int rank, const void* src, con
   const bool raw = (kind_flags & NEPTUNE_HIP_REDUCE_RAW) != 0;
   const int kind = kind_flags & ~NEPTUNE_HIP_REDUCE_RAW;
   if (kind < NEPTUNE_HIP_REDUCE_SUM || kind > NEPTUNE_HIP_REDUCE_L2) return NEPTUNE_HIP_EINVAL;
-  if (kind == NEPTUNE_HIP_REDUCE_SUM) return neptune_hip_reduce_sum(dtype, rank, src, src_lb, src_ub, lb, ub, result, stream);
   ReducePlan pl;
   const int rc = reduce_plan(dtype, rank, src, src_lb, src_ub, lb, ub, result, pl);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  if (pl.total == 0) {  // empty domain: the accumulator stays at the kind's identity
-    *result = kind == NEPTUNE_HIP_REDUCE_MAX ? -HUGE_VAL : (kind == NEPTUNE_HIP_REDUCE_MIN ? HUGE_VAL : 0.0);
+  if (pl.total == 0) {  // empty domain: the reference's loop never runs, the accumulator stays at the kind's identity (sum: 0)
+    *result = reduce_identity(kind);
     return NEPTUNE_HIP_OK;
   }
   ensure_init();
   hipStream_t st = as_stream(stream);
-  if (dtype == NEPTUNE_HIP_F64) return reduce_kind<double>(kind, raw, pl, src, result, st);
-  return reduce_kind<float>(kind, raw, pl, src, result, st);
+  return dtype == NEPTUNE_HIP_F64 ? reduce_kind<double>(kind, raw, pl, src, result, st) : reduce_kind<float>(kind, raw, pl, src, result, st);
 }
 
 // ---------------------------------------------------------------- Krylov vector updates

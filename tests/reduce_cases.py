@@ -145,7 +145,7 @@ def fused_sentinel_masks(result_box, bounds, reduce_box, input_boxes, footprints
 
 # ---- launch geometry and tree height ------------------------------------------------------------------------------
 def plain_path(shape, box, aligned=True):
-    """the first-pass kernel neptune_hip_reduce_sum picks (csrc/runtime/neptune_hip_rt.hip:825, `whole`): the flat
+    """the first-pass kernel neptune_hip_reduce picks (reduce_plan in csrc/runtime/neptune_hip_rt.hip, `whole`): the flat
     kernel for the whole buffer at a 16-byte-aligned base, the box kernel otherwise"""
     lo, hi = box if box is not None else ((0,) * len(shape), tuple(shape))
     whole = all(l == 0 and h == n for l, h, n in zip(lo, hi, shape)) and aligned
@@ -153,8 +153,8 @@ def plain_path(shape, box, aligned=True):
 
 
 def fused_path(dtype, pointwise, result_shape, reduce_lo, reduce_hi, inputs_share_result_box):
-    """the first-pass kernel run_apply_reduce_sum picks (csrc/runtime/lowered_runtime.hpp:776-780, `vec`): the vector
-    kernel for a pointwise body (FP::MARCH_OK && FP::HALO_MASK == 0) when eK, the reduced box's first K index and the row
+    """the first-pass kernel a fused reduce(apply) picks (plan_reduce_apply in csrc/kernels/reduce_launch.hpp, `vec`): the
+    vector kernel for a pointwise body (run_apply_reduce_op: FP::MARCH_OK && FP::HALO_MASK == 0) when eK, the reduced box's first K index and the row
     length are multiples of VK and every input is 16-byte aligned and has the result's box (sh == 0, m == n); all
     coordinates here are result-physical, K the last axis"""
     v = VK[np.dtype(dtype)]
@@ -168,34 +168,43 @@ def launch_blocks(path, dtype, ext):
     v = VK[np.dtype(dtype)]
     total = int(np.prod(ext))
     rows, last = total // max(ext[-1], 1), ext[-1]
-    if path == "flat":          # neptune_hip_rt.hip:836, min(ceil(total / 256), kReduceBlocks)
+    if path == "flat":          # reduce_plan: min(ceil(total / 256), kReduceBlocks)
         return min(_cdiv(total, 256), K_REDUCE_BLOCKS)
-    if path == "box":           # neptune_hip_rt.hip:837-841, !whole: trips of 4 chunks of 256 * VK cells
+    if path == "box":           # reduce_plan, !whole: trips of 4 chunks of 256 * VK cells
         trips = _cdiv(rows * _cdiv(last, 256 * v), 4)
         return min(max(trips, 1), K_REDUCE_BLOCKS)
     cells, it = (256 * v, K_REDUCE_APPLY_ITER // 2) if path == "fused_vec" else (256, K_REDUCE_APPLY_ITER)
-    trips = _cdiv(rows * _cdiv(last, cells), it)     # lowered_runtime.hpp:781-784
+    trips = _cdiv(rows * _cdiv(last, cells), it)     # plan_reduce_apply
     return min(trips, K_REDUCE_BLOCKS)
 
 
 # The host and kernel lines the functions above restate, verbatim (paths relative to neptune-pde-solver_amd/csrc).
 # tests/test_reduce_cases.py checks that each is still there, so a change to the kernel choice, the grid or the
-# loop structure fails a CPU test until this mirror is brought up to date with it.
-MIRRORED = [
+# loop structure fails a CPU test until this mirror is brought up to date with it.  A host rule has ONE home: each line
+# of MIRRORED_HOST must occur in no other file under csrc and only once in its own, so a second copy of a launch rule,
+# which could drift from the mirrored one with every test green, fails that test too.
+MIRRORED_HOST = [
+    # the plain reduce: reduce_plan (the kernel choice `whole`, the grid) and reduce_launch
     ("runtime/neptune_hip_rt.hip", "whole = whole && off[d] == 0 && ext[d] == shp[d] && ((uintptr_t)src % 16 == 0);"),
     ("runtime/neptune_hip_rt.hip", "int blocks = (int)((total + 255) / 256 < kReduceBlocks ? (total + 255) / 256 : kReduceBlocks);"),
     ("runtime/neptune_hip_rt.hip", "const int64_t cells = 256 * (dtype == NEPTUNE_HIP_F64 ? 2 : 4);"),
     ("runtime/neptune_hip_rt.hip", "const int64_t trips = ((total / (last ? last : 1)) * ((last + cells - 1) / cells) + 3) / 4;"),
     ("runtime/neptune_hip_rt.hip", "blocks = (int)(trips < kReduceBlocks ? (trips < 1 ? 1 : trips) : kReduceBlocks);"),
-    ("runtime/lowered_runtime.hpp",
-     "bool vec = FP::MARCH_OK && FP::HALO_MASK == 0u && eK % VK == 0 && P.rlb[2] % VK == 0 && P.n[2] % VK == 0;"),
-    ("runtime/lowered_runtime.hpp", "vec = vec && ((uintptr_t)ptrs[k] % 16 == 0);"),
-    ("runtime/lowered_runtime.hpp", "for (int ax = 0; ax < 3; ++ax) vec = vec && P.sh[k][ax] == 0 && P.m[k][ax] == P.n[ax];"),
-    ("runtime/lowered_runtime.hpp",
+    # reduce(apply): plan_reduce_apply (the kernel choice `vec`, the grid), launch_reduce_apply and launch_reduce_root;
+    # run_apply_reduce_op (lowered_runtime.hpp) passes `pointwise`
+    ("kernels/reduce_launch.hpp", "bool vec = pointwise && eK % VK == 0 && P.rlb[2] % VK == 0 && P.n[2] % VK == 0;"),
+    ("kernels/reduce_launch.hpp", "vec = vec && ((uintptr_t)ptrs[k] % 16 == 0);"),
+    ("kernels/reduce_launch.hpp", "for (int ax = 0; ax < 3; ++ax) vec = vec && P.sh[k][ax] == 0 && P.m[k][ax] == P.n[ax];"),
+    ("kernels/reduce_launch.hpp",
      "const int cells_per_chunk = 256 * (vec ? VK : 1), iter = vec ? kReduceApplyIter / 2 : kReduceApplyIter;"),
-    ("runtime/lowered_runtime.hpp",
+    ("kernels/reduce_launch.hpp",
      "const int64_t trips = ((P.rub[0] - P.rlb[0]) * (P.rub[1] - P.rlb[1]) * nchunk + iter - 1) / iter;"),
-    ("runtime/lowered_runtime.hpp", "const int blocks = (int)(trips < kReduceBlocks ? trips : kReduceBlocks);"),
+    ("kernels/reduce_launch.hpp", "const int blocks = (int)(trips < kReduceBlocks ? trips : kReduceBlocks);"),
+    ("kernels/reduce_launch.hpp", "hipLaunchKernelGGL((neptune_reduce_final<T, FOp>), dim3(1), dim3(256)"),
+    ("kernels/reduce_launch.hpp", "hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN, POp>), dim3(pl.blocks), dim3(256)"),
+    ("runtime/lowered_runtime.hpp", "constexpr bool kPointwise = FP::MARCH_OK && FP::HALO_MASK == 0u;"),
+]
+MIRRORED_KERNEL = [
     ("kernels/util_kernels.hpp", "constexpr int kReduceBlocks = 2048;"),
     ("kernels/util_kernels.hpp", "for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o);"),
     ("kernels/util_kernels.hpp", "for (int i = 0; i < nw; ++i) r += lds[i];"),
@@ -205,23 +214,22 @@ MIRRORED = [
     ("kernels/util_kernels.hpp", "constexpr int VK = 16 / sizeof(T), ITER = 4;"),
     ("kernels/util_kernels.hpp", "for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];"),
     ("kernels/apply_common.hpp", "constexpr int kWave = 64;"),
-    ("runtime/neptune_hip_rt.hip", "hipLaunchKernelGGL(neptune_reduce_final<double>, dim3(1), dim3(256)"),
-    ("runtime/lowered_runtime.hpp", "hipLaunchKernelGGL((neptune_reduce_apply<Body, T, RANK, NIN>), dim3(blocks), dim3(256)"),
     ("kernels/reduce_apply.hpp", "constexpr int kReduceApplyIter = 8;"),
     ("kernels/reduce_apply.hpp", "for (int it = 0; it < kReduceApplyIter; ++it) acc += v[it];"),
     ("kernels/reduce_apply.hpp", "constexpr int ITER = kReduceApplyIter / 2;"),
 ]
+MIRRORED = MIRRORED_HOST + MIRRORED_KERNEL
 
 
 def _final_height(blocks):
-    # neptune_reduce_final (util_kernels.hpp:254-260): lane t adds partials t, t + 256, ... to 0, then block_sum
-    # (util_kernels.hpp:155-166: 6 shuffle levels, thread 0 adds the 4 wave sums to 0)
+    # neptune_reduce_final (util_kernels.hpp): lane t adds partials t, t + 256, ... to 0, then block_sum
+    # (6 shuffle levels, thread 0 adds the 4 wave sums to 0)
     return _cdiv(blocks, BLOCK) + SHUFFLE_LEVELS + LDS_CHAIN
 
 
 def tree_height(path, dtype, ext):
     """an upper bound on the number of additions on any path from a cell to the result, from the loop structure of the
-    kernels (util_kernels.hpp:170-260, reduce_apply.hpp:26-147) and the grid of launch_blocks().  It counts the first addition of
+    kernels (util_kernels.hpp, reduce_apply.hpp) and the grid of launch_blocks().  It counts the first addition of
     every chain to its zero accumulator, which is exact: these spare levels also cover the rounding of a correctly
     rounded reference such as math.fsum.  path: flat | box | fused_scalar | fused_vec."""
     v = VK[np.dtype(dtype)]
@@ -232,23 +240,23 @@ def tree_height(path, dtype, ext):
     blocks = launch_blocks(path, dtype, ext)
     rows, last = total // ext[-1], ext[-1]
     if path == "flat":
-        # neptune_reduce_partial_flat (util_kernels.hpp:170-200): per = ceil(nvec / blocks) vectors per workgroup, lane-strided by 256 into VK
+        # neptune_reduce_partial_flat: per = ceil(nvec / blocks) vectors per workgroup, lane-strided by 256 into VK
         # partials each, those VK partials added in order, then (last workgroup, lane 0) the count % VK tail cells,
         # counted as VK - 1 whatever the tail so that h stays monotone in n
         nvec = total // v
         per = _cdiv(nvec, blocks)
         h = _cdiv(per, BLOCK) + v + (v - 1)
     elif path == "box":
-        # neptune_reduce_partial_box (util_kernels.hpp:204-251): per = ceil(chunks / blocks), trips of ITER = 4 chunks, each adding one cell to
+        # neptune_reduce_partial_box: per = ceil(chunks / blocks), trips of ITER = 4 chunks, each adding one cell to
         # each of VK partials; then the VK partials in order
         per = _cdiv(rows * _cdiv(last, 256 * v), blocks)
         h = 4 * _cdiv(per, 4) + v
     elif path == "fused_scalar":
-        # neptune_reduce_apply (reduce_apply.hpp:26-64): trips of ITER = 8 chunks, one cell per chunk per lane, one accumulator
+        # neptune_reduce_apply: trips of ITER = 8 chunks, one cell per chunk per lane, one accumulator
         per = _cdiv(rows * _cdiv(last, 256), blocks)
         h = K_REDUCE_APPLY_ITER * _cdiv(per, K_REDUCE_APPLY_ITER)
     elif path == "fused_vec":
-        # neptune_reduce_apply_vec (reduce_apply.hpp:94-147): trips of ITER = 4 chunks, VK cells per chunk per lane, one accumulator
+        # neptune_reduce_apply_vec: trips of ITER = 4 chunks, VK cells per chunk per lane, one accumulator
         it = K_REDUCE_APPLY_ITER // 2
         per = _cdiv(rows * _cdiv(last, 256 * v), blocks)
         h = it * v * _cdiv(per, it)

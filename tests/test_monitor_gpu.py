@@ -197,3 +197,56 @@ def test_builtin_bodies_through_the_c_abi(nh, body, kind, shape):
     assert nh.lib.neptune_hip_apply_builtin_norm(body_id, C.byref(g), arr, out.ptr, out.ptr + 8, st, None) == K.EINVAL
     assert nh.lib.neptune_hip_apply_builtin_norm(body_id, C.byref(g), arr, fin.ptr, dst.data_ptr(), st, None) == K.EINVAL
     assert nh.lib.neptune_hip_apply_builtin_norm(99, C.byref(g), arr, out.ptr, dst.data_ptr(), st, None) == K.EINVAL
+
+
+_DIFFSQ = """
+#l = #neptune_ir.location<"cell">
+#b = #neptune_ir.bounds<lb = [0, 0, 0], ub = [{ub}]>
+!t = !neptune_ir.temp<element = {elem}, bounds = #b, location = #l>
+!f = !neptune_ir.field<element = {elem}, bounds = #b, location = #l>
+module {{
+  func.func @diffsq(%a: memref<?x?x?x{elem}>, %b: memref<?x?x?x{elem}>) -> {elem} {{
+    %fa = neptune_ir.wrap %a : memref<?x?x?x{elem}> -> !f
+    %fb = neptune_ir.wrap %b : memref<?x?x?x{elem}> -> !f
+    %u = neptune_ir.load %fa : !f -> !t
+    %v = neptune_ir.load %fb : !f -> !t
+    %sq = neptune_ir.apply(%u, %v) attributes {{bounds = #b}} : (!t, !t) -> !t {{
+      ^bb0(%i: index, %j: index, %k: index, %x: !t, %y: !t):
+        %p = neptune_ir.access %x[0, 0, 0] : !t -> {elem}
+        %q = neptune_ir.access %y[0, 0, 0] : !t -> {elem}
+        %d = arith.subf %p, %q : {elem}
+        %e = arith.mulf %d, %d : {elem}
+        neptune_ir.yield %e : {elem}
+    }}
+    %s = neptune_ir.reduce %sq in #b {{kind = "sum"}} : !t -> {elem}
+    func.return %s : {elem}
+  }}
+}}
+"""
+
+
+@pytest.mark.parametrize("shape,dtype", [((5, 7, 520), np.float64), ((5, 7, 519), np.float64),
+                                         ((3, 9, 1028), np.float32), ((3, 9, 1027), np.float32)])
+def test_update_norm_returns_the_bits_of_the_lowered_fused_reduce(nh, shape, dtype):
+    """neptune_hip_update_norm(a, b) and a lowered reduce(apply((a - b) * (a - b))) over the whole box run the same kernels
+    on one launch plan (plan_reduce_apply, csrc/kernels/reduce_launch.hpp), so on the same device buffers they return the
+    same bits: no tolerance.  The first shape of each pair takes the vector kernel with two chunks per row, the second the
+    scalar kernel with a ragged last chunk."""
+    elem = "f64" if dtype == np.float64 else "f32"
+    tdtype = nh.torch.float64 if dtype == np.float64 else nh.torch.float32
+    F = nh.fields.DeviceField
+    a = F.from_numpy(helpers.hash_field(shape, dtype, seed=51))
+    b = F.from_numpy(helpers.hash_field(shape, dtype, seed=52))
+    mod = nh.lowering.compile_module(_DIFFSQ.format(ub=", ".join(map(str, shape)), elem=elem))
+    assert [x["kernel"] for x in mod.report["applies"]] == ["reduce"]
+    lowered = mod.call("diffsq", a.tensor, b.tensor)
+    dst = nh.torch.full((1,), -1.0, dtype=tdtype, device="cuda")
+    g = nh.apply.geom_for([b], a, ([0, 0, 0], list(shape)))
+    cdtype = nh.capi.F64 if dtype == np.float64 else nh.capi.F32
+    nh.capi.check(nh.lib.neptune_hip_update_norm(cdtype, C.byref(g), a.ptr, b.ptr, dst.data_ptr(), nh.fields.current_stream_ptr()),
+                  "update_norm")
+    nh.torch.cuda.synchronize()
+    direct = float(dst.item())
+    print(f"{shape} {elem}: update_norm = {direct!r} lowered = {lowered!r}")
+    assert math.isfinite(direct) and direct > 0.0
+    assert np.float64(direct).tobytes() == np.float64(lowered).tobytes()

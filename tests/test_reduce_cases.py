@@ -142,10 +142,14 @@ def test_gamma_bound_is_far_tighter_than_the_serial_bound_on_every_gpu_shape(dt)
 def test_the_mirrored_host_and_kernel_lines_are_unchanged():
     """fused_path, plain_path, launch_blocks and tree_height restate the host's kernel choice and grid and the kernels'
     loop structure; the GPU tests rely on them to know which kernel a case runs.  Each restated line must still be
-    there, verbatim, or the mirror in reduce_cases.py is out of date."""
+    there, verbatim, or the mirror in reduce_cases.py is out of date.  A host line must moreover be the only copy of its
+    rule: it occurs in exactly one file under csrc and exactly once in it, so no other launch path can restate the rule
+    and then drift from the mirrored one."""
     csrc = Path(__file__).resolve().parent.parent / "neptune-pde-solver_amd" / "csrc"
-    texts = {}
+    texts = {str(f.relative_to(csrc)): " ".join(f.read_text().split()) for f in sorted(csrc.rglob("*")) if f.is_file()}
     for rel, line in rc.MIRRORED:
-        if rel not in texts:
-            texts[rel] = " ".join((csrc / rel).read_text().split())
         assert " ".join(line.split()) in texts[rel], (rel, line)
+    assert rc.MIRRORED_HOST and rc.MIRRORED_KERNEL and rc.MIRRORED == rc.MIRRORED_HOST + rc.MIRRORED_KERNEL
+    for rel, line in rc.MIRRORED_HOST:
+        counts = {name: text.count(" ".join(line.split())) for name, text in texts.items()}
+        assert {name: n for name, n in counts.items() if n} == {rel: 1}, (rel, line, counts)
