@@ -7,7 +7,11 @@ KSP on the host (lib/Runtime/PETSc/NeptunePETScRuntime.cpp:182-230, 719-786), wi
     dot  : reduce(apply(a*b)) -- one fused kernel, reads both vectors once
     axpy : plain torch (NeptuneIR regions are IsolatedFromAbove: a run-time scalar cannot enter an apply)
 
-usage: examples/cg_matrix_free.py [N]      (default 256: a 256^3 Poisson problem)"""
+With --solver the same problem runs through neptune_hip.apply.cg_solve instead: the loop, its scalars and its
+vector updates stay on the device, p . A(p) comes out of the launch that computes A(p) (lowering option dot-entries), and the
+host reads one scalar every 10 iterations.
+
+usage: examples/cg_matrix_free.py [N] [--solver]      (default 256: a 256^3 Poisson problem)"""
 import sys
 import time
 from pathlib import Path
@@ -98,8 +102,26 @@ def cg(matmult, dot, b, x, tol=1e-10, maxit=500):
     return x, it, (rs / rs0) ** 0.5
 
 
+def run_solver(shape, b, tol):
+    """the same solve through neptune_hip_cg_solve: -> (iterations, relative residual, seconds)"""
+    import torch
+    from neptune_hip import _capi, apply, fields, lowering
+    mod = lowering.compile_module(module_text(shape), dot_entries=True)
+    entry = mod.dot_entry(next(a["function"] for a in mod.report["applies"] if a.get("dot_symbol")))
+    interior = ([1, 1, 1], [n - 1 for n in shape])
+    field = lambda t: fields.DeviceField((0, 0, 0), shape, _capi.F64, t)
+    work = [field(torch.empty_like(b)) for _ in range(3)]
+    _, rr0, _ = apply.cg_solve(entry, field(torch.zeros_like(b)), field(b), interior, 0, 0.0, work=work)   # r . r of the first guess
+    x = field(torch.zeros_like(b))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    it, _, rr = apply.cg_solve(entry, x, field(b), interior, 500, tol * tol * rr0, check_every=10, work=work)
+    return it, (rr / rr0) ** 0.5, time.perf_counter() - t0
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+    args = [a for a in sys.argv[1:] if a != "--solver"]
+    n = int(args[0]) if args else 256
     import torch
     from neptune_hip import lowering
     shape = (n, n, n)
@@ -108,6 +130,10 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(7)
     b = torch.zeros(shape, dtype=torch.float64, device="cuda")
     b[1:-1, 1:-1, 1:-1] = torch.rand((n - 2,) * 3, dtype=torch.float64, device="cuda", generator=g)
+    if "--solver" in sys.argv[1:]:
+        it, rel, dt = run_solver(shape, b, 1e-8)
+        print(f"{n}^3 Poisson, cg_solve: {it} iterations, relative residual {rel:.2e}, {dt * 1e3 / max(it, 1):.3f} ms per iteration")
+        return
     x = torch.zeros_like(b)
     t0 = time.perf_counter()
     x, it, rel = cg(lambda y, v: mod.call("matmult", y, v), lambda u, v: mod.call("dot", u, v), b, x, tol=1e-8)

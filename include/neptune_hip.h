@@ -394,6 +394,57 @@ int neptune_hip_step_loop_until(neptune_hip_apply_fn fn, neptune_hip_apply_norm_
  * that ran the fallback, and checks (read-backs) in all */
 void neptune_hip_until_loop_counts(int64_t *fused, int64_t *fallback, int64_t *checks);
 
+/* Device-resident conjugate gradients: the dot products out of the launches that move the data.
+ * A DOT-MONITORED launch is a monitored launch (above) with another term: D = sum new * old over the cells of apply.bounds
+ * that lie in the launch region -- one rounding of the product of the fresh value and input 0 at the same physical index, in
+ * the element type T; a cell that does not count adds +0.  With in[0] = p it returns q = A(p) exactly as
+ * neptune_hip_apply_builtin computes it and p . A(p) out of the same launch.  Same tree, workspace, refusals
+ * (NEPTUNE_HIP_EUNSUPPORTED, nothing launched: a plan onto the plane-in-LDS kernels, every tile spilling, workspace growth
+ * under capture; dot_out overlapping a field: NEPTUNE_HIP_EINVAL) and asynchrony as neptune_hip_apply_builtin_norm.
+ * Lowered applies export the same as <function>_<k>__geomD on request (lowering option dot-entries). */
+int neptune_hip_apply_builtin_dot(int body, const neptune_hip_apply_geom_t *g, const void *const *in, void *out,
+                                  void *dot_out, void *stream, const neptune_hip_launch_cfg_t *cfg);
+typedef int (*neptune_hip_apply_dot_fn)(const neptune_hip_apply_geom_t *g, const void *const *in, void *out,
+                                        void *dot_out, void *stream, const neptune_hip_launch_cfg_t *cfg);
+/* The same D from two fields, in one read-only pass: *out_dev = sum a * b over apply.bounds x launch region of `g` (a = a
+ * field in the result's box, b = one in input 0's box), summed by the fixed tree of the reduce(apply) kernels: the
+ * counterpart of neptune_hip_update_norm, within 2 (n - 1) eps sum |a_i b_i| of a dot-monitored launch's D.
+ * dtype: NEPTUNE_HIP_F64 / _F32.  out_dev: DEVICE pointer; asynchronous. */
+int neptune_hip_dot(int dtype, const neptune_hip_apply_geom_t *g, const void *a, const void *b, void *out_dev,
+                    void *stream);
+
+/* Solve A(x) = b by unpreconditioned conjugate gradients for the apply `fn` (fn = NULL: built-in body `body`), whose
+ * input 0 must have the result's box; inputs 1.. are fixed fields, in_rest[i] = input i + 1 (NULL when there is none).
+ * The unknowns are the cells of Omega = apply.bounds x launch region of `g`.  x: initial guess in, solution out; cells of x
+ * outside Omega keep their values (the flat update adds alpha * (+0) there) and enter only through A(x) in the initial
+ * residual (Dirichlet data).  b: right-hand
+ * side.  work[3] = r, p, q: caller-supplied fields of the same box; nothing but a small scalar / partials block is
+ * allocated by the call.  All arithmetic in the element type T, no FMA:
+ *   set-up     q = A(x);  r = b - q on Omega, +0 elsewhere;  p = r;  rr_0 = sum r * r
+ *   iteration  q = A(p), pq = sum_Omega q * p out of the same launch (fn_dot);  alpha = rr / pq;
+ *              x = x + (alpha p), r = r - (alpha q) on the whole flat buffers, rr' = sum r * r out of that launch;
+ *              beta = rr' / rr;  p = r + (beta p);  rr <- rr'
+ * An iteration that finds rr == 0 or pq == 0 uses alpha = beta = 0.  Sums: the fixed tree of the monitored launches, no
+ * atomics.  alpha and beta never leave the device: the scalars live in a device block that one-workgroup kernels rotate, so
+ * an iteration's launches have fixed arguments and blocks of iterations replay as hipGraphs.
+ * The loop runs in blocks of check_every iterations (the last one shortened: max_iters is never exceeded); after each block
+ * one stream synchronise and one sizeof(T) read, and the loop stops when rr <= tol2 (the threshold on rr itself; a NaN
+ * never satisfies it).  *rr0 = rr_0 (read back once after the set-up, for a relative tolerance); rr_0 <= tol2 returns with
+ * zero iterations.  *iters_done, *rr_last: iterations run, the last rr read.  trace: NULL, or a DEVICE pointer to
+ * 2 * max_iters values of T: iteration k stores pq_k at [2 k] and rr_(k+1) at [2 k + 1].
+ * Fallback: when fn_dot is NULL (with fn set) or answers NEPTUNE_HIP_EUNSUPPORTED (remembered for the rest of the call),
+ * q = A(p) is a plain launch followed by neptune_hip_dot.
+ * NEPTUNE_HIP_EINVAL, nothing launched: a call while `stream` is being captured, check_every < 1, max_iters < 0, a null
+ * field, input 0's box differing from the result's, any two of x, b, r, p, q overlapping, a trace that overlaps a field. */
+int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                         const neptune_hip_apply_geom_t *g, void *x, const void *b, void *const work[3],
+                         const void *const *in_rest, int64_t max_iters, int64_t check_every, double tol2, void *trace,
+                         void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0,
+                         double *rr_last);
+/* the last neptune_hip_cg_solve call of this process: iterations whose q = A(p) ran as a dot-monitored launch, iterations
+ * that ran the fallback, and read-backs after blocks (the read of rr_0 is not counted) */
+void neptune_hip_cg_counts(int64_t *fused, int64_t *fallback, int64_t *checks);
+
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t *g,

@@ -28,12 +28,17 @@ int neptune_lowering_verify(const char *mlir_text, char **diag_out);
  *               the exported geometry-level entry of that apply (neptune_hip_apply_fn, include/neptune_hip.h);
  *               leapfrog_symbol, the pair entry <geom_symbol>L2 of a two-level scheme (neptune_hip_leapfrog2_fn), or ""
  *               norm_symbol (only with the option below), the monitored launch <geom_symbol>N (neptune_hip_apply_norm_fn)
+ *               dot_symbol (only with its option below), the dot-monitored launch <geom_symbol>D (neptune_hip_apply_dot_fn)
  * Lowering options travel in the module text, one comment line each: "// neptune-hip-option: <name>".
  *   norm-entries   every apply whose input 0 has the result's element type and a box equal to the result's (a fused
  *                  explicit Euler step included) also exports its monitored launch <function>_<k>__geomN: the apply and
  *                  the update norm sum (new - old)^2 from one launch (include/neptune_hip.h).  Without it
  *                  source and report are what they are without this feature.  neptune-opt: --norm-entries; Python:
  *                  compile_module(..., norm_entries=True).
+ *   dot-entries    the applies norm-entries names also export their dot-monitored launch <function>_<k>__geomD: the apply and
+ *                  sum new * in[0] from one launch -- p . A(p) for a conjugate-gradient iteration (include/neptune_hip.h,
+ *                  DESIGN.md 3.11).  Without it source and report are what they are without this feature.  neptune-opt:
+ *                  --dot-entries; Python: compile_module(..., dot_entries=True).
  *   reduce-kinds   neptune_ir.reduce kinds "max" | "min" | "l1" | "l2" verify and lower (semantics: DESIGN.md 3.3; any other
  *                  kind: 'neptune_ir.reduce' op unsupported reduce kind "<k>"); every reduce then goes through the kind-taking
  *                  runtime forms, and the report entry of an apply fused into a reduce carries "reduce_kind".  Without it a

@@ -151,9 +151,32 @@ struct MonitorPlan {     // host side of one monitored call: a counting pass siz
   int64_t blocks;        // workgroups so far: where the next launch's partials start
   void* base;            // the partials buffer (launching pass)
 };
-template <class Body, class T>
+// one term of S: two roundings (the difference, then the square), no FMA; a cell that does not count adds +0
+template <class T>
+__device__ __forceinline__ T monitor_term(bool counts, T fresh, T old) {
+  const T d = fresh - old;
+  const T q = d * d;
+  return counts ? q : (T)0;
+}
+// The term policy of a monitored launch: what a counted cell adds, from the value the store site holds (`fresh`) and input 0
+// at the same physical index (`old`).  MonitorDiffSq is the update norm's (fresh - old)^2 above; MonitorDot is one rounding
+// of fresh * old -- with fresh = A(p) and old = p the launch returns p . A(p), the dot product a conjugate-gradient
+// iteration needs.  A cell that does not count adds +0 through a select in both.
+struct MonitorDiffSq {
+  template <class T>
+  static __device__ __forceinline__ T term(bool counts, T fresh, T old) { return monitor_term(counts, fresh, old); }
+};
+struct MonitorDot {
+  template <class T>
+  static __device__ __forceinline__ T term(bool counts, T fresh, T old) {
+    const T q = fresh * old;
+    return counts ? q : (T)0;
+  }
+};
+template <class Body, class T, class Term_ = MonitorDiffSq>
 struct MonitoredBody {
   static constexpr bool MONITORED = true;
+  using Term = Term_;
   Body body;
   T* partials;           // this launch's partials, one per workgroup
   MonitorPlan* plan;     // host only
@@ -164,17 +187,10 @@ template <class Body, class = void>
 struct IsMonitored { static constexpr bool value = false; };
 template <class Body>
 struct IsMonitored<Body, std::void_t<decltype(Body::MONITORED)>> { static constexpr bool value = true; };
-template <class Body, class T>
-struct OutsideOf<MonitoredBody<Body, T>, T, void> {
-  static __device__ __forceinline__ T apply(const MonitoredBody<Body, T>& b, T through) { return OutsideOf<Body, T>::apply(b.body, through); }
+template <class Body, class T, class Term>
+struct OutsideOf<MonitoredBody<Body, T, Term>, T, void> {
+  static __device__ __forceinline__ T apply(const MonitoredBody<Body, T, Term>& b, T through) { return OutsideOf<Body, T>::apply(b.body, through); }
 };
-// one term of S: two roundings (the difference, then the square), no FMA; a cell that does not count adds +0
-template <class T>
-__device__ __forceinline__ T monitor_term(bool counts, T fresh, T old) {
-  const T d = fresh - old;
-  const T q = d * d;
-  return counts ? q : (T)0;
-}
 
 // The workgroup's sum of `v`, valid in thread 0: wave shuffle tree, one slot per wave in `lds` (>= blockDim.x / 64 entries),
 // the waves' sums added in wave order -- the same fixed tree as util_kernels.hpp's block_sum, which this header cannot

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void neptune_apply_direct(DirectParams<T, NIN>
   // (non-temporal: the result is not read again by this launch, and keeping it out of L2 leaves the neighbours' lines there --
   //  rows form 1024^3 7-point 2.52 -> 2.84 TB/s)
   __builtin_nontemporal_store(inside ? val : OutsideOf<Body, T>::apply(body, through), P.out + o);
-  if constexpr (MON) mon_term = monitor_term(inside, val, through);
+  if constexpr (MON) mon_term = Body::Term::term(inside, val, through);
   }
   }
   if constexpr (MON) {
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void neptune_apply_rows(DirectParams<T, NIN> P
   const T through = in0[(uint32_t)a.qk];  // copy-through: physical-index-wise (DataflowLowering.cpp:283-287)
   const T val = body(a);
   __builtin_nontemporal_store(inside ? val : OutsideOf<Body, T>::apply(body, through), out + (uint32_t)a.qk);
-  if constexpr (MON) mon_term = monitor_term(inside, val, through);
+  if constexpr (MON) mon_term = Body::Term::term(inside, val, through);
   }
   }
   if constexpr (MON) {

@@ -872,9 +872,10 @@ inline int launch_apply_impl(const Body& body, const neptune_hip_apply_geom_t* g
 // of S depend on the launch configuration (tile, chunk) only.  Asynchronous.  No first-use measuring: the automatic tile,
 // or cfg's.  NEPTUNE_HIP_EUNSUPPORTED, nothing launched: a plan onto the plane-in-LDS kernels, every tile spilling, a
 // workspace that would have to grow while the stream is being captured.  sum_out overlapping a field: NEPTUNE_HIP_EINVAL.
-template <class Body, class T, int RANK, int NIN, class FP>
-inline int launch_apply_norm(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* sum_out,
-                             hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
+// Term: the term policy (apply_common.hpp) -- MonitorDiffSq for launch_apply_norm, MonitorDot for launch_apply_dot below.
+template <class Term, class Body, class T, int RANK, int NIN, class FP>
+inline int launch_apply_monitored(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* sum_out,
+                                  hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
   if (!g || !in || !out || !sum_out) return NEPTUNE_HIP_EINVAL;
   int rc = geom_validate(g);
   if (rc != NEPTUNE_HIP_OK) return rc;
@@ -883,7 +884,7 @@ inline int launch_apply_norm(const Body& body, const neptune_hip_apply_geom_t* g
   if (buffers_overlap(sum_out, sizeof(T), out, geom_box_bytes(g->out_lb, g->out_ub, RANK, sizeof(T)))) return NEPTUNE_HIP_EINVAL;
   for (int k = 0; k < NIN; ++k)
     if (in[k] && buffers_overlap(sum_out, sizeof(T), in[k], geom_box_bytes(g->in_lb[k], g->in_ub[k], RANK, sizeof(T)))) return NEPTUNE_HIP_EINVAL;
-  using MB = MonitoredBody<Body, T>;
+  using MB = MonitoredBody<Body, T, Term>;
   MonitorPlan mp = {true, 0, nullptr};
   const MB mb = {body, nullptr, &mp};
   rc = launch_apply_impl<MB, T, RANK, NIN, FP>(mb, g, in, out, stream, cfg);
@@ -898,6 +899,19 @@ inline int launch_apply_norm(const Body& body, const neptune_hip_apply_geom_t* g
   hipLaunchKernelGGL(neptune_monitor_final<T>, dim3(1), dim3(256), 0, stream, static_cast<const T*>(ws), (int64_t)mp.blocks, static_cast<T*>(sum_out));
   NEPTUNE_HIP_CHECK(hipGetLastError());
   return NEPTUNE_HIP_OK;
+}
+template <class Body, class T, int RANK, int NIN, class FP>
+inline int launch_apply_norm(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* sum_out,
+                             hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
+  return launch_apply_monitored<MonitorDiffSq, Body, T, RANK, NIN, FP>(body, g, in, out, sum_out, stream, cfg);
+}
+// ---- a dot-monitored launch: the apply and D = sum new * old over apply.bounds x launch region ----------
+// launch_apply_norm with the term fresh * old (one rounding) in place of (fresh - old)^2: the same counting pass, workspace,
+// refusals and final kernel.  With in[0] = p and out = q = A(p) it returns p . A(p) out of the launch that computes A(p).
+template <class Body, class T, int RANK, int NIN, class FP>
+inline int launch_apply_dot(const Body& body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* dot_out,
+                            hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
+  return launch_apply_monitored<MonitorDot, Body, T, RANK, NIN, FP>(body, g, in, out, dot_out, stream, cfg);
 }
 
 // ---- measured launch choice at first use, remembered as wisdom -----------------------------------------------

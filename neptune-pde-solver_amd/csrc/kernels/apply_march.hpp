@@ -745,7 +745,7 @@ __global__ __launch_bounds__(kWave* TL::WJ* TL::WK) void neptune_apply_march(Mar
         else through = pt[0][r][e];
         res[e] = inside ? val : OutsideOf<Body, T>::apply(body, through);
         // the store's own predicates plus `inside`: copy-through, clamped and predicated-off cells add nothing
-        if constexpr (IsMonitored<Body>::value) mon_acc += monitor_term(inside && row_ok[r] && lane_ok, val, through);
+        if constexpr (IsMonitored<Body>::value) mon_acc += Body::Term::term(inside && row_ok[r] && lane_ok, val, through);
       });
       if (row_ok[r] && lane_ok) {
         // rowb[0][r+R1] is this own row's offset in the result (own rows are never clamped when row_ok)

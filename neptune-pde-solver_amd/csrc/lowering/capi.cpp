@@ -73,6 +73,7 @@ std::string report_json(const LowerInfo& info) {
       << ", \"geom_symbol\": \"" << a.geom_symbol << "\", \"exact\": " << (a.exact ? "true" : "false")
       << ", \"leapfrog_symbol\": \"" << a.leapfrog_symbol << "\"";
     if (!a.norm_symbol.empty()) o << ", \"norm_symbol\": \"" << a.norm_symbol << "\"";
+    if (!a.dot_symbol.empty()) o << ", \"dot_symbol\": \"" << a.dot_symbol << "\"";
     if (!a.reduce_kind.empty()) o << ", \"reduce_kind\": \"" << a.reduce_kind << "\"";
     if (a.group >= 0) o << ", \"group\": " << a.group;
     o << "}";
@@ -189,6 +190,7 @@ LowerOptions options_in_text(const char* mlir_text) {
       const size_t f = name.find_first_not_of(" \t"), l = name.find_last_not_of(" \t\r");
       name = f == std::string::npos ? "" : name.substr(f, l - f + 1);
       if (name == "norm-entries") opt.norm_entries = true;
+      if (name == "dot-entries") opt.dot_entries = true;
       if (name == "reduce-kinds") opt.reduce_kinds = true;
     }
     pos = eol + 1;

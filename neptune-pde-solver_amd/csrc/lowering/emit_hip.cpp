@@ -651,7 +651,7 @@ struct Emitter {
   // (caller-supplied boxes, bounds, region, stream and launch configuration; no allocation, no synchronisation).
   // The slab decomposition drives user stencils through them.
   void emit_geom_entries(const std::string& sym, const std::string& reach, const std::string& body, const std::string& init,
-                         const std::string& T, int rank, int nin, const std::string& fp, bool norm = false) {
+                         const std::string& T, int rank, int nin, const std::string& fp, bool norm = false, bool dot = false) {
     static const char* const suffix[3] = {"", "2", "3"};
     static const char* const launch[3] = {"launch_apply", "launch_apply_twice", "launch_apply_thrice"};
     for (int v = 0; v < 3; ++v) {
@@ -680,6 +680,17 @@ struct Emitter {
                    << "  if (neptune_hip::check_no_alias(g, in, out, sizeof(" << T << ")) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;\n"
                    << "  return neptune_hip::launch_apply_norm<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
                    << ">(" << body << "{" << init << "}, g, in, out, sum_out, (hipStream_t)stream, cfg);\n}\n";
+    if (dot)
+      geom_entries << "// the dot-monitored launch (lowering option dot-entries; neptune_hip_apply_dot_fn, include/neptune_hip.h): the apply and\n"
+                   << "// D = sum new * in[0] over apply.bounds x launch region into *dot_out, or NEPTUNE_HIP_EUNSUPPORTED, nothing launched\n"
+                   << "extern \"C\" int " << sym << "D(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* dot_out,\n"
+                   << "    void* stream, const neptune_hip_launch_cfg_t* cfg) {\n"
+                   << "  if (!g || !in || !out || !dot_out) return NEPTUNE_HIP_EINVAL;\n"
+                   << "  const int rc = neptune_hip::geom_check_radius(g, " << reach << ");\n"
+                   << "  if (rc != NEPTUNE_HIP_OK) return rc;\n"
+                   << "  if (neptune_hip::check_no_alias(g, in, out, sizeof(" << T << ")) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;\n"
+                   << "  return neptune_hip::launch_apply_dot<" << body << ", " << T << ", " << rank << ", " << nin << ", " << fp
+                   << ">(" << body << "{" << init << "}, g, in, out, dot_out, (hipStream_t)stream, cfg);\n}\n";
     geom_entries << "// march tiles this module holds for that entry (plan-time tuning: neptune_hip_autotune_fn)\n"
                  << "extern \"C\" int " << sym << "_variants(int rank) { return neptune_hip::march_variant_count(rank); }\n\n";
   }
@@ -687,12 +698,15 @@ struct Emitter {
   // Lowering option norm-entries: an apply whose input 0 has the result's element type and a box equal to the result's --
   // the old state of an iteration u <- A(u) -- also exports its monitored launch <geom_symbol>N
   bool norm_entries = false;
+  bool dot_entries = false;    // lowering option dot-entries: the same eligibility, <geom_symbol>D
   bool reduce_kinds = false;   // lowering option reduce-kinds: reduces go through the kind-taking runtime forms
-  bool wants_norm_entry(const Op& op) const {
+  static bool monitor_eligible(const Op& op) {
     const int nin = (int)op.operands.size();
     const Type& res = op.types[nin];
-    return norm_entries && op.types[0].elem == res.elem && op.types[0].bounds == res.bounds;
+    return op.types[0].elem == res.elem && op.types[0].bounds == res.bounds;
   }
+  bool wants_norm_entry(const Op& op) const { return norm_entries && monitor_eligible(op); }
+  bool wants_dot_entry(const Op& op) const { return dot_entries && monitor_eligible(op); }
 
   // A two-level scheme u(n+1) = B(u(n), u(n-1), c...) the chain kernel can step twice per pass: input 0 a star of radius
   // 1..2 per axis (what march2_footprint / march2_rank2_footprint of csrc/kernels/apply_march2.hpp take), input 1 -- the
@@ -768,8 +782,9 @@ struct Emitter {
       ai.group = group;
       ai.geom_symbol = tag + "__geom";
       if (wants_norm_entry(op)) ai.norm_symbol = ai.geom_symbol + "N";
+      if (wants_dot_entry(op)) ai.dot_symbol = ai.geom_symbol + "D";
       emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag,
-                        !ai.norm_symbol.empty());
+                        !ai.norm_symbol.empty(), !ai.dot_symbol.empty());
       if (leapfrog_capable(fp, op)) {
         ai.leapfrog_symbol = ai.geom_symbol + "L2";
         emit_leapfrog_entry(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
@@ -817,8 +832,9 @@ struct Emitter {
       ApplyInfo ai = apply_info(s, tag, fp, fp.rank, res.elem, halo0_of(fp));
       ai.geom_symbol = tag + "__geom";
       if (wants_norm_entry(op)) ai.norm_symbol = ai.geom_symbol + "N";
+      if (wants_dot_entry(op)) ai.dot_symbol = ai.geom_symbol + "D";
       emit_geom_entries(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, "", ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag,
-                        !ai.norm_symbol.empty());
+                        !ai.norm_symbol.empty(), !ai.dot_symbol.empty());
       if (leapfrog_capable(fp, op)) {
         ai.leapfrog_symbol = ai.geom_symbol + "L2";
         emit_leapfrog_entry(ai.geom_symbol, "kTopRadius_" + tag, "Body_" + tag, ctype(res.elem), res.bounds.rank(), nin, "FP_" + tag);
@@ -1100,7 +1116,8 @@ struct Emitter {
       ai.geom_symbol = tag + "__geom";
       geom_entries << "static const neptune_hip::Reach kTopRadiusG_" << tag << " = " << fused_reach(cfp, st.rank()) << ";\n";
       if (norm_entries) ai.norm_symbol = ai.geom_symbol + "N";   // the state is input 0 and the result: always eligible
-      emit_geom_entries(ai.geom_symbol, "kTopRadiusG_" + tag, body, "(" + T + ")" + lit, T, st.rank(), 1, "FP_" + ctag, norm_entries);
+      if (dot_entries) ai.dot_symbol = ai.geom_symbol + "D";
+      emit_geom_entries(ai.geom_symbol, "kTopRadiusG_" + tag, body, "(" + T + ")" + lit, T, st.rank(), 1, "FP_" + ctag, norm_entries, dot_entries);
     }
     info.applies.push_back(ai);
     return true;
@@ -1452,6 +1469,7 @@ struct Emitter {
 bool lower_to_hip(const Module& m, std::string& out_source, LowerInfo& info, Diag& diag, const LowerOptions& options) {
   Emitter e(m, diag, info);
   e.norm_entries = options.norm_entries;
+  e.dot_entries = options.dot_entries;
   e.reduce_kinds = options.reduce_kinds;
   return e.run(out_source) && diag.ok;
 }

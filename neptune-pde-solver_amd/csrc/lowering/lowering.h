@@ -18,6 +18,7 @@ struct ApplyInfo {
   std::string geom_symbol;    // exported geometry-level entry (empty: none)
   std::string leapfrog_symbol;  // exported leapfrog pair entry <geom_symbol>L2 of a two-level scheme (empty: none)
   std::string norm_symbol;    // exported monitored launch <geom_symbol>N (lowering option norm-entries; empty: none)
+  std::string dot_symbol;     // exported dot-monitored launch <geom_symbol>D (lowering option dot-entries; empty: none)
   std::string reduce_kind;    // fused_reduce under the lowering option reduce-kinds: the consuming reduce's kind (else empty)
   bool exact = true;          // false: the body uses elementary functions (exp, log, ...): a few ulp, not bit-exact
   int group = -1;             // index into LowerInfo::groups when this apply is a member of a group
@@ -66,6 +67,7 @@ struct LowerInfo {
 // about its artefact.
 struct LowerOptions {
   bool norm_entries = false;   // "norm-entries": eligible applies also export their monitored launch <fn>_<k>__geomN
+  bool dot_entries = false;    // "dot-entries": the same applies also export their dot-monitored launch <fn>_<k>__geomD
   bool reduce_kinds = false;   // "reduce-kinds": neptune_ir.reduce kinds max | min | l1 | l2 verify and lower
 };
 LowerOptions options_in_text(const char* mlir_text);   // capi.cpp

@@ -7,6 +7,7 @@
 //     neptune-opt in.mlir --verify-only                           run the verifiers only
 //     neptune-opt in.mlir --report                                 print what was lowered, as JSON
 //     --norm-entries  (with --neptuneir-to-hip) lowering option norm-entries: eligible applies also export <fn>_<k>__geomN
+//     --dot-entries   (with --neptuneir-to-hip) lowering option dot-entries: the same applies also export <fn>_<k>__geomD
 //     --reduce-kinds  lowering option reduce-kinds: neptune_ir.reduce kinds max | min | l1 | l2 verify and lower
 // --neptuneir-to-llvm is recognised and answered with a pointer to --neptuneir-to-hip (there is
 // no MLIR/LLVM in this toolchain; the CPU pipeline stays with the reference build).
@@ -35,7 +36,7 @@ static std::string self_repo_root(const char* argv0) {
 
 int main(int argc, char** argv) {
   std::string in, out, emit = "hip";
-  bool to_hip = false, verify_only = false, report = false, to_llvm = false, norm_entries = false, reduce_kinds = false;
+  bool to_hip = false, verify_only = false, report = false, to_llvm = false, norm_entries = false, dot_entries = false, reduce_kinds = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--neptuneir-to-hip") to_hip = true;
@@ -43,12 +44,13 @@ int main(int argc, char** argv) {
     else if (a == "--verify-only" || a == "--neptune-ir-verify-annotate") verify_only = true;
     else if (a == "--report") report = true;
     else if (a == "--norm-entries") norm_entries = true;
+    else if (a == "--dot-entries") dot_entries = true;
     else if (a == "--reduce-kinds") reduce_kinds = true;
     else if (a.compare(0, 7, "--emit=") == 0) emit = a.substr(7);
     else if (a == "-o" && i + 1 < argc) out = argv[++i];
     else if (a == "--version") { std::puts(neptune_lowering_version()); return 0; }
     else if (a == "-h" || a == "--help") {
-      std::puts("usage: neptune-opt <in.mlir|-> (--neptuneir-to-hip [--emit=hip|so] [--norm-entries] [-o file] | --verify-only) [--reduce-kinds] [--report]");
+      std::puts("usage: neptune-opt <in.mlir|-> (--neptuneir-to-hip [--emit=hip|so] [--norm-entries] [--dot-entries] [-o file] | --verify-only) [--reduce-kinds] [--report]");
       return 0;
     } else if (!a.empty() && a[0] == '-' && a != "-") { std::fprintf(stderr, "neptune-opt: unknown option %s\n", a.c_str()); return 2; }
     else in = a;
@@ -68,6 +70,7 @@ int main(int argc, char** argv) {
   }
   // lowering options travel in the module text (include/neptune_lowering.h)
   const std::string text = (norm_entries ? std::string("// neptune-hip-option: norm-entries\n") : std::string()) +
+                           (dot_entries ? std::string("// neptune-hip-option: dot-entries\n") : std::string()) +
                            (reduce_kinds ? std::string("// neptune-hip-option: reduce-kinds\n") : std::string()) + ss.str();
   char *diag = nullptr, *src = nullptr, *rep = nullptr;
   struct Release {  // the library hands out malloc'ed strings (include/neptune_lowering.h)

@@ -198,8 +198,16 @@ struct DiffSquared {
     return d * d;
   }
 };
+// a * b: the term of a dot product (one rounding), likewise
 template <class T>
-int update_norm(const neptune_hip_apply_geom_t* g, const void* a, const void* b, void* sum_out, hipStream_t st) {
+struct Product {
+  template <class A>
+  __device__ __forceinline__ T operator()(const A& acc) const { return acc.template get<0, 0, 0, 0>() * acc.template get<1, 0, 0, 0>(); }
+};
+// sum over apply.bounds x launch region of `g` of Term(a, b), in one read-only pass: a = a field in the result's box, b = one
+// in input 0's box
+template <class T, class Term>
+int two_field_sum(const neptune_hip_apply_geom_t* g, const void* a, const void* b, void* sum_out, hipStream_t st) {
   // a two-input apply geometry: input 0 = a in the result's box, input 1 = b in input 0's box; reduced box = bounds x region
   neptune_hip_apply_geom_t g2 = *g;
   g2.num_inputs = 2;
@@ -225,9 +233,13 @@ int update_norm(const neptune_hip_apply_geom_t* g, const void* a, const void* b,
   }
   const ReduceApplyPlan pl = plan_reduce_apply(P, ptrs, true);
   if (!pl.narrow) return NEPTUNE_HIP_EUNSUPPORTED;   // the kernels keep coordinates and row indices in 32 bits
-  launch_reduce_apply<RedSum<T>, RedSum<T>, true, DiffSquared<T>, T, 3, 2>(pl, P, DiffSquared<T>{}, static_cast<T*>(rt().reduce_ws),
-                                                                          static_cast<T*>(sum_out), st);
+  launch_reduce_apply<RedSum<T>, RedSum<T>, true, Term, T, 3, 2>(pl, P, Term{}, static_cast<T*>(rt().reduce_ws),
+                                                                  static_cast<T*>(sum_out), st);
   return NEPTUNE_HIP_OK;
+}
+template <class T>
+int update_norm(const neptune_hip_apply_geom_t* g, const void* a, const void* b, void* sum_out, hipStream_t st) {
+  return two_field_sum<T, DiffSquared<T>>(g, a, b, sum_out, st);
 }
 }  // namespace
 
@@ -562,6 +574,31 @@ int neptune_hip_apply_builtin_norm(int body, const neptune_hip_apply_geom_t* g, 
   if (rc != NEPTUNE_HIP_OK) return rc;
   ensure_init();
   return body_entry(body)->apply_norm(g, in, out, sum_out, as_stream(stream), cfg);
+}
+
+// ---------------------------------------------------------------- dot-monitored applies
+int neptune_hip_apply_builtin_dot(int body, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* dot_out,
+                                  void* stream, const neptune_hip_launch_cfg_t* cfg) {
+  if (!g || !in || !out || !dot_out) return NEPTUNE_HIP_EINVAL;
+  if (body < 0 || body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
+  int rc = geom_validate(g);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  for (int k = 0; k < g->num_inputs; ++k)
+    if (!in[k]) return NEPTUNE_HIP_EINVAL;
+  rc = check_no_alias(g, in, out, body_elem_size(body));
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  ensure_init();
+  return body_entry(body)->apply_dot(g, in, out, dot_out, as_stream(stream), cfg);
+}
+
+int neptune_hip_dot(int dtype, const neptune_hip_apply_geom_t* g, const void* a, const void* b, void* out_dev, void* stream) {
+  if (!g || !a || !b || !out_dev) return NEPTUNE_HIP_EINVAL;
+  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
+  const int rc = geom_validate(g);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  ensure_init();
+  return dtype == NEPTUNE_HIP_F64 ? two_field_sum<double, Product<double>>(g, a, b, out_dev, as_stream(stream))
+                                  : two_field_sum<float, Product<float>>(g, a, b, out_dev, as_stream(stream));
 }
 
 void* neptune_hip_monitor_workspace(size_t bytes, void* stream) {

@@ -15,6 +15,8 @@ struct Entry {
   int (*chain)(int applies, const neptune_hip_apply_geom_t*, const void* const*, void*, hipStream_t, const neptune_hip_launch_cfg_t*);
   // the monitored launch (apply_launch.hpp launch_apply_norm): the apply and the update norm into a device scalar
   int (*apply_norm)(const neptune_hip_apply_geom_t*, const void* const*, void*, void* sum_out, hipStream_t, const neptune_hip_launch_cfg_t*);
+  // the dot-monitored launch (launch_apply_dot): the apply and sum new * old into a device scalar
+  int (*apply_dot)(const neptune_hip_apply_geom_t*, const void* const*, void*, void* dot_out, hipStream_t, const neptune_hip_launch_cfg_t*);
 };
 const Entry& lap2d5();
 const Entry& lap3d7();

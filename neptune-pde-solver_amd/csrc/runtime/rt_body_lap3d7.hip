@@ -26,6 +26,11 @@ int apply_norm(const neptune_hip_apply_geom_t* g, const void* const* in, void* o
   if (rc != NEPTUNE_HIP_OK) return rc;
   return launch_apply_norm<B, B::T, B::RANK, B::NIN, B::FP>(B{}, g, in, out, sum_out, stream, cfg);
 }
+int apply_dot(const neptune_hip_apply_geom_t* g, const void* const* in, void* out, void* dot_out, hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
+  const int rc = geom_check_radius(g, B::radius);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  return launch_apply_dot<B, B::T, B::RANK, B::NIN, B::FP>(B{}, g, in, out, dot_out, stream, cfg);
+}
 int variant(const neptune_hip_apply_geom_t* g, const neptune_hip_launch_cfg_t* cfg) { return pick_march_variant<B::T, B::RANK, B::FP>(g, cfg); }
 int chain(int applies, const neptune_hip_apply_geom_t* g, const void* const* in, void* out, hipStream_t stream, const neptune_hip_launch_cfg_t* cfg) {
   return applies == 2 ? launch_apply_twice<B, B::T, B::RANK, 1, B::FP>(B{}, g, in, out, stream, cfg)
@@ -33,7 +38,7 @@ int chain(int applies, const neptune_hip_apply_geom_t* g, const void* const* in,
 }
 }  // namespace
 const Entry& lap3d7() {
-  static const Entry e = {apply, plan, variant, chain, apply_norm};
+  static const Entry e = {apply, plan, variant, chain, apply_norm, apply_dot};
   return e;
 }
 }  // namespace rtbody

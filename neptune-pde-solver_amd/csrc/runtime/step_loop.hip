@@ -1,8 +1,9 @@
 // step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (stream scope, graph cache, replay,
 // grouping choice) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
 // neptune_hip_step_loop_chain (one-level schemes, two fields), neptune_hip_step_loop_leapfrog (two-level schemes, three or
-// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields).  Host code
-// only (its own translation unit: builds in seconds, linked into libneptune_hip.so); it launches through the public C API.
+// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and neptune_hip_cg_solve,
+// whose iteration the same engine replays.  Its own translation unit (builds in seconds, linked into libneptune_hip.so):
+// host code that launches applies through the public C API, plus the solver's few vector kernels (cg_kernels.hpp).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -11,7 +12,8 @@
 #include <vector>
 
 #include "../../../include/neptune_hip.h"
-#include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no kernel is instantiated here)
+#include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no apply kernel is instantiated here)
+#include "../kernels/cg_kernels.hpp"
 
 using namespace neptune_hip;
 
@@ -280,6 +282,10 @@ int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last leapf
 int64_t g_system_counts[2] = {0, 0}; // steps / graph launches of the last system loop
 void* g_until_sum = nullptr;            // the until loop's device scalar (one element), released with the graphs
 int64_t g_until_counts[3] = {0, 0, 0};  // monitored checked steps / fallback checked steps / checks of the last until loop
+void* g_cg_ws = nullptr;                // the solver's device block: CgScalars, then the partials of its own kernels; grown on demand
+size_t g_cg_ws_bytes = 0;
+int64_t g_cg_counts[3] = {0, 0, 0};     // dot-monitored iterations / fallback iterations / checks of the last cg_solve
+constexpr size_t kCgScalarBytes = 64;   // room for CgScalars<double>, keeps the partials 16-byte aligned
 
 // ---------------------------------------------------------------- the one-level loop on a stream scope
 // `steps` applies from fields[0] (the state) into fields[steps % 2]: what neptune_hip_step_loop_chain is once its arguments
@@ -357,6 +363,11 @@ __attribute__((visibility("hidden"))) void step_loop_destroy_graphs() {
   if (g_until_sum) {
     (void)hipFree(g_until_sum);
     g_until_sum = nullptr;
+  }
+  if (g_cg_ws) {
+    (void)hipFree(g_cg_ws);
+    g_cg_ws = nullptr;
+    g_cg_ws_bytes = 0;
   }
 }
 }  // namespace neptune_hip
@@ -605,6 +616,216 @@ int neptune_hip_step_loop_system(neptune_hip_group_fn fn, const neptune_hip_appl
   const int rc = replay(key, sc, 1, steps, from, 16, launch, &g_system_counts[1]);
   if (rc == NEPTUNE_HIP_OK) g_system_counts[0] = steps;
   return rc;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- conjugate gradients on a stream scope
+namespace {
+// the flat kernels' grids: exact for the 16-byte form (one vector per lane), capped for the grid-stride scalar form
+struct CgFlatGrid { bool vec; uint32_t blocks; };
+CgFlatGrid cg_flat_grid(int64_t n, size_t elem, std::initializer_list<const void*> ptrs) {
+  bool aligned = true;
+  for (const void* q : ptrs) aligned = aligned && (uintptr_t)q % 16 == 0;
+  const int64_t nv = n / (int64_t)(16 / elem), vblocks = nv > 0 ? (nv + 255) / 256 : 1;
+  if (aligned && vblocks <= 0x7fffffffLL) return {true, (uint32_t)vblocks};
+  const int64_t want = (n + 255) / 256;
+  return {false, (uint32_t)(want < 256 * 32 ? want : 256 * 32)};
+}
+
+template <class T>
+int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body,
+                   const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[3], const void* const* in_rest,
+                   int64_t max_iters, int64_t check_every, double tol2, void* trace, const neptune_hip_launch_cfg_t* cfg,
+                   int64_t* iters_done, double* rr0_out, double* rr_last) {
+  const int dtype = sizeof(T) == 8 ? NEPTUNE_HIP_F64 : NEPTUNE_HIP_F32;
+  T* const r = static_cast<T*>(work[0]);
+  T* const p = static_cast<T*>(work[1]);
+  T* const q = static_cast<T*>(work[2]);
+  // the box all five fields share, and Omega in its physical coordinates, on the kernels' (I, J, K) axes
+  CgBoxParams B;
+  int64_t n = 1;
+  {
+    int64_t shape[3], lo[3], hi[3];
+    for (int d = 0; d < g->rank; ++d) {
+      shape[d] = g->out_ub[d] - g->out_lb[d];
+      lo[d] = std::max(g->lb[d] - g->out_lb[d], g->region_lb[d]);
+      hi[d] = std::min(g->ub[d] - g->out_lb[d], g->region_ub[d]);
+      n *= shape[d];
+    }
+    auto axes = [&](const int64_t* src, int64_t* dst, int64_t fill) {
+      if (g->rank == 3) to_axes<3>(src, dst, fill);
+      else if (g->rank == 2) to_axes<2>(src, dst, fill);
+      else to_axes<1>(src, dst, fill);
+    };
+    axes(shape, B.n, 1);
+    axes(lo, B.lo, 0);
+    axes(hi, B.hi, 1);
+  }
+  const int64_t nchunk = (B.n[2] + 255) / 256;
+  const dim3 init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
+  const int64_t init_blocks = (int64_t)init_grid.x * init_grid.y;
+  const CgFlatGrid upd = cg_flat_grid(n, sizeof(T), {p, q, x, r}), dir = cg_flat_grid(n, sizeof(T), {r, p});
+
+  // the device block: the scalars, then room for the partials of the init and update kernels
+  const size_t need = kCgScalarBytes + (size_t)std::max<int64_t>(init_blocks, upd.blocks) * sizeof(T);
+  if (need > g_cg_ws_bytes) {
+    std::lock_guard<std::mutex> lk(g_loop_mu);   // cached graphs hold the old block's address: their keys do too
+    if (g_cg_ws) {
+      NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+      NEPTUNE_HIP_CHECK(hipFree(g_cg_ws));
+    }
+    g_cg_ws = nullptr;
+    g_cg_ws_bytes = 0;
+    NEPTUNE_HIP_CHECK(hipMalloc(&g_cg_ws, need));
+    g_cg_ws_bytes = need;
+  }
+  CgScalars<T>* const scal = static_cast<CgScalars<T>*>(g_cg_ws);
+  T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_cg_ws) + kCgScalarBytes);
+  T* const tr = static_cast<T*>(trace);
+  const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
+
+  auto apply_plain = [&](const void* in0, void* out) -> int {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    ins[0] = in0;
+    for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
+    return fn ? fn(g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(body, g, ins, out, (void*)sc.stream, c);
+  };
+  auto read_rr = [&]() -> double {
+    T h = 0;
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, &scal->rr, sizeof(T), hipMemcpyDeviceToHost, sc.stream));
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+    return (double)h;
+  };
+
+  // set-up: q = A(x), r = p = b - q on Omega, rr_0.  An apply stores nothing outside its launch region, and the flat update
+  // reads q everywhere: where the region is not the whole box, q starts as +0 and stays so out there.
+  bool whole = true;
+  for (int d = 0; d < g->rank; ++d) whole = whole && g->region_lb[d] <= 0 && g->region_ub[d] >= g->out_ub[d] - g->out_lb[d];
+  if (!whole) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
+  int rc = apply_plain(x, q);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  hipLaunchKernelGGL(neptune_cg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, static_cast<const T*>(b), (const T*)q, r, p, partials);
+  hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, init_blocks, scal, (T*)nullptr, (int64_t)0, true);
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  double rr = read_rr();
+  if (rr0_out) *rr0_out = rr;
+  if (rr_last) *rr_last = rr;
+  if (rr <= tol2 || max_iters == 0) return NEPTUNE_HIP_OK;
+
+  LoopKey key;
+  init_key(key, fn, fn ? -1 : body, g, cfg, sc.stream);
+  key.n_out = -1;   // no other loop's key: the solver's iteration
+  key.more[0] = (group_fn)fn_dot;
+  key.fields[0] = x; key.fields[1] = r; key.fields[2] = p; key.fields[3] = q;
+  key.fields_b[0] = g_cg_ws;
+  key.fields_b[2] = trace;
+  key.through[0] = (int)(max_iters < 0x7fffffff ? max_iters : 0x7fffffff);   // the trace's length is a kernel argument
+  for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in_rest[i - 1];
+
+  // one iteration; kind 1: q = A(p) and pq out of one dot-monitored launch, kind 2: a plain launch and neptune_hip_dot.
+  // NEPTUNE_HIP_EUNSUPPORTED comes from the dot-monitored entry alone, which then has launched nothing.
+  auto iteration = [&](int kind, int&) -> int {
+    int rc;
+    if (kind == 1) {
+      const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+      ins[0] = p;
+      for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
+      rc = fn ? fn_dot(g, ins, q, &scal->pq, (void*)sc.stream, c)
+              : neptune_hip_apply_builtin_dot(body, g, ins, q, &scal->pq, (void*)sc.stream, c);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+      key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
+    } else {
+      rc = apply_plain(p, q);
+      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+      rc = neptune_hip_dot(dtype, g, q, p, &scal->pq, (void*)sc.stream);
+      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+    }
+    if (upd.vec) hipLaunchKernelGGL(neptune_cg_update_v<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)p, (const T*)q, static_cast<T*>(x), r, partials);
+    else hipLaunchKernelGGL(neptune_cg_update<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)p, (const T*)q, static_cast<T*>(x), r, partials);
+    hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, (int64_t)upd.blocks, scal, tr, max_iters, false);
+    if (dir.vec) hipLaunchKernelGGL(neptune_cg_direction_v<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)r, p);
+    else hipLaunchKernelGGL(neptune_cg_direction<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)r, p);
+    NEPTUNE_HIP_CHECK(hipGetLastError());
+    return NEPTUNE_HIP_OK;
+  };
+
+  bool fused_ok = fn ? fn_dot != nullptr : true;   // false once the dot-monitored entry has refused this geometry
+  int64_t done = 0;
+  int state = 0;   // an iteration leaves no rotation behind: the device block carries it
+  while (done < max_iters) {
+    const int64_t block = check_every < max_iters - done ? check_every : max_iters - done;
+    // graphs of 8 iterations (about 40 kernel nodes), as the other loops amortise a graph launch over 16 applies
+    rc = NEPTUNE_HIP_EUNSUPPORTED;
+    if (fused_ok) {
+      rc = replay(key, sc, 1, block, state, 8, iteration);
+      if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused_ok = false;   // from the block's first launch: nothing of this block has run
+    }
+    if (!fused_ok && rc == NEPTUNE_HIP_EUNSUPPORTED) rc = replay(key, sc, 2, block, state, 8, iteration);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    g_cg_counts[fused_ok ? 0 : 1] += block;
+    done += block;
+    if (iters_done) *iters_done = done;
+    rr = read_rr();
+    ++g_cg_counts[2];
+    if (rr_last) *rr_last = rr;
+    if (rr <= tol2) break;   // false for a NaN: such a solve runs to max_iters
+  }
+  return NEPTUNE_HIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void neptune_hip_cg_counts(int64_t* fused, int64_t* fallback, int64_t* checks) {
+  if (fused) *fused = g_cg_counts[0];
+  if (fallback) *fallback = g_cg_counts[1];
+  if (checks) *checks = g_cg_counts[2];
+}
+
+int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                         const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[3], const void* const* in_rest,
+                         int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
+                         const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
+  if (iters_done) *iters_done = 0;
+  if (rr0) *rr0 = 0.0;
+  if (rr_last) *rr_last = 0.0;
+  if (!g || !x || !b || !work || !work[0] || !work[1] || !work[2] || max_iters < 0 || check_every < 1) return NEPTUNE_HIP_EINVAL;
+  if (geom_validate(g) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;
+  if (g->num_inputs > 1 && !in_rest) return NEPTUNE_HIP_EINVAL;
+  for (int i = 1; i < g->num_inputs; ++i)
+    if (!in_rest[i - 1]) return NEPTUNE_HIP_EINVAL;
+  // the iteration feeds the result q back as input 0 (through p): one box for both
+  for (int d = 0; d < g->rank; ++d)
+    if (g->in_lb[0][d] != g->out_lb[d] || g->in_ub[0][d] != g->out_ub[d]) return NEPTUNE_HIP_EINVAL;
+  int dtype = dtype_of_fn;
+  if (!fn) {
+    if (body < 0 || body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
+    dtype = body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64;
+  }
+  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
+  const size_t elem = dtype == NEPTUNE_HIP_F64 ? 8 : 4;
+  const size_t bytes = geom_box_bytes(g->out_lb, g->out_ub, g->rank, elem);
+  const void* const five[5] = {x, b, work[0], work[1], work[2]};
+  for (int a = 0; a < 5; ++a) {
+    if ((uintptr_t)five[a] % elem != 0) return NEPTUNE_HIP_EINVAL;
+    for (int o = 0; o < a; ++o)
+      if (buffers_overlap(five[a], bytes, five[o], bytes)) return NEPTUNE_HIP_EINVAL;
+    if (trace && buffers_overlap(trace, (size_t)(2 * max_iters) * elem, five[a], bytes)) return NEPTUNE_HIP_EINVAL;
+  }
+  if (trace && (uintptr_t)trace % elem != 0) return NEPTUNE_HIP_EINVAL;
+  {
+    // rr is read back after every block: not while the caller's stream is being captured
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return NEPTUNE_HIP_EINVAL;
+  }
+  ensure_init();
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  return dtype == NEPTUNE_HIP_F64
+             ? cg_solve_typed<double>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last)
+             : cg_solve_typed<float>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last);
 }
 
 }  // extern "C"

@@ -126,6 +126,11 @@ SIGNATURES = {
     "neptune_hip_step_loop_until": (_i, [_vp, _vp, _i, _i, _geom_p, _vpp, _vpp, _i64, _i64, _dbl, _vp, _cfg_p, _i64p,
                                          C.POINTER(C.c_double)]),
     "neptune_hip_until_loop_counts": (None, [_i64p, _i64p, _i64p]),
+    "neptune_hip_apply_builtin_dot": (_i, [_i, _geom_p, _vpp, _vp, _vp, _vp, _cfg_p]),
+    "neptune_hip_dot": (_i, [_i, _geom_p, _vp, _vp, _vp, _vp]),
+    "neptune_hip_cg_solve": (_i, [_vp, _vp, _i, _i, _geom_p, _vp, _vp, _vpp, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_cg_counts": (None, [_i64p, _i64p, _i64p]),
     "neptune_hip_kernel_name": (C.c_char_p, [_i]),
     "neptune_hip_apply_builtin_variant": (_i, [_i, _geom_p, _cfg_p]),
     "neptune_hip_march_variant_count": (_i, [_i]),

@@ -143,6 +143,95 @@ def step_loop_until(body, a: DeviceField, b: DeviceField, bounds: Box, max_steps
     return done.value, last.value
 
 
+def apply_dot(body, inputs: Sequence[DeviceField], out: DeviceField, bounds: Box, dot_out=None,
+              region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
+    """a dot-monitored launch: out = apply(inputs) {bounds} exactly as apply_builtin computes it, and D = sum new * old over
+    the cells of `bounds` in the launch region (old = inputs[0] at the same physical index, one rounding per product) in the
+    field's element type -- p . A(p) when inputs[0] = p.  `body`: a built-in body id, or the dot entry of a lowered apply
+    (LoweredModule.dot_entry).  `dot_out`, the return value and the refusal (None, nothing launched): as apply_norm."""
+    import torch
+    lib = _capi.load()
+    g = geom_for(inputs, out, bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    dst = dot_out if dot_out is not None else torch.empty(1, dtype=out.tensor.dtype, device=out.tensor.device)
+    cfg_p = C.byref(cfg) if cfg is not None else None
+    if hasattr(body, "fn"):
+        if body.fn_dot is None:
+            raise ValueError(f"{body.symbol}: no dot-monitored launch (compile the module with dot_entries=True)")
+        rc, what = body.fn_dot(C.byref(g), _in_array(inputs), out.ptr, dst.data_ptr(), st, cfg_p), body.symbol
+    else:
+        rc = lib.neptune_hip_apply_builtin_dot(body, C.byref(g), _in_array(inputs), out.ptr, dst.data_ptr(), st, cfg_p)
+        what = "neptune_hip_apply_builtin_dot"
+    if rc == _capi.EUNSUPPORTED:
+        return None
+    _capi.check(rc, what)
+    if dot_out is not None:
+        return dot_out
+    torch.cuda.synchronize()
+    return float(dst.item())
+
+
+def dot(a: DeviceField, b: DeviceField, bounds: Box, region: Optional[Box] = None, dot_out=None, stream: Optional[int] = None):
+    """sum a * b over the cells of `bounds` in the launch region, in one read-only pass (neptune_hip_dot): what apply_dot
+    returns for out = a, inputs[0] = b, in another summation order.  `dot_out` and the return value: as apply_dot."""
+    import torch
+    lib = _capi.load()
+    g = geom_for([b], a, bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    dst = dot_out if dot_out is not None else torch.empty(1, dtype=a.tensor.dtype, device=a.tensor.device)
+    _capi.check(lib.neptune_hip_dot(a.dtype, C.byref(g), a.ptr, b.ptr, dst.data_ptr(), st), "neptune_hip_dot")
+    if dot_out is not None:
+        return dot_out
+    torch.cuda.synchronize()
+    return float(dst.item())
+
+
+def cg_counts():
+    """(iterations whose q = A(p) ran as a dot-monitored launch, iterations that ran plain launch + neptune_hip_dot, read-backs
+    after blocks of iterations) of the last cg_solve call"""
+    fused, fallback, checks = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _capi.load().neptune_hip_cg_counts(C.byref(fused), C.byref(fallback), C.byref(checks))
+    return fused.value, fallback.value, checks.value
+
+
+def cg_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int, tol2: float, check_every: int = 1,
+             others: Sequence[DeviceField] = (), trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
+             work: Optional[Sequence[DeviceField]] = None, region: Optional[Box] = None, stream: Optional[int] = None):
+    """solve A(x) = b by conjugate gradients on the device (neptune_hip_cg_solve): `entry` is a built-in body id or a lowered
+    apply's geometry-level entry whose input 0 has the result's box; `others` are its fixed inputs 1...  x: initial guess in,
+    solution out; its cells outside `bounds` (x region) are boundary data and are never written.  The loop stops when
+    r . r <= tol2 (checked every `check_every` iterations) or after max_iters iterations.  dot: the apply's dot entry
+    (LoweredModule.dot_entry), "auto": entry's own if it has one (built-in bodies do), "fallback" or None: a plain launch
+    and a separate dot product per iteration.  work: three fields like x for r, p, q (allocated here when None).
+    Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a numpy array of shape (iters, 2) holding
+    (p . A(p) of iteration k, r . r after it).  cg_counts() tells which path the iterations took."""
+    import torch
+    lib = _capi.load()
+    others = list(others)
+    if work is None:
+        work = [DeviceField.empty_like(x) for _ in range(3)]
+    g = geom_for([x] + others, work[2], bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    is_entry = hasattr(entry, "fn")
+    fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
+    if isinstance(dot, str):
+        if dot not in ("auto", "fallback"):
+            raise ValueError('cg_solve: dot is "auto", "fallback", None or a dot entry')
+        dot = entry if (dot == "auto" and is_entry) else None
+    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    tr = torch.zeros(2 * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    warr = (C.c_void_p * 3)(*[f.ptr for f in work])
+    rest = _in_array(others) if others else None
+    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    rc = lib.neptune_hip_cg_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, warr, rest, max_iters,
+                                  check_every, tol2, tr.data_ptr() if trace else None, st,
+                                  C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    _capi.check(rc, "neptune_hip_cg_solve")
+    if trace:
+        return done.value, rr0.value, last.value, tr.cpu().numpy()[:2 * done.value].reshape(-1, 2)
+    return done.value, rr0.value, last.value
+
+
 def _as_field(x) -> DeviceField:
     """a DeviceField as it is; a contiguous torch CUDA tensor as a field with a zero-based box"""
     if isinstance(x, DeviceField):

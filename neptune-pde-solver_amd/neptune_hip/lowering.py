@@ -67,24 +67,29 @@ def verify(text: str, reduce_kinds: bool = False) -> None:
 
 NORM_ENTRIES_LINE = "// neptune-hip-option: norm-entries\n"
 REDUCE_KINDS_LINE = "// neptune-hip-option: reduce-kinds\n"
+DOT_ENTRIES_LINE = "// neptune-hip-option: dot-entries\n"
 
 
-def with_options(text: str, norm_entries: bool = False, reduce_kinds: bool = False) -> str:
+def with_options(text: str, norm_entries: bool = False, reduce_kinds: bool = False, dot_entries: bool = False) -> str:
     """the module text with its lowering options: they travel in the text, one comment line each
     (include/neptune_lowering.h), so the cache key of a module covers them"""
     if reduce_kinds and REDUCE_KINDS_LINE.strip() not in text:
         text = REDUCE_KINDS_LINE + text
+    if dot_entries and DOT_ENTRIES_LINE.strip() not in text:
+        text = DOT_ENTRIES_LINE + text
     if norm_entries and NORM_ENTRIES_LINE.strip() not in text:
         text = NORM_ENTRIES_LINE + text
     return text
 
 
-def to_hip(text: str, norm_entries: bool = False, reduce_kinds: bool = False):
+def to_hip(text: str, norm_entries: bool = False, reduce_kinds: bool = False, dot_entries: bool = False):
     """-> (HIP source, report dict).  norm_entries: lowering option norm-entries (eligible applies also export their
     monitored launch <fn>_<k>__geomN; the report names it as "norm_symbol").  reduce_kinds: lowering option reduce-kinds
-    (neptune_ir.reduce kinds max | min | l1 | l2 verify and lower; a fused apply's report entry carries "reduce_kind")"""
+    (neptune_ir.reduce kinds max | min | l1 | l2 verify and lower; a fused apply's report entry carries "reduce_kind").
+    dot_entries: lowering option dot-entries (the applies norm-entries names also export their dot-monitored launch
+    <fn>_<k>__geomD; the report names it as "dot_symbol")"""
     lib = _load()
-    text = with_options(text, norm_entries, reduce_kinds)
+    text = with_options(text, norm_entries, reduce_kinds, dot_entries)
     src, rep, diag = C.c_void_p(), C.c_void_p(), C.c_void_p()
     if lib.neptune_lowering_to_hip(text.encode(), C.byref(src), C.byref(rep), C.byref(diag)) != 0:
         raise LoweringError(_take(lib, diag))
@@ -143,13 +148,14 @@ def module_hash(text: str) -> str:
 
 def compile_module(text: str, so_path: Optional[os.PathLike] = None, use_cache: bool = True,
                    cache_directory: Optional[os.PathLike] = None, load: bool = True,
-                   norm_entries: bool = False, reduce_kinds: bool = False) -> Optional["LoweredModule"]:
+                   norm_entries: bool = False, reduce_kinds: bool = False,
+                   dot_entries: bool = False) -> Optional["LoweredModule"]:
     """lower + hipcc (gfx950) + load.  Compiling needs no GPU; loading needs libneptune_hip.so.  Without an explicit
     so_path the object lives in `cache_directory` (default: cache_dir()) under its module_hash.  load=False only fills
     the cache (what the profiling scripts do before they start rocprofv3: hipcc is started with an environment scrubbed
     of LD_PRELOAD / ROCP* / HSA_TOOLS_*, csrc/lowering/capi.cpp, but a profiled run should be a pure cache hit)."""
     lib = _load()
-    text = with_options(text, norm_entries, reduce_kinds)   # lowering options: see to_hip
+    text = with_options(text, norm_entries, reduce_kinds, dot_entries)   # lowering options: see to_hip
     if so_path is None:
         directory = Path(cache_directory) if cache_directory else cache_dir()
         directory.mkdir(parents=True, exist_ok=True)
@@ -209,6 +215,14 @@ class GeomEntry:
             self.fn_norm.restype = C.c_int
             self.fn_norm.argtypes = [C.POINTER(_capi.ApplyGeom), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(_capi.LaunchCfg)]
+
+        # the dot-monitored launch (lowering option dot-entries; neptune_hip_apply_dot_fn), or None
+        sym = info.get("dot_symbol") or ""
+        self.fn_dot = getattr(module.lib, sym) if sym else None
+        if self.fn_dot is not None:
+            self.fn_dot.restype = C.c_int
+            self.fn_dot.argtypes = [C.POINTER(_capi.ApplyGeom), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(_capi.LaunchCfg)]
 
     def __call__(self, geom, in_array, out_ptr, stream, cfg=None) -> int:
         return self.fn(C.byref(geom), in_array, out_ptr, stream, C.byref(cfg) if cfg is not None else None)
@@ -279,6 +293,14 @@ class LoweredModule:
         cands = [a for a in self.report["applies"] if a["function"] == function and a.get("norm_symbol")]
         if index >= len(cands):
             raise KeyError(f"@{function} has no apply #{index} with a monitored launch (compile with norm_entries=True)")
+        return GeomEntry(self, cands[index])
+
+    def dot_entry(self, function: str, index: int = 0) -> "GeomEntry":
+        """the `index`-th apply of @function that exports a dot-monitored launch (module compiled with dot_entries=True): a
+        GeomEntry whose fn_dot is set -- what neptune_hip.apply.apply_dot launches and cg_solve iterates with"""
+        cands = [a for a in self.report["applies"] if a["function"] == function and a.get("dot_symbol")]
+        if index >= len(cands):
+            raise KeyError(f"@{function} has no apply #{index} with a dot-monitored launch (compile with dot_entries=True)")
         return GeomEntry(self, cands[index])
 
     def group_entry(self, function: str, index: int = 0) -> "GroupEntry":
