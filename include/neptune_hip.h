@@ -441,9 +441,37 @@ int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_do
                          const void *const *in_rest, int64_t max_iters, int64_t check_every, double tol2, void *trace,
                          void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0,
                          double *rr_last);
-/* the last neptune_hip_cg_solve call of this process: iterations whose q = A(p) ran as a dot-monitored launch, iterations
+/* the last neptune_hip_cg_solve / neptune_hip_pcg_solve call of this process: iterations whose q = A(p) ran as a dot-monitored launch, iterations
  * that ran the fallback, and read-backs after blocks (the read of rr_0 is not counted) */
 void neptune_hip_cg_counts(int64_t *fused, int64_t *fallback, int64_t *checks);
+
+/* The same solve with a diagonal (Jacobi) preconditioner fused into the solver's kernels.  Everything is as
+ * for neptune_hip_cg_solve -- element type T, no FMA, the fixed summation tree, no atomics, Omega, the work fields, the
+ * blocks of check_every iterations, the fallback, the replay schedule -- except where stated here.  minv: a device field in
+ * the box of x holding M^-1; it must be finite on every cell of the box, is meant to be positive (not checked on the
+ * device), and cells outside Omega should hold 1.  z = minv * r is never stored: the kernels that stream r form it in
+ * registers, one rounding, from the same two operands wherever it is needed, so it has the same bits everywhere.
+ *   set-up     q = A(x);  r = b - q on Omega, +0 elsewhere;  p = minv * r on Omega (one rounding), +0 elsewhere through the
+ *              same select;  rz_0 = sum r * (minv * r) (two roundings per term: z = minv * r, then r * z);  rr_0 = sum r * r
+ *   iteration  q = A(p), pq = sum_Omega q * p out of the same launch (fn_dot; the fallback of neptune_hip_cg_solve);
+ *              alpha = rz / pq;  x = x + (alpha p), r = r - (alpha q) on the whole flat buffers, and out of that launch, from
+ *              the freshly stored r, rz' = sum r * (minv * r) and rr' = sum r * r;
+ *              beta = rz' / rz;  p = (minv * r) + (beta p) on the whole flat buffers;  rz <- rz', rr <- rr'
+ * An iteration that finds rz == 0 or pq == 0 uses alpha = beta = 0.  The loop stops on rr <= tol2 -- the true residual,
+ * exactly the meaning tol2 has in neptune_hip_cg_solve; a NaN never stops it; *rr0 and *rr_last are rr_0 and the last rr
+ * read.  trace: NULL, or a DEVICE pointer to 3 * max_iters values of T: iteration k stores pq_k, rz_(k+1), rr_(k+1) at
+ * [3 k], [3 k + 1], [3 k + 2].  The counters are those of neptune_hip_cg_counts.  With minv = 1 everywhere the recurrences
+ * are those of neptune_hip_cg_solve (1 * r is r, rz is rr).
+ * NEPTUNE_HIP_EINVAL, nothing launched: the refusals of neptune_hip_cg_solve, and a null minv, a minv that is misaligned
+ * for T, a minv that overlaps any of x, b, r, p, q or the trace. */
+int neptune_hip_pcg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                          const neptune_hip_apply_geom_t *g, void *x, const void *b, const void *minv,
+                          void *const work[3], const void *const *in_rest, int64_t max_iters, int64_t check_every,
+                          double tol2, void *trace, void *stream, const neptune_hip_launch_cfg_t *cfg,
+                          int64_t *iters_done, double *rr0, double *rr_last);
+/* rz_0 = sum r * (minv * r) after the set-up of the last neptune_hip_pcg_solve call of this process (0 when it was refused):
+ * with *rr0 and the trace, every scalar the recurrences used -- alpha_0 = rz_0 / pq_0 -- so that a run can be replayed */
+double neptune_hip_pcg_rz0(void);
 
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */

@@ -1,9 +1,10 @@
 // step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (stream scope, graph cache, replay,
 // grouping choice) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
 // neptune_hip_step_loop_chain (one-level schemes, two fields), neptune_hip_step_loop_leapfrog (two-level schemes, three or
-// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and neptune_hip_cg_solve,
-// whose iteration the same engine replays.  Its own translation unit (builds in seconds, linked into libneptune_hip.so):
-// host code that launches applies through the public C API, plus the solver's few vector kernels (cg_kernels.hpp).
+// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and neptune_hip_cg_solve /
+// neptune_hip_pcg_solve, whose iteration the same engine replays.  Its own translation unit (builds in seconds, linked into
+// libneptune_hip.so): host code that launches applies through the public C API, plus the solvers' few vector kernels
+// (cg_kernels.hpp, pcg_kernels.hpp).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no apply kernel is instantiated here)
 #include "../kernels/cg_kernels.hpp"
+#include "../kernels/pcg_kernels.hpp"
 
 using namespace neptune_hip;
 
@@ -282,10 +284,12 @@ int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last leapf
 int64_t g_system_counts[2] = {0, 0}; // steps / graph launches of the last system loop
 void* g_until_sum = nullptr;            // the until loop's device scalar (one element), released with the graphs
 int64_t g_until_counts[3] = {0, 0, 0};  // monitored checked steps / fallback checked steps / checks of the last until loop
-void* g_cg_ws = nullptr;                // the solver's device block: CgScalars, then the partials of its own kernels; grown on demand
+void* g_cg_ws = nullptr;                // the solver's device block: CgScalars / PcgScalars, then the partials of its own kernels; grown on demand
 size_t g_cg_ws_bytes = 0;
-int64_t g_cg_counts[3] = {0, 0, 0};     // dot-monitored iterations / fallback iterations / checks of the last cg_solve
-constexpr size_t kCgScalarBytes = 64;   // room for CgScalars<double>, keeps the partials 16-byte aligned
+int64_t g_cg_counts[3] = {0, 0, 0};     // dot-monitored iterations / fallback iterations / checks of the last cg_solve / pcg_solve
+double g_pcg_rz0 = 0.0;                 // r . (minv r) after the set-up of the last pcg_solve
+constexpr size_t kCgScalarBytes = 64;   // room for CgScalars<double> and PcgScalars<double>, keeps the partials 16-byte aligned
+static_assert(sizeof(CgScalars<double>) <= kCgScalarBytes && sizeof(PcgScalars<double>) <= kCgScalarBytes, "the scalar block");
 
 // ---------------------------------------------------------------- the one-level loop on a stream scope
 // `steps` applies from fields[0] (the state) into fields[steps % 2]: what neptune_hip_step_loop_chain is once its arguments
@@ -620,7 +624,7 @@ int neptune_hip_step_loop_system(neptune_hip_group_fn fn, const neptune_hip_appl
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- conjugate gradients on a stream scope (DESIGN 3.11)
+// ---------------------------------------------------------------- conjugate gradients on a stream scope (DESIGN 3.11, 3.12)
 namespace {
 // the flat kernels' grids: exact for the 16-byte form (one vector per lane), capped for the grid-stride scalar form
 struct CgFlatGrid { bool vec; uint32_t blocks; };
@@ -633,15 +637,18 @@ CgFlatGrid cg_flat_grid(int64_t n, size_t elem, std::initializer_list<const void
   return {false, (uint32_t)(want < 256 * 32 ? want : 256 * 32)};
 }
 
+// minv = nullptr: the solver of 3.11 on the kernels of cg_kernels.hpp; a field: the Jacobi-preconditioned solver of 3.12 on those
+// of pcg_kernels.hpp.  Everything else -- the apply launches, the blocks, the replay schedule, the counters -- is one code.
 template <class T>
 int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body,
-                   const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[3], const void* const* in_rest,
-                   int64_t max_iters, int64_t check_every, double tol2, void* trace, const neptune_hip_launch_cfg_t* cfg,
+                   const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv_field, void* const work[3],
+                   const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, const neptune_hip_launch_cfg_t* cfg,
                    int64_t* iters_done, double* rr0_out, double* rr_last) {
   const int dtype = sizeof(T) == 8 ? NEPTUNE_HIP_F64 : NEPTUNE_HIP_F32;
   T* const r = static_cast<T*>(work[0]);
   T* const p = static_cast<T*>(work[1]);
   T* const q = static_cast<T*>(work[2]);
+  const T* const minv = static_cast<const T*>(minv_field);
   // the box all five fields share, and Omega in its physical coordinates, on the kernels' (I, J, K) axes
   CgBoxParams B;
   int64_t n = 1;
@@ -665,10 +672,11 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   const int64_t nchunk = (B.n[2] + 255) / 256;
   const dim3 init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
   const int64_t init_blocks = (int64_t)init_grid.x * init_grid.y;
-  const CgFlatGrid upd = cg_flat_grid(n, sizeof(T), {p, q, x, r}), dir = cg_flat_grid(n, sizeof(T), {r, p});
+  // (a null minv is 16-byte aligned: it does not decide the form)
+  const CgFlatGrid upd = cg_flat_grid(n, sizeof(T), {p, q, x, r, minv}), dir = cg_flat_grid(n, sizeof(T), {r, p, minv});
 
-  // the device block: the scalars, then room for the partials of the init and update kernels
-  const size_t need = kCgScalarBytes + (size_t)std::max<int64_t>(init_blocks, upd.blocks) * sizeof(T);
+  // the device block: the scalars, then room for the partials of the init and update kernels (two sums with a preconditioner)
+  const size_t need = kCgScalarBytes + (size_t)(minv ? 2 : 1) * (size_t)std::max<int64_t>(init_blocks, upd.blocks) * sizeof(T);
   if (need > g_cg_ws_bytes) {
     std::lock_guard<std::mutex> lk(g_loop_mu);   // cached graphs hold the old block's address: their keys do too
     if (g_cg_ws) {
@@ -681,6 +689,9 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
     g_cg_ws_bytes = need;
   }
   CgScalars<T>* const scal = static_cast<CgScalars<T>*>(g_cg_ws);
+  PcgScalars<T>* const pscal = static_cast<PcgScalars<T>*>(g_cg_ws);   // the same bytes: one of the two is in use
+  T* const pq_dev = minv ? &pscal->pq : &scal->pq;
+  T* const rr_dev = minv ? &pscal->rr : &scal->rr;
   T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_cg_ws) + kCgScalarBytes);
   T* const tr = static_cast<T*>(trace);
   const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
@@ -693,7 +704,7 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   };
   auto read_rr = [&]() -> double {
     T h = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, &scal->rr, sizeof(T), hipMemcpyDeviceToHost, sc.stream));
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, rr_dev, sizeof(T), hipMemcpyDeviceToHost, sc.stream));
     NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
     return (double)h;
   };
@@ -705,10 +716,24 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   if (!whole) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
   int rc = apply_plain(x, q);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  hipLaunchKernelGGL(neptune_cg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, static_cast<const T*>(b), (const T*)q, r, p, partials);
-  hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, init_blocks, scal, (T*)nullptr, (int64_t)0, true);
+  if (minv) {
+    hipLaunchKernelGGL(neptune_pcg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, init_blocks, static_cast<const T*>(b), (const T*)q, minv, r, p, partials);
+    hipLaunchKernelGGL(neptune_pcg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, init_blocks, pscal, (T*)nullptr, (int64_t)0, true);
+  } else {
+    hipLaunchKernelGGL(neptune_cg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, static_cast<const T*>(b), (const T*)q, r, p, partials);
+    hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, init_blocks, scal, (T*)nullptr, (int64_t)0, true);
+  }
   NEPTUNE_HIP_CHECK(hipGetLastError());
-  double rr = read_rr();
+  double rr;
+  if (minv) {   // rz_0 and rr_0 lie side by side
+    T h[2] = {0, 0};
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(h, &pscal->rz, 2 * sizeof(T), hipMemcpyDeviceToHost, sc.stream));
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+    g_pcg_rz0 = (double)h[0];
+    rr = (double)h[1];
+  } else {
+    rr = read_rr();
+  }
   if (rr0_out) *rr0_out = rr;
   if (rr_last) *rr_last = rr;
   if (rr <= tol2 || max_iters == 0) return NEPTUNE_HIP_OK;
@@ -720,6 +745,7 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   key.fields[0] = x; key.fields[1] = r; key.fields[2] = p; key.fields[3] = q;
   key.fields_b[0] = g_cg_ws;
   key.fields_b[2] = trace;
+  key.fields_b[3] = const_cast<T*>(minv);   // a graph captured with one preconditioner is never replayed with another
   key.through[0] = (int)(max_iters < 0x7fffffff ? max_iters : 0x7fffffff);   // the trace's length is a kernel argument
   for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in_rest[i - 1];
 
@@ -731,15 +757,24 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
       const void* ins[NEPTUNE_HIP_MAX_INPUTS];
       ins[0] = p;
       for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
-      rc = fn ? fn_dot(g, ins, q, &scal->pq, (void*)sc.stream, c)
-              : neptune_hip_apply_builtin_dot(body, g, ins, q, &scal->pq, (void*)sc.stream, c);
+      rc = fn ? fn_dot(g, ins, q, pq_dev, (void*)sc.stream, c)
+              : neptune_hip_apply_builtin_dot(body, g, ins, q, pq_dev, (void*)sc.stream, c);
       if (rc != NEPTUNE_HIP_OK) return rc;
       key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
     } else {
       rc = apply_plain(p, q);
       if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-      rc = neptune_hip_dot(dtype, g, q, p, &scal->pq, (void*)sc.stream);
+      rc = neptune_hip_dot(dtype, g, q, p, pq_dev, (void*)sc.stream);
       if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+    }
+    if (minv) {
+      if (upd.vec) hipLaunchKernelGGL(neptune_pcg_update_v<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)p, (const T*)q, minv, static_cast<T*>(x), r, partials);
+      else hipLaunchKernelGGL(neptune_pcg_update<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)p, (const T*)q, minv, static_cast<T*>(x), r, partials);
+      hipLaunchKernelGGL(neptune_pcg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, (int64_t)upd.blocks, pscal, tr, max_iters, false);
+      if (dir.vec) hipLaunchKernelGGL(neptune_pcg_direction_v<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)r, minv, p);
+      else hipLaunchKernelGGL(neptune_pcg_direction<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)r, minv, p);
+      NEPTUNE_HIP_CHECK(hipGetLastError());
+      return NEPTUNE_HIP_OK;
     }
     if (upd.vec) hipLaunchKernelGGL(neptune_cg_update_v<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)p, (const T*)q, static_cast<T*>(x), r, partials);
     else hipLaunchKernelGGL(neptune_cg_update<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)p, (const T*)q, static_cast<T*>(x), r, partials);
@@ -783,15 +818,17 @@ void neptune_hip_cg_counts(int64_t* fused, int64_t* fallback, int64_t* checks) {
   if (checks) *checks = g_cg_counts[2];
 }
 
-int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
-                         const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[3], const void* const* in_rest,
-                         int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
-                         const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+// the argument checks and the dispatch on the element type of both entries; pre: neptune_hip_pcg_solve (minv is required)
+static int cg_solve_checked(bool pre, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                            const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv, void* const work[3],
+                            const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
+                            const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
   g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
   if (iters_done) *iters_done = 0;
   if (rr0) *rr0 = 0.0;
   if (rr_last) *rr_last = 0.0;
   if (!g || !x || !b || !work || !work[0] || !work[1] || !work[2] || max_iters < 0 || check_every < 1) return NEPTUNE_HIP_EINVAL;
+  if (pre && !minv) return NEPTUNE_HIP_EINVAL;
   if (geom_validate(g) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;
   if (g->num_inputs > 1 && !in_rest) return NEPTUNE_HIP_EINVAL;
   for (int i = 1; i < g->num_inputs; ++i)
@@ -807,13 +844,16 @@ int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_do
   if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
   const size_t elem = dtype == NEPTUNE_HIP_F64 ? 8 : 4;
   const size_t bytes = geom_box_bytes(g->out_lb, g->out_ub, g->rank, elem);
+  const size_t trace_bytes = (size_t)((pre ? 3 : 2) * max_iters) * elem;
   const void* const five[5] = {x, b, work[0], work[1], work[2]};
   for (int a = 0; a < 5; ++a) {
     if ((uintptr_t)five[a] % elem != 0) return NEPTUNE_HIP_EINVAL;
     for (int o = 0; o < a; ++o)
       if (buffers_overlap(five[a], bytes, five[o], bytes)) return NEPTUNE_HIP_EINVAL;
-    if (trace && buffers_overlap(trace, (size_t)(2 * max_iters) * elem, five[a], bytes)) return NEPTUNE_HIP_EINVAL;
+    if (trace && buffers_overlap(trace, trace_bytes, five[a], bytes)) return NEPTUNE_HIP_EINVAL;
+    if (pre && buffers_overlap(minv, bytes, five[a], bytes)) return NEPTUNE_HIP_EINVAL;
   }
+  if (pre && ((uintptr_t)minv % elem != 0 || (trace && buffers_overlap(trace, trace_bytes, minv, bytes)))) return NEPTUNE_HIP_EINVAL;
   if (trace && (uintptr_t)trace % elem != 0) return NEPTUNE_HIP_EINVAL;
   {
     // rr is read back after every block: not while the caller's stream is being captured
@@ -824,8 +864,27 @@ int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_do
   ensure_init();
   StreamScope sc(reinterpret_cast<hipStream_t>(stream));
   return dtype == NEPTUNE_HIP_F64
-             ? cg_solve_typed<double>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last)
-             : cg_solve_typed<float>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last);
+             ? cg_solve_typed<double>(sc, fn, fn_dot, body, g, x, b, pre ? minv : nullptr, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last)
+             : cg_solve_typed<float>(sc, fn, fn_dot, body, g, x, b, pre ? minv : nullptr, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last);
+}
+
+int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                         const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[3], const void* const* in_rest,
+                         int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
+                         const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  return cg_solve_checked(false, fn, fn_dot, body, dtype_of_fn, g, x, b, nullptr, work, in_rest, max_iters, check_every, tol2, trace,
+                          stream, cfg, iters_done, rr0, rr_last);
+}
+
+double neptune_hip_pcg_rz0(void) { return g_pcg_rz0; }
+
+int neptune_hip_pcg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                          const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv, void* const work[3],
+                          const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
+                          const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  g_pcg_rz0 = 0.0;
+  return cg_solve_checked(true, fn, fn_dot, body, dtype_of_fn, g, x, b, minv, work, in_rest, max_iters, check_every, tol2, trace,
+                          stream, cfg, iters_done, rr0, rr_last);
 }
 
 }  // extern "C"

@@ -196,7 +196,8 @@ def cg_counts():
 
 def cg_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int, tol2: float, check_every: int = 1,
              others: Sequence[DeviceField] = (), trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
-             work: Optional[Sequence[DeviceField]] = None, region: Optional[Box] = None, stream: Optional[int] = None):
+             work: Optional[Sequence[DeviceField]] = None, region: Optional[Box] = None, stream: Optional[int] = None,
+             minv: Optional[DeviceField] = None):
     """solve A(x) = b by conjugate gradients on the device (neptune_hip_cg_solve): `entry` is a built-in body id or a lowered
     apply's geometry-level entry whose input 0 has the result's box; `others` are its fixed inputs 1...  x: initial guess in,
     solution out; its cells outside `bounds` (x region) are boundary data and are never written.  The loop stops when
@@ -204,7 +205,10 @@ def cg_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int,
     (LoweredModule.dot_entry), "auto": entry's own if it has one (built-in bodies do), "fallback" or None: a plain launch
     and a separate dot product per iteration.  work: three fields like x for r, p, q (allocated here when None).
     Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a numpy array of shape (iters, 2) holding
-    (p . A(p) of iteration k, r . r after it).  cg_counts() tells which path the iterations took."""
+    (p . A(p) of iteration k, r . r after it).  cg_counts() tells which path the iterations took.
+    minv: a field like x holding the inverse of a diagonal preconditioner (jacobi_minv): the solve is then
+    neptune_hip_pcg_solve, tol2 still bounds the true r . r, and the trace has shape (iters, 3): (p . A(p) of iteration k,
+    r . (minv r) after it, r . r after it)."""
     import torch
     lib = _capi.load()
     others = list(others)
@@ -219,17 +223,113 @@ def cg_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int,
             raise ValueError('cg_solve: dot is "auto", "fallback", None or a dot entry')
         dot = entry if (dot == "auto" and is_entry) else None
     fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
-    tr = torch.zeros(2 * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    cols = 2 if minv is None else 3
+    tr = torch.zeros(cols * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
     warr = (C.c_void_p * 3)(*[f.ptr for f in work])
     rest = _in_array(others) if others else None
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-    rc = lib.neptune_hip_cg_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, warr, rest, max_iters,
-                                  check_every, tol2, tr.data_ptr() if trace else None, st,
-                                  C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
-    _capi.check(rc, "neptune_hip_cg_solve")
+    tail = (warr, rest, max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
+            C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    if minv is None:
+        rc = lib.neptune_hip_cg_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, *tail)
+        _capi.check(rc, "neptune_hip_cg_solve")
+    else:
+        if minv.box != x.box or minv.dtype != x.dtype:
+            raise ValueError("cg_solve: minv must have the box and the element type of x")
+        rc = lib.neptune_hip_pcg_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, minv.ptr, *tail)
+        _capi.check(rc, "neptune_hip_pcg_solve")
     if trace:
-        return done.value, rr0.value, last.value, tr.cpu().numpy()[:2 * done.value].reshape(-1, 2)
+        return done.value, rr0.value, last.value, tr.cpu().numpy()[:cols * done.value].reshape(-1, cols)
     return done.value, rr0.value, last.value
+
+
+def pcg_rz0() -> float:
+    """r . (minv r) after the set-up of the last cg_solve(..., minv=...) call: with rr0 and the trace, every scalar the
+    recurrences used"""
+    return float(_capi.load().neptune_hip_pcg_rz0())
+
+
+def _omega(like: DeviceField, bounds: Box, region: Optional[Box]):
+    """Omega = bounds (logical) x launch region (physical) as physical [lo, hi) per dimension of `like`'s box"""
+    lo = [max(int(bounds[0][d]) - like.lb[d], 0 if region is None else int(region[0][d]), 0) for d in range(like.rank)]
+    hi = [min(int(bounds[1][d]) - like.lb[d], like.shape[d] if region is None else int(region[1][d]), like.shape[d])
+          for d in range(like.rank)]
+    return lo, hi
+
+
+def operator_diagonal(entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), reach=None,
+                      region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None) -> DeviceField:
+    """the diagonal of a LINEAR operator: a field like `like` holding A's diagonal entry on the cells of
+    Omega = bounds x region and +0 elsewhere.  `entry`, `others`, `bounds`, `region`: as cg_solve.  The operator is probed with
+    coloured unit vectors: with s_d = 2 reach_d + 1, each of the prod s_d colours c is a field that is 1 on the cells of Omega
+    whose offset from Omega's lower corner is = c (mod s) and 0 on every other cell of the box (the boundary cells too); one
+    plain launch per colour, and the result is copied at exactly those cells -- two cells of one colour are further apart than
+    the operator reaches, so each sees its own diagonal entry alone.  reach: an int or one int per dimension, how far A reads
+    from a cell; for a lowered entry it defaults to the entry's halo0 in every dimension (right for star and box stencils of
+    one radius; give it per dimension for an operator that reaches further along another dimension than along dim 0), for a
+    built-in body it is required.  One more launch guards the choice: a unit vector at the middle cell of Omega must not be
+    seen beyond `reach`, else ValueError (a NaN out there counts as seen).  Set-up work: prod s_d + 1 launches and torch
+    indexing, blocking.
+    An AFFINE operator (A(0) != 0: a source term inside the apply) gives a wrong answer: the probe returns A(0) + diagonal."""
+    import itertools
+    import torch
+    if reach is None:
+        if not hasattr(entry, "halo0"):
+            raise ValueError("operator_diagonal: reach is required for a built-in body")
+        reach = entry.halo0
+    reach = [int(reach)] * like.rank if isinstance(reach, int) else [int(r) for r in reach]
+    if len(reach) != like.rank or any(r < 0 for r in reach):
+        raise ValueError("operator_diagonal: reach is a non-negative int or one per dimension")
+    others = list(others)
+    lo, hi = _omega(like, bounds, region)
+    diag = DeviceField.empty_like(like)
+    diag.tensor.zero_()
+    if any(h <= l for l, h in zip(lo, hi)):
+        return diag
+    probe, out = DeviceField.empty_like(like), DeviceField.empty_like(like)
+    stride = [2 * r + 1 for r in reach]
+    # guard: one unit vector at the middle cell of Omega must come back as zeros beyond `reach` around it -- an operator that
+    # reaches further there would let two cells of one colour see each other and the diagonal would be silently wrong
+    mid = [(l + h) // 2 for l, h in zip(lo, hi)]
+    probe.tensor.zero_()
+    probe.tensor[tuple(mid)] = 1.0
+    out.tensor.zero_()
+    apply_builtin(entry, [probe] + others, out, bounds, region=region, cfg=cfg)
+    seen = out.tensor[tuple(slice(l, h) for l, h in zip(lo, hi))].clone()
+    seen[tuple(slice(max(m - r - l, 0), m + r + 1 - l) for m, r, l in zip(mid, reach, lo))] = 0.0
+    if bool((seen != 0).any()):
+        raise ValueError(f"operator_diagonal: the operator reaches further than reach = {reach} (a unit vector at {mid} is seen "
+                         "beyond it): give reach per dimension")
+    for colour in itertools.product(*[range(min(s, h - l)) for s, l, h in zip(stride, lo, hi)]):
+        cells = tuple(slice(l + c, h, s) for l, h, c, s in zip(lo, hi, colour, stride))
+        probe.tensor.zero_()
+        probe.tensor[cells] = 1.0
+        out.tensor.zero_()
+        apply_builtin(entry, [probe] + others, out, bounds, region=region, cfg=cfg)
+        diag.tensor[cells] = out.tensor[cells]
+    torch.cuda.synchronize()
+    return diag
+
+
+def jacobi_minv(entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), reach=None,
+                region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None) -> DeviceField:
+    """the Jacobi preconditioner of a linear operator for cg_solve(minv=...): 1 / diagonal (one division in the element
+    type) on Omega, 1 elsewhere; arguments as operator_diagonal.  ValueError when a diagonal entry on Omega is 0 or not
+    finite.  (A negative entry is not refused here: the solver wants a positive preconditioner and does not check.)"""
+    import torch
+    diag = operator_diagonal(entry, like, bounds, others, reach, region, cfg)
+    lo, hi = _omega(like, bounds, region)
+    minv = DeviceField.empty_like(like)
+    minv.tensor.fill_(1.0)
+    if any(h <= l for l, h in zip(lo, hi)):
+        return minv
+    cells = tuple(slice(l, h) for l, h in zip(lo, hi))
+    d = diag.tensor[cells]
+    bad = int(((d == 0) | ~torch.isfinite(d)).sum().item())
+    if bad:
+        raise ValueError(f"jacobi_minv: {bad} diagonal entries on Omega are 0 or not finite")
+    minv.tensor[cells] = torch.ones_like(d) / d
+    return minv
 
 
 def _as_field(x) -> DeviceField:
