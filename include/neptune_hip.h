@@ -441,7 +441,8 @@ int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_do
                          const void *const *in_rest, int64_t max_iters, int64_t check_every, double tol2, void *trace,
                          void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0,
                          double *rr_last);
-/* the last neptune_hip_cg_solve / neptune_hip_pcg_solve call of this process: iterations whose q = A(p) ran as a dot-monitored launch, iterations
+/* the last neptune_hip_cg_solve / neptune_hip_pcg_solve / neptune_hip_bicgstab_solve call of this process, whichever solver
+ * ran last: iterations whose q = A(p) (BiCGStab: t = A(s)) ran as a dot-monitored launch, iterations
  * that ran the fallback, and read-backs after blocks (the read of rr_0 is not counted) */
 void neptune_hip_cg_counts(int64_t *fused, int64_t *fallback, int64_t *checks);
 
@@ -472,6 +473,37 @@ int neptune_hip_pcg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_d
 /* rz_0 = sum r * (minv * r) after the set-up of the last neptune_hip_pcg_solve call of this process (0 when it was refused):
  * with *rr0 and the trace, every scalar the recurrences used -- alpha_0 = rz_0 / pq_0 -- so that a run can be replayed */
 double neptune_hip_pcg_rz0(void);
+
+/* Solve A(x) = b by unpreconditioned BiCGStab for an apply that need not be symmetric.  Everything is as
+ * for neptune_hip_cg_solve -- element type T, no FMA (one rounding per operation), A and its inputs, Omega, the fixed
+ * summation tree, no atomics, the blocks of check_every iterations, the read-backs -- except where stated here.
+ * work[5] = r, rh, p, v, t: caller-supplied fields of the box of x; s lives in r between the two half-steps.
+ *   set-up     v = A(x) (plain launch);  r = b - v on Omega, +0 elsewhere;  rh = r;  p = r;  rr_0 = sum r * r;  rho_0 := rr_0
+ *              (the same value, not a second sum).  Where the launch region is not the whole box, v and t are zeroed once
+ *              before the set-up.
+ *   iteration  1. v = A(p) (plain launch);  rv = sum rh * v over all n cells of the flat buffers (v is +0 outside Omega)
+ *              2. alpha = rho / rv;  r = r - (alpha v) on all n cells: this is s
+ *              3. t = A(s) and ts = sum_Omega t * s out of the same dot-monitored launch (fn_dot);  tt = sum t * t over all n
+ *                 cells in a read-only pass over t
+ *              4. omega = ts / tt;  x = (x + (alpha p)) + (omega s);  r = s - (omega t);  out of that launch, from the freshly
+ *                 stored r, rho' = sum rh * r and rr' = sum r * r
+ *              5. beta = (rho' / rho) * (alpha / omega): two divisions, then one product;  p = r + (beta (p - (omega v)));
+ *                 rho <- rho', rr <- rr'
+ * Breakdown: alpha = 0 when rho == 0 or rv == 0; omega = 0 when tt == 0; beta = 0 when rho == 0, rv == 0 or omega == 0: nothing
+ * becomes NaN from finite data.  The loop stops on rr <= tol2 exactly as neptune_hip_cg_solve's (a NaN never stops it;
+ * rr_0 <= tol2 returns with zero iterations).  trace: NULL, or a DEVICE pointer to 5 * max_iters values of T: iteration k
+ * stores rv_k, ts_k, tt_k, rho_(k+1), rr_(k+1) at [5 k .. 5 k + 4]; with *rr0 these are every scalar the recurrences used
+ * (alpha, omega, beta follow by the divisions above).  The counters are those of neptune_hip_cg_counts.
+ * Fallback: when fn_dot is NULL (with fn set) or answers NEPTUNE_HIP_EUNSUPPORTED (remembered for the rest of the call),
+ * step 3 is a plain launch followed by ONE flat pass over t and s that forms ts and tt (both over all n cells: s is +0
+ * outside Omega).
+ * NEPTUNE_HIP_EINVAL, nothing launched: the refusals of neptune_hip_cg_solve, any two of the seven fields x, b, r, rh, p, v, t
+ * overlapping, a trace that overlaps a field. */
+int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                               const neptune_hip_apply_geom_t *g, void *x, const void *b, void *const work[5],
+                               const void *const *in_rest, int64_t max_iters, int64_t check_every, double tol2,
+                               void *trace, void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done,
+                               double *rr0, double *rr_last);
 
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */

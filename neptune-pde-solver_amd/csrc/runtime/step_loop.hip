@@ -2,9 +2,9 @@
 // grouping choice) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
 // neptune_hip_step_loop_chain (one-level schemes, two fields), neptune_hip_step_loop_leapfrog (two-level schemes, three or
 // four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and neptune_hip_cg_solve /
-// neptune_hip_pcg_solve, whose iteration the same engine replays.  Its own translation unit (builds in seconds, linked into
-// libneptune_hip.so): host code that launches applies through the public C API, plus the solvers' few vector kernels
-// (cg_kernels.hpp, pcg_kernels.hpp).
+// neptune_hip_pcg_solve / neptune_hip_bicgstab_solve, whose iteration the same engine replays.  Its own translation unit
+// (builds in seconds, linked into libneptune_hip.so): host code that launches applies through the public C API, plus the
+// solvers' few vector kernels (cg_kernels.hpp, pcg_kernels.hpp, bicg_kernels.hpp).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,6 +16,7 @@
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no apply kernel is instantiated here)
 #include "../kernels/cg_kernels.hpp"
 #include "../kernels/pcg_kernels.hpp"
+#include "../kernels/bicg_kernels.hpp"
 
 using namespace neptune_hip;
 
@@ -37,6 +38,7 @@ struct LoopKey {
   // the system loop: fields[] is set A of its n_out unknowns, fields_b[] set B, through[m] the union input member m advances;
   // n_out = 0 and the rest zero in the other loops
   void* fields_b[4];
+  void* fields_c[4];           // the BiCGStab solver's further vectors (its iteration touches more than eight buffers); zero elsewhere
   int through[4];
   int n_out;
   const void* in[NEPTUNE_HIP_MAX_INPUTS];   // the inputs that are no state (centre-only inputs: the same field at every stage)
@@ -284,12 +286,15 @@ int64_t g_leap_counts[2] = {0, 0};   // single / pair launches of the last leapf
 int64_t g_system_counts[2] = {0, 0}; // steps / graph launches of the last system loop
 void* g_until_sum = nullptr;            // the until loop's device scalar (one element), released with the graphs
 int64_t g_until_counts[3] = {0, 0, 0};  // monitored checked steps / fallback checked steps / checks of the last until loop
-void* g_cg_ws = nullptr;                // the solver's device block: CgScalars / PcgScalars, then the partials of its own kernels; grown on demand
+void* g_cg_ws = nullptr;                // the solver's device block: CgScalars / PcgScalars / BicgScalars, then the partials of its own kernels; grown on demand
 size_t g_cg_ws_bytes = 0;
-int64_t g_cg_counts[3] = {0, 0, 0};     // dot-monitored iterations / fallback iterations / checks of the last cg_solve / pcg_solve
+int64_t g_cg_counts[3] = {0, 0, 0};     // dot-monitored iterations / fallback iterations / checks of the last cg_solve / pcg_solve / bicgstab_solve
 double g_pcg_rz0 = 0.0;                 // r . (minv r) after the set-up of the last pcg_solve
 constexpr size_t kCgScalarBytes = 64;   // room for CgScalars<double> and PcgScalars<double>, keeps the partials 16-byte aligned
-static_assert(sizeof(CgScalars<double>) <= kCgScalarBytes && sizeof(PcgScalars<double>) <= kCgScalarBytes, "the scalar block");
+constexpr size_t kBicgScalarBytes = 96; // BiCGStab's own reserve in the same block: BicgScalars<double> is 80 bytes; a multiple of 16 likewise
+static_assert(sizeof(CgScalars<double>) <= kCgScalarBytes && sizeof(PcgScalars<double>) <= kCgScalarBytes &&
+              sizeof(BicgScalars<double>) <= kBicgScalarBytes && kCgScalarBytes % 16 == 0 && kBicgScalarBytes % 16 == 0,
+              "the scalar block");
 
 // ---------------------------------------------------------------- the one-level loop on a stream scope
 // `steps` applies from fields[0] (the state) into fields[steps % 2]: what neptune_hip_step_loop_chain is once its arguments
@@ -637,6 +642,48 @@ CgFlatGrid cg_flat_grid(int64_t n, size_t elem, std::initializer_list<const void
   return {false, (uint32_t)(want < 256 * 32 ? want : 256 * 32)};
 }
 
+// the solvers' device block holds at least `need` bytes from here on
+void grow_cg_ws(size_t need, hipStream_t stream) {
+  if (need <= g_cg_ws_bytes) return;
+  std::lock_guard<std::mutex> lk(g_loop_mu);   // cached graphs hold the old block's address: their keys do too
+  if (g_cg_ws) {
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(stream));
+    NEPTUNE_HIP_CHECK(hipFree(g_cg_ws));
+  }
+  g_cg_ws = nullptr;
+  g_cg_ws_bytes = 0;
+  NEPTUNE_HIP_CHECK(hipMalloc(&g_cg_ws, need));
+  g_cg_ws_bytes = need;
+}
+
+// the box all of a solver's fields share, and Omega in its physical coordinates, on the kernels' (I, J, K) axes; -> the cells
+// of the box
+int64_t solver_box(const neptune_hip_apply_geom_t* g, CgBoxParams& B) {
+  int64_t n = 1;
+  int64_t shape[3], lo[3], hi[3];
+  for (int d = 0; d < g->rank; ++d) {
+    shape[d] = g->out_ub[d] - g->out_lb[d];
+    lo[d] = std::max(g->lb[d] - g->out_lb[d], g->region_lb[d]);
+    hi[d] = std::min(g->ub[d] - g->out_lb[d], g->region_ub[d]);
+    n *= shape[d];
+  }
+  auto axes = [&](const int64_t* src, int64_t* dst, int64_t fill) {
+    if (g->rank == 3) to_axes<3>(src, dst, fill);
+    else if (g->rank == 2) to_axes<2>(src, dst, fill);
+    else to_axes<1>(src, dst, fill);
+  };
+  axes(shape, B.n, 1);
+  axes(lo, B.lo, 0);
+  axes(hi, B.hi, 1);
+  return n;
+}
+// whether the launch region is the whole box (an apply stores nothing outside its launch region)
+bool region_is_whole(const neptune_hip_apply_geom_t* g) {
+  bool whole = true;
+  for (int d = 0; d < g->rank; ++d) whole = whole && g->region_lb[d] <= 0 && g->region_ub[d] >= g->out_ub[d] - g->out_lb[d];
+  return whole;
+}
+
 // minv = nullptr: the solver of 3.11 on the kernels of cg_kernels.hpp; a field: the Jacobi-preconditioned solver of 3.12 on those
 // of pcg_kernels.hpp.  Everything else -- the apply launches, the blocks, the replay schedule, the counters -- is one code.
 template <class T>
@@ -649,26 +696,8 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   T* const p = static_cast<T*>(work[1]);
   T* const q = static_cast<T*>(work[2]);
   const T* const minv = static_cast<const T*>(minv_field);
-  // the box all five fields share, and Omega in its physical coordinates, on the kernels' (I, J, K) axes
   CgBoxParams B;
-  int64_t n = 1;
-  {
-    int64_t shape[3], lo[3], hi[3];
-    for (int d = 0; d < g->rank; ++d) {
-      shape[d] = g->out_ub[d] - g->out_lb[d];
-      lo[d] = std::max(g->lb[d] - g->out_lb[d], g->region_lb[d]);
-      hi[d] = std::min(g->ub[d] - g->out_lb[d], g->region_ub[d]);
-      n *= shape[d];
-    }
-    auto axes = [&](const int64_t* src, int64_t* dst, int64_t fill) {
-      if (g->rank == 3) to_axes<3>(src, dst, fill);
-      else if (g->rank == 2) to_axes<2>(src, dst, fill);
-      else to_axes<1>(src, dst, fill);
-    };
-    axes(shape, B.n, 1);
-    axes(lo, B.lo, 0);
-    axes(hi, B.hi, 1);
-  }
+  const int64_t n = solver_box(g, B);
   const int64_t nchunk = (B.n[2] + 255) / 256;
   const dim3 init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
   const int64_t init_blocks = (int64_t)init_grid.x * init_grid.y;
@@ -676,18 +705,7 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   const CgFlatGrid upd = cg_flat_grid(n, sizeof(T), {p, q, x, r, minv}), dir = cg_flat_grid(n, sizeof(T), {r, p, minv});
 
   // the device block: the scalars, then room for the partials of the init and update kernels (two sums with a preconditioner)
-  const size_t need = kCgScalarBytes + (size_t)(minv ? 2 : 1) * (size_t)std::max<int64_t>(init_blocks, upd.blocks) * sizeof(T);
-  if (need > g_cg_ws_bytes) {
-    std::lock_guard<std::mutex> lk(g_loop_mu);   // cached graphs hold the old block's address: their keys do too
-    if (g_cg_ws) {
-      NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-      NEPTUNE_HIP_CHECK(hipFree(g_cg_ws));
-    }
-    g_cg_ws = nullptr;
-    g_cg_ws_bytes = 0;
-    NEPTUNE_HIP_CHECK(hipMalloc(&g_cg_ws, need));
-    g_cg_ws_bytes = need;
-  }
+  grow_cg_ws(kCgScalarBytes + (size_t)(minv ? 2 : 1) * (size_t)std::max<int64_t>(init_blocks, upd.blocks) * sizeof(T), sc.stream);
   CgScalars<T>* const scal = static_cast<CgScalars<T>*>(g_cg_ws);
   PcgScalars<T>* const pscal = static_cast<PcgScalars<T>*>(g_cg_ws);   // the same bytes: one of the two is in use
   T* const pq_dev = minv ? &pscal->pq : &scal->pq;
@@ -711,9 +729,7 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
 
   // set-up: q = A(x), r = p = b - q on Omega, rr_0.  An apply stores nothing outside its launch region, and the flat update
   // reads q everywhere: where the region is not the whole box, q starts as +0 and stays so out there.
-  bool whole = true;
-  for (int d = 0; d < g->rank; ++d) whole = whole && g->region_lb[d] <= 0 && g->region_ub[d] >= g->out_ub[d] - g->out_lb[d];
-  if (!whole) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
+  if (!region_is_whole(g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
   int rc = apply_plain(x, q);
   if (rc != NEPTUNE_HIP_OK) return rc;
   if (minv) {
@@ -808,6 +824,158 @@ int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
   }
   return NEPTUNE_HIP_OK;
 }
+
+// ---------------------------------------------------------------- BiCGStab on a stream scope
+// A host loop of its own on the same engine: other vectors, other kernels and three reduction points per iteration; it
+// shares with cg_solve_typed the box, the device block and the block / replay / read-back schedule.
+template <class T>
+int bicgstab_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body,
+                         const neptune_hip_apply_geom_t* g, void* x_field, const void* b, void* const work[5],
+                         const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace,
+                         const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0_out, double* rr_last) {
+  T* const x = static_cast<T*>(x_field);
+  T* const r = static_cast<T*>(work[0]);    // s between the two half-steps
+  T* const rh = static_cast<T*>(work[1]);
+  T* const p = static_cast<T*>(work[2]);
+  T* const v = static_cast<T*>(work[3]);
+  T* const t = static_cast<T*>(work[4]);
+  CgBoxParams B;
+  const int64_t n = solver_box(g, B);
+  const int64_t nchunk = (B.n[2] + 255) / 256;
+  const dim3 init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
+  const int64_t init_blocks = (int64_t)init_grid.x * init_grid.y;
+  const CgFlatGrid g_rv = cg_flat_grid(n, sizeof(T), {rh, v}), g_s = cg_flat_grid(n, sizeof(T), {v, r}),
+                   g_tt = cg_flat_grid(n, sizeof(T), {t}), g_ts = cg_flat_grid(n, sizeof(T), {t, r}),
+                   g_upd = cg_flat_grid(n, sizeof(T), {p, t, rh, x, r}), g_dir = cg_flat_grid(n, sizeof(T), {r, v, p});
+  // the device block: the scalars, then room for the partials of the init, sum and update kernels (two sums at the most)
+  const int64_t most = std::max<int64_t>({init_blocks, g_rv.blocks, g_tt.blocks, g_ts.blocks, g_upd.blocks});
+  grow_cg_ws(kBicgScalarBytes + 2 * (size_t)most * sizeof(T), sc.stream);
+  BicgScalars<T>* const scal = static_cast<BicgScalars<T>*>(g_cg_ws);
+  T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_cg_ws) + kBicgScalarBytes);
+  T* const tr = static_cast<T*>(trace);
+  const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
+
+  auto inputs = [&](const void** ins, const void* in0) {
+    ins[0] = in0;
+    for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
+  };
+  auto apply_plain = [&](const void* in0, void* out) -> int {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    inputs(ins, in0);
+    return fn ? fn(g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(body, g, ins, out, (void*)sc.stream, c);
+  };
+  auto final_kernel = [&](int64_t count, int stage) {
+    hipLaunchKernelGGL(neptune_bicg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, count, scal, tr, max_iters, stage);
+  };
+  auto read_rr = [&]() -> double {
+    T h = 0;
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, &scal->rr, sizeof(T), hipMemcpyDeviceToHost, sc.stream));
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+    return (double)h;
+  };
+
+  // set-up: v = A(x), r = rh = p = b - v on Omega, rr_0 = rho_0.  An apply stores nothing outside its launch region, and the
+  // flat kernels read v and t everywhere: where the region is not the whole box, both start as +0 and stay so out there.
+  if (!region_is_whole(g)) {
+    NEPTUNE_HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(T), sc.stream));
+    NEPTUNE_HIP_CHECK(hipMemsetAsync(t, 0, (size_t)n * sizeof(T), sc.stream));
+  }
+  int rc = apply_plain(x, v);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  hipLaunchKernelGGL(neptune_bicg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, static_cast<const T*>(b), (const T*)v, r, rh, p, partials);
+  final_kernel(init_blocks, kBicgStart);
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  double rr = read_rr();
+  if (rr0_out) *rr0_out = rr;
+  if (rr_last) *rr_last = rr;
+  if (rr <= tol2 || max_iters == 0) return NEPTUNE_HIP_OK;
+
+  LoopKey key;
+  init_key(key, fn, fn ? -1 : body, g, cfg, sc.stream);
+  key.n_out = -2;   // no other loop's key, and not the CG solvers': this solver's iteration
+  key.more[0] = (group_fn)fn_dot;
+  key.fields[0] = x; key.fields[1] = r; key.fields[2] = p; key.fields[3] = v;
+  key.fields_b[0] = g_cg_ws;
+  key.fields_b[2] = trace;
+  key.fields_c[0] = rh; key.fields_c[1] = t; key.fields_c[2] = const_cast<void*>(b);
+  key.through[0] = (int)(max_iters < 0x7fffffff ? max_iters : 0x7fffffff);   // the trace's length is a kernel argument
+  for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in_rest[i - 1];
+
+  const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+  auto dot_launch = [&]() -> int {
+    inputs(ins, r);
+    return fn ? fn_dot(g, ins, t, &scal->ts, (void*)sc.stream, c)
+              : neptune_hip_apply_builtin_dot(body, g, ins, t, &scal->ts, (void*)sc.stream, c);
+  };
+  // The dot-monitored entry is an iteration's FOURTH launch: a refusal from there would leave half an iteration behind.  So the
+  // entry is asked once per call, before the first iteration, with the very launch step 3 makes (t = A(r) and ts, both of
+  // which every iteration writes again before it reads them): a refusal -- NEPTUNE_HIP_EUNSUPPORTED, nothing launched -- is
+  // remembered for the rest of the call, and an acceptance has grown the monitor workspace outside of any capture.
+  bool fused_ok = fn ? fn_dot != nullptr : true;
+  if (fused_ok) {
+    rc = dot_launch();
+    if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused_ok = false;
+    else if (rc != NEPTUNE_HIP_OK) return rc;
+  }
+
+  // one iteration; kind 1: t = A(s) and ts out of one dot-monitored launch, then tt; kind 2: a plain launch, then ts and tt out
+  // of one pass
+  auto iteration = [&](int kind, int&) -> int {
+    int rc;
+    // 1. v = A(p), rv = rh . v, alpha
+    rc = apply_plain(p, v);
+    if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+    if (g_rv.vec) hipLaunchKernelGGL(neptune_bicg_rv_v<T>, dim3(g_rv.blocks), dim3(256), 0, sc.stream, n, (const T*)rh, (const T*)v, partials);
+    else hipLaunchKernelGGL(neptune_bicg_rv<T>, dim3(g_rv.blocks), dim3(256), 0, sc.stream, n, (const T*)rh, (const T*)v, partials);
+    final_kernel((int64_t)g_rv.blocks, kBicgRv);
+    // 2. s = r - alpha v, in place
+    if (g_s.vec) hipLaunchKernelGGL(neptune_bicg_s_v<T>, dim3(g_s.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)v, r);
+    else hipLaunchKernelGGL(neptune_bicg_s<T>, dim3(g_s.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)v, r);
+    NEPTUNE_HIP_CHECK(hipGetLastError());
+    // 3. t = A(s), ts, tt, omega
+    if (kind == 1) {
+      rc = dot_launch();
+      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+      key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
+      if (g_tt.vec) hipLaunchKernelGGL((neptune_bicg_tt_v<T, false>), dim3(g_tt.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)t, partials);
+      else hipLaunchKernelGGL((neptune_bicg_tt<T, false>), dim3(g_tt.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)t, partials);
+      final_kernel((int64_t)g_tt.blocks, kBicgTt);
+    } else {
+      rc = apply_plain(r, t);
+      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+      if (g_ts.vec) hipLaunchKernelGGL((neptune_bicg_tt_v<T, true>), dim3(g_ts.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)r, partials);
+      else hipLaunchKernelGGL((neptune_bicg_tt<T, true>), dim3(g_ts.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)r, partials);
+      final_kernel((int64_t)g_ts.blocks, kBicgTsTt);
+    }
+    // 4. x, r, rho', rr', beta, the trace row and the rotation
+    if (g_upd.vec) hipLaunchKernelGGL(neptune_bicg_update_v<T>, dim3(g_upd.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)p, (const T*)t, (const T*)rh, x, r, partials);
+    else hipLaunchKernelGGL(neptune_bicg_update<T>, dim3(g_upd.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)p, (const T*)t, (const T*)rh, x, r, partials);
+    final_kernel((int64_t)g_upd.blocks, kBicgUpdate);
+    // 5. p = r + beta (p - omega v)
+    if (g_dir.vec) hipLaunchKernelGGL(neptune_bicg_direction_v<T>, dim3(g_dir.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)r, (const T*)v, p);
+    else hipLaunchKernelGGL(neptune_bicg_direction<T>, dim3(g_dir.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)r, (const T*)v, p);
+    NEPTUNE_HIP_CHECK(hipGetLastError());
+    return NEPTUNE_HIP_OK;
+  };
+
+  int64_t done = 0;
+  int state = 0;   // an iteration leaves no rotation behind: the device block carries it
+  while (done < max_iters) {
+    const int64_t block = check_every < max_iters - done ? check_every : max_iters - done;
+    // graphs of 4 iterations: an iteration is 11 kernel nodes (10 on the fallback path) against CG's 5, so 4 of them are the
+    // about 40 nodes over which the other loops amortise a graph launch
+    rc = replay(key, sc, fused_ok ? 1 : 2, block, state, 4, iteration);
+    if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+    g_cg_counts[fused_ok ? 0 : 1] += block;
+    done += block;
+    if (iters_done) *iters_done = done;
+    rr = read_rr();
+    ++g_cg_counts[2];
+    if (rr_last) *rr_last = rr;
+    if (rr <= tol2) break;   // false for a NaN: such a solve runs to max_iters
+  }
+  return NEPTUNE_HIP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -818,22 +986,20 @@ void neptune_hip_cg_counts(int64_t* fused, int64_t* fallback, int64_t* checks) {
   if (checks) *checks = g_cg_counts[2];
 }
 
-// the argument checks and the dispatch on the element type of both entries; pre: neptune_hip_pcg_solve (minv is required)
-static int cg_solve_checked(bool pre, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
-                            const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv, void* const work[3],
-                            const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
-                            const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
-  g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
-  if (iters_done) *iters_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
-  if (!g || !x || !b || !work || !work[0] || !work[1] || !work[2] || max_iters < 0 || check_every < 1) return NEPTUNE_HIP_EINVAL;
-  if (pre && !minv) return NEPTUNE_HIP_EINVAL;
+// The argument checks every solver shares, before anything touches the device: the scalars, the geometry, the fixed inputs,
+// one box for input 0 and the result, the element type (-> *dtype_out), `count` non-null fields aligned for it and pairwise
+// disjoint, a trace (of trace_values elements, or NULL) aligned and clear of every field, and no capture under way on `stream`.
+static int solver_args_checked(neptune_hip_apply_fn fn, int body, int dtype_of_fn, const neptune_hip_apply_geom_t* g,
+                               const void* const* fields, int count, const void* const* in_rest, int64_t max_iters, int64_t check_every,
+                               const void* trace, int64_t trace_values, void* stream, int* dtype_out) {
+  if (!g || max_iters < 0 || check_every < 1) return NEPTUNE_HIP_EINVAL;
+  for (int a = 0; a < count; ++a)
+    if (!fields[a]) return NEPTUNE_HIP_EINVAL;
   if (geom_validate(g) != NEPTUNE_HIP_OK) return NEPTUNE_HIP_EINVAL;
   if (g->num_inputs > 1 && !in_rest) return NEPTUNE_HIP_EINVAL;
   for (int i = 1; i < g->num_inputs; ++i)
     if (!in_rest[i - 1]) return NEPTUNE_HIP_EINVAL;
-  // the iteration feeds the result q back as input 0 (through p): one box for both
+  // the iteration feeds the result back as input 0: one box for both
   for (int d = 0; d < g->rank; ++d)
     if (g->in_lb[0][d] != g->out_lb[d] || g->in_ub[0][d] != g->out_ub[d]) return NEPTUNE_HIP_EINVAL;
   int dtype = dtype_of_fn;
@@ -844,16 +1010,13 @@ static int cg_solve_checked(bool pre, neptune_hip_apply_fn fn, neptune_hip_apply
   if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
   const size_t elem = dtype == NEPTUNE_HIP_F64 ? 8 : 4;
   const size_t bytes = geom_box_bytes(g->out_lb, g->out_ub, g->rank, elem);
-  const size_t trace_bytes = (size_t)((pre ? 3 : 2) * max_iters) * elem;
-  const void* const five[5] = {x, b, work[0], work[1], work[2]};
-  for (int a = 0; a < 5; ++a) {
-    if ((uintptr_t)five[a] % elem != 0) return NEPTUNE_HIP_EINVAL;
+  const size_t trace_bytes = (size_t)trace_values * elem;
+  for (int a = 0; a < count; ++a) {
+    if ((uintptr_t)fields[a] % elem != 0) return NEPTUNE_HIP_EINVAL;
     for (int o = 0; o < a; ++o)
-      if (buffers_overlap(five[a], bytes, five[o], bytes)) return NEPTUNE_HIP_EINVAL;
-    if (trace && buffers_overlap(trace, trace_bytes, five[a], bytes)) return NEPTUNE_HIP_EINVAL;
-    if (pre && buffers_overlap(minv, bytes, five[a], bytes)) return NEPTUNE_HIP_EINVAL;
+      if (buffers_overlap(fields[a], bytes, fields[o], bytes)) return NEPTUNE_HIP_EINVAL;
+    if (trace && buffers_overlap(trace, trace_bytes, fields[a], bytes)) return NEPTUNE_HIP_EINVAL;
   }
-  if (pre && ((uintptr_t)minv % elem != 0 || (trace && buffers_overlap(trace, trace_bytes, minv, bytes)))) return NEPTUNE_HIP_EINVAL;
   if (trace && (uintptr_t)trace % elem != 0) return NEPTUNE_HIP_EINVAL;
   {
     // rr is read back after every block: not while the caller's stream is being captured
@@ -861,6 +1024,26 @@ static int cg_solve_checked(bool pre, neptune_hip_apply_fn fn, neptune_hip_apply
     if (stream && hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
     if (cs != hipStreamCaptureStatusNone) return NEPTUNE_HIP_EINVAL;
   }
+  *dtype_out = dtype;
+  return NEPTUNE_HIP_OK;
+}
+
+// the argument checks and the dispatch on the element type of both CG entries; pre: neptune_hip_pcg_solve (minv is required
+// and is a sixth field)
+static int cg_solve_checked(bool pre, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                            const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv, void* const work[3],
+                            const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
+                            const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
+  if (iters_done) *iters_done = 0;
+  if (rr0) *rr0 = 0.0;
+  if (rr_last) *rr_last = 0.0;
+  if (!work) return NEPTUNE_HIP_EINVAL;
+  const void* const six[6] = {x, b, work[0], work[1], work[2], minv};
+  int dtype = 0;
+  if (solver_args_checked(fn, body, dtype_of_fn, g, six, pre ? 6 : 5, in_rest, max_iters, check_every, trace, (pre ? 3 : 2) * max_iters,
+                          stream, &dtype) != NEPTUNE_HIP_OK)
+    return NEPTUNE_HIP_EINVAL;
   ensure_init();
   StreamScope sc(reinterpret_cast<hipStream_t>(stream));
   return dtype == NEPTUNE_HIP_F64
@@ -885,6 +1068,27 @@ int neptune_hip_pcg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_d
   g_pcg_rz0 = 0.0;
   return cg_solve_checked(true, fn, fn_dot, body, dtype_of_fn, g, x, b, minv, work, in_rest, max_iters, check_every, tol2, trace,
                           stream, cfg, iters_done, rr0, rr_last);
+}
+
+int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
+                               const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[5], const void* const* in_rest,
+                               int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
+                               const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
+  if (iters_done) *iters_done = 0;
+  if (rr0) *rr0 = 0.0;
+  if (rr_last) *rr_last = 0.0;
+  if (!work) return NEPTUNE_HIP_EINVAL;
+  const void* const seven[7] = {x, b, work[0], work[1], work[2], work[3], work[4]};
+  int dtype = 0;
+  if (solver_args_checked(fn, body, dtype_of_fn, g, seven, 7, in_rest, max_iters, check_every, trace, 5 * max_iters, stream, &dtype) !=
+      NEPTUNE_HIP_OK)
+    return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
+  return dtype == NEPTUNE_HIP_F64
+             ? bicgstab_solve_typed<double>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last)
+             : bicgstab_solve_typed<float>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last);
 }
 
 }  // extern "C"

@@ -133,6 +133,8 @@ SIGNATURES = {
     "neptune_hip_pcg_solve": (_i, [_vp, _vp, _i, _i, _geom_p, _vp, _vp, _vp, _vpp, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,
                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_pcg_rz0": (_dbl, []),
+    "neptune_hip_bicgstab_solve": (_i, [_vp, _vp, _i, _i, _geom_p, _vp, _vp, _vpp, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_cg_counts": (None, [_i64p, _i64p, _i64p]),
     "neptune_hip_kernel_name": (C.c_char_p, [_i]),
     "neptune_hip_apply_builtin_variant": (_i, [_i, _geom_p, _cfg_p]),

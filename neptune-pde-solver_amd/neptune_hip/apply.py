@@ -188,7 +188,7 @@ def dot(a: DeviceField, b: DeviceField, bounds: Box, region: Optional[Box] = Non
 
 def cg_counts():
     """(iterations whose q = A(p) ran as a dot-monitored launch, iterations that ran plain launch + neptune_hip_dot, read-backs
-    after blocks of iterations) of the last cg_solve call"""
+    after blocks of iterations) of the last cg_solve or bicgstab_solve call (for BiCGStab the launch in question is t = A(s))"""
     fused, fallback, checks = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     _capi.load().neptune_hip_cg_counts(C.byref(fused), C.byref(fallback), C.byref(checks))
     return fused.value, fallback.value, checks.value
@@ -247,6 +247,44 @@ def pcg_rz0() -> float:
     """r . (minv r) after the set-up of the last cg_solve(..., minv=...) call: with rr0 and the trace, every scalar the
     recurrences used"""
     return float(_capi.load().neptune_hip_pcg_rz0())
+
+
+def bicgstab_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int, tol2: float, check_every: int = 1,
+                   others: Sequence[DeviceField] = (), trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
+                   work: Optional[Sequence[DeviceField]] = None, region: Optional[Box] = None, stream: Optional[int] = None):
+    """solve A(x) = b by BiCGStab on the device (neptune_hip_bicgstab_solve) for an apply that need not be symmetric.  entry,
+    x, b, bounds, others, max_iters, tol2 (the threshold on r . r), check_every, dot ("auto", "fallback", None or a dot entry), cfg,
+    region and stream: as cg_solve.  work: five fields like x for r, rh, p, v, t (allocated here when None).
+    Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a numpy array of shape (iters, 5) holding
+    (rh . A(p), A(s) . s, A(s) . A(s) of iteration k, rh . r and r . r after it).  cg_counts() tells which path the iterations
+    took."""
+    import torch
+    lib = _capi.load()
+    others = list(others)
+    if work is None:
+        work = [DeviceField.empty_like(x) for _ in range(5)]
+    if len(work) != 5:
+        raise ValueError("bicgstab_solve: work is five fields (r, rh, p, v, t)")
+    g = geom_for([x] + others, work[3], bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    is_entry = hasattr(entry, "fn")
+    fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
+    if isinstance(dot, str):
+        if dot not in ("auto", "fallback"):
+            raise ValueError('bicgstab_solve: dot is "auto", "fallback", None or a dot entry')
+        dot = entry if (dot == "auto" and is_entry) else None
+    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    tr = torch.zeros(5 * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    warr = (C.c_void_p * 5)(*[f.ptr for f in work])
+    rest = _in_array(others) if others else None
+    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    rc = lib.neptune_hip_bicgstab_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, warr, rest,
+                                        max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
+                                        C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    _capi.check(rc, "neptune_hip_bicgstab_solve")
+    if trace:
+        return done.value, rr0.value, last.value, tr.cpu().numpy()[:5 * done.value].reshape(-1, 5)
+    return done.value, rr0.value, last.value
 
 
 def _omega(like: DeviceField, bounds: Box, region: Optional[Box]):
