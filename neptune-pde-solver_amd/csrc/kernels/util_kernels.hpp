@@ -4,6 +4,7 @@
 #include "../../../include/neptune_hip.h"
 #include "apply_common.hpp"
 #include "body_ops.hpp"
+#include "flat_kernels.hpp"
 
 namespace neptune_hip {
 
@@ -77,40 +78,22 @@ __global__ __launch_bounds__(256) void neptune_copy16_unrolled(const u32x4* __re
 // such as CG's alpha cannot enter an apply; these two kernels are the missing piece for a solver loop that never leaves
 // the GPU.  Two roundings each (the product, then the sum), no FMA -- what numpy's `y += a * x` computes.
 //   AXPY: y[i] = y[i] + a * x[i]        XPAY: y[i] = x[i] + a * y[i]
-template <class T, bool XPAY>
+// On the frame of flat_kernels.hpp: VEC, for 16-byte-aligned vectors, is one 16-byte load of x and of y per lane, an exact
+// grid and a non-temporal store (the access pattern of the fastest copy kernel: grid-stride loops of scalar accesses run
+// ~25 % below it); the other form is that grid-stride loop.
+template <class T, bool XPAY, bool VEC>
 __global__ __launch_bounds__(256) void neptune_vec_update(int64_t n, T a, const T* __restrict__ x, T* __restrict__ y) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if constexpr (XPAY) { const T t = a * y[i]; y[i] = x[i] + t; }
-    else { const T t = a * x[i]; y[i] = y[i] + t; }
-  }
-}
-
-// the same update on 16-byte-aligned vectors: one 16-byte load of x and of y per lane, exact grid, non-temporal store (the
-// access pattern of the fastest copy kernel: grid-stride loops of scalar accesses run ~25 % below it); the n % VK elements
-// at the end go through lane 0 of the first workgroup
-template <class T, bool XPAY>
-__global__ __launch_bounds__(256) void neptune_vec_update_v(int64_t n, T a, const T* __restrict__ x, T* __restrict__ y) {
-  constexpr int VK = 16 / (int)sizeof(T);
-  typedef T V __attribute__((ext_vector_type(VK)));
-  const int64_t nv = n / VK;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < nv) {
-    const V xv = reinterpret_cast<const V*>(x)[i];
-    const V yv = reinterpret_cast<const V*>(y)[i];
-    V r;
+  flat_cells<T, VEC>(n, [&](auto w, int64_t c) {
+    constexpr int W = decltype(w)::value;
+    const auto xv = flat_load<W>(x, c), yv = flat_load<W>(y, c);
+    flat_vec<T, W> r;
 #pragma unroll
-    for (int e = 0; e < VK; ++e) {
+    for (int e = 0; e < W; ++e) {
       if constexpr (XPAY) { const T t = a * yv[e]; r[e] = xv[e] + t; }
       else { const T t = a * xv[e]; r[e] = yv[e] + t; }
     }
-    __builtin_nontemporal_store(r, reinterpret_cast<V*>(y) + i);
-  }
-  if (i == 0)
-    for (int64_t j = nv * VK; j < n; ++j) {
-      if constexpr (XPAY) { const T t = a * y[j]; y[j] = x[j] + t; }
-      else { const T t = a * x[j]; y[j] = y[j] + t; }
-    }
+    flat_store<W>(y, c, r);
+  });
 }
 
 template <class T>

@@ -1,10 +1,11 @@
 // step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (stream scope, graph cache, replay,
 // grouping choice) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
 // neptune_hip_step_loop_chain (one-level schemes, two fields), neptune_hip_step_loop_leapfrog (two-level schemes, three or
-// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and neptune_hip_cg_solve /
-// neptune_hip_pcg_solve / neptune_hip_bicgstab_solve, whose iteration the same engine replays.  Its own translation unit
-// (builds in seconds, linked into libneptune_hip.so): host code that launches applies through the public C API, plus the
-// solvers' few vector kernels (cg_kernels.hpp, pcg_kernels.hpp, bicg_kernels.hpp).
+// four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and the Krylov solvers
+// neptune_hip_cg_solve / neptune_hip_pcg_solve / neptune_hip_bicgstab_solve, whose iteration the same engine replays: ONE
+// host schedule (SolverFrame: the operator's launches, the key, blocks of iterations, the read-back, the counters), and per
+// solver its set-up and its iteration.  Its own translation unit (builds in seconds, linked into libneptune_hip.so): host
+// code that launches applies through the public C API, plus the solvers' few vector kernels (krylov_kernels.hpp).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,9 +15,7 @@
 
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no apply kernel is instantiated here)
-#include "../kernels/cg_kernels.hpp"
-#include "../kernels/pcg_kernels.hpp"
-#include "../kernels/bicg_kernels.hpp"
+#include "../kernels/krylov_kernels.hpp"
 
 using namespace neptune_hip;
 
@@ -57,9 +56,10 @@ void init_key(LoopKey& k, neptune_hip_apply_fn fn, int body, const neptune_hip_a
   k.stream = stream;
 }
 // the cfg to launch with: nullptr unless the caller set anything
-const neptune_hip_launch_cfg_t* loop_cfg(const LoopKey& k) {
-  return (k.cfg.kernel || k.cfg.variant >= 0 || k.cfg.chunk || k.cfg.flags) ? &k.cfg : nullptr;
+const neptune_hip_launch_cfg_t* set_cfg(const neptune_hip_launch_cfg_t* cfg) {
+  return (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
 }
+const neptune_hip_launch_cfg_t* loop_cfg(const LoopKey& k) { return set_cfg(&k.cfg); }
 // the inputs of one launch: the state in fields[cur], a two-level scheme's previous state in fields[prev] (-1: none), the rest
 // riding along unchanged
 void loop_inputs(const LoopKey& k, const void** ins, int cur, int prev) {
@@ -441,7 +441,7 @@ int neptune_hip_step_loop_until(neptune_hip_apply_fn fn, neptune_hip_apply_norm_
   if (!g_until_sum) NEPTUNE_HIP_CHECK(hipMalloc(&g_until_sum, 8));
   void* const sum_dev = g_until_sum;
   StreamScope sc(reinterpret_cast<hipStream_t>(stream));
-  const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
+  const neptune_hip_launch_cfg_t* c = set_cfg(cfg);
   bool fused_ok = fn ? fn_norm != nullptr : true;   // false once the monitored entry has refused this geometry
   int64_t done = 0;
   int cur = 0;   // fields[cur] holds the state
@@ -629,19 +629,8 @@ int neptune_hip_step_loop_system(neptune_hip_group_fn fn, const neptune_hip_appl
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- conjugate gradients on a stream scope
+// ---------------------------------------------------------------- the Krylov solvers on a stream scope
 namespace {
-// the flat kernels' grids: exact for the 16-byte form (one vector per lane), capped for the grid-stride scalar form
-struct CgFlatGrid { bool vec; uint32_t blocks; };
-CgFlatGrid cg_flat_grid(int64_t n, size_t elem, std::initializer_list<const void*> ptrs) {
-  bool aligned = true;
-  for (const void* q : ptrs) aligned = aligned && (uintptr_t)q % 16 == 0;
-  const int64_t nv = n / (int64_t)(16 / elem), vblocks = nv > 0 ? (nv + 255) / 256 : 1;
-  if (aligned && vblocks <= 0x7fffffffLL) return {true, (uint32_t)vblocks};
-  const int64_t want = (n + 255) / 256;
-  return {false, (uint32_t)(want < 256 * 32 ? want : 256 * 32)};
-}
-
 // the solvers' device block holds at least `need` bytes from here on
 void grow_cg_ws(size_t need, hipStream_t stream) {
   if (need <= g_cg_ws_bytes) return;
@@ -684,297 +673,284 @@ bool region_is_whole(const neptune_hip_apply_geom_t* g) {
   return whole;
 }
 
-// minv = nullptr: the solver of 3.11 on the kernels of cg_kernels.hpp; a field: the Jacobi-preconditioned solver of 3.12 on those
-// of pcg_kernels.hpp.  Everything else -- the apply launches, the blocks, the replay schedule, the counters -- is one code.
+// a launch's error, or what an iteration answers for it: a refusal after the iteration's first launch is an error
+int late(int rc) { return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc; }
+
+// a solver entry's arguments once they are checked (include/neptune_hip.h); minv: nullptr unless neptune_hip_pcg_solve
+struct SolveArgs {
+  neptune_hip_apply_fn fn;
+  neptune_hip_apply_dot_fn fn_dot;
+  int body;
+  const neptune_hip_apply_geom_t* g;
+  void* x;
+  const void* b;
+  const void* minv;
+  void* const* work;
+  const void* const* in_rest;
+  int64_t max_iters, check_every;
+  double tol2;
+  void* trace;
+  const neptune_hip_launch_cfg_t* cfg;
+  int64_t* iters_done;
+  double* rr0;
+  double* rr_last;
+};
+
+// What the host loops of all solvers share: the box and the set-up grid, the operator's launches, the read-back of a device
+// scalar, the common part of the graph key and the schedule -- blocks of check_every iterations, each replayed through the
+// engine, r . r read back after each.  A solver is its set-up, its `iteration` and one call of run().
 template <class T>
-int cg_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body,
-                   const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv_field, void* const work[3],
-                   const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, const neptune_hip_launch_cfg_t* cfg,
-                   int64_t* iters_done, double* rr0_out, double* rr_last) {
-  const int dtype = sizeof(T) == 8 ? NEPTUNE_HIP_F64 : NEPTUNE_HIP_F32;
-  T* const r = static_cast<T*>(work[0]);
-  T* const p = static_cast<T*>(work[1]);
-  T* const q = static_cast<T*>(work[2]);
-  const T* const minv = static_cast<const T*>(minv_field);
+struct SolverFrame {
+  const StreamScope& sc;
+  const SolveArgs& a;
+  const neptune_hip_launch_cfg_t* const c;   // the cfg to launch with
   CgBoxParams B;
-  const int64_t n = solver_box(g, B);
-  const int64_t nchunk = (B.n[2] + 255) / 256;
-  const dim3 init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
-  const int64_t init_blocks = (int64_t)init_grid.x * init_grid.y;
+  int64_t n, nchunk, init_blocks;
+  dim3 init_grid;
+  bool fused_ok;   // false once the dot-monitored entry has refused this geometry
+
+  SolverFrame(const StreamScope& sc_, const SolveArgs& a_) : sc(sc_), a(a_), c(set_cfg(a_.cfg)), fused_ok(a_.fn ? a_.fn_dot != nullptr : true) {
+    n = solver_box(a.g, B);
+    nchunk = (B.n[2] + 255) / 256;
+    init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
+    init_blocks = (int64_t)init_grid.x * init_grid.y;
+  }
+  void inputs(const void** ins, const void* in0) const {
+    ins[0] = in0;
+    for (int i = 1; i < a.g->num_inputs; ++i) ins[i] = a.in_rest[i - 1];
+  }
+  // out = A(in0), a plain launch
+  int apply_plain(const void* in0, void* out) const {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    inputs(ins, in0);
+    return a.fn ? a.fn(a.g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(a.body, a.g, ins, out, (void*)sc.stream, c);
+  }
+  // out = A(in0) and *dot_dev = out . in0 out of one dot-monitored launch; NEPTUNE_HIP_EUNSUPPORTED: nothing was launched
+  int apply_dot(const void* in0, void* out, T* dot_dev) const {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    inputs(ins, in0);
+    return a.fn ? a.fn_dot(a.g, ins, out, dot_dev, (void*)sc.stream, c)
+                : neptune_hip_apply_builtin_dot(a.body, a.g, ins, out, dot_dev, (void*)sc.stream, c);
+  }
+  // `count` consecutive device scalars, after everything queued on the stream
+  void read(const T* dev, int count, double* host) const {
+    T h[2] = {0, 0};
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(h, dev, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, sc.stream));
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
+    for (int i = 0; i < count; ++i) host[i] = (double)h[i];
+  }
+  // rr_0 is known: -> whether there is nothing to iterate
+  bool done_after_setup(double rr) const {
+    if (a.rr0) *a.rr0 = rr;
+    if (a.rr_last) *a.rr_last = rr;
+    return rr <= a.tol2 || a.max_iters == 0;
+  }
+  // the part of the graph key every solver fills alike; n_out < 0 tells the solvers' keys from every loop's and from each other's
+  void init_solver_key(LoopKey& key, int n_out) const {
+    init_key(key, a.fn, a.fn ? -1 : a.body, a.g, a.cfg, sc.stream);
+    key.n_out = n_out;
+    key.more[0] = (group_fn)a.fn_dot;
+    key.fields_b[0] = g_cg_ws;
+    key.fields_b[2] = a.trace;
+    key.through[0] = (int)(a.max_iters < 0x7fffffff ? a.max_iters : 0x7fffffff);   // the trace's length is a kernel argument
+    for (int i = 1; i < a.g->num_inputs; ++i) key.in[i] = a.in_rest[i - 1];
+  }
+  // The schedule.  iteration(kind, state): kind 1 uses the dot-monitored launch, kind 2 the fallback; graphs of `per_graph`
+  // iterations (about 40 kernel nodes, as the other loops amortise a graph launch over 16 applies).
+  // retry_on_refusal (CG, whose iteration BEGINS with the dot-monitored launch): NEPTUNE_HIP_EUNSUPPORTED from a block comes
+  // from its first launch alone (replay), so nothing of the block has run; the block runs again as kind 2, as does the rest
+  // of the call.  Without it (BiCGStab, which asks the entry once before its first iteration) a refusal is an error.
+  template <class Iteration>
+  int run(LoopKey& key, const T* rr_dev, int per_graph, bool retry_on_refusal, Iteration&& iteration) {
+    int64_t done = 0;
+    int state = 0;   // an iteration leaves no rotation behind: the device block carries it
+    while (done < a.max_iters) {
+      const int64_t block = a.check_every < a.max_iters - done ? a.check_every : a.max_iters - done;
+      int rc = replay(key, sc, fused_ok ? 1 : 2, block, state, per_graph, iteration);
+      if (retry_on_refusal) {
+        if (rc == NEPTUNE_HIP_EUNSUPPORTED && fused_ok) {
+          fused_ok = false;
+          rc = replay(key, sc, 2, block, state, per_graph, iteration);
+        }
+        if (rc != NEPTUNE_HIP_OK) return rc;
+      } else if (rc != NEPTUNE_HIP_OK) {
+        return late(rc);
+      }
+      g_cg_counts[fused_ok ? 0 : 1] += block;
+      done += block;
+      if (a.iters_done) *a.iters_done = done;
+      double rr;
+      read(rr_dev, 1, &rr);
+      ++g_cg_counts[2];
+      if (a.rr_last) *a.rr_last = rr;
+      if (rr <= a.tol2) break;   // false for a NaN: such a solve runs to max_iters
+    }
+    return NEPTUNE_HIP_OK;
+  }
+};
+// minv = nullptr: the solver of 3.11; a field: the Jacobi-preconditioned solver of 3.12 on its own kernels and scalar block
+template <class T>
+int cg_solve_typed(const StreamScope& sc, const SolveArgs& a) {
+  SolverFrame<T> S(sc, a);
+  const int dtype = sizeof(T) == 8 ? NEPTUNE_HIP_F64 : NEPTUNE_HIP_F32;
+  T* const x = static_cast<T*>(a.x);
+  T* const r = static_cast<T*>(a.work[0]);
+  T* const p = static_cast<T*>(a.work[1]);
+  T* const q = static_cast<T*>(a.work[2]);
+  const T* const b = static_cast<const T*>(a.b);
+  const T* const minv = static_cast<const T*>(a.minv);
+  const int64_t n = S.n;
   // (a null minv is 16-byte aligned: it does not decide the form)
-  const CgFlatGrid upd = cg_flat_grid(n, sizeof(T), {p, q, x, r, minv}), dir = cg_flat_grid(n, sizeof(T), {r, p, minv});
+  const FlatGrid upd = flat_grid(n, sizeof(T), {p, q, x, r, minv}), dir = flat_grid(n, sizeof(T), {r, p, minv});
 
   // the device block: the scalars, then room for the partials of the init and update kernels (two sums with a preconditioner)
-  grow_cg_ws(kCgScalarBytes + (size_t)(minv ? 2 : 1) * (size_t)std::max<int64_t>(init_blocks, upd.blocks) * sizeof(T), sc.stream);
+  grow_cg_ws(kCgScalarBytes + (size_t)(minv ? 2 : 1) * (size_t)std::max<int64_t>(S.init_blocks, upd.blocks) * sizeof(T), sc.stream);
   CgScalars<T>* const scal = static_cast<CgScalars<T>*>(g_cg_ws);
   PcgScalars<T>* const pscal = static_cast<PcgScalars<T>*>(g_cg_ws);   // the same bytes: one of the two is in use
   T* const pq_dev = minv ? &pscal->pq : &scal->pq;
-  T* const rr_dev = minv ? &pscal->rr : &scal->rr;
   T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_cg_ws) + kCgScalarBytes);
-  T* const tr = static_cast<T*>(trace);
-  const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
-
-  auto apply_plain = [&](const void* in0, void* out) -> int {
-    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    ins[0] = in0;
-    for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
-    return fn ? fn(g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(body, g, ins, out, (void*)sc.stream, c);
-  };
-  auto read_rr = [&]() -> double {
-    T h = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, rr_dev, sizeof(T), hipMemcpyDeviceToHost, sc.stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-    return (double)h;
+  T* const tr = static_cast<T*>(a.trace);
+  // the one-workgroup kernel after the init kernel (start) or after the update kernel
+  auto final_kernel = [&](int64_t count, T* trace, int64_t trace_iters, bool start) {
+    if (minv) hipLaunchKernelGGL(neptune_pcg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, count, pscal, trace, trace_iters, start);
+    else hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, count, scal, trace, trace_iters, start);
   };
 
   // set-up: q = A(x), r = p = b - q on Omega, rr_0.  An apply stores nothing outside its launch region, and the flat update
   // reads q everywhere: where the region is not the whole box, q starts as +0 and stays so out there.
-  if (!region_is_whole(g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
-  int rc = apply_plain(x, q);
+  if (!region_is_whole(a.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
+  const int rc = S.apply_plain(x, q);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  if (minv) {
-    hipLaunchKernelGGL(neptune_pcg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, init_blocks, static_cast<const T*>(b), (const T*)q, minv, r, p, partials);
-    hipLaunchKernelGGL(neptune_pcg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, init_blocks, pscal, (T*)nullptr, (int64_t)0, true);
-  } else {
-    hipLaunchKernelGGL(neptune_cg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, static_cast<const T*>(b), (const T*)q, r, p, partials);
-    hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, init_blocks, scal, (T*)nullptr, (int64_t)0, true);
-  }
+  if (minv) hipLaunchKernelGGL(neptune_pcg_init<T>, S.init_grid, dim3(256), 0, sc.stream, S.B, S.nchunk, S.init_blocks, b, (const T*)q, minv, r, p, partials);
+  else hipLaunchKernelGGL(neptune_cg_init<T>, S.init_grid, dim3(256), 0, sc.stream, S.B, S.nchunk, b, (const T*)q, r, p, partials);
+  final_kernel(S.init_blocks, nullptr, 0, true);
   NEPTUNE_HIP_CHECK(hipGetLastError());
-  double rr;
+  double h[2];
   if (minv) {   // rz_0 and rr_0 lie side by side
-    T h[2] = {0, 0};
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(h, &pscal->rz, 2 * sizeof(T), hipMemcpyDeviceToHost, sc.stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-    g_pcg_rz0 = (double)h[0];
-    rr = (double)h[1];
+    S.read(&pscal->rz, 2, h);
+    g_pcg_rz0 = h[0];
   } else {
-    rr = read_rr();
+    S.read(&scal->rr, 1, &h[1]);
   }
-  if (rr0_out) *rr0_out = rr;
-  if (rr_last) *rr_last = rr;
-  if (rr <= tol2 || max_iters == 0) return NEPTUNE_HIP_OK;
+  if (S.done_after_setup(h[1])) return NEPTUNE_HIP_OK;
 
   LoopKey key;
-  init_key(key, fn, fn ? -1 : body, g, cfg, sc.stream);
-  key.n_out = -1;   // no other loop's key: the solver's iteration
-  key.more[0] = (group_fn)fn_dot;
+  S.init_solver_key(key, -1);
   key.fields[0] = x; key.fields[1] = r; key.fields[2] = p; key.fields[3] = q;
-  key.fields_b[0] = g_cg_ws;
-  key.fields_b[2] = trace;
   key.fields_b[3] = const_cast<T*>(minv);   // a graph captured with one preconditioner is never replayed with another
-  key.through[0] = (int)(max_iters < 0x7fffffff ? max_iters : 0x7fffffff);   // the trace's length is a kernel argument
-  for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in_rest[i - 1];
 
   // one iteration; kind 1: q = A(p) and pq out of one dot-monitored launch, kind 2: a plain launch and neptune_hip_dot.
   // NEPTUNE_HIP_EUNSUPPORTED comes from the dot-monitored entry alone, which then has launched nothing.
   auto iteration = [&](int kind, int&) -> int {
     int rc;
     if (kind == 1) {
-      const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-      ins[0] = p;
-      for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
-      rc = fn ? fn_dot(g, ins, q, pq_dev, (void*)sc.stream, c)
-              : neptune_hip_apply_builtin_dot(body, g, ins, q, pq_dev, (void*)sc.stream, c);
+      rc = S.apply_dot(p, q, pq_dev);
       if (rc != NEPTUNE_HIP_OK) return rc;
       key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
     } else {
-      rc = apply_plain(p, q);
-      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-      rc = neptune_hip_dot(dtype, g, q, p, pq_dev, (void*)sc.stream);
-      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+      rc = S.apply_plain(p, q);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
+      rc = neptune_hip_dot(dtype, a.g, q, p, pq_dev, (void*)sc.stream);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
     }
-    if (minv) {
-      if (upd.vec) hipLaunchKernelGGL(neptune_pcg_update_v<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)p, (const T*)q, minv, static_cast<T*>(x), r, partials);
-      else hipLaunchKernelGGL(neptune_pcg_update<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)p, (const T*)q, minv, static_cast<T*>(x), r, partials);
-      hipLaunchKernelGGL(neptune_pcg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, (int64_t)upd.blocks, pscal, tr, max_iters, false);
-      if (dir.vec) hipLaunchKernelGGL(neptune_pcg_direction_v<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)r, minv, p);
-      else hipLaunchKernelGGL(neptune_pcg_direction<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const PcgScalars<T>*)pscal, (const T*)r, minv, p);
-      NEPTUNE_HIP_CHECK(hipGetLastError());
-      return NEPTUNE_HIP_OK;
-    }
-    if (upd.vec) hipLaunchKernelGGL(neptune_cg_update_v<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)p, (const T*)q, static_cast<T*>(x), r, partials);
-    else hipLaunchKernelGGL(neptune_cg_update<T>, dim3(upd.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)p, (const T*)q, static_cast<T*>(x), r, partials);
-    hipLaunchKernelGGL(neptune_cg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, (int64_t)upd.blocks, scal, tr, max_iters, false);
-    if (dir.vec) hipLaunchKernelGGL(neptune_cg_direction_v<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)r, p);
-    else hipLaunchKernelGGL(neptune_cg_direction<T>, dim3(dir.blocks), dim3(256), 0, sc.stream, n, (const CgScalars<T>*)scal, (const T*)r, p);
+    if (minv) flat_launch(upd, sc.stream, neptune_pcg_update<T, true>, neptune_pcg_update<T, false>, n, pscal, p, q, minv, x, r, partials);
+    else flat_launch(upd, sc.stream, neptune_cg_update<T, true>, neptune_cg_update<T, false>, n, scal, p, q, x, r, partials);
+    final_kernel((int64_t)upd.blocks, tr, a.max_iters, false);
+    if (minv) flat_launch(dir, sc.stream, neptune_pcg_direction<T, true>, neptune_pcg_direction<T, false>, n, pscal, r, minv, p);
+    else flat_launch(dir, sc.stream, neptune_cg_direction<T, true>, neptune_cg_direction<T, false>, n, scal, r, p);
     NEPTUNE_HIP_CHECK(hipGetLastError());
     return NEPTUNE_HIP_OK;
   };
-
-  bool fused_ok = fn ? fn_dot != nullptr : true;   // false once the dot-monitored entry has refused this geometry
-  int64_t done = 0;
-  int state = 0;   // an iteration leaves no rotation behind: the device block carries it
-  while (done < max_iters) {
-    const int64_t block = check_every < max_iters - done ? check_every : max_iters - done;
-    // graphs of 8 iterations (about 40 kernel nodes), as the other loops amortise a graph launch over 16 applies
-    rc = NEPTUNE_HIP_EUNSUPPORTED;
-    if (fused_ok) {
-      rc = replay(key, sc, 1, block, state, 8, iteration);
-      if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused_ok = false;   // from the block's first launch: nothing of this block has run
-    }
-    if (!fused_ok && rc == NEPTUNE_HIP_EUNSUPPORTED) rc = replay(key, sc, 2, block, state, 8, iteration);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    g_cg_counts[fused_ok ? 0 : 1] += block;
-    done += block;
-    if (iters_done) *iters_done = done;
-    rr = read_rr();
-    ++g_cg_counts[2];
-    if (rr_last) *rr_last = rr;
-    if (rr <= tol2) break;   // false for a NaN: such a solve runs to max_iters
-  }
-  return NEPTUNE_HIP_OK;
+  return S.run(key, minv ? &pscal->rr : &scal->rr, 8, true, iteration);
 }
 
-// ---------------------------------------------------------------- BiCGStab on a stream scope
-// A host loop of its own on the same engine: other vectors, other kernels and three reduction points per iteration; it
-// shares with cg_solve_typed the box, the device block and the block / replay / read-back schedule.
+// BiCGStab (3.13): other vectors, other kernels and three reduction points per iteration on the same frame
 template <class T>
-int bicgstab_solve_typed(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body,
-                         const neptune_hip_apply_geom_t* g, void* x_field, const void* b, void* const work[5],
-                         const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace,
-                         const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0_out, double* rr_last) {
-  T* const x = static_cast<T*>(x_field);
-  T* const r = static_cast<T*>(work[0]);    // s between the two half-steps
-  T* const rh = static_cast<T*>(work[1]);
-  T* const p = static_cast<T*>(work[2]);
-  T* const v = static_cast<T*>(work[3]);
-  T* const t = static_cast<T*>(work[4]);
-  CgBoxParams B;
-  const int64_t n = solver_box(g, B);
-  const int64_t nchunk = (B.n[2] + 255) / 256;
-  const dim3 init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
-  const int64_t init_blocks = (int64_t)init_grid.x * init_grid.y;
-  const CgFlatGrid g_rv = cg_flat_grid(n, sizeof(T), {rh, v}), g_s = cg_flat_grid(n, sizeof(T), {v, r}),
-                   g_tt = cg_flat_grid(n, sizeof(T), {t}), g_ts = cg_flat_grid(n, sizeof(T), {t, r}),
-                   g_upd = cg_flat_grid(n, sizeof(T), {p, t, rh, x, r}), g_dir = cg_flat_grid(n, sizeof(T), {r, v, p});
+int bicgstab_solve_typed(const StreamScope& sc, const SolveArgs& a) {
+  SolverFrame<T> S(sc, a);
+  T* const x = static_cast<T*>(a.x);
+  T* const r = static_cast<T*>(a.work[0]);    // s between the two half-steps
+  T* const rh = static_cast<T*>(a.work[1]);
+  T* const p = static_cast<T*>(a.work[2]);
+  T* const v = static_cast<T*>(a.work[3]);
+  T* const t = static_cast<T*>(a.work[4]);
+  const int64_t n = S.n;
+  const FlatGrid g_rv = flat_grid(n, sizeof(T), {rh, v}), g_s = flat_grid(n, sizeof(T), {v, r}),
+                 g_tt = flat_grid(n, sizeof(T), {t}), g_ts = flat_grid(n, sizeof(T), {t, r}),
+                 g_upd = flat_grid(n, sizeof(T), {p, t, rh, x, r}), g_dir = flat_grid(n, sizeof(T), {r, v, p});
   // the device block: the scalars, then room for the partials of the init, sum and update kernels (two sums at the most)
-  const int64_t most = std::max<int64_t>({init_blocks, g_rv.blocks, g_tt.blocks, g_ts.blocks, g_upd.blocks});
+  const int64_t most = std::max<int64_t>({S.init_blocks, g_rv.blocks, g_tt.blocks, g_ts.blocks, g_upd.blocks});
   grow_cg_ws(kBicgScalarBytes + 2 * (size_t)most * sizeof(T), sc.stream);
   BicgScalars<T>* const scal = static_cast<BicgScalars<T>*>(g_cg_ws);
   T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_cg_ws) + kBicgScalarBytes);
-  T* const tr = static_cast<T*>(trace);
-  const neptune_hip_launch_cfg_t* c = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
-
-  auto inputs = [&](const void** ins, const void* in0) {
-    ins[0] = in0;
-    for (int i = 1; i < g->num_inputs; ++i) ins[i] = in_rest[i - 1];
-  };
-  auto apply_plain = [&](const void* in0, void* out) -> int {
-    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    inputs(ins, in0);
-    return fn ? fn(g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(body, g, ins, out, (void*)sc.stream, c);
-  };
   auto final_kernel = [&](int64_t count, int stage) {
-    hipLaunchKernelGGL(neptune_bicg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, count, scal, tr, max_iters, stage);
-  };
-  auto read_rr = [&]() -> double {
-    T h = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, &scal->rr, sizeof(T), hipMemcpyDeviceToHost, sc.stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-    return (double)h;
+    hipLaunchKernelGGL(neptune_bicg_final<T>, dim3(1), dim3(256), 0, sc.stream, (const T*)partials, count, scal, static_cast<T*>(a.trace), a.max_iters, stage);
   };
 
   // set-up: v = A(x), r = rh = p = b - v on Omega, rr_0 = rho_0.  An apply stores nothing outside its launch region, and the
   // flat kernels read v and t everywhere: where the region is not the whole box, both start as +0 and stay so out there.
-  if (!region_is_whole(g)) {
+  if (!region_is_whole(a.g)) {
     NEPTUNE_HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(T), sc.stream));
     NEPTUNE_HIP_CHECK(hipMemsetAsync(t, 0, (size_t)n * sizeof(T), sc.stream));
   }
-  int rc = apply_plain(x, v);
+  int rc = S.apply_plain(x, v);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  hipLaunchKernelGGL(neptune_bicg_init<T>, init_grid, dim3(256), 0, sc.stream, B, nchunk, static_cast<const T*>(b), (const T*)v, r, rh, p, partials);
-  final_kernel(init_blocks, kBicgStart);
+  hipLaunchKernelGGL(neptune_bicg_init<T>, S.init_grid, dim3(256), 0, sc.stream, S.B, S.nchunk, static_cast<const T*>(a.b), (const T*)v, r, rh, p, partials);
+  final_kernel(S.init_blocks, kBicgStart);
   NEPTUNE_HIP_CHECK(hipGetLastError());
-  double rr = read_rr();
-  if (rr0_out) *rr0_out = rr;
-  if (rr_last) *rr_last = rr;
-  if (rr <= tol2 || max_iters == 0) return NEPTUNE_HIP_OK;
+  double rr;
+  S.read(&scal->rr, 1, &rr);
+  if (S.done_after_setup(rr)) return NEPTUNE_HIP_OK;
 
   LoopKey key;
-  init_key(key, fn, fn ? -1 : body, g, cfg, sc.stream);
-  key.n_out = -2;   // no other loop's key, and not the CG solvers': this solver's iteration
-  key.more[0] = (group_fn)fn_dot;
+  S.init_solver_key(key, -2);
   key.fields[0] = x; key.fields[1] = r; key.fields[2] = p; key.fields[3] = v;
-  key.fields_b[0] = g_cg_ws;
-  key.fields_b[2] = trace;
-  key.fields_c[0] = rh; key.fields_c[1] = t; key.fields_c[2] = const_cast<void*>(b);
-  key.through[0] = (int)(max_iters < 0x7fffffff ? max_iters : 0x7fffffff);   // the trace's length is a kernel argument
-  for (int i = 1; i < g->num_inputs; ++i) key.in[i] = in_rest[i - 1];
+  key.fields_c[0] = rh; key.fields_c[1] = t; key.fields_c[2] = const_cast<void*>(a.b);
 
-  const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-  auto dot_launch = [&]() -> int {
-    inputs(ins, r);
-    return fn ? fn_dot(g, ins, t, &scal->ts, (void*)sc.stream, c)
-              : neptune_hip_apply_builtin_dot(body, g, ins, t, &scal->ts, (void*)sc.stream, c);
-  };
   // The dot-monitored entry is an iteration's FOURTH launch: a refusal from there would leave half an iteration behind.  So the
   // entry is asked once per call, before the first iteration, with the very launch step 3 makes (t = A(r) and ts, both of
   // which every iteration writes again before it reads them): a refusal -- NEPTUNE_HIP_EUNSUPPORTED, nothing launched -- is
   // remembered for the rest of the call, and an acceptance has grown the monitor workspace outside of any capture.
-  bool fused_ok = fn ? fn_dot != nullptr : true;
-  if (fused_ok) {
-    rc = dot_launch();
-    if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused_ok = false;
+  if (S.fused_ok) {
+    rc = S.apply_dot(r, t, &scal->ts);
+    if (rc == NEPTUNE_HIP_EUNSUPPORTED) S.fused_ok = false;
     else if (rc != NEPTUNE_HIP_OK) return rc;
   }
 
   // one iteration; kind 1: t = A(s) and ts out of one dot-monitored launch, then tt; kind 2: a plain launch, then ts and tt out
   // of one pass
   auto iteration = [&](int kind, int&) -> int {
-    int rc;
     // 1. v = A(p), rv = rh . v, alpha
-    rc = apply_plain(p, v);
-    if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-    if (g_rv.vec) hipLaunchKernelGGL(neptune_bicg_rv_v<T>, dim3(g_rv.blocks), dim3(256), 0, sc.stream, n, (const T*)rh, (const T*)v, partials);
-    else hipLaunchKernelGGL(neptune_bicg_rv<T>, dim3(g_rv.blocks), dim3(256), 0, sc.stream, n, (const T*)rh, (const T*)v, partials);
+    int rc = S.apply_plain(p, v);
+    if (rc != NEPTUNE_HIP_OK) return late(rc);
+    flat_launch(g_rv, sc.stream, neptune_bicg_rv<T, true>, neptune_bicg_rv<T, false>, n, rh, v, partials);
     final_kernel((int64_t)g_rv.blocks, kBicgRv);
     // 2. s = r - alpha v, in place
-    if (g_s.vec) hipLaunchKernelGGL(neptune_bicg_s_v<T>, dim3(g_s.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)v, r);
-    else hipLaunchKernelGGL(neptune_bicg_s<T>, dim3(g_s.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)v, r);
+    flat_launch(g_s, sc.stream, neptune_bicg_s<T, true>, neptune_bicg_s<T, false>, n, scal, v, r);
     NEPTUNE_HIP_CHECK(hipGetLastError());
     // 3. t = A(s), ts, tt, omega
     if (kind == 1) {
-      rc = dot_launch();
-      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
+      rc = S.apply_dot(r, t, &scal->ts);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
       key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
-      if (g_tt.vec) hipLaunchKernelGGL((neptune_bicg_tt_v<T, false>), dim3(g_tt.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)t, partials);
-      else hipLaunchKernelGGL((neptune_bicg_tt<T, false>), dim3(g_tt.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)t, partials);
+      flat_launch(g_tt, sc.stream, neptune_bicg_tt<T, true, false>, neptune_bicg_tt<T, false, false>, n, t, t, partials);
       final_kernel((int64_t)g_tt.blocks, kBicgTt);
     } else {
-      rc = apply_plain(r, t);
-      if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-      if (g_ts.vec) hipLaunchKernelGGL((neptune_bicg_tt_v<T, true>), dim3(g_ts.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)r, partials);
-      else hipLaunchKernelGGL((neptune_bicg_tt<T, true>), dim3(g_ts.blocks), dim3(256), 0, sc.stream, n, (const T*)t, (const T*)r, partials);
+      rc = S.apply_plain(r, t);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
+      flat_launch(g_ts, sc.stream, neptune_bicg_tt<T, true, true>, neptune_bicg_tt<T, false, true>, n, t, r, partials);
       final_kernel((int64_t)g_ts.blocks, kBicgTsTt);
     }
     // 4. x, r, rho', rr', beta, the trace row and the rotation
-    if (g_upd.vec) hipLaunchKernelGGL(neptune_bicg_update_v<T>, dim3(g_upd.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)p, (const T*)t, (const T*)rh, x, r, partials);
-    else hipLaunchKernelGGL(neptune_bicg_update<T>, dim3(g_upd.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)p, (const T*)t, (const T*)rh, x, r, partials);
+    flat_launch(g_upd, sc.stream, neptune_bicg_update<T, true>, neptune_bicg_update<T, false>, n, scal, p, t, rh, x, r, partials);
     final_kernel((int64_t)g_upd.blocks, kBicgUpdate);
     // 5. p = r + beta (p - omega v)
-    if (g_dir.vec) hipLaunchKernelGGL(neptune_bicg_direction_v<T>, dim3(g_dir.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)r, (const T*)v, p);
-    else hipLaunchKernelGGL(neptune_bicg_direction<T>, dim3(g_dir.blocks), dim3(256), 0, sc.stream, n, (const BicgScalars<T>*)scal, (const T*)r, (const T*)v, p);
+    flat_launch(g_dir, sc.stream, neptune_bicg_direction<T, true>, neptune_bicg_direction<T, false>, n, scal, r, v, p);
     NEPTUNE_HIP_CHECK(hipGetLastError());
     return NEPTUNE_HIP_OK;
   };
-
-  int64_t done = 0;
-  int state = 0;   // an iteration leaves no rotation behind: the device block carries it
-  while (done < max_iters) {
-    const int64_t block = check_every < max_iters - done ? check_every : max_iters - done;
-    // graphs of 4 iterations: an iteration is 11 kernel nodes (10 on the fallback path) against CG's 5, so 4 of them are the
-    // about 40 nodes over which the other loops amortise a graph launch
-    rc = replay(key, sc, fused_ok ? 1 : 2, block, state, 4, iteration);
-    if (rc != NEPTUNE_HIP_OK) return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc;
-    g_cg_counts[fused_ok ? 0 : 1] += block;
-    done += block;
-    if (iters_done) *iters_done = done;
-    rr = read_rr();
-    ++g_cg_counts[2];
-    if (rr_last) *rr_last = rr;
-    if (rr <= tol2) break;   // false for a NaN: such a solve runs to max_iters
-  }
-  return NEPTUNE_HIP_OK;
+  // graphs of 4 iterations: an iteration is 11 kernel nodes (10 on the fallback path) against CG's 5
+  return S.run(key, &scal->rr, 4, false, iteration);
 }
 }  // namespace
 
@@ -1028,35 +1004,38 @@ static int solver_args_checked(neptune_hip_apply_fn fn, int body, int dtype_of_f
   return NEPTUNE_HIP_OK;
 }
 
-// the argument checks and the dispatch on the element type of both CG entries; pre: neptune_hip_pcg_solve (minv is required
-// and is a sixth field)
-static int cg_solve_checked(bool pre, neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
-                            const neptune_hip_apply_geom_t* g, void* x, const void* b, const void* minv, void* const work[3],
-                            const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
-                            const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+// The three entries' common path: counters and out-parameters zeroed, the arguments checked (x, b, the solver's n_work work
+// fields and, where a.minv is set, minv as one more field; a trace of `cols` values per iteration), then the dispatch on the
+// element type
+enum Solver { kSolverCg, kSolverPcg, kSolverBicgstab };
+static int solve_checked(Solver solver, int dtype_of_fn, void* stream, const SolveArgs& a) {
   g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
-  if (iters_done) *iters_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
-  if (!work) return NEPTUNE_HIP_EINVAL;
-  const void* const six[6] = {x, b, work[0], work[1], work[2], minv};
+  if (a.iters_done) *a.iters_done = 0;
+  if (a.rr0) *a.rr0 = 0.0;
+  if (a.rr_last) *a.rr_last = 0.0;
+  if (!a.work) return NEPTUNE_HIP_EINVAL;
+  const int n_work = solver == kSolverBicgstab ? 5 : 3;
+  const int cols = solver == kSolverCg ? 2 : solver == kSolverPcg ? 3 : 5;
+  const void* fields[8] = {a.x, a.b};
+  int count = 2;
+  for (int i = 0; i < n_work; ++i) fields[count++] = a.work[i];
+  if (solver == kSolverPcg) fields[count++] = a.minv;
   int dtype = 0;
-  if (solver_args_checked(fn, body, dtype_of_fn, g, six, pre ? 6 : 5, in_rest, max_iters, check_every, trace, (pre ? 3 : 2) * max_iters,
+  if (solver_args_checked(a.fn, a.body, dtype_of_fn, a.g, fields, count, a.in_rest, a.max_iters, a.check_every, a.trace, cols * a.max_iters,
                           stream, &dtype) != NEPTUNE_HIP_OK)
     return NEPTUNE_HIP_EINVAL;
   ensure_init();
   StreamScope sc(reinterpret_cast<hipStream_t>(stream));
-  return dtype == NEPTUNE_HIP_F64
-             ? cg_solve_typed<double>(sc, fn, fn_dot, body, g, x, b, pre ? minv : nullptr, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last)
-             : cg_solve_typed<float>(sc, fn, fn_dot, body, g, x, b, pre ? minv : nullptr, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last);
+  if (solver == kSolverBicgstab) return dtype == NEPTUNE_HIP_F64 ? bicgstab_solve_typed<double>(sc, a) : bicgstab_solve_typed<float>(sc, a);
+  return dtype == NEPTUNE_HIP_F64 ? cg_solve_typed<double>(sc, a) : cg_solve_typed<float>(sc, a);
 }
 
 int neptune_hip_cg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
                          const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[3], const void* const* in_rest,
                          int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
                          const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
-  return cg_solve_checked(false, fn, fn_dot, body, dtype_of_fn, g, x, b, nullptr, work, in_rest, max_iters, check_every, tol2, trace,
-                          stream, cfg, iters_done, rr0, rr_last);
+  return solve_checked(kSolverCg, dtype_of_fn, stream,
+                       {fn, fn_dot, body, g, x, b, nullptr, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last});
 }
 
 double neptune_hip_pcg_rz0(void) { return g_pcg_rz0; }
@@ -1066,29 +1045,16 @@ int neptune_hip_pcg_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_d
                           const void* const* in_rest, int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
                           const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
   g_pcg_rz0 = 0.0;
-  return cg_solve_checked(true, fn, fn_dot, body, dtype_of_fn, g, x, b, minv, work, in_rest, max_iters, check_every, tol2, trace,
-                          stream, cfg, iters_done, rr0, rr_last);
+  return solve_checked(kSolverPcg, dtype_of_fn, stream,
+                       {fn, fn_dot, body, g, x, b, minv, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last});
 }
 
 int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn fn_dot, int body, int dtype_of_fn,
                                const neptune_hip_apply_geom_t* g, void* x, const void* b, void* const work[5], const void* const* in_rest,
                                int64_t max_iters, int64_t check_every, double tol2, void* trace, void* stream,
                                const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
-  g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
-  if (iters_done) *iters_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
-  if (!work) return NEPTUNE_HIP_EINVAL;
-  const void* const seven[7] = {x, b, work[0], work[1], work[2], work[3], work[4]};
-  int dtype = 0;
-  if (solver_args_checked(fn, body, dtype_of_fn, g, seven, 7, in_rest, max_iters, check_every, trace, 5 * max_iters, stream, &dtype) !=
-      NEPTUNE_HIP_OK)
-    return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
-  return dtype == NEPTUNE_HIP_F64
-             ? bicgstab_solve_typed<double>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last)
-             : bicgstab_solve_typed<float>(sc, fn, fn_dot, body, g, x, b, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last);
+  return solve_checked(kSolverBicgstab, dtype_of_fn, stream,
+                       {fn, fn_dot, body, g, x, b, nullptr, work, in_rest, max_iters, check_every, tol2, trace, cfg, iters_done, rr0, rr_last});
 }
 
 }  // extern "C"

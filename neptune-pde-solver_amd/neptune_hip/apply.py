@@ -194,6 +194,38 @@ def cg_counts():
     return fused.value, fallback.value, checks.value
 
 
+def _krylov_solve(entry, x, b, bounds, max_iters, tol2, check_every, others, trace, dot, cfg, work, region, stream, *,
+                  who, symbol, n_work, out_index, cols, extra=()):
+    """what cg_solve and bicgstab_solve share: the entries, the geometry (the field work[out_index] receives the operator's
+    result), the n_work work fields and the trace of `cols` values per iteration, then the C entry `symbol`(fn, fn_dot, body,
+    dtype, g, x, b, *extra, work, ...) and the result tuple.  who: the caller's name in error texts."""
+    import torch
+    lib = _capi.load()
+    others = list(others)
+    if work is None:
+        work = [DeviceField.empty_like(x) for _ in range(n_work)]
+    g = geom_for([x] + others, work[out_index], bounds, region)
+    st = current_stream_ptr() if stream is None else stream
+    is_entry = hasattr(entry, "fn")
+    fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
+    if isinstance(dot, str):
+        if dot not in ("auto", "fallback"):
+            raise ValueError(f'{who}: dot is "auto", "fallback", None or a dot entry')
+        dot = entry if (dot == "auto" and is_entry) else None
+    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    tr = torch.zeros(cols * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    warr = (C.c_void_p * n_work)(*[f.ptr for f in work])
+    rest = _in_array(others) if others else None
+    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    rc = getattr(lib, symbol)(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, *extra, warr, rest,
+                              max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
+                              C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    _capi.check(rc, symbol)
+    if trace:
+        return done.value, rr0.value, last.value, tr.cpu().numpy()[:cols * done.value].reshape(-1, cols)
+    return done.value, rr0.value, last.value
+
+
 def cg_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int, tol2: float, check_every: int = 1,
              others: Sequence[DeviceField] = (), trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
              work: Optional[Sequence[DeviceField]] = None, region: Optional[Box] = None, stream: Optional[int] = None,
@@ -209,38 +241,13 @@ def cg_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters: int,
     minv: a field like x holding the inverse of a diagonal preconditioner (jacobi_minv): the solve is then
     neptune_hip_pcg_solve, tol2 still bounds the true r . r, and the trace has shape (iters, 3): (p . A(p) of iteration k,
     r . (minv r) after it, r . r after it)."""
-    import torch
-    lib = _capi.load()
-    others = list(others)
-    if work is None:
-        work = [DeviceField.empty_like(x) for _ in range(3)]
-    g = geom_for([x] + others, work[2], bounds, region)
-    st = current_stream_ptr() if stream is None else stream
-    is_entry = hasattr(entry, "fn")
-    fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
-    if isinstance(dot, str):
-        if dot not in ("auto", "fallback"):
-            raise ValueError('cg_solve: dot is "auto", "fallback", None or a dot entry')
-        dot = entry if (dot == "auto" and is_entry) else None
-    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
-    cols = 2 if minv is None else 3
-    tr = torch.zeros(cols * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
-    warr = (C.c_void_p * 3)(*[f.ptr for f in work])
-    rest = _in_array(others) if others else None
-    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-    tail = (warr, rest, max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
-            C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
     if minv is None:
-        rc = lib.neptune_hip_cg_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, *tail)
-        _capi.check(rc, "neptune_hip_cg_solve")
-    else:
-        if minv.box != x.box or minv.dtype != x.dtype:
-            raise ValueError("cg_solve: minv must have the box and the element type of x")
-        rc = lib.neptune_hip_pcg_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, minv.ptr, *tail)
-        _capi.check(rc, "neptune_hip_pcg_solve")
-    if trace:
-        return done.value, rr0.value, last.value, tr.cpu().numpy()[:cols * done.value].reshape(-1, cols)
-    return done.value, rr0.value, last.value
+        return _krylov_solve(entry, x, b, bounds, max_iters, tol2, check_every, others, trace, dot, cfg, work, region, stream,
+                             who="cg_solve", symbol="neptune_hip_cg_solve", n_work=3, out_index=2, cols=2)
+    if minv.box != x.box or minv.dtype != x.dtype:
+        raise ValueError("cg_solve: minv must have the box and the element type of x")
+    return _krylov_solve(entry, x, b, bounds, max_iters, tol2, check_every, others, trace, dot, cfg, work, region, stream,
+                         who="cg_solve", symbol="neptune_hip_pcg_solve", n_work=3, out_index=2, cols=3, extra=(minv.ptr,))
 
 
 def pcg_rz0() -> float:
@@ -258,33 +265,10 @@ def bicgstab_solve(entry, x: DeviceField, b: DeviceField, bounds: Box, max_iters
     Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a numpy array of shape (iters, 5) holding
     (rh . A(p), A(s) . s, A(s) . A(s) of iteration k, rh . r and r . r after it).  cg_counts() tells which path the iterations
     took."""
-    import torch
-    lib = _capi.load()
-    others = list(others)
-    if work is None:
-        work = [DeviceField.empty_like(x) for _ in range(5)]
-    if len(work) != 5:
+    if work is not None and len(work) != 5:
         raise ValueError("bicgstab_solve: work is five fields (r, rh, p, v, t)")
-    g = geom_for([x] + others, work[3], bounds, region)
-    st = current_stream_ptr() if stream is None else stream
-    is_entry = hasattr(entry, "fn")
-    fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
-    if isinstance(dot, str):
-        if dot not in ("auto", "fallback"):
-            raise ValueError('bicgstab_solve: dot is "auto", "fallback", None or a dot entry')
-        dot = entry if (dot == "auto" and is_entry) else None
-    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
-    tr = torch.zeros(5 * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
-    warr = (C.c_void_p * 5)(*[f.ptr for f in work])
-    rest = _in_array(others) if others else None
-    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-    rc = lib.neptune_hip_bicgstab_solve(fn, fn_dot, -1 if is_entry else entry, x.dtype, C.byref(g), x.ptr, b.ptr, warr, rest,
-                                        max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
-                                        C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
-    _capi.check(rc, "neptune_hip_bicgstab_solve")
-    if trace:
-        return done.value, rr0.value, last.value, tr.cpu().numpy()[:5 * done.value].reshape(-1, 5)
-    return done.value, rr0.value, last.value
+    return _krylov_solve(entry, x, b, bounds, max_iters, tol2, check_every, others, trace, dot, cfg, work, region, stream,
+                         who="bicgstab_solve", symbol="neptune_hip_bicgstab_solve", n_work=5, out_index=3, cols=5)
 
 
 def _omega(like: DeviceField, bounds: Box, region: Optional[Box]):
