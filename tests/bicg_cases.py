@@ -10,7 +10,8 @@ ONE association order, in the module text and in numpy_operator alike:
     m_d = (1 + c_d) * u<p - e_d>                     three products
     s   = ((((m_0 + m_1) + m_2) + u<p + e_0>) + u<p + e_1>) + u<p + e_2>      left to right
     A(u)<p> = (14 * u<p>) - s                         one product, one subtraction
-every operation rounded once in the element type.
+every operation rounded once in the element type.  At rank 1 and 2 the same with c = C_ADV[:rank]: rank products, s summed in
+the same order over the dimensions there are, centre weight 2 * rank + sum(c) + sigma (9 at rank 2, 7 at rank 1).
 
 Everything else follows the normative definition of neptune_hip_bicgstab_solve (include/neptune_hip.h) the way cg_cases
 follows neptune_hip_cg_solve's: arithmetic in the element type, one rounding per operation (numpy never fuses), the operator
@@ -27,11 +28,14 @@ C_ADV = (4.0, 2.0, 1.0)
 SIGMA = 1.0
 
 
-def bicg_module(shape, dtype=np.float64):
-    """NeptuneIR text of @entry(out, in): out = A(in) as described above (pcg_cases.pcg_module's frame: box [0, shape), bounds
-    one cell in from every face); rank 3"""
-    assert len(shape) == 3
-    rank = 3
+def bicg_module(shape, dtype=np.float64, origin=None, bounds=None):
+    """NeptuneIR text of @entry(out, in): out = A(in) as described above (pcg_cases.pcg_module's frame: box
+    [origin, origin + shape), origin 0 by default; `bounds` logical, by default one cell in from every face); rank 1 to 3"""
+    rank = len(shape)
+    assert 1 <= rank <= 3
+    origin = [0] * rank if origin is None else [int(x) for x in origin]
+    if bounds is None:
+        bounds = ([o + 1 for o in origin], [o + n - 1 for o, n in zip(origin, shape)])
     elem = mc.ELEM[np.dtype(dtype)]
     lst = lambda v: ", ".join(str(int(x)) for x in v)
     mr = "x".join(["?"] * rank) + "x" + elem
@@ -43,17 +47,21 @@ def bicg_module(shape, dtype=np.float64):
             off = list(zero)
             off[d] = sgn
             acc.append(f"        %n{d}{tag} = neptune_ir.access %a[{lst(off)}] : !temp -> {elem}")
-    ops = [f"        %wc = arith.constant {6.0 + sum(C_ADV) + SIGMA!r} : {elem}"]
+    ops = [f"        %wc = arith.constant {centre_weight(rank)!r} : {elem}"]
     for d in range(rank):
         ops += [f"        %w{d} = arith.constant {1.0 + C_ADV[d]!r} : {elem}",
                 f"        %m{d} = arith.mulf %w{d}, %n{d}m : {elem}"]
-    ops += [f"        %s0 = arith.addf %m0, %m1 : {elem}", f"        %s1 = arith.addf %s0, %m2 : {elem}",
-            f"        %s2 = arith.addf %s1, %n0p : {elem}", f"        %s3 = arith.addf %s2, %n1p : {elem}",
-            f"        %s4 = arith.addf %s3, %n2p : {elem}", f"        %t0 = arith.mulf %wc, %c : {elem}",
-            f"        %t1 = arith.subf %t0, %s4 : {elem}", f"        neptune_ir.yield %t1 : {elem}"]
+    # s = m_0 + ... + m_(rank-1) + u<p + e_0> + ... + u<p + e_(rank-1)>, left to right
+    terms = [f"m{d}" for d in range(rank)] + [f"n{d}p" for d in range(rank)]
+    prev = terms[0]
+    for t, nm in enumerate(terms[1:]):
+        ops.append(f"        %s{t} = arith.addf %{prev}, %{nm} : {elem}")
+        prev = f"s{t}"
+    ops += [f"        %t0 = arith.mulf %wc, %c : {elem}",
+            f"        %t1 = arith.subf %t0, %{prev} : {elem}", f"        neptune_ir.yield %t1 : {elem}"]
     out = ['#loc = #neptune_ir.location<"cell">',
-           f"#b   = #neptune_ir.bounds<lb = [{lst(zero)}], ub = [{lst(shape)}]>",
-           f"#bi  = #neptune_ir.bounds<lb = [{lst([1] * rank)}], ub = [{lst([n - 1 for n in shape])}]>",
+           f"#b   = #neptune_ir.bounds<lb = [{lst(origin)}], ub = [{lst([o + n for o, n in zip(origin, shape)])}]>",
+           f"#bi  = #neptune_ir.bounds<lb = [{lst(bounds[0])}], ub = [{lst(bounds[1])}]>",
            f"!temp  = !neptune_ir.temp<element = {elem}, bounds = #b, location = #loc>",
            f"!field = !neptune_ir.field<element = {elem}, bounds = #b, location = #loc>",
            "module {",
@@ -70,23 +78,33 @@ def bicg_module(shape, dtype=np.float64):
     return "\n".join(out) + "\n"
 
 
-def numpy_operator(u: np.ndarray) -> np.ndarray:
-    """the operator restated in numpy, in the association order fixed above"""
+def centre_weight(rank):
+    """2 * rank + c_0 + ... + c_(rank-1) + sigma: 14 at rank 3, 9 at rank 2, 7 at rank 1"""
+    return 2.0 * rank + sum(C_ADV[:rank]) + SIGMA
+
+
+def numpy_operator(u: np.ndarray, origin=None, bounds=None) -> np.ndarray:
+    """the operator restated in numpy, in the association order fixed above, at rank 1 to 3 with c = C_ADV[:rank]; origin and
+    bounds (logical) as bicg_module's"""
     dt = u.dtype.type
-    shape = u.shape
-    where = tuple(slice(1, n - 1) for n in shape)
+    shape, rank = u.shape, u.ndim
+    origin = [0] * rank if origin is None else list(origin)
+    if bounds is None:
+        bounds = ([o + 1 for o in origin], [o + n - 1 for o, n in zip(origin, shape)])
+    where = mc.inside_slices(shape, origin, bounds)
 
     def nb(ax, sg):
         sl = list(where)
-        sl[ax] = slice(1 + sg, shape[ax] - 1 + sg)
+        sl[ax] = slice(where[ax].start + sg, where[ax].stop + sg)
         return u[tuple(sl)]
-    m = [(dt(1.0 + C_ADV[d]) * nb(d, -1)).astype(dt) for d in range(3)]
-    s = (m[0] + m[1]).astype(dt)
-    s = (s + m[2]).astype(dt)
-    for d in range(3):
+    m = [(dt(1.0 + C_ADV[d]) * nb(d, -1)).astype(dt) for d in range(rank)]
+    s = m[0]
+    for d in range(1, rank):
+        s = (s + m[d]).astype(dt)
+    for d in range(rank):
         s = (s + nb(d, 1)).astype(dt)
     out = u.copy()
-    out[where] = ((dt(6.0 + sum(C_ADV) + SIGMA) * u[where]).astype(dt) - s).astype(dt)
+    out[where] = ((dt(centre_weight(rank)) * u[where]).astype(dt) - s).astype(dt)
     return out
 
 
@@ -222,14 +240,19 @@ def expected_stop(seq, check_every, max_iters, tol2):
 
 
 class Problem:
-    """one test problem, built once and left unchanged: shape, dtype, module text, the oracle's operator, Omega, b, x0"""
+    """one test problem, built once and left unchanged: shape, dtype, module text, the oracle's operator, Omega, b, x0.
+    origin: the logical lower corner of the fields' box (default 0); bounds: logical (default one cell in from every face);
+    `where` is Omega in physical indices."""
 
-    def __init__(self, shape, dtype, rim=False):
+    def __init__(self, shape, dtype, rim=False, origin=None, bounds=None):
         self.shape, self.dtype = tuple(shape), dtype
-        self.text = bicg_module(shape, dtype)
+        self.origin = tuple([0] * len(shape) if origin is None else [int(o) for o in origin])
+        if bounds is None:
+            bounds = ([o + 1 for o in self.origin], [o + n - 1 for o, n in zip(self.origin, shape)])
+        self.text = bicg_module(shape, dtype, origin, bounds)
         self.A = Operator(self.text)
-        self.bounds = cc.interior(shape)
-        self.where = tuple(slice(1, n - 1) for n in shape)
+        self.bounds = bounds
+        self.where = mc.inside_slices(shape, self.origin, bounds)
         self.b = helpers.hash_field(shape, dtype, seed=71)
         self.x0 = helpers.hash_field(shape, dtype, seed=72) if rim else np.zeros(shape, dtype)
         for a in (self.b, self.x0):

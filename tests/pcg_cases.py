@@ -21,10 +21,13 @@ import monitor_cases as mc
 W_VALUES = (0.0, 16.0, 256.0, 4096.0)
 
 
-def pcg_module(shape, dtype=np.float64):
+def pcg_module(shape, dtype=np.float64, origin=None, bounds=None):
     """NeptuneIR text of @entry(out, in, in1): out = A(in) with w = in1 as described above (monitor_cases.star_module's
-    frame: box [0, shape), bounds one cell in from every face)"""
+    frame: box [origin, origin + shape), origin 0 by default; `bounds` logical, by default one cell in from every face)"""
     rank = len(shape)
+    origin = [0] * rank if origin is None else [int(x) for x in origin]
+    if bounds is None:
+        bounds = ([o + 1 for o in origin], [o + n - 1 for o, n in zip(origin, shape)])
     elem = mc.ELEM[np.dtype(dtype)]
     lst = lambda v: ", ".join(str(int(x)) for x in v)
     mr = "x".join(["?"] * rank) + "x" + elem
@@ -48,8 +51,8 @@ def pcg_module(shape, dtype=np.float64):
             f"        %t1 = arith.mulf %ws, %{prev} : {elem}", f"        %t2 = arith.addf %t0, %t1 : {elem}",
             f"        neptune_ir.yield %t2 : {elem}"]
     out = ['#loc = #neptune_ir.location<"cell">',
-           f"#b   = #neptune_ir.bounds<lb = [{lst(zero)}], ub = [{lst(shape)}]>",
-           f"#bi  = #neptune_ir.bounds<lb = [{lst([1] * rank)}], ub = [{lst([n - 1 for n in shape])}]>",
+           f"#b   = #neptune_ir.bounds<lb = [{lst(origin)}], ub = [{lst([o + n for o, n in zip(origin, shape)])}]>",
+           f"#bi  = #neptune_ir.bounds<lb = [{lst(bounds[0])}], ub = [{lst(bounds[1])}]>",
            f"!temp  = !neptune_ir.temp<element = {elem}, bounds = #b, location = #loc>",
            f"!field = !neptune_ir.field<element = {elem}, bounds = #b, location = #loc>",
            "module {",
@@ -76,7 +79,7 @@ def w_field(shape, dtype=np.float64, seed=73, values=W_VALUES):
 
 
 def diagonal(w: np.ndarray, where):
-    """the exact diagonal of A on Omega, +0 elsewhere"""
+    """the exact diagonal of A on Omega (any part of apply.bounds), +0 elsewhere"""
     d = np.zeros_like(w)
     d[where] = (w.dtype.type(4 * w.ndim) + w[where]).astype(w.dtype)
     return d
@@ -195,15 +198,19 @@ def replay(A, x0, b, minv, where, rz0, trace):
 
 class Problem:
     """one test problem, built once and left unchanged: shape, dtype, module text, w, the oracle's operator, Omega, b, x0,
-    the exact diagonal and the Jacobi minv"""
+    the exact diagonal and the Jacobi minv.  origin: the logical lower corner of the fields' box (default 0); bounds: logical
+    (default one cell in from every face); `where` is Omega in physical indices."""
 
-    def __init__(self, shape, dtype, rim=False, w_values=W_VALUES):
+    def __init__(self, shape, dtype, rim=False, w_values=W_VALUES, origin=None, bounds=None):
         self.shape, self.dtype = tuple(shape), dtype
-        self.text = pcg_module(shape, dtype)
+        self.origin = tuple([0] * len(shape) if origin is None else [int(o) for o in origin])
+        if bounds is None:
+            bounds = ([o + 1 for o in self.origin], [o + n - 1 for o, n in zip(self.origin, shape)])
+        self.text = pcg_module(shape, dtype, origin, bounds)
         self.w = w_field(shape, dtype, values=w_values)
         self.A = Operator(self.text, self.w)
-        self.bounds = cc.interior(shape)
-        self.where = tuple(slice(1, n - 1) for n in shape)
+        self.bounds = bounds
+        self.where = mc.inside_slices(shape, self.origin, bounds)
         self.b = helpers.hash_field(shape, dtype, seed=71)
         self.x0 = helpers.hash_field(shape, dtype, seed=72) if rim else np.zeros(shape, dtype)
         self.diag = diagonal(self.w, self.where)
