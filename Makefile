@@ -25,7 +25,7 @@ HIPFLAGS += -DNEPTUNE_HIP_BUILD_ID=\"$(BUILD_ID)\"
 all: rt lowering oracle
 
 # translation units: the runtime proper, one per built-in body (minutes each: every tile of the library -- built side
-# by side under make -j), and the host-only slab / wisdom / step-loop code (seconds each)
+# by side under make -j), and the host-only slab / wisdom / step-loop / multigrid code (seconds each)
 rt: $(LIBDIR)/libneptune_hip.so
 build/obj/neptune_hip_rt.o: $(CSRC)/runtime/neptune_hip_rt.hip $(KERNEL_HDRS)
 	@mkdir -p build/obj
@@ -42,8 +42,11 @@ build/obj/wisdom.o: $(CSRC)/runtime/wisdom.hip include/neptune_hip.h
 build/obj/step_loop.o: $(CSRC)/runtime/step_loop.hip $(KERNEL_HDRS)
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+build/obj/multigrid.o: $(CSRC)/runtime/multigrid.hip $(KERNEL_HDRS)
+	@mkdir -p build/obj
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 RT_BODIES := lap2d5 lap3d7 lap3d27 lap1d3
-$(LIBDIR)/libneptune_hip.so: build/obj/neptune_hip_rt.o $(RT_BODIES:%=build/obj/rt_body_%.o) build/obj/slab_rccl.o build/obj/wisdom.o build/obj/step_loop.o
+$(LIBDIR)/libneptune_hip.so: build/obj/neptune_hip_rt.o $(RT_BODIES:%=build/obj/rt_body_%.o) build/obj/slab_rccl.o build/obj/wisdom.o build/obj/step_loop.o build/obj/multigrid.o
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared $^ -ldl -o $@
 

@@ -505,6 +505,73 @@ int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn
                                void *trace, void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done,
                                double *rr0, double *rr_last);
 
+/* Device-resident geometric multigrid: V-cycles over a hierarchy of applies.
+ * ARITHMETIC.  Everything in the element type T (NEPTUNE_HIP_F64 / _F32), one rounding per operation, no FMA, every
+ * intermediate a named temporary.  No reduction enters a field: the fields of a run are fully determined, bit for bit.
+ * LEVELS.  L >= 1 levels, level 0 the finest.  Level l has a geometry g_l (rank 1..3, one rank for all levels, input 0's
+ * box = the result's box), an operator A_l (fn, or fn = NULL: built-in body `body`, whose element type must be the call's)
+ * with fixed inputs in_rest (in_rest[i] = input i + 1), and the fields x_l, b_l, q_l, minv_l in that box.  Omega_l =
+ * apply.bounds x launch region of g_l as a physical [lo, hi) per dimension, m_l[d] = hi - lo >= 1.  The grids are
+ * vertex-centred with a Dirichlet rim: every dimension must satisfy m_l[d] = 2 m_(l+1)[d] + 1, and the coarse cell with
+ * interior index j (counted from Omega's lower corner) coincides with the fine cell of interior index 2 j + 1.
+ * SMOOTHING SWEEP on level l (damped Jacobi; the caller folds omega / diagonal into minv):  q = A_l(x) as a plain launch of
+ * g_l, then on Omega_l only  d = b - q,  w = minv * d,  x = x + w.  Cells of x outside Omega_l are not written; minv outside
+ * Omega_l is never read.
+ * RESTRICTION l -> l+1, fused with the residual (r is never a field):  d<f> = b_l<f> - q_l<f> (q_l = A_l(x_l) from a plain
+ * launch just before), then the one-dimensional stencil  t = ((0.25 a-) + (0.5 a0)) + (0.25 a+)  centred on fine interior
+ * index 2 j + 1, along dimension rank-1 (the contiguous one) first, then rank-2, then rank-3; then
+ * b_(l+1)<c> = rscale_l * t  and  x_(l+1)<c> = +0  for every c in Omega_(l+1).  Cells outside Omega_(l+1) are not written,
+ * and no fine cell outside Omega_l is read.
+ * PROLONGATION AND CORRECTION l+1 -> l.  Along one axis a fine cell of interior index i takes  e[(i - 1) / 2]  for odd i and
+ * 0.5 * (e[i / 2 - 1] + e[i / 2])  for even i (one rounded addition, then the exact scaling), with e[-1] = e[m_(l+1)] = +0
+ * whatever the coarse field holds outside Omega_(l+1).  The tensor product runs along dimension rank-1 first, then rank-2,
+ * then rank-3; then  x_l = x_l + e  on Omega_l.  Cells outside keep their bits.
+ * CYCLE(l).  On level L-1: coarse_sweeps smoothing sweeps.  On any other level: `pre` sweeps;  q = A(x) and the
+ * restriction;  Cycle(l+1);  prolongation and correction;  `post` sweeps.
+ * The three kernels alone (asynchronous on `stream`; NEPTUNE_HIP_EINVAL, nothing launched: a null pointer, an unknown
+ * dtype, a malformed geometry, an empty Omega, ranks that differ, the size relation violated, a non-finite rscale, a
+ * written field overlapping a field the same launch reads): */
+int neptune_hip_mg_smooth(int dtype, const neptune_hip_apply_geom_t *g, const void *q, const void *b, const void *minv,
+                          void *x, void *stream);
+int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
+                            const void *b_fine, const void *q_fine, double rscale, void *b_coarse, void *x_coarse,
+                            void *stream);
+int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
+                               const void *x_coarse, void *x_fine, void *stream);
+/* One level of a hierarchy.  Level 0's x and b are the caller's problem: initial guess in, solution out, and the
+ * right-hand side; the cells of x_0 outside Omega_0 are Dirichlet data that enter through A(x) only.  x_l, b_l of the
+ * coarser levels and every q_l are work fields: what they hold on entry does not matter. */
+typedef struct {
+  neptune_hip_apply_fn fn; int body;          /* fn = NULL: built-in body */
+  neptune_hip_apply_geom_t g;
+  const void *const *in_rest;                 /* inputs 1.., NULL when none */
+  const void *minv;  void *x, *b, *q;         /* level 0: x and b are the caller's */
+  double rscale;                              /* applied by the restriction that LEAVES this level; unused on the last */
+} neptune_hip_mg_level_t;
+/* SOLVE.  x_l for l >= 1 is zero-filled once, whole box.  rr_0 = sum over Omega_0 of (b - A(x))^2: a plain launch into q_0,
+ * then neptune_hip_update_norm.  rr_0 <= tol2 returns with zero cycles.  Otherwise blocks of check_every cycles (the last
+ * one shortened: max_cycles is never exceeded); after each block the same rr, one stream synchronise and one scalar read;
+ * the loop stops on rr <= tol2 (the threshold on rr itself; a NaN never stops it).  Every rr read after a block is also
+ * stored into rr_checks, a HOST array of ceil(max_cycles / check_every) doubles, or NULL.  *cycles_done, *rr0, *rr_last
+ * (each may be NULL): cycles run, rr_0, the last rr read.  cfg: the launch configuration of level 0's operator; the
+ * coarser levels launch with the defaults.
+ * REPLAY.  The first cycle of a call runs as plain launches.  When at least two more cycles may follow, one cycle is
+ * captured once on the call's stream -- a linear graph, no parallel branches -- and every further cycle is one
+ * hipGraphLaunch of it; the graph is destroyed when the call returns.  A launch that refuses under capture ends the capture,
+ * the graph is discarded and the call goes on with plain launches: not an error.  Environment NEPTUNE_HIP_MG_GRAPH=0
+ * (read at every call) disables the graph path.
+ * NEPTUNE_HIP_EINVAL, nothing launched: n_levels < 1 or > 16, a rank that differs between levels, the size relation
+ * violated in any dimension, an empty Omega, a null field, a missing fixed input, any two of a level's x, b, q, minv
+ * overlapping, a level's fields overlapping those of a neighbouring level, input 0's box differing from the result's,
+ * negative pre, post or coarse_sweeps, check_every < 1, max_cycles < 0, a stream that is being captured, a non-finite
+ * rscale on a level that has a coarser one, an unknown dtype, a built-in body of another element type. */
+int neptune_hip_mg_solve(const neptune_hip_mg_level_t *levels, int n_levels, int dtype, int pre, int post, int coarse_sweeps,
+                         int64_t max_cycles, int64_t check_every, double tol2, double *rr_checks, void *stream,
+                         const neptune_hip_launch_cfg_t *cfg, int64_t *cycles_done, double *rr0, double *rr_last);
+/* the last neptune_hip_mg_solve call of this process: cycles that ran as plain launches, cycles that ran as graph launches,
+ * and read-backs after blocks (the read of rr_0 is not counted) */
+void neptune_hip_mg_counts(int64_t *plain_cycles, int64_t *graph_cycles, int64_t *checks);
+
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t *g,

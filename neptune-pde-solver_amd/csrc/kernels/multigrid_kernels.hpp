@@ -1,0 +1,178 @@
+// multigrid_kernels.hpp -- the three kernels of the geometric multigrid V-cycle (neptune_hip_mg_solve):
+//
+//   neptune_mg_smooth        x = x + (minv * (b - q)) on Omega                       reads q, b, minv, x; writes x: 5 passes
+//   neptune_mg_restrict      b_c = rscale * R(b_f - q_f), x_c = +0 on the coarse Omega   reads b_f, q_f once; writes 2 / 2^rank
+//   neptune_mg_prolong_add   x_f = x_f + P(x_c) on the fine Omega                     reads and writes x_f; reads x_c through L1
+//
+// Grids: vertex-centred, Dirichlet rim, m_fine = 2 m_coarse + 1 per dimension; the coarse cell of interior index j sits on the
+// fine cell of interior index 2 j + 1 (interior indices count from Omega's lower corner).
+//
+// The frame, stated once.  Addressing is the rows form of krylov_kernels.hpp's box_cell, over Omega instead of the box: a
+// workgroup owns ONE 256-cell chunk of one row of (the fine or the coarse) Omega, so the row decode is workgroup-uniform
+// scalar work and only Omega's cells are ever addressed -- nothing outside is read or written.  Axes: every level's box is
+// held on three axes with the field's dimensions RIGHT-aligned (rank 2: axes 1, 2; rank 1: axis 2), absent axes have extent
+// 1 and no transfer stencil: axis a carries one iff a >= 3 - RANK.  Axis 2 is the contiguous one.
+// Arithmetic: everything in T, every intermediate a named temporary, one rounding per operation (build with
+// -ffp-contract=off).  The transfer stencils run along axis 2 first, then axis 1, then axis 0.  No atomics, no reductions.
+// Templates only: the translation unit that holds the solver instantiates them.
+#pragma once
+#include "apply_common.hpp"
+
+namespace neptune_hip {
+
+// one level's box and Omega on the three axes
+struct MgBox {
+  int64_t n[3];    // the box's extents
+  int64_t lo[3];   // Omega's lower corner, physical
+  int64_t m[3];    // Omega's extents (>= 1)
+};
+
+// The row decode all three kernels share: workgroup `blk` owns chunk c of row (i, j) of B's Omega; -> false past the last
+// workgroup of a folded grid (workgroup-uniform).  k = the lane's interior index along axis 2 (may be >= m[2]: no cell).
+__device__ __forceinline__ bool mg_row(const MgBox& B, int64_t nchunk, int64_t blk, int64_t& i, int64_t& j, int64_t& k0) {
+  if (blk >= B.m[0] * B.m[1] * nchunk) return false;
+  const int64_t row = blk / nchunk, c = blk - row * nchunk;
+  i = row / B.m[1];
+  j = row - i * B.m[1];
+  k0 = c * 256;
+  return true;
+}
+// flat index of the cell with interior indices (i, j, k)
+__device__ __forceinline__ int64_t mg_at(const MgBox& B, int64_t i, int64_t j, int64_t k) {
+  return ((B.lo[0] + i) * B.n[1] + (B.lo[1] + j)) * B.n[2] + (B.lo[2] + k);
+}
+
+// ---------------------------------------------------------------- smoothing sweep
+// On Omega: d = b - q, w = minv * d, x = x + w.  q = A(x) comes from the plain launch just before.
+template <class T>
+__global__ __launch_bounds__(256) void neptune_mg_smooth(MgBox B, int64_t nchunk, const T* __restrict__ q, const T* __restrict__ b,
+                                                         const T* __restrict__ minv, T* __restrict__ x) {
+  int64_t i, j, k0;
+  if (!mg_row(B, nchunk, linear_block(), i, j, k0)) return;
+  const int64_t k = k0 + threadIdx.x;
+  if (k >= B.m[2]) return;
+  const int64_t o = mg_at(B, i, j, k);
+  const T d = b[o] - q[o];
+  const T w = minv[o] * d;
+  x[o] = x[o] + w;
+}
+
+// ---------------------------------------------------------------- restriction, fused with the residual
+// the one-dimensional full-weighting stencil: two exact products, two rounded additions
+template <class T>
+__device__ __forceinline__ T mg_weigh(T am, T a0, T ap) {
+  const T qm = (T)0.25 * am;
+  const T h0 = (T)0.5 * a0;
+  const T qp = (T)0.25 * ap;
+  const T s = qm + h0;
+  return s + qp;
+}
+
+// The workgroup owns coarse cells (ci, cj, ck0 .. ck0 + 255).  It needs d = b - q on the fine rows (2 ci + {0, 1, 2},
+// 2 cj + {0, 1, 2}) at fine interior indices 2 ck0 .. 2 ck0 + 512 along axis 2: each such row segment is loaded ONCE by the
+// workgroup, coalesced, differenced and staged in LDS (the rows of one fine plane side by side), from where every lane takes
+// its three operands.  Rows and planes that neighbouring workgroups share (even fine indices) come out of L2.  Per fine plane
+// the stencil runs along axis 2, then axis 1, in registers; the three planes are combined last.
+constexpr int kMgRestrictRow = 2 * 256 + 1;   // fine cells of one staged row segment
+constexpr int kMgRestrictPitch = kMgRestrictRow + 3;
+template <class T, int RANK>
+__global__ __launch_bounds__(256) void neptune_mg_restrict(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ b_f,
+                                                           const T* __restrict__ q_f, T rscale, T* __restrict__ b_c,
+                                                           T* __restrict__ x_c) {
+  constexpr int NI = RANK >= 3 ? 3 : 1, NJ = RANK >= 2 ? 3 : 1;
+  __shared__ T lds[NJ * kMgRestrictPitch];
+  int64_t ci, cj, ck0;
+  if (!mg_row(Cb, nchunk, linear_block(), ci, cj, ck0)) return;
+  const int64_t ck = ck0 + threadIdx.x;
+  const bool owns = ck < Cb.m[2];
+  // the staged segment: fine interior indices [fk0, fk0 + len) along axis 2; the size relation keeps it inside Omega
+  const int64_t fk0 = 2 * ck0;
+  const int64_t rest = F.m[2] - fk0;
+  const int len = (int)(rest < (int64_t)kMgRestrictRow ? rest : (int64_t)kMgRestrictRow);
+  const int64_t fi0 = RANK >= 3 ? 2 * ci : ci, fj0 = RANK >= 2 ? 2 * cj : cj;
+  T plane[NI];
+#pragma unroll
+  for (int a = 0; a < NI; ++a) {
+    if (a > 0) __syncthreads();   // the previous plane's operands are in registers before its rows are overwritten
+#pragma unroll
+    for (int r = 0; r < NJ; ++r) {
+      const int64_t o = mg_at(F, fi0 + a, fj0 + r, fk0);
+      for (int t = threadIdx.x; t < len; t += 256) {
+        const T d = b_f[o + t] - q_f[o + t];
+        lds[r * kMgRestrictPitch + t] = d;
+      }
+    }
+    __syncthreads();
+    T row[NJ];
+#pragma unroll
+    for (int r = 0; r < NJ; ++r) {
+      row[r] = (T)0;
+      if (owns) {
+        const T* s = lds + r * kMgRestrictPitch + 2 * (int)threadIdx.x;
+        row[r] = mg_weigh(s[0], s[1], s[2]);
+      }
+    }
+    if constexpr (NJ == 3) plane[a] = mg_weigh(row[0], row[1], row[2]);
+    else plane[a] = row[0];
+  }
+  if (!owns) return;
+  T t;
+  if constexpr (NI == 3) t = mg_weigh(plane[0], plane[1], plane[2]);
+  else t = plane[0];
+  const int64_t oc = mg_at(Cb, ci, cj, ck);
+  b_c[oc] = rscale * t;
+  x_c[oc] = (T)0;
+}
+
+// ---------------------------------------------------------------- prolongation and correction
+// one-dimensional interpolation at a fine cell: odd interior index -> the coarse value `hi` itself; even -> 0.5 * (lo + hi),
+// one rounded addition and the exact scaling.  (lo, hi) = e[i / 2 - 1], e[i / 2] for even i, and hi = e[(i - 1) / 2] for odd i;
+// an operand on the rim is +0.
+template <class T>
+__device__ __forceinline__ T mg_interp(bool odd, T lo, T hi) {
+  const T s = lo + hi;
+  const T h = (T)0.5 * s;
+  return odd ? hi : h;
+}
+
+// The workgroup owns fine cells (fi, fj, fk0 .. fk0 + 255).  Along axes 0 and 1 the parity is workgroup-uniform: an odd index
+// needs one coarse row / plane, an even one two, of which one may be the rim.  The coarse operands -- up to 2^RANK per cell,
+// consecutive lanes on consecutive or equal coarse cells of the same few rows -- are read through L1: the coarse field is
+// 1 / 2^RANK of the fine one.
+template <class T, int RANK>
+__global__ __launch_bounds__(256) void neptune_mg_prolong_add(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ x_c,
+                                                              T* __restrict__ x_f) {
+  constexpr int NI = RANK >= 3 ? 2 : 1, NJ = RANK >= 2 ? 2 : 1;
+  int64_t fi, fj, fk0;
+  if (!mg_row(F, nchunk, linear_block(), fi, fj, fk0)) return;
+  const int64_t fk = fk0 + threadIdx.x;
+  if (fk >= F.m[2]) return;
+  // per axis: the two coarse interior indices (lo, hi) and the parity; an absent axis takes its only index as `hi`
+  const bool oi = RANK >= 3 ? (fi & 1) != 0 : true, oj = RANK >= 2 ? (fj & 1) != 0 : true, ok = (fk & 1) != 0;
+  const int64_t ci[2] = {RANK >= 3 ? fi / 2 - 1 : -1, RANK >= 3 ? (oi ? (fi - 1) / 2 : fi / 2) : fi};
+  const int64_t cj[2] = {RANK >= 2 ? fj / 2 - 1 : -1, RANK >= 2 ? (oj ? (fj - 1) / 2 : fj / 2) : fj};
+  const int64_t ck[2] = {fk / 2 - 1, ok ? (fk - 1) / 2 : fk / 2};
+  // slot 0 (`lo`) is used on an even index only; an index outside [0, m) is the rim
+  const bool vi[2] = {!oi && ci[0] >= 0, ci[1] < Cb.m[0]}, vj[2] = {!oj && cj[0] >= 0, cj[1] < Cb.m[1]};
+  const bool vk[2] = {!ok && ck[0] >= 0, ck[1] < Cb.m[2]};
+  T ei[2] = {(T)0, (T)0};
+#pragma unroll
+  for (int a = 2 - NI; a < 2; ++a) {
+    T ej[2] = {(T)0, (T)0};
+#pragma unroll
+    for (int r = 2 - NJ; r < 2; ++r) {
+      T klo = (T)0, khi = (T)0;
+      if (vi[a] && vj[r]) {
+        if (vk[0]) klo = x_c[mg_at(Cb, ci[a], cj[r], ck[0])];
+        if (vk[1]) khi = x_c[mg_at(Cb, ci[a], cj[r], ck[1])];
+      }
+      ej[r] = mg_interp(ok, klo, khi);
+    }
+    ei[a] = RANK >= 2 ? mg_interp(oj, ej[0], ej[1]) : ej[1];
+  }
+  const T e = RANK >= 3 ? mg_interp(oi, ei[0], ei[1]) : ei[1];
+  const int64_t o = mg_at(F, fi, fj, fk);
+  x_f[o] = x_f[o] + e;
+}
+
+}  // namespace neptune_hip

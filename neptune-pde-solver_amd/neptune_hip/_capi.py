@@ -62,6 +62,12 @@ class LaunchCfg(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("variant", C.c_int32), ("chunk", C.c_int32), ("flags", C.c_int32)]
 
 
+class MgLevel(C.Structure):
+    """neptune_hip_mg_level_t: one level of a multigrid hierarchy"""
+    _fields_ = [("fn", C.c_void_p), ("body", C.c_int), ("g", ApplyGeom), ("in_rest", C.POINTER(C.c_void_p)),
+                ("minv", C.c_void_p), ("x", C.c_void_p), ("b", C.c_void_p), ("q", C.c_void_p), ("rscale", C.c_double)]
+
+
 def _memref(rank: int):
     class _M(C.Structure):
         _fields_ = [("allocated", C.c_void_p), ("aligned", C.c_void_p), ("offset", C.c_int64),
@@ -136,6 +142,12 @@ SIGNATURES = {
     "neptune_hip_bicgstab_solve": (_i, [_vp, _vp, _i, _i, _geom_p, _vp, _vp, _vpp, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_cg_counts": (None, [_i64p, _i64p, _i64p]),
+    "neptune_hip_mg_smooth": (_i, [_i, _geom_p, _vp, _vp, _vp, _vp, _vp]),
+    "neptune_hip_mg_restrict": (_i, [_i, _geom_p, _geom_p, _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "neptune_hip_mg_prolong_add": (_i, [_i, _geom_p, _geom_p, _vp, _vp, _vp]),
+    "neptune_hip_mg_solve": (_i, [C.POINTER(MgLevel), _i, _i, _i, _i, _i, _i64, _i64, _dbl, C.POINTER(C.c_double), _vp, _cfg_p,
+                                  _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mg_counts": (None, [_i64p, _i64p, _i64p]),
     "neptune_hip_kernel_name": (C.c_char_p, [_i]),
     "neptune_hip_apply_builtin_variant": (_i, [_i, _geom_p, _cfg_p]),
     "neptune_hip_march_variant_count": (_i, [_i]),

@@ -1,0 +1,183 @@
+"""Geometric multigrid V-cycles on the device (neptune_hip_mg_solve): a hierarchy of applies -- one operator
+per level shape --, damped-Jacobi smoothing, full-weighting restriction fused with the residual, and trilinear
+prolongation, all in the element type with one rounding per operation.  The normative definition is in
+include/neptune_hip.h; this module builds the C structs and allocates the work fields.
+
+    levels = [multigrid.Level(entry_l, like_l, bounds_l, minv=multigrid.jacobi_weights(entry_l, like_l, bounds_l, omega=6 / 7))
+              for ...]
+    h = multigrid.Hierarchy(levels)
+    cycles, rr0, rr_last, rr_checks = multigrid.solve(h, x, b, max_cycles=20, tol2=1e-16 * rr0)
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+from . import _capi
+from . import apply as _apply
+from .fields import DeviceField, current_stream_ptr
+from .geometry import Box, make_geom
+
+
+def coarsen_bounds(bounds: Box) -> list:
+    """the next level's interior extents for a level whose interior is `bounds` (lb, ub): (m - 1) / 2 per dimension.
+    ValueError when an extent is even (a vertex-centred grid with a Dirichlet rim nests only for odd extents) or below 3."""
+    out = []
+    for d, (l, u) in enumerate(zip(bounds[0], bounds[1])):
+        m = int(u) - int(l)
+        if m < 3 or m % 2 == 0:
+            raise ValueError(f"coarsen_bounds: interior extent {m} of dimension {d} is not an odd number >= 3")
+        out.append((m - 1) // 2)
+    return out
+
+
+def jacobi_weights(entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), omega: float = 1.0, reach=None,
+                   region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None) -> DeviceField:
+    """the damped-Jacobi weights of a linear operator for Level(minv=...): omega / diagonal (one division in the element
+    type) on Omega = bounds x region, +0 elsewhere; the other arguments as apply.operator_diagonal, on which it is built.
+    ValueError when a diagonal entry on Omega is 0 or not finite (as apply.jacobi_minv)."""
+    import torch
+    diag = _apply.operator_diagonal(entry, like, bounds, others, reach, region, cfg)
+    lo, hi = _apply._omega(like, bounds, region)
+    w = DeviceField.empty_like(like)
+    w.tensor.zero_()
+    if any(h <= l for l, h in zip(lo, hi)):
+        return w
+    cells = tuple(slice(l, h) for l, h in zip(lo, hi))
+    d = diag.tensor[cells]
+    bad = int(((d == 0) | ~torch.isfinite(d)).sum().item())
+    if bad:
+        raise ValueError(f"jacobi_weights: {bad} diagonal entries on Omega are 0 or not finite")
+    w.tensor[cells] = torch.full_like(d, float(omega)) / d
+    return w
+
+
+class Level:
+    """one level of a hierarchy: the operator (`entry`: a built-in body id or a lowered apply's geometry-level entry whose
+    input 0 has the result's box), a field `like` that gives the level's box and element type, the apply's `bounds`
+    (logical), its fixed inputs 1.. (`others`), the smoother's weights `minv` (a field like `like`: omega / diagonal on
+    Omega, e.g. jacobi_weights; required before a solve), the factor `rscale` of the restriction that leaves this level
+    (4 for an operator that is not scaled by 1 / h^2: the coarse operator is then the fine one's stencil) and the launch
+    `region` (result-physical, default: the whole box)."""
+
+    def __init__(self, entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), minv: Optional[DeviceField] = None,
+                 rscale: float = 4.0, region: Optional[Box] = None):
+        self.entry, self.like, self.others, self.minv, self.rscale, self.region = entry, like, list(others), minv, float(rscale), region
+        self.bounds = ([int(v) for v in bounds[0]], [int(v) for v in bounds[1]])
+        self.geom = make_geom(like.box, self.bounds, [like.box] + [f.box for f in self.others], region)
+        self.lo, self.hi = _apply._omega(like, self.bounds, region)
+        self.m = [h - l for l, h in zip(self.lo, self.hi)]
+        if minv is not None and (minv.box != like.box or minv.dtype != like.dtype):
+            raise ValueError("Level: minv must have the box and the element type of `like`")
+
+    @property
+    def omega(self):
+        """numpy / torch index of Omega in the level's fields"""
+        return tuple(slice(l, h) for l, h in zip(self.lo, self.hi))
+
+
+class Hierarchy:
+    """the levels of a solve, finest first.  Checks the size relation m_l = 2 m_(l+1) + 1 (ValueError naming the level and
+    the dimension), one rank and one element type; allocates x_l and b_l for l >= 1 and every q_l."""
+
+    def __init__(self, levels: Sequence[Level]):
+        self.levels = list(levels)
+        if not 1 <= len(self.levels) <= 16:
+            raise ValueError("Hierarchy: 1..16 levels")
+        first = self.levels[0]
+        for l, L in enumerate(self.levels):
+            if L.like.rank != first.like.rank or L.like.dtype != first.like.dtype:
+                raise ValueError(f"Hierarchy: level {l} has another rank or element type than level 0")
+            if any(m < 1 for m in L.m):
+                raise ValueError(f"Hierarchy: level {l} has an empty Omega")
+            if l > 0:
+                for d, (mf, mc) in enumerate(zip(self.levels[l - 1].m, L.m)):
+                    if mf != 2 * mc + 1:
+                        raise ValueError(f"Hierarchy: level {l}, dimension {d}: interior extent {mc} does not nest in level "
+                                         f"{l - 1}'s {mf} (m_fine = 2 m_coarse + 1)")
+        self.dtype, self.rank = first.like.dtype, first.like.rank
+        self.q = [DeviceField.empty_like(L.like) for L in self.levels]
+        self.x = [None] + [DeviceField.empty_like(L.like) for L in self.levels[1:]]
+        self.b = [None] + [DeviceField.empty_like(L.like) for L in self.levels[1:]]
+
+    def __len__(self):
+        return len(self.levels)
+
+    def _structs(self, x: DeviceField, b: DeviceField):
+        """-> (the C array of levels, what must stay alive while it is used)"""
+        n = len(self.levels)
+        arr = (_capi.MgLevel * n)()
+        keep = []
+        for l, L in enumerate(self.levels):
+            if L.minv is None:
+                raise ValueError(f"multigrid: level {l} has no minv (jacobi_weights)")
+            is_entry = hasattr(L.entry, "fn")
+            arr[l].fn = C.cast(L.entry.fn, C.c_void_p) if is_entry else None
+            arr[l].body = -1 if is_entry else int(L.entry)
+            arr[l].g = L.geom
+            if L.others:
+                rest = (C.c_void_p * len(L.others))(*[f.ptr for f in L.others])
+                keep.append(rest)
+                arr[l].in_rest = rest
+            arr[l].minv = L.minv.ptr
+            arr[l].x = (x if l == 0 else self.x[l]).ptr
+            arr[l].b = (b if l == 0 else self.b[l]).ptr
+            arr[l].q = self.q[l].ptr
+            arr[l].rscale = L.rscale
+        return arr, keep
+
+
+def counts():
+    """(cycles that ran as plain launches, cycles that ran as graph launches, read-backs after blocks of cycles) of the last
+    solve call"""
+    plain, graph, checks = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _capi.load().neptune_hip_mg_counts(C.byref(plain), C.byref(graph), C.byref(checks))
+    return plain.value, graph.value, checks.value
+
+
+def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int = 2, coarse_sweeps: int = 8, max_cycles: int = 20,
+          tol2: float = 0.0, check_every: int = 1, cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
+    """solve A_0(x) = b by V(pre, post) cycles over the hierarchy `h` (neptune_hip_mg_solve).  x: initial guess in, solution
+    out; its cells outside Omega_0 are boundary data and are never written.  The loop stops when r . r <= tol2 (checked every
+    `check_every` cycles) or after max_cycles cycles.  cfg: the launch configuration of level 0's operator.
+    Blocking; -> (cycles, rr0, rr_last, rr_checks): rr_checks is the list of r . r values read after each block of cycles.
+    counts() tells how the cycles were launched."""
+    lib = _capi.load()
+    first = h.levels[0].like
+    if x.box != first.box or b.box != first.box or x.dtype != h.dtype or b.dtype != h.dtype:
+        raise ValueError("multigrid.solve: x and b must have the box and the element type of level 0")
+    arr, keep = h._structs(x, b)
+    st = current_stream_ptr() if stream is None else stream
+    n_checks = max(-(-int(max_cycles) // max(int(check_every), 1)), 1)
+    rr = (C.c_double * n_checks)()
+    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    rc = lib.neptune_hip_mg_solve(arr, len(h), h.dtype, pre, post, coarse_sweeps, max_cycles, check_every, tol2, rr, st,
+                                  C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    _capi.check(rc, "neptune_hip_mg_solve")
+    del keep
+    return done.value, rr0.value, last.value, list(rr[:counts()[2]])
+
+
+def smooth(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, stream: Optional[int] = None) -> None:
+    """one smoothing update on `level` from q = A(x): x = x + minv * (b - q) on Omega (neptune_hip_mg_smooth); asynchronous"""
+    if level.minv is None:
+        raise ValueError("multigrid.smooth: the level has no minv")
+    st = current_stream_ptr() if stream is None else stream
+    _capi.check(_capi.load().neptune_hip_mg_smooth(x.dtype, C.byref(level.geom), q.ptr, b.ptr, level.minv.ptr, x.ptr, st),
+                "neptune_hip_mg_smooth")
+
+
+def restrict(fine: Level, coarse: Level, b_fine: DeviceField, q_fine: DeviceField, b_coarse: DeviceField, x_coarse: DeviceField,
+             stream: Optional[int] = None) -> None:
+    """b_coarse = fine.rscale * R(b_fine - q_fine) and x_coarse = +0 on the coarse Omega (neptune_hip_mg_restrict);
+    asynchronous"""
+    st = current_stream_ptr() if stream is None else stream
+    _capi.check(_capi.load().neptune_hip_mg_restrict(b_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom), b_fine.ptr, q_fine.ptr,
+                                                     fine.rscale, b_coarse.ptr, x_coarse.ptr, st), "neptune_hip_mg_restrict")
+
+
+def prolong_add(fine: Level, coarse: Level, x_coarse: DeviceField, x_fine: DeviceField, stream: Optional[int] = None) -> None:
+    """x_fine = x_fine + P(x_coarse) on the fine Omega (neptune_hip_mg_prolong_add); asynchronous"""
+    st = current_stream_ptr() if stream is None else stream
+    _capi.check(_capi.load().neptune_hip_mg_prolong_add(x_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom), x_coarse.ptr,
+                                                        x_fine.ptr, st), "neptune_hip_mg_prolong_add")
