@@ -572,6 +572,69 @@ int neptune_hip_mg_solve(const neptune_hip_mg_level_t *levels, int n_levels, int
  * and read-backs after blocks (the read of rr_0 is not counted) */
 void neptune_hip_mg_counts(int64_t *plain_cycles, int64_t *graph_cycles, int64_t *checks);
 
+/* Multigrid-preconditioned conjugate gradients: CG on level 0 whose preconditioner is one V-cycle.
+ * ARITHMETIC as above and as for neptune_hip_pcg_solve: element type T, one rounding per operation, no FMA, every
+ * intermediate a named temporary, sums on the fixed tree of the monitored launches, no atomics.
+ * THE SMOOTHING SWEEP WITH A SUM, alone:  neptune_hip_mg_smooth_dot is neptune_hip_mg_smooth (the same update of x on Omega,
+ * the same cells read and written) and *dot_out = sum over Omega of b * x_new, one rounding per term from the b and the
+ * freshly stored x of the cell, each lane's accumulator being that one term; one partial per workgroup, added in index order
+ * by one workgroup.  dot_out: a DEVICE pointer to one T; asynchronous.  The refusals of neptune_hip_mg_smooth, and
+ * NEPTUNE_HIP_EINVAL for a null dot_out or one that overlaps a field; NEPTUNE_HIP_EUNSUPPORTED, nothing launched, when
+ * `stream` is being captured and the partials' workspace would have to grow. */
+int neptune_hip_mg_smooth_dot(int dtype, const neptune_hip_apply_geom_t *g, const void *q, const void *b, const void *minv,
+                              void *x, void *dot_out, void *stream);
+/* SOLVE A_0(x) = b.  levels: the hierarchy of neptune_hip_mg_solve, 2 <= n_levels <= 16; level 0's x and b are the caller's
+ * unknown and right-hand side, level 0's q serves both A(p) and the cycle.  work[3] = r, p, z: caller-supplied fields of
+ * level 0's box.  sweeps >= 1 is the pre-sweep AND the post-sweep count of every level but the last, which runs
+ * coarse_sweeps: the preconditioner is then symmetric.  A_0 is taken to be linear in input 0 (A(0) = 0), as CG assumes
+ * anyway.  fn_dot: level 0's dot-monitored entry, or NULL.
+ * THE PRECONDITIONER z = M(r): one V(sweeps, sweeps) cycle as defined above on A_0 z = r from z = 0, level 0's (x, b) replaced
+ * by (z, r), with two differences, both on level 0:
+ *   - its first pre-sweep runs no apply and is not a launch of its own: from z = 0 and A(0) = 0 it is z = minv_0 * r, one
+ *     rounding, formed on EVERY cell of the flat buffer by the kernel that stores the new r.  r is +0 outside Omega_0, and
+ *     minv_0 must be finite on the whole box (jacobi_weights puts +0 there; not checked on the device): z outside Omega_0 is
+ *     then a zero, the zero Dirichlet rim of the error equation.
+ *   - its last post-sweep is neptune_hip_mg_smooth_dot's kernel: it also yields r . z = sum over Omega_0 of r * z_new.
+ * "The rest of M" below is everything after that first pre-sweep.  Levels >= 1 run exactly Cycle(l).
+ *   set-up     x_l for l >= 1 is zero-filled once, whole box; where level 0's launch region is not its whole box, q_0 is
+ *              zero-filled once as well (the flat update reads it everywhere).
+ *              1. q = A(x), a plain launch   2. on Omega: r = b - q, z = minv_0 * r; outside: +0 for both through one select;
+ *              out of that launch rr_0 = sum r * r   3. rr_0 is read back (the set-up's one synchronise): rr_0 <= tol2 or
+ *              max_iters == 0 returns with zero iterations   4. the rest of M, which yields rz_0   5. p = z, a device copy of
+ *              the whole box
+ *   iteration  1. q = A(p) and pq = sum_Omega q * p out of one dot-monitored launch (fn_dot, or
+ *                 neptune_hip_apply_builtin_dot for a built-in body)
+ *              2. alpha = rz / pq;  on all cells x = x + (alpha p), r = r - (alpha q), z = minv_0 * r from the new r; out of
+ *                 that launch rr' = sum r * r
+ *              3. the rest of M, which yields rz'
+ *              4. beta = rz' / rz;  on all cells p = z + (beta p);  rz <- rz', rr <- rr'
+ * An iteration that finds rz == 0 or pq == 0 uses alpha = beta = 0.  The loop stops on rr <= tol2 exactly as
+ * neptune_hip_pcg_solve's: blocks of check_every iterations (the last one shortened), after each block one stream
+ * synchronise and one scalar read; a NaN never stops it.  *iters_done, *rr0, *rr_last (each may be NULL): iterations run,
+ * rr_0, the last rr read.  trace: NULL, or a DEVICE pointer to 3 * max_iters values of T: iteration k stores pq_k,
+ * rz_(k+1), rr_(k+1) at [3 k .. 3 k + 2].  The scalars live in a device block that one-workgroup kernels rotate, so every
+ * launch of an iteration has fixed arguments.
+ * Fallback: when fn_dot is NULL (with level 0's fn set) or the dot-monitored entry answers NEPTUNE_HIP_EUNSUPPORTED
+ * (remembered for the rest of the call), step 1 is a plain launch followed by neptune_hip_dot.
+ * REPLAY as neptune_hip_mg_solve's, per iteration: the first iteration runs as plain launches; when at least two more may
+ * follow, ONE iteration is captured once as a linear graph and every later iteration is one hipGraphLaunch of it; a launch
+ * that refuses under capture ends the capture and the call goes on with plain launches; NEPTUNE_HIP_MG_GRAPH=0 disables
+ * the graph path.  cfg: the launch configuration of level 0's operator.
+ * NEPTUNE_HIP_EINVAL, nothing launched: every refusal of neptune_hip_mg_solve that applies (pre / post read as sweeps,
+ * max_cycles as max_iters), n_levels < 2, sweeps < 1, a null work array, a null or misaligned work[i] or trace, any overlap
+ * among x, b, r, p, z, level 0's q and minv, the trace, and level 1's x, b, q, minv, a stream that is being captured. */
+int neptune_hip_mgcg_solve(const neptune_hip_mg_level_t *levels, int n_levels, int dtype, neptune_hip_apply_dot_fn fn_dot,
+                           int sweeps, int coarse_sweeps, void *const work[3], int64_t max_iters, int64_t check_every,
+                           double tol2, void *trace, void *stream, const neptune_hip_launch_cfg_t *cfg,
+                           int64_t *iters_done, double *rr0, double *rr_last);
+/* rz_0 = r . M(r) after the set-up of the last neptune_hip_mgcg_solve call of this process (0 when it was refused or ran
+ * no iteration): with *rr0 and the trace, every scalar the recurrences used, so that a run can be replayed */
+double neptune_hip_mgcg_rz0(void);
+/* the last neptune_hip_mgcg_solve call of this process: iterations that ran as plain launches, iterations that ran as
+ * graph launches, how many of all these took the fallback of step 1, and read-backs after blocks (the read of rr_0 is not
+ * counted) */
+void neptune_hip_mgcg_counts(int64_t *plain_iters, int64_t *graph_iters, int64_t *fallback_iters, int64_t *checks);
+
 /* Which kernel neptune_hip_apply_builtin would run for (body, g, cfg):
  * NEPTUNE_HIP_KERNEL_DIRECT / _MARCH, or a negative error. */
 int neptune_hip_apply_builtin_plan(int body, const neptune_hip_apply_geom_t *g,

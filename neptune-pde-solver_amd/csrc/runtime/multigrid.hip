@@ -14,6 +14,7 @@
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, geom_validate, buffers_overlap (no apply kernel is instantiated here)
 #include "../kernels/multigrid_kernels.hpp"
+#include "../kernels/mgcg_kernels.hpp"
 
 using namespace neptune_hip;
 
@@ -165,15 +166,67 @@ struct Solve {
   const neptune_hip_launch_cfg_t* cfg;   // level 0's, nullptr unless the caller set anything
   hipStream_t stream;
 
-  // q_l = A_l(x_l), a plain launch
-  int apply(int l) const {
+  // The arguments every solve over a hierarchy shares, checked before anything touches the device, and the solve's fields
+  // filled in from them (all but `stream`); -> false: refuse
+  bool check(const neptune_hip_mg_level_t* levels_, int n_levels_, int dtype_, int pre_, int post_, int coarse_sweeps_,
+             const neptune_hip_launch_cfg_t* cfg_) {
+    if (!levels_ || n_levels_ < 1 || n_levels_ > kMaxLevels || !known_dtype(dtype_)) return false;
+    if (pre_ < 0 || post_ < 0 || coarse_sweeps_ < 0) return false;
+    levels = levels_;
+    n_levels = n_levels_;
+    dtype = dtype_;
+    pre = pre_;
+    post = post_;
+    coarse_sweeps = coarse_sweeps_;
+    cfg = (cfg_ && (cfg_->kernel || cfg_->variant >= 0 || cfg_->chunk || cfg_->flags)) ? cfg_ : nullptr;
+    rank = levels[0].g.rank;
+    const size_t elem = elem_size(dtype);
+    for (int l = 0; l < n_levels; ++l) {
+      const neptune_hip_mg_level_t& L = levels[l];
+      if (!L.x || !L.b || !L.q || !L.minv) return false;
+      if (!level_box(&L.g, box[l]) || L.g.rank != rank) return false;
+      if (!L.fn) {
+        if (L.body < 0 || L.body >= NEPTUNE_HIP_BODY_COUNT) return false;
+        if ((L.body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64) != dtype) return false;
+      }
+      if (L.g.num_inputs > 1 && !L.in_rest) return false;
+      for (int i = 1; i < L.g.num_inputs; ++i)
+        if (!L.in_rest[i - 1]) return false;
+      if (l + 1 < n_levels && !isfinite(L.rscale)) return false;
+      if (l > 0 && !sizes_nest(box[l - 1], box[l], rank)) return false;
+      const void* mine[4] = {L.x, L.b, L.q, L.minv};
+      const size_t bytes = box_bytes(box[l], elem);
+      for (int a = 0; a < 4; ++a) {
+        if ((uintptr_t)mine[a] % elem != 0) return false;
+        for (int o = 0; o < a; ++o)
+          if (buffers_overlap(mine[a], bytes, mine[o], bytes)) return false;
+        if (l > 0) {
+          const neptune_hip_mg_level_t& P = levels[l - 1];
+          const void* finer[4] = {P.x, P.b, P.q, P.minv};
+          const size_t finer_bytes = box_bytes(box[l - 1], elem);
+          for (int o = 0; o < 4; ++o)
+            if (buffers_overlap(mine[a], bytes, finer[o], finer_bytes)) return false;
+        }
+      }
+    }
+    return true;
+  }
+  // level l's inputs with `in0` as input 0
+  void inputs(int l, const void* in0, const void** ins) const {
+    const neptune_hip_mg_level_t& L = levels[l];
+    ins[0] = in0;
+    for (int i = 1; i < L.g.num_inputs; ++i) ins[i] = L.in_rest[i - 1];
+  }
+  // q_l = A_l(in0), a plain launch
+  int apply_of(int l, const void* in0) const {
     const neptune_hip_mg_level_t& L = levels[l];
     const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    ins[0] = L.x;
-    for (int i = 1; i < L.g.num_inputs; ++i) ins[i] = L.in_rest[i - 1];
+    inputs(l, in0, ins);
     const neptune_hip_launch_cfg_t* c = l == 0 ? cfg : nullptr;
     return L.fn ? L.fn(&L.g, ins, L.q, (void*)stream, c) : neptune_hip_apply_builtin(L.body, &L.g, ins, L.q, (void*)stream, c);
   }
+  // q_l = A_l(x_l)
+  int apply(int l) const { return apply_of(l, levels[l].x); }
   int sweeps(int l, int count) const {
     const neptune_hip_mg_level_t& L = levels[l];
     for (int s = 0; s < count; ++s) {
@@ -245,6 +298,223 @@ bool graph_path_enabled() {
   return !(e && strcmp(e, "0") == 0);
 }
 
+// ---------------------------------------------------------------- multigrid-preconditioned conjugate gradients
+// The device block of neptune_hip_mgcg_solve and neptune_hip_mg_smooth_dot: PcgScalars, then rz_0, then the partials of the
+// solver's own kernels; grown on demand, never while a capture is under way.
+void* g_mgcg_ws = nullptr;
+size_t g_mgcg_ws_bytes = 0;
+int64_t g_mgcg_counts[4] = {0, 0, 0, 0};   // plain / graph / fallback iterations, checks of the last mgcg_solve
+double g_mgcg_rz0 = 0.0;                   // r . M(r) after the set-up of the last mgcg_solve
+constexpr size_t kMgcgRz0Offset = 64;      // room for PcgScalars<double> (56 bytes)
+constexpr size_t kMgcgScalarBytes = 80;    // then rz_0; keeps the partials 16-byte aligned
+static_assert(sizeof(PcgScalars<double>) <= kMgcgRz0Offset && kMgcgScalarBytes % 16 == 0, "the scalar block");
+
+bool grow_mgcg_ws(size_t bytes, void* stream) {
+  if (bytes <= g_mgcg_ws_bytes) return true;
+  if (stream_capturing(stream)) return false;
+  if (g_mgcg_ws) NEPTUNE_HIP_CHECK(hipFree(g_mgcg_ws));   // waits for every launch that may still use the old block
+  g_mgcg_ws = nullptr;
+  g_mgcg_ws_bytes = 0;
+  NEPTUNE_HIP_CHECK(hipMalloc(&g_mgcg_ws, bytes));
+  g_mgcg_ws_bytes = bytes;
+  return true;
+}
+
+int64_t grid_blocks(const dim3& g) { return (int64_t)g.x * g.y; }
+
+bool region_is_whole(const neptune_hip_apply_geom_t* g) {
+  bool whole = true;
+  for (int d = 0; d < g->rank; ++d) whole = whole && g->region_lb[d] <= 0 && g->region_ub[d] >= g->out_ub[d] - g->out_lb[d];
+  return whole;
+}
+
+// what neptune_hip_mgcg_solve is once its arguments are checked.  S: the solve over the hierarchy whose level 0 carries
+// (z, r) for (x, b) -- the cycle of the preconditioner --, L0: the caller's level 0.
+struct MgcgArgs {
+  neptune_hip_apply_dot_fn fn_dot;
+  int sweeps;
+  void* const* work;
+  int64_t max_iters, check_every;
+  double tol2;
+  void* trace;
+  int64_t* iters_done;
+  double* rr0;
+  double* rr_last;
+};
+template <class T>
+int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const MgcgArgs& a) {
+  const hipStream_t stream = S.stream;
+  const MgBox& B0 = S.box[0];
+  const int64_t n = B0.n[0] * B0.n[1] * B0.n[2];
+  T* const x = static_cast<T*>(L0.x);
+  const T* const b = static_cast<const T*>(L0.b);
+  T* const q = static_cast<T*>(L0.q);
+  const T* const minv = static_cast<const T*>(L0.minv);
+  T* const r = static_cast<T*>(a.work[0]);
+  T* const p = static_cast<T*>(a.work[1]);
+  T* const z = static_cast<T*>(a.work[2]);
+  T* const tr = static_cast<T*>(a.trace);
+
+  CgBoxParams P;
+  for (int d = 0; d < 3; ++d) {
+    P.n[d] = B0.n[d];
+    P.lo[d] = B0.lo[d];
+    P.hi[d] = B0.lo[d] + B0.m[d];
+  }
+  const int64_t init_chunk = (P.n[2] + 255) / 256;
+  const dim3 init_grid = grid_for_blocks(P.n[0] * P.n[1] * init_chunk);
+  const FlatGrid upd = flat_grid(n, sizeof(T), {p, q, minv, x, r, z}), dir = flat_grid(n, sizeof(T), {z, p});
+  const RowGrid sd = row_grid(B0);
+  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, grid_blocks(sd.grid)});
+  grow_mgcg_ws(kMgcgScalarBytes + (size_t)most * sizeof(T), (void*)stream);   // no capture is under way: the entry refused one
+  PcgScalars<T>* const scal = static_cast<PcgScalars<T>*>(g_mgcg_ws);
+  T* const rz0_dev = reinterpret_cast<T*>(static_cast<char*>(g_mgcg_ws) + kMgcgRz0Offset);
+  T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes);
+  auto final_kernel = [&](int64_t count, int stage) {
+    hipLaunchKernelGGL(neptune_mgcg_final<T>, dim3(1), dim3(256), 0, stream, (const T*)partials, count, scal, rz0_dev, tr, a.max_iters, stage);
+  };
+  // `count` device scalars from `dev` after everything queued on the stream: the one synchronise of a block
+  auto read = [&](const T* dev, double* host, const T* dev2 = nullptr, double* host2 = nullptr) {
+    T h = 0, h2 = 0;
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, dev, sizeof(T), hipMemcpyDeviceToHost, stream));
+    if (dev2) NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h2, dev2, sizeof(T), hipMemcpyDeviceToHost, stream));
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(stream));
+    *host = (double)h;
+    if (dev2) *host2 = (double)h2;
+  };
+  // the rest of M: everything of the cycle on A z = r after its first pre-sweep (z = minv r, stored with r); its last
+  // post-sweep yields r . z, which `stage` of the bookkeeping kernel takes
+  auto rest_of_cycle = [&](int stage) -> int {
+    const neptune_hip_mg_level_t& F = S.levels[0];
+    const neptune_hip_mg_level_t& Cl = S.levels[1];
+    int rc = S.sweeps(0, a.sweeps - 1);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.apply(0);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = do_restrict(S.dtype, S.rank, S.box[0], S.box[1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.cycle(1);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = do_prolong(S.dtype, S.rank, S.box[0], S.box[1], Cl.x, F.x, stream);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.sweeps(0, a.sweeps - 1);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.apply(0);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    hipLaunchKernelGGL(neptune_mg_smooth_dot<T>, sd.grid, dim3(256), 0, stream, B0, sd.nchunk, (const T*)q, (const T*)r, minv, z, partials);
+    final_kernel(grid_blocks(sd.grid), stage);
+    return launched();
+  };
+
+  // ---- set-up
+  for (int l = 1; l < S.n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(S.levels[l].x, 0, box_bytes(S.box[l], sizeof(T)), stream));
+  if (!region_is_whole(&L0.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), stream));
+  int rc = S.apply_of(0, x);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  hipLaunchKernelGGL(neptune_mgcg_init<T>, init_grid, dim3(256), 0, stream, P, init_chunk, b, (const T*)q, minv, r, z, partials);
+  final_kernel(grid_blocks(init_grid), kMgcgStartRr);
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  double rr = 0.0;
+  read(&scal->rr, &rr);
+  if (a.rr0) *a.rr0 = rr;
+  if (a.rr_last) *a.rr_last = rr;
+  if (rr <= a.tol2 || a.max_iters == 0) return NEPTUNE_HIP_OK;
+  rc = rest_of_cycle(kMgcgStartRz);
+  if (rc != NEPTUNE_HIP_OK) return late(rc);
+  NEPTUNE_HIP_CHECK(hipMemcpyAsync(p, z, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+
+  // ---- one iteration.  fused: q = A(p) and pq out of one dot-monitored launch; a refusal of that entry
+  // (NEPTUNE_HIP_EUNSUPPORTED, nothing launched) is remembered: a plain launch and neptune_hip_dot from then on
+  bool fused = L0.fn ? a.fn_dot != nullptr : true;
+  auto iteration = [&]() -> int {
+    int rc;
+    if (fused) {
+      const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+      S.inputs(0, p, ins);
+      rc = L0.fn ? a.fn_dot(&L0.g, ins, q, &scal->pq, (void*)stream, S.cfg)
+                 : neptune_hip_apply_builtin_dot(L0.body, &L0.g, ins, q, &scal->pq, (void*)stream, S.cfg);
+      if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
+      else if (rc != NEPTUNE_HIP_OK) return rc;
+    }
+    if (!fused) {
+      rc = S.apply_of(0, p);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
+      rc = neptune_hip_dot(S.dtype, &L0.g, q, p, &scal->pq, (void*)stream);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
+    }
+    flat_launch(upd, stream, neptune_mgcg_update<T, true>, neptune_mgcg_update<T, false>, n, scal, p, q, minv, x, r, z, partials);
+    final_kernel((int64_t)upd.blocks, kMgcgRr);
+    rc = rest_of_cycle(kMgcgRz);
+    if (rc != NEPTUNE_HIP_OK) return late(rc);
+    flat_launch(dir, stream, neptune_mgcg_direction<T, true>, neptune_mgcg_direction<T, false>, n, scal, z, p);
+    return launched();
+  };
+
+  struct Graph {    // this call's graph of one iteration
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool fallback = false;
+    ~Graph() {
+      if (exec) (void)hipGraphExecDestroy(exec);
+      if (graph) (void)hipGraphDestroy(graph);
+    }
+  } G;
+  // One iteration as a graph: captured on the stream (nothing runs), instantiated; on any refusal under capture the graph is
+  // discarded and the call goes on with plain launches
+  auto capture = [&]() {
+    if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return; }
+    const bool was_fused = fused;
+    const int rc = iteration();
+    hipGraph_t graph = nullptr;
+    if (hipStreamEndCapture(stream, &graph) != hipSuccess) { (void)hipGetLastError(); graph = nullptr; }
+    if (rc != NEPTUNE_HIP_OK || !graph) {
+      if (graph) (void)hipGraphDestroy(graph);
+      fused = was_fused;   // what refused under capture may well run outside
+      return;
+    }
+    if (hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipGraphDestroy(graph);
+      G.exec = nullptr;
+      fused = was_fused;
+      return;
+    }
+    G.graph = graph;
+    G.fallback = !fused;
+  };
+
+  const bool graphs = graph_path_enabled();
+  bool capture_tried = false, rz0_read = false;
+  int64_t done = 0;
+  while (done < a.max_iters) {
+    const int64_t block = a.check_every < a.max_iters - done ? a.check_every : a.max_iters - done;
+    for (int64_t c = 0; c < block; ++c, ++done) {
+      if (done > 0 && graphs && !capture_tried && a.max_iters - done >= 2) {
+        capture_tried = true;
+        capture();
+      }
+      if (done > 0 && G.exec) {
+        NEPTUNE_HIP_CHECK(hipGraphLaunch(G.exec, stream));
+        ++g_mgcg_counts[1];
+        if (G.fallback) ++g_mgcg_counts[2];
+      } else {
+        rc = iteration();
+        if (rc != NEPTUNE_HIP_OK) return late(rc);
+        ++g_mgcg_counts[0];
+        if (!fused) ++g_mgcg_counts[2];
+      }
+      if (a.iters_done) *a.iters_done = done + 1;
+    }
+    if (!rz0_read) read(&scal->rr, &rr, rz0_dev, &g_mgcg_rz0);
+    else read(&scal->rr, &rr);
+    rz0_read = true;
+    ++g_mgcg_counts[3];
+    if (a.rr_last) *a.rr_last = rr;
+    if (rr <= a.tol2) break;   // false for a NaN: such a solve runs to max_iters
+  }
+  return NEPTUNE_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -299,46 +569,10 @@ int neptune_hip_mg_solve(const neptune_hip_mg_level_t* levels, int n_levels, int
   if (rr0) *rr0 = 0.0;
   if (rr_last) *rr_last = 0.0;
   // ---- the refusals, before anything touches the device
-  if (!levels || n_levels < 1 || n_levels > kMaxLevels || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  if (pre < 0 || post < 0 || coarse_sweeps < 0 || check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
+  if (check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
   Solve S;
-  S.levels = levels;
-  S.n_levels = n_levels;
-  S.dtype = dtype;
-  S.pre = pre;
-  S.post = post;
-  S.coarse_sweeps = coarse_sweeps;
-  S.cfg = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
-  S.rank = levels[0].g.rank;
+  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg)) return NEPTUNE_HIP_EINVAL;
   const size_t elem = elem_size(dtype);
-  for (int l = 0; l < n_levels; ++l) {
-    const neptune_hip_mg_level_t& L = levels[l];
-    if (!L.x || !L.b || !L.q || !L.minv) return NEPTUNE_HIP_EINVAL;
-    if (!level_box(&L.g, S.box[l]) || L.g.rank != S.rank) return NEPTUNE_HIP_EINVAL;
-    if (!L.fn) {
-      if (L.body < 0 || L.body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
-      if ((L.body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64) != dtype) return NEPTUNE_HIP_EINVAL;
-    }
-    if (L.g.num_inputs > 1 && !L.in_rest) return NEPTUNE_HIP_EINVAL;
-    for (int i = 1; i < L.g.num_inputs; ++i)
-      if (!L.in_rest[i - 1]) return NEPTUNE_HIP_EINVAL;
-    if (l + 1 < n_levels && !isfinite(L.rscale)) return NEPTUNE_HIP_EINVAL;
-    if (l > 0 && !sizes_nest(S.box[l - 1], S.box[l], S.rank)) return NEPTUNE_HIP_EINVAL;
-    const void* mine[4] = {L.x, L.b, L.q, L.minv};
-    const size_t bytes = box_bytes(S.box[l], elem);
-    for (int a = 0; a < 4; ++a) {
-      if ((uintptr_t)mine[a] % elem != 0) return NEPTUNE_HIP_EINVAL;
-      for (int o = 0; o < a; ++o)
-        if (buffers_overlap(mine[a], bytes, mine[o], bytes)) return NEPTUNE_HIP_EINVAL;
-      if (l > 0) {
-        const neptune_hip_mg_level_t& P = levels[l - 1];
-        const void* finer[4] = {P.x, P.b, P.q, P.minv};
-        const size_t finer_bytes = box_bytes(S.box[l - 1], elem);
-        for (int o = 0; o < 4; ++o)
-          if (buffers_overlap(mine[a], bytes, finer[o], finer_bytes)) return NEPTUNE_HIP_EINVAL;
-      }
-    }
-  }
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
@@ -397,6 +631,93 @@ int neptune_hip_mg_solve(const neptune_hip_mg_level_t* levels, int n_levels, int
     if (rr <= tol2) break;   // false for a NaN: such a solve runs to max_cycles
   }
   return NEPTUNE_HIP_OK;
+}
+
+int neptune_hip_mg_smooth_dot(int dtype, const neptune_hip_apply_geom_t* g, const void* q, const void* b, const void* minv, void* x,
+                              void* dot_out, void* stream) {
+  if (!g || !q || !b || !minv || !x || !dot_out || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B)) return NEPTUNE_HIP_EINVAL;
+  const size_t elem = elem_size(dtype), bytes = box_bytes(B, elem);
+  if (buffers_overlap(x, bytes, q, bytes) || buffers_overlap(x, bytes, b, bytes) || buffers_overlap(x, bytes, minv, bytes)) return NEPTUNE_HIP_EINVAL;
+  if ((uintptr_t)dot_out % elem != 0) return NEPTUNE_HIP_EINVAL;
+  for (const void* f : {q, b, minv, (const void*)x})
+    if (buffers_overlap(dot_out, elem, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const RowGrid r = row_grid(B);
+  const int64_t blocks = grid_blocks(r.grid);
+  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)blocks * elem, stream)) return NEPTUNE_HIP_EUNSUPPORTED;
+  void* const partials = static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return by_type(dtype,
+                 [&] {
+                   hipLaunchKernelGGL(neptune_mg_smooth_dot<double>, r.grid, dim3(256), 0, s, B, r.nchunk, static_cast<const double*>(q),
+                                      static_cast<const double*>(b), static_cast<const double*>(minv), static_cast<double*>(x),
+                                      static_cast<double*>(partials));
+                   hipLaunchKernelGGL(neptune_monitor_final<double>, dim3(1), dim3(256), 0, s, static_cast<const double*>(partials), blocks,
+                                      static_cast<double*>(dot_out));
+                   return launched();
+                 },
+                 [&] {
+                   hipLaunchKernelGGL(neptune_mg_smooth_dot<float>, r.grid, dim3(256), 0, s, B, r.nchunk, static_cast<const float*>(q),
+                                      static_cast<const float*>(b), static_cast<const float*>(minv), static_cast<float*>(x),
+                                      static_cast<float*>(partials));
+                   hipLaunchKernelGGL(neptune_monitor_final<float>, dim3(1), dim3(256), 0, s, static_cast<const float*>(partials), blocks,
+                                      static_cast<float*>(dot_out));
+                   return launched();
+                 });
+}
+
+double neptune_hip_mgcg_rz0(void) { return g_mgcg_rz0; }
+
+void neptune_hip_mgcg_counts(int64_t* plain_iters, int64_t* graph_iters, int64_t* fallback_iters, int64_t* checks) {
+  if (plain_iters) *plain_iters = g_mgcg_counts[0];
+  if (graph_iters) *graph_iters = g_mgcg_counts[1];
+  if (fallback_iters) *fallback_iters = g_mgcg_counts[2];
+  if (checks) *checks = g_mgcg_counts[3];
+}
+
+int neptune_hip_mgcg_solve(const neptune_hip_mg_level_t* levels, int n_levels, int dtype, neptune_hip_apply_dot_fn fn_dot, int sweeps,
+                           int coarse_sweeps, void* const work[3], int64_t max_iters, int64_t check_every, double tol2, void* trace,
+                           void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
+  g_mgcg_rz0 = 0.0;
+  if (iters_done) *iters_done = 0;
+  if (rr0) *rr0 = 0.0;
+  if (rr_last) *rr_last = 0.0;
+  // ---- the refusals, before anything touches the device
+  if (n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
+  Solve S;
+  if (!S.check(levels, n_levels, dtype, sweeps, sweeps, coarse_sweeps, cfg)) return NEPTUNE_HIP_EINVAL;
+  const size_t elem = elem_size(dtype);
+  const size_t bytes0 = box_bytes(S.box[0], elem), bytes1 = box_bytes(S.box[1], elem), trace_bytes = (size_t)(3 * max_iters) * elem;
+  const void* const fine[4] = {levels[0].x, levels[0].b, levels[0].q, levels[0].minv};
+  const void* const coarse[4] = {levels[1].x, levels[1].b, levels[1].q, levels[1].minv};
+  if (trace && (uintptr_t)trace % elem != 0) return NEPTUNE_HIP_EINVAL;
+  for (int i = 0; i < 3; ++i) {
+    if (!work[i] || (uintptr_t)work[i] % elem != 0) return NEPTUNE_HIP_EINVAL;
+    for (int o = 0; o < i; ++o)
+      if (buffers_overlap(work[i], bytes0, work[o], bytes0)) return NEPTUNE_HIP_EINVAL;
+    for (int o = 0; o < 4; ++o)
+      if (buffers_overlap(work[i], bytes0, fine[o], bytes0) || buffers_overlap(work[i], bytes0, coarse[o], bytes1)) return NEPTUNE_HIP_EINVAL;
+    if (trace && buffers_overlap(trace, trace_bytes, work[i], bytes0)) return NEPTUNE_HIP_EINVAL;
+  }
+  for (int o = 0; o < 4 && trace; ++o)
+    if (buffers_overlap(trace, trace_bytes, fine[o], bytes0) || buffers_overlap(trace, trace_bytes, coarse[o], bytes1)) return NEPTUNE_HIP_EINVAL;
+  // rr is read back after every block: not while the caller's stream is being captured
+  if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
+
+  ensure_init();
+  SolveStream sc(reinterpret_cast<hipStream_t>(stream));
+  S.stream = sc.stream;
+  // the preconditioner's hierarchy: level 0 carries (z, r) for (x, b)
+  neptune_hip_mg_level_t lv[kMaxLevels];
+  for (int l = 0; l < n_levels; ++l) lv[l] = levels[l];
+  lv[0].x = work[2];
+  lv[0].b = work[0];
+  S.levels = lv;
+  const MgcgArgs a = {fn_dot, sweeps, work, max_iters, check_every, tol2, trace, iters_done, rr0, rr_last};
+  return dtype == NEPTUNE_HIP_F64 ? mgcg_solve_typed<double>(S, levels[0], a) : mgcg_solve_typed<float>(S, levels[0], a);
 }
 
 }  // extern "C"

@@ -148,6 +148,11 @@ SIGNATURES = {
     "neptune_hip_mg_solve": (_i, [C.POINTER(MgLevel), _i, _i, _i, _i, _i, _i64, _i64, _dbl, C.POINTER(C.c_double), _vp, _cfg_p,
                                   _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_mg_counts": (None, [_i64p, _i64p, _i64p]),
+    "neptune_hip_mg_smooth_dot": (_i, [_i, _geom_p, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "neptune_hip_mgcg_solve": (_i, [C.POINTER(MgLevel), _i, _i, _vp, _i, _i, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mgcg_rz0": (_dbl, []),
+    "neptune_hip_mgcg_counts": (None, [_i64p, _i64p, _i64p, _i64p]),
     "neptune_hip_kernel_name": (C.c_char_p, [_i]),
     "neptune_hip_apply_builtin_variant": (_i, [_i, _geom_p, _cfg_p]),
     "neptune_hip_march_variant_count": (_i, [_i]),

@@ -7,6 +7,10 @@ include/neptune_hip.h; this module builds the C structs and allocates the work f
               for ...]
     h = multigrid.Hierarchy(levels)
     cycles, rr0, rr_last, rr_checks = multigrid.solve(h, x, b, max_cycles=20, tol2=1e-16 * rr0)
+
+multigrid.cg_solve(h, x, b, ...) wraps conjugate gradients around one symmetric V-cycle of the same hierarchy
+(neptune_hip_mgcg_solve): the iteration count stays grid-independent where plain cycles stall, e.g. on
+anisotropic operators.
 """
 from __future__ import annotations
 
@@ -156,6 +160,78 @@ def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int 
     _capi.check(rc, "neptune_hip_mg_solve")
     del keep
     return done.value, rr0.value, last.value, list(rr[:counts()[2]])
+
+
+def cg_counts():
+    """(iterations that ran as plain launches, iterations that ran as graph launches, how many of all these took a plain
+    launch and a separate dot product for q = A(p), read-backs after blocks of iterations) of the last cg_solve call"""
+    vals = [C.c_int64(0) for _ in range(4)]
+    _capi.load().neptune_hip_mgcg_counts(*[C.byref(v) for v in vals])
+    return tuple(v.value for v in vals)
+
+
+def cg_rz0() -> float:
+    """r . M(r) after the set-up of the last cg_solve call (0 when it ran no iteration): with rr0 and the trace, every scalar
+    the recurrences used"""
+    return float(_capi.load().neptune_hip_mgcg_rz0())
+
+
+def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coarse_sweeps: int = 8, max_iters: int = 50,
+             tol2: float = 0.0, check_every: int = 1, trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
+             work: Optional[Sequence[DeviceField]] = None, stream: Optional[int] = None):
+    """solve A_0(x) = b by conjugate gradients preconditioned with one V(sweeps, sweeps) cycle over the hierarchy `h`
+    (neptune_hip_mgcg_solve; at least two levels, sweeps >= 1).  Level 0's minv must be finite on its whole box
+    (jacobi_weights puts +0 outside Omega).  x: initial guess in, solution out; its cells outside Omega_0 are boundary data
+    and are never changed.  The loop stops when r . r <= tol2 (checked every `check_every` iterations) or after max_iters
+    iterations.  dot: level 0's dot entry (LoweredModule.dot_entry), "auto": level 0's entry's own if it has one (built-in
+    bodies do), "fallback" or None: a plain launch and a separate dot product per iteration.  work: three fields like x for
+    r, p, z (allocated here when None).  cfg: the launch configuration of level 0's operator.
+    Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a numpy array of shape (iters, 3) holding
+    (p . A(p) of iteration k, r . M(r) after it, r . r after it).  cg_counts() tells how the iterations were launched."""
+    import torch
+    lib = _capi.load()
+    first = h.levels[0].like
+    if x.box != first.box or b.box != first.box or x.dtype != h.dtype or b.dtype != h.dtype:
+        raise ValueError("multigrid.cg_solve: x and b must have the box and the element type of level 0")
+    if len(h) < 2:
+        raise ValueError("multigrid.cg_solve: at least two levels (one level is apply.cg_solve with minv)")
+    if work is None:
+        work = [DeviceField.empty_like(x) for _ in range(3)]
+    entry = h.levels[0].entry
+    is_entry = hasattr(entry, "fn")
+    if isinstance(dot, str):
+        if dot not in ("auto", "fallback"):
+            raise ValueError('multigrid.cg_solve: dot is "auto", "fallback", None or a dot entry')
+        dot = entry if (dot == "auto" and is_entry) else None
+    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    arr, keep = h._structs(x, b)
+    st = current_stream_ptr() if stream is None else stream
+    tr = torch.zeros(3 * max(int(max_iters), 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    warr = (C.c_void_p * 3)(*[f.ptr for f in work])
+    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    rc = lib.neptune_hip_mgcg_solve(arr, len(h), h.dtype, fn_dot, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2,
+                                    tr.data_ptr() if trace else None, st, C.byref(cfg) if cfg is not None else None,
+                                    C.byref(done), C.byref(rr0), C.byref(last))
+    _capi.check(rc, "neptune_hip_mgcg_solve")
+    del keep
+    if trace:
+        return done.value, rr0.value, last.value, tr.cpu().numpy()[:3 * done.value].reshape(-1, 3)
+    return done.value, rr0.value, last.value
+
+
+def smooth_dot(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, dot_out=None, stream: Optional[int] = None):
+    """smooth(level, q, b, x) and sum over Omega of b * x_new out of the same launch (neptune_hip_mg_smooth_dot).  dot_out: a
+    one-element device tensor of x's element type to receive the sum (asynchronous; -> None), or None: blocking, -> the sum"""
+    import torch
+    if level.minv is None:
+        raise ValueError("multigrid.smooth_dot: the level has no minv")
+    st = current_stream_ptr() if stream is None else stream
+    dst = dot_out if dot_out is not None else torch.zeros(1, dtype=x.tensor.dtype, device=x.tensor.device)
+    _capi.check(_capi.load().neptune_hip_mg_smooth_dot(x.dtype, C.byref(level.geom), q.ptr, b.ptr, level.minv.ptr, x.ptr,
+                                                       dst.data_ptr(), st), "neptune_hip_mg_smooth_dot")
+    if dot_out is not None:
+        return None
+    return float(dst.item())
 
 
 def smooth(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, stream: Optional[int] = None) -> None:
