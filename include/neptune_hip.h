@@ -512,25 +512,34 @@ int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn
  * box = the result's box), an operator A_l (fn, or fn = NULL: built-in body `body`, whose element type must be the call's)
  * with fixed inputs in_rest (in_rest[i] = input i + 1), and the fields x_l, b_l, q_l, minv_l in that box.  Omega_l =
  * apply.bounds x launch region of g_l as a physical [lo, hi) per dimension, m_l[d] = hi - lo >= 1.  The grids are
- * vertex-centred with a Dirichlet rim: every dimension must satisfy m_l[d] = 2 m_(l+1)[d] + 1, and the coarse cell with
- * interior index j (counted from Omega's lower corner) coincides with the fine cell of interior index 2 j + 1.
+ * vertex-centred with a Dirichlet rim.  Between neighbouring levels l and l+1 every dimension d is in one of two states
+ * (semi-coarsening), inferred from the extents -- for m >= 1 both cannot hold:
+ *   COARSENED  m_l[d] = 2 m_(l+1)[d] + 1: the coarse cell with interior index j (counted from Omega's lower corner)
+ *              coincides with the fine cell of interior index 2 j + 1;
+ *   KEPT       m_l[d] = m_(l+1)[d]: the coarse cell with interior index j coincides with the fine cell of interior index j.
+ * At least one dimension must be coarsened; a dimension that is neither, or a pair with none coarsened, is refused.
+ * Along a kept dimension both transfers are the identity -- no operation, no rounding, -0 and NaN keep their bits: the
+ * restriction hands d = b - q through to the next dimension, the prolongation takes e[j] itself, and there is no rim
+ * along it.  The coarsened dimensions run in the order stated below, the kept ones skipped.  With every dimension
+ * coarsened this is full coarsening.
  * SMOOTHING SWEEP on level l (damped Jacobi; the caller folds omega / diagonal into minv):  q = A_l(x) as a plain launch of
  * g_l, then on Omega_l only  d = b - q,  w = minv * d,  x = x + w.  Cells of x outside Omega_l are not written; minv outside
  * Omega_l is never read.
  * RESTRICTION l -> l+1, fused with the residual (r is never a field):  d<f> = b_l<f> - q_l<f> (q_l = A_l(x_l) from a plain
  * launch just before), then the one-dimensional stencil  t = ((0.25 a-) + (0.5 a0)) + (0.25 a+)  centred on fine interior
- * index 2 j + 1, along dimension rank-1 (the contiguous one) first, then rank-2, then rank-3; then
+ * index 2 j + 1, along dimension rank-1 (the contiguous one) first, then rank-2, then rank-3 (kept dimensions skipped); then
  * b_(l+1)<c> = rscale_l * t  and  x_(l+1)<c> = +0  for every c in Omega_(l+1).  Cells outside Omega_(l+1) are not written,
  * and no fine cell outside Omega_l is read.
  * PROLONGATION AND CORRECTION l+1 -> l.  Along one axis a fine cell of interior index i takes  e[(i - 1) / 2]  for odd i and
  * 0.5 * (e[i / 2 - 1] + e[i / 2])  for even i (one rounded addition, then the exact scaling), with e[-1] = e[m_(l+1)] = +0
  * whatever the coarse field holds outside Omega_(l+1).  The tensor product runs along dimension rank-1 first, then rank-2,
- * then rank-3; then  x_l = x_l + e  on Omega_l.  Cells outside keep their bits.
+ * then rank-3 (kept dimensions skipped: the coarse rim is +0 along coarsened dimensions only); then  x_l = x_l + e  on
+ * Omega_l.  Cells outside keep their bits.
  * CYCLE(l).  On level L-1: coarse_sweeps smoothing sweeps.  On any other level: `pre` sweeps;  q = A(x) and the
  * restriction;  Cycle(l+1);  prolongation and correction;  `post` sweeps.
  * The three kernels alone (asynchronous on `stream`; NEPTUNE_HIP_EINVAL, nothing launched: a null pointer, an unknown
- * dtype, a malformed geometry, an empty Omega, ranks that differ, the size relation violated, a non-finite rscale, a
- * written field overlapping a field the same launch reads): */
+ * dtype, a malformed geometry, an empty Omega, ranks that differ, the size relation violated (a dimension neither
+ * coarsened nor kept, or none coarsened), a non-finite rscale, a written field overlapping a field the same launch reads): */
 int neptune_hip_mg_smooth(int dtype, const neptune_hip_apply_geom_t *g, const void *q, const void *b, const void *minv,
                           void *x, void *stream);
 int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
@@ -538,6 +547,12 @@ int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t *g_fine, c
                             void *stream);
 int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
                                const void *x_coarse, void *x_fine, void *stream);
+/* What a pair of levels means: *mask_out = the dimensions coarsened between g_fine and g_coarse, bit d = field dimension d
+ * (the others are kept).  Host-side geometry only, nothing is launched.  NEPTUNE_HIP_EINVAL, *mask_out untouched, where the
+ * transfers would refuse the pair: a null pointer, a malformed geometry, an empty Omega, ranks that differ, a dimension
+ * that is neither coarsened nor kept, no dimension coarsened. */
+int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
+                                  int *mask_out);
 /* One level of a hierarchy.  Level 0's x and b are the caller's problem: initial guess in, solution out, and the
  * right-hand side; the cells of x_0 outside Omega_0 are Dirichlet data that enter through A(x) only.  x_l, b_l of the
  * coarser levels and every q_l are work fields: what they hold on entry does not matter. */

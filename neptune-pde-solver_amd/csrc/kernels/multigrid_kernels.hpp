@@ -1,19 +1,24 @@
-// multigrid_kernels.hpp -- the three kernels of the geometric multigrid V-cycle (neptune_hip_mg_solve):
+// multigrid_kernels.hpp -- the kernels of the geometric multigrid V-cycle (neptune_hip_mg_solve):
 //
 //   neptune_mg_smooth        x = x + (minv * (b - q)) on Omega                       reads q, b, minv, x; writes x: 5 passes
-//   neptune_mg_restrict      b_c = rscale * R(b_f - q_f), x_c = +0 on the coarse Omega   reads b_f, q_f once; writes 2 / 2^rank
+//   neptune_mg_restrict      b_c = rscale * R(b_f - q_f), x_c = +0 on the coarse Omega   reads b_f, q_f once; writes 2 / 2^k (k axes coarsened)
+//   neptune_mg_restrict_kept2   the same with the contiguous axis kept
 //   neptune_mg_prolong_add   x_f = x_f + P(x_c) on the fine Omega                     reads and writes x_f; reads x_c through L1
 //
-// Grids: vertex-centred, Dirichlet rim, m_fine = 2 m_coarse + 1 per dimension; the coarse cell of interior index j sits on the
-// fine cell of interior index 2 j + 1 (interior indices count from Omega's lower corner).
+// Grids: vertex-centred, Dirichlet rim.  Per pair of levels every dimension is either COARSENED, m_fine = 2 m_coarse + 1: the
+// coarse cell of interior index j sits on the fine cell of interior index 2 j + 1 (interior indices count from Omega's lower
+// corner); or KEPT, m_fine = m_coarse: coarse j sits on fine j and the transfer along it is the identity (semi-coarsening,
+// DESIGN 3.16).  The transfer kernels take the pair's state as a compile-time mask MASK: bit a (value 1 << a) set = axis a
+// is coarsened; at least one bit is set.
 //
 // The frame, stated once.  Addressing is the rows form of krylov_kernels.hpp's box_cell, over Omega instead of the box: a
 // workgroup owns ONE 256-cell chunk of one row of (the fine or the coarse) Omega, so the row decode is workgroup-uniform
 // scalar work and only Omega's cells are ever addressed -- nothing outside is read or written.  Axes: every level's box is
 // held on three axes with the field's dimensions RIGHT-aligned (rank 2: axes 1, 2; rank 1: axis 2), absent axes have extent
-// 1 and no transfer stencil: axis a carries one iff a >= 3 - RANK.  Axis 2 is the contiguous one.
+// 1 and are kept: full coarsening of rank 3, 2, 1 is MASK 7, 6, 4.  Axis 2 is the contiguous one.
 // Arithmetic: everything in T, every intermediate a named temporary, one rounding per operation (build with
-// -ffp-contract=off).  The transfer stencils run along axis 2 first, then axis 1, then axis 0.  No atomics, no reductions.
+// -ffp-contract=off).  The transfer stencils run along axis 2 first, then axis 1, then axis 0, skipping kept axes.  No
+// atomics, no reductions.
 // Templates only: the translation unit that holds the solver instantiates them.
 #pragma once
 #include "apply_common.hpp"
@@ -75,11 +80,13 @@ __device__ __forceinline__ T mg_weigh(T am, T a0, T ap) {
 // the stencil runs along axis 2, then axis 1, in registers; the three planes are combined last.
 constexpr int kMgRestrictRow = 2 * 256 + 1;   // fine cells of one staged row segment
 constexpr int kMgRestrictPitch = kMgRestrictRow + 3;
-template <class T, int RANK>
+// This kernel: axis 2 coarsened (MASK & 4); the row count NJ and the plane count NI follow bits 1 and 0.
+template <class T, int MASK>
 __global__ __launch_bounds__(256) void neptune_mg_restrict(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ b_f,
                                                            const T* __restrict__ q_f, T rscale, T* __restrict__ b_c,
                                                            T* __restrict__ x_c) {
-  constexpr int NI = RANK >= 3 ? 3 : 1, NJ = RANK >= 2 ? 3 : 1;
+  static_assert((MASK & 4) != 0 && MASK < 8, "axis 2 coarsened");
+  constexpr int NI = (MASK & 1) ? 3 : 1, NJ = (MASK & 2) ? 3 : 1;
   __shared__ T lds[NJ * kMgRestrictPitch];
   int64_t ci, cj, ck0;
   if (!mg_row(Cb, nchunk, linear_block(), ci, cj, ck0)) return;
@@ -89,7 +96,7 @@ __global__ __launch_bounds__(256) void neptune_mg_restrict(MgBox F, MgBox Cb, in
   const int64_t fk0 = 2 * ck0;
   const int64_t rest = F.m[2] - fk0;
   const int len = (int)(rest < (int64_t)kMgRestrictRow ? rest : (int64_t)kMgRestrictRow);
-  const int64_t fi0 = RANK >= 3 ? 2 * ci : ci, fj0 = RANK >= 2 ? 2 * cj : cj;
+  const int64_t fi0 = (MASK & 1) ? 2 * ci : ci, fj0 = (MASK & 2) ? 2 * cj : cj;
   T plane[NI];
 #pragma unroll
   for (int a = 0; a < NI; ++a) {
@@ -124,6 +131,40 @@ __global__ __launch_bounds__(256) void neptune_mg_restrict(MgBox F, MgBox Cb, in
   x_c[oc] = (T)0;
 }
 
+// Axis 2 kept (MASK = 1, 2, 3): the workgroup's 256 coarse cells sit on the same 256 interior indices of the fine rows
+// (2 ci + {0, 1, 2} or ci, 2 cj + {0, 1, 2} or cj).  Every lane loads its own cell of the NI x NJ rows directly -- coalesced,
+// nothing staged, no barrier -- and d = b - q goes through to the stencil along axis 1, then axis 0, unchanged.
+template <class T, int MASK>
+__global__ __launch_bounds__(256) void neptune_mg_restrict_kept2(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ b_f,
+                                                                 const T* __restrict__ q_f, T rscale, T* __restrict__ b_c,
+                                                                 T* __restrict__ x_c) {
+  static_assert((MASK & 4) == 0 && MASK > 0, "axis 2 kept, another one coarsened");
+  constexpr int NI = (MASK & 1) ? 3 : 1, NJ = (MASK & 2) ? 3 : 1;
+  int64_t ci, cj, ck0;
+  if (!mg_row(Cb, nchunk, linear_block(), ci, cj, ck0)) return;
+  const int64_t ck = ck0 + threadIdx.x;
+  if (ck >= Cb.m[2]) return;
+  const int64_t fi0 = (MASK & 1) ? 2 * ci : ci, fj0 = (MASK & 2) ? 2 * cj : cj;
+  T plane[NI];
+#pragma unroll
+  for (int a = 0; a < NI; ++a) {
+    T row[NJ];
+#pragma unroll
+    for (int r = 0; r < NJ; ++r) {
+      const int64_t o = mg_at(F, fi0 + a, fj0 + r, ck);
+      row[r] = b_f[o] - q_f[o];
+    }
+    if constexpr (NJ == 3) plane[a] = mg_weigh(row[0], row[1], row[2]);
+    else plane[a] = row[0];
+  }
+  T t;
+  if constexpr (NI == 3) t = mg_weigh(plane[0], plane[1], plane[2]);
+  else t = plane[0];
+  const int64_t oc = mg_at(Cb, ci, cj, ck);
+  b_c[oc] = rscale * t;
+  x_c[oc] = (T)0;
+}
+
 // ---------------------------------------------------------------- prolongation and correction
 // one-dimensional interpolation at a fine cell: odd interior index -> the coarse value `hi` itself; even -> 0.5 * (lo + hi),
 // one rounded addition and the exact scaling.  (lo, hi) = e[i / 2 - 1], e[i / 2] for even i, and hi = e[(i - 1) / 2] for odd i;
@@ -135,26 +176,29 @@ __device__ __forceinline__ T mg_interp(bool odd, T lo, T hi) {
   return odd ? hi : h;
 }
 
-// The workgroup owns fine cells (fi, fj, fk0 .. fk0 + 255).  Along axes 0 and 1 the parity is workgroup-uniform: an odd index
-// needs one coarse row / plane, an even one two, of which one may be the rim.  The coarse operands -- up to 2^RANK per cell,
+// The workgroup owns fine cells (fi, fj, fk0 .. fk0 + 255).  Along axes 0 and 1 the parity is workgroup-uniform: on a
+// coarsened axis an odd index needs one coarse row / plane, an even one two, of which one may be the rim; on a kept axis the
+// one row / plane of the same index is read and there is no rim.  The coarse operands -- up to 2^(coarsened axes) per cell,
 // consecutive lanes on consecutive or equal coarse cells of the same few rows -- are read through L1: the coarse field is
-// 1 / 2^RANK of the fine one.
-template <class T, int RANK>
+// that fraction of the fine one.  Axis 2 kept: consecutive lanes read consecutive coarse cells, one operand, no parity.
+template <class T, int MASK>
 __global__ __launch_bounds__(256) void neptune_mg_prolong_add(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ x_c,
                                                               T* __restrict__ x_f) {
-  constexpr int NI = RANK >= 3 ? 2 : 1, NJ = RANK >= 2 ? 2 : 1;
+  static_assert(MASK > 0 && MASK < 8, "at least one axis coarsened");
+  constexpr bool C0 = (MASK & 1) != 0, C1 = (MASK & 2) != 0, C2 = (MASK & 4) != 0;
+  constexpr int NI = C0 ? 2 : 1, NJ = C1 ? 2 : 1;
   int64_t fi, fj, fk0;
   if (!mg_row(F, nchunk, linear_block(), fi, fj, fk0)) return;
   const int64_t fk = fk0 + threadIdx.x;
   if (fk >= F.m[2]) return;
-  // per axis: the two coarse interior indices (lo, hi) and the parity; an absent axis takes its only index as `hi`
-  const bool oi = RANK >= 3 ? (fi & 1) != 0 : true, oj = RANK >= 2 ? (fj & 1) != 0 : true, ok = (fk & 1) != 0;
-  const int64_t ci[2] = {RANK >= 3 ? fi / 2 - 1 : -1, RANK >= 3 ? (oi ? (fi - 1) / 2 : fi / 2) : fi};
-  const int64_t cj[2] = {RANK >= 2 ? fj / 2 - 1 : -1, RANK >= 2 ? (oj ? (fj - 1) / 2 : fj / 2) : fj};
-  const int64_t ck[2] = {fk / 2 - 1, ok ? (fk - 1) / 2 : fk / 2};
+  // per axis: the two coarse interior indices (lo, hi) and the parity; a kept axis takes its only index as `hi`
+  const bool oi = C0 ? (fi & 1) != 0 : true, oj = C1 ? (fj & 1) != 0 : true, ok = C2 ? (fk & 1) != 0 : true;
+  const int64_t ci[2] = {C0 ? fi / 2 - 1 : -1, C0 ? (oi ? (fi - 1) / 2 : fi / 2) : fi};
+  const int64_t cj[2] = {C1 ? fj / 2 - 1 : -1, C1 ? (oj ? (fj - 1) / 2 : fj / 2) : fj};
+  const int64_t ck[2] = {C2 ? fk / 2 - 1 : -1, C2 ? (ok ? (fk - 1) / 2 : fk / 2) : fk};
   // slot 0 (`lo`) is used on an even index only; an index outside [0, m) is the rim
-  const bool vi[2] = {!oi && ci[0] >= 0, ci[1] < Cb.m[0]}, vj[2] = {!oj && cj[0] >= 0, cj[1] < Cb.m[1]};
-  const bool vk[2] = {!ok && ck[0] >= 0, ck[1] < Cb.m[2]};
+  const bool vi[2] = {!oi && ci[0] >= 0, C0 ? ci[1] < Cb.m[0] : true}, vj[2] = {!oj && cj[0] >= 0, C1 ? cj[1] < Cb.m[1] : true};
+  const bool vk[2] = {!ok && ck[0] >= 0, C2 ? ck[1] < Cb.m[2] : true};
   T ei[2] = {(T)0, (T)0};
 #pragma unroll
   for (int a = 2 - NI; a < 2; ++a) {
@@ -163,14 +207,16 @@ __global__ __launch_bounds__(256) void neptune_mg_prolong_add(MgBox F, MgBox Cb,
     for (int r = 2 - NJ; r < 2; ++r) {
       T klo = (T)0, khi = (T)0;
       if (vi[a] && vj[r]) {
-        if (vk[0]) klo = x_c[mg_at(Cb, ci[a], cj[r], ck[0])];
+        if constexpr (C2) {
+          if (vk[0]) klo = x_c[mg_at(Cb, ci[a], cj[r], ck[0])];
+        }
         if (vk[1]) khi = x_c[mg_at(Cb, ci[a], cj[r], ck[1])];
       }
-      ej[r] = mg_interp(ok, klo, khi);
+      ej[r] = C2 ? mg_interp(ok, klo, khi) : khi;
     }
-    ei[a] = RANK >= 2 ? mg_interp(oj, ej[0], ej[1]) : ej[1];
+    ei[a] = C1 ? mg_interp(oj, ej[0], ej[1]) : ej[1];
   }
-  const T e = RANK >= 3 ? mg_interp(oi, ei[0], ei[1]) : ei[1];
+  const T e = C0 ? mg_interp(oi, ei[0], ei[1]) : ei[1];
   const int64_t o = mg_at(F, fi, fj, fk);
   x_f[o] = x_f[o] + e;
 }

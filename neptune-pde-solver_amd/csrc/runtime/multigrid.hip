@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, geom_validate, buffers_overlap (no apply kernel is instantiated here)
@@ -50,11 +51,16 @@ bool level_box(const neptune_hip_apply_geom_t* g, MgBox& B) {
   }
   return true;
 }
-// m_fine = 2 m_coarse + 1 on every axis that carries a dimension
-bool sizes_nest(const MgBox& F, const MgBox& Cb, int rank) {
-  for (int a = 3 - rank; a < 3; ++a)
-    if (F.m[a] != 2 * Cb.m[a] + 1) return false;
-  return true;
+// How two neighbouring levels nest: per axis that carries a dimension either coarsened, m_fine = 2 m_coarse + 1, or kept,
+// m_fine = m_coarse (the two exclude each other for m >= 1).  -> the kernels' mask (bit a: axis a is coarsened), or 0 =
+// refuse: an axis that is neither, or no axis coarsened
+int sizes_nest(const MgBox& F, const MgBox& Cb, int rank) {
+  int mask = 0;
+  for (int a = 3 - rank; a < 3; ++a) {
+    if (F.m[a] == 2 * Cb.m[a] + 1) mask |= 1 << a;
+    else if (F.m[a] != Cb.m[a]) return 0;
+  }
+  return mask;
 }
 size_t box_bytes(const MgBox& B, size_t elem) { return (size_t)(B.n[0] * B.n[1] * B.n[2]) * elem; }
 
@@ -79,48 +85,59 @@ int smooth_launch(const MgBox& B, const void* q, const void* b, const void* minv
                      static_cast<const T*>(minv), static_cast<T*>(x));
   return launched();
 }
-template <class T, int RANK>
+template <class T, int MASK>
 int restrict_launch(const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c, void* x_c,
                     hipStream_t stream) {
   const RowGrid r = row_grid(Cb);
-  hipLaunchKernelGGL((neptune_mg_restrict<T, RANK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
-                     static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
+  // axis 2 coarsened: the fine row segments staged in LDS; kept: every lane on its own fine cells
+  if constexpr ((MASK & 4) != 0)
+    hipLaunchKernelGGL((neptune_mg_restrict<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
+                       static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
+  else
+    hipLaunchKernelGGL((neptune_mg_restrict_kept2<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
+                       static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
   return launched();
 }
-template <class T, int RANK>
+template <class T, int MASK>
 int prolong_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t stream) {
   const RowGrid r = row_grid(F);
-  hipLaunchKernelGGL((neptune_mg_prolong_add<T, RANK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(x_c),
+  hipLaunchKernelGGL((neptune_mg_prolong_add<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(x_c),
                      static_cast<T*>(x_f));
   return launched();
 }
-// the dispatch on element type and rank, stated once
+// the dispatch on element type and on the mask of coarsened axes (1..7, from sizes_nest), stated once
 template <class F64, class F32>
 int by_type(int dtype, F64&& f64, F32&& f32) { return dtype == NEPTUNE_HIP_F64 ? f64() : f32(); }
 int do_smooth(int dtype, const MgBox& B, const void* q, const void* b, const void* minv, void* x, hipStream_t s) {
   return by_type(dtype, [&] { return smooth_launch<double>(B, q, b, minv, x, s); }, [&] { return smooth_launch<float>(B, q, b, minv, x, s); });
 }
-template <class T>
-int restrict_ranked(int rank, const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c, void* x_c,
-                    hipStream_t s) {
-  if (rank == 3) return restrict_launch<T, 3>(F, Cb, b_f, q_f, rscale, b_c, x_c, s);
-  if (rank == 2) return restrict_launch<T, 2>(F, Cb, b_f, q_f, rscale, b_c, x_c, s);
-  return restrict_launch<T, 1>(F, Cb, b_f, q_f, rscale, b_c, x_c, s);
+template <class Launch>
+int by_mask(int mask, Launch&& launch) {
+  switch (mask) {
+    case 1: return launch(std::integral_constant<int, 1>());
+    case 2: return launch(std::integral_constant<int, 2>());
+    case 3: return launch(std::integral_constant<int, 3>());
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 5: return launch(std::integral_constant<int, 5>());
+    case 6: return launch(std::integral_constant<int, 6>());
+    case 7: return launch(std::integral_constant<int, 7>());
+    default: return NEPTUNE_HIP_EINVAL;
+  }
 }
-int do_restrict(int dtype, int rank, const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c,
+int do_restrict(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c,
                 void* x_c, hipStream_t s) {
-  return by_type(dtype, [&] { return restrict_ranked<double>(rank, F, Cb, b_f, q_f, rscale, b_c, x_c, s); },
-                 [&] { return restrict_ranked<float>(rank, F, Cb, b_f, q_f, rscale, b_c, x_c, s); });
+  return by_mask(mask, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    return by_type(dtype, [&] { return restrict_launch<double, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); },
+                   [&] { return restrict_launch<float, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); });
+  });
 }
-template <class T>
-int prolong_ranked(int rank, const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t s) {
-  if (rank == 3) return prolong_launch<T, 3>(F, Cb, x_c, x_f, s);
-  if (rank == 2) return prolong_launch<T, 2>(F, Cb, x_c, x_f, s);
-  return prolong_launch<T, 1>(F, Cb, x_c, x_f, s);
-}
-int do_prolong(int dtype, int rank, const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t s) {
-  return by_type(dtype, [&] { return prolong_ranked<double>(rank, F, Cb, x_c, x_f, s); },
-                 [&] { return prolong_ranked<float>(rank, F, Cb, x_c, x_f, s); });
+int do_prolong(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t s) {
+  return by_mask(mask, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    return by_type(dtype, [&] { return prolong_launch<double, M>(F, Cb, x_c, x_f, s); },
+                   [&] { return prolong_launch<float, M>(F, Cb, x_c, x_f, s); });
+  });
 }
 
 bool stream_capturing(void* stream) {
@@ -163,6 +180,7 @@ struct Solve {
   const neptune_hip_mg_level_t* levels;
   int n_levels, dtype, rank, pre, post, coarse_sweeps;
   MgBox box[kMaxLevels];
+  int mask[kMaxLevels];                  // mask[l]: the axes coarsened between level l and l + 1 (sizes_nest)
   const neptune_hip_launch_cfg_t* cfg;   // level 0's, nullptr unless the caller set anything
   hipStream_t stream;
 
@@ -193,7 +211,10 @@ struct Solve {
       for (int i = 1; i < L.g.num_inputs; ++i)
         if (!L.in_rest[i - 1]) return false;
       if (l + 1 < n_levels && !isfinite(L.rscale)) return false;
-      if (l > 0 && !sizes_nest(box[l - 1], box[l], rank)) return false;
+      if (l > 0) {
+        mask[l - 1] = sizes_nest(box[l - 1], box[l], rank);
+        if (!mask[l - 1]) return false;
+      }
       const void* mine[4] = {L.x, L.b, L.q, L.minv};
       const size_t bytes = box_bytes(box[l], elem);
       for (int a = 0; a < 4; ++a) {
@@ -245,11 +266,11 @@ struct Solve {
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = apply(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_restrict(dtype, rank, box[l], box[l + 1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    rc = do_restrict(dtype, mask[l], box[l], box[l + 1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = cycle(l + 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_prolong(dtype, rank, box[l], box[l + 1], Cl.x, F.x, stream);
+    rc = do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
     return sweeps(l, post);
   }
@@ -391,11 +412,11 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.apply(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_restrict(S.dtype, S.rank, S.box[0], S.box[1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    rc = do_restrict(S.dtype, S.mask[0], S.box[0], S.box[1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.cycle(1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_prolong(S.dtype, S.rank, S.box[0], S.box[1], Cl.x, F.x, stream);
+    rc = do_prolong(S.dtype, S.mask[0], S.box[0], S.box[1], Cl.x, F.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.sweeps(0, a.sweeps - 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
@@ -535,13 +556,14 @@ int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t* g_fine, c
   if (!g_fine || !g_coarse || !b_fine || !q_fine || !b_coarse || !x_coarse || !known_dtype(dtype) || !isfinite(rscale)) return NEPTUNE_HIP_EINVAL;
   MgBox F, Cb;
   if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
-  if (g_fine->rank != g_coarse->rank || !sizes_nest(F, Cb, g_fine->rank)) return NEPTUNE_HIP_EINVAL;
+  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
+  if (!mask) return NEPTUNE_HIP_EINVAL;
   const size_t fb = box_bytes(F, elem_size(dtype)), cb = box_bytes(Cb, elem_size(dtype));
   if (buffers_overlap(b_coarse, cb, x_coarse, cb)) return NEPTUNE_HIP_EINVAL;
   for (const void* w : {(const void*)b_coarse, (const void*)x_coarse})
     if (buffers_overlap(w, cb, b_fine, fb) || buffers_overlap(w, cb, q_fine, fb)) return NEPTUNE_HIP_EINVAL;
   ensure_init();
-  return do_restrict(dtype, g_fine->rank, F, Cb, b_fine, q_fine, rscale, b_coarse, x_coarse, reinterpret_cast<hipStream_t>(stream));
+  return do_restrict(dtype, mask, F, Cb, b_fine, q_fine, rscale, b_coarse, x_coarse, reinterpret_cast<hipStream_t>(stream));
 }
 
 int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
@@ -549,10 +571,21 @@ int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t* g_fine
   if (!g_fine || !g_coarse || !x_coarse || !x_fine || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
   MgBox F, Cb;
   if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
-  if (g_fine->rank != g_coarse->rank || !sizes_nest(F, Cb, g_fine->rank)) return NEPTUNE_HIP_EINVAL;
+  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
+  if (!mask) return NEPTUNE_HIP_EINVAL;
   if (buffers_overlap(x_fine, box_bytes(F, elem_size(dtype)), x_coarse, box_bytes(Cb, elem_size(dtype)))) return NEPTUNE_HIP_EINVAL;
   ensure_init();
-  return do_prolong(dtype, g_fine->rank, F, Cb, x_coarse, x_fine, reinterpret_cast<hipStream_t>(stream));
+  return do_prolong(dtype, mask, F, Cb, x_coarse, x_fine, reinterpret_cast<hipStream_t>(stream));
+}
+
+int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse, int* mask_out) {
+  if (!g_fine || !g_coarse || !mask_out) return NEPTUNE_HIP_EINVAL;
+  MgBox F, Cb;
+  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb) || g_fine->rank != g_coarse->rank) return NEPTUNE_HIP_EINVAL;
+  const int mask = sizes_nest(F, Cb, g_fine->rank);
+  if (!mask) return NEPTUNE_HIP_EINVAL;
+  *mask_out = mask >> (3 - g_fine->rank);   // the kernels' axes are the dimensions right-aligned
+  return NEPTUNE_HIP_OK;
 }
 
 void neptune_hip_mg_counts(int64_t* plain_cycles, int64_t* graph_cycles, int64_t* checks) {

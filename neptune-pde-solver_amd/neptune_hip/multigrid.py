@@ -11,6 +11,11 @@ include/neptune_hip.h; this module builds the C structs and allocates the work f
 multigrid.cg_solve(h, x, b, ...) wraps conjugate gradients around one symmetric V-cycle of the same hierarchy
 (neptune_hip_mgcg_solve): the iteration count stays grid-independent where plain cycles stall, e.g. on
 anisotropic operators.
+
+Two neighbouring levels may coarsen only some dimensions and keep the others (semi-coarsening): the pair's
+extents say which (m_fine = 2 m_coarse + 1 coarsened, m_fine = m_coarse kept).  coarsen_bounds(bounds, axes=...) gives the
+next level's extents, Hierarchy.coarsened records what it found, and coarsening_plan(extents, weights) chooses the
+dimensions per level for an axis-aligned anisotropic operator -sum_d w_d u_dd.
 """
 from __future__ import annotations
 
@@ -23,16 +28,58 @@ from .fields import DeviceField, current_stream_ptr
 from .geometry import Box, make_geom
 
 
-def coarsen_bounds(bounds: Box) -> list:
-    """the next level's interior extents for a level whose interior is `bounds` (lb, ub): (m - 1) / 2 per dimension.
-    ValueError when an extent is even (a vertex-centred grid with a Dirichlet rim nests only for odd extents) or below 3."""
+def coarsen_bounds(bounds: Box, axes=None) -> list:
+    """the next level's interior extents for a level whose interior is `bounds` (lb, ub): (m - 1) / 2 along every dimension
+    in `axes` (an iterable of dimensions to coarsen; default: all of them), m itself along the others (kept: semi-coarsening,
+    DESIGN 3.16).  ValueError when a coarsened extent is even (a vertex-centred grid with a Dirichlet rim nests only for odd
+    extents) or below 3 -- a kept one may be anything --, when `axes` is empty or names a dimension the bounds do not have."""
+    rank = len(bounds[0])
+    chosen = set(range(rank)) if axes is None else {int(d) for d in axes}
+    if not chosen:
+        raise ValueError("coarsen_bounds: no dimension to coarsen (axes is empty)")
+    if not chosen <= set(range(rank)):
+        raise ValueError(f"coarsen_bounds: axes {sorted(chosen)} name a dimension outside 0..{rank - 1}")
     out = []
     for d, (l, u) in enumerate(zip(bounds[0], bounds[1])):
         m = int(u) - int(l)
+        if d not in chosen:
+            out.append(m)
+            continue
         if m < 3 or m % 2 == 0:
             raise ValueError(f"coarsen_bounds: interior extent {m} of dimension {d} is not an odd number >= 3")
         out.append((m - 1) // 2)
     return out
+
+
+def coarsening_plan(extents, weights, threshold: float = 0.5, max_levels: int = 16) -> list:
+    """which dimensions to coarsen on each level of a hierarchy for the operator  -sum_d w_d u_dd  on unscaled star stencils
+    with rscale = 4; -> per level (extents, weights, axes), finest first, `axes` = the dimensions coarsened
+    towards the next level (() on the last).
+
+    The rule: a dimension is coarsenable when its extent is odd and >= 3; of those, the ones whose weight is at least
+    `threshold` x the largest weight among them are coarsened -- the smoother smooths along strongly coupled dimensions
+    only.  The next level keeps w_d on a coarsened dimension and takes 4 w_d on a kept one (with rscale = 4 the coarse
+    stencil is the fine one's, so relative to the coarsened dimensions, whose spacing doubled, a kept one couples 4x as
+    strongly): the anisotropy falls 4x per level until every dimension is coarsened.  The plan ends when nothing is
+    coarsenable or after max_levels levels.
+
+    A heuristic for axis-aligned anisotropy -- one constant weight per dimension --, not a general coarsening strategy:
+    it knows nothing of variable coefficients, rotated anisotropy or mixed derivatives."""
+    m = [int(v) for v in extents]
+    w = [float(v) for v in weights]
+    if len(m) != len(w) or not m or any(v < 1 for v in m) or any(not v > 0.0 for v in w):
+        raise ValueError("coarsening_plan: one positive weight per dimension, extents >= 1")
+    plan = []
+    while True:
+        can = [d for d, v in enumerate(m) if v >= 3 and v % 2 == 1]
+        if not can or len(plan) + 1 >= max_levels:
+            plan.append((tuple(m), tuple(w), ()))
+            return plan
+        strongest = max(w[d] for d in can)
+        axes = tuple(d for d in can if w[d] >= threshold * strongest)
+        plan.append((tuple(m), tuple(w), axes))
+        m = [(v - 1) // 2 if d in axes else v for d, v in enumerate(m)]
+        w = [v if d in axes else 4.0 * v for d, v in enumerate(w)]
 
 
 def jacobi_weights(entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), omega: float = 1.0, reach=None,
@@ -81,24 +128,33 @@ class Level:
 
 
 class Hierarchy:
-    """the levels of a solve, finest first.  Checks the size relation m_l = 2 m_(l+1) + 1 (ValueError naming the level and
-    the dimension), one rank and one element type; allocates x_l and b_l for l >= 1 and every q_l."""
+    """the levels of a solve, finest first.  Checks the size relation per dimension -- coarsened, m_l = 2 m_(l+1) + 1, or
+    kept, m_l = m_(l+1); at least one coarsened -- (ValueError naming the level and the dimension), one rank and one
+    element type; allocates x_l and b_l for l >= 1 and every q_l.  coarsened[l]: the tuple of dimensions coarsened between
+    level l and l + 1."""
 
     def __init__(self, levels: Sequence[Level]):
         self.levels = list(levels)
         if not 1 <= len(self.levels) <= 16:
             raise ValueError("Hierarchy: 1..16 levels")
         first = self.levels[0]
+        self.coarsened = []
         for l, L in enumerate(self.levels):
             if L.like.rank != first.like.rank or L.like.dtype != first.like.dtype:
                 raise ValueError(f"Hierarchy: level {l} has another rank or element type than level 0")
             if any(m < 1 for m in L.m):
                 raise ValueError(f"Hierarchy: level {l} has an empty Omega")
             if l > 0:
+                axes = []
                 for d, (mf, mc) in enumerate(zip(self.levels[l - 1].m, L.m)):
-                    if mf != 2 * mc + 1:
+                    if mf == 2 * mc + 1:
+                        axes.append(d)
+                    elif mf != mc:
                         raise ValueError(f"Hierarchy: level {l}, dimension {d}: interior extent {mc} does not nest in level "
-                                         f"{l - 1}'s {mf} (m_fine = 2 m_coarse + 1)")
+                                         f"{l - 1}'s {mf} (m_fine = 2 m_coarse + 1, or m_fine = m_coarse for a kept dimension)")
+                if not axes:
+                    raise ValueError(f"Hierarchy: level {l} coarsens no dimension of level {l - 1}")
+                self.coarsened.append(tuple(axes))
         self.dtype, self.rank = first.like.dtype, first.like.rank
         self.q = [DeviceField.empty_like(L.like) for L in self.levels]
         self.x = [None] + [DeviceField.empty_like(L.like) for L in self.levels[1:]]
@@ -219,6 +275,15 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
     return done.value, rr0.value, last.value
 
 
+def coarsened_axes(fine: Level, coarse: Level) -> tuple:
+    """the dimensions coarsened between two levels, as the library reads the pair (neptune_hip_mg_coarsened_axes; the others
+    are kept); _capi.NeptuneHipError where the transfers would refuse the pair"""
+    mask = C.c_int(0)
+    _capi.check(_capi.load().neptune_hip_mg_coarsened_axes(C.byref(fine.geom), C.byref(coarse.geom), C.byref(mask)),
+                "neptune_hip_mg_coarsened_axes")
+    return tuple(d for d in range(fine.like.rank) if mask.value >> d & 1)
+
+
 def smooth_dot(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, dot_out=None, stream: Optional[int] = None):
     """smooth(level, q, b, x) and sum over Omega of b * x_new out of the same launch (neptune_hip_mg_smooth_dot).  dot_out: a
     one-element device tensor of x's element type to receive the sum (asynchronous; -> None), or None: blocking, -> the sum"""
@@ -245,15 +310,16 @@ def smooth(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, stream:
 
 def restrict(fine: Level, coarse: Level, b_fine: DeviceField, q_fine: DeviceField, b_coarse: DeviceField, x_coarse: DeviceField,
              stream: Optional[int] = None) -> None:
-    """b_coarse = fine.rscale * R(b_fine - q_fine) and x_coarse = +0 on the coarse Omega (neptune_hip_mg_restrict);
-    asynchronous"""
+    """b_coarse = fine.rscale * R(b_fine - q_fine) and x_coarse = +0 on the coarse Omega (neptune_hip_mg_restrict); R runs
+    along the dimensions the pair coarsens (coarsened_axes) and is the identity along the kept ones; asynchronous"""
     st = current_stream_ptr() if stream is None else stream
     _capi.check(_capi.load().neptune_hip_mg_restrict(b_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom), b_fine.ptr, q_fine.ptr,
                                                      fine.rscale, b_coarse.ptr, x_coarse.ptr, st), "neptune_hip_mg_restrict")
 
 
 def prolong_add(fine: Level, coarse: Level, x_coarse: DeviceField, x_fine: DeviceField, stream: Optional[int] = None) -> None:
-    """x_fine = x_fine + P(x_coarse) on the fine Omega (neptune_hip_mg_prolong_add); asynchronous"""
+    """x_fine = x_fine + P(x_coarse) on the fine Omega (neptune_hip_mg_prolong_add); P interpolates along the dimensions
+    the pair coarsens and is the identity along the kept ones; asynchronous"""
     st = current_stream_ptr() if stream is None else stream
     _capi.check(_capi.load().neptune_hip_mg_prolong_add(x_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom), x_coarse.ptr,
                                                         x_fine.ptr, st), "neptune_hip_mg_prolong_add")
