@@ -587,6 +587,46 @@ int neptune_hip_mg_solve(const neptune_hip_mg_level_t *levels, int n_levels, int
  * and read-backs after blocks (the read of rr_0 is not counted) */
 void neptune_hip_mg_counts(int64_t *plain_cycles, int64_t *graph_cycles, int64_t *checks);
 
+/* Line smoothers: tridiagonal solves along any axis in place of the point sweep.
+ * ARITHMETIC as above: element type T, one rounding per operation, no FMA, every intermediate a named temporary, no
+ * reduction enters a field: every field of a run stays determined bit for bit.
+ * A LINE STAGE on level l is a field dimension a, 0 <= a < rank, plus three factor fields lo, inv, up in the level's box.
+ * It runs  q = A_l(x)  as a plain launch, then for every line of Omega_l along a -- the other interior indices fixed,
+ * m = m_l[a], interior index i --
+ *   forward    d_i = b_i - q_i;   g_0 = d_0 * inv_0;   for i >= 1:  t = lo_i * g_(i-1),  s = d_i - t,  g_i = s * inv_i
+ *   backward   e_(m-1) = g_(m-1);   for i < m-1:  t = up_i * e_(i+1),  e_i = g_i - t
+ *   update     x_i = x_i + e_i
+ * lo_0, up_(m-1) and the factor fields outside Omega are never read.  x outside Omega keeps its bits.  q on Omega holds
+ * unspecified values afterwards (the kernel keeps g there: q is not const); outside Omega q keeps its bits.  m = 1 is
+ * x = x + inv * (b - q): the point sweep's bits when inv = minv.  The values are those of these recurrences, so the solve
+ * along a line is sequential.
+ * THE FACTORS are Thomas's elimination of T / omega, T the tridiagonal part (l_i, t_i, u_i) of A_l along a restricted to
+ * Omega -- couplings to rim cells are dropped: they are Dirichlet data.  Set-up work of the caller, in T with one rounding
+ * per operation:
+ *   l'_i = l_i / omega,  t'_i = t_i / omega,  u'_i = u_i / omega;
+ *   inv_0 = 1 / t'_0,  c_0 = u'_0 * inv_0;   for i >= 1:  p = l'_i * c_(i-1),  den = t'_i - p,  inv_i = 1 / den,  c_i = u'_i * inv_i;
+ *   lo = l',  up = c;  all three +0 outside Omega, lo +0 at i = 0 and up +0 at i = m-1.
+ * A SWEEP on a level that has k >= 1 stages runs all k, each with its own apply.  Pre-sweeps and the last level's coarse
+ * sweeps run stages 0 .. k-1, post-sweeps run k-1 .. 0: a cycle with symmetric stages stays symmetric.  A level with k = 0
+ * runs the point sweep with minv.
+ * The stage's kernel alone (asynchronous on `stream`): the refusals of neptune_hip_mg_smooth, and NEPTUNE_HIP_EINVAL,
+ * nothing launched, for an axis outside the rank, a null factor field, x or q overlapping any other field of the call. */
+int neptune_hip_mg_line_smooth(int dtype, const neptune_hip_apply_geom_t *g, int axis, void *q, const void *b, const void *lo,
+                               const void *inv, const void *up, void *x, void *stream);
+/* The stages of one level: stage s runs along field dimension axis[s] with the factor fields lo[s], inv[s], up[s]. */
+typedef struct { int32_t n_stages; int32_t axis[3]; const void *lo[3], *inv[3], *up[3]; } neptune_hip_mg_lines_t;
+/* neptune_hip_mg_solve with line stages: lines[l] belongs to levels[l]; the solve, the stop rule, rr_checks, the replay (a
+ * stage is two plain launches: the captured cycle stays a linear graph) and the counts are neptune_hip_mg_solve's.
+ * lines == NULL, or n_stages = 0 on every level, is neptune_hip_mg_solve exactly -- the same launches, the same bits --
+ * and neptune_hip_mg_solve is that call.  A level with stages does not read minv, which may then be NULL.
+ * NEPTUNE_HIP_EINVAL, nothing launched: the refusals of neptune_hip_mg_solve, n_stages outside 0..3, an axis outside the
+ * rank, a null or misaligned factor field, a factor field overlapping the level's x, b, q or those of a neighbouring
+ * level.  neptune_hip_mgcg_solve takes no lines: its fused first and last sweeps on level 0 are point Jacobi. */
+int neptune_hip_mg_solve_lines(const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines, int n_levels,
+                               int dtype, int pre, int post, int coarse_sweeps, int64_t max_cycles, int64_t check_every,
+                               double tol2, double *rr_checks, void *stream, const neptune_hip_launch_cfg_t *cfg,
+                               int64_t *cycles_done, double *rr0, double *rr_last);
+
 /* Multigrid-preconditioned conjugate gradients: CG on level 0 whose preconditioner is one V-cycle.
  * ARITHMETIC as above and as for neptune_hip_pcg_solve: element type T, one rounding per operation, no FMA, every
  * intermediate a named temporary, sums on the fixed tree of the monitored launches, no atomics.

@@ -3,7 +3,9 @@
 // neptune_hip_mg_solve is the cycle driver: the levels' operators through the public C API, the kernels in between, r . r
 // through neptune_hip_update_norm, and its own small capture / replay of ONE cycle (a linear graph on the call's stream,
 // captured once per call, destroyed when the call returns).  Its own translation unit (builds in seconds, linked into
-// libneptune_hip.so): host code plus the three kernels' instantiations.
+// libneptune_hip.so): host code plus the kernels' instantiations.  neptune_hip_mg_line_smooth launches one stage of the line
+// smoother (mg_line_kernels.hpp) alone; neptune_hip_mg_solve_lines is the driver with line stages per level, and
+// neptune_hip_mg_solve is that call without any.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -15,6 +17,7 @@
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, geom_validate, buffers_overlap (no apply kernel is instantiated here)
 #include "../kernels/multigrid_kernels.hpp"
+#include "../kernels/mg_line_kernels.hpp"
 #include "../kernels/mgcg_kernels.hpp"
 
 using namespace neptune_hip;
@@ -105,9 +108,44 @@ int prolong_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, 
                      static_cast<T*>(x_f));
   return launched();
 }
+// One stage of the line smoother along box axis `axis`.  Axis 2: a one-wave workgroup per 64 lines.  A slow axis: a workgroup
+// per chunk of lanes along axis 2 and index of the other slow axis; 256 lanes wide where that still gives every CU two
+// workgroups, else 64 lanes, so that a small level (a 2-D field's lines along dim 0 have m[2] / width workgroups in all)
+// spreads over the CUs.
+template <class T, int AXIS, int WIDTH>
+void line_slow_launch(const MgBox& B, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x, hipStream_t stream) {
+  const int64_t nchunk = (B.m[2] + WIDTH - 1) / WIDTH;
+  hipLaunchKernelGGL((neptune_mg_line_slow<T, AXIS, WIDTH>), grid_for_blocks(B.m[1 - AXIS] * nchunk), dim3(WIDTH), 0, stream, B, nchunk,
+                     static_cast<T*>(q), static_cast<const T*>(b), static_cast<const T*>(lo), static_cast<const T*>(inv),
+                     static_cast<const T*>(up), static_cast<T*>(x));
+}
+template <class T>
+int line_launch(const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x, hipStream_t stream) {
+  if (axis == 2) {
+    const int64_t groups = (B.m[0] * B.m[1] + kMgLineGroup - 1) / kMgLineGroup;
+    hipLaunchKernelGGL(neptune_mg_line_contig<T>, grid_for_blocks(groups), dim3(kMgLineGroup), 0, stream, B, static_cast<T*>(q),
+                       static_cast<const T*>(b), static_cast<const T*>(lo), static_cast<const T*>(inv), static_cast<const T*>(up),
+                       static_cast<T*>(x));
+    return launched();
+  }
+  const bool wide = B.m[1 - axis] * ((B.m[2] + 255) / 256) >= 2 * (int64_t)neptune_hip_cu_count();
+  if (axis == 0) {
+    if (wide) line_slow_launch<T, 0, 256>(B, q, b, lo, inv, up, x, stream);
+    else line_slow_launch<T, 0, 64>(B, q, b, lo, inv, up, x, stream);
+  } else {
+    if (wide) line_slow_launch<T, 1, 256>(B, q, b, lo, inv, up, x, stream);
+    else line_slow_launch<T, 1, 64>(B, q, b, lo, inv, up, x, stream);
+  }
+  return launched();
+}
 // the dispatch on element type and on the mask of coarsened axes (1..7, from sizes_nest), stated once
 template <class F64, class F32>
 int by_type(int dtype, F64&& f64, F32&& f32) { return dtype == NEPTUNE_HIP_F64 ? f64() : f32(); }
+int do_line(int dtype, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
+            hipStream_t s) {
+  return by_type(dtype, [&] { return line_launch<double>(B, axis, q, b, lo, inv, up, x, s); },
+                 [&] { return line_launch<float>(B, axis, q, b, lo, inv, up, x, s); });
+}
 int do_smooth(int dtype, const MgBox& B, const void* q, const void* b, const void* minv, void* x, hipStream_t s) {
   return by_type(dtype, [&] { return smooth_launch<double>(B, q, b, minv, x, s); }, [&] { return smooth_launch<float>(B, q, b, minv, x, s); });
 }
@@ -178,6 +216,7 @@ int64_t g_mg_counts[3] = {0, 0, 0};   // plain cycles, graph cycles, checks of t
 // one solve, its arguments checked
 struct Solve {
   const neptune_hip_mg_level_t* levels;
+  const neptune_hip_mg_lines_t* lines;   // per level, or nullptr: no level has line stages
   int n_levels, dtype, rank, pre, post, coarse_sweeps;
   MgBox box[kMaxLevels];
   int mask[kMaxLevels];                  // mask[l]: the axes coarsened between level l and l + 1 (sizes_nest)
@@ -187,10 +226,11 @@ struct Solve {
   // The arguments every solve over a hierarchy shares, checked before anything touches the device, and the solve's fields
   // filled in from them (all but `stream`); -> false: refuse
   bool check(const neptune_hip_mg_level_t* levels_, int n_levels_, int dtype_, int pre_, int post_, int coarse_sweeps_,
-             const neptune_hip_launch_cfg_t* cfg_) {
+             const neptune_hip_launch_cfg_t* cfg_, const neptune_hip_mg_lines_t* lines_ = nullptr) {
     if (!levels_ || n_levels_ < 1 || n_levels_ > kMaxLevels || !known_dtype(dtype_)) return false;
     if (pre_ < 0 || post_ < 0 || coarse_sweeps_ < 0) return false;
     levels = levels_;
+    lines = lines_;
     n_levels = n_levels_;
     dtype = dtype_;
     pre = pre_;
@@ -201,7 +241,9 @@ struct Solve {
     const size_t elem = elem_size(dtype);
     for (int l = 0; l < n_levels; ++l) {
       const neptune_hip_mg_level_t& L = levels[l];
-      if (!L.x || !L.b || !L.q || !L.minv) return false;
+      const int n_stages = lines ? lines[l].n_stages : 0;
+      if (n_stages < 0 || n_stages > 3) return false;
+      if (!L.x || !L.b || !L.q || (!L.minv && n_stages == 0)) return false;   // a level with stages does not read minv
       if (!level_box(&L.g, box[l]) || L.g.rank != rank) return false;
       if (!L.fn) {
         if (L.body < 0 || L.body >= NEPTUNE_HIP_BODY_COUNT) return false;
@@ -218,15 +260,30 @@ struct Solve {
       const void* mine[4] = {L.x, L.b, L.q, L.minv};
       const size_t bytes = box_bytes(box[l], elem);
       for (int a = 0; a < 4; ++a) {
+        if (!mine[a]) continue;   // minv of a level with stages
         if ((uintptr_t)mine[a] % elem != 0) return false;
         for (int o = 0; o < a; ++o)
-          if (buffers_overlap(mine[a], bytes, mine[o], bytes)) return false;
+          if (mine[o] && buffers_overlap(mine[a], bytes, mine[o], bytes)) return false;
         if (l > 0) {
           const neptune_hip_mg_level_t& P = levels[l - 1];
           const void* finer[4] = {P.x, P.b, P.q, P.minv};
           const size_t finer_bytes = box_bytes(box[l - 1], elem);
           for (int o = 0; o < 4; ++o)
-            if (buffers_overlap(mine[a], bytes, finer[o], finer_bytes)) return false;
+            if (finer[o] && buffers_overlap(mine[a], bytes, finer[o], finer_bytes)) return false;
+        }
+      }
+    }
+    // the line stages' factor fields: read-only, so they may not meet a field that the level or a neighbour writes
+    for (int l = 0; l < n_levels && lines; ++l) {
+      const neptune_hip_mg_lines_t& S = lines[l];
+      const size_t bytes = box_bytes(box[l], elem);
+      for (int s = 0; s < S.n_stages; ++s) {
+        if (S.axis[s] < 0 || S.axis[s] >= rank) return false;
+        for (const void* f : {S.lo[s], S.inv[s], S.up[s]}) {
+          if (!f || (uintptr_t)f % elem != 0) return false;
+          for (int o = std::max(l - 1, 0); o <= std::min(l + 1, n_levels - 1); ++o)
+            for (const void* w : {(const void*)levels[o].x, (const void*)levels[o].b, (const void*)levels[o].q})
+              if (buffers_overlap(f, bytes, w, box_bytes(box[o], elem))) return false;
         }
       }
     }
@@ -248,13 +305,24 @@ struct Solve {
   }
   // q_l = A_l(x_l)
   int apply(int l) const { return apply_of(l, levels[l].x); }
-  int sweeps(int l, int count) const {
+  // `count` sweeps: the point sweep with minv, or on a level with k >= 1 line stages all k, each after its own apply --
+  // stages 0 .. k-1, or k-1 .. 0 when `reversed` (the post-sweeps: a cycle of symmetric stages stays symmetric)
+  int sweeps(int l, int count, bool reversed = false) const {
     const neptune_hip_mg_level_t& L = levels[l];
+    const int k = lines ? lines[l].n_stages : 0;
     for (int s = 0; s < count; ++s) {
-      int rc = apply(l);
-      if (rc != NEPTUNE_HIP_OK) return rc;
-      rc = do_smooth(dtype, box[l], L.q, L.b, L.minv, L.x, stream);
-      if (rc != NEPTUNE_HIP_OK) return rc;
+      for (int t = 0; t < std::max(k, 1); ++t) {
+        int rc = apply(l);
+        if (rc != NEPTUNE_HIP_OK) return rc;
+        if (k == 0) {
+          rc = do_smooth(dtype, box[l], L.q, L.b, L.minv, L.x, stream);
+        } else {
+          const neptune_hip_mg_lines_t& S = lines[l];
+          const int st = reversed ? k - 1 - t : t;
+          rc = do_line(dtype, box[l], S.axis[st] + 3 - rank, L.q, L.b, S.lo[st], S.inv[st], S.up[st], L.x, stream);
+        }
+        if (rc != NEPTUNE_HIP_OK) return rc;
+      }
     }
     return NEPTUNE_HIP_OK;
   }
@@ -272,7 +340,7 @@ struct Solve {
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    return sweeps(l, post);
+    return sweeps(l, post, true);
   }
   // rr = sum over Omega_0 of (b - A(x))^2 into *rr_dev, then read back: one stream synchronise, one scalar
   int residual(void* rr_dev, double* rr) const {
@@ -551,6 +619,20 @@ int neptune_hip_mg_smooth(int dtype, const neptune_hip_apply_geom_t* g, const vo
   return do_smooth(dtype, B, q, b, minv, x, reinterpret_cast<hipStream_t>(stream));
 }
 
+int neptune_hip_mg_line_smooth(int dtype, const neptune_hip_apply_geom_t* g, int axis, void* q, const void* b, const void* lo,
+                               const void* inv, const void* up, void* x, void* stream) {
+  if (!g || !q || !b || !lo || !inv || !up || !x || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
+  const size_t bytes = box_bytes(B, elem_size(dtype));
+  for (const void* f : {(const void*)q, b, lo, inv, up})
+    if (buffers_overlap(x, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  for (const void* f : {b, lo, inv, up})
+    if (buffers_overlap(q, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  return do_line(dtype, B, axis + 3 - g->rank, q, b, lo, inv, up, x, reinterpret_cast<hipStream_t>(stream));
+}
+
 int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
                             const void* b_fine, const void* q_fine, double rscale, void* b_coarse, void* x_coarse, void* stream) {
   if (!g_fine || !g_coarse || !b_fine || !q_fine || !b_coarse || !x_coarse || !known_dtype(dtype) || !isfinite(rscale)) return NEPTUNE_HIP_EINVAL;
@@ -597,6 +679,14 @@ void neptune_hip_mg_counts(int64_t* plain_cycles, int64_t* graph_cycles, int64_t
 int neptune_hip_mg_solve(const neptune_hip_mg_level_t* levels, int n_levels, int dtype, int pre, int post, int coarse_sweeps,
                          int64_t max_cycles, int64_t check_every, double tol2, double* rr_checks, void* stream,
                          const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done, double* rr0, double* rr_last) {
+  return neptune_hip_mg_solve_lines(levels, nullptr, n_levels, dtype, pre, post, coarse_sweeps, max_cycles, check_every, tol2, rr_checks,
+                                    stream, cfg, cycles_done, rr0, rr_last);
+}
+
+int neptune_hip_mg_solve_lines(const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines, int n_levels, int dtype,
+                               int pre, int post, int coarse_sweeps, int64_t max_cycles, int64_t check_every, double tol2,
+                               double* rr_checks, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done,
+                               double* rr0, double* rr_last) {
   g_mg_counts[0] = g_mg_counts[1] = g_mg_counts[2] = 0;
   if (cycles_done) *cycles_done = 0;
   if (rr0) *rr0 = 0.0;
@@ -604,7 +694,7 @@ int neptune_hip_mg_solve(const neptune_hip_mg_level_t* levels, int n_levels, int
   // ---- the refusals, before anything touches the device
   if (check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
   Solve S;
-  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg)) return NEPTUNE_HIP_EINVAL;
+  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg, lines)) return NEPTUNE_HIP_EINVAL;
   const size_t elem = elem_size(dtype);
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;

@@ -68,6 +68,12 @@ class MgLevel(C.Structure):
                 ("minv", C.c_void_p), ("x", C.c_void_p), ("b", C.c_void_p), ("q", C.c_void_p), ("rscale", C.c_double)]
 
 
+class MgLines(C.Structure):
+    """neptune_hip_mg_lines_t: the line stages of one level"""
+    _fields_ = [("n_stages", C.c_int32), ("axis", C.c_int32 * 3), ("lo", C.c_void_p * 3), ("inv", C.c_void_p * 3),
+                ("up", C.c_void_p * 3)]
+
+
 def _memref(rank: int):
     class _M(C.Structure):
         _fields_ = [("allocated", C.c_void_p), ("aligned", C.c_void_p), ("offset", C.c_int64),
@@ -147,6 +153,9 @@ SIGNATURES = {
     "neptune_hip_mg_prolong_add": (_i, [_i, _geom_p, _geom_p, _vp, _vp, _vp]),
     "neptune_hip_mg_solve": (_i, [C.POINTER(MgLevel), _i, _i, _i, _i, _i, _i64, _i64, _dbl, C.POINTER(C.c_double), _vp, _cfg_p,
                                   _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mg_line_smooth": (_i, [_i, _geom_p, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "neptune_hip_mg_solve_lines": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), _i, _i, _i, _i, _i, _i64, _i64, _dbl,
+                                        C.POINTER(C.c_double), _vp, _cfg_p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_mg_coarsened_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
     "neptune_hip_mg_counts": (None, [_i64p, _i64p, _i64p]),
     "neptune_hip_mg_smooth_dot": (_i, [_i, _geom_p, _vp, _vp, _vp, _vp, _vp, _vp]),

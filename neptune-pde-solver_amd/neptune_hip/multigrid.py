@@ -16,11 +16,16 @@ Two neighbouring levels may coarsen only some dimensions and keep the others (se
 extents say which (m_fine = 2 m_coarse + 1 coarsened, m_fine = m_coarse kept).  coarsen_bounds(bounds, axes=...) gives the
 next level's extents, Hierarchy.coarsened records what it found, and coarsening_plan(extents, weights) chooses the
 dimensions per level for an axis-aligned anisotropic operator -sum_d w_d u_dd.
+
+A level may smooth with line stages instead of the point sweep: Level(..., lines=[line_weights(entry, like,
+bounds, axis=d, omega=0.8) for d in (0, 1)]) solves the operator's tridiagonal part along dimension 0, then along dimension
+1, in every sweep -- the repair for anisotropy whose strong direction varies in space.  solve() then runs
+neptune_hip_mg_solve_lines; cg_solve() takes no line stages.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 from . import _capi
 from . import apply as _apply
@@ -103,16 +108,146 @@ def jacobi_weights(entry, like: DeviceField, bounds: Box, others: Sequence[Devic
     return w
 
 
+def operator_tridiagonal(entry, like: DeviceField, bounds: Box, axis: int, others: Sequence[DeviceField] = (), reach=None,
+                         region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None):
+    """the tridiagonal part of a LINEAR operator along dimension `axis`, restricted to Omega = bounds x region:
+    -> (lower, diag, upper), fields like `like` with A's entry at (p, p - e_axis), (p, p), (p, p + e_axis) on the cells p of
+    Omega and +0 elsewhere; an entry that couples to a cell outside Omega (the rim) is +0.  The coloured unit-vector probes of
+    apply.operator_diagonal, with its guard launch, its arguments and its caveat for an affine operator: with a colour at
+    cell j the result at j - e_axis is `upper` of that cell and the result at j + e_axis is `lower` of that cell -- cells of
+    one colour are 2 reach + 1 >= 3 apart along `axis`, so neither sees another coloured cell.  ValueError when reach along
+    `axis` is below 1.  Set-up work, blocking."""
+    import itertools
+    import torch
+    axis = int(axis)
+    if not 0 <= axis < like.rank:
+        raise ValueError(f"operator_tridiagonal: axis {axis} is outside 0..{like.rank - 1}")
+    if reach is None:
+        if not hasattr(entry, "halo0"):
+            raise ValueError("operator_tridiagonal: reach is required for a built-in body")
+        reach = entry.halo0
+    reach = [int(reach)] * like.rank if isinstance(reach, int) else [int(r) for r in reach]
+    if len(reach) != like.rank or any(r < 0 for r in reach):
+        raise ValueError("operator_tridiagonal: reach is a non-negative int or one per dimension")
+    if reach[axis] < 1:
+        raise ValueError(f"operator_tridiagonal: reach along axis {axis} must be at least 1")
+    others = list(others)
+    lo, hi = _apply._omega(like, bounds, region)
+    lower, diag, upper = (DeviceField.empty_like(like) for _ in range(3))
+    for f in (lower, diag, upper):
+        f.tensor.zero_()
+    if any(h <= l for l, h in zip(lo, hi)):
+        return lower, diag, upper
+    probe, out = DeviceField.empty_like(like), DeviceField.empty_like(like)
+    stride = [2 * r + 1 for r in reach]
+    mid = [(l + h) // 2 for l, h in zip(lo, hi)]
+    probe.tensor.zero_()
+    probe.tensor[tuple(mid)] = 1.0
+    out.tensor.zero_()
+    _apply.apply_builtin(entry, [probe] + others, out, bounds, region=region, cfg=cfg)
+    seen = out.tensor[tuple(slice(l, h) for l, h in zip(lo, hi))].clone()
+    seen[tuple(slice(max(m - r - l, 0), m + r + 1 - l) for m, r, l in zip(mid, reach, lo))] = 0.0
+    if bool((seen != 0).any()):
+        raise ValueError(f"operator_tridiagonal: the operator reaches further than reach = {reach} (a unit vector at {mid} is "
+                         "seen beyond it): give reach per dimension")
+    for colour in itertools.product(*[range(min(s, h - l)) for s, l, h in zip(stride, lo, hi)]):
+        cells = [slice(l + c, h, s) for l, h, c, s in zip(lo, hi, colour, stride)]
+        probe.tensor.zero_()
+        probe.tensor[tuple(cells)] = 1.0
+        out.tensor.zero_()
+        _apply.apply_builtin(entry, [probe] + others, out, bounds, region=region, cfg=cfg)
+        diag.tensor[tuple(cells)] = out.tensor[tuple(cells)]
+        l, h, c, s = lo[axis], hi[axis], colour[axis], stride[axis]
+        below, above = list(cells), list(cells)
+        below[axis] = slice(l + c - 1 if c >= 1 else l + c + s - 1, h - 1, s)   # j - 1 for the coloured j >= l + 1
+        above[axis] = slice(l + c + 1, h, s)                                    # j + 1 for the coloured j <= h - 2
+        upper.tensor[tuple(below)] = out.tensor[tuple(below)]
+        lower.tensor[tuple(above)] = out.tensor[tuple(above)]
+    torch.cuda.synchronize()
+    return lower, diag, upper
+
+
+class LineStage(NamedTuple):
+    """one stage of a line smoother: the field dimension the lines run along and the factor fields of Thomas's elimination
+    (line_weights; the definition is in include/neptune_hip.h)"""
+    axis: int
+    lo: DeviceField
+    inv: DeviceField
+    up: DeviceField
+
+
+def line_factors(lower, diag, upper, where, axis: int, omega: float = 1.0):
+    """the factor recurrence of a line stage on NumPy arrays (the tridiagonal part of the operator over the level's box,
+    `where`: Omega as a tuple of slices): -> (lo, inv, up), in the arrays' element type with one rounding per operation, +0
+    outside Omega; ValueError when a pivot is 0 or not finite"""
+    import numpy as np
+    dt = diag.dtype.type
+    w = dt(omega)
+    move = lambda a: np.moveaxis(a[where], axis, 0)
+    l, t, u = move(lower), move(diag), move(upper)
+    m = t.shape[0]
+    lo_, inv_, up_ = (np.zeros(t.shape, diag.dtype) for _ in range(3))
+    with np.errstate(all="ignore"):
+        ls, ts, us = (l / w).astype(dt), (t / w).astype(dt), (u / w).astype(dt)
+        c = None
+        for i in range(m):
+            if i == 0:
+                den = ts[0]
+            else:
+                p = (ls[i] * c).astype(dt)
+                den = (ts[i] - p).astype(dt)
+            bad = int(((den == 0) | ~np.isfinite(den)).sum())
+            if bad:
+                raise ValueError(f"line_weights: {bad} pivots at interior index {i} along axis {axis} are 0 or not finite")
+            inv_[i] = (dt(1) / den).astype(dt)
+            c = (us[i] * inv_[i]).astype(dt)
+            if i > 0:
+                lo_[i] = ls[i]
+            if i < m - 1:
+                up_[i] = c
+    out = []
+    for a in (lo_, inv_, up_):
+        full = np.zeros(diag.shape, diag.dtype)
+        full[where] = np.moveaxis(a, 0, axis)
+        out.append(full)
+    return tuple(out)
+
+
+def line_weights(entry, like: DeviceField, bounds: Box, axis: int, others: Sequence[DeviceField] = (), omega: float = 1.0,
+                 reach=None, region: Optional[Box] = None, cfg: Optional[_capi.LaunchCfg] = None) -> LineStage:
+    """the factors of a line stage along dimension `axis` for Level(lines=...): Thomas's elimination of T / omega, T the
+    tridiagonal part of the operator along `axis` restricted to Omega (operator_tridiagonal, whose arguments the others are).
+    The recurrence is set-up work and runs on the host in NumPy, in the element type with one rounding per operation as
+    include/neptune_hip.h defines it -- the device's division is not relied on.  ValueError when a pivot (t'_0 or a den) is 0
+    or not finite."""
+    lower, diag, upper = operator_tridiagonal(entry, like, bounds, axis, others, reach, region, cfg)
+    lo, hi = _apply._omega(like, bounds, region)
+    where = tuple(slice(l, h) for l, h in zip(lo, hi))
+    if any(h <= l for l, h in zip(lo, hi)):
+        return LineStage(int(axis), lower, diag, upper)   # all +0
+    f = line_factors(lower.numpy(), diag.numpy(), upper.numpy(), where, int(axis), omega)
+    return LineStage(int(axis), *[DeviceField.from_numpy(a) for a in f])
+
+
 class Level:
     """one level of a hierarchy: the operator (`entry`: a built-in body id or a lowered apply's geometry-level entry whose
     input 0 has the result's box), a field `like` that gives the level's box and element type, the apply's `bounds`
     (logical), its fixed inputs 1.. (`others`), the smoother's weights `minv` (a field like `like`: omega / diagonal on
     Omega, e.g. jacobi_weights; required before a solve), the factor `rscale` of the restriction that leaves this level
-    (4 for an operator that is not scaled by 1 / h^2: the coarse operator is then the fine one's stencil) and the launch
-    `region` (result-physical, default: the whole box)."""
+    (4 for an operator that is not scaled by 1 / h^2: the coarse operator is then the fine one's stencil), the launch
+    `region` (result-physical, default: the whole box) and `lines`: up to three LineStages (line_weights) that replace the
+    point sweep on this level; minv may be omitted when lines is given."""
 
     def __init__(self, entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), minv: Optional[DeviceField] = None,
-                 rscale: float = 4.0, region: Optional[Box] = None):
+                 rscale: float = 4.0, region: Optional[Box] = None, lines: Sequence[LineStage] = ()):
+        self.lines = [LineStage(*st) for st in lines]
+        if len(self.lines) > 3:
+            raise ValueError("Level: at most three line stages")
+        for st in self.lines:
+            if not 0 <= int(st.axis) < like.rank:
+                raise ValueError(f"Level: a line stage along axis {st.axis} on a field of rank {like.rank}")
+            if any(f.box != like.box or f.dtype != like.dtype for f in (st.lo, st.inv, st.up)):
+                raise ValueError("Level: a line stage's factor fields must have the box and the element type of `like`")
         self.entry, self.like, self.others, self.minv, self.rscale, self.region = entry, like, list(others), minv, float(rscale), region
         self.bounds = ([int(v) for v in bounds[0]], [int(v) for v in bounds[1]])
         self.geom = make_geom(like.box, self.bounds, [like.box] + [f.box for f in self.others], region)
@@ -169,8 +304,8 @@ class Hierarchy:
         arr = (_capi.MgLevel * n)()
         keep = []
         for l, L in enumerate(self.levels):
-            if L.minv is None:
-                raise ValueError(f"multigrid: level {l} has no minv (jacobi_weights)")
+            if L.minv is None and not L.lines:
+                raise ValueError(f"multigrid: level {l} has no minv (jacobi_weights) and no line stages")
             is_entry = hasattr(L.entry, "fn")
             arr[l].fn = C.cast(L.entry.fn, C.c_void_p) if is_entry else None
             arr[l].body = -1 if is_entry else int(L.entry)
@@ -179,12 +314,26 @@ class Hierarchy:
                 rest = (C.c_void_p * len(L.others))(*[f.ptr for f in L.others])
                 keep.append(rest)
                 arr[l].in_rest = rest
-            arr[l].minv = L.minv.ptr
+            arr[l].minv = L.minv.ptr if L.minv is not None else None
             arr[l].x = (x if l == 0 else self.x[l]).ptr
             arr[l].b = (b if l == 0 else self.b[l]).ptr
             arr[l].q = self.q[l].ptr
             arr[l].rscale = L.rscale
         return arr, keep
+
+    @property
+    def has_lines(self) -> bool:
+        return any(L.lines for L in self.levels)
+
+    def _line_structs(self):
+        """-> the C array of neptune_hip_mg_lines_t, one per level (the factor fields stay alive in the levels)"""
+        arr = (_capi.MgLines * len(self.levels))()
+        for l, L in enumerate(self.levels):
+            arr[l].n_stages = len(L.lines)
+            for s, st in enumerate(L.lines):
+                arr[l].axis[s] = int(st.axis)
+                arr[l].lo[s], arr[l].inv[s], arr[l].up[s] = st.lo.ptr, st.inv.ptr, st.up.ptr
+        return arr
 
 
 def counts():
@@ -197,7 +346,8 @@ def counts():
 
 def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int = 2, coarse_sweeps: int = 8, max_cycles: int = 20,
           tol2: float = 0.0, check_every: int = 1, cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
-    """solve A_0(x) = b by V(pre, post) cycles over the hierarchy `h` (neptune_hip_mg_solve).  x: initial guess in, solution
+    """solve A_0(x) = b by V(pre, post) cycles over the hierarchy `h` (neptune_hip_mg_solve; neptune_hip_mg_solve_lines when
+    any level has line stages).  x: initial guess in, solution
     out; its cells outside Omega_0 are boundary data and are never written.  The loop stops when r . r <= tol2 (checked every
     `check_every` cycles) or after max_cycles cycles.  cfg: the launch configuration of level 0's operator.
     Blocking; -> (cycles, rr0, rr_last, rr_checks): rr_checks is the list of r . r values read after each block of cycles.
@@ -211,9 +361,12 @@ def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int 
     n_checks = max(-(-int(max_cycles) // max(int(check_every), 1)), 1)
     rr = (C.c_double * n_checks)()
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-    rc = lib.neptune_hip_mg_solve(arr, len(h), h.dtype, pre, post, coarse_sweeps, max_cycles, check_every, tol2, rr, st,
-                                  C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
-    _capi.check(rc, "neptune_hip_mg_solve")
+    rest = (pre, post, coarse_sweeps, max_cycles, check_every, tol2, rr, st, C.byref(cfg) if cfg is not None else None,
+            C.byref(done), C.byref(rr0), C.byref(last))
+    if h.has_lines:
+        _capi.check(lib.neptune_hip_mg_solve_lines(arr, h._line_structs(), len(h), h.dtype, *rest), "neptune_hip_mg_solve_lines")
+    else:
+        _capi.check(lib.neptune_hip_mg_solve(arr, len(h), h.dtype, *rest), "neptune_hip_mg_solve")
     del keep
     return done.value, rr0.value, last.value, list(rr[:counts()[2]])
 
@@ -251,6 +404,9 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
         raise ValueError("multigrid.cg_solve: x and b must have the box and the element type of level 0")
     if len(h) < 2:
         raise ValueError("multigrid.cg_solve: at least two levels (one level is apply.cg_solve with minv)")
+    if h.has_lines:
+        raise ValueError("multigrid.cg_solve: the hierarchy has line stages; neptune_hip_mgcg_solve smooths with point Jacobi "
+                         "only (its fused first and last sweeps on level 0)")
     if work is None:
         work = [DeviceField.empty_like(x) for _ in range(3)]
     entry = h.levels[0].entry
@@ -306,6 +462,14 @@ def smooth(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, stream:
     st = current_stream_ptr() if stream is None else stream
     _capi.check(_capi.load().neptune_hip_mg_smooth(x.dtype, C.byref(level.geom), q.ptr, b.ptr, level.minv.ptr, x.ptr, st),
                 "neptune_hip_mg_smooth")
+
+
+def line_smooth(level: Level, stage: LineStage, q: DeviceField, b: DeviceField, x: DeviceField, stream: Optional[int] = None) -> None:
+    """one line stage on `level` from q = A(x): the tridiagonal solves along stage.axis on Omega and x = x + e
+    (neptune_hip_mg_line_smooth); q on Omega is overwritten; asynchronous"""
+    st = current_stream_ptr() if stream is None else stream
+    _capi.check(_capi.load().neptune_hip_mg_line_smooth(x.dtype, C.byref(level.geom), int(stage.axis), q.ptr, b.ptr, stage.lo.ptr,
+                                                        stage.inv.ptr, stage.up.ptr, x.ptr, st), "neptune_hip_mg_line_smooth")
 
 
 def restrict(fine: Level, coarse: Level, b_fine: DeviceField, q_fine: DeviceField, b_coarse: DeviceField, x_coarse: DeviceField,
