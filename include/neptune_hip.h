@@ -621,11 +621,33 @@ typedef struct { int32_t n_stages; int32_t axis[3]; const void *lo[3], *inv[3], 
  * and neptune_hip_mg_solve is that call.  A level with stages does not read minv, which may then be NULL.
  * NEPTUNE_HIP_EINVAL, nothing launched: the refusals of neptune_hip_mg_solve, n_stages outside 0..3, an axis outside the
  * rank, a null or misaligned factor field, a factor field overlapping the level's x, b, q or those of a neighbouring
- * level.  neptune_hip_mgcg_solve takes no lines: its fused first and last sweeps on level 0 are point Jacobi. */
+ * level.  neptune_hip_mgcg_solve itself takes no lines (its fused first and last sweeps on level 0 are point Jacobi);
+ * neptune_hip_mgcg_solve_lines below does. */
 int neptune_hip_mg_solve_lines(const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines, int n_levels,
                                int dtype, int pre, int post, int coarse_sweeps, int64_t max_cycles, int64_t check_every,
                                double tol2, double *rr_checks, void *stream, const neptune_hip_launch_cfg_t *cfg,
                                int64_t *cycles_done, double *rr0, double *rr_last);
+
+/* TWO MORE FORMS OF THE STAGE'S KERNEL, alone (asynchronous on `stream`).  ARITHMETIC as above.
+ * neptune_hip_mg_line_first is the APPLY-FREE stage: the values of the plain stage run on q = +0, x = +0 --
+ *   d_i = b_i, the forward and backward recurrences unchanged, x_i = (+0) + e_i
+ * -- the addition of +0 stays: the bits are the plain stage's, a -0 becomes +0.  It reads b, lo, inv, up and writes x on Omega
+ * only; it does not read x (it keeps g there between its two marches) and has no q.  The refusals of
+ * neptune_hip_mg_line_smooth, without those for q. */
+int neptune_hip_mg_line_first(int dtype, const neptune_hip_apply_geom_t *g, int axis, const void *b, const void *lo,
+                              const void *inv, const void *up, void *x, void *stream);
+/* neptune_hip_mg_line_smooth_dot is neptune_hip_mg_line_smooth (the same update of x on Omega, the same cells read and
+ * written) and *dot_out = sum over Omega of b * x_new: in the backward march t_i = b_i * x_new,i, one rounding, from the
+ * freshly formed x_new; a lane adds its line's terms to one accumulator in the order of that march (i = m-1 .. 0) from +0;
+ * one partial per workgroup on the fixed tree of the monitored launches (a 64-lane workgroup's partial is its single wave's
+ * sum), added in index order by one workgroup.  Which lines share a workgroup is the launch's choice (the lanes of a slow-axis
+ * workgroup own consecutive cells of the contiguous axis, 256 or 64 of them; a contiguous-axis workgroup owns 64 consecutive
+ * lines): the sum is one of the orders this allows, and is the same from run to run.  dot_out: a DEVICE pointer to one T.
+ * The refusals of neptune_hip_mg_line_smooth, and as for neptune_hip_mg_smooth_dot: NEPTUNE_HIP_EINVAL for a null or
+ * misaligned dot_out or one that overlaps a field, NEPTUNE_HIP_EUNSUPPORTED, nothing launched, when `stream` is being
+ * captured and the partials' workspace would have to grow. */
+int neptune_hip_mg_line_smooth_dot(int dtype, const neptune_hip_apply_geom_t *g, int axis, void *q, const void *b,
+                                   const void *lo, const void *inv, const void *up, void *x, void *dot_out, void *stream);
 
 /* Multigrid-preconditioned conjugate gradients: CG on level 0 whose preconditioner is one V-cycle.
  * ARITHMETIC as above and as for neptune_hip_pcg_solve: element type T, one rounding per operation, no FMA, every
@@ -682,6 +704,28 @@ int neptune_hip_mgcg_solve(const neptune_hip_mg_level_t *levels, int n_levels, i
                            int sweeps, int coarse_sweeps, void *const work[3], int64_t max_iters, int64_t check_every,
                            double tol2, void *trace, void *stream, const neptune_hip_launch_cfg_t *cfg,
                            int64_t *iters_done, double *rr0, double *rr_last);
+/* neptune_hip_mgcg_solve WITH LINE STAGES: lines[l] belongs to levels[l] as in neptune_hip_mg_solve_lines.
+ * lines == NULL, or n_stages = 0 on every level, is neptune_hip_mgcg_solve exactly -- the same launches, the same bits --
+ * and neptune_hip_mgcg_solve is that call.  A level with stages does not read minv, which may then be NULL; that includes
+ * level 0.  Stages on levels >= 1 change nothing else: those levels run Cycle(l) with their stages.
+ * WHEN LEVEL 0 HAS k >= 1 STAGES the preconditioner z = M(r) is one V(sweeps, sweeps) cycle of neptune_hip_mg_solve_lines on
+ * A_0 z = r from z = 0, with two differences, both on level 0:
+ *   - the first stage (stage 0) of the first pre-sweep runs no apply: it is neptune_hip_mg_line_first's kernel on b = r,
+ *     x = z.  Stages 1 .. k-1 of that sweep are plain (apply + stage).  z outside Omega_0 is zero-filled once at set-up, whole
+ *     box -- the error equation's Dirichlet rim -- and nothing writes there again.
+ *   - the last stage (stage 0) of the last post-sweep is neptune_hip_mg_line_smooth_dot's kernel after its own apply: it
+ *     also yields r . z.
+ * The set-up and the iteration are neptune_hip_mgcg_solve's step for step, except that the set-up's step 2 and the
+ * iteration's step 2 store r (and x) only -- z = minv_0 * r is not formed, rr is unchanged -- and that "the rest of M"
+ * starts with the apply-free stage.  Scalars, trace, stop rule, the fallback of step 1, the counts and the replay (a stage is
+ * plain launches: the captured iteration stays a linear graph) are unchanged.
+ * NEPTUNE_HIP_EINVAL, nothing launched: the refusals of neptune_hip_mgcg_solve, those neptune_hip_mg_solve_lines adds for
+ * `lines`, and a factor field that overlaps work[0..2] or the trace. */
+int neptune_hip_mgcg_solve_lines(const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines, int n_levels,
+                                 int dtype, neptune_hip_apply_dot_fn fn_dot, int sweeps, int coarse_sweeps,
+                                 void *const work[3], int64_t max_iters, int64_t check_every, double tol2, void *trace,
+                                 void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0,
+                                 double *rr_last);
 /* rz_0 = r . M(r) after the set-up of the last neptune_hip_mgcg_solve call of this process (0 when it was refused or ran
  * no iteration): with *rr0 and the trace, every scalar the recurrences used, so that a run can be replayed */
 double neptune_hip_mgcg_rz0(void);

@@ -5,6 +5,9 @@
 //   neptune_mg_line_contig   lines along box axis 2 (the contiguous one): a wave owns 64 lines and walks them in segments
 //                            that are transposed through LDS
 //
+//   neptune_mg_line_{slow,contig}_first   the apply-free form of either: the stage on q = +0, x = +0
+//   neptune_mg_line_{slow,contig}_dot     either with the sum of b * x_new out of the backward march
+//
 // Per line of Omega along the axis (interior index i, m cells), from q = A(x) of the plain launch just before:
 //   forward    d_i = b_i - q_i;  g_0 = d_0 * inv_0;  i >= 1:  t = lo_i * g_(i-1),  s = d_i - t,  g_i = s * inv_i     (g is stored into q)
 //   backward   e_(m-1) = g_(m-1);  i < m-1:  t = up_i * e_(i+1),  e_i = g_i - t
@@ -29,28 +32,49 @@ namespace neptune_hip {
 // WIDTH is 256, or 64 where the level has too few lines to fill the CUs with 256-lane workgroups (the host decides).
 constexpr int kMgLineUnroll = 4;
 
-template <class T, int AXIS, int WIDTH>
-__global__ __launch_bounds__(WIDTH) void neptune_mg_line_slow(MgBox B, int64_t nchunk, T* __restrict__ q, const T* __restrict__ b,
-                                                              const T* __restrict__ lo, const T* __restrict__ inv,
-                                                              const T* __restrict__ up, T* __restrict__ x) {
+// The stage's three forms.  kMgLinePlain is the stage as above.  kMgLineFirst is the stage on q = +0, x = +0
+// without reading either: d_i = b_i, g is kept in x (q is not touched), x_i = (+0) + e_i -- the addition stays, it turns a
+// -0 into the +0 of the plain stage.  kMgLineDot is the plain stage that also forms t_i = b_i * x_new,i in the backward
+// march, one rounding, and adds it to the lane's accumulator in the order of that march (i = m-1 .. 0) from +0.
+enum : int { kMgLinePlain = 0, kMgLineFirst = 1, kMgLineDot = 2 };
+
+// -> the lane's accumulator (kMgLineDot; +0 otherwise and for a lane without a line)
+template <class T, int AXIS, int WIDTH, int MODE>
+__device__ __forceinline__ T mg_line_slow_body(const MgBox& B, int64_t nchunk, T* __restrict__ q, const T* __restrict__ b,
+                                               const T* __restrict__ lo, const T* __restrict__ inv, const T* __restrict__ up,
+                                               T* __restrict__ x) {
   static_assert(AXIS == 0 || AXIS == 1, "a slow axis");
   constexpr int OTHER = 1 - AXIS;
   constexpr int U = kMgLineUnroll;
+  constexpr bool FIRST = MODE == kMgLineFirst, DOT = MODE == kMgLineDot;
+  T acc = (T)0;
+  T* const gq = FIRST ? x : q;   // where g is kept between the two marches
+  const T zero = (T)0;
   const int64_t blk = linear_block();
-  if (blk >= B.m[OTHER] * nchunk) return;
+  if (blk >= B.m[OTHER] * nchunk) return acc;
   const int64_t o = blk / nchunk, c = blk - o * nchunk;
   const int64_t k = c * WIDTH + threadIdx.x;
-  if (k >= B.m[2]) return;
+  if (k >= B.m[2]) return acc;
   const int64_t first = AXIS == 0 ? mg_at(B, 0, o, k) : mg_at(B, o, 0, k);
   const int64_t step = AXIS == 0 ? B.n[1] * B.n[2] : B.n[2];
   const int64_t m = B.m[AXIS];
 
   // ---- forward: g into q
+  // d of one cell: b - q, or b itself
+  auto rhs = [&](int64_t off) -> T {
+    const T bb = b[off];
+    if constexpr (FIRST) {
+      return bb;
+    } else {
+      const T qq = q[off];
+      return bb - qq;
+    }
+  };
   T g;
   {
-    const T d = b[first] - q[first];
+    const T d = rhs(first);
     g = d * inv[first];
-    q[first] = g;
+    gq[first] = g;
   }
   int64_t i = 1;
   for (; i + U <= m; i += U) {
@@ -58,58 +82,93 @@ __global__ __launch_bounds__(WIDTH) void neptune_mg_line_slow(MgBox B, int64_t n
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t off = first + (i + u) * step;
-      const T bb = b[off];
-      const T qq = q[off];
+      dv[u] = rhs(off);
       lv[u] = lo[off];
       iv[u] = inv[off];
-      dv[u] = bb - qq;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const T t = lv[u] * g;
       const T s = dv[u] - t;
       g = s * iv[u];
-      q[first + (i + u) * step] = g;
+      gq[first + (i + u) * step] = g;
     }
   }
   for (; i < m; ++i) {
     const int64_t off = first + i * step;
-    const T d = b[off] - q[off];
+    const T d = rhs(off);
     const T t = lo[off] * g;
     const T s = d - t;
     g = s * inv[off];
-    q[off] = g;
+    gq[off] = g;
   }
 
   // ---- backward and update
+  // x_new of one cell from its e (and, kMgLineDot, its term of b . x_new into the accumulator)
+  auto update = [&](int64_t off, T xv, T bv, T e) {
+    const T xn = xv + e;
+    x[off] = xn;
+    if constexpr (DOT) {
+      const T t = bv * xn;
+      acc += t;
+    }
+  };
   T e = g;
   {
     const int64_t off = first + (m - 1) * step;
-    x[off] = x[off] + e;
+    update(off, FIRST ? zero : x[off], DOT ? b[off] : zero, e);
   }
   i = m - 2;
   for (; i - (U - 1) >= 0; i -= U) {
-    T uv[U], gv[U], xv[U];
+    T uv[U], gv[U], xv[U], bv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t off = first + (i - u) * step;
       uv[u] = up[off];
-      gv[u] = q[off];
-      xv[u] = x[off];
+      gv[u] = gq[off];
+      xv[u] = FIRST ? zero : x[off];
+      bv[u] = DOT ? b[off] : zero;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const T t = uv[u] * e;
       e = gv[u] - t;
-      x[first + (i - u) * step] = xv[u] + e;
+      update(first + (i - u) * step, xv[u], bv[u], e);
     }
   }
   for (; i >= 0; --i) {
     const int64_t off = first + i * step;
     const T t = up[off] * e;
-    e = q[off] - t;
-    x[off] = x[off] + e;
+    e = gq[off] - t;
+    update(off, FIRST ? zero : x[off], DOT ? b[off] : zero, e);
   }
+  return acc;
+}
+
+template <class T, int AXIS, int WIDTH>
+__global__ __launch_bounds__(WIDTH) void neptune_mg_line_slow(MgBox B, int64_t nchunk, T* __restrict__ q, const T* __restrict__ b,
+                                                              const T* __restrict__ lo, const T* __restrict__ inv,
+                                                              const T* __restrict__ up, T* __restrict__ x) {
+  (void)mg_line_slow_body<T, AXIS, WIDTH, kMgLinePlain>(B, nchunk, q, b, lo, inv, up, x);
+}
+// the apply-free stage: reads b, lo, inv, up, writes x on Omega (g on the way up, x on the way down): 7 passes
+template <class T, int AXIS, int WIDTH>
+__global__ __launch_bounds__(WIDTH) void neptune_mg_line_slow_first(MgBox B, int64_t nchunk, const T* __restrict__ b,
+                                                                    const T* __restrict__ lo, const T* __restrict__ inv,
+                                                                    const T* __restrict__ up, T* __restrict__ x) {
+  (void)mg_line_slow_body<T, AXIS, WIDTH, kMgLineFirst>(B, nchunk, (T*)nullptr, b, lo, inv, up, x);
+}
+// the stage with b . x_new: the backward march also loads b, 9 passes; one partial per workgroup of the (possibly folded)
+// grid at its linear index -- the lanes' accumulators on the tree of the monitored launches (monitor_block_sum)
+template <class T, int AXIS, int WIDTH>
+__global__ __launch_bounds__(WIDTH) void neptune_mg_line_slow_dot(MgBox B, int64_t nchunk, T* __restrict__ q, const T* __restrict__ b,
+                                                                  const T* __restrict__ lo, const T* __restrict__ inv,
+                                                                  const T* __restrict__ up, T* __restrict__ x,
+                                                                  T* __restrict__ partials) {
+  __shared__ T lds[4];
+  const T acc = mg_line_slow_body<T, AXIS, WIDTH, kMgLineDot>(B, nchunk, q, b, lo, inv, up, x);
+  const T sum = monitor_block_sum(acc, lds);
+  if (threadIdx.x == 0) partials[linear_block()] = sum;
 }
 
 // ---------------------------------------------------------------- lines along the contiguous axis
@@ -137,19 +196,27 @@ constexpr int kMgLineSeg = 32;
 constexpr int kMgLinePitch = kMgLineSeg + 1;
 constexpr int kMgLineRounds = 16;   // rounds of the stage phase whose loads are issued together
 
-template <class T>
-__global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig(MgBox B, T* __restrict__ q, const T* __restrict__ b,
-                                                                       const T* __restrict__ lo, const T* __restrict__ inv,
-                                                                       const T* __restrict__ up, T* __restrict__ x) {
+// The three forms as for the slow axes.  kMgLineFirst stages b, lo, inv on the way up (d = b), keeps g in x, and on the way
+// down stages two arrays, g and up: the result (+0) + e replaces g in place.  kMgLineDot needs b beside g, up, x on the way
+// down: its loads are issued with the others and held in registers over the solve phase, then staged through the array of
+// up, which that phase has consumed; lane r adds line r's terms b * x_new out of LDS in the order of the backward march.  No
+// fourth array.  -> the lane's accumulator (kMgLineDot; +0 otherwise)
+template <class T, int MODE>
+__device__ __forceinline__ T mg_line_contig_body(const MgBox& B, T* __restrict__ q, const T* __restrict__ b, const T* __restrict__ lo,
+                                                 const T* __restrict__ inv, const T* __restrict__ up, T* __restrict__ x) {
   constexpr int SEG = kMgLineSeg, P = kMgLinePitch, R = kMgLineRounds;
-  __shared__ T s0[kMgLineGroup * P];   // forward: d, then g; backward: g
-  __shared__ T s1[kMgLineGroup * P];   // forward: lo; backward: up
-  __shared__ T s2[kMgLineGroup * P];   // forward: inv; backward: x, then x + e
+  constexpr bool FIRST = MODE == kMgLineFirst, DOT = MODE == kMgLineDot;
+  constexpr int BATCHES = kMgLineGroup / (2 * R);   // batches of R rounds that cover the group's lines
+  __shared__ T s0[kMgLineGroup * P];   // forward: d, then g; backward: g (kMgLineFirst: then (+0) + e)
+  __shared__ T s1[kMgLineGroup * P];   // forward: lo; backward: up (kMgLineDot: then b)
+  __shared__ T s2[kMgLineGroup * P];   // forward: inv; backward: x, then x + e (kMgLineFirst: unused)
   __shared__ int64_t sbase[kMgLineGroup];
+  T acc = (T)0;
+  T* const gq = FIRST ? x : q;         // where g is kept between the two marches
   const int lane = threadIdx.x;
   const int64_t nlines = B.m[0] * B.m[1];
   const int64_t line0 = linear_block() * kMgLineGroup;
-  if (line0 >= nlines) return;   // workgroup-uniform: past the last workgroup of a folded grid
+  if (line0 >= nlines) return acc;   // workgroup-uniform: past the last workgroup of a folded grid
   const int64_t rest = nlines - line0;
   const int nvalid = (int)(rest < (int64_t)kMgLineGroup ? rest : (int64_t)kMgLineGroup);
   const bool owns = lane < nvalid;
@@ -166,7 +233,7 @@ __global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig(MgBox B, 
   T* const r1 = s1 + lane * P;
   T* const r2 = s2 + lane * P;
 
-  // ---- forward: g into q
+  // ---- forward: g into q (kMgLineFirst: into x)
   T carry = (T)0;
   for (int64_t seg0 = 0; seg0 < m; seg0 += SEG) {
     const int len = (int)(m - seg0 < (int64_t)SEG ? m - seg0 : (int64_t)SEG);
@@ -179,7 +246,7 @@ __global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig(MgBox B, 
           const int r = r0 + 2 * j < nvalid ? r0 + 2 * j : nvalid - 1;   // past the group's tail: a line of the group again
           const int64_t off = sbase[r] + seg0 + c;
           bv[j] = b[off];
-          qv[j] = q[off];
+          if constexpr (!FIRST) qv[j] = q[off];
           iv[j] = inv[off];
           lv[j] = reads_lo ? lo[off] : (T)0;
         }
@@ -188,7 +255,8 @@ __global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig(MgBox B, 
           const int r = r0 + 2 * j;
           if (r < nvalid) {
             const int at = r * P + c;
-            const T d = bv[j] - qv[j];
+            T d = bv[j];
+            if constexpr (!FIRST) d = bv[j] - qv[j];
             s0[at] = d;
             s1[at] = lv[j];
             s2[at] = iv[j];
@@ -217,60 +285,145 @@ __global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig(MgBox B, 
     __syncthreads();
     if (c < len) {
 #pragma unroll 4
-      for (int r = half; r < nvalid; r += 2) q[sbase[r] + seg0 + c] = s0[r * P + c];
+      for (int r = half; r < nvalid; r += 2) gq[sbase[r] + seg0 + c] = s0[r * P + c];
     }
     __syncthreads();
   }
 
   // ---- backward and update, from the far end; `carry` becomes e_(i+1)
+  const T zero = (T)0;
   for (int64_t seg0 = ((m - 1) / SEG) * SEG; seg0 >= 0; seg0 -= SEG) {
     const int len = (int)(m - seg0 < (int64_t)SEG ? m - seg0 : (int64_t)SEG);
+    [[maybe_unused]] T bh[DOT ? BATCHES : 1][DOT ? R : 1];   // kMgLineDot: b of this lane's cells, held over the solve phase
     if (c < len) {
       const bool reads_up = seg0 + c < m - 1;   // up_(m-1) is never read
-      for (int r0 = half; r0 < nvalid; r0 += 2 * R) {
-        T gv[R], xv[R], uv[R];
+      if constexpr (DOT) {
 #pragma unroll
-        for (int j = 0; j < R; ++j) {
-          const int r = r0 + 2 * j < nvalid ? r0 + 2 * j : nvalid - 1;
-          const int64_t off = sbase[r] + seg0 + c;
-          gv[j] = q[off];
-          xv[j] = x[off];
-          uv[j] = reads_up ? up[off] : (T)0;
+        for (int bt = 0; bt < BATCHES; ++bt) {
+          const int r0 = half + bt * 2 * R;
+          if (r0 < nvalid) {
+            T gv[R], xv[R], uv[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+              const int r = r0 + 2 * j < nvalid ? r0 + 2 * j : nvalid - 1;
+              const int64_t off = sbase[r] + seg0 + c;
+              gv[j] = q[off];
+              xv[j] = x[off];
+              uv[j] = reads_up ? up[off] : (T)0;
+              bh[bt][j] = b[off];
+            }
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+              const int r = r0 + 2 * j;
+              if (r < nvalid) {
+                const int at = r * P + c;
+                s0[at] = gv[j];
+                s1[at] = uv[j];
+                s2[at] = xv[j];
+              }
+            }
+          }
         }
+      } else {
+        for (int r0 = half; r0 < nvalid; r0 += 2 * R) {
+          T gv[R], xv[R], uv[R];
 #pragma unroll
-        for (int j = 0; j < R; ++j) {
-          const int r = r0 + 2 * j;
-          if (r < nvalid) {
-            const int at = r * P + c;
-            s0[at] = gv[j];
-            s1[at] = uv[j];
-            s2[at] = xv[j];
+          for (int j = 0; j < R; ++j) {
+            const int r = r0 + 2 * j < nvalid ? r0 + 2 * j : nvalid - 1;
+            const int64_t off = sbase[r] + seg0 + c;
+            gv[j] = gq[off];
+            if constexpr (!FIRST) xv[j] = x[off];
+            uv[j] = reads_up ? up[off] : (T)0;
+          }
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            const int r = r0 + 2 * j;
+            if (r < nvalid) {
+              const int at = r * P + c;
+              s0[at] = gv[j];
+              s1[at] = uv[j];
+              if constexpr (!FIRST) s2[at] = xv[j];
+            }
           }
         }
       }
     }
     __syncthreads();
+    T* const rx = FIRST ? r0 : r2;   // the line's x: kMgLineFirst leaves (+0) + e where g was
     if (owns) {
       int cc = len - 1;
       T e = carry;
       if (seg0 + len == m) {
         e = r0[cc];
-        r2[cc] = r2[cc] + e;
+        rx[cc] = (FIRST ? zero : r2[cc]) + e;
         --cc;
       }
       for (; cc >= 0; --cc) {
         const T t = r1[cc] * e;
         e = r0[cc] - t;
-        r2[cc] = r2[cc] + e;
+        rx[cc] = (FIRST ? zero : r2[cc]) + e;
       }
       carry = e;
     }
     __syncthreads();
+    if constexpr (DOT) {
+      // up is consumed: b goes through its array, then lane r adds line r's terms from the segment's far end down
+      if (c < len) {
+#pragma unroll
+        for (int bt = 0; bt < BATCHES; ++bt) {
+          const int r0 = half + bt * 2 * R;
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            const int r = r0 + 2 * j;
+            if (r < nvalid) s1[r * P + c] = bh[bt][j];
+          }
+        }
+      }
+      __syncthreads();
+      if (owns) {
+        for (int cc = len - 1; cc >= 0; --cc) {
+          const T t = r1[cc] * r2[cc];
+          acc += t;
+        }
+      }
+    }
     if (c < len) {
+      const T* const sx = FIRST ? s0 : s2;
 #pragma unroll 4
-      for (int r = half; r < nvalid; r += 2) x[sbase[r] + seg0 + c] = s2[r * P + c];
+      for (int r = half; r < nvalid; r += 2) x[sbase[r] + seg0 + c] = sx[r * P + c];
     }
     __syncthreads();
+  }
+  return acc;
+}
+
+template <class T>
+__global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig(MgBox B, T* __restrict__ q, const T* __restrict__ b,
+                                                                       const T* __restrict__ lo, const T* __restrict__ inv,
+                                                                       const T* __restrict__ up, T* __restrict__ x) {
+  (void)mg_line_contig_body<T, kMgLinePlain>(B, q, b, lo, inv, up, x);
+}
+// the apply-free stage on the contiguous axis: LDS as the plain form's
+template <class T>
+__global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig_first(MgBox B, const T* __restrict__ b, const T* __restrict__ lo,
+                                                                             const T* __restrict__ inv, const T* __restrict__ up,
+                                                                             T* __restrict__ x) {
+  (void)mg_line_contig_body<T, kMgLineFirst>(B, (T*)nullptr, b, lo, inv, up, x);
+}
+// the stage with b . x_new on the contiguous axis: the workgroup is one wave, so its partial is that wave's sum on the
+// shuffle tree of monitor_block_sum (whose sum over one wave this is, bit for bit) and needs no LDS word
+template <class T>
+__global__ __launch_bounds__(kMgLineGroup) void neptune_mg_line_contig_dot(MgBox B, T* __restrict__ q, const T* __restrict__ b,
+                                                                           const T* __restrict__ lo, const T* __restrict__ inv,
+                                                                           const T* __restrict__ up, T* __restrict__ x,
+                                                                           T* __restrict__ partials) {
+  static_assert(kMgLineGroup == kWave, "one wave per workgroup");
+  T v = mg_line_contig_body<T, kMgLineDot>(B, q, b, lo, inv, up, x);
+  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o);
+  if (threadIdx.x == 0) {
+    T r = 0;
+    r += v;
+    partials[linear_block()] = r;
   }
 }
 

@@ -22,8 +22,9 @@
 namespace neptune_hip {
 
 // The set-up: r = b - q on Omega and +0 elsewhere, z = minv * r on Omega and +0 elsewhere through the same select, one partial
-// of sum r * r per workgroup of the (possibly folded) grid
-template <class T>
+// of sum r * r per workgroup of the (possibly folded) grid.  WITH_Z = false (level 0 smooths with line stages):
+// r only -- minv and z are not touched and may be null
+template <class T, bool WITH_Z = true>
 __global__ __launch_bounds__(256) void neptune_mgcg_init(CgBoxParams P, int64_t nchunk, const T* __restrict__ b, const T* __restrict__ q,
                                                          const T* __restrict__ minv, T* __restrict__ r, T* __restrict__ z,
                                                          T* __restrict__ partials) {
@@ -34,19 +35,22 @@ __global__ __launch_bounds__(256) void neptune_mgcg_init(CgBoxParams P, int64_t 
   bool inside;
   if (box_cell(P, nchunk, blk, o, inside)) {
     const T d = b[o] - q[o];
-    const T zd = minv[o] * d;
     const T v = inside ? d : (T)0;
-    const T w = inside ? zd : (T)0;
     r[o] = v;
-    z[o] = w;
+    if constexpr (WITH_Z) {
+      const T zd = minv[o] * d;
+      const T w = inside ? zd : (T)0;
+      z[o] = w;
+    }
     term = v * v;
   }
   block_partial_sums({term}, lds, partials, blk, (int64_t)0);
 }
 
 // x = x + (alpha p), r = r - (alpha q), z = minv * r (the freshly stored r) on all n cells, and one partial of sum r * r per
-// workgroup.  alpha = rz / pq from the scalar block (pcg_alpha)
-template <class T, bool VEC>
+// workgroup.  alpha = rz / pq from the scalar block (pcg_alpha).  WITH_Z = false: x and r only -- reads p, q, x, r, writes x, r,
+// 6 passes; minv and z are not touched and may be null
+template <class T, bool VEC, bool WITH_Z = true>
 __global__ __launch_bounds__(256) void neptune_mgcg_update(int64_t n, const PcgScalars<T>* __restrict__ s, const T* __restrict__ p,
                                                            const T* __restrict__ q, const T* __restrict__ minv, T* __restrict__ x,
                                                            T* __restrict__ r, T* __restrict__ z, T* __restrict__ partials) {
@@ -55,22 +59,22 @@ __global__ __launch_bounds__(256) void neptune_mgcg_update(int64_t n, const PcgS
   T acc = (T)0;
   flat_cells<T, VEC>(n, [&](auto w, int64_t c) {
     constexpr int W = decltype(w)::value;
-    const auto pv = flat_load<W>(p, c), qv = flat_load<W>(q, c), mv = flat_load<W>(minv, c), xv = flat_load<W>(x, c),
-               rv = flat_load<W>(r, c);
-    flat_vec<T, W> xn, rn, zn;
+    const auto pv = flat_load<W>(p, c), qv = flat_load<W>(q, c), xv = flat_load<W>(x, c), rv = flat_load<W>(r, c);
+    flat_vec<T, W> mv, xn, rn, zn;
+    if constexpr (WITH_Z) mv = flat_load<W>(minv, c);
 #pragma unroll
     for (int e = 0; e < W; ++e) {
       const T ap = alpha * pv[e];
       const T aq = alpha * qv[e];
       xn[e] = xv[e] + ap;
       rn[e] = rv[e] - aq;
-      zn[e] = mv[e] * rn[e];
+      if constexpr (WITH_Z) zn[e] = mv[e] * rn[e];
       const T t = rn[e] * rn[e];
       acc += t;
     }
     flat_store<W>(x, c, xn);
     flat_store<W>(r, c, rn);
-    flat_store<W>(z, c, zn);
+    if constexpr (WITH_Z) flat_store<W>(z, c, zn);
   });
   block_partial_sums({acc}, lds, partials, (int64_t)blockIdx.x, (int64_t)gridDim.x);
 }

@@ -5,7 +5,10 @@
 // captured once per call, destroyed when the call returns).  Its own translation unit (builds in seconds, linked into
 // libneptune_hip.so): host code plus the kernels' instantiations.  neptune_hip_mg_line_smooth launches one stage of the line
 // smoother (mg_line_kernels.hpp) alone; neptune_hip_mg_solve_lines is the driver with line stages per level, and
-// neptune_hip_mg_solve is that call without any.
+// neptune_hip_mg_solve is that call without any.  neptune_hip_mgcg_solve_lines is multigrid-preconditioned CG with line stages
+// (DESIGN 3.18): on level 0 the cycle starts with the apply-free form of the stage and ends with the form that yields r . z
+// (neptune_hip_mg_line_first, neptune_hip_mg_line_smooth_dot launch the two alone); neptune_hip_mgcg_solve is that call without
+// lines.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -111,30 +114,62 @@ int prolong_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, 
 // One stage of the line smoother along box axis `axis`.  Axis 2: a one-wave workgroup per 64 lines.  A slow axis: a workgroup
 // per chunk of lanes along axis 2 and index of the other slow axis; 256 lanes wide where that still gives every CU two
 // workgroups, else 64 lanes, so that a small level (a 2-D field's lines along dim 0 have m[2] / width workgroups in all)
-// spreads over the CUs.
-template <class T, int AXIS, int WIDTH>
-void line_slow_launch(const MgBox& B, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x, hipStream_t stream) {
-  const int64_t nchunk = (B.m[2] + WIDTH - 1) / WIDTH;
-  hipLaunchKernelGGL((neptune_mg_line_slow<T, AXIS, WIDTH>), grid_for_blocks(B.m[1 - AXIS] * nchunk), dim3(WIDTH), 0, stream, B, nchunk,
-                     static_cast<T*>(q), static_cast<const T*>(b), static_cast<const T*>(lo), static_cast<const T*>(inv),
-                     static_cast<const T*>(up), static_cast<T*>(x));
-}
-template <class T>
-int line_launch(const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x, hipStream_t stream) {
+// spreads over the CUs.  The grid is the same for the stage's three forms (kMgLinePlain, kMgLineFirst, kMgLineDot).
+struct LineGrid {
+  int width;        // lanes per workgroup
+  int64_t nchunk;   // a slow axis: workgroups along axis 2
+  dim3 grid;
+};
+LineGrid line_grid(const MgBox& B, int axis) {
+  LineGrid L;
   if (axis == 2) {
-    const int64_t groups = (B.m[0] * B.m[1] + kMgLineGroup - 1) / kMgLineGroup;
-    hipLaunchKernelGGL(neptune_mg_line_contig<T>, grid_for_blocks(groups), dim3(kMgLineGroup), 0, stream, B, static_cast<T*>(q),
-                       static_cast<const T*>(b), static_cast<const T*>(lo), static_cast<const T*>(inv), static_cast<const T*>(up),
-                       static_cast<T*>(x));
-    return launched();
+    L.width = kMgLineGroup;
+    L.nchunk = 0;
+    L.grid = grid_for_blocks((B.m[0] * B.m[1] + kMgLineGroup - 1) / kMgLineGroup);
+    return L;
   }
   const bool wide = B.m[1 - axis] * ((B.m[2] + 255) / 256) >= 2 * (int64_t)neptune_hip_cu_count();
+  L.width = wide ? 256 : 64;
+  L.nchunk = (B.m[2] + L.width - 1) / L.width;
+  L.grid = grid_for_blocks(B.m[1 - axis] * L.nchunk);
+  return L;
+}
+// q: unused by kMgLineFirst; partials: one T per workgroup of the grid, kMgLineDot only
+template <class T, int MODE, int AXIS, int WIDTH>
+void line_slow_launch(const MgBox& B, const LineGrid& L, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
+                      void* partials, hipStream_t stream) {
+  const T *bp = static_cast<const T*>(b), *lp = static_cast<const T*>(lo), *ip = static_cast<const T*>(inv), *up_ = static_cast<const T*>(up);
+  if constexpr (MODE == kMgLineFirst)
+    hipLaunchKernelGGL((neptune_mg_line_slow_first<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, bp, lp, ip, up_, static_cast<T*>(x));
+  else if constexpr (MODE == kMgLineDot)
+    hipLaunchKernelGGL((neptune_mg_line_slow_dot<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, static_cast<T*>(q), bp, lp, ip,
+                       up_, static_cast<T*>(x), static_cast<T*>(partials));
+  else
+    hipLaunchKernelGGL((neptune_mg_line_slow<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, static_cast<T*>(q), bp, lp, ip, up_,
+                       static_cast<T*>(x));
+}
+template <class T, int MODE>
+int line_launch(const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x, void* partials,
+                hipStream_t stream) {
+  const LineGrid L = line_grid(B, axis);
+  if (axis == 2) {
+    const T *bp = static_cast<const T*>(b), *lp = static_cast<const T*>(lo), *ip = static_cast<const T*>(inv), *up_ = static_cast<const T*>(up);
+    if constexpr (MODE == kMgLineFirst)
+      hipLaunchKernelGGL(neptune_mg_line_contig_first<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, bp, lp, ip, up_, static_cast<T*>(x));
+    else if constexpr (MODE == kMgLineDot)
+      hipLaunchKernelGGL(neptune_mg_line_contig_dot<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, static_cast<T*>(q), bp, lp, ip, up_,
+                         static_cast<T*>(x), static_cast<T*>(partials));
+    else
+      hipLaunchKernelGGL(neptune_mg_line_contig<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, static_cast<T*>(q), bp, lp, ip, up_,
+                         static_cast<T*>(x));
+    return launched();
+  }
   if (axis == 0) {
-    if (wide) line_slow_launch<T, 0, 256>(B, q, b, lo, inv, up, x, stream);
-    else line_slow_launch<T, 0, 64>(B, q, b, lo, inv, up, x, stream);
+    if (L.width == 256) line_slow_launch<T, MODE, 0, 256>(B, L, q, b, lo, inv, up, x, partials, stream);
+    else line_slow_launch<T, MODE, 0, 64>(B, L, q, b, lo, inv, up, x, partials, stream);
   } else {
-    if (wide) line_slow_launch<T, 1, 256>(B, q, b, lo, inv, up, x, stream);
-    else line_slow_launch<T, 1, 64>(B, q, b, lo, inv, up, x, stream);
+    if (L.width == 256) line_slow_launch<T, MODE, 1, 256>(B, L, q, b, lo, inv, up, x, partials, stream);
+    else line_slow_launch<T, MODE, 1, 64>(B, L, q, b, lo, inv, up, x, partials, stream);
   }
   return launched();
 }
@@ -143,8 +178,18 @@ template <class F64, class F32>
 int by_type(int dtype, F64&& f64, F32&& f32) { return dtype == NEPTUNE_HIP_F64 ? f64() : f32(); }
 int do_line(int dtype, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
             hipStream_t s) {
-  return by_type(dtype, [&] { return line_launch<double>(B, axis, q, b, lo, inv, up, x, s); },
-                 [&] { return line_launch<float>(B, axis, q, b, lo, inv, up, x, s); });
+  return by_type(dtype, [&] { return line_launch<double, kMgLinePlain>(B, axis, q, b, lo, inv, up, x, nullptr, s); },
+                 [&] { return line_launch<float, kMgLinePlain>(B, axis, q, b, lo, inv, up, x, nullptr, s); });
+}
+// the apply-free stage (x from b alone) and the stage that also leaves one partial of b . x_new per workgroup of line_grid
+int do_line_first(int dtype, const MgBox& B, int axis, const void* b, const void* lo, const void* inv, const void* up, void* x, hipStream_t s) {
+  return by_type(dtype, [&] { return line_launch<double, kMgLineFirst>(B, axis, nullptr, b, lo, inv, up, x, nullptr, s); },
+                 [&] { return line_launch<float, kMgLineFirst>(B, axis, nullptr, b, lo, inv, up, x, nullptr, s); });
+}
+int do_line_dot(int dtype, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
+                void* partials, hipStream_t s) {
+  return by_type(dtype, [&] { return line_launch<double, kMgLineDot>(B, axis, q, b, lo, inv, up, x, partials, s); },
+                 [&] { return line_launch<float, kMgLineDot>(B, axis, q, b, lo, inv, up, x, partials, s); });
 }
 int do_smooth(int dtype, const MgBox& B, const void* q, const void* b, const void* minv, void* x, hipStream_t s) {
   return by_type(dtype, [&] { return smooth_launch<double>(B, q, b, minv, x, s); }, [&] { return smooth_launch<float>(B, q, b, minv, x, s); });
@@ -305,6 +350,15 @@ struct Solve {
   }
   // q_l = A_l(x_l)
   int apply(int l) const { return apply_of(l, levels[l].x); }
+  int stages(int l) const { return lines ? lines[l].n_stages : 0; }
+  // stage `st` of level l: q = A(x), then the line kernel
+  int line_stage(int l, int st) const {
+    const neptune_hip_mg_level_t& L = levels[l];
+    const neptune_hip_mg_lines_t& S = lines[l];
+    const int rc = apply(l);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    return do_line(dtype, box[l], S.axis[st] + 3 - rank, L.q, L.b, S.lo[st], S.inv[st], S.up[st], L.x, stream);
+  }
   // `count` sweeps: the point sweep with minv, or on a level with k >= 1 line stages all k, each after its own apply --
   // stages 0 .. k-1, or k-1 .. 0 when `reversed` (the post-sweeps: a cycle of symmetric stages stays symmetric)
   int sweeps(int l, int count, bool reversed = false) const {
@@ -452,9 +506,16 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
   }
   const int64_t init_chunk = (P.n[2] + 255) / 256;
   const dim3 init_grid = grid_for_blocks(P.n[0] * P.n[1] * init_chunk);
-  const FlatGrid upd = flat_grid(n, sizeof(T), {p, q, minv, x, r, z}), dir = flat_grid(n, sizeof(T), {z, p});
+  // k0 >= 1: level 0 smooths with line stages: r is stored without z = minv r, the cycle starts with the
+  // apply-free stage and ends with the stage that yields r . z
+  const int k0 = S.stages(0);
+  const neptune_hip_mg_lines_t* const ln0 = k0 ? &S.lines[0] : nullptr;
+  const int dot_axis = k0 ? ln0->axis[0] + 3 - S.rank : 0;
+  const FlatGrid upd = k0 ? flat_grid(n, sizeof(T), {p, q, x, r}) : flat_grid(n, sizeof(T), {p, q, minv, x, r, z}),
+                 dir = flat_grid(n, sizeof(T), {z, p});
   const RowGrid sd = row_grid(B0);
-  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, grid_blocks(sd.grid)});
+  const int64_t dot_blocks = k0 ? grid_blocks(line_grid(B0, dot_axis).grid) : grid_blocks(sd.grid);
+  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, dot_blocks});
   grow_mgcg_ws(kMgcgScalarBytes + (size_t)most * sizeof(T), (void*)stream);   // no capture is under way: the entry refused one
   PcgScalars<T>* const scal = static_cast<PcgScalars<T>*>(g_mgcg_ws);
   T* const rz0_dev = reinterpret_cast<T*>(static_cast<char*>(g_mgcg_ws) + kMgcgRz0Offset);
@@ -476,7 +537,13 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
   auto rest_of_cycle = [&](int stage) -> int {
     const neptune_hip_mg_level_t& F = S.levels[0];
     const neptune_hip_mg_level_t& Cl = S.levels[1];
-    int rc = S.sweeps(0, a.sweeps - 1);
+    int rc = NEPTUNE_HIP_OK;
+    if (k0) {   // the first pre-sweep: stage 0 without an apply, from z = 0; then its other stages
+      rc = do_line_first(S.dtype, B0, dot_axis, r, ln0->lo[0], ln0->inv[0], ln0->up[0], z, stream);
+      for (int st = 1; st < k0 && rc == NEPTUNE_HIP_OK; ++st) rc = S.line_stage(0, st);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+    }
+    rc = S.sweeps(0, a.sweeps - 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.apply(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
@@ -486,21 +553,30 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = do_prolong(S.dtype, S.mask[0], S.box[0], S.box[1], Cl.x, F.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.sweeps(0, a.sweeps - 1);
+    rc = S.sweeps(0, a.sweeps - 1, true);
+    for (int st = k0 - 1; st >= 1 && rc == NEPTUNE_HIP_OK; --st) rc = S.line_stage(0, st);   // the last post-sweep, down to stage 1
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.apply(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    hipLaunchKernelGGL(neptune_mg_smooth_dot<T>, sd.grid, dim3(256), 0, stream, B0, sd.nchunk, (const T*)q, (const T*)r, minv, z, partials);
-    final_kernel(grid_blocks(sd.grid), stage);
+    if (k0) {
+      rc = do_line_dot(S.dtype, B0, dot_axis, q, r, ln0->lo[0], ln0->inv[0], ln0->up[0], z, partials, stream);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+    } else {
+      hipLaunchKernelGGL(neptune_mg_smooth_dot<T>, sd.grid, dim3(256), 0, stream, B0, sd.nchunk, (const T*)q, (const T*)r, minv, z, partials);
+    }
+    final_kernel(dot_blocks, stage);
     return launched();
   };
 
   // ---- set-up
   for (int l = 1; l < S.n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(S.levels[l].x, 0, box_bytes(S.box[l], sizeof(T)), stream));
   if (!region_is_whole(&L0.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), stream));
+  // with line stages on level 0, z outside Omega_0 is the error equation's rim: zero-filled here, never written again
+  if (k0) NEPTUNE_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)n * sizeof(T), stream));
   int rc = S.apply_of(0, x);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  hipLaunchKernelGGL(neptune_mgcg_init<T>, init_grid, dim3(256), 0, stream, P, init_chunk, b, (const T*)q, minv, r, z, partials);
+  if (k0) hipLaunchKernelGGL((neptune_mgcg_init<T, false>), init_grid, dim3(256), 0, stream, P, init_chunk, b, (const T*)q, minv, r, z, partials);
+  else hipLaunchKernelGGL(neptune_mgcg_init<T>, init_grid, dim3(256), 0, stream, P, init_chunk, b, (const T*)q, minv, r, z, partials);
   final_kernel(grid_blocks(init_grid), kMgcgStartRr);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   double rr = 0.0;
@@ -531,7 +607,8 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
       rc = neptune_hip_dot(S.dtype, &L0.g, q, p, &scal->pq, (void*)stream);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
     }
-    flat_launch(upd, stream, neptune_mgcg_update<T, true>, neptune_mgcg_update<T, false>, n, scal, p, q, minv, x, r, z, partials);
+    if (k0) flat_launch(upd, stream, neptune_mgcg_update<T, true, false>, neptune_mgcg_update<T, false, false>, n, scal, p, q, minv, x, r, z, partials);
+    else flat_launch(upd, stream, neptune_mgcg_update<T, true>, neptune_mgcg_update<T, false>, n, scal, p, q, minv, x, r, z, partials);
     final_kernel((int64_t)upd.blocks, kMgcgRr);
     rc = rest_of_cycle(kMgcgRz);
     if (rc != NEPTUNE_HIP_OK) return late(rc);
@@ -631,6 +708,52 @@ int neptune_hip_mg_line_smooth(int dtype, const neptune_hip_apply_geom_t* g, int
     if (buffers_overlap(q, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
   ensure_init();
   return do_line(dtype, B, axis + 3 - g->rank, q, b, lo, inv, up, x, reinterpret_cast<hipStream_t>(stream));
+}
+
+int neptune_hip_mg_line_first(int dtype, const neptune_hip_apply_geom_t* g, int axis, const void* b, const void* lo, const void* inv,
+                              const void* up, void* x, void* stream) {
+  if (!g || !b || !lo || !inv || !up || !x || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
+  const size_t bytes = box_bytes(B, elem_size(dtype));
+  for (const void* f : {b, lo, inv, up})
+    if (buffers_overlap(x, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  return do_line_first(dtype, B, axis + 3 - g->rank, b, lo, inv, up, x, reinterpret_cast<hipStream_t>(stream));
+}
+
+int neptune_hip_mg_line_smooth_dot(int dtype, const neptune_hip_apply_geom_t* g, int axis, void* q, const void* b, const void* lo,
+                                   const void* inv, const void* up, void* x, void* dot_out, void* stream) {
+  if (!g || !q || !b || !lo || !inv || !up || !x || !dot_out || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
+  const size_t elem = elem_size(dtype), bytes = box_bytes(B, elem);
+  for (const void* f : {(const void*)q, b, lo, inv, up})
+    if (buffers_overlap(x, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  for (const void* f : {b, lo, inv, up})
+    if (buffers_overlap(q, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  if ((uintptr_t)dot_out % elem != 0) return NEPTUNE_HIP_EINVAL;
+  for (const void* f : {(const void*)q, b, lo, inv, up, (const void*)x})
+    if (buffers_overlap(dot_out, elem, f, bytes)) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const int box_axis = axis + 3 - g->rank;
+  const int64_t blocks = grid_blocks(line_grid(B, box_axis).grid);
+  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)blocks * elem, stream)) return NEPTUNE_HIP_EUNSUPPORTED;
+  void* const partials = static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = do_line_dot(dtype, B, box_axis, q, b, lo, inv, up, x, partials, s);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  return by_type(dtype,
+                 [&] {
+                   hipLaunchKernelGGL(neptune_monitor_final<double>, dim3(1), dim3(256), 0, s, static_cast<const double*>(partials), blocks,
+                                      static_cast<double*>(dot_out));
+                   return launched();
+                 },
+                 [&] {
+                   hipLaunchKernelGGL(neptune_monitor_final<float>, dim3(1), dim3(256), 0, s, static_cast<const float*>(partials), blocks,
+                                      static_cast<float*>(dot_out));
+                   return launched();
+                 });
 }
 
 int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
@@ -803,6 +926,14 @@ void neptune_hip_mgcg_counts(int64_t* plain_iters, int64_t* graph_iters, int64_t
 int neptune_hip_mgcg_solve(const neptune_hip_mg_level_t* levels, int n_levels, int dtype, neptune_hip_apply_dot_fn fn_dot, int sweeps,
                            int coarse_sweeps, void* const work[3], int64_t max_iters, int64_t check_every, double tol2, void* trace,
                            void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0, double* rr_last) {
+  return neptune_hip_mgcg_solve_lines(levels, nullptr, n_levels, dtype, fn_dot, sweeps, coarse_sweeps, work, max_iters, check_every, tol2,
+                                      trace, stream, cfg, iters_done, rr0, rr_last);
+}
+
+int neptune_hip_mgcg_solve_lines(const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines, int n_levels, int dtype,
+                                 neptune_hip_apply_dot_fn fn_dot, int sweeps, int coarse_sweeps, void* const work[3], int64_t max_iters,
+                                 int64_t check_every, double tol2, void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg,
+                                 int64_t* iters_done, double* rr0, double* rr_last) {
   g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
   g_mgcg_rz0 = 0.0;
   if (iters_done) *iters_done = 0;
@@ -811,7 +942,7 @@ int neptune_hip_mgcg_solve(const neptune_hip_mg_level_t* levels, int n_levels, i
   // ---- the refusals, before anything touches the device
   if (n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
   Solve S;
-  if (!S.check(levels, n_levels, dtype, sweeps, sweeps, coarse_sweeps, cfg)) return NEPTUNE_HIP_EINVAL;
+  if (!S.check(levels, n_levels, dtype, sweeps, sweeps, coarse_sweeps, cfg, lines)) return NEPTUNE_HIP_EINVAL;
   const size_t elem = elem_size(dtype);
   const size_t bytes0 = box_bytes(S.box[0], elem), bytes1 = box_bytes(S.box[1], elem), trace_bytes = (size_t)(3 * max_iters) * elem;
   const void* const fine[4] = {levels[0].x, levels[0].b, levels[0].q, levels[0].minv};
@@ -821,12 +952,23 @@ int neptune_hip_mgcg_solve(const neptune_hip_mg_level_t* levels, int n_levels, i
     if (!work[i] || (uintptr_t)work[i] % elem != 0) return NEPTUNE_HIP_EINVAL;
     for (int o = 0; o < i; ++o)
       if (buffers_overlap(work[i], bytes0, work[o], bytes0)) return NEPTUNE_HIP_EINVAL;
-    for (int o = 0; o < 4; ++o)
-      if (buffers_overlap(work[i], bytes0, fine[o], bytes0) || buffers_overlap(work[i], bytes0, coarse[o], bytes1)) return NEPTUNE_HIP_EINVAL;
+    for (int o = 0; o < 4; ++o)   // minv of a level with stages may be null
+      if ((fine[o] && buffers_overlap(work[i], bytes0, fine[o], bytes0)) || (coarse[o] && buffers_overlap(work[i], bytes0, coarse[o], bytes1)))
+        return NEPTUNE_HIP_EINVAL;
     if (trace && buffers_overlap(trace, trace_bytes, work[i], bytes0)) return NEPTUNE_HIP_EINVAL;
   }
   for (int o = 0; o < 4 && trace; ++o)
-    if (buffers_overlap(trace, trace_bytes, fine[o], bytes0) || buffers_overlap(trace, trace_bytes, coarse[o], bytes1)) return NEPTUNE_HIP_EINVAL;
+    if ((fine[o] && buffers_overlap(trace, trace_bytes, fine[o], bytes0)) || (coarse[o] && buffers_overlap(trace, trace_bytes, coarse[o], bytes1)))
+      return NEPTUNE_HIP_EINVAL;
+  // the factor fields are read while r, p, z and the trace are written: they may meet none of them
+  for (int l = 0; l < n_levels && lines; ++l)
+    for (int st = 0; st < lines[l].n_stages; ++st)
+      for (const void* f : {lines[l].lo[st], lines[l].inv[st], lines[l].up[st]}) {
+        const size_t fb = box_bytes(S.box[l], elem);
+        for (int i = 0; i < 3; ++i)
+          if (buffers_overlap(f, fb, work[i], bytes0)) return NEPTUNE_HIP_EINVAL;
+        if (trace && buffers_overlap(f, fb, trace, trace_bytes)) return NEPTUNE_HIP_EINVAL;
+      }
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 

@@ -20,7 +20,8 @@ dimensions per level for an axis-aligned anisotropic operator -sum_d w_d u_dd.
 A level may smooth with line stages instead of the point sweep: Level(..., lines=[line_weights(entry, like,
 bounds, axis=d, omega=0.8) for d in (0, 1)]) solves the operator's tridiagonal part along dimension 0, then along dimension
 1, in every sweep -- the repair for anisotropy whose strong direction varies in space.  solve() then runs
-neptune_hip_mg_solve_lines; cg_solve() takes no line stages.
+neptune_hip_mg_solve_lines, and cg_solve(..., lines=True) wraps conjugate gradients around the line-smoothed cycle
+(neptune_hip_mgcg_solve_lines): its iteration count does not move with the anisotropy.
 """
 from __future__ import annotations
 
@@ -387,10 +388,12 @@ def cg_rz0() -> float:
 
 def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coarse_sweeps: int = 8, max_iters: int = 50,
              tol2: float = 0.0, check_every: int = 1, trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
-             work: Optional[Sequence[DeviceField]] = None, stream: Optional[int] = None):
+             work: Optional[Sequence[DeviceField]] = None, stream: Optional[int] = None, lines: bool = False):
     """solve A_0(x) = b by conjugate gradients preconditioned with one V(sweeps, sweeps) cycle over the hierarchy `h`
     (neptune_hip_mgcg_solve; at least two levels, sweeps >= 1).  Level 0's minv must be finite on its whole box
-    (jacobi_weights puts +0 outside Omega).  x: initial guess in, solution out; its cells outside Omega_0 are boundary data
+    (jacobi_weights puts +0 outside Omega).  lines=True: a hierarchy whose levels have line stages runs
+    neptune_hip_mgcg_solve_lines -- a level with stages needs no minv, level 0 included; without the keyword
+    such a hierarchy is refused (ValueError).  A hierarchy without stages behaves the same either way.  x: initial guess in, solution out; its cells outside Omega_0 are boundary data
     and are never changed.  The loop stops when r . r <= tol2 (checked every `check_every` iterations) or after max_iters
     iterations.  dot: level 0's dot entry (LoweredModule.dot_entry), "auto": level 0's entry's own if it has one (built-in
     bodies do), "fallback" or None: a plain launch and a separate dot product per iteration.  work: three fields like x for
@@ -404,9 +407,9 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
         raise ValueError("multigrid.cg_solve: x and b must have the box and the element type of level 0")
     if len(h) < 2:
         raise ValueError("multigrid.cg_solve: at least two levels (one level is apply.cg_solve with minv)")
-    if h.has_lines:
+    if h.has_lines and not lines:
         raise ValueError("multigrid.cg_solve: the hierarchy has line stages; neptune_hip_mgcg_solve smooths with point Jacobi "
-                         "only (its fused first and last sweeps on level 0)")
+                         "only (its fused first and last sweeps on level 0): pass lines=True for neptune_hip_mgcg_solve_lines")
     if work is None:
         work = [DeviceField.empty_like(x) for _ in range(3)]
     entry = h.levels[0].entry
@@ -421,10 +424,12 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
     tr = torch.zeros(3 * max(int(max_iters), 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
     warr = (C.c_void_p * 3)(*[f.ptr for f in work])
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-    rc = lib.neptune_hip_mgcg_solve(arr, len(h), h.dtype, fn_dot, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2,
-                                    tr.data_ptr() if trace else None, st, C.byref(cfg) if cfg is not None else None,
-                                    C.byref(done), C.byref(rr0), C.byref(last))
-    _capi.check(rc, "neptune_hip_mgcg_solve")
+    rest = (fn_dot, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
+            C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    if h.has_lines:
+        _capi.check(lib.neptune_hip_mgcg_solve_lines(arr, h._line_structs(), len(h), h.dtype, *rest), "neptune_hip_mgcg_solve_lines")
+    else:
+        _capi.check(lib.neptune_hip_mgcg_solve(arr, len(h), h.dtype, *rest), "neptune_hip_mgcg_solve")
     del keep
     if trace:
         return done.value, rr0.value, last.value, tr.cpu().numpy()[:3 * done.value].reshape(-1, 3)
@@ -470,6 +475,30 @@ def line_smooth(level: Level, stage: LineStage, q: DeviceField, b: DeviceField, 
     st = current_stream_ptr() if stream is None else stream
     _capi.check(_capi.load().neptune_hip_mg_line_smooth(x.dtype, C.byref(level.geom), int(stage.axis), q.ptr, b.ptr, stage.lo.ptr,
                                                         stage.inv.ptr, stage.up.ptr, x.ptr, st), "neptune_hip_mg_line_smooth")
+
+
+def line_first(level: Level, stage: LineStage, b: DeviceField, x: DeviceField, stream: Optional[int] = None) -> None:
+    """the apply-free line stage on `level`: the values of line_smooth on q = +0, x = +0, from b alone
+    (neptune_hip_mg_line_first); x on Omega is overwritten without being read; asynchronous"""
+    st = current_stream_ptr() if stream is None else stream
+    _capi.check(_capi.load().neptune_hip_mg_line_first(x.dtype, C.byref(level.geom), int(stage.axis), b.ptr, stage.lo.ptr, stage.inv.ptr,
+                                                       stage.up.ptr, x.ptr, st), "neptune_hip_mg_line_first")
+
+
+def line_smooth_dot(level: Level, stage: LineStage, q: DeviceField, b: DeviceField, x: DeviceField, dot_out=None,
+                    stream: Optional[int] = None):
+    """line_smooth(level, stage, q, b, x) and sum over Omega of b * x_new out of the same launch
+    (neptune_hip_mg_line_smooth_dot).  dot_out: a one-element device tensor of x's element type to receive the sum
+    (asynchronous; -> None), or None: blocking, -> the sum"""
+    import torch
+    st = current_stream_ptr() if stream is None else stream
+    dst = dot_out if dot_out is not None else torch.zeros(1, dtype=x.tensor.dtype, device=x.tensor.device)
+    _capi.check(_capi.load().neptune_hip_mg_line_smooth_dot(x.dtype, C.byref(level.geom), int(stage.axis), q.ptr, b.ptr, stage.lo.ptr,
+                                                            stage.inv.ptr, stage.up.ptr, x.ptr, dst.data_ptr(), st),
+                "neptune_hip_mg_line_smooth_dot")
+    if dot_out is not None:
+        return None
+    return float(dst.item())
 
 
 def restrict(fine: Level, coarse: Level, b_fine: DeviceField, q_fine: DeviceField, b_coarse: DeviceField, x_coarse: DeviceField,
