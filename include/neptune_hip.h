@@ -726,6 +726,56 @@ int neptune_hip_mgcg_solve_lines(const neptune_hip_mg_level_t *levels, const nep
                                  void *const work[3], int64_t max_iters, int64_t check_every, double tol2, void *trace,
                                  void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0,
                                  double *rr_last);
+/* MIXED PRECISION: conjugate gradients in D = f64 around the preconditioner's V-cycle in S = f32.  Only
+ * (dtype_outer, dtype_inner) = (NEPTUNE_HIP_F64, NEPTUNE_HIP_F32) is accepted.  Arithmetic as everywhere: one rounding per
+ * operation, no FMA, every intermediate a named temporary, sums on the fixed tree of the monitored launches, no atomics;
+ * operations on D values round in D, operations on S values round in S.  The two conversions:
+ *   narrow(v)  D -> S, one rounding to nearest even, as the cast (float) gives it: a finite value beyond f32's range becomes
+ *              +-inf, a result in f32's subnormal range is kept (the kernels run in the default mode, which preserves f32
+ *              subnormals), -0 and NaN pass through
+ *   widen(v)   S -> D, exact
+ * No scaling of r is applied: A CALLER WHOSE RESIDUAL LEAVES f32'S RANGE (about 1e-45 .. 3e38 in magnitude) MUST SCALE THE
+ * SYSTEM -- components that narrow to +-inf poison the cycle, components that narrow to 0 are not preconditioned.
+ * outer: ONE level in D that carries the operator (fn / body, g, in_rest), x (the unknown), b (the right-hand side) and q; its
+ * minv and rscale are not read.  fn_dot: the outer operator's dot-monitored entry, or NULL.  levels[0 .. n_levels), lines:
+ * exactly a hierarchy of neptune_hip_mg_solve_lines in S, n_levels >= 2; level 0 has its own f32 operator (the same operator
+ * lowered at f32, or an f32 built-in body); level 0's b is the narrowed residual r32 and level 0's x is z32, both
+ * caller-supplied work fields.  levels[0].g must describe the same box and the same Omega as outer->g.  work[2] = r, p in D,
+ * in level 0's box.
+ * THE PRECONDITIONER z32 = M32(r32) is the preconditioner of neptune_hip_mgcg_solve word for word, run in S on (z32, r32):
+ * its first pre-sweep is z32 = minv_0 * r32 on every cell, formed by the kernel that stores the residual; its last post-sweep
+ * is neptune_hip_mg_smooth_dot_wide's kernel and yields r . z = sum over Omega_0 of widen(r32) * widen(z32_new) -- each
+ * term exact in D, partials and root in D.  So rz = r32 . M32(r32): positive for a symmetric positive definite M32 whatever
+ * the narrowing did, at no pass over the f64 r.
+ *   set-up     x_l for l >= 1 zero-filled once; q zero-filled once where the outer launch region is not the whole box.
+ *              1. q = A(x), a plain launch in D   2. on Omega: r = b - q in D, outside +0; r32 = narrow(r), z32 = minv_0 * r32
+ *              in S, +0 outside Omega for both through the same select; out of that launch rr_0 = sum r * r in D
+ *              3. rr_0 is read back: rr_0 <= tol2 or max_iters == 0 returns with zero iterations (r, r32, z32 hold what step
+ *              2 stored)   4. the rest of M32, which yields rz_0   5. p = widen(z32), whole box
+ *   iteration  1. q = A(p) and pq = sum_Omega q * p out of the outer operator's dot-monitored launch
+ *              2. alpha = rz / pq in D;  on all cells x = x + (alpha p), r = r - (alpha q), r32 = narrow(r) from the new r,
+ *                 z32 = minv_0 * r32; out of that launch rr' = sum r * r in D
+ *              3. the rest of M32, which yields rz'
+ *              4. beta = rz' / rz;  on all cells p = widen(z32) + (beta p);  rz <- rz', rr <- rr'
+ * As in neptune_hip_mgcg_solve: the breakdown rule (rz == 0 or pq == 0 gives alpha = beta = 0), the stop rule on the f64 rr,
+ * check_every, trace (a DEVICE pointer to 3 * max_iters values of D), the fallback of step 1, the replay of one captured
+ * iteration as a linear graph with its plain-launch fallback and NEPTUNE_HIP_MG_GRAPH=0, and cfg (the OUTER operator's launch
+ * configuration).  neptune_hip_mgcg_rz0 and neptune_hip_mgcg_counts report on this entry as well.
+ * LINE STAGES on levels >= 1 run through the unchanged cycle.  Stages on level 0: NEPTUNE_HIP_EUNSUPPORTED, nothing launched.
+ * NEPTUNE_HIP_EINVAL, nothing launched: everything neptune_hip_mgcg_solve_lines refuses that applies; a dtype pair other than
+ * (f64, f32); outer->g and levels[0].g disagreeing in rank, box or Omega; a null or misaligned work[i] or trace; any overlap
+ * among outer's x, b, q, r, p, the trace and level 0's and level 1's x, b, q, minv; a factor field that overlaps a field the
+ * solve writes in D; a stream that is being captured. */
+int neptune_hip_mgcg_solve_mixed(const neptune_hip_mg_level_t *outer, int dtype_outer, neptune_hip_apply_dot_fn fn_dot,
+                                 const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines, int n_levels,
+                                 int dtype_inner, int sweeps, int coarse_sweeps, void *const work[2], int64_t max_iters,
+                                 int64_t check_every, double tol2, void *trace, void *stream,
+                                 const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0, double *rr_last);
+/* neptune_hip_mg_smooth_dot with a wide sum, alone: the sweep in `dtype` exactly as neptune_hip_mg_smooth (the same bits in
+ * x), and *dot_out = sum over Omega of widen(b) * widen(x_new) in `dtype_sum` -- each term exact.  (dtype, dtype_sum) =
+ * (NEPTUNE_HIP_F32, NEPTUNE_HIP_F64) only.  dot_out: a DEVICE pointer to one double; otherwise as neptune_hip_mg_smooth_dot. */
+int neptune_hip_mg_smooth_dot_wide(int dtype, int dtype_sum, const neptune_hip_apply_geom_t *g, const void *q, const void *b,
+                                   const void *minv, void *x, void *dot_out, void *stream);
 /* rz_0 = r . M(r) after the set-up of the last neptune_hip_mgcg_solve call of this process (0 when it was refused or ran
  * no iteration): with *rr0 and the trace, every scalar the recurrences used, so that a run can be replayed */
 double neptune_hip_mgcg_rz0(void);

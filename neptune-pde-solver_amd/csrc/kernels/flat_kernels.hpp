@@ -42,6 +42,58 @@ __device__ __forceinline__ void flat_store(T* p, int64_t cell, flat_vec<T, W> v)
   else __builtin_nontemporal_store(v, reinterpret_cast<flat_vec<T, W>*>(p + cell));
 }
 
+// W cells that may span more than one 16-byte access (a group of 4 doubles next to 4 floats, mgcg_mixed_kernels.hpp): as
+// 16-byte pieces, so that the operand needs 16-byte alignment only; W cells of at most 16 bytes: flat_load / flat_store
+template <int W, class T>
+__device__ __forceinline__ flat_vec<T, W> flat_load_wide(const T* p, int64_t cell) {
+  constexpr int PK = 16 / (int)sizeof(T);
+  if constexpr (W <= PK) {
+    return flat_load<W>(p, cell);
+  } else {
+    static_assert(W % PK == 0, "whole 16-byte pieces");
+    flat_vec<T, W> v;
+#pragma unroll
+    for (int h = 0; h < W / PK; ++h) {
+      const auto piece = flat_load<PK>(p, cell + h * PK);
+#pragma unroll
+      for (int e = 0; e < PK; ++e) v[h * PK + e] = piece[e];
+    }
+    return v;
+  }
+}
+template <int W, class T>
+__device__ __forceinline__ void flat_store_wide(T* p, int64_t cell, flat_vec<T, W> v) {
+  constexpr int PK = 16 / (int)sizeof(T);
+  if constexpr (W <= PK) {
+    flat_store<W>(p, cell, v);
+  } else {
+    static_assert(W % PK == 0, "whole 16-byte pieces");
+#pragma unroll
+    for (int h = 0; h < W / PK; ++h) {
+      flat_vec<T, PK> piece;
+#pragma unroll
+      for (int e = 0; e < PK; ++e) piece[e] = v[h * PK + e];
+      flat_store<PK>(p, cell + h * PK, piece);
+    }
+  }
+}
+
+// flat_cells for operands of more than one element size: the 16-byte form takes one group of VK cells per lane whatever the
+// types (the kernel loads each operand with flat_load_wide), the tail and the grid-stride form are flat_cells'
+template <int VK, bool VEC, class F>
+__device__ __forceinline__ void flat_cells_group(int64_t n, F&& body) {
+  if constexpr (VEC) {
+    const int64_t nv = n / VK;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < nv) body(flat_width<VK>{}, i * VK);
+    if (i == 0)
+      for (int64_t j = nv * VK; j < n; ++j) body(flat_width<1>{}, j);
+  } else {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) body(flat_width<1>{}, i);
+  }
+}
+
 template <class T, bool VEC, class F>
 __device__ __forceinline__ void flat_cells(int64_t n, F&& body) {
   if constexpr (VEC) {
@@ -69,6 +121,8 @@ inline FlatGrid flat_grid(int64_t n, size_t elem, std::initializer_list<const vo
   const int64_t want = (n + 255) / 256;
   return {false, (uint32_t)(want < 256 * 32 ? want : 256 * 32)};
 }
+// the grid of a flat_cells_group<vk> kernel: groups of `vk` cells whatever the operands' element sizes
+inline FlatGrid flat_grid_group(int64_t n, int vk, std::initializer_list<const void*> ptrs) { return flat_grid(n, (size_t)(16 / vk), ptrs); }
 // the two instantiations of one kernel and ONE argument list (converted to the kernel's parameter types): whichever form
 // the grid asks for
 template <class... P, class... A>

@@ -8,7 +8,8 @@
 // neptune_hip_mg_solve is that call without any.  neptune_hip_mgcg_solve_lines is multigrid-preconditioned CG with line stages
 // (DESIGN 3.18): on level 0 the cycle starts with the apply-free form of the stage and ends with the form that yields r . z
 // (neptune_hip_mg_line_first, neptune_hip_mg_line_smooth_dot launch the two alone); neptune_hip_mgcg_solve is that call without
-// lines.
+// lines.  neptune_hip_mgcg_solve_mixed is that solver with x, b, r, p, q and the scalars in f64 around the cycle in f32
+// (mgcg_mixed_kernels.hpp); neptune_hip_mg_smooth_dot_wide launches its last sweep, the one with the wide sum, alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -22,6 +23,7 @@
 #include "../kernels/multigrid_kernels.hpp"
 #include "../kernels/mg_line_kernels.hpp"
 #include "../kernels/mgcg_kernels.hpp"
+#include "../kernels/mgcg_mixed_kernels.hpp"
 
 using namespace neptune_hip;
 
@@ -484,6 +486,78 @@ struct MgcgArgs {
   double* rr0;
   double* rr_last;
 };
+// The loop of an MGCG solve once its set-up has run, shared by the one-type and the mixed driver: blocks of check_every
+// iterations, the first one as plain launches, then -- when at least two more may follow -- ONE capture of `iteration` as a
+// linear graph that every later iteration replays; after each block read_rr(first, &rr) reads rr back (the block's one
+// synchronise; `first`: rz_0 into g_mgcg_rz0 as well).  `fused` is the iteration's own flag (whether step 1 is the
+// dot-monitored launch): what refused under capture may well run outside, so a failed capture restores it.
+template <class Iteration, class ReadRr>
+int mgcg_iterations(hipStream_t stream, const MgcgArgs& a, bool& fused, Iteration&& iteration, ReadRr&& read_rr) {
+  double rr = 0.0;
+  struct Graph {    // this call's graph of one iteration
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool fallback = false;
+    ~Graph() {
+      if (exec) (void)hipGraphExecDestroy(exec);
+      if (graph) (void)hipGraphDestroy(graph);
+    }
+  } G;
+  // One iteration as a graph: captured on the stream (nothing runs), instantiated; on any refusal under capture the graph is
+  // discarded and the call goes on with plain launches
+  auto capture = [&]() {
+    if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return; }
+    const bool was_fused = fused;
+    const int rc = iteration();
+    hipGraph_t graph = nullptr;
+    if (hipStreamEndCapture(stream, &graph) != hipSuccess) { (void)hipGetLastError(); graph = nullptr; }
+    if (rc != NEPTUNE_HIP_OK || !graph) {
+      if (graph) (void)hipGraphDestroy(graph);
+      fused = was_fused;   // what refused under capture may well run outside
+      return;
+    }
+    if (hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipGraphDestroy(graph);
+      G.exec = nullptr;
+      fused = was_fused;
+      return;
+    }
+    G.graph = graph;
+    G.fallback = !fused;
+  };
+
+  const bool graphs = graph_path_enabled();
+  bool capture_tried = false, rz0_read = false;
+  int64_t done = 0;
+  while (done < a.max_iters) {
+    const int64_t block = a.check_every < a.max_iters - done ? a.check_every : a.max_iters - done;
+    for (int64_t c = 0; c < block; ++c, ++done) {
+      if (done > 0 && graphs && !capture_tried && a.max_iters - done >= 2) {
+        capture_tried = true;
+        capture();
+      }
+      if (done > 0 && G.exec) {
+        NEPTUNE_HIP_CHECK(hipGraphLaunch(G.exec, stream));
+        ++g_mgcg_counts[1];
+        if (G.fallback) ++g_mgcg_counts[2];
+      } else {
+        const int rc = iteration();
+        if (rc != NEPTUNE_HIP_OK) return late(rc);
+        ++g_mgcg_counts[0];
+        if (!fused) ++g_mgcg_counts[2];
+      }
+      if (a.iters_done) *a.iters_done = done + 1;
+    }
+    read_rr(!rz0_read, &rr);
+    rz0_read = true;
+    ++g_mgcg_counts[3];
+    if (a.rr_last) *a.rr_last = rr;
+    if (rr <= a.tol2) break;   // false for a NaN: such a solve runs to max_iters
+  }
+  return NEPTUNE_HIP_OK;
+}
+
 template <class T>
 int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const MgcgArgs& a) {
   const hipStream_t stream = S.stream;
@@ -616,69 +690,141 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
     return launched();
   };
 
-  struct Graph {    // this call's graph of one iteration
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool fallback = false;
-    ~Graph() {
-      if (exec) (void)hipGraphExecDestroy(exec);
-      if (graph) (void)hipGraphDestroy(graph);
-    }
-  } G;
-  // One iteration as a graph: captured on the stream (nothing runs), instantiated; on any refusal under capture the graph is
-  // discarded and the call goes on with plain launches
-  auto capture = [&]() {
-    if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return; }
-    const bool was_fused = fused;
-    const int rc = iteration();
-    hipGraph_t graph = nullptr;
-    if (hipStreamEndCapture(stream, &graph) != hipSuccess) { (void)hipGetLastError(); graph = nullptr; }
-    if (rc != NEPTUNE_HIP_OK || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      fused = was_fused;   // what refused under capture may well run outside
-      return;
-    }
-    if (hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipGraphDestroy(graph);
-      G.exec = nullptr;
-      fused = was_fused;
-      return;
-    }
-    G.graph = graph;
-    G.fallback = !fused;
+  return mgcg_iterations(stream, a, fused, iteration, [&](bool first, double* out) {
+    if (first) read(&scal->rr, out, rz0_dev, &g_mgcg_rz0);
+    else read(&scal->rr, out);
+  });
+}
+
+// ---------------------------------------------------------------- mixed precision: CG in D around a cycle in S
+// what neptune_hip_mgcg_solve_mixed is once its arguments are checked.  S: the solve over the inner hierarchy in S, whose
+// level 0 carries (z32, r32) for (x, b); O: the outer operator in D with the caller's x, b and q; a.work = r, p in D; cfg: the
+// outer operator's launch configuration (nullptr unless the caller set anything).  Level 0
+// has no line stages (the entry refused them).
+template <class D, class Sx>
+int mgcg_solve_mixed_typed(const Solve& S, const neptune_hip_mg_level_t& O, const neptune_hip_launch_cfg_t* cfg, const MgcgArgs& a) {
+  const hipStream_t stream = S.stream;
+  const MgBox& B0 = S.box[0];
+  const neptune_hip_mg_level_t& F = S.levels[0];
+  const neptune_hip_mg_level_t& Cl = S.levels[1];
+  const int64_t n = B0.n[0] * B0.n[1] * B0.n[2];
+  D* const x = static_cast<D*>(O.x);
+  const D* const b = static_cast<const D*>(O.b);
+  D* const q = static_cast<D*>(O.q);
+  D* const r = static_cast<D*>(a.work[0]);
+  D* const p = static_cast<D*>(a.work[1]);
+  D* const tr = static_cast<D*>(a.trace);
+  const Sx* const minv = static_cast<const Sx*>(F.minv);
+  Sx* const r32 = static_cast<Sx*>(F.b);
+  Sx* const z32 = static_cast<Sx*>(F.x);
+
+  CgBoxParams P;
+  for (int d = 0; d < 3; ++d) {
+    P.n[d] = B0.n[d];
+    P.lo[d] = B0.lo[d];
+    P.hi[d] = B0.lo[d] + B0.m[d];
+  }
+  const int64_t init_chunk = (P.n[2] + 255) / 256;
+  const dim3 init_grid = grid_for_blocks(P.n[0] * P.n[1] * init_chunk);
+  const FlatGrid upd = flat_grid_group(n, kMixedGroup, {p, q, minv, x, r, r32, z32}), dir = flat_grid_group(n, kMixedGroup, {z32, p});
+  const RowGrid sd = row_grid(B0);
+  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, grid_blocks(sd.grid)});
+  grow_mgcg_ws(kMgcgScalarBytes + (size_t)most * sizeof(D), (void*)stream);   // no capture is under way: the entry refused one
+  PcgScalars<D>* const scal = static_cast<PcgScalars<D>*>(g_mgcg_ws);
+  D* const rz0_dev = reinterpret_cast<D*>(static_cast<char*>(g_mgcg_ws) + kMgcgRz0Offset);
+  D* const partials = reinterpret_cast<D*>(static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes);
+  auto final_kernel = [&](int64_t count, int stage) {
+    hipLaunchKernelGGL(neptune_mgcg_final<D>, dim3(1), dim3(256), 0, stream, (const D*)partials, count, scal, rz0_dev, tr, a.max_iters, stage);
+  };
+  auto read = [&](const D* dev, double* host, const D* dev2 = nullptr, double* host2 = nullptr) {
+    D h = 0, h2 = 0;
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, dev, sizeof(D), hipMemcpyDeviceToHost, stream));
+    if (dev2) NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h2, dev2, sizeof(D), hipMemcpyDeviceToHost, stream));
+    NEPTUNE_HIP_CHECK(hipStreamSynchronize(stream));
+    *host = (double)h;
+    if (dev2) *host2 = (double)h2;
+  };
+  // q = A(in0) by the outer operator, a plain launch in D
+  auto outer_inputs = [&](const void* in0, const void** ins) {
+    ins[0] = in0;
+    for (int i = 1; i < O.g.num_inputs; ++i) ins[i] = O.in_rest[i - 1];
+  };
+  auto outer_apply = [&](const void* in0) -> int {
+    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+    outer_inputs(in0, ins);
+    return O.fn ? O.fn(&O.g, ins, q, (void*)stream, cfg) : neptune_hip_apply_builtin(O.body, &O.g, ins, q, (void*)stream, cfg);
+  };
+  // the rest of M32: the cycle in S on A z32 = r32 after its first pre-sweep (z32 = minv r32, stored with r32); its last
+  // post-sweep yields r32 . z32 in D, which `stage` of the bookkeeping kernel takes
+  auto rest_of_cycle = [&](int stage) -> int {
+    int rc = S.sweeps(0, a.sweeps - 1);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.apply(0);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = do_restrict(S.dtype, S.mask[0], S.box[0], S.box[1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.cycle(1);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = do_prolong(S.dtype, S.mask[0], S.box[0], S.box[1], Cl.x, F.x, stream);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.sweeps(0, a.sweeps - 1, true);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = S.apply(0);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    hipLaunchKernelGGL((neptune_mg_smooth_dot_wide<D, Sx>), sd.grid, dim3(256), 0, stream, B0, sd.nchunk, static_cast<const Sx*>(F.q),
+                       (const Sx*)r32, minv, z32, partials);
+    final_kernel(grid_blocks(sd.grid), stage);
+    return launched();
   };
 
-  const bool graphs = graph_path_enabled();
-  bool capture_tried = false, rz0_read = false;
-  int64_t done = 0;
-  while (done < a.max_iters) {
-    const int64_t block = a.check_every < a.max_iters - done ? a.check_every : a.max_iters - done;
-    for (int64_t c = 0; c < block; ++c, ++done) {
-      if (done > 0 && graphs && !capture_tried && a.max_iters - done >= 2) {
-        capture_tried = true;
-        capture();
-      }
-      if (done > 0 && G.exec) {
-        NEPTUNE_HIP_CHECK(hipGraphLaunch(G.exec, stream));
-        ++g_mgcg_counts[1];
-        if (G.fallback) ++g_mgcg_counts[2];
-      } else {
-        rc = iteration();
-        if (rc != NEPTUNE_HIP_OK) return late(rc);
-        ++g_mgcg_counts[0];
-        if (!fused) ++g_mgcg_counts[2];
-      }
-      if (a.iters_done) *a.iters_done = done + 1;
+  // ---- set-up
+  for (int l = 1; l < S.n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(S.levels[l].x, 0, box_bytes(S.box[l], sizeof(Sx)), stream));
+  if (!region_is_whole(&O.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(D), stream));
+  int rc = outer_apply(x);
+  if (rc != NEPTUNE_HIP_OK) return rc;
+  hipLaunchKernelGGL((neptune_mgcg_init_mixed<D, Sx>), init_grid, dim3(256), 0, stream, P, init_chunk, b, (const D*)q, minv, r, r32, z32, partials);
+  final_kernel(grid_blocks(init_grid), kMgcgStartRr);
+  NEPTUNE_HIP_CHECK(hipGetLastError());
+  double rr = 0.0;
+  read(&scal->rr, &rr);
+  if (a.rr0) *a.rr0 = rr;
+  if (a.rr_last) *a.rr_last = rr;
+  if (rr <= a.tol2 || a.max_iters == 0) return NEPTUNE_HIP_OK;
+  rc = rest_of_cycle(kMgcgStartRz);
+  if (rc != NEPTUNE_HIP_OK) return late(rc);
+  flat_launch(dir, stream, neptune_mgcg_direction_mixed<D, Sx, true, true>, neptune_mgcg_direction_mixed<D, Sx, false, true>, n, scal, z32, p);
+
+  // ---- one iteration; `fused` as in mgcg_solve_typed, on the outer operator
+  bool fused = O.fn ? a.fn_dot != nullptr : true;
+  auto iteration = [&]() -> int {
+    int rc;
+    if (fused) {
+      const void* ins[NEPTUNE_HIP_MAX_INPUTS];
+      outer_inputs(p, ins);
+      rc = O.fn ? a.fn_dot(&O.g, ins, q, &scal->pq, (void*)stream, cfg)
+                : neptune_hip_apply_builtin_dot(O.body, &O.g, ins, q, &scal->pq, (void*)stream, cfg);
+      if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
+      else if (rc != NEPTUNE_HIP_OK) return rc;
     }
-    if (!rz0_read) read(&scal->rr, &rr, rz0_dev, &g_mgcg_rz0);
-    else read(&scal->rr, &rr);
-    rz0_read = true;
-    ++g_mgcg_counts[3];
-    if (a.rr_last) *a.rr_last = rr;
-    if (rr <= a.tol2) break;   // false for a NaN: such a solve runs to max_iters
-  }
-  return NEPTUNE_HIP_OK;
+    if (!fused) {
+      rc = outer_apply(p);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
+      rc = neptune_hip_dot(NEPTUNE_HIP_F64, &O.g, q, p, &scal->pq, (void*)stream);
+      if (rc != NEPTUNE_HIP_OK) return late(rc);
+    }
+    flat_launch(upd, stream, neptune_mgcg_update_mixed<D, Sx, true>, neptune_mgcg_update_mixed<D, Sx, false>, n, scal, p, q, minv, x, r, r32, z32,
+                partials);
+    final_kernel((int64_t)upd.blocks, kMgcgRr);
+    rc = rest_of_cycle(kMgcgRz);
+    if (rc != NEPTUNE_HIP_OK) return late(rc);
+    flat_launch(dir, stream, neptune_mgcg_direction_mixed<D, Sx, true>, neptune_mgcg_direction_mixed<D, Sx, false>, n, scal, z32, p);
+    return launched();
+  };
+
+  return mgcg_iterations(stream, a, fused, iteration, [&](bool first, double* out) {
+    if (first) read(&scal->rr, out, rz0_dev, &g_mgcg_rz0);
+    else read(&scal->rr, out);
+  });
 }
 
 }  // namespace
@@ -912,6 +1058,92 @@ int neptune_hip_mg_smooth_dot(int dtype, const neptune_hip_apply_geom_t* g, cons
                                       static_cast<float*>(dot_out));
                    return launched();
                  });
+}
+
+int neptune_hip_mg_smooth_dot_wide(int dtype, int dtype_sum, const neptune_hip_apply_geom_t* g, const void* q, const void* b,
+                                   const void* minv, void* x, void* dot_out, void* stream) {
+  if (!g || !q || !b || !minv || !x || !dot_out || dtype != NEPTUNE_HIP_F32 || dtype_sum != NEPTUNE_HIP_F64) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B)) return NEPTUNE_HIP_EINVAL;
+  const size_t bytes = box_bytes(B, sizeof(float));
+  if (buffers_overlap(x, bytes, q, bytes) || buffers_overlap(x, bytes, b, bytes) || buffers_overlap(x, bytes, minv, bytes)) return NEPTUNE_HIP_EINVAL;
+  if ((uintptr_t)dot_out % sizeof(double) != 0) return NEPTUNE_HIP_EINVAL;
+  for (const void* f : {q, b, minv, (const void*)x})
+    if (buffers_overlap(dot_out, sizeof(double), f, bytes)) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const RowGrid r = row_grid(B);
+  const int64_t blocks = grid_blocks(r.grid);
+  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)blocks * sizeof(double), stream)) return NEPTUNE_HIP_EUNSUPPORTED;
+  double* const partials = reinterpret_cast<double*>(static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes);
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL((neptune_mg_smooth_dot_wide<double, float>), r.grid, dim3(256), 0, s, B, r.nchunk, static_cast<const float*>(q),
+                     static_cast<const float*>(b), static_cast<const float*>(minv), static_cast<float*>(x), partials);
+  hipLaunchKernelGGL(neptune_monitor_final<double>, dim3(1), dim3(256), 0, s, (const double*)partials, blocks, static_cast<double*>(dot_out));
+  return launched();
+}
+
+int neptune_hip_mgcg_solve_mixed(const neptune_hip_mg_level_t* outer, int dtype_outer, neptune_hip_apply_dot_fn fn_dot,
+                                 const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines, int n_levels, int dtype_inner,
+                                 int sweeps, int coarse_sweeps, void* const work[2], int64_t max_iters, int64_t check_every, double tol2,
+                                 void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
+                                 double* rr_last) {
+  g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
+  g_mgcg_rz0 = 0.0;
+  if (iters_done) *iters_done = 0;
+  if (rr0) *rr0 = 0.0;
+  if (rr_last) *rr_last = 0.0;
+  // ---- the refusals, before anything touches the device
+  if (dtype_outer != NEPTUNE_HIP_F64 || dtype_inner != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
+  if (!outer || n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
+  Solve S;   // the inner hierarchy; cfg belongs to the outer operator
+  if (!S.check(levels, n_levels, dtype_inner, sweeps, sweeps, coarse_sweeps, nullptr, lines)) return NEPTUNE_HIP_EINVAL;
+  // the outer operator: what Solve::check asks of a level's operator, in D, and level 0's box and Omega
+  const neptune_hip_mg_level_t& O = *outer;
+  MgBox OB;
+  if (!O.x || !O.b || !O.q || !level_box(&O.g, OB) || O.g.rank != S.rank) return NEPTUNE_HIP_EINVAL;
+  for (int a = 0; a < 3; ++a)
+    if (OB.n[a] != S.box[0].n[a] || OB.lo[a] != S.box[0].lo[a] || OB.m[a] != S.box[0].m[a]) return NEPTUNE_HIP_EINVAL;
+  if (!O.fn && (O.body < 0 || O.body >= NEPTUNE_HIP_BODY_COUNT || O.body == NEPTUNE_HIP_BODY_LAP3D27_F32)) return NEPTUNE_HIP_EINVAL;
+  if (O.g.num_inputs > 1 && !O.in_rest) return NEPTUNE_HIP_EINVAL;
+  for (int i = 1; i < O.g.num_inputs; ++i)
+    if (!O.in_rest[i - 1]) return NEPTUNE_HIP_EINVAL;
+  // the fields of both precisions that the solve touches on levels 0 and 1, the trace included: none may meet another (each
+  // inner level's own four were checked against each other and the neighbour's above)
+  struct Span { const void* p; size_t bytes; size_t align; };
+  const size_t wide0 = box_bytes(OB, sizeof(double)), narrow0 = box_bytes(S.box[0], sizeof(float)), narrow1 = box_bytes(S.box[1], sizeof(float));
+  const Span spans[14] = {{O.x, wide0, 8},           {O.b, wide0, 8},           {O.q, wide0, 8},           {work[0], wide0, 8},
+                          {work[1], wide0, 8},       {trace, (size_t)(3 * max_iters) * sizeof(double), 8},
+                          {levels[0].x, narrow0, 4}, {levels[0].b, narrow0, 4}, {levels[0].q, narrow0, 4}, {levels[0].minv, narrow0, 4},
+                          {levels[1].x, narrow1, 4}, {levels[1].b, narrow1, 4}, {levels[1].q, narrow1, 4}, {levels[1].minv, narrow1, 4}};
+  for (int i = 0; i < 14; ++i) {
+    const bool optional = i == 5 || i == 9 || i == 13;   // the trace; minv of a level with line stages
+    if (!spans[i].p) {
+      if (optional) continue;
+      return NEPTUNE_HIP_EINVAL;
+    }
+    if ((uintptr_t)spans[i].p % spans[i].align != 0) return NEPTUNE_HIP_EINVAL;
+    for (int o = 0; o < (i < 6 ? i : 6); ++o)   // an inner field against the wide ones and the trace only
+      if (spans[o].p && buffers_overlap(spans[i].p, spans[i].bytes, spans[o].p, spans[o].bytes)) return NEPTUNE_HIP_EINVAL;
+  }
+  // line stages on level 0 need a wide-sum form of both code paths of the line kernel: not built yet
+  if (S.stages(0) > 0) return NEPTUNE_HIP_EUNSUPPORTED;
+  // the factor fields are read while x, q, r, p and the trace are written: they may meet none of them
+  for (int l = 0; l < n_levels && lines; ++l)
+    for (int st = 0; st < lines[l].n_stages; ++st)
+      for (const void* f : {lines[l].lo[st], lines[l].inv[st], lines[l].up[st]}) {
+        const size_t fb = box_bytes(S.box[l], sizeof(float));
+        for (int o = 0; o < 6; ++o)
+          if (spans[o].p && buffers_overlap(f, fb, spans[o].p, spans[o].bytes)) return NEPTUNE_HIP_EINVAL;
+      }
+  // rr is read back after every block: not while the caller's stream is being captured
+  if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
+
+  ensure_init();
+  SolveStream sc(reinterpret_cast<hipStream_t>(stream));
+  S.stream = sc.stream;
+  const neptune_hip_launch_cfg_t* const outer_cfg = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
+  const MgcgArgs a = {fn_dot, sweeps, work, max_iters, check_every, tol2, trace, iters_done, rr0, rr_last};
+  return mgcg_solve_mixed_typed<double, float>(S, O, outer_cfg, a);
 }
 
 double neptune_hip_mgcg_rz0(void) { return g_mgcg_rz0; }

@@ -163,6 +163,9 @@ SIGNATURES = {
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_mgcg_solve_lines": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), _i, _i, _vp, _i, _i, _vpp, _i64, _i64, _dbl, _vp, _vp,
                                           _cfg_p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mgcg_solve_mixed": (_i, [C.POINTER(MgLevel), _i, _vp, C.POINTER(MgLevel), C.POINTER(MgLines), _i, _i, _i, _i, _vpp, _i64,
+                                          _i64, _dbl, _vp, _vp, _cfg_p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mg_smooth_dot_wide": (_i, [_i, _i, _geom_p, _vp, _vp, _vp, _vp, _vp, _vp]),
     "neptune_hip_mg_line_first": (_i, [_i, _geom_p, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "neptune_hip_mg_line_smooth_dot": (_i, [_i, _geom_p, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "neptune_hip_mgcg_rz0": (_dbl, []),

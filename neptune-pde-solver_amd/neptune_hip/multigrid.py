@@ -22,6 +22,10 @@ bounds, axis=d, omega=0.8) for d in (0, 1)]) solves the operator's tridiagonal p
 1, in every sweep -- the repair for anisotropy whose strong direction varies in space.  solve() then runs
 neptune_hip_mg_solve_lines, and cg_solve(..., lines=True) wraps conjugate gradients around the line-smoothed cycle
 (neptune_hip_mgcg_solve_lines): its iteration count does not move with the anisotropy.
+
+multigrid.cg_solve_mixed(outer, inner, x, b, ...) is cg_solve in two precisions (neptune_hip_mgcg_solve_mixed):
+x, b and the CG recurrences in float64 on the operator of the Level `outer`, the V-cycle of the preconditioner in float32 on
+the Hierarchy `inner` -- the same iteration count at about 0.6 of the bytes per iteration.
 """
 from __future__ import annotations
 
@@ -434,6 +438,99 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
     if trace:
         return done.value, rr0.value, last.value, tr.cpu().numpy()[:3 * done.value].reshape(-1, 3)
     return done.value, rr0.value, last.value
+
+
+def cg_solve_mixed(outer: Level, inner: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coarse_sweeps: int = 8,
+                   max_iters: int = 50, tol2: float = 0.0, check_every: int = 1, trace: bool = False, dot="auto",
+                   cfg: Optional[_capi.LaunchCfg] = None, work: Optional[Sequence[DeviceField]] = None, stream: Optional[int] = None):
+    """solve A(x) = b in f64 by conjugate gradients whose preconditioner, one V(sweeps, sweeps) cycle, runs in f32
+    (neptune_hip_mgcg_solve_mixed): x, b, r, p, q and every scalar stay f64, the cycle works on a narrowed copy
+    of the residual, and the iteration count is that of cg_solve while the cycle moves half the bytes.  No scaling is
+    applied: a residual that leaves f32's range must be scaled by the caller.
+    outer: an f64 Level with the operator (entry, bounds, others, region); it needs no minv.  inner: an f32 Hierarchy of at
+    least two levels whose level 0 has outer's box and Omega and its own f32 operator; levels >= 1 may have line stages,
+    level 0 may not (ValueError).  The narrowed residual r32 and z32 are level 0's b and x: inner.b[0] and inner.x[0], f32
+    fields allocated here when they are None and left there for the caller to read.  work: r, p and optionally q, f64 fields
+    like x (allocated here when None).  dot: the outer operator's dot entry, as cg_solve's; cfg: the outer operator's launch
+    configuration.  Everything else as cg_solve.
+    Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a float64 numpy array of shape (iters, 3) holding
+    (p . A(p) of iteration k, r32 . M32(r32) after it, r . r after it).  cg_counts() and cg_rz0() report on this call too."""
+    import numpy as np
+    import torch
+    lib = _capi.load()
+    first = inner.levels[0]
+    if outer.like.dtype != _capi.F64 or x.dtype != _capi.F64 or b.dtype != _capi.F64:
+        raise ValueError("multigrid.cg_solve_mixed: the outer level, x and b must be float64")
+    if inner.dtype != _capi.F32:
+        raise ValueError("multigrid.cg_solve_mixed: the inner hierarchy must be float32")
+    if x.box != outer.like.box or b.box != outer.like.box:
+        raise ValueError("multigrid.cg_solve_mixed: x and b must have the box of the outer level")
+    if first.like.box != outer.like.box or (first.lo, first.hi) != (outer.lo, outer.hi):
+        raise ValueError("multigrid.cg_solve_mixed: level 0 of the inner hierarchy must have the box and the Omega of the outer level")
+    if len(inner) < 2:
+        raise ValueError("multigrid.cg_solve_mixed: at least two inner levels")
+    if first.lines:
+        raise ValueError("multigrid.cg_solve_mixed: line stages on level 0 are not supported (levels >= 1 may have them)")
+    for name in ("x", "b"):
+        held = getattr(inner, name)
+        if held[0] is None:
+            held[0] = DeviceField.empty_like(first.like)
+        elif held[0].box != first.like.box or held[0].dtype != _capi.F32:
+            raise ValueError(f"multigrid.cg_solve_mixed: inner.{name}[0] must be a float32 field of level 0's box")
+    if work is None:
+        work = [DeviceField.empty_like(x) for _ in range(3)]
+    work = list(work)
+    if len(work) == 2:
+        work.append(DeviceField.empty_like(x))
+    if len(work) != 3 or any(f.box != x.box or f.dtype != _capi.F64 for f in work):
+        raise ValueError("multigrid.cg_solve_mixed: work is two or three float64 fields like x (r, p[, q])")
+    entry = outer.entry
+    is_entry = hasattr(entry, "fn")
+    if isinstance(dot, str):
+        if dot not in ("auto", "fallback"):
+            raise ValueError('multigrid.cg_solve_mixed: dot is "auto", "fallback", None or a dot entry')
+        dot = entry if (dot == "auto" and is_entry) else None
+    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    arr, keep = inner._structs(inner.x[0], inner.b[0])
+    out = (_capi.MgLevel * 1)()
+    out[0].fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
+    out[0].body = -1 if is_entry else int(entry)
+    out[0].g = outer.geom
+    if outer.others:
+        rest_in = (C.c_void_p * len(outer.others))(*[f.ptr for f in outer.others])
+        keep.append(rest_in)
+        out[0].in_rest = rest_in
+    out[0].x, out[0].b, out[0].q, out[0].rscale = x.ptr, b.ptr, work[2].ptr, outer.rscale
+    st = current_stream_ptr() if stream is None else stream
+    tr = torch.zeros(3 * max(int(max_iters), 1), dtype=torch.float64, device=x.tensor.device) if trace else None
+    warr = (C.c_void_p * 2)(work[0].ptr, work[1].ptr)
+    done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    _capi.check(lib.neptune_hip_mgcg_solve_mixed(out, _capi.F64, fn_dot, arr, inner._line_structs() if inner.has_lines else None,
+                                                 len(inner), _capi.F32, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2,
+                                                 tr.data_ptr() if trace else None, st, C.byref(cfg) if cfg is not None else None,
+                                                 C.byref(done), C.byref(rr0), C.byref(last)), "neptune_hip_mgcg_solve_mixed")
+    del keep
+    if trace:
+        return done.value, rr0.value, last.value, tr.cpu().numpy()[:3 * done.value].reshape(-1, 3).astype(np.float64, copy=False)
+    return done.value, rr0.value, last.value
+
+
+def smooth_dot_wide(level: Level, q: DeviceField, b: DeviceField, x: DeviceField, dot_out=None, stream: Optional[int] = None):
+    """smooth(level, q, b, x) on float32 fields and the sum over Omega of b * x_new in float64, each term exact, out of the
+    same launch (neptune_hip_mg_smooth_dot_wide).  dot_out: a one-element float64 device tensor to receive the sum
+    (asynchronous; -> None), or None: blocking, -> the sum"""
+    import torch
+    if level.minv is None:
+        raise ValueError("multigrid.smooth_dot_wide: the level has no minv")
+    if x.dtype != _capi.F32:
+        raise ValueError("multigrid.smooth_dot_wide: float32 fields only (the sum is float64)")
+    st = current_stream_ptr() if stream is None else stream
+    dst = dot_out if dot_out is not None else torch.zeros(1, dtype=torch.float64, device=x.tensor.device)
+    _capi.check(_capi.load().neptune_hip_mg_smooth_dot_wide(_capi.F32, _capi.F64, C.byref(level.geom), q.ptr, b.ptr, level.minv.ptr,
+                                                            x.ptr, dst.data_ptr(), st), "neptune_hip_mg_smooth_dot_wide")
+    if dot_out is not None:
+        return None
+    return float(dst.item())
 
 
 def coarsened_axes(fine: Level, coarse: Level) -> tuple:
