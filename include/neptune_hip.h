@@ -518,6 +518,27 @@ int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn
  *              coincides with the fine cell of interior index 2 j + 1;
  *   KEPT       m_l[d] = m_(l+1)[d]: the coarse cell with interior index j coincides with the fine cell of interior index j.
  * At least one dimension must be coarsened; a dimension that is neither, or a pair with none coarsened, is refused.
+ * CELL-CENTRED PAIRS.  Between neighbouring levels a dimension may be in a third state, inferred from the
+ * extents as the other two are -- for m >= 1 no two states can hold at once:
+ *   HALVED     m_l[d] = 2 m_(l+1)[d]: the coarse cell of interior index j covers the fine cells of interior index 2 j and
+ *              2 j + 1.
+ * A pair of levels must have at least one dimension COARSENED or HALVED.  A pair that has both a COARSENED and a HALVED
+ * dimension is refused with NEPTUNE_HIP_EINVAL and nothing is launched: one pair is one grid kind; KEPT dimensions mix
+ * with either, and a hierarchy may change its grid kind from one pair to the next.  The arithmetic rules are the ones
+ * above (T, one rounding per operation, no FMA, named temporaries, dimension rank-1, then rank-2, then rank-3, kept ones
+ * skipped).  For a pair with halved dimensions:
+ *   RESTRICTION, fused with the residual:  d = b - q on the fine Omega;  along each halved dimension  t = 0.5 * (a[2 j] +
+ *     a[2 j + 1])  (one rounded addition and an exact scaling);  then  b_(l+1) = rscale_l * t  and  x_(l+1) = +0  on
+ *     Omega_(l+1).  No fine cell outside Omega_l is read: there is no rim operand at all.
+ *   PROLONGATION AND CORRECTION:  along a halved dimension the fine cell i takes  e[i / 2]  itself -- no operation, so -0
+ *     and NaN keep their bits --, then  x_l = x_l + e  on Omega_l.  No coarse cell outside Omega_(l+1) is read.
+ * The pair satisfies P = 2^k R^T for k halved dimensions, which keeps the V-cycle a symmetric preconditioner
+ * (neptune_hip_mgcg_solve requires one).  Boundary conditions live entirely in the operator the caller lowers (face
+ * coefficients that vanish on a Neumann face, a diagonal term for a Dirichlet face): the transfers do not know about them.
+ * The pure-Neumann problem is singular and is served as it stands: the coarsest level runs sweeps, not an exact solve, the
+ * right-hand side must be compatible (it must sum to zero over Omega_0), and the mean of x is whatever the iteration
+ * leaves.  A level whose operator has a zero diagonal (a 1 x 1 Neumann level) cannot be smoothed: end such a hierarchy
+ * at extent 2 (a non-finite minv is not refused).
  * Along a kept dimension both transfers are the identity -- no operation, no rounding, -0 and NaN keep their bits: the
  * restriction hands d = b - q through to the next dimension, the prolongation takes e[j] itself, and there is no rim
  * along it.  The coarsened dimensions run in the order stated below, the kept ones skipped.  With every dimension
@@ -539,7 +560,9 @@ int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn
  * restriction;  Cycle(l+1);  prolongation and correction;  `post` sweeps.
  * The three kernels alone (asynchronous on `stream`; NEPTUNE_HIP_EINVAL, nothing launched: a null pointer, an unknown
  * dtype, a malformed geometry, an empty Omega, ranks that differ, the size relation violated (a dimension neither
- * coarsened nor kept, or none coarsened), a non-finite rscale, a written field overlapping a field the same launch reads): */
+ * coarsened, halved nor kept, none coarsened or halved, or a coarsened and a halved one in the same pair), a non-finite
+ * rscale, a written field overlapping a field the same launch reads).  neptune_hip_mg_restrict and _prolong_add dispatch on
+ * the pair's inferred grid kind: */
 int neptune_hip_mg_smooth(int dtype, const neptune_hip_apply_geom_t *g, const void *q, const void *b, const void *minv,
                           void *x, void *stream);
 int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
@@ -547,12 +570,17 @@ int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t *g_fine, c
                             void *stream);
 int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
                                const void *x_coarse, void *x_fine, void *stream);
-/* What a pair of levels means: *mask_out = the dimensions coarsened between g_fine and g_coarse, bit d = field dimension d
- * (the others are kept).  Host-side geometry only, nothing is launched.  NEPTUNE_HIP_EINVAL, *mask_out untouched, where the
- * transfers would refuse the pair: a null pointer, a malformed geometry, an empty Omega, ranks that differ, a dimension
- * that is neither coarsened nor kept, no dimension coarsened. */
+/* What a pair of levels means: *mask_out = the dimensions coarsened or halved between g_fine and g_coarse (the union of
+ * the COARSENED and the HALVED ones), bit d = field dimension d (the others are kept).  Host-side geometry only, nothing is
+ * launched.  NEPTUNE_HIP_EINVAL, *mask_out untouched, where the transfers would refuse the pair: a null pointer, a
+ * malformed geometry, an empty Omega, ranks that differ, a dimension in none of the three states, no dimension coarsened
+ * or halved, a coarsened and a halved dimension in the same pair. */
 int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
                                   int *mask_out);
+/* *mask_out = the HALVED dimensions only: 0 for a vertex-centred pair, the mask of neptune_hip_mg_coarsened_axes for a
+ * cell-centred one.  It refuses the same pairs as neptune_hip_mg_coarsened_axes. */
+int neptune_hip_mg_halved_axes(const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
+                               int *mask_out);
 /* One level of a hierarchy.  Level 0's x and b are the caller's problem: initial guess in, solution out, and the
  * right-hand side; the cells of x_0 outside Omega_0 are Dirichlet data that enter through A(x) only.  x_l, b_l of the
  * coarser levels and every q_l are work fields: what they hold on entry does not matter. */

@@ -4,6 +4,7 @@
 //   neptune_mg_restrict      b_c = rscale * R(b_f - q_f), x_c = +0 on the coarse Omega   reads b_f, q_f once; writes 2 / 2^k (k axes coarsened)
 //   neptune_mg_restrict_kept2   the same with the contiguous axis kept
 //   neptune_mg_prolong_add   x_f = x_f + P(x_c) on the fine Omega                     reads and writes x_f; reads x_c through L1
+//   neptune_mg_restrict_cell / neptune_mg_prolong_add_cell   the two transfers of a cell-centred pair (at the end)
 //
 // Grids: vertex-centred, Dirichlet rim.  Per pair of levels every dimension is either COARSENED, m_fine = 2 m_coarse + 1: the
 // coarse cell of interior index j sits on the fine cell of interior index 2 j + 1 (interior indices count from Omega's lower
@@ -217,6 +218,100 @@ __global__ __launch_bounds__(256) void neptune_mg_prolong_add(MgBox F, MgBox Cb,
     ei[a] = C1 ? mg_interp(oj, ej[0], ej[1]) : ej[1];
   }
   const T e = C0 ? mg_interp(oi, ei[0], ei[1]) : ei[1];
+  const int64_t o = mg_at(F, fi, fj, fk);
+  x_f[o] = x_f[o] + e;
+}
+
+// ================================================================ cell-centred pairs
+// A dimension may be in a third state, HALVED: m_fine = 2 m_coarse, the coarse cell of interior index j covers the fine cells
+// of interior index 2 j and 2 j + 1.  One pair of levels is one grid kind: the two kernels below take MASK = the HALVED axes
+// (the others are kept; at least one bit is set) and never see a COARSENED one.  There is no rim operand: the restriction
+// reads the fine Omega only, the prolongation the coarse Omega only.  Neither needs LDS or a barrier.
+
+// the mean of a pair: one rounded addition and the exact scaling
+template <class T>
+__device__ __forceinline__ T mg_mean(T a0, T a1) {
+  const T s = a0 + a1;
+  return (T)0.5 * s;
+}
+// the cells p[0], p[1].  `aligned` (workgroup-uniform): p is a multiple of 2 sizeof(T) -- one load of twice the width;
+// else two loads.  The same bits either way.
+template <class T>
+__device__ __forceinline__ void mg_load_pair(const T* p, bool aligned, T& a0, T& a1) {
+  if (aligned) {
+    T v[2];
+    __builtin_memcpy(v, __builtin_assume_aligned(p, 2 * sizeof(T)), 2 * sizeof(T));
+    a0 = v[0];
+    a1 = v[1];
+  } else {
+    a0 = p[0];
+    a1 = p[1];
+  }
+}
+
+// ---------------------------------------------------------------- restriction, fused with the residual
+// The workgroup owns coarse cells (ci, cj, ck0 .. ck0 + 255).  Per halved slow axis it reads two fine rows / planes (2 c and
+// 2 c + 1; a kept axis: the one of the same index).  Axis 2 halved: lane ck takes the fine cells 2 ck and 2 ck + 1 of each
+// row, so consecutive lanes cover one contiguous span of 512 fine cells per row: every byte fetched is used and no fine row
+// is read by two workgroups.  Axis 2 kept: every lane loads its own cell of each row.  d = b - q, then the mean along axis
+// 2, then axis 1, then axis 0, skipping kept axes.
+template <class T, int MASK>
+__global__ __launch_bounds__(256) void neptune_mg_restrict_cell(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ b_f,
+                                                                const T* __restrict__ q_f, T rscale, T* __restrict__ b_c,
+                                                                T* __restrict__ x_c) {
+  static_assert(MASK > 0 && MASK < 8, "at least one axis halved");
+  constexpr bool H0 = (MASK & 1) != 0, H1 = (MASK & 2) != 0, H2 = (MASK & 4) != 0;
+  constexpr int NI = H0 ? 2 : 1, NJ = H1 ? 2 : 1;
+  int64_t ci, cj, ck0;
+  if (!mg_row(Cb, nchunk, linear_block(), ci, cj, ck0)) return;
+  const int64_t ck = ck0 + threadIdx.x;
+  if (ck >= Cb.m[2]) return;
+  const int64_t fi0 = H0 ? 2 * ci : ci, fj0 = H1 ? 2 * cj : cj, fk = H2 ? 2 * ck : ck;
+  T plane[NI];
+#pragma unroll
+  for (int a = 0; a < NI; ++a) {
+    T row[NJ];
+#pragma unroll
+    for (int r = 0; r < NJ; ++r) {
+      const int64_t o = mg_at(F, fi0 + a, fj0 + r, fk);
+      if constexpr (H2) {
+        // fk is even: the pair's alignment is that of the row's first Omega cell, the same for every lane
+        const bool aligned = (((uintptr_t)(b_f + o) | (uintptr_t)(q_f + o)) & (2 * sizeof(T) - 1)) == 0;
+        T b0, b1, q0, q1;
+        mg_load_pair(b_f + o, aligned, b0, b1);
+        mg_load_pair(q_f + o, aligned, q0, q1);
+        const T d0 = b0 - q0;
+        const T d1 = b1 - q1;
+        row[r] = mg_mean(d0, d1);
+      } else {
+        row[r] = b_f[o] - q_f[o];
+      }
+    }
+    if constexpr (H1) plane[a] = mg_mean(row[0], row[1]);
+    else plane[a] = row[0];
+  }
+  T t;
+  if constexpr (H0) t = mg_mean(plane[0], plane[1]);
+  else t = plane[0];
+  const int64_t oc = mg_at(Cb, ci, cj, ck);
+  b_c[oc] = rscale * t;
+  x_c[oc] = (T)0;
+}
+
+// ---------------------------------------------------------------- prolongation and correction
+// The workgroup owns fine cells (fi, fj, fk0 .. fk0 + 255).  The coarse row and plane are workgroup-uniform (fi / 2, fj / 2,
+// or the same index on a kept axis); along a halved axis 2 the lanes 2 j and 2 j + 1 read the same coarse cell through L1.
+// One coarse operand per fine cell, taken as it is (no operation: -0 and NaN keep their bits), no parity select.
+template <class T, int MASK>
+__global__ __launch_bounds__(256) void neptune_mg_prolong_add_cell(MgBox F, MgBox Cb, int64_t nchunk, const T* __restrict__ x_c,
+                                                                   T* __restrict__ x_f) {
+  static_assert(MASK > 0 && MASK < 8, "at least one axis halved");
+  int64_t fi, fj, fk0;
+  if (!mg_row(F, nchunk, linear_block(), fi, fj, fk0)) return;
+  const int64_t fk = fk0 + threadIdx.x;
+  if (fk >= F.m[2]) return;
+  const int64_t ci = (MASK & 1) ? fi / 2 : fi, cj = (MASK & 2) ? fj / 2 : fj, ck = (MASK & 4) ? fk / 2 : fk;
+  const T e = x_c[mg_at(Cb, ci, cj, ck)];
   const int64_t o = mg_at(F, fi, fj, fk);
   x_f[o] = x_f[o] + e;
 }

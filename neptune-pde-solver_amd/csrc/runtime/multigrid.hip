@@ -10,6 +10,8 @@
 // (neptune_hip_mg_line_first, neptune_hip_mg_line_smooth_dot launch the two alone); neptune_hip_mgcg_solve is that call without
 // lines.  neptune_hip_mgcg_solve_mixed is that solver with x, b, r, p, q and the scalars in f64 around the cycle in f32
 // (mgcg_mixed_kernels.hpp); neptune_hip_mg_smooth_dot_wide launches its last sweep, the one with the wide sum, alone.
+// A pair of levels is vertex-centred or cell-centred: sizes_nest infers which, and the two transfer launches
+// dispatch on it -- everything else here is the same code for both.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -59,16 +61,20 @@ bool level_box(const neptune_hip_apply_geom_t* g, MgBox& B) {
   }
   return true;
 }
-// How two neighbouring levels nest: per axis that carries a dimension either coarsened, m_fine = 2 m_coarse + 1, or kept,
-// m_fine = m_coarse (the two exclude each other for m >= 1).  -> the kernels' mask (bit a: axis a is coarsened), or 0 =
-// refuse: an axis that is neither, or no axis coarsened
+// How two neighbouring levels nest: per axis that carries a dimension coarsened, m_fine = 2 m_coarse + 1, halved, m_fine =
+// 2 m_coarse (a cell-centred pair), or kept, m_fine = m_coarse (the three exclude each other for m >= 1).
+// -> the kernels' mask (bit a: axis a is coarsened or halved), with kMgCell set when the axes are halved ones; or 0 = refuse:
+// an axis in no state, none coarsened or halved, or both kinds in one pair
+constexpr int kMgCell = 8;
 int sizes_nest(const MgBox& F, const MgBox& Cb, int rank) {
-  int mask = 0;
+  int coarsened = 0, halved = 0;
   for (int a = 3 - rank; a < 3; ++a) {
-    if (F.m[a] == 2 * Cb.m[a] + 1) mask |= 1 << a;
+    if (F.m[a] == 2 * Cb.m[a] + 1) coarsened |= 1 << a;
+    else if (F.m[a] == 2 * Cb.m[a]) halved |= 1 << a;
     else if (F.m[a] != Cb.m[a]) return 0;
   }
-  return mask;
+  if (coarsened && halved) return 0;
+  return halved ? (halved | kMgCell) : coarsened;
 }
 size_t box_bytes(const MgBox& B, size_t elem) { return (size_t)(B.n[0] * B.n[1] * B.n[2]) * elem; }
 
@@ -110,6 +116,22 @@ template <class T, int MASK>
 int prolong_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t stream) {
   const RowGrid r = row_grid(F);
   hipLaunchKernelGGL((neptune_mg_prolong_add<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(x_c),
+                     static_cast<T*>(x_f));
+  return launched();
+}
+// the transfers of a cell-centred pair: MASK = the halved axes
+template <class T, int MASK>
+int restrict_cell_launch(const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c, void* x_c,
+                         hipStream_t stream) {
+  const RowGrid r = row_grid(Cb);
+  hipLaunchKernelGGL((neptune_mg_restrict_cell<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
+                     static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
+  return launched();
+}
+template <class T, int MASK>
+int prolong_cell_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t stream) {
+  const RowGrid r = row_grid(F);
+  hipLaunchKernelGGL((neptune_mg_prolong_add_cell<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(x_c),
                      static_cast<T*>(x_f));
   return launched();
 }
@@ -175,7 +197,7 @@ int line_launch(const MgBox& B, int axis, void* q, const void* b, const void* lo
   }
   return launched();
 }
-// the dispatch on element type and on the mask of coarsened axes (1..7, from sizes_nest), stated once
+// the dispatch on element type and on the pair's mask (sizes_nest: the axes 1..7, kMgCell for a cell-centred pair), stated once
 template <class F64, class F32>
 int by_type(int dtype, F64&& f64, F32&& f32) { return dtype == NEPTUNE_HIP_F64 ? f64() : f32(); }
 int do_line(int dtype, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
@@ -211,15 +233,21 @@ int by_mask(int mask, Launch&& launch) {
 }
 int do_restrict(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c,
                 void* x_c, hipStream_t s) {
-  return by_mask(mask, [&](auto m) {
+  return by_mask(mask & 7, [&](auto m) {
     constexpr int M = decltype(m)::value;
+    if (mask & kMgCell)
+      return by_type(dtype, [&] { return restrict_cell_launch<double, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); },
+                     [&] { return restrict_cell_launch<float, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); });
     return by_type(dtype, [&] { return restrict_launch<double, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); },
                    [&] { return restrict_launch<float, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); });
   });
 }
 int do_prolong(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t s) {
-  return by_mask(mask, [&](auto m) {
+  return by_mask(mask & 7, [&](auto m) {
     constexpr int M = decltype(m)::value;
+    if (mask & kMgCell)
+      return by_type(dtype, [&] { return prolong_cell_launch<double, M>(F, Cb, x_c, x_f, s); },
+                     [&] { return prolong_cell_launch<float, M>(F, Cb, x_c, x_f, s); });
     return by_type(dtype, [&] { return prolong_launch<double, M>(F, Cb, x_c, x_f, s); },
                    [&] { return prolong_launch<float, M>(F, Cb, x_c, x_f, s); });
   });
@@ -266,7 +294,7 @@ struct Solve {
   const neptune_hip_mg_lines_t* lines;   // per level, or nullptr: no level has line stages
   int n_levels, dtype, rank, pre, post, coarse_sweeps;
   MgBox box[kMaxLevels];
-  int mask[kMaxLevels];                  // mask[l]: the axes coarsened between level l and l + 1 (sizes_nest)
+  int mask[kMaxLevels];                  // mask[l]: how level l and l + 1 nest (sizes_nest: the axes, and the grid kind)
   const neptune_hip_launch_cfg_t* cfg;   // level 0's, nullptr unless the caller set anything
   hipStream_t stream;
 
@@ -935,7 +963,17 @@ int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t* g_fine, const 
   if (!level_box(g_fine, F) || !level_box(g_coarse, Cb) || g_fine->rank != g_coarse->rank) return NEPTUNE_HIP_EINVAL;
   const int mask = sizes_nest(F, Cb, g_fine->rank);
   if (!mask) return NEPTUNE_HIP_EINVAL;
-  *mask_out = mask >> (3 - g_fine->rank);   // the kernels' axes are the dimensions right-aligned
+  *mask_out = (mask & 7) >> (3 - g_fine->rank);   // the kernels' axes are the dimensions right-aligned
+  return NEPTUNE_HIP_OK;
+}
+
+int neptune_hip_mg_halved_axes(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse, int* mask_out) {
+  if (!g_fine || !g_coarse || !mask_out) return NEPTUNE_HIP_EINVAL;
+  MgBox F, Cb;
+  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb) || g_fine->rank != g_coarse->rank) return NEPTUNE_HIP_EINVAL;
+  const int mask = sizes_nest(F, Cb, g_fine->rank);
+  if (!mask) return NEPTUNE_HIP_EINVAL;
+  *mask_out = (mask & kMgCell) ? (mask & 7) >> (3 - g_fine->rank) : 0;
   return NEPTUNE_HIP_OK;
 }
 

@@ -157,6 +157,7 @@ SIGNATURES = {
     "neptune_hip_mg_solve_lines": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), _i, _i, _i, _i, _i, _i64, _i64, _dbl,
                                         C.POINTER(C.c_double), _vp, _cfg_p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_mg_coarsened_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
+    "neptune_hip_mg_halved_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
     "neptune_hip_mg_counts": (None, [_i64p, _i64p, _i64p]),
     "neptune_hip_mg_smooth_dot": (_i, [_i, _geom_p, _vp, _vp, _vp, _vp, _vp, _vp]),
     "neptune_hip_mgcg_solve": (_i, [C.POINTER(MgLevel), _i, _i, _vp, _i, _i, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,

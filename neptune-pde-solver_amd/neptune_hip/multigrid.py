@@ -26,6 +26,13 @@ neptune_hip_mg_solve_lines, and cg_solve(..., lines=True) wraps conjugate gradie
 multigrid.cg_solve_mixed(outer, inner, x, b, ...) is cg_solve in two precisions (neptune_hip_mgcg_solve_mixed):
 x, b and the CG recurrences in float64 on the operator of the Level `outer`, the V-cycle of the preconditioner in float32 on
 the Hierarchy `inner` -- the same iteration count at about 0.6 of the bytes per iteration.
+
+Cell-centred grids: a pair of levels may instead halve dimensions, m_fine = 2 m_coarse -- the coarse cell j
+covers the fine cells 2 j and 2 j + 1 --, with averaging restriction and piecewise-constant prolongation; the boundary
+conditions live in the operator (e.g. face coefficients that vanish on a Neumann face).  coarsen_bounds(...,
+centring="cell") and coarsening_plan(..., centring="cell") give the extents, Hierarchy.halved records what it found; one
+pair is one grid kind (halved and coarsened dimensions do not mix in a pair; kept ones mix with either).  The pure-Neumann
+problem is singular: b must sum to zero over Omega, and the mean of x is whatever the iteration leaves.
 """
 from __future__ import annotations
 
@@ -38,11 +45,21 @@ from .fields import DeviceField, current_stream_ptr
 from .geometry import Box, make_geom
 
 
-def coarsen_bounds(bounds: Box, axes=None) -> list:
+def _centring(name: str, centring) -> bool:
+    """-> whether `centring` is "cell"; ValueError unless it is "vertex" or "cell"."""
+    if centring not in ("vertex", "cell"):
+        raise ValueError(f'{name}: centring is "vertex" or "cell", not {centring!r}')
+    return centring == "cell"
+
+
+def coarsen_bounds(bounds: Box, axes=None, centring: str = "vertex") -> list:
     """the next level's interior extents for a level whose interior is `bounds` (lb, ub): (m - 1) / 2 along every dimension
     in `axes` (an iterable of dimensions to coarsen; default: all of them), m itself along the others (kept: semi-coarsening,
     DESIGN 3.16).  ValueError when a coarsened extent is even (a vertex-centred grid with a Dirichlet rim nests only for odd
-    extents) or below 3 -- a kept one may be anything --, when `axes` is empty or names a dimension the bounds do not have."""
+    extents) or below 3 -- a kept one may be anything --, when `axes` is empty or names a dimension the bounds do not have.
+    centring="cell" (DESIGN 3.20): m / 2 along every dimension in `axes` (halved); ValueError for an odd extent or one
+    below 2."""
+    cell = _centring("coarsen_bounds", centring)
     rank = len(bounds[0])
     chosen = set(range(rank)) if axes is None else {int(d) for d in axes}
     if not chosen:
@@ -55,13 +72,18 @@ def coarsen_bounds(bounds: Box, axes=None) -> list:
         if d not in chosen:
             out.append(m)
             continue
+        if cell:
+            if m < 2 or m % 2 == 1:
+                raise ValueError(f"coarsen_bounds: interior extent {m} of dimension {d} is not an even number >= 2")
+            out.append(m // 2)
+            continue
         if m < 3 or m % 2 == 0:
             raise ValueError(f"coarsen_bounds: interior extent {m} of dimension {d} is not an odd number >= 3")
         out.append((m - 1) // 2)
     return out
 
 
-def coarsening_plan(extents, weights, threshold: float = 0.5, max_levels: int = 16) -> list:
+def coarsening_plan(extents, weights, threshold: float = 0.5, max_levels: int = 16, centring: str = "vertex") -> list:
     """which dimensions to coarsen on each level of a hierarchy for the operator  -sum_d w_d u_dd  on unscaled star stencils
     with rscale = 4; -> per level (extents, weights, axes), finest first, `axes` = the dimensions coarsened
     towards the next level (() on the last).
@@ -74,21 +96,26 @@ def coarsening_plan(extents, weights, threshold: float = 0.5, max_levels: int = 
     coarsenable or after max_levels levels.
 
     A heuristic for axis-aligned anisotropy -- one constant weight per dimension --, not a general coarsening strategy:
-    it knows nothing of variable coefficients, rotated anisotropy or mixed derivatives."""
+    it knows nothing of variable coefficients, rotated anisotropy or mixed derivatives.
+
+    centring="cell" (DESIGN 3.20): a dimension is coarsenable when its extent is even and >= 4 and is halved, m / 2; the
+    rule is otherwise the same.  An extent ends at 2: a Neumann level of extent 1 has a zero diagonal and cannot be
+    smoothed."""
+    cell = _centring("coarsening_plan", centring)
     m = [int(v) for v in extents]
     w = [float(v) for v in weights]
     if len(m) != len(w) or not m or any(v < 1 for v in m) or any(not v > 0.0 for v in w):
         raise ValueError("coarsening_plan: one positive weight per dimension, extents >= 1")
     plan = []
     while True:
-        can = [d for d, v in enumerate(m) if v >= 3 and v % 2 == 1]
+        can = [d for d, v in enumerate(m) if (v >= 4 and v % 2 == 0 if cell else v >= 3 and v % 2 == 1)]
         if not can or len(plan) + 1 >= max_levels:
             plan.append((tuple(m), tuple(w), ()))
             return plan
         strongest = max(w[d] for d in can)
         axes = tuple(d for d in can if w[d] >= threshold * strongest)
         plan.append((tuple(m), tuple(w), axes))
-        m = [(v - 1) // 2 if d in axes else v for d, v in enumerate(m)]
+        m = [(v // 2 if cell else (v - 1) // 2) if d in axes else v for d, v in enumerate(m)]
         w = [v if d in axes else 4.0 * v for d, v in enumerate(w)]
 
 
@@ -271,7 +298,10 @@ class Hierarchy:
     """the levels of a solve, finest first.  Checks the size relation per dimension -- coarsened, m_l = 2 m_(l+1) + 1, or
     kept, m_l = m_(l+1); at least one coarsened -- (ValueError naming the level and the dimension), one rank and one
     element type; allocates x_l and b_l for l >= 1 and every q_l.  coarsened[l]: the tuple of dimensions coarsened between
-    level l and l + 1."""
+    level l and l + 1.  A pair may instead be cell-centred: dimensions halved, m_l = 2 m_(l+1), the others
+    kept; halved[l]: the tuple of dimensions halved between level l and l + 1 (() for a vertex-centred pair), and
+    coarsened[l] then lists the same dimensions, as neptune_hip_mg_coarsened_axes does.  A pair with both a coarsened and
+    a halved dimension is refused (ValueError naming the level and both kinds)."""
 
     def __init__(self, levels: Sequence[Level]):
         self.levels = list(levels)
@@ -279,22 +309,30 @@ class Hierarchy:
             raise ValueError("Hierarchy: 1..16 levels")
         first = self.levels[0]
         self.coarsened = []
+        self.halved = []
         for l, L in enumerate(self.levels):
             if L.like.rank != first.like.rank or L.like.dtype != first.like.dtype:
                 raise ValueError(f"Hierarchy: level {l} has another rank or element type than level 0")
             if any(m < 1 for m in L.m):
                 raise ValueError(f"Hierarchy: level {l} has an empty Omega")
             if l > 0:
-                axes = []
+                axes, halved = [], []
                 for d, (mf, mc) in enumerate(zip(self.levels[l - 1].m, L.m)):
                     if mf == 2 * mc + 1:
                         axes.append(d)
+                    elif mf == 2 * mc:
+                        halved.append(d)
                     elif mf != mc:
                         raise ValueError(f"Hierarchy: level {l}, dimension {d}: interior extent {mc} does not nest in level "
                                          f"{l - 1}'s {mf} (m_fine = 2 m_coarse + 1, or m_fine = m_coarse for a kept dimension)")
-                if not axes:
+                if axes and halved:
+                    raise ValueError(f"Hierarchy: level {l} mixes two grid kinds against level {l - 1}: dimensions {axes} are "
+                                     f"coarsened (vertex-centred, m_fine = 2 m_coarse + 1) and dimensions {halved} are halved "
+                                     "(cell-centred, m_fine = 2 m_coarse); one pair of levels is one grid kind")
+                if not axes and not halved:
                     raise ValueError(f"Hierarchy: level {l} coarsens no dimension of level {l - 1}")
-                self.coarsened.append(tuple(axes))
+                self.coarsened.append(tuple(axes or halved))
+                self.halved.append(tuple(halved))
         self.dtype, self.rank = first.like.dtype, first.like.rank
         self.q = [DeviceField.empty_like(L.like) for L in self.levels]
         self.x = [None] + [DeviceField.empty_like(L.like) for L in self.levels[1:]]
@@ -539,6 +577,15 @@ def coarsened_axes(fine: Level, coarse: Level) -> tuple:
     mask = C.c_int(0)
     _capi.check(_capi.load().neptune_hip_mg_coarsened_axes(C.byref(fine.geom), C.byref(coarse.geom), C.byref(mask)),
                 "neptune_hip_mg_coarsened_axes")
+    return tuple(d for d in range(fine.like.rank) if mask.value >> d & 1)
+
+
+def halved_axes(fine: Level, coarse: Level) -> tuple:
+    """the dimensions halved between two levels, as the library reads the pair (neptune_hip_mg_halved_axes): () for a
+    vertex-centred pair; _capi.NeptuneHipError where the transfers would refuse the pair"""
+    mask = C.c_int(0)
+    _capi.check(_capi.load().neptune_hip_mg_halved_axes(C.byref(fine.geom), C.byref(coarse.geom), C.byref(mask)),
+                "neptune_hip_mg_halved_axes")
     return tuple(d for d in range(fine.like.rank) if mask.value >> d & 1)
 
 
