@@ -44,8 +44,8 @@ def pairs_forced_on(monkeypatch, cache):
 
 
 class Case:
-    """one module and its initial data.  Windows: 32 kept rows of 36 (3 x 12 waves; 28 of 32 with a coefficient field, 20 of 24
-    at radius 2), 120 kept fp64 / 240 fp32 columns per wave span: every shape below has window seams along J and K, and
+    """one module and its initial data.  Windows: 32 kept rows of 36 (3 x 12 waves; 28 of 32 with a coefficient field, 16 of 24
+    at radius 2: two stages lose two rows per side each), 120 kept fp64 / 240 fp32 columns per wave span: every shape below has window seams along J and K, and
     `chunk` planes / rows per chunk put chunk seams inside the field."""
 
     def __init__(self, shape, elem="f64", radius=1, coef=False, origin=None, bounds=None, chunk=5):
