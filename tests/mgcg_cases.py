@@ -18,12 +18,15 @@ tol_between = mgc.tol_between           # a threshold between two check values a
 
 
 # ---------------------------------------------------------------- the anisotropic star
-def aniso_module(shape, weights, dtype=np.float64):
+def aniso_module(shape, weights, dtype=np.float64, bounds=None):
     """NeptuneIR text of @entry(out, in): out<p> = (2 * sum of weights) * u<p> - sum over axes d of weights[d] * (u<p - e_d> +
     u<p + e_d>) one cell in from every face, copy-through on the rim: the unscaled operator -sum_d weights[d] u_dd, with
-    its own side weight per axis (mg_cases.mg_module is weights = 1 everywhere, in another order of additions)"""
+    its own side weight per axis (mg_cases.mg_module is weights = 1 everywhere, in another order of additions).
+    bounds: (lb, ub) of the apply instead of one cell in from every face"""
     rank = len(shape)
     assert len(weights) == rank
+    if bounds is None:
+        bounds = ([1] * rank, [n - 1 for n in shape])
     elem = mc.ELEM[np.dtype(dtype)]
     lst = lambda v: ", ".join(str(int(x)) for x in v)
     mr = "x".join(["?"] * rank) + "x" + elem
@@ -44,7 +47,7 @@ def aniso_module(shape, weights, dtype=np.float64):
     body.append(f"        neptune_ir.yield %acc{rank} : {elem}")
     out = ['#loc = #neptune_ir.location<"cell">',
            f"#b   = #neptune_ir.bounds<lb = [{lst(zero)}], ub = [{lst(shape)}]>",
-           f"#bi  = #neptune_ir.bounds<lb = [{lst([1] * rank)}], ub = [{lst([n - 1 for n in shape])}]>",
+           f"#bi  = #neptune_ir.bounds<lb = [{lst(bounds[0])}], ub = [{lst(bounds[1])}]>",
            f"!temp  = !neptune_ir.temp<element = {elem}, bounds = #b, location = #loc>",
            f"!field = !neptune_ir.field<element = {elem}, bounds = #b, location = #loc>",
            "module {",

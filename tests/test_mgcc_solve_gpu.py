@@ -23,6 +23,9 @@ import pytest
 
 import mg_cases as mgc
 import mgcc_cases as cc
+import mgcgmixed_cases as mx
+import mgfuzz_cases as fz
+import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
 from mgcc_cases import Halved
 
@@ -290,10 +293,30 @@ def test_mixed_precision_smoke(nh):
     inner = nh.mg.Hierarchy(_levels(nh, P32))
     assert inner.halved == [(0, 1, 2), (0, 1, 2), (2,), (2,)]
     x, b = F.from_numpy(P64.x0), F.from_numpy(P64.b)
-    done, rr0, rr_last = nh.mg.cg_solve_mixed(outer, inner, x, b, max_iters=20, tol2=tol2)
+    work = [F.from_numpy(np.full(P64.x0.shape, np.nan)) for _ in range(3)]
+    nan32 = lambda f: F.from_numpy(np.full(f.shape, np.nan, np.float32))
+    inner.q = [nan32(f) for f in inner.q]
+    inner.x = [nan32(inner.q[0])] + [nan32(f) for f in inner.x[1:]]
+    inner.b = [nan32(inner.q[0])] + [nan32(f) for f in inner.b[1:]]
+    done, rr0, rr_last, trace = nh.mg.cg_solve_mixed(outer, inner, x, b, max_iters=20, tol2=tol2, trace=True, work=work)
     nh.torch.cuda.synchronize()
+    rz0 = nh.mg.cg_rz0()
     print(f"mixed: done = {done} (f64: {len(seq) - 1}), rr0 = {rr0!r}, rr_last = {rr_last!r}")
     assert 1 <= done <= len(seq) + 1 and rr_last <= tol2 < rr0 and np.isfinite(x.numpy()).all()
+    # every field against the composed restatement, driven by the device's scalars: f64 recurrences on the f64 operator
+    # around the f32 cycle of the halved hierarchy
+    R = mx.Problem(P64.ref[0].A, P32.ref)
+    st, sums, rr0_ref, rz0_ref, _ = fz.replay(R, P64.x0, P64.b, rz0, trace)
+    assert trace.shape == (done, 3) and abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(rz0 - rz0_ref[0]) <= rz0_ref[1]
+    for k, row in enumerate(sums):
+        for c, (s, bd) in enumerate(row):
+            assert abs(float(trace[k][c]) - s) <= bd, (k, c, trace[k][c], s, bd)
+    for nm, got, want in (("x", x.numpy(), st.x), ("r", work[0].numpy(), st.r), ("p", work[1].numpy(), st.p),
+                          ("r32", inner.b[0].numpy(), st.r32), ("z32", inner.x[0].numpy(), st.z32)):
+        assert bits_equal(got, want), f"{nm}: " + mismatch_report(got, want)
+    for l in range(1, len(P32.ref)):
+        for nm, got, want in ((f"x_{l}", inner.x[l].numpy(), P32.ref[l].x), (f"b_{l}", inner.b[l].numpy(), P32.ref[l].b)):
+            assert bits_equal(got, want), f"{nm}: " + mismatch_report(got, want)
 
 
 def test_a_line_stage_on_level_one_smoke(nh, monkeypatch):
@@ -303,14 +326,36 @@ def test_a_line_stage_on_level_one_smoke(nh, monkeypatch):
 
     def lines(l, entry, like, bounds, others):
         return [nh.mg.line_weights(entry, like, bounds, axis=1, others=others, omega=DAMP, reach=1)] if l == 1 else ()
+    # the reference: the composed restatement on the same levels, level 1 with the stage's factors from the operator's own
+    # coefficient fields (the boundary faces' coefficients are 0: no coupling leaves Omega)
+    R1, (c0, c1, _) = P.ref[1], P.rests[1]
+    up_coef = np.zeros_like(c1)
+    up_coef[:, :-1] = c1[:, 1:]
+    diag = cc.face_fields(R1.m, P.dtype, P.faces, R1.weights)[1]
+    stage = (1,) + lc.factors(-c1, diag, -up_coef, R1.where, 1, DAMP)
+    R1.stages = [stage]
+    try:
+        ref_rr0, ref_checks = fz.run(P.ref, P.x0, P.b, 4)
+        ref_x, ref_b = [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref]
+    finally:
+        del R1.stages
     out = []
     for graph in ("1", "0"):
         monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", graph)        # read at every call
         h, x, b, _ = _hierarchy(nh, P, lines)
         assert h.has_lines
+        for nm, got, want in zip(("lo", "inv", "up"), h.levels[1].lines[0][1:], stage[1:]):
+            assert bits_equal(got.numpy(), want), f"line_weights' {nm}: " + mismatch_report(got.numpy(), want)
         done, rr0, rr_last, rr_checks = nh.mg.solve(h, x, b, max_cycles=4)
         nh.torch.cuda.synchronize()
         print(f"graph = {graph}: rr0 = {rr0!r}, checks = {rr_checks}, counts = {nh.mg.counts()}")
         assert done == 4 and all(after < 0.5 * before for before, after in zip([rr0] + rr_checks, rr_checks))
         out.append(x.numpy())
+        assert abs(rr0 - ref_rr0[0]) <= ref_rr0[1]
+        for got, (want, bound) in zip(rr_checks, ref_checks):
+            assert abs(got - want) <= bound
+        for l, (got, want) in enumerate(zip([x.numpy()] + [f.numpy() for f in h.x[1:]], ref_x)):
+            assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
+        for l, (got, want) in enumerate(zip([b.numpy()] + [f.numpy() for f in h.b[1:]], ref_b)):
+            assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
     assert bits_equal(out[0], out[1]), mismatch_report(out[0], out[1])
