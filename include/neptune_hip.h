@@ -539,6 +539,20 @@ int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn
  * right-hand side must be compatible (it must sum to zero over Omega_0), and the mean of x is whatever the iteration
  * leaves.  A level whose operator has a zero diagonal (a 1 x 1 Neumann level) cannot be smoothed: end such a hierarchy
  * at extent 2 (a non-finite minv is not refused).
+ * LINEAR PROLONGATION OF A CELL-CENTRED PAIR, chosen per pair by the caller
+ * (neptune_hip_mg_prolong_t below; the default stays the piecewise-constant one above).  The arithmetic rules are the ones
+ * above: T, one rounding per operation, no FMA, named temporaries, dimension rank-1, then rank-2, then rank-3, kept ones
+ * skipped.  Along one halved dimension let e[0 .. m_c) be the coarse values -- the values AFTER the dimensions already
+ * done.  A fine cell of interior index i has j = i / 2, and its neighbour is n = j - 1 for even i, n = j + 1 for odd i:
+ *     v = e[n]                   if 0 <= n < m_c
+ *     v = +e[j]   (rule EVEN)    if n is outside: a Neumann face, the ghost cell mirrored
+ *     v = -e[j]   (rule ODD)     if n is outside: the value 0 ON the face, the ghost cell mirrored with its sign flipped
+ *     p = 0.75 * e[j];   s = 0.25 * v;   t = p + s
+ *   then  x_l = x_l + t  on Omega_l.  The rule is given per face, low and high, per dimension.  In the tensor product the
+ *   ghost of a later dimension is +- the INTERMEDIATE at the edge (what padding the intermediate array gives).  m_c = 1
+ *   makes both neighbours ghosts.  No coarse cell outside Omega_(l+1) is read, no fine cell outside Omega_l is written;
+ *   along a kept dimension the transfer is the identity.  The restriction stays the averaging one, so P != c R^T and the
+ *   cycle is NOT a symmetric preconditioner: the neptune_hip_mgcg_* entries take no such pair.
  * Along a kept dimension both transfers are the identity -- no operation, no rounding, -0 and NaN keep their bits: the
  * restriction hands d = b - q through to the next dimension, the prolongation takes e[j] itself, and there is no rim
  * along it.  The coarsened dimensions run in the order stated below, the kept ones skipped.  With every dimension
@@ -655,6 +669,32 @@ int neptune_hip_mg_solve_lines(const neptune_hip_mg_level_t *levels, const neptu
                                int dtype, int pre, int post, int coarse_sweeps, int64_t max_cycles, int64_t check_every,
                                double tol2, double *rr_checks, void *stream, const neptune_hip_launch_cfg_t *cfg,
                                int64_t *cycles_done, double *rr0, double *rr_last);
+
+/* The prolongation of one pair of levels: the piecewise-constant / interpolating one the pair's grid kind
+ * implies (CONSTANT: what neptune_hip_mg_prolong_add does), or the LINEAR one of a cell-centred pair defined above, with a
+ * rule per face, indexed by field dimension.  Entries of dimensions >= rank, and every rule of a CONSTANT pair, are not
+ * read. */
+#define NEPTUNE_HIP_MG_PROLONG_CONSTANT 0
+#define NEPTUNE_HIP_MG_PROLONG_LINEAR   1
+#define NEPTUNE_HIP_MG_RIM_EVEN 0   /* a Neumann face: the ghost is +e at the edge */
+#define NEPTUNE_HIP_MG_RIM_ODD  1   /* the value 0 on the face: the ghost is -e at the edge */
+typedef struct { int32_t kind; int32_t rim_lo[3], rim_hi[3]; } neptune_hip_mg_prolong_t;   /* indexed by field dimension */
+/* The prolongation kernel alone, by *p (asynchronous on `stream`): kind CONSTANT is neptune_hip_mg_prolong_add.  The
+ * refusals of neptune_hip_mg_prolong_add, and NEPTUNE_HIP_EINVAL, nothing launched, for p = NULL, a kind outside {0, 1},
+ * LINEAR on a pair with no halved dimension, a rule outside {0, 1} on a dimension < rank of a LINEAR pair. */
+int neptune_hip_mg_prolong_add_linear(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
+                                      const neptune_hip_mg_prolong_t *p, const void *x_coarse, void *x_fine, void *stream);
+/* neptune_hip_mg_solve_lines with the prolongation chosen per pair: prolong[l] belongs to the pair (l, l + 1), n_levels - 1
+ * entries are read.  prolong == NULL, or kind CONSTANT everywhere, is neptune_hip_mg_solve_lines exactly -- the same
+ * launches, the same bits -- and neptune_hip_mg_solve_lines is that call.  The solve, the stop rule, rr_checks, the replay
+ * and the counts are neptune_hip_mg_solve's.  NEPTUNE_HIP_EINVAL, nothing launched, every field's bits unchanged: the
+ * refusals of neptune_hip_mg_solve_lines and those of neptune_hip_mg_prolong_add_linear for any pair.  The
+ * neptune_hip_mgcg_* entries take no such array: with a LINEAR pair the cycle is not a symmetric preconditioner. */
+int neptune_hip_mg_solve_prolong(const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines,
+                                 const neptune_hip_mg_prolong_t *prolong, int n_levels, int dtype, int pre, int post,
+                                 int coarse_sweeps, int64_t max_cycles, int64_t check_every, double tol2, double *rr_checks,
+                                 void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *cycles_done, double *rr0,
+                                 double *rr_last);
 
 /* TWO MORE FORMS OF THE STAGE'S KERNEL, alone (asynchronous on `stream`).  ARITHMETIC as above.
  * neptune_hip_mg_line_first is the APPLY-FREE stage: the values of the plain stage run on q = +0, x = +0 --

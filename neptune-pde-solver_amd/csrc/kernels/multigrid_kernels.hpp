@@ -5,6 +5,7 @@
 //   neptune_mg_restrict_kept2   the same with the contiguous axis kept
 //   neptune_mg_prolong_add   x_f = x_f + P(x_c) on the fine Omega                     reads and writes x_f; reads x_c through L1
 //   neptune_mg_restrict_cell / neptune_mg_prolong_add_cell   the two transfers of a cell-centred pair (at the end)
+//   neptune_mg_prolong_add_linear   the linear prolongation of a cell-centred pair, weights 3/4 and 1/4, a rule per face
 //
 // Grids: vertex-centred, Dirichlet rim.  Per pair of levels every dimension is either COARSENED, m_fine = 2 m_coarse + 1: the
 // coarse cell of interior index j sits on the fine cell of interior index 2 j + 1 (interior indices count from Omega's lower
@@ -314,6 +315,134 @@ __global__ __launch_bounds__(256) void neptune_mg_prolong_add_cell(MgBox F, MgBo
   const T e = x_c[mg_at(Cb, ci, cj, ck)];
   const int64_t o = mg_at(F, fi, fj, fk);
   x_f[o] = x_f[o] + e;
+}
+
+// ================================================================ linear prolongation on a cell-centred pair
+// Along a halved axis the fine cell i lies a quarter of a coarse cell from the centre of its own coarse cell j = i / 2,
+// towards the neighbour n = j - 1 (even i) or j + 1 (odd i):  p = 0.75 * e[j],  s = 0.25 * v,  t = p + s  with v = e[n], or,
+// where n is outside the coarse Omega, the ghost value the face's rule gives: +e[j] (EVEN: a Neumann face) or -e[j] (ODD:
+// the value 0 on the face).  e is the intermediate after the axes already done (axis 2, then 1, then 0), so a ghost along a
+// later axis is +- the intermediate at the edge.  The negation is a sign flip: exact, and 0.25 * (-a) = -(0.25 * a).
+
+// the rule per face on the kernels' three axes: 0 = EVEN, 1 = ODD; axes that are kept are never looked at
+struct MgRim {
+  int32_t lo[3], hi[3];
+};
+template <class T>
+__device__ __forceinline__ T mg_lin(T own, T v) {
+  const T p = (T)0.75 * own;
+  const T s = (T)0.25 * v;
+  return p + s;
+}
+// the coarse indices one fine index needs along one axis: its own cell, and the neighbour -- or, where that is outside
+// [0, m_c), `ghost`, with `near` = own (always a cell of Omega) and `flip` = the face's rule is ODD.  A kept axis: own only.
+struct MgNear {
+  int64_t own, near;
+  bool ghost, flip;
+};
+__device__ __forceinline__ MgNear mg_near(bool halved, int64_t i, int64_t m_c, int32_t rule_lo, int32_t rule_hi) {
+  MgNear s;
+  s.own = halved ? i / 2 : i;
+  const int64_t n = (i & 1) ? s.own + 1 : s.own - 1;
+  s.ghost = halved && (n < 0 || n >= m_c);
+  s.flip = s.ghost && (n < 0 ? rule_lo : rule_hi) != 0;
+  s.near = (halved && !s.ghost) ? n : s.own;
+  return s;
+}
+template <class T>
+__device__ __forceinline__ void mg_store_pair(T* p, bool aligned, T a0, T a1) {
+  if (aligned) {
+    const T v[2] = {a0, a1};
+    __builtin_memcpy(__builtin_assume_aligned(p, 2 * sizeof(T)), v, 2 * sizeof(T));
+  } else {
+    p[0] = a0;
+    p[1] = a1;
+  }
+}
+
+// The workgroup owns one chunk of the fine row (fi, fj).  Along axes 0 and 1 the own and the neighbour coarse row / plane,
+// and whether the neighbour is a ghost, are workgroup-uniform scalar work (mg_near); a ghost row is not loaded at all: it
+// is +- the intermediate of the own row.  Up to 2 x 2 coarse rows feed a fine row, all through L1 / L2 -- the coarse field is
+// 1 / 2^k of the fine one.  Along axis 2:
+//   halved (PAIR): the workgroup's chunk is 256 COARSE cells; the lane owns the coarse index ck and the fine cells 2 ck,
+//     2 ck + 1, formed from e[ck - 1], e[ck], e[ck + 1] of each coarse row (three coalesced loads; the product 0.75 * e[ck]
+//     is the same value for both cells); x_f is read and written as one access of 2 sizeof(T) where the row's first Omega
+//     cell is aligned to that, as two otherwise -- the same bits.  Only lanes ck = 0 and ck = m - 1 meet a ghost: a per-lane
+//     select.  (A form with one fine cell per lane, two coarse loads by parity, measured 1.6x slower: DESIGN 3.22.)
+//   kept: the chunk is 256 fine cells, the lane loads e[fk] alone.
+// A neighbour index outside the coarse Omega is clamped to the own cell before the load, so no coarse cell outside Omega is
+// read; no fine cell outside Omega is written.  No LDS, no barrier, no atomics.
+template <class T, int MASK>
+__global__ __launch_bounds__(256) void neptune_mg_prolong_add_linear(MgBox F, MgBox Cb, int64_t nchunk, MgRim rim,
+                                                                     const T* __restrict__ x_c, T* __restrict__ x_f) {
+  static_assert(MASK > 0 && MASK < 8, "at least one axis halved");
+  constexpr bool H0 = (MASK & 1) != 0, H1 = (MASK & 2) != 0, PAIR = (MASK & 4) != 0;
+  constexpr int NI = H0 ? 2 : 1, NJ = H1 ? 2 : 1, W = PAIR ? 2 : 1;
+  int64_t fi, fj, k0;
+  if (!mg_row(F, nchunk, linear_block(), fi, fj, k0)) return;
+  const int64_t k = k0 + threadIdx.x;   // PAIR: the coarse interior index along axis 2; else the fine one
+  if (k >= (PAIR ? Cb.m[2] : F.m[2])) return;
+  const MgNear si = mg_near(H0, fi, Cb.m[0], rim.lo[0], rim.hi[0]);
+  const MgNear sj = mg_near(H1, fj, Cb.m[1], rim.lo[1], rim.hi[1]);
+  const int64_t ci[2] = {si.own, si.near}, cj[2] = {sj.own, sj.near};
+  T ei[NI][W];
+#pragma unroll
+  for (int a = 0; a < NI; ++a) {
+    if (a == 1 && si.ghost) {
+#pragma unroll
+      for (int w = 0; w < W; ++w) ei[a][w] = si.flip ? -ei[0][w] : ei[0][w];
+      continue;
+    }
+    T ej[NJ][W];
+#pragma unroll
+    for (int r = 0; r < NJ; ++r) {
+      if (r == 1 && sj.ghost) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) ej[r][w] = sj.flip ? -ej[0][w] : ej[0][w];
+        continue;
+      }
+      const T* row = x_c + mg_at(Cb, ci[a], cj[r], 0);
+      if constexpr (PAIR) {
+        const bool first = k == 0, last = k + 1 == Cb.m[2];
+        const T own = row[k];
+        T vm = row[first ? k : k - 1];
+        T vp = row[last ? k : k + 1];
+        if (first && rim.lo[2] != 0) vm = -vm;
+        if (last && rim.hi[2] != 0) vp = -vp;
+        const T p = (T)0.75 * own;
+        const T sm = (T)0.25 * vm;
+        const T sp = (T)0.25 * vp;
+        ej[r][0] = p + sm;
+        ej[r][1] = p + sp;
+      } else {
+        ej[r][0] = row[k];
+      }
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      if constexpr (H1) ei[a][w] = mg_lin(ej[0][w], ej[1][w]);
+      else ei[a][w] = ej[0][w];
+    }
+  }
+  T e[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    if constexpr (H0) e[w] = mg_lin(ei[0][w], ei[1][w]);
+    else e[w] = ei[0][w];
+  }
+  if constexpr (PAIR) {
+    // 2 k is even: the pair's alignment is that of the row's first Omega cell, the same for every lane
+    T* const p = x_f + mg_at(F, fi, fj, 2 * k);
+    const bool aligned = ((uintptr_t)p & (2 * sizeof(T) - 1)) == 0;
+    T a0, a1;
+    mg_load_pair(p, aligned, a0, a1);
+    const T u0 = a0 + e[0];
+    const T u1 = a1 + e[1];
+    mg_store_pair(p, aligned, u0, u1);
+  } else {
+    const int64_t o = mg_at(F, fi, fj, k);
+    x_f[o] = x_f[o] + e[0];
+  }
 }
 
 }  // namespace neptune_hip

@@ -11,7 +11,10 @@
 // lines.  neptune_hip_mgcg_solve_mixed is that solver with x, b, r, p, q and the scalars in f64 around the cycle in f32
 // (mgcg_mixed_kernels.hpp); neptune_hip_mg_smooth_dot_wide launches its last sweep, the one with the wide sum, alone.
 // A pair of levels is vertex-centred or cell-centred: sizes_nest infers which, and the two transfer launches
-// dispatch on it -- everything else here is the same code for both.
+// dispatch on it -- everything else here is the same code for both.  A cell-centred pair may prolong linearly instead, by a rule
+// per face that the caller states: neptune_hip_mg_prolong_add_linear launches that kernel alone,
+// neptune_hip_mg_solve_prolong is the plain-cycle driver with the choice per pair, and neptune_hip_mg_solve_lines is that call
+// without any; the MGCG drivers take none (the cycle would not be a symmetric preconditioner).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -135,6 +138,17 @@ int prolong_cell_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* 
                      static_cast<T*>(x_f));
   return launched();
 }
+// The linear prolongation of a cell-centred pair: one workgroup per chunk of a fine row -- 256 COARSE cells
+// (512 fine ones) where axis 2 is halved, 256 fine cells where it is kept
+template <class T, int MASK>
+int prolong_linear_launch(const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* x_c, void* x_f, hipStream_t stream) {
+  RowGrid r;
+  r.nchunk = (Cb.m[2] + 255) / 256;   // axis 2 kept: Cb.m[2] = F.m[2]
+  r.grid = grid_for_blocks(F.m[0] * F.m[1] * r.nchunk);
+  hipLaunchKernelGGL((neptune_mg_prolong_add_linear<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, rim, static_cast<const T*>(x_c),
+                     static_cast<T*>(x_f));
+  return launched();
+}
 // One stage of the line smoother along box axis `axis`.  Axis 2: a one-wave workgroup per 64 lines.  A slow axis: a workgroup
 // per chunk of lanes along axis 2 and index of the other slow axis; 256 lanes wide where that still gives every CU two
 // workgroups, else 64 lanes, so that a small level (a 2-D field's lines along dim 0 have m[2] / width workgroups in all)
@@ -252,6 +266,31 @@ int do_prolong(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void*
                    [&] { return prolong_launch<float, M>(F, Cb, x_c, x_f, s); });
   });
 }
+int do_prolong_linear(int dtype, int mask, const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* x_c, void* x_f, hipStream_t s) {
+  return by_mask(mask & 7, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    return by_type(dtype, [&] { return prolong_linear_launch<double, M>(F, Cb, rim, x_c, x_f, s); },
+                   [&] { return prolong_linear_launch<float, M>(F, Cb, rim, x_c, x_f, s); });
+  });
+}
+// What the caller states about the prolongation of one pair (sizes_nest's `mask`): -> false: refuse -- a kind outside
+// {CONSTANT, LINEAR}, LINEAR on a pair without a halved dimension, a rule outside {EVEN, ODD} on a dimension < rank of a
+// LINEAR pair.  *linear: the kind; rim: a LINEAR pair's rules on the kernels' axes (the dimensions right-aligned).
+// Nothing but `kind` is read of a CONSTANT entry, and no entry of a dimension >= rank.
+bool prolong_rules(const neptune_hip_mg_prolong_t& p, int mask, int rank, bool* linear, MgRim& rim) {
+  if (p.kind != NEPTUNE_HIP_MG_PROLONG_CONSTANT && p.kind != NEPTUNE_HIP_MG_PROLONG_LINEAR) return false;
+  *linear = p.kind == NEPTUNE_HIP_MG_PROLONG_LINEAR;
+  for (int a = 0; a < 3; ++a) rim.lo[a] = rim.hi[a] = NEPTUNE_HIP_MG_RIM_EVEN;
+  if (!*linear) return true;
+  if (!(mask & kMgCell)) return false;
+  for (int d = 0; d < rank; ++d) {
+    for (const int32_t v : {p.rim_lo[d], p.rim_hi[d]})
+      if (v != NEPTUNE_HIP_MG_RIM_EVEN && v != NEPTUNE_HIP_MG_RIM_ODD) return false;
+    rim.lo[d + 3 - rank] = p.rim_lo[d];
+    rim.hi[d + 3 - rank] = p.rim_hi[d];
+  }
+  return true;
+}
 
 bool stream_capturing(void* stream) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -295,13 +334,16 @@ struct Solve {
   int n_levels, dtype, rank, pre, post, coarse_sweeps;
   MgBox box[kMaxLevels];
   int mask[kMaxLevels];                  // mask[l]: how level l and l + 1 nest (sizes_nest: the axes, and the grid kind)
+  bool linear[kMaxLevels];               // linear[l]: the pair (l, l + 1) prolongs linearly, by the rules rim[l]
+  MgRim rim[kMaxLevels];
   const neptune_hip_launch_cfg_t* cfg;   // level 0's, nullptr unless the caller set anything
   hipStream_t stream;
 
   // The arguments every solve over a hierarchy shares, checked before anything touches the device, and the solve's fields
   // filled in from them (all but `stream`); -> false: refuse
   bool check(const neptune_hip_mg_level_t* levels_, int n_levels_, int dtype_, int pre_, int post_, int coarse_sweeps_,
-             const neptune_hip_launch_cfg_t* cfg_, const neptune_hip_mg_lines_t* lines_ = nullptr) {
+             const neptune_hip_launch_cfg_t* cfg_, const neptune_hip_mg_lines_t* lines_ = nullptr,
+             const neptune_hip_mg_prolong_t* prolong_ = nullptr) {
     if (!levels_ || n_levels_ < 1 || n_levels_ > kMaxLevels || !known_dtype(dtype_)) return false;
     if (pre_ < 0 || post_ < 0 || coarse_sweeps_ < 0) return false;
     levels = levels_;
@@ -331,6 +373,8 @@ struct Solve {
       if (l > 0) {
         mask[l - 1] = sizes_nest(box[l - 1], box[l], rank);
         if (!mask[l - 1]) return false;
+        linear[l - 1] = false;
+        if (prolong_ && !prolong_rules(prolong_[l - 1], mask[l - 1], rank, &linear[l - 1], rim[l - 1])) return false;
       }
       const void* mine[4] = {L.x, L.b, L.q, L.minv};
       const size_t bytes = box_bytes(box[l], elem);
@@ -422,7 +466,8 @@ struct Solve {
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = cycle(l + 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
+    rc = linear[l] ? do_prolong_linear(dtype, mask[l], box[l], box[l + 1], rim[l], Cl.x, F.x, stream)
+                   : do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
     return sweeps(l, post, true);
   }
@@ -957,6 +1002,22 @@ int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t* g_fine
   return do_prolong(dtype, mask, F, Cb, x_coarse, x_fine, reinterpret_cast<hipStream_t>(stream));
 }
 
+int neptune_hip_mg_prolong_add_linear(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
+                                      const neptune_hip_mg_prolong_t* p, const void* x_coarse, void* x_fine, void* stream) {
+  if (!g_fine || !g_coarse || !p || !x_coarse || !x_fine || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  MgBox F, Cb;
+  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
+  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
+  if (!mask) return NEPTUNE_HIP_EINVAL;
+  bool linear = false;
+  MgRim rim;
+  if (!prolong_rules(*p, mask, g_fine->rank, &linear, rim)) return NEPTUNE_HIP_EINVAL;
+  if (buffers_overlap(x_fine, box_bytes(F, elem_size(dtype)), x_coarse, box_bytes(Cb, elem_size(dtype)))) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return linear ? do_prolong_linear(dtype, mask, F, Cb, rim, x_coarse, x_fine, s) : do_prolong(dtype, mask, F, Cb, x_coarse, x_fine, s);
+}
+
 int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse, int* mask_out) {
   if (!g_fine || !g_coarse || !mask_out) return NEPTUNE_HIP_EINVAL;
   MgBox F, Cb;
@@ -994,6 +1055,14 @@ int neptune_hip_mg_solve_lines(const neptune_hip_mg_level_t* levels, const neptu
                                int pre, int post, int coarse_sweeps, int64_t max_cycles, int64_t check_every, double tol2,
                                double* rr_checks, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done,
                                double* rr0, double* rr_last) {
+  return neptune_hip_mg_solve_prolong(levels, lines, nullptr, n_levels, dtype, pre, post, coarse_sweeps, max_cycles, check_every, tol2,
+                                      rr_checks, stream, cfg, cycles_done, rr0, rr_last);
+}
+
+int neptune_hip_mg_solve_prolong(const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines,
+                                 const neptune_hip_mg_prolong_t* prolong, int n_levels, int dtype, int pre, int post, int coarse_sweeps,
+                                 int64_t max_cycles, int64_t check_every, double tol2, double* rr_checks, void* stream,
+                                 const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done, double* rr0, double* rr_last) {
   g_mg_counts[0] = g_mg_counts[1] = g_mg_counts[2] = 0;
   if (cycles_done) *cycles_done = 0;
   if (rr0) *rr0 = 0.0;
@@ -1001,7 +1070,7 @@ int neptune_hip_mg_solve_lines(const neptune_hip_mg_level_t* levels, const neptu
   // ---- the refusals, before anything touches the device
   if (check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
   Solve S;
-  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg, lines)) return NEPTUNE_HIP_EINVAL;
+  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg, lines, prolong)) return NEPTUNE_HIP_EINVAL;
   const size_t elem = elem_size(dtype);
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;

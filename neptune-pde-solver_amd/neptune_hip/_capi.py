@@ -30,6 +30,8 @@ REDUCE_KINDS = {"sum": REDUCE_SUM, "max": REDUCE_MAX, "min": REDUCE_MIN, "l1": R
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_MARCH = 0, 1, 2
 FLAG_DIRECT_FLAT = 1   # direct kernel: flat one-lane-per-cell form instead of the rows form
 BODY_LAP2D5_F64, BODY_LAP3D7_F64, BODY_LAP3D27_F32, BODY_LAP1D3_F64 = 0, 1, 2, 3
+MG_PROLONG_CONSTANT, MG_PROLONG_LINEAR = 0, 1   # neptune_hip_mg_prolong_t.kind
+MG_RIM_EVEN, MG_RIM_ODD = 0, 1                   # ... and its rule per face: a Neumann face / the value 0 on the face
 
 ERROR_NAMES = {EINVAL: "NEPTUNE_HIP_EINVAL", EUNSUPPORTED: "NEPTUNE_HIP_EUNSUPPORTED", EOOB: "NEPTUNE_HIP_EOOB",
                ECOMM: "NEPTUNE_HIP_ECOMM"}
@@ -66,6 +68,11 @@ class MgLevel(C.Structure):
     """neptune_hip_mg_level_t: one level of a multigrid hierarchy"""
     _fields_ = [("fn", C.c_void_p), ("body", C.c_int), ("g", ApplyGeom), ("in_rest", C.POINTER(C.c_void_p)),
                 ("minv", C.c_void_p), ("x", C.c_void_p), ("b", C.c_void_p), ("q", C.c_void_p), ("rscale", C.c_double)]
+
+
+class MgProlong(C.Structure):
+    """neptune_hip_mg_prolong_t: the prolongation of one pair of levels; the rules per face are indexed by field dimension"""
+    _fields_ = [("kind", C.c_int32), ("rim_lo", C.c_int32 * 3), ("rim_hi", C.c_int32 * 3)]
 
 
 class MgLines(C.Structure):
@@ -156,6 +163,10 @@ SIGNATURES = {
     "neptune_hip_mg_line_smooth": (_i, [_i, _geom_p, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "neptune_hip_mg_solve_lines": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), _i, _i, _i, _i, _i, _i64, _i64, _dbl,
                                         C.POINTER(C.c_double), _vp, _cfg_p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mg_prolong_add_linear": (_i, [_i, _geom_p, _geom_p, C.POINTER(MgProlong), _vp, _vp, _vp]),
+    "neptune_hip_mg_solve_prolong": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), C.POINTER(MgProlong), _i, _i, _i, _i, _i, _i64, _i64,
+                                          _dbl, C.POINTER(C.c_double), _vp, _cfg_p, _i64p, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
     "neptune_hip_mg_coarsened_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
     "neptune_hip_mg_halved_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
     "neptune_hip_mg_counts": (None, [_i64p, _i64p, _i64p]),

@@ -33,6 +33,11 @@ conditions live in the operator (e.g. face coefficients that vanish on a Neumann
 centring="cell") and coarsening_plan(..., centring="cell") give the extents, Hierarchy.halved records what it found; one
 pair is one grid kind (halved and coarsened dimensions do not mix in a pair; kept ones mix with either).  The pure-Neumann
 problem is singular: b must sum to zero over Omega, and the mean of x is whatever the iteration leaves.
+
+Linear prolongation on cell-centred pairs: Level(..., prolong="linear", faces="dirichlet" | "neumann" | one
+(low, high) pair per dimension) interpolates with the weights 3/4 and 1/4 and the stated rule per face; plain cycles
+(solve) are then grid-independent where the constant prolongation is not.  The cycle is no longer a symmetric
+preconditioner: cg_solve and cg_solve_mixed refuse such a hierarchy.
 """
 from __future__ import annotations
 
@@ -268,10 +273,16 @@ class Level:
     Omega, e.g. jacobi_weights; required before a solve), the factor `rscale` of the restriction that leaves this level
     (4 for an operator that is not scaled by 1 / h^2: the coarse operator is then the fine one's stencil), the launch
     `region` (result-physical, default: the whole box) and `lines`: up to three LineStages (line_weights) that replace the
-    point sweep on this level; minv may be omitted when lines is given."""
+    point sweep on this level; minv may be omitted when lines is given.
+    prolong, faces describe the prolongation of the pair that LEAVES this level (ignored on the last one): "constant", what
+    the pair's grid kind implies, or "linear" (a cell-centred pair only), which needs the rule per face:
+    faces = "neumann" or "dirichlet" (the value 0 on the face) for all faces, or one (low, high) pair of these per
+    dimension.  Hierarchy checks both."""
 
     def __init__(self, entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), minv: Optional[DeviceField] = None,
-                 rscale: float = 4.0, region: Optional[Box] = None, lines: Sequence[LineStage] = ()):
+                 rscale: float = 4.0, region: Optional[Box] = None, lines: Sequence[LineStage] = (), prolong: str = "constant",
+                 faces=None):
+        self.prolong, self.faces = prolong, faces
         self.lines = [LineStage(*st) for st in lines]
         if len(self.lines) > 3:
             raise ValueError("Level: at most three line stages")
@@ -292,6 +303,45 @@ class Level:
     def omega(self):
         """numpy / torch index of Omega in the level's fields"""
         return tuple(slice(l, h) for l, h in zip(self.lo, self.hi))
+
+    @property
+    def linear(self) -> bool:
+        return self.prolong == "linear"
+
+    def prolong_struct(self) -> _capi.MgProlong:
+        """neptune_hip_mg_prolong_t of the pair that leaves this level; ValueError for a malformed prolong / faces"""
+        p = _capi.MgProlong()
+        if self.prolong not in ("constant", "linear"):
+            raise ValueError(f'prolong is "constant" or "linear", not {self.prolong!r}')
+        if not self.linear:
+            p.kind = _capi.MG_PROLONG_CONSTANT
+            return p
+        p.kind = _capi.MG_PROLONG_LINEAR
+        lo, hi = face_rules(self.faces, self.like.rank)
+        for d in range(self.like.rank):
+            p.rim_lo[d], p.rim_hi[d] = lo[d], hi[d]
+        return p
+
+
+_FACE_RULE = {"neumann": _capi.MG_RIM_EVEN, "dirichlet": _capi.MG_RIM_ODD}
+
+
+def face_rules(faces, rank: int):
+    """the linear prolongation's rule per face from `faces`: "neumann" / "dirichlet" for all faces, or a
+    sequence of `rank` (low, high) pairs of them; -> (low rules, high rules) per dimension as _capi.MG_RIM_EVEN / _ODD;
+    ValueError for anything else"""
+    if faces is None:
+        raise ValueError('prolong="linear" needs faces ("neumann", "dirichlet", or a (low, high) pair of them per dimension)')
+    if isinstance(faces, str):
+        faces = [(faces, faces)] * rank
+    try:
+        pairs = [tuple(f) for f in faces]
+    except TypeError:
+        pairs = None
+    if (pairs is None or len(pairs) != rank or any(len(f) != 2 or isinstance(f, str) for f in faces)
+            or any(not isinstance(v, str) or v not in _FACE_RULE for f in pairs for v in f)):
+        raise ValueError(f'faces is "neumann", "dirichlet", or {rank} (low, high) pairs of them (one per dimension), not {faces!r}')
+    return [_FACE_RULE[f[0]] for f in pairs], [_FACE_RULE[f[1]] for f in pairs]
 
 
 class Hierarchy:
@@ -333,6 +383,14 @@ class Hierarchy:
                     raise ValueError(f"Hierarchy: level {l} coarsens no dimension of level {l - 1}")
                 self.coarsened.append(tuple(axes or halved))
                 self.halved.append(tuple(halved))
+                above = self.levels[l - 1]
+                try:
+                    above.prolong_struct()
+                except ValueError as err:
+                    raise ValueError(f"Hierarchy: level {l - 1}: {err}") from None
+                if above.linear and not halved:
+                    raise ValueError(f'Hierarchy: level {l - 1}: prolong="linear" needs a cell-centred pair, but no dimension is '
+                                     f"halved towards level {l} (m_fine = 2 m_coarse)")
         self.dtype, self.rank = first.like.dtype, first.like.rank
         self.q = [DeviceField.empty_like(L.like) for L in self.levels]
         self.x = [None] + [DeviceField.empty_like(L.like) for L in self.levels[1:]]
@@ -368,6 +426,18 @@ class Hierarchy:
     def has_lines(self) -> bool:
         return any(L.lines for L in self.levels)
 
+    @property
+    def has_linear(self) -> bool:
+        """whether any pair of levels prolongs linearly (the last level's setting is ignored)"""
+        return any(L.linear for L in self.levels[:-1])
+
+    def _prolong_structs(self):
+        """-> the C array of neptune_hip_mg_prolong_t, entry l for the pair (l, l + 1)"""
+        arr = (_capi.MgProlong * max(len(self.levels) - 1, 1))()
+        for l, L in enumerate(self.levels[:-1]):
+            arr[l] = L.prolong_struct()
+        return arr
+
     def _line_structs(self):
         """-> the C array of neptune_hip_mg_lines_t, one per level (the factor fields stay alive in the levels)"""
         arr = (_capi.MgLines * len(self.levels))()
@@ -390,7 +460,7 @@ def counts():
 def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int = 2, coarse_sweeps: int = 8, max_cycles: int = 20,
           tol2: float = 0.0, check_every: int = 1, cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
     """solve A_0(x) = b by V(pre, post) cycles over the hierarchy `h` (neptune_hip_mg_solve; neptune_hip_mg_solve_lines when
-    any level has line stages).  x: initial guess in, solution
+    any level has line stages; neptune_hip_mg_solve_prolong when any pair prolongs linearly).  x: initial guess in, solution
     out; its cells outside Omega_0 are boundary data and are never written.  The loop stops when r . r <= tol2 (checked every
     `check_every` cycles) or after max_cycles cycles.  cfg: the launch configuration of level 0's operator.
     Blocking; -> (cycles, rr0, rr_last, rr_checks): rr_checks is the list of r . r values read after each block of cycles.
@@ -406,12 +476,20 @@ def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int 
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
     rest = (pre, post, coarse_sweeps, max_cycles, check_every, tol2, rr, st, C.byref(cfg) if cfg is not None else None,
             C.byref(done), C.byref(rr0), C.byref(last))
-    if h.has_lines:
+    if h.has_linear:
+        _capi.check(lib.neptune_hip_mg_solve_prolong(arr, h._line_structs() if h.has_lines else None, h._prolong_structs(), len(h),
+                                                     h.dtype, *rest), "neptune_hip_mg_solve_prolong")
+    elif h.has_lines:
         _capi.check(lib.neptune_hip_mg_solve_lines(arr, h._line_structs(), len(h), h.dtype, *rest), "neptune_hip_mg_solve_lines")
     else:
         _capi.check(lib.neptune_hip_mg_solve(arr, len(h), h.dtype, *rest), "neptune_hip_mg_solve")
     del keep
     return done.value, rr0.value, last.value, list(rr[:counts()[2]])
+
+
+_NOT_SYMMETRIC = ("multigrid.{}: the hierarchy has a pair with prolong=\"linear\": with the averaging restriction P is not a "
+                  "multiple of R^T, so the V-cycle would not be a symmetric preconditioner and conjugate gradients do not apply; "
+                  "use multigrid.solve, or prolong=\"constant\"")
 
 
 def cg_counts():
@@ -449,6 +527,8 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
         raise ValueError("multigrid.cg_solve: x and b must have the box and the element type of level 0")
     if len(h) < 2:
         raise ValueError("multigrid.cg_solve: at least two levels (one level is apply.cg_solve with minv)")
+    if h.has_linear:
+        raise ValueError(_NOT_SYMMETRIC.format("cg_solve"))
     if h.has_lines and not lines:
         raise ValueError("multigrid.cg_solve: the hierarchy has line stages; neptune_hip_mgcg_solve smooths with point Jacobi "
                          "only (its fused first and last sweeps on level 0): pass lines=True for neptune_hip_mgcg_solve_lines")
@@ -507,6 +587,8 @@ def cg_solve_mixed(outer: Level, inner: Hierarchy, x: DeviceField, b: DeviceFiel
         raise ValueError("multigrid.cg_solve_mixed: level 0 of the inner hierarchy must have the box and the Omega of the outer level")
     if len(inner) < 2:
         raise ValueError("multigrid.cg_solve_mixed: at least two inner levels")
+    if inner.has_linear:
+        raise ValueError(_NOT_SYMMETRIC.format("cg_solve_mixed"))
     if first.lines:
         raise ValueError("multigrid.cg_solve_mixed: line stages on level 0 are not supported (levels >= 1 may have them)")
     for name in ("x", "b"):
@@ -656,7 +738,13 @@ def restrict(fine: Level, coarse: Level, b_fine: DeviceField, q_fine: DeviceFiel
 
 def prolong_add(fine: Level, coarse: Level, x_coarse: DeviceField, x_fine: DeviceField, stream: Optional[int] = None) -> None:
     """x_fine = x_fine + P(x_coarse) on the fine Omega (neptune_hip_mg_prolong_add); P interpolates along the dimensions
-    the pair coarsens and is the identity along the kept ones; asynchronous"""
+    the pair coarsens and is the identity along the kept ones; asynchronous.  fine.prolong = "linear": the linear
+    prolongation of a cell-centred pair by fine.faces (neptune_hip_mg_prolong_add_linear)"""
     st = current_stream_ptr() if stream is None else stream
+    if fine.linear:
+        _capi.check(_capi.load().neptune_hip_mg_prolong_add_linear(x_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom),
+                                                                   C.byref(fine.prolong_struct()), x_coarse.ptr, x_fine.ptr, st),
+                    "neptune_hip_mg_prolong_add_linear")
+        return
     _capi.check(_capi.load().neptune_hip_mg_prolong_add(x_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom), x_coarse.ptr,
                                                         x_fine.ptr, st), "neptune_hip_mg_prolong_add")
