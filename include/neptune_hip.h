@@ -551,8 +551,24 @@ int neptune_hip_bicgstab_solve(neptune_hip_apply_fn fn, neptune_hip_apply_dot_fn
  *   then  x_l = x_l + t  on Omega_l.  The rule is given per face, low and high, per dimension.  In the tensor product the
  *   ghost of a later dimension is +- the INTERMEDIATE at the edge (what padding the intermediate array gives).  m_c = 1
  *   makes both neighbours ghosts.  No coarse cell outside Omega_(l+1) is read, no fine cell outside Omega_l is written;
- *   along a kept dimension the transfer is the identity.  The restriction stays the averaging one, so P != c R^T and the
- *   cycle is NOT a symmetric preconditioner: the neptune_hip_mgcg_* entries take no such pair.
+ *   along a kept dimension the transfer is the identity.  With the averaging restriction P != c R^T and the cycle is NOT a
+ *   symmetric preconditioner: the neptune_hip_mgcg_* entries take such a pair only with the restriction below.
+ * TRANSPOSED LINEAR RESTRICTION OF A CELL-CENTRED PAIR, chosen per pair by the caller
+ * (neptune_hip_mg_transfer_t below; the default stays the averaging one above): R = P^T / 2^k for k halved dimensions, P the
+ * linear prolongation above BY THE SAME RULE PER FACE.  The arithmetic rules are the ones above: T, one rounding per
+ * operation, no FMA, named temporaries, dimension rank-1, then rank-2, then rank-3, kept ones the identity.  Fused with the
+ * residual as the other restrictions:  d = b - q on the fine Omega.  Along one halved dimension let a[0 .. 2 m_c) be the
+ * values AFTER the dimensions already done.  For the coarse index j:
+ *     a_m = a[2 j - 1]   if j >= 1,          else  +a[0] (rule_lo EVEN)  or  -a[0] (rule_lo ODD)
+ *     a_p = a[2 j + 2]   if j <= m_c - 2,    else  +a[2 m_c - 1] (rule_hi EVEN)  or  -a[2 m_c - 1] (rule_hi ODD)
+ *     s_m = 0.25 * a_m;   p_0 = 0.75 * a[2 j];   p_1 = 0.75 * a[2 j + 1];   s_p = 0.25 * a_p
+ *     u = s_m + p_0;   v = p_1 + s_p;   w = u + v;   t = 0.5 * w
+ *   then  b_(l+1) = rscale_l * t  and  x_(l+1) = +0  on Omega_(l+1).  The ghost is an exact sign flip.  In the tensor
+ *   product a later dimension's ghost is +- the INTERMEDIATE at the edge: padding the fine array with +- its edge is exactly
+ *   the transpose of padding the coarse array with +- its edge.  m_c = 1 makes both outer operands ghosts.  No fine cell
+ *   outside Omega_l is read, no coarse cell outside Omega_(l+1) is written.  In exact arithmetic this is P^T / 2 per halved
+ *   dimension: interior weights 1/8, 3/8, 3/8, 1/8; end weights 1/2, 3/8, 1/8 under EVEN and 1/4, 3/8, 1/8 under ODD.  With
+ *   the LINEAR prolongation the pair satisfies P = 2^k R^T and the V-cycle is a symmetric preconditioner again.
  * Along a kept dimension both transfers are the identity -- no operation, no rounding, -0 and NaN keep their bits: the
  * restriction hands d = b - q through to the next dimension, the prolongation takes e[j] itself, and there is no rim
  * along it.  The coarsened dimensions run in the order stated below, the kept ones skipped.  With every dimension
@@ -695,6 +711,29 @@ int neptune_hip_mg_solve_prolong(const neptune_hip_mg_level_t *levels, const nep
                                  int coarse_sweeps, int64_t max_cycles, int64_t check_every, double tol2, double *rr_checks,
                                  void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *cycles_done, double *rr0,
                                  double *rr_last);
+/* Both transfers of one pair of levels: `prolong` as neptune_hip_mg_prolong_t's kind, restrict_kind the
+ * restriction, and ONE rule array for both -- a pair that restricts by one rule and prolongs by another cannot be expressed.
+ * The rules are read when either transfer is LINEAR; entries of dimensions >= rank never. */
+#define NEPTUNE_HIP_MG_RESTRICT_AVERAGE 0   /* what neptune_hip_mg_restrict does for the pair's grid kind */
+#define NEPTUNE_HIP_MG_RESTRICT_LINEAR  1   /* the transpose of the LINEAR prolongation, by the same face rules */
+typedef struct { int32_t prolong, restrict_kind; int32_t rim_lo[3], rim_hi[3]; } neptune_hip_mg_transfer_t;
+/* The restriction kernel alone, by *t (asynchronous on `stream`): restrict_kind AVERAGE is neptune_hip_mg_restrict exactly;
+ * t->prolong is validated and otherwise unused.  The refusals of neptune_hip_mg_restrict, and NEPTUNE_HIP_EINVAL, nothing
+ * launched, for t = NULL, a prolong or restrict_kind outside {0, 1}, a LINEAR transfer on a pair with no halved dimension, a
+ * rule outside {0, 1} on a dimension < rank when either transfer is LINEAR. */
+int neptune_hip_mg_restrict_linear(int dtype, const neptune_hip_apply_geom_t *g_fine, const neptune_hip_apply_geom_t *g_coarse,
+                                   const neptune_hip_mg_transfer_t *t, const void *b_fine, const void *q_fine, double rscale,
+                                   void *b_coarse, void *x_coarse, void *stream);
+/* neptune_hip_mg_solve_lines with both transfers chosen per pair: transfer[l] belongs to the pair (l, l + 1), n_levels - 1
+ * entries are read; any combination is accepted per pair.  transfer == NULL, or CONSTANT / AVERAGE everywhere, is
+ * neptune_hip_mg_solve_lines exactly -- the same launches, the same bits; neptune_hip_mg_solve_prolong is this call with
+ * AVERAGE everywhere.  NEPTUNE_HIP_EINVAL, nothing launched, every field's bits unchanged: the refusals of
+ * neptune_hip_mg_solve_lines and those of neptune_hip_mg_restrict_linear for any pair. */
+int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines,
+                                  const neptune_hip_mg_transfer_t *transfer, int n_levels, int dtype, int pre, int post,
+                                  int coarse_sweeps, int64_t max_cycles, int64_t check_every, double tol2, double *rr_checks,
+                                  void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *cycles_done, double *rr0,
+                                  double *rr_last);
 
 /* TWO MORE FORMS OF THE STAGE'S KERNEL, alone (asynchronous on `stream`).  ARITHMETIC as above.
  * neptune_hip_mg_line_first is the APPLY-FREE stage: the values of the plain stage run on q = +0, x = +0 --
@@ -794,6 +833,18 @@ int neptune_hip_mgcg_solve_lines(const neptune_hip_mg_level_t *levels, const nep
                                  void *const work[3], int64_t max_iters, int64_t check_every, double tol2, void *trace,
                                  void *stream, const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0,
                                  double *rr_last);
+/* neptune_hip_mgcg_solve_lines with the transfers chosen per pair: transfer as in
+ * neptune_hip_mg_solve_transfer, but a pair is accepted only if it is SYMMETRIC -- CONSTANT with AVERAGE, or LINEAR with
+ * LINEAR --, so that the cycle stays a symmetric preconditioner; both level-0 seams of the iteration (the restriction and
+ * the prolongation of "the rest of M") follow pair 0's choice.  transfer == NULL, or CONSTANT / AVERAGE everywhere, is
+ * neptune_hip_mgcg_solve_lines exactly -- the same launches, the same bits -- and neptune_hip_mgcg_solve_lines is this call
+ * with NULL.  NEPTUNE_HIP_EINVAL, nothing launched, every field's bits unchanged: the refusals of
+ * neptune_hip_mgcg_solve_lines, those of neptune_hip_mg_restrict_linear for any pair, and an asymmetric pair. */
+int neptune_hip_mgcg_solve_transfer(const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines,
+                                    const neptune_hip_mg_transfer_t *transfer, int n_levels, int dtype,
+                                    neptune_hip_apply_dot_fn fn_dot, int sweeps, int coarse_sweeps, void *const work[3],
+                                    int64_t max_iters, int64_t check_every, double tol2, void *trace, void *stream,
+                                    const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0, double *rr_last);
 /* MIXED PRECISION: conjugate gradients in D = f64 around the preconditioner's V-cycle in S = f32.  Only
  * (dtype_outer, dtype_inner) = (NEPTUNE_HIP_F64, NEPTUNE_HIP_F32) is accepted.  Arithmetic as everywhere: one rounding per
  * operation, no FMA, every intermediate a named temporary, sums on the fixed tree of the monitored launches, no atomics;
@@ -839,6 +890,15 @@ int neptune_hip_mgcg_solve_mixed(const neptune_hip_mg_level_t *outer, int dtype_
                                  int dtype_inner, int sweeps, int coarse_sweeps, void *const work[2], int64_t max_iters,
                                  int64_t check_every, double tol2, void *trace, void *stream,
                                  const neptune_hip_launch_cfg_t *cfg, int64_t *iters_done, double *rr0, double *rr_last);
+/* neptune_hip_mgcg_solve_mixed with the inner hierarchy's transfers chosen per pair, under the rule of
+ * neptune_hip_mgcg_solve_transfer (symmetric pairs only; NULL or all-default is neptune_hip_mgcg_solve_mixed exactly, which is
+ * this call with NULL); the same additional refusals. */
+int neptune_hip_mgcg_solve_mixed_transfer(const neptune_hip_mg_level_t *outer, int dtype_outer, neptune_hip_apply_dot_fn fn_dot,
+                                          const neptune_hip_mg_level_t *levels, const neptune_hip_mg_lines_t *lines,
+                                          const neptune_hip_mg_transfer_t *transfer, int n_levels, int dtype_inner, int sweeps,
+                                          int coarse_sweeps, void *const work[2], int64_t max_iters, int64_t check_every,
+                                          double tol2, void *trace, void *stream, const neptune_hip_launch_cfg_t *cfg,
+                                          int64_t *iters_done, double *rr0, double *rr_last);
 /* neptune_hip_mg_smooth_dot with a wide sum, alone: the sweep in `dtype` exactly as neptune_hip_mg_smooth (the same bits in
  * x), and *dot_out = sum over Omega of widen(b) * widen(x_new) in `dtype_sum` -- each term exact.  (dtype, dtype_sum) =
  * (NEPTUNE_HIP_F32, NEPTUNE_HIP_F64) only.  dot_out: a DEVICE pointer to one double; otherwise as neptune_hip_mg_smooth_dot. */

@@ -6,6 +6,7 @@
 //   neptune_mg_prolong_add   x_f = x_f + P(x_c) on the fine Omega                     reads and writes x_f; reads x_c through L1
 //   neptune_mg_restrict_cell / neptune_mg_prolong_add_cell   the two transfers of a cell-centred pair (at the end)
 //   neptune_mg_prolong_add_linear   the linear prolongation of a cell-centred pair, weights 3/4 and 1/4, a rule per face
+//   neptune_mg_restrict_linear      its transpose / 2^k as the restriction, by the same rules
 //
 // Grids: vertex-centred, Dirichlet rim.  Per pair of levels every dimension is either COARSENED, m_fine = 2 m_coarse + 1: the
 // coarse cell of interior index j sits on the fine cell of interior index 2 j + 1 (interior indices count from Omega's lower
@@ -24,6 +25,7 @@
 // Templates only: the translation unit that holds the solver instantiates them.
 #pragma once
 #include "apply_common.hpp"
+#include "apply_march.hpp"   // the wave shifts from_prev / from_next
 
 namespace neptune_hip {
 
@@ -442,6 +444,127 @@ __global__ __launch_bounds__(256) void neptune_mg_prolong_add_linear(MgBox F, Mg
   } else {
     const int64_t o = mg_at(F, fi, fj, k);
     x_f[o] = x_f[o] + e[0];
+  }
+}
+
+// ================================================================ transposed linear restriction on a cell-centred pair
+// R = P^T / 2 per halved axis, P the linear prolongation above with the same rule per face.  Along a halved axis the coarse
+// cell j takes the four fine values a[2 j - 1 .. 2 j + 2] with the weights 1/4, 3/4, 3/4, 1/4 and half of their sum; an outer
+// operand outside the fine Omega is the ghost +a[edge] (EVEN) or -a[edge] (ODD) -- padding the fine array with +- its edge is
+// the transpose of padding the coarse one.  a is the intermediate after the axes already done (axis 2, then 1, then 0).
+template <class T>
+__device__ __forceinline__ T mg_lin4(T am, T a0, T a1, T ap) {
+  const T sm = (T)0.25 * am;
+  const T p0 = (T)0.75 * a0;
+  const T p1 = (T)0.75 * a1;
+  const T sp = (T)0.25 * ap;
+  const T u = sm + p0;
+  const T v = p1 + sp;
+  const T w = u + v;
+  return (T)0.5 * w;
+}
+// The lane's value of ONE fine row after axis 2; b_row, q_row: the row's first Omega cell.  Called by all 256 lanes together.
+//   halved: the lane owns the coarse index ck, loads the pair d[2 ck], d[2 ck + 1] (d = b - q; one access of 2 sizeof(T) where
+//     the row is aligned to that, workgroup-uniform) and takes d[2 ck - 1], d[2 ck + 2] from the neighbouring lanes' pairs by
+//     a wave shift; lane 0 and lane 63 of a wave load their one extra cell (`edge` of the shift).  The lanes ck = 0 and
+//     ck = m_c - 1 take the ghost instead: a per-lane select.  A lane without a cell (ck >= m_c) loads nothing.
+//   kept: d[ck] itself.
+template <class T, bool H2>
+__device__ __forceinline__ T mg_lin_row(const T* __restrict__ b_row, const T* __restrict__ q_row, int64_t ck, int64_t m_c, bool owns,
+                                        int lane, int32_t rule_lo, int32_t rule_hi) {
+  if constexpr (!H2) {
+    return owns ? b_row[ck] - q_row[ck] : (T)0;
+  } else {
+    const bool aligned = (((uintptr_t)b_row | (uintptr_t)q_row) & (2 * sizeof(T) - 1)) == 0;
+    const bool first = ck == 0, last = ck + 1 == m_c;
+    T d0 = (T)0, d1 = (T)0, em = (T)0, ep = (T)0;
+    if (owns) {
+      T b0, b1, q0, q1;
+      mg_load_pair(b_row + 2 * ck, aligned, b0, b1);
+      mg_load_pair(q_row + 2 * ck, aligned, q0, q1);
+      d0 = b0 - q0;
+      d1 = b1 - q1;
+      if (lane == 0 && !first) em = b_row[2 * ck - 1] - q_row[2 * ck - 1];
+      if (lane == kWave - 1 && !last) ep = b_row[2 * ck + 2] - q_row[2 * ck + 2];
+    }
+    T am = from_prev<true>(d1, em, lane);
+    T ap = from_next<true>(d0, ep, lane);
+    if (first) am = rule_lo != 0 ? -d0 : d0;
+    if (last) ap = rule_hi != 0 ? -d1 : d1;
+    return mg_lin4(am, d0, d1, ap);
+  }
+}
+
+// The workgroup owns one 256-cell chunk along axis 2 of the coarse plane ci and MARCHES a run of kMgLinearRun coarse rows
+// along axis 1.  Axis 1 halved: coarse row cj needs the fine rows 2 cj - 1 .. 2 cj + 2, of which two were the previous step's;
+// per fine plane the last four axis-2 results stay in registers (ring), so a step loads two new fine rows per plane and a
+// fine row is loaded once per workgroup along that axis (twice where two runs meet).  Axis 0 halved: the four fine planes
+// 2 ci - 1 .. 2 ci + 2 are read directly, each carrying its own ring; the two coarse planes that share a fine plane fetch it
+// twice unless a cache holds it (the pass model is in DESIGN 3.23).  A ghost row or plane is never loaded: it is +- the
+// intermediate of the edge row / plane, workgroup-uniform scalar work.  No fine cell outside Omega is read, no coarse cell
+// outside Omega is written.  No LDS, no barrier, no atomics; every lane stays in the loop (the wave shifts need them all).
+constexpr int kMgLinearRun = 8;
+template <class T, int MASK>
+__global__ __launch_bounds__(256) void neptune_mg_restrict_linear(MgBox F, MgBox Cb, int64_t nchunk, MgRim rim, const T* __restrict__ b_f,
+                                                                  const T* __restrict__ q_f, T rscale, T* __restrict__ b_c,
+                                                                  T* __restrict__ x_c) {
+  static_assert(MASK > 0 && MASK < 8, "at least one axis halved");
+  constexpr bool H0 = (MASK & 1) != 0, H1 = (MASK & 2) != 0, H2 = (MASK & 4) != 0;
+  constexpr int NI = H0 ? 4 : 1, NJ = H1 ? 4 : 1;
+  const int64_t nrun = (Cb.m[1] + kMgLinearRun - 1) / kMgLinearRun;
+  const int64_t blk = linear_block();
+  if (blk >= Cb.m[0] * nrun * nchunk) return;   // workgroup-uniform
+  const int64_t pr = blk / nchunk, c = blk - pr * nchunk;
+  const int64_t ci = pr / nrun, cj0 = (pr - ci * nrun) * kMgLinearRun;
+  const int64_t cj1 = cj0 + kMgLinearRun < Cb.m[1] ? cj0 + kMgLinearRun : Cb.m[1];
+  const int64_t ck = c * 256 + threadIdx.x;
+  const bool owns = ck < Cb.m[2];
+  const int lane = threadIdx.x & (kWave - 1);
+  // plane a of the NI is the fine plane fi0 + a; the outer ones are ghosts on the first / last coarse plane
+  const bool glo0 = H0 && ci == 0, ghi0 = H0 && ci + 1 == Cb.m[0];
+  const int64_t fi0 = H0 ? 2 * ci - 1 : ci;
+  auto row = [&](int64_t fi, int64_t fj) {
+    const int64_t o = mg_at(F, fi, fj, 0);
+    return mg_lin_row<T, H2>(b_f + o, q_f + o, ck, Cb.m[2], owns, lane, rim.lo[2], rim.hi[2]);
+  };
+  T ring[NI][NJ];
+  for (int64_t cj = cj0; cj < cj1; ++cj) {
+    const bool glo1 = H1 && cj == 0, ghi1 = H1 && cj + 1 == Cb.m[1];
+    const int64_t fj0 = H1 ? 2 * cj - 1 : cj;   // slot r of the ring is the fine row fj0 + r
+    T pa[NI];
+#pragma unroll
+    for (int a = 0; a < NI; ++a) {
+      if ((a == 0 && glo0) || (a == NI - 1 && ghi0)) continue;
+      if constexpr (H1) {
+        if (cj == cj0) {
+          if (!glo1) ring[a][0] = row(fi0 + a, fj0);
+          ring[a][1] = row(fi0 + a, fj0 + 1);
+        } else {
+          ring[a][0] = ring[a][2];
+          ring[a][1] = ring[a][3];
+        }
+        ring[a][2] = row(fi0 + a, fj0 + 2);
+        if (!ghi1) ring[a][3] = row(fi0 + a, fj0 + 3);
+        if (glo1) ring[a][0] = rim.lo[1] != 0 ? -ring[a][1] : ring[a][1];
+        if (ghi1) ring[a][3] = rim.hi[1] != 0 ? -ring[a][2] : ring[a][2];
+        pa[a] = mg_lin4(ring[a][0], ring[a][1], ring[a][2], ring[a][3]);
+      } else {
+        pa[a] = row(fi0 + a, fj0);
+      }
+    }
+    T t;
+    if constexpr (H0) {
+      if (glo0) pa[0] = rim.lo[0] != 0 ? -pa[1] : pa[1];
+      if (ghi0) pa[3] = rim.hi[0] != 0 ? -pa[2] : pa[2];
+      t = mg_lin4(pa[0], pa[1], pa[2], pa[3]);
+    } else {
+      t = pa[0];
+    }
+    if (owns) {
+      const int64_t oc = mg_at(Cb, ci, cj, ck);
+      b_c[oc] = rscale * t;
+      x_c[oc] = (T)0;
+    }
   }
 }
 

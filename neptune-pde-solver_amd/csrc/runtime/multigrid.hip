@@ -14,7 +14,11 @@
 // dispatch on it -- everything else here is the same code for both.  A cell-centred pair may prolong linearly instead, by a rule
 // per face that the caller states: neptune_hip_mg_prolong_add_linear launches that kernel alone,
 // neptune_hip_mg_solve_prolong is the plain-cycle driver with the choice per pair, and neptune_hip_mg_solve_lines is that call
-// without any; the MGCG drivers take none (the cycle would not be a symmetric preconditioner).
+// without any.  The restriction of such a pair may be the transpose of that prolongation: one
+// neptune_hip_mg_transfer_t per pair states both transfers and the one rule array they share; neptune_hip_mg_restrict_linear
+// launches that kernel alone, neptune_hip_mg_solve_transfer is the plain-cycle driver (neptune_hip_mg_solve_prolong is that
+// call with the averaging restriction everywhere), and the neptune_hip_mgcg_*_transfer drivers take a pair only when it is
+// symmetric -- CONSTANT with AVERAGE, or LINEAR with LINEAR; the older MGCG entries are those calls without an array.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -149,6 +153,16 @@ int prolong_linear_launch(const MgBox& F, const MgBox& Cb, const MgRim& rim, con
                      static_cast<T*>(x_f));
   return launched();
 }
+// The transposed linear restriction of a cell-centred pair: one workgroup per 256-cell chunk of a run of
+// kMgLinearRun coarse rows of one coarse plane
+template <class T, int MASK>
+int restrict_linear_launch(const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* b_f, const void* q_f, double rscale, void* b_c,
+                           void* x_c, hipStream_t stream) {
+  const int64_t nchunk = (Cb.m[2] + 255) / 256, nrun = (Cb.m[1] + kMgLinearRun - 1) / kMgLinearRun;
+  hipLaunchKernelGGL((neptune_mg_restrict_linear<T, MASK>), grid_for_blocks(Cb.m[0] * nrun * nchunk), dim3(256), 0, stream, F, Cb, nchunk, rim,
+                     static_cast<const T*>(b_f), static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
+  return launched();
+}
 // One stage of the line smoother along box axis `axis`.  Axis 2: a one-wave workgroup per 64 lines.  A slow axis: a workgroup
 // per chunk of lanes along axis 2 and index of the other slow axis; 256 lanes wide where that still gives every CU two
 // workgroups, else 64 lanes, so that a small level (a 2-D field's lines along dim 0 have m[2] / width workgroups in all)
@@ -273,6 +287,14 @@ int do_prolong_linear(int dtype, int mask, const MgBox& F, const MgBox& Cb, cons
                    [&] { return prolong_linear_launch<float, M>(F, Cb, rim, x_c, x_f, s); });
   });
 }
+int do_restrict_linear(int dtype, int mask, const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* b_f, const void* q_f, double rscale,
+                       void* b_c, void* x_c, hipStream_t s) {
+  return by_mask(mask & 7, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    return by_type(dtype, [&] { return restrict_linear_launch<double, M>(F, Cb, rim, b_f, q_f, rscale, b_c, x_c, s); },
+                   [&] { return restrict_linear_launch<float, M>(F, Cb, rim, b_f, q_f, rscale, b_c, x_c, s); });
+  });
+}
 // What the caller states about the prolongation of one pair (sizes_nest's `mask`): -> false: refuse -- a kind outside
 // {CONSTANT, LINEAR}, LINEAR on a pair without a halved dimension, a rule outside {EVEN, ODD} on a dimension < rank of a
 // LINEAR pair.  *linear: the kind; rim: a LINEAR pair's rules on the kernels' axes (the dimensions right-aligned).
@@ -290,6 +312,25 @@ bool prolong_rules(const neptune_hip_mg_prolong_t& p, int mask, int rank, bool* 
     rim.hi[d + 3 - rank] = p.rim_hi[d];
   }
   return true;
+}
+
+// The same for both transfers of one pair: -> false: refuse -- what prolong_rules refuses of t.prolong, a
+// restrict_kind outside {AVERAGE, LINEAR}, LINEAR restriction on a pair without a halved dimension, a rule outside {EVEN,
+// ODD} on a dimension < rank when either transfer is LINEAR.  The one rule array serves both.  Nothing but the two kinds is
+// read of a CONSTANT / AVERAGE entry.
+bool transfer_rules(const neptune_hip_mg_transfer_t& t, int mask, int rank, bool* linear, bool* rlinear, MgRim& rim) {
+  if (t.prolong != NEPTUNE_HIP_MG_PROLONG_CONSTANT && t.prolong != NEPTUNE_HIP_MG_PROLONG_LINEAR) return false;
+  if (t.restrict_kind != NEPTUNE_HIP_MG_RESTRICT_AVERAGE && t.restrict_kind != NEPTUNE_HIP_MG_RESTRICT_LINEAR) return false;
+  *linear = t.prolong == NEPTUNE_HIP_MG_PROLONG_LINEAR;
+  *rlinear = t.restrict_kind == NEPTUNE_HIP_MG_RESTRICT_LINEAR;
+  neptune_hip_mg_prolong_t p;
+  p.kind = (*linear || *rlinear) ? NEPTUNE_HIP_MG_PROLONG_LINEAR : NEPTUNE_HIP_MG_PROLONG_CONSTANT;
+  for (int d = 0; d < 3; ++d) {
+    p.rim_lo[d] = t.rim_lo[d];
+    p.rim_hi[d] = t.rim_hi[d];
+  }
+  bool either = false;
+  return prolong_rules(p, mask, rank, &either, rim);
 }
 
 bool stream_capturing(void* stream) {
@@ -335,6 +376,7 @@ struct Solve {
   MgBox box[kMaxLevels];
   int mask[kMaxLevels];                  // mask[l]: how level l and l + 1 nest (sizes_nest: the axes, and the grid kind)
   bool linear[kMaxLevels];               // linear[l]: the pair (l, l + 1) prolongs linearly, by the rules rim[l]
+  bool rlinear[kMaxLevels];              // rlinear[l]: it restricts by the transpose of that prolongation, same rules
   MgRim rim[kMaxLevels];
   const neptune_hip_launch_cfg_t* cfg;   // level 0's, nullptr unless the caller set anything
   hipStream_t stream;
@@ -343,7 +385,7 @@ struct Solve {
   // filled in from them (all but `stream`); -> false: refuse
   bool check(const neptune_hip_mg_level_t* levels_, int n_levels_, int dtype_, int pre_, int post_, int coarse_sweeps_,
              const neptune_hip_launch_cfg_t* cfg_, const neptune_hip_mg_lines_t* lines_ = nullptr,
-             const neptune_hip_mg_prolong_t* prolong_ = nullptr) {
+             const neptune_hip_mg_transfer_t* transfer_ = nullptr, bool symmetric_only = false) {
     if (!levels_ || n_levels_ < 1 || n_levels_ > kMaxLevels || !known_dtype(dtype_)) return false;
     if (pre_ < 0 || post_ < 0 || coarse_sweeps_ < 0) return false;
     levels = levels_;
@@ -373,8 +415,9 @@ struct Solve {
       if (l > 0) {
         mask[l - 1] = sizes_nest(box[l - 1], box[l], rank);
         if (!mask[l - 1]) return false;
-        linear[l - 1] = false;
-        if (prolong_ && !prolong_rules(prolong_[l - 1], mask[l - 1], rank, &linear[l - 1], rim[l - 1])) return false;
+        linear[l - 1] = rlinear[l - 1] = false;
+        if (transfer_ && !transfer_rules(transfer_[l - 1], mask[l - 1], rank, &linear[l - 1], &rlinear[l - 1], rim[l - 1])) return false;
+        if (symmetric_only && linear[l - 1] != rlinear[l - 1]) return false;   // P must be a multiple of R^T
       }
       const void* mine[4] = {L.x, L.b, L.q, L.minv};
       const size_t bytes = box_bytes(box[l], elem);
@@ -454,20 +497,30 @@ struct Solve {
     }
     return NEPTUNE_HIP_OK;
   }
-  int cycle(int l) const {
-    if (l == n_levels - 1) return sweeps(l, coarse_sweeps);
+  // the two transfers of the pair (l, l + 1), each by the pair's choice
+  int restrict_pair(int l) const {
     const neptune_hip_mg_level_t& F = levels[l];
     const neptune_hip_mg_level_t& Cl = levels[l + 1];
+    return rlinear[l] ? do_restrict_linear(dtype, mask[l], box[l], box[l + 1], rim[l], F.b, F.q, F.rscale, Cl.b, Cl.x, stream)
+                      : do_restrict(dtype, mask[l], box[l], box[l + 1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+  }
+  int prolong_pair(int l) const {
+    const neptune_hip_mg_level_t& F = levels[l];
+    const neptune_hip_mg_level_t& Cl = levels[l + 1];
+    return linear[l] ? do_prolong_linear(dtype, mask[l], box[l], box[l + 1], rim[l], Cl.x, F.x, stream)
+                     : do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
+  }
+  int cycle(int l) const {
+    if (l == n_levels - 1) return sweeps(l, coarse_sweeps);
     int rc = sweeps(l, pre);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = apply(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_restrict(dtype, mask[l], box[l], box[l + 1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    rc = restrict_pair(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = cycle(l + 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = linear[l] ? do_prolong_linear(dtype, mask[l], box[l], box[l + 1], rim[l], Cl.x, F.x, stream)
-                   : do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
+    rc = prolong_pair(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
     return sweeps(l, post, true);
   }
@@ -682,8 +735,6 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
   // the rest of M: everything of the cycle on A z = r after its first pre-sweep (z = minv r, stored with r); its last
   // post-sweep yields r . z, which `stage` of the bookkeeping kernel takes
   auto rest_of_cycle = [&](int stage) -> int {
-    const neptune_hip_mg_level_t& F = S.levels[0];
-    const neptune_hip_mg_level_t& Cl = S.levels[1];
     int rc = NEPTUNE_HIP_OK;
     if (k0) {   // the first pre-sweep: stage 0 without an apply, from z = 0; then its other stages
       rc = do_line_first(S.dtype, B0, dot_axis, r, ln0->lo[0], ln0->inv[0], ln0->up[0], z, stream);
@@ -694,11 +745,11 @@ int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const Mgc
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.apply(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_restrict(S.dtype, S.mask[0], S.box[0], S.box[1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    rc = S.restrict_pair(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.cycle(1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_prolong(S.dtype, S.mask[0], S.box[0], S.box[1], Cl.x, F.x, stream);
+    rc = S.prolong_pair(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.sweeps(0, a.sweeps - 1, true);
     for (int st = k0 - 1; st >= 1 && rc == NEPTUNE_HIP_OK; --st) rc = S.line_stage(0, st);   // the last post-sweep, down to stage 1
@@ -779,7 +830,6 @@ int mgcg_solve_mixed_typed(const Solve& S, const neptune_hip_mg_level_t& O, cons
   const hipStream_t stream = S.stream;
   const MgBox& B0 = S.box[0];
   const neptune_hip_mg_level_t& F = S.levels[0];
-  const neptune_hip_mg_level_t& Cl = S.levels[1];
   const int64_t n = B0.n[0] * B0.n[1] * B0.n[2];
   D* const x = static_cast<D*>(O.x);
   const D* const b = static_cast<const D*>(O.b);
@@ -834,11 +884,11 @@ int mgcg_solve_mixed_typed(const Solve& S, const neptune_hip_mg_level_t& O, cons
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.apply(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_restrict(S.dtype, S.mask[0], S.box[0], S.box[1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    rc = S.restrict_pair(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.cycle(1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = do_prolong(S.dtype, S.mask[0], S.box[0], S.box[1], Cl.x, F.x, stream);
+    rc = S.prolong_pair(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.sweeps(0, a.sweeps - 1, true);
     if (rc != NEPTUNE_HIP_OK) return rc;
@@ -1018,6 +1068,27 @@ int neptune_hip_mg_prolong_add_linear(int dtype, const neptune_hip_apply_geom_t*
   return linear ? do_prolong_linear(dtype, mask, F, Cb, rim, x_coarse, x_fine, s) : do_prolong(dtype, mask, F, Cb, x_coarse, x_fine, s);
 }
 
+int neptune_hip_mg_restrict_linear(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
+                                   const neptune_hip_mg_transfer_t* t, const void* b_fine, const void* q_fine, double rscale, void* b_coarse,
+                                   void* x_coarse, void* stream) {
+  if (!g_fine || !g_coarse || !t || !b_fine || !q_fine || !b_coarse || !x_coarse || !known_dtype(dtype) || !isfinite(rscale)) return NEPTUNE_HIP_EINVAL;
+  MgBox F, Cb;
+  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
+  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
+  if (!mask) return NEPTUNE_HIP_EINVAL;
+  bool linear = false, rlinear = false;
+  MgRim rim;
+  if (!transfer_rules(*t, mask, g_fine->rank, &linear, &rlinear, rim)) return NEPTUNE_HIP_EINVAL;
+  const size_t fb = box_bytes(F, elem_size(dtype)), cb = box_bytes(Cb, elem_size(dtype));
+  if (buffers_overlap(b_coarse, cb, x_coarse, cb)) return NEPTUNE_HIP_EINVAL;
+  for (const void* w : {(const void*)b_coarse, (const void*)x_coarse})
+    if (buffers_overlap(w, cb, b_fine, fb) || buffers_overlap(w, cb, q_fine, fb)) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return rlinear ? do_restrict_linear(dtype, mask, F, Cb, rim, b_fine, q_fine, rscale, b_coarse, x_coarse, s)
+                 : do_restrict(dtype, mask, F, Cb, b_fine, q_fine, rscale, b_coarse, x_coarse, s);
+}
+
 int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse, int* mask_out) {
   if (!g_fine || !g_coarse || !mask_out) return NEPTUNE_HIP_EINVAL;
   MgBox F, Cb;
@@ -1063,6 +1134,25 @@ int neptune_hip_mg_solve_prolong(const neptune_hip_mg_level_t* levels, const nep
                                  const neptune_hip_mg_prolong_t* prolong, int n_levels, int dtype, int pre, int post, int coarse_sweeps,
                                  int64_t max_cycles, int64_t check_every, double tol2, double* rr_checks, void* stream,
                                  const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done, double* rr0, double* rr_last) {
+  // the same choice per pair with the averaging restriction; an n_levels out of range is refused below whatever the array
+  neptune_hip_mg_transfer_t tr[kMaxLevels];
+  const bool have = prolong && n_levels >= 1 && n_levels <= kMaxLevels;
+  for (int l = 0; have && l + 1 < n_levels; ++l) {
+    tr[l].prolong = prolong[l].kind;
+    tr[l].restrict_kind = NEPTUNE_HIP_MG_RESTRICT_AVERAGE;
+    for (int d = 0; d < 3; ++d) {
+      tr[l].rim_lo[d] = prolong[l].rim_lo[d];
+      tr[l].rim_hi[d] = prolong[l].rim_hi[d];
+    }
+  }
+  return neptune_hip_mg_solve_transfer(levels, lines, have ? tr : nullptr, n_levels, dtype, pre, post, coarse_sweeps, max_cycles, check_every,
+                                       tol2, rr_checks, stream, cfg, cycles_done, rr0, rr_last);
+}
+
+int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines,
+                                  const neptune_hip_mg_transfer_t* transfer, int n_levels, int dtype, int pre, int post, int coarse_sweeps,
+                                  int64_t max_cycles, int64_t check_every, double tol2, double* rr_checks, void* stream,
+                                  const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done, double* rr0, double* rr_last) {
   g_mg_counts[0] = g_mg_counts[1] = g_mg_counts[2] = 0;
   if (cycles_done) *cycles_done = 0;
   if (rr0) *rr0 = 0.0;
@@ -1070,7 +1160,7 @@ int neptune_hip_mg_solve_prolong(const neptune_hip_mg_level_t* levels, const nep
   // ---- the refusals, before anything touches the device
   if (check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
   Solve S;
-  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg, lines, prolong)) return NEPTUNE_HIP_EINVAL;
+  if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg, lines, transfer)) return NEPTUNE_HIP_EINVAL;
   const size_t elem = elem_size(dtype);
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
@@ -1194,6 +1284,16 @@ int neptune_hip_mgcg_solve_mixed(const neptune_hip_mg_level_t* outer, int dtype_
                                  int sweeps, int coarse_sweeps, void* const work[2], int64_t max_iters, int64_t check_every, double tol2,
                                  void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
                                  double* rr_last) {
+  return neptune_hip_mgcg_solve_mixed_transfer(outer, dtype_outer, fn_dot, levels, lines, nullptr, n_levels, dtype_inner, sweeps, coarse_sweeps,
+                                               work, max_iters, check_every, tol2, trace, stream, cfg, iters_done, rr0, rr_last);
+}
+
+int neptune_hip_mgcg_solve_mixed_transfer(const neptune_hip_mg_level_t* outer, int dtype_outer, neptune_hip_apply_dot_fn fn_dot,
+                                          const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines,
+                                          const neptune_hip_mg_transfer_t* transfer, int n_levels, int dtype_inner, int sweeps,
+                                          int coarse_sweeps, void* const work[2], int64_t max_iters, int64_t check_every, double tol2,
+                                          void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
+                                          double* rr_last) {
   g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
   g_mgcg_rz0 = 0.0;
   if (iters_done) *iters_done = 0;
@@ -1203,7 +1303,7 @@ int neptune_hip_mgcg_solve_mixed(const neptune_hip_mg_level_t* outer, int dtype_
   if (dtype_outer != NEPTUNE_HIP_F64 || dtype_inner != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
   if (!outer || n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
   Solve S;   // the inner hierarchy; cfg belongs to the outer operator
-  if (!S.check(levels, n_levels, dtype_inner, sweeps, sweeps, coarse_sweeps, nullptr, lines)) return NEPTUNE_HIP_EINVAL;
+  if (!S.check(levels, n_levels, dtype_inner, sweeps, sweeps, coarse_sweeps, nullptr, lines, transfer, true)) return NEPTUNE_HIP_EINVAL;
   // the outer operator: what Solve::check asks of a level's operator, in D, and level 0's box and Omega
   const neptune_hip_mg_level_t& O = *outer;
   MgBox OB;
@@ -1273,6 +1373,15 @@ int neptune_hip_mgcg_solve_lines(const neptune_hip_mg_level_t* levels, const nep
                                  neptune_hip_apply_dot_fn fn_dot, int sweeps, int coarse_sweeps, void* const work[3], int64_t max_iters,
                                  int64_t check_every, double tol2, void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg,
                                  int64_t* iters_done, double* rr0, double* rr_last) {
+  return neptune_hip_mgcg_solve_transfer(levels, lines, nullptr, n_levels, dtype, fn_dot, sweeps, coarse_sweeps, work, max_iters, check_every,
+                                         tol2, trace, stream, cfg, iters_done, rr0, rr_last);
+}
+
+int neptune_hip_mgcg_solve_transfer(const neptune_hip_mg_level_t* levels, const neptune_hip_mg_lines_t* lines,
+                                    const neptune_hip_mg_transfer_t* transfer, int n_levels, int dtype, neptune_hip_apply_dot_fn fn_dot,
+                                    int sweeps, int coarse_sweeps, void* const work[3], int64_t max_iters, int64_t check_every, double tol2,
+                                    void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
+                                    double* rr_last) {
   g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
   g_mgcg_rz0 = 0.0;
   if (iters_done) *iters_done = 0;
@@ -1281,7 +1390,7 @@ int neptune_hip_mgcg_solve_lines(const neptune_hip_mg_level_t* levels, const nep
   // ---- the refusals, before anything touches the device
   if (n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
   Solve S;
-  if (!S.check(levels, n_levels, dtype, sweeps, sweeps, coarse_sweeps, cfg, lines)) return NEPTUNE_HIP_EINVAL;
+  if (!S.check(levels, n_levels, dtype, sweeps, sweeps, coarse_sweeps, cfg, lines, transfer, true)) return NEPTUNE_HIP_EINVAL;
   const size_t elem = elem_size(dtype);
   const size_t bytes0 = box_bytes(S.box[0], elem), bytes1 = box_bytes(S.box[1], elem), trace_bytes = (size_t)(3 * max_iters) * elem;
   const void* const fine[4] = {levels[0].x, levels[0].b, levels[0].q, levels[0].minv};

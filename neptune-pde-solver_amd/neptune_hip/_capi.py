@@ -32,6 +32,7 @@ FLAG_DIRECT_FLAT = 1   # direct kernel: flat one-lane-per-cell form instead of t
 BODY_LAP2D5_F64, BODY_LAP3D7_F64, BODY_LAP3D27_F32, BODY_LAP1D3_F64 = 0, 1, 2, 3
 MG_PROLONG_CONSTANT, MG_PROLONG_LINEAR = 0, 1   # neptune_hip_mg_prolong_t.kind
 MG_RIM_EVEN, MG_RIM_ODD = 0, 1                   # ... and its rule per face: a Neumann face / the value 0 on the face
+MG_RESTRICT_AVERAGE, MG_RESTRICT_LINEAR = 0, 1   # neptune_hip_mg_transfer_t.restrict_kind
 
 ERROR_NAMES = {EINVAL: "NEPTUNE_HIP_EINVAL", EUNSUPPORTED: "NEPTUNE_HIP_EUNSUPPORTED", EOOB: "NEPTUNE_HIP_EOOB",
                ECOMM: "NEPTUNE_HIP_ECOMM"}
@@ -73,6 +74,11 @@ class MgLevel(C.Structure):
 class MgProlong(C.Structure):
     """neptune_hip_mg_prolong_t: the prolongation of one pair of levels; the rules per face are indexed by field dimension"""
     _fields_ = [("kind", C.c_int32), ("rim_lo", C.c_int32 * 3), ("rim_hi", C.c_int32 * 3)]
+
+
+class MgTransfer(C.Structure):
+    """neptune_hip_mg_transfer_t: both transfers of one pair of levels and the one rule array they share"""
+    _fields_ = [("prolong", C.c_int32), ("restrict_kind", C.c_int32), ("rim_lo", C.c_int32 * 3), ("rim_hi", C.c_int32 * 3)]
 
 
 class MgLines(C.Structure):
@@ -167,6 +173,15 @@ SIGNATURES = {
     "neptune_hip_mg_solve_prolong": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), C.POINTER(MgProlong), _i, _i, _i, _i, _i, _i64, _i64,
                                           _dbl, C.POINTER(C.c_double), _vp, _cfg_p, _i64p, C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
+    "neptune_hip_mg_restrict_linear": (_i, [_i, _geom_p, _geom_p, C.POINTER(MgTransfer), _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "neptune_hip_mg_solve_transfer": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), C.POINTER(MgTransfer), _i, _i, _i, _i, _i, _i64, _i64,
+                                           _dbl, C.POINTER(C.c_double), _vp, _cfg_p, _i64p, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double)]),
+    "neptune_hip_mgcg_solve_transfer": (_i, [C.POINTER(MgLevel), C.POINTER(MgLines), C.POINTER(MgTransfer), _i, _i, _vp, _i, _i, _vpp, _i64,
+                                             _i64, _dbl, _vp, _vp, _cfg_p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "neptune_hip_mgcg_solve_mixed_transfer": (_i, [C.POINTER(MgLevel), _i, _vp, C.POINTER(MgLevel), C.POINTER(MgLines),
+                                                   C.POINTER(MgTransfer), _i, _i, _i, _i, _vpp, _i64, _i64, _dbl, _vp, _vp, _cfg_p, _i64p,
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "neptune_hip_mg_coarsened_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
     "neptune_hip_mg_halved_axes": (_i, [_geom_p, _geom_p, C.POINTER(C.c_int)]),
     "neptune_hip_mg_counts": (None, [_i64p, _i64p, _i64p]),

@@ -38,6 +38,11 @@ Linear prolongation on cell-centred pairs: Level(..., prolong="lin
 (low, high) pair per dimension) interpolates with the weights 3/4 and 1/4 and the stated rule per face; plain cycles
 (solve) are then grid-independent where the constant prolongation is not.  The cycle is no longer a symmetric
 preconditioner: cg_solve and cg_solve_mixed refuse such a hierarchy.
+
+Transposed linear restriction: Level(..., prolong="linear", faces=..., restrict="linear") restricts by the
+transpose of that prolongation under the same face rules, R = P^T / 2^k.  The pair is symmetric again, so cg_solve,
+cg_solve(..., lines=True) and cg_solve_mixed accept it (Hierarchy.symmetric) and keep a grid-independent iteration count
+on Dirichlet faces, where the constant pair does not.  For plain cycles the linear / averaging pair stays the better one.
 """
 from __future__ import annotations
 
@@ -277,12 +282,14 @@ class Level:
     prolong, faces describe the prolongation of the pair that LEAVES this level (ignored on the last one): "constant", what
     the pair's grid kind implies, or "linear" (a cell-centred pair only), which needs the rule per face:
     faces = "neumann" or "dirichlet" (the value 0 on the face) for all faces, or one (low, high) pair of these per
-    dimension.  Hierarchy checks both."""
+    dimension.  restrict describes the restriction of the same pair: "average", what the pair's grid kind implies, or
+    "linear" (a cell-centred pair only): the transpose of the linear prolongation by the same `faces`.
+    Hierarchy checks all three."""
 
     def __init__(self, entry, like: DeviceField, bounds: Box, others: Sequence[DeviceField] = (), minv: Optional[DeviceField] = None,
                  rscale: float = 4.0, region: Optional[Box] = None, lines: Sequence[LineStage] = (), prolong: str = "constant",
-                 faces=None):
-        self.prolong, self.faces = prolong, faces
+                 faces=None, restrict: str = "average"):
+        self.prolong, self.faces, self.restrict = prolong, faces, restrict
         self.lines = [LineStage(*st) for st in lines]
         if len(self.lines) > 3:
             raise ValueError("Level: at most three line stages")
@@ -308,6 +315,25 @@ class Level:
     def linear(self) -> bool:
         return self.prolong == "linear"
 
+    @property
+    def restrict_linear(self) -> bool:
+        return self.restrict == "linear"
+
+    def transfer_struct(self) -> _capi.MgTransfer:
+        """neptune_hip_mg_transfer_t of the pair that leaves this level; ValueError for a malformed prolong / restrict / faces"""
+        t = _capi.MgTransfer()
+        if self.prolong not in ("constant", "linear"):
+            raise ValueError(f'prolong is "constant" or "linear", not {self.prolong!r}')
+        if self.restrict not in ("average", "linear"):
+            raise ValueError(f'restrict is "average" or "linear", not {self.restrict!r}')
+        t.prolong = _capi.MG_PROLONG_LINEAR if self.linear else _capi.MG_PROLONG_CONSTANT
+        t.restrict_kind = _capi.MG_RESTRICT_LINEAR if self.restrict_linear else _capi.MG_RESTRICT_AVERAGE
+        if self.linear or self.restrict_linear:
+            lo, hi = face_rules(self.faces, self.like.rank, "restrict" if not self.linear else "prolong")
+            for d in range(self.like.rank):
+                t.rim_lo[d], t.rim_hi[d] = lo[d], hi[d]
+        return t
+
     def prolong_struct(self) -> _capi.MgProlong:
         """neptune_hip_mg_prolong_t of the pair that leaves this level; ValueError for a malformed prolong / faces"""
         p = _capi.MgProlong()
@@ -326,12 +352,12 @@ class Level:
 _FACE_RULE = {"neumann": _capi.MG_RIM_EVEN, "dirichlet": _capi.MG_RIM_ODD}
 
 
-def face_rules(faces, rank: int):
+def face_rules(faces, rank: int, what: str = "prolong"):
     """the linear prolongation's rule per face from `faces`: "neumann" / "dirichlet" for all faces, or a
     sequence of `rank` (low, high) pairs of them; -> (low rules, high rules) per dimension as _capi.MG_RIM_EVEN / _ODD;
     ValueError for anything else"""
     if faces is None:
-        raise ValueError('prolong="linear" needs faces ("neumann", "dirichlet", or a (low, high) pair of them per dimension)')
+        raise ValueError(f'{what}="linear" needs faces ("neumann", "dirichlet", or a (low, high) pair of them per dimension)')
     if isinstance(faces, str):
         faces = [(faces, faces)] * rank
     try:
@@ -386,8 +412,12 @@ class Hierarchy:
                 above = self.levels[l - 1]
                 try:
                     above.prolong_struct()
+                    above.transfer_struct()
                 except ValueError as err:
                     raise ValueError(f"Hierarchy: level {l - 1}: {err}") from None
+                if above.restrict_linear and not halved:
+                    raise ValueError(f'Hierarchy: level {l - 1}: restrict="linear" needs a cell-centred pair, but no dimension is '
+                                     f"halved towards level {l} (m_fine = 2 m_coarse)")
                 if above.linear and not halved:
                     raise ValueError(f'Hierarchy: level {l - 1}: prolong="linear" needs a cell-centred pair, but no dimension is '
                                      f"halved towards level {l} (m_fine = 2 m_coarse)")
@@ -431,6 +461,24 @@ class Hierarchy:
         """whether any pair of levels prolongs linearly (the last level's setting is ignored)"""
         return any(L.linear for L in self.levels[:-1])
 
+    @property
+    def has_linear_restrict(self) -> bool:
+        """whether any pair of levels restricts by the transposed linear prolongation"""
+        return any(L.restrict_linear for L in self.levels[:-1])
+
+    @property
+    def symmetric(self) -> bool:
+        """whether every pair's prolongation is a multiple of its restriction's transpose, so that a V(s, s) cycle is a symmetric
+        preconditioner: each pair is constant / average or linear / linear (the last level's settings are ignored)"""
+        return all(L.linear == L.restrict_linear for L in self.levels[:-1])
+
+    def _transfer_structs(self):
+        """-> the C array of neptune_hip_mg_transfer_t, entry l for the pair (l, l + 1)"""
+        arr = (_capi.MgTransfer * max(len(self.levels) - 1, 1))()
+        for l, L in enumerate(self.levels[:-1]):
+            arr[l] = L.transfer_struct()
+        return arr
+
     def _prolong_structs(self):
         """-> the C array of neptune_hip_mg_prolong_t, entry l for the pair (l, l + 1)"""
         arr = (_capi.MgProlong * max(len(self.levels) - 1, 1))()
@@ -460,7 +508,8 @@ def counts():
 def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int = 2, coarse_sweeps: int = 8, max_cycles: int = 20,
           tol2: float = 0.0, check_every: int = 1, cfg: Optional[_capi.LaunchCfg] = None, stream: Optional[int] = None):
     """solve A_0(x) = b by V(pre, post) cycles over the hierarchy `h` (neptune_hip_mg_solve; neptune_hip_mg_solve_lines when
-    any level has line stages; neptune_hip_mg_solve_prolong when any pair prolongs linearly).  x: initial guess in, solution
+    any level has line stages; neptune_hip_mg_solve_prolong when any pair prolongs linearly; neptune_hip_mg_solve_transfer when
+    any pair restricts by the transposed linear prolongation).  x: initial guess in, solution
     out; its cells outside Omega_0 are boundary data and are never written.  The loop stops when r . r <= tol2 (checked every
     `check_every` cycles) or after max_cycles cycles.  cfg: the launch configuration of level 0's operator.
     Blocking; -> (cycles, rr0, rr_last, rr_checks): rr_checks is the list of r . r values read after each block of cycles.
@@ -476,7 +525,10 @@ def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int 
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
     rest = (pre, post, coarse_sweeps, max_cycles, check_every, tol2, rr, st, C.byref(cfg) if cfg is not None else None,
             C.byref(done), C.byref(rr0), C.byref(last))
-    if h.has_linear:
+    if h.has_linear_restrict:
+        _capi.check(lib.neptune_hip_mg_solve_transfer(arr, h._line_structs() if h.has_lines else None, h._transfer_structs(), len(h),
+                                                      h.dtype, *rest), "neptune_hip_mg_solve_transfer")
+    elif h.has_linear:
         _capi.check(lib.neptune_hip_mg_solve_prolong(arr, h._line_structs() if h.has_lines else None, h._prolong_structs(), len(h),
                                                      h.dtype, *rest), "neptune_hip_mg_solve_prolong")
     elif h.has_lines:
@@ -487,9 +539,10 @@ def solve(h: Hierarchy, x: DeviceField, b: DeviceField, pre: int = 2, post: int 
     return done.value, rr0.value, last.value, list(rr[:counts()[2]])
 
 
-_NOT_SYMMETRIC = ("multigrid.{}: the hierarchy has a pair with prolong=\"linear\": with the averaging restriction P is not a "
-                  "multiple of R^T, so the V-cycle would not be a symmetric preconditioner and conjugate gradients do not apply; "
-                  "use multigrid.solve, or prolong=\"constant\"")
+_NOT_SYMMETRIC = ("multigrid.{}: the hierarchy has a pair with prolong=\"linear\" and the averaging restriction (or "
+                  "restrict=\"linear\" and the constant prolongation): P is not a multiple of R^T, so the V-cycle would not be a "
+                  "symmetric preconditioner and conjugate gradients do not apply; use multigrid.solve, or make the pair symmetric: "
+                  "prolong=\"linear\" with restrict=\"linear\" (the transposed restriction, DESIGN 3.23), or prolong=\"constant\"")
 
 
 def cg_counts():
@@ -510,7 +563,8 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
              tol2: float = 0.0, check_every: int = 1, trace: bool = False, dot="auto", cfg: Optional[_capi.LaunchCfg] = None,
              work: Optional[Sequence[DeviceField]] = None, stream: Optional[int] = None, lines: bool = False):
     """solve A_0(x) = b by conjugate gradients preconditioned with one V(sweeps, sweeps) cycle over the hierarchy `h`
-    (neptune_hip_mgcg_solve; at least two levels, sweeps >= 1).  Level 0's minv must be finite on its whole box
+    (neptune_hip_mgcg_solve; at least two levels, sweeps >= 1; every pair symmetric -- Hierarchy.symmetric --, a hierarchy with
+    restrict="linear" pairs runs neptune_hip_mgcg_solve_transfer).  Level 0's minv must be finite on its whole box
     (jacobi_weights puts +0 outside Omega).  lines=True: a hierarchy whose levels have line stages runs
     neptune_hip_mgcg_solve_lines -- a level with stages needs no minv, level 0 included; without the keyword
     such a hierarchy is refused (ValueError).  A hierarchy without stages behaves the same either way.  x: initial guess in, solution out; its cells outside Omega_0 are boundary data
@@ -527,7 +581,7 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
         raise ValueError("multigrid.cg_solve: x and b must have the box and the element type of level 0")
     if len(h) < 2:
         raise ValueError("multigrid.cg_solve: at least two levels (one level is apply.cg_solve with minv)")
-    if h.has_linear:
+    if not h.symmetric:
         raise ValueError(_NOT_SYMMETRIC.format("cg_solve"))
     if h.has_lines and not lines:
         raise ValueError("multigrid.cg_solve: the hierarchy has line stages; neptune_hip_mgcg_solve smooths with point Jacobi "
@@ -548,7 +602,10 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
     rest = (fn_dot, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
             C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
-    if h.has_lines:
+    if h.has_linear_restrict:
+        _capi.check(lib.neptune_hip_mgcg_solve_transfer(arr, h._line_structs() if h.has_lines else None, h._transfer_structs(), len(h),
+                                                        h.dtype, *rest), "neptune_hip_mgcg_solve_transfer")
+    elif h.has_lines:
         _capi.check(lib.neptune_hip_mgcg_solve_lines(arr, h._line_structs(), len(h), h.dtype, *rest), "neptune_hip_mgcg_solve_lines")
     else:
         _capi.check(lib.neptune_hip_mgcg_solve(arr, len(h), h.dtype, *rest), "neptune_hip_mgcg_solve")
@@ -587,7 +644,7 @@ def cg_solve_mixed(outer: Level, inner: Hierarchy, x: DeviceField, b: DeviceFiel
         raise ValueError("multigrid.cg_solve_mixed: level 0 of the inner hierarchy must have the box and the Omega of the outer level")
     if len(inner) < 2:
         raise ValueError("multigrid.cg_solve_mixed: at least two inner levels")
-    if inner.has_linear:
+    if not inner.symmetric:
         raise ValueError(_NOT_SYMMETRIC.format("cg_solve_mixed"))
     if first.lines:
         raise ValueError("multigrid.cg_solve_mixed: line stages on level 0 are not supported (levels >= 1 may have them)")
@@ -625,10 +682,13 @@ def cg_solve_mixed(outer: Level, inner: Hierarchy, x: DeviceField, b: DeviceFiel
     tr = torch.zeros(3 * max(int(max_iters), 1), dtype=torch.float64, device=x.tensor.device) if trace else None
     warr = (C.c_void_p * 2)(work[0].ptr, work[1].ptr)
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-    _capi.check(lib.neptune_hip_mgcg_solve_mixed(out, _capi.F64, fn_dot, arr, inner._line_structs() if inner.has_lines else None,
-                                                 len(inner), _capi.F32, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2,
-                                                 tr.data_ptr() if trace else None, st, C.byref(cfg) if cfg is not None else None,
-                                                 C.byref(done), C.byref(rr0), C.byref(last)), "neptune_hip_mgcg_solve_mixed")
+    head = (out, _capi.F64, fn_dot, arr, inner._line_structs() if inner.has_lines else None)
+    rest = (len(inner), _capi.F32, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
+            C.byref(cfg) if cfg is not None else None, C.byref(done), C.byref(rr0), C.byref(last))
+    if inner.has_linear_restrict:
+        _capi.check(lib.neptune_hip_mgcg_solve_mixed_transfer(*head, inner._transfer_structs(), *rest), "neptune_hip_mgcg_solve_mixed_transfer")
+    else:
+        _capi.check(lib.neptune_hip_mgcg_solve_mixed(*head, *rest), "neptune_hip_mgcg_solve_mixed")
     del keep
     if trace:
         return done.value, rr0.value, last.value, tr.cpu().numpy()[:3 * done.value].reshape(-1, 3).astype(np.float64, copy=False)
@@ -730,8 +790,15 @@ def line_smooth_dot(level: Level, stage: LineStage, q: DeviceField, b: DeviceFie
 def restrict(fine: Level, coarse: Level, b_fine: DeviceField, q_fine: DeviceField, b_coarse: DeviceField, x_coarse: DeviceField,
              stream: Optional[int] = None) -> None:
     """b_coarse = fine.rscale * R(b_fine - q_fine) and x_coarse = +0 on the coarse Omega (neptune_hip_mg_restrict); R runs
-    along the dimensions the pair coarsens (coarsened_axes) and is the identity along the kept ones; asynchronous"""
+    along the dimensions the pair coarsens (coarsened_axes) and is the identity along the kept ones; asynchronous.
+    fine.restrict = "linear": the transposed linear restriction of a cell-centred pair by fine.faces
+    (neptune_hip_mg_restrict_linear)"""
     st = current_stream_ptr() if stream is None else stream
+    if fine.restrict_linear:
+        _capi.check(_capi.load().neptune_hip_mg_restrict_linear(b_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom),
+                                                                C.byref(fine.transfer_struct()), b_fine.ptr, q_fine.ptr, fine.rscale,
+                                                                b_coarse.ptr, x_coarse.ptr, st), "neptune_hip_mg_restrict_linear")
+        return
     _capi.check(_capi.load().neptune_hip_mg_restrict(b_fine.dtype, C.byref(fine.geom), C.byref(coarse.geom), b_fine.ptr, q_fine.ptr,
                                                      fine.rscale, b_coarse.ptr, x_coarse.ptr, st), "neptune_hip_mg_restrict")
 
