@@ -1,30 +1,29 @@
-// multigrid.hip -- include/neptune_hip.h: geometric multigrid V-cycles over a hierarchy of applies.
-// neptune_hip_mg_smooth / _restrict / _prolong_add launch the three kernels of multigrid_kernels.hpp alone;
-// neptune_hip_mg_solve is the cycle driver: the levels' operators through the public C API, the kernels in between, r . r
-// through neptune_hip_update_norm, and its own small capture / replay of ONE cycle (a linear graph on the call's stream,
-// captured once per call, destroyed when the call returns).  Its own translation unit (builds in seconds, linked into
-// libneptune_hip.so): host code plus the kernels' instantiations.  neptune_hip_mg_line_smooth launches one stage of the line
-// smoother (mg_line_kernels.hpp) alone; neptune_hip_mg_solve_lines is the driver with line stages per level, and
-// neptune_hip_mg_solve is that call without any.  neptune_hip_mgcg_solve_lines is multigrid-preconditioned CG with line stages
-// (DESIGN 3.18): on level 0 the cycle starts with the apply-free form of the stage and ends with the form that yields r . z
-// (neptune_hip_mg_line_first, neptune_hip_mg_line_smooth_dot launch the two alone); neptune_hip_mgcg_solve is that call without
-// lines.  neptune_hip_mgcg_solve_mixed is that solver with x, b, r, p, q and the scalars in f64 around the cycle in f32
-// (mgcg_mixed_kernels.hpp); neptune_hip_mg_smooth_dot_wide launches its last sweep, the one with the wide sum, alone.
-// A pair of levels is vertex-centred or cell-centred: sizes_nest infers which, and the two transfer launches
-// dispatch on it -- everything else here is the same code for both.  A cell-centred pair may prolong linearly instead, by a rule
-// per face that the caller states: neptune_hip_mg_prolong_add_linear launches that kernel alone,
-// neptune_hip_mg_solve_prolong is the plain-cycle driver with the choice per pair, and neptune_hip_mg_solve_lines is that call
-// without any.  The restriction of such a pair may be the transpose of that prolongation: one
-// neptune_hip_mg_transfer_t per pair states both transfers and the one rule array they share; neptune_hip_mg_restrict_linear
-// launches that kernel alone, neptune_hip_mg_solve_transfer is the plain-cycle driver (neptune_hip_mg_solve_prolong is that
-// call with the averaging restriction everywhere), and the neptune_hip_mgcg_*_transfer drivers take a pair only when it is
-// symmetric -- CONSTANT with AVERAGE, or LINEAR with LINEAR; the older MGCG entries are those calls without an array.
+// multigrid.hip -- include/neptune_hip.h: geometric multigrid over a hierarchy of applies.  Its own
+// translation unit (builds in seconds, linked into libneptune_hip.so): host code plus the kernels' instantiations.
+//
+//   kernels alone    neptune_hip_mg_smooth, _smooth_dot, _smooth_dot_wide            the point sweep; with r . z; with the wide sum
+//                    neptune_hip_mg_line_smooth, _line_first, _line_smooth_dot       one line stage: plain, apply-free, with r . z
+//                    neptune_hip_mg_restrict, _restrict_linear                       a pair's restriction (Pair: which kernel)
+//                    neptune_hip_mg_prolong_add, _prolong_add_linear                 a pair's prolongation
+//                    neptune_hip_mg_coarsened_axes, _halved_axes                     how a pair nests
+//   drivers          neptune_hip_mg_solve_transfer            V-cycles; any transfers per pair                 (Solve, run_blocks)
+//                    neptune_hip_mgcg_solve_transfer          MGCG in one type; symmetric pairs only           (mgcg_drive<MgcgOneType<T>>)
+//                    neptune_hip_mgcg_solve_mixed_transfer    MGCG in f64 around a cycle in f32                (mgcg_drive<MgcgMixed>)
+//   forwarding       neptune_hip_mg_solve -> _solve_lines (lines = NULL) -> _solve_prolong (prolong = NULL) -> _solve_transfer
+//                    (the prolong array restated as transfers with the averaging restriction);
+//                    neptune_hip_mgcg_solve -> _mgcg_solve_lines (lines = NULL) -> _mgcg_solve_transfer (transfer = NULL);
+//                    neptune_hip_mgcg_solve_mixed -> _mgcg_solve_mixed_transfer (transfer = NULL)
+//
+// Every driver runs its loop on run_blocks: blocks of check_every units (a cycle, an iteration), the first unit as plain
+// launches, then ONE capture of a unit as a linear graph on the call's stream that every later unit replays; the graph is
+// destroyed when the call returns.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../../include/neptune_hip.h"
@@ -45,6 +44,10 @@ void ensure_init() { (void)neptune_hip_cu_count(); }
 
 bool known_dtype(int dtype) { return dtype == NEPTUNE_HIP_F64 || dtype == NEPTUNE_HIP_F32; }
 size_t elem_size(int dtype) { return dtype == NEPTUNE_HIP_F64 ? 8 : 4; }
+// a launch configuration, nullptr unless the caller set anything in it
+const neptune_hip_launch_cfg_t* set_cfg(const neptune_hip_launch_cfg_t* cfg) {
+  return (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
+}
 
 // A level's box and Omega = apply.bounds x launch region on the kernels' three axes (the field's dimensions right-aligned);
 // -> false for a malformed geometry, an input 0 in another box than the result's, or an empty Omega
@@ -68,6 +71,8 @@ bool level_box(const neptune_hip_apply_geom_t* g, MgBox& B) {
   }
   return true;
 }
+size_t box_bytes(const MgBox& B, size_t elem) { return (size_t)(B.n[0] * B.n[1] * B.n[2]) * elem; }
+
 // How two neighbouring levels nest: per axis that carries a dimension coarsened, m_fine = 2 m_coarse + 1, halved, m_fine =
 // 2 m_coarse (a cell-centred pair), or kept, m_fine = m_coarse (the three exclude each other for m >= 1).
 // -> the kernels' mask (bit a: axis a is coarsened or halved), with kMgCell set when the axes are halved ones; or 0 = refuse:
@@ -83,8 +88,101 @@ int sizes_nest(const MgBox& F, const MgBox& Cb, int rank) {
   if (coarsened && halved) return 0;
   return halved ? (halved | kMgCell) : coarsened;
 }
-size_t box_bytes(const MgBox& B, size_t elem) { return (size_t)(B.n[0] * B.n[1] * B.n[2]) * elem; }
 
+// One pair of levels, checked: the two boxes, how they nest, and which kernel each transfer takes.  Vertex-centred or
+// cell-centred by `mask`; a cell-centred pair may prolong linearly by a rule per face and restrict
+// by the transpose of that prolongation, the one rule array `rim` serving both.
+struct Pair {
+  MgBox F, Cb;
+  int rank = 0, mask = 0;                 // mask: sizes_nest's, never 0 once nest() has answered true
+  bool linear = false, rlinear = false;   // the prolongation / the restriction is the linear one
+  MgRim rim;                              // a linear transfer's rules on the kernels' axes (the dimensions right-aligned)
+
+  // -> false: refuse -- the boxes do not nest.  Both transfers are the ones the pair's grid kind implies until rules() says otherwise.
+  bool nest(const MgBox& fine, const MgBox& coarse, int rank_) {
+    F = fine;
+    Cb = coarse;
+    rank = rank_;
+    mask = sizes_nest(F, Cb, rank);
+    linear = rlinear = false;
+    for (int a = 0; a < 3; ++a) rim.lo[a] = rim.hi[a] = NEPTUNE_HIP_MG_RIM_EVEN;
+    return mask != 0;
+  }
+  // the same from two geometries: -> false also for a malformed one and for two ranks
+  bool nest(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse) {
+    MgBox fine, coarse;
+    return level_box(g_fine, fine) && level_box(g_coarse, coarse) && g_fine->rank == g_coarse->rank && nest(fine, coarse, g_fine->rank);
+  }
+  // What the caller states about the pair's transfers, after nest(): -> false: refuse -- a prolong outside {CONSTANT, LINEAR},
+  // a restrict_kind outside {AVERAGE, LINEAR}, a LINEAR transfer on a pair without a halved dimension, a rule outside {EVEN,
+  // ODD} on a dimension < rank when either transfer is LINEAR.  Nothing but the two kinds is read of a CONSTANT / AVERAGE
+  // entry, and no rule of a dimension >= rank.
+  bool rules(const neptune_hip_mg_transfer_t& t) {
+    if (t.prolong != NEPTUNE_HIP_MG_PROLONG_CONSTANT && t.prolong != NEPTUNE_HIP_MG_PROLONG_LINEAR) return false;
+    if (t.restrict_kind != NEPTUNE_HIP_MG_RESTRICT_AVERAGE && t.restrict_kind != NEPTUNE_HIP_MG_RESTRICT_LINEAR) return false;
+    linear = t.prolong == NEPTUNE_HIP_MG_PROLONG_LINEAR;
+    rlinear = t.restrict_kind == NEPTUNE_HIP_MG_RESTRICT_LINEAR;
+    if (!linear && !rlinear) return true;
+    if (!(mask & kMgCell)) return false;
+    for (int d = 0; d < rank; ++d) {
+      for (const int32_t v : {t.rim_lo[d], t.rim_hi[d]})
+        if (v != NEPTUNE_HIP_MG_RIM_EVEN && v != NEPTUNE_HIP_MG_RIM_ODD) return false;
+      rim.lo[d + 3 - rank] = t.rim_lo[d];
+      rim.hi[d + 3 - rank] = t.rim_hi[d];
+    }
+    return true;
+  }
+};
+// a prolongation stated alone is that prolongation with the averaging restriction
+neptune_hip_mg_transfer_t transfer_of(const neptune_hip_mg_prolong_t& p) {
+  neptune_hip_mg_transfer_t t;
+  t.prolong = p.kind;
+  t.restrict_kind = NEPTUNE_HIP_MG_RESTRICT_AVERAGE;
+  for (int d = 0; d < 3; ++d) {
+    t.rim_lo[d] = p.rim_lo[d];
+    t.rim_hi[d] = p.rim_hi[d];
+  }
+  return t;
+}
+
+// A field (or a scalar, or the trace) as the bytes a call touches.  align: what the address must be a multiple of;
+// optional: the member may be null and is then left out of every test.
+struct Span {
+  const void* p;
+  size_t bytes;
+  size_t align = 1;
+  bool optional = false;
+};
+// A view of some Spans, for apart()'s arguments only: it points into the braces or the array it was made from and must not
+// outlive the call it is built in (a named Spans made from braces would dangle).
+struct Spans {
+  const Span* p;
+  size_t n;
+  Spans(std::initializer_list<Span> l) : p(l.begin()), n(l.size()) {}
+  template <size_t N>
+  Spans(const Span (&a)[N]) : p(a), n(N) {}
+  Spans(const Span* p_, size_t n_) : p(p_), n(n_) {}
+};
+// The fields a call writes (or otherwise needs to itself) against the fields it only reads: -> false: refuse -- a member
+// that is null without being optional, one that is misaligned, two of `own` that meet, one of `own` that meets one of
+// `read`.  Two of `read` may meet.
+bool apart(Spans own, Spans read) {
+  auto sound = [](const Span& s) { return s.p ? (uintptr_t)s.p % s.align == 0 : s.optional; };
+  auto meet = [](const Span& a, const Span& b) { return a.p && b.p && buffers_overlap(a.p, a.bytes, b.p, b.bytes); };
+  for (size_t i = 0; i < own.n; ++i) {
+    if (!sound(own.p[i])) return false;
+    for (size_t o = 0; o < i; ++o)
+      if (meet(own.p[i], own.p[o])) return false;
+  }
+  for (size_t i = 0; i < read.n; ++i) {
+    if (!sound(read.p[i])) return false;
+    for (size_t o = 0; o < own.n; ++o)
+      if (meet(read.p[i], own.p[o])) return false;
+  }
+  return true;
+}
+
+// ---------------------------------------------------------------- launch geometry and dispatch
 struct RowGrid {
   int64_t nchunk;
   dim3 grid;
@@ -96,73 +194,115 @@ RowGrid row_grid(const MgBox& B) {
   r.grid = grid_for_blocks(B.m[0] * B.m[1] * r.nchunk);
   return r;
 }
+int64_t grid_blocks(const dim3& g) { return (int64_t)g.x * g.y; }
 
 int launched() { return hipGetLastError() == hipSuccess ? NEPTUNE_HIP_OK : NEPTUNE_HIP_EUNSUPPORTED; }
 
+// the dispatch on element type, stated once: f(T()) with T the type
+template <class Fn>
+int by_type(int dtype, Fn&& f) { return dtype == NEPTUNE_HIP_F64 ? f(double()) : f(float()); }
+// ... and on a pair's axes (Pair::mask & 7): launch(std::integral_constant<int, MASK>())
+template <class Launch>
+int by_mask(int mask, Launch&& launch) {
+  switch (mask) {
+    case 1: return launch(std::integral_constant<int, 1>());
+    case 2: return launch(std::integral_constant<int, 2>());
+    case 3: return launch(std::integral_constant<int, 3>());
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 5: return launch(std::integral_constant<int, 5>());
+    case 6: return launch(std::integral_constant<int, 6>());
+    case 7: return launch(std::integral_constant<int, 7>());
+    default: return NEPTUNE_HIP_EINVAL;
+  }
+}
 template <class T>
-int smooth_launch(const MgBox& B, const void* q, const void* b, const void* minv, void* x, hipStream_t stream) {
+const T* in(const void* p) { return static_cast<const T*>(p); }
+template <class T>
+T* io(void* p) { return static_cast<T*>(p); }
+
+int do_smooth(int dtype, const MgBox& B, const void* q, const void* b, const void* minv, void* x, hipStream_t s) {
   const RowGrid r = row_grid(B);
-  hipLaunchKernelGGL(neptune_mg_smooth<T>, r.grid, dim3(256), 0, stream, B, r.nchunk, static_cast<const T*>(q), static_cast<const T*>(b),
-                     static_cast<const T*>(minv), static_cast<T*>(x));
-  return launched();
+  return by_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(neptune_mg_smooth<T>, r.grid, dim3(256), 0, s, B, r.nchunk, in<T>(q), in<T>(b), in<T>(minv), io<T>(x));
+    return launched();
+  });
 }
-template <class T, int MASK>
-int restrict_launch(const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c, void* x_c,
-                    hipStream_t stream) {
+// the sweep that also leaves one partial of b . x_new per workgroup of row_grid, in T, or -- `wide` -- on f32 fields in f64
+int do_smooth_dot(int dtype, bool wide, const MgBox& B, const void* q, const void* b, const void* minv, void* x, void* partials, hipStream_t s) {
+  const RowGrid r = row_grid(B);
+  if (wide) {
+    hipLaunchKernelGGL((neptune_mg_smooth_dot_wide<double, float>), r.grid, dim3(256), 0, s, B, r.nchunk, in<float>(q), in<float>(b),
+                       in<float>(minv), io<float>(x), io<double>(partials));
+    return launched();
+  }
+  return by_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(neptune_mg_smooth_dot<T>, r.grid, dim3(256), 0, s, B, r.nchunk, in<T>(q), in<T>(b), in<T>(minv), io<T>(x), io<T>(partials));
+    return launched();
+  });
+}
+// *out = the sum of `count` partials
+int monitor_final(int dtype, const void* partials, int64_t count, void* out, hipStream_t s) {
+  return by_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(neptune_monitor_final<T>, dim3(1), dim3(256), 0, s, in<T>(partials), count, io<T>(out));
+    return launched();
+  });
+}
+
+// The restriction of a pair, by the pair's choice.  The averaging ones: one workgroup per 256-cell chunk of a coarse row
+// (vertex-centred with axis 2 coarsened: the fine row segments staged in LDS; kept: every lane on its own fine cells).  The
+// transposed linear one: one workgroup per 256-cell chunk of a run of kMgLinearRun coarse rows of one coarse plane.
+int do_restrict(int dtype, const Pair& P, const void* b_f, const void* q_f, double rscale, void* b_c, void* x_c, hipStream_t s) {
+  const MgBox &F = P.F, &Cb = P.Cb;
   const RowGrid r = row_grid(Cb);
-  // axis 2 coarsened: the fine row segments staged in LDS; kept: every lane on its own fine cells
-  if constexpr ((MASK & 4) != 0)
-    hipLaunchKernelGGL((neptune_mg_restrict<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
-                       static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
-  else
-    hipLaunchKernelGGL((neptune_mg_restrict_kept2<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
-                       static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
-  return launched();
+  return by_mask(P.mask & 7, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    return by_type(dtype, [&](auto t) {
+      using T = decltype(t);
+      if (P.rlinear) {
+        const int64_t nrun = (Cb.m[1] + kMgLinearRun - 1) / kMgLinearRun;
+        hipLaunchKernelGGL((neptune_mg_restrict_linear<T, M>), grid_for_blocks(Cb.m[0] * nrun * r.nchunk), dim3(256), 0, s, F, Cb, r.nchunk, P.rim,
+                           in<T>(b_f), in<T>(q_f), (T)rscale, io<T>(b_c), io<T>(x_c));
+      } else if (P.mask & kMgCell) {
+        hipLaunchKernelGGL((neptune_mg_restrict_cell<T, M>), r.grid, dim3(256), 0, s, F, Cb, r.nchunk, in<T>(b_f), in<T>(q_f), (T)rscale,
+                           io<T>(b_c), io<T>(x_c));
+      } else if constexpr ((M & 4) != 0) {
+        hipLaunchKernelGGL((neptune_mg_restrict<T, M>), r.grid, dim3(256), 0, s, F, Cb, r.nchunk, in<T>(b_f), in<T>(q_f), (T)rscale, io<T>(b_c),
+                           io<T>(x_c));
+      } else {
+        hipLaunchKernelGGL((neptune_mg_restrict_kept2<T, M>), r.grid, dim3(256), 0, s, F, Cb, r.nchunk, in<T>(b_f), in<T>(q_f), (T)rscale,
+                           io<T>(b_c), io<T>(x_c));
+      }
+      return launched();
+    });
+  });
 }
-template <class T, int MASK>
-int prolong_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t stream) {
-  const RowGrid r = row_grid(F);
-  hipLaunchKernelGGL((neptune_mg_prolong_add<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(x_c),
-                     static_cast<T*>(x_f));
-  return launched();
+// The prolongation of a pair, by the pair's choice: one workgroup per chunk of a fine row -- 256 fine cells, but for the
+// linear one 256 COARSE cells (512 fine ones) where axis 2 is halved (where it is kept, Cb.m[2] = F.m[2])
+int do_prolong(int dtype, const Pair& P, const void* x_c, void* x_f, hipStream_t s) {
+  const MgBox &F = P.F, &Cb = P.Cb;
+  RowGrid r = row_grid(F);
+  if (P.linear) {
+    r.nchunk = (Cb.m[2] + 255) / 256;
+    r.grid = grid_for_blocks(F.m[0] * F.m[1] * r.nchunk);
+  }
+  return by_mask(P.mask & 7, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    return by_type(dtype, [&](auto t) {
+      using T = decltype(t);
+      if (P.linear)
+        hipLaunchKernelGGL((neptune_mg_prolong_add_linear<T, M>), r.grid, dim3(256), 0, s, F, Cb, r.nchunk, P.rim, in<T>(x_c), io<T>(x_f));
+      else if (P.mask & kMgCell)
+        hipLaunchKernelGGL((neptune_mg_prolong_add_cell<T, M>), r.grid, dim3(256), 0, s, F, Cb, r.nchunk, in<T>(x_c), io<T>(x_f));
+      else
+        hipLaunchKernelGGL((neptune_mg_prolong_add<T, M>), r.grid, dim3(256), 0, s, F, Cb, r.nchunk, in<T>(x_c), io<T>(x_f));
+      return launched();
+    });
+  });
 }
-// the transfers of a cell-centred pair: MASK = the halved axes
-template <class T, int MASK>
-int restrict_cell_launch(const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c, void* x_c,
-                         hipStream_t stream) {
-  const RowGrid r = row_grid(Cb);
-  hipLaunchKernelGGL((neptune_mg_restrict_cell<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(b_f),
-                     static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
-  return launched();
-}
-template <class T, int MASK>
-int prolong_cell_launch(const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t stream) {
-  const RowGrid r = row_grid(F);
-  hipLaunchKernelGGL((neptune_mg_prolong_add_cell<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, static_cast<const T*>(x_c),
-                     static_cast<T*>(x_f));
-  return launched();
-}
-// The linear prolongation of a cell-centred pair: one workgroup per chunk of a fine row -- 256 COARSE cells
-// (512 fine ones) where axis 2 is halved, 256 fine cells where it is kept
-template <class T, int MASK>
-int prolong_linear_launch(const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* x_c, void* x_f, hipStream_t stream) {
-  RowGrid r;
-  r.nchunk = (Cb.m[2] + 255) / 256;   // axis 2 kept: Cb.m[2] = F.m[2]
-  r.grid = grid_for_blocks(F.m[0] * F.m[1] * r.nchunk);
-  hipLaunchKernelGGL((neptune_mg_prolong_add_linear<T, MASK>), r.grid, dim3(256), 0, stream, F, Cb, r.nchunk, rim, static_cast<const T*>(x_c),
-                     static_cast<T*>(x_f));
-  return launched();
-}
-// The transposed linear restriction of a cell-centred pair: one workgroup per 256-cell chunk of a run of
-// kMgLinearRun coarse rows of one coarse plane
-template <class T, int MASK>
-int restrict_linear_launch(const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* b_f, const void* q_f, double rscale, void* b_c,
-                           void* x_c, hipStream_t stream) {
-  const int64_t nchunk = (Cb.m[2] + 255) / 256, nrun = (Cb.m[1] + kMgLinearRun - 1) / kMgLinearRun;
-  hipLaunchKernelGGL((neptune_mg_restrict_linear<T, MASK>), grid_for_blocks(Cb.m[0] * nrun * nchunk), dim3(256), 0, stream, F, Cb, nchunk, rim,
-                     static_cast<const T*>(b_f), static_cast<const T*>(q_f), (T)rscale, static_cast<T*>(b_c), static_cast<T*>(x_c));
-  return launched();
-}
+
 // One stage of the line smoother along box axis `axis`.  Axis 2: a one-wave workgroup per 64 lines.  A slow axis: a workgroup
 // per chunk of lanes along axis 2 and index of the other slow axis; 256 lanes wide where that still gives every CU two
 // workgroups, else 64 lanes, so that a small level (a 2-D field's lines along dim 0 have m[2] / width workgroups in all)
@@ -186,151 +326,53 @@ LineGrid line_grid(const MgBox& B, int axis) {
   L.grid = grid_for_blocks(B.m[1 - axis] * L.nchunk);
   return L;
 }
-// q: unused by kMgLineFirst; partials: one T per workgroup of the grid, kMgLineDot only
+// the fields of one stage.  q: unused by kMgLineFirst; partials: one T per workgroup of the grid, kMgLineDot only
+template <class T>
+struct LineArgs {
+  T* q;
+  const T *b, *lo, *inv, *up;
+  T *x, *partials;
+};
 template <class T, int MODE, int AXIS, int WIDTH>
-void line_slow_launch(const MgBox& B, const LineGrid& L, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
-                      void* partials, hipStream_t stream) {
-  const T *bp = static_cast<const T*>(b), *lp = static_cast<const T*>(lo), *ip = static_cast<const T*>(inv), *up_ = static_cast<const T*>(up);
+void line_slow_launch(const MgBox& B, const LineGrid& L, const LineArgs<T>& a, hipStream_t stream) {
   if constexpr (MODE == kMgLineFirst)
-    hipLaunchKernelGGL((neptune_mg_line_slow_first<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, bp, lp, ip, up_, static_cast<T*>(x));
+    hipLaunchKernelGGL((neptune_mg_line_slow_first<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, a.b, a.lo, a.inv, a.up, a.x);
   else if constexpr (MODE == kMgLineDot)
-    hipLaunchKernelGGL((neptune_mg_line_slow_dot<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, static_cast<T*>(q), bp, lp, ip,
-                       up_, static_cast<T*>(x), static_cast<T*>(partials));
+    hipLaunchKernelGGL((neptune_mg_line_slow_dot<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, a.q, a.b, a.lo, a.inv, a.up, a.x,
+                       a.partials);
   else
-    hipLaunchKernelGGL((neptune_mg_line_slow<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, static_cast<T*>(q), bp, lp, ip, up_,
-                       static_cast<T*>(x));
+    hipLaunchKernelGGL((neptune_mg_line_slow<T, AXIS, WIDTH>), L.grid, dim3(WIDTH), 0, stream, B, L.nchunk, a.q, a.b, a.lo, a.inv, a.up, a.x);
 }
 template <class T, int MODE>
-int line_launch(const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x, void* partials,
-                hipStream_t stream) {
+int line_launch(const MgBox& B, int axis, const LineArgs<T>& a, hipStream_t stream) {
   const LineGrid L = line_grid(B, axis);
   if (axis == 2) {
-    const T *bp = static_cast<const T*>(b), *lp = static_cast<const T*>(lo), *ip = static_cast<const T*>(inv), *up_ = static_cast<const T*>(up);
     if constexpr (MODE == kMgLineFirst)
-      hipLaunchKernelGGL(neptune_mg_line_contig_first<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, bp, lp, ip, up_, static_cast<T*>(x));
+      hipLaunchKernelGGL(neptune_mg_line_contig_first<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, a.b, a.lo, a.inv, a.up, a.x);
     else if constexpr (MODE == kMgLineDot)
-      hipLaunchKernelGGL(neptune_mg_line_contig_dot<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, static_cast<T*>(q), bp, lp, ip, up_,
-                         static_cast<T*>(x), static_cast<T*>(partials));
+      hipLaunchKernelGGL(neptune_mg_line_contig_dot<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, a.q, a.b, a.lo, a.inv, a.up, a.x, a.partials);
     else
-      hipLaunchKernelGGL(neptune_mg_line_contig<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, static_cast<T*>(q), bp, lp, ip, up_,
-                         static_cast<T*>(x));
-    return launched();
-  }
-  if (axis == 0) {
-    if (L.width == 256) line_slow_launch<T, MODE, 0, 256>(B, L, q, b, lo, inv, up, x, partials, stream);
-    else line_slow_launch<T, MODE, 0, 64>(B, L, q, b, lo, inv, up, x, partials, stream);
+      hipLaunchKernelGGL(neptune_mg_line_contig<T>, L.grid, dim3(kMgLineGroup), 0, stream, B, a.q, a.b, a.lo, a.inv, a.up, a.x);
+  } else if (axis == 0) {
+    if (L.width == 256) line_slow_launch<T, MODE, 0, 256>(B, L, a, stream);
+    else line_slow_launch<T, MODE, 0, 64>(B, L, a, stream);
   } else {
-    if (L.width == 256) line_slow_launch<T, MODE, 1, 256>(B, L, q, b, lo, inv, up, x, partials, stream);
-    else line_slow_launch<T, MODE, 1, 64>(B, L, q, b, lo, inv, up, x, partials, stream);
+    if (L.width == 256) line_slow_launch<T, MODE, 1, 256>(B, L, a, stream);
+    else line_slow_launch<T, MODE, 1, 64>(B, L, a, stream);
   }
   return launched();
 }
-// the dispatch on element type and on the pair's mask (sizes_nest: the axes 1..7, kMgCell for a cell-centred pair), stated once
-template <class F64, class F32>
-int by_type(int dtype, F64&& f64, F32&& f32) { return dtype == NEPTUNE_HIP_F64 ? f64() : f32(); }
-int do_line(int dtype, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
-            hipStream_t s) {
-  return by_type(dtype, [&] { return line_launch<double, kMgLinePlain>(B, axis, q, b, lo, inv, up, x, nullptr, s); },
-                 [&] { return line_launch<float, kMgLinePlain>(B, axis, q, b, lo, inv, up, x, nullptr, s); });
-}
-// the apply-free stage (x from b alone) and the stage that also leaves one partial of b . x_new per workgroup of line_grid
-int do_line_first(int dtype, const MgBox& B, int axis, const void* b, const void* lo, const void* inv, const void* up, void* x, hipStream_t s) {
-  return by_type(dtype, [&] { return line_launch<double, kMgLineFirst>(B, axis, nullptr, b, lo, inv, up, x, nullptr, s); },
-                 [&] { return line_launch<float, kMgLineFirst>(B, axis, nullptr, b, lo, inv, up, x, nullptr, s); });
-}
-int do_line_dot(int dtype, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
-                void* partials, hipStream_t s) {
-  return by_type(dtype, [&] { return line_launch<double, kMgLineDot>(B, axis, q, b, lo, inv, up, x, partials, s); },
-                 [&] { return line_launch<float, kMgLineDot>(B, axis, q, b, lo, inv, up, x, partials, s); });
-}
-int do_smooth(int dtype, const MgBox& B, const void* q, const void* b, const void* minv, void* x, hipStream_t s) {
-  return by_type(dtype, [&] { return smooth_launch<double>(B, q, b, minv, x, s); }, [&] { return smooth_launch<float>(B, q, b, minv, x, s); });
-}
-template <class Launch>
-int by_mask(int mask, Launch&& launch) {
-  switch (mask) {
-    case 1: return launch(std::integral_constant<int, 1>());
-    case 2: return launch(std::integral_constant<int, 2>());
-    case 3: return launch(std::integral_constant<int, 3>());
-    case 4: return launch(std::integral_constant<int, 4>());
-    case 5: return launch(std::integral_constant<int, 5>());
-    case 6: return launch(std::integral_constant<int, 6>());
-    case 7: return launch(std::integral_constant<int, 7>());
-    default: return NEPTUNE_HIP_EINVAL;
-  }
-}
-int do_restrict(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void* b_f, const void* q_f, double rscale, void* b_c,
-                void* x_c, hipStream_t s) {
-  return by_mask(mask & 7, [&](auto m) {
-    constexpr int M = decltype(m)::value;
-    if (mask & kMgCell)
-      return by_type(dtype, [&] { return restrict_cell_launch<double, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); },
-                     [&] { return restrict_cell_launch<float, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); });
-    return by_type(dtype, [&] { return restrict_launch<double, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); },
-                   [&] { return restrict_launch<float, M>(F, Cb, b_f, q_f, rscale, b_c, x_c, s); });
+// mode: kMgLinePlain; kMgLineFirst, the apply-free stage (x from b alone; q is not read); kMgLineDot, the stage that also
+// leaves one partial of b . x_new per workgroup of line_grid
+int do_line(int dtype, int mode, const MgBox& B, int axis, void* q, const void* b, const void* lo, const void* inv, const void* up, void* x,
+            void* partials, hipStream_t s) {
+  return by_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    const LineArgs<T> a = {io<T>(q), in<T>(b), in<T>(lo), in<T>(inv), in<T>(up), io<T>(x), io<T>(partials)};
+    if (mode == kMgLineFirst) return line_launch<T, kMgLineFirst>(B, axis, a, s);
+    if (mode == kMgLineDot) return line_launch<T, kMgLineDot>(B, axis, a, s);
+    return line_launch<T, kMgLinePlain>(B, axis, a, s);
   });
-}
-int do_prolong(int dtype, int mask, const MgBox& F, const MgBox& Cb, const void* x_c, void* x_f, hipStream_t s) {
-  return by_mask(mask & 7, [&](auto m) {
-    constexpr int M = decltype(m)::value;
-    if (mask & kMgCell)
-      return by_type(dtype, [&] { return prolong_cell_launch<double, M>(F, Cb, x_c, x_f, s); },
-                     [&] { return prolong_cell_launch<float, M>(F, Cb, x_c, x_f, s); });
-    return by_type(dtype, [&] { return prolong_launch<double, M>(F, Cb, x_c, x_f, s); },
-                   [&] { return prolong_launch<float, M>(F, Cb, x_c, x_f, s); });
-  });
-}
-int do_prolong_linear(int dtype, int mask, const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* x_c, void* x_f, hipStream_t s) {
-  return by_mask(mask & 7, [&](auto m) {
-    constexpr int M = decltype(m)::value;
-    return by_type(dtype, [&] { return prolong_linear_launch<double, M>(F, Cb, rim, x_c, x_f, s); },
-                   [&] { return prolong_linear_launch<float, M>(F, Cb, rim, x_c, x_f, s); });
-  });
-}
-int do_restrict_linear(int dtype, int mask, const MgBox& F, const MgBox& Cb, const MgRim& rim, const void* b_f, const void* q_f, double rscale,
-                       void* b_c, void* x_c, hipStream_t s) {
-  return by_mask(mask & 7, [&](auto m) {
-    constexpr int M = decltype(m)::value;
-    return by_type(dtype, [&] { return restrict_linear_launch<double, M>(F, Cb, rim, b_f, q_f, rscale, b_c, x_c, s); },
-                   [&] { return restrict_linear_launch<float, M>(F, Cb, rim, b_f, q_f, rscale, b_c, x_c, s); });
-  });
-}
-// What the caller states about the prolongation of one pair (sizes_nest's `mask`): -> false: refuse -- a kind outside
-// {CONSTANT, LINEAR}, LINEAR on a pair without a halved dimension, a rule outside {EVEN, ODD} on a dimension < rank of a
-// LINEAR pair.  *linear: the kind; rim: a LINEAR pair's rules on the kernels' axes (the dimensions right-aligned).
-// Nothing but `kind` is read of a CONSTANT entry, and no entry of a dimension >= rank.
-bool prolong_rules(const neptune_hip_mg_prolong_t& p, int mask, int rank, bool* linear, MgRim& rim) {
-  if (p.kind != NEPTUNE_HIP_MG_PROLONG_CONSTANT && p.kind != NEPTUNE_HIP_MG_PROLONG_LINEAR) return false;
-  *linear = p.kind == NEPTUNE_HIP_MG_PROLONG_LINEAR;
-  for (int a = 0; a < 3; ++a) rim.lo[a] = rim.hi[a] = NEPTUNE_HIP_MG_RIM_EVEN;
-  if (!*linear) return true;
-  if (!(mask & kMgCell)) return false;
-  for (int d = 0; d < rank; ++d) {
-    for (const int32_t v : {p.rim_lo[d], p.rim_hi[d]})
-      if (v != NEPTUNE_HIP_MG_RIM_EVEN && v != NEPTUNE_HIP_MG_RIM_ODD) return false;
-    rim.lo[d + 3 - rank] = p.rim_lo[d];
-    rim.hi[d + 3 - rank] = p.rim_hi[d];
-  }
-  return true;
-}
-
-// The same for both transfers of one pair: -> false: refuse -- what prolong_rules refuses of t.prolong, a
-// restrict_kind outside {AVERAGE, LINEAR}, LINEAR restriction on a pair without a halved dimension, a rule outside {EVEN,
-// ODD} on a dimension < rank when either transfer is LINEAR.  The one rule array serves both.  Nothing but the two kinds is
-// read of a CONSTANT / AVERAGE entry.
-bool transfer_rules(const neptune_hip_mg_transfer_t& t, int mask, int rank, bool* linear, bool* rlinear, MgRim& rim) {
-  if (t.prolong != NEPTUNE_HIP_MG_PROLONG_CONSTANT && t.prolong != NEPTUNE_HIP_MG_PROLONG_LINEAR) return false;
-  if (t.restrict_kind != NEPTUNE_HIP_MG_RESTRICT_AVERAGE && t.restrict_kind != NEPTUNE_HIP_MG_RESTRICT_LINEAR) return false;
-  *linear = t.prolong == NEPTUNE_HIP_MG_PROLONG_LINEAR;
-  *rlinear = t.restrict_kind == NEPTUNE_HIP_MG_RESTRICT_LINEAR;
-  neptune_hip_mg_prolong_t p;
-  p.kind = (*linear || *rlinear) ? NEPTUNE_HIP_MG_PROLONG_LINEAR : NEPTUNE_HIP_MG_PROLONG_CONSTANT;
-  for (int d = 0; d < 3; ++d) {
-    p.rim_lo[d] = t.rim_lo[d];
-    p.rim_hi[d] = t.rim_hi[d];
-  }
-  bool either = false;
-  return prolong_rules(p, mask, rank, &either, rim);
 }
 
 bool stream_capturing(void* stream) {
@@ -374,10 +416,7 @@ struct Solve {
   const neptune_hip_mg_lines_t* lines;   // per level, or nullptr: no level has line stages
   int n_levels, dtype, rank, pre, post, coarse_sweeps;
   MgBox box[kMaxLevels];
-  int mask[kMaxLevels];                  // mask[l]: how level l and l + 1 nest (sizes_nest: the axes, and the grid kind)
-  bool linear[kMaxLevels];               // linear[l]: the pair (l, l + 1) prolongs linearly, by the rules rim[l]
-  bool rlinear[kMaxLevels];              // rlinear[l]: it restricts by the transpose of that prolongation, same rules
-  MgRim rim[kMaxLevels];
+  Pair pair[kMaxLevels];                 // pair[l]: levels l and l + 1
   const neptune_hip_launch_cfg_t* cfg;   // level 0's, nullptr unless the caller set anything
   hipStream_t stream;
 
@@ -395,7 +434,7 @@ struct Solve {
     pre = pre_;
     post = post_;
     coarse_sweeps = coarse_sweeps_;
-    cfg = (cfg_ && (cfg_->kernel || cfg_->variant >= 0 || cfg_->chunk || cfg_->flags)) ? cfg_ : nullptr;
+    cfg = set_cfg(cfg_);
     rank = levels[0].g.rank;
     const size_t elem = elem_size(dtype);
     for (int l = 0; l < n_levels; ++l) {
@@ -413,11 +452,10 @@ struct Solve {
         if (!L.in_rest[i - 1]) return false;
       if (l + 1 < n_levels && !isfinite(L.rscale)) return false;
       if (l > 0) {
-        mask[l - 1] = sizes_nest(box[l - 1], box[l], rank);
-        if (!mask[l - 1]) return false;
-        linear[l - 1] = rlinear[l - 1] = false;
-        if (transfer_ && !transfer_rules(transfer_[l - 1], mask[l - 1], rank, &linear[l - 1], &rlinear[l - 1], rim[l - 1])) return false;
-        if (symmetric_only && linear[l - 1] != rlinear[l - 1]) return false;   // P must be a multiple of R^T
+        Pair& P = pair[l - 1];
+        if (!P.nest(box[l - 1], box[l], rank)) return false;
+        if (transfer_ && !P.rules(transfer_[l - 1])) return false;
+        if (symmetric_only && P.linear != P.rlinear) return false;   // P must be a multiple of R^T
       }
       const void* mine[4] = {L.x, L.b, L.q, L.minv};
       const size_t bytes = box_bytes(box[l], elem);
@@ -451,76 +489,79 @@ struct Solve {
     }
     return true;
   }
-  // level l's inputs with `in0` as input 0
-  void inputs(int l, const void* in0, const void** ins) const {
-    const neptune_hip_mg_level_t& L = levels[l];
-    ins[0] = in0;
-    for (int i = 1; i < L.g.num_inputs; ++i) ins[i] = L.in_rest[i - 1];
+  // every level's factor fields are read while a driver writes `written`: -> false when one meets one of them (one apart()
+  // over all of them; `written` itself has passed its own tests in the entry and passes them here once more)
+  bool factors_apart(Spans written) const {
+    Span factors[kMaxLevels * 9];
+    size_t n = 0;
+    for (int l = 0; l < n_levels && lines; ++l)
+      for (int st = 0; st < lines[l].n_stages; ++st)
+        for (const void* f : {lines[l].lo[st], lines[l].inv[st], lines[l].up[st]}) factors[n++] = {f, box_bytes(box[l], elem_size(dtype))};
+    return apart(written, Spans(factors, n));
+  }
+  // x_l = 0 on every level below the finest
+  void zero_coarse() const {
+    for (int l = 1; l < n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(levels[l].x, 0, box_bytes(box[l], elem_size(dtype)), stream));
   }
   // q_l = A_l(in0), a plain launch
   int apply_of(int l, const void* in0) const {
     const neptune_hip_mg_level_t& L = levels[l];
     const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    inputs(l, in0, ins);
+    ins[0] = in0;
+    for (int i = 1; i < L.g.num_inputs; ++i) ins[i] = L.in_rest[i - 1];
     const neptune_hip_launch_cfg_t* c = l == 0 ? cfg : nullptr;
     return L.fn ? L.fn(&L.g, ins, L.q, (void*)stream, c) : neptune_hip_apply_builtin(L.body, &L.g, ins, L.q, (void*)stream, c);
   }
   // q_l = A_l(x_l)
   int apply(int l) const { return apply_of(l, levels[l].x); }
   int stages(int l) const { return lines ? lines[l].n_stages : 0; }
-  // stage `st` of level l: q = A(x), then the line kernel
-  int line_stage(int l, int st) const {
+  // stage `st` of level l without its apply, in the form `mode`
+  int line_kernel(int l, int st, int mode, void* partials = nullptr) const {
     const neptune_hip_mg_level_t& L = levels[l];
     const neptune_hip_mg_lines_t& S = lines[l];
+    return do_line(dtype, mode, box[l], S.axis[st] + 3 - rank, L.q, L.b, S.lo[st], S.inv[st], S.up[st], L.x, partials, stream);
+  }
+  // stage `st` of level l: q = A(x), then the line kernel
+  int line_stage(int l, int st) const {
     const int rc = apply(l);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    return do_line(dtype, box[l], S.axis[st] + 3 - rank, L.q, L.b, S.lo[st], S.inv[st], S.up[st], L.x, stream);
+    return rc != NEPTUNE_HIP_OK ? rc : line_kernel(l, st, kMgLinePlain);
   }
   // `count` sweeps: the point sweep with minv, or on a level with k >= 1 line stages all k, each after its own apply --
   // stages 0 .. k-1, or k-1 .. 0 when `reversed` (the post-sweeps: a cycle of symmetric stages stays symmetric)
   int sweeps(int l, int count, bool reversed = false) const {
     const neptune_hip_mg_level_t& L = levels[l];
-    const int k = lines ? lines[l].n_stages : 0;
+    const int k = stages(l);
     for (int s = 0; s < count; ++s) {
-      for (int t = 0; t < std::max(k, 1); ++t) {
-        int rc = apply(l);
-        if (rc != NEPTUNE_HIP_OK) return rc;
-        if (k == 0) {
-          rc = do_smooth(dtype, box[l], L.q, L.b, L.minv, L.x, stream);
-        } else {
-          const neptune_hip_mg_lines_t& S = lines[l];
-          const int st = reversed ? k - 1 - t : t;
-          rc = do_line(dtype, box[l], S.axis[st] + 3 - rank, L.q, L.b, S.lo[st], S.inv[st], S.up[st], L.x, stream);
-        }
-        if (rc != NEPTUNE_HIP_OK) return rc;
+      int rc = NEPTUNE_HIP_OK;
+      if (k == 0) {
+        rc = apply(l);
+        if (rc == NEPTUNE_HIP_OK) rc = do_smooth(dtype, box[l], L.q, L.b, L.minv, L.x, stream);
       }
+      for (int t = 0; t < k && rc == NEPTUNE_HIP_OK; ++t) rc = line_stage(l, reversed ? k - 1 - t : t);
+      if (rc != NEPTUNE_HIP_OK) return rc;
     }
     return NEPTUNE_HIP_OK;
   }
-  // the two transfers of the pair (l, l + 1), each by the pair's choice
+  // the two transfers of the pair (l, l + 1)
   int restrict_pair(int l) const {
-    const neptune_hip_mg_level_t& F = levels[l];
-    const neptune_hip_mg_level_t& Cl = levels[l + 1];
-    return rlinear[l] ? do_restrict_linear(dtype, mask[l], box[l], box[l + 1], rim[l], F.b, F.q, F.rscale, Cl.b, Cl.x, stream)
-                      : do_restrict(dtype, mask[l], box[l], box[l + 1], F.b, F.q, F.rscale, Cl.b, Cl.x, stream);
+    return do_restrict(dtype, pair[l], levels[l].b, levels[l].q, levels[l].rscale, levels[l + 1].b, levels[l + 1].x, stream);
   }
-  int prolong_pair(int l) const {
-    const neptune_hip_mg_level_t& F = levels[l];
-    const neptune_hip_mg_level_t& Cl = levels[l + 1];
-    return linear[l] ? do_prolong_linear(dtype, mask[l], box[l], box[l + 1], rim[l], Cl.x, F.x, stream)
-                     : do_prolong(dtype, mask[l], box[l], box[l + 1], Cl.x, F.x, stream);
-  }
-  int cycle(int l) const {
-    if (l == n_levels - 1) return sweeps(l, coarse_sweeps);
-    int rc = sweeps(l, pre);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = apply(l);
+  int prolong_pair(int l) const { return do_prolong(dtype, pair[l], levels[l + 1].x, levels[l].x, stream); }
+  // what a cycle does on level l between its pre- and its post-sweeps: the residual down, the cycle below, the correction up
+  int coarse_correction(int l) const {
+    int rc = apply(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = restrict_pair(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = cycle(l + 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = prolong_pair(l);
+    return prolong_pair(l);
+  }
+  int cycle(int l) const {
+    if (l == n_levels - 1) return sweeps(l, coarse_sweeps);
+    int rc = sweeps(l, pre);
+    if (rc != NEPTUNE_HIP_OK) return rc;
+    rc = coarse_correction(l);
     if (rc != NEPTUNE_HIP_OK) return rc;
     return sweeps(l, post, true);
   }
@@ -538,27 +579,6 @@ struct Solve {
     *rr = dtype == NEPTUNE_HIP_F64 ? h64 : (double)h32;
     return NEPTUNE_HIP_OK;
   }
-  // One cycle as a graph: captured on the stream (nothing runs), instantiated; nullptr when any launch refused under
-  // capture or the runtime would not have the graph -- the caller goes on with plain launches.
-  hipGraphExec_t capture(hipGraph_t* graph_out) const {
-    *graph_out = nullptr;
-    if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    const int rc = cycle(0);
-    hipGraph_t graph = nullptr;
-    if (hipStreamEndCapture(stream, &graph) != hipSuccess) { (void)hipGetLastError(); graph = nullptr; }
-    if (rc != NEPTUNE_HIP_OK || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      return nullptr;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipGraphDestroy(graph);
-      return nullptr;
-    }
-    *graph_out = graph;
-    return exec;
-  }
 };
 
 // a late refusal: after the first launch of a cycle the fields have moved
@@ -569,9 +589,70 @@ bool graph_path_enabled() {
   return !(e && strcmp(e, "0") == 0);
 }
 
+// ---------------------------------------------------------------- the block loop of every driver
+// One unit (a cycle, an iteration) as a graph, this call's: captured on the stream (nothing runs) and instantiated.
+struct UnitGraph {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  // -> false, and nothing kept: a launch refused under capture, or the runtime would not have the graph
+  template <class Unit>
+  bool capture(hipStream_t stream, Unit&& unit) {
+    if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const int rc = unit();
+    if (hipStreamEndCapture(stream, &graph) != hipSuccess) { (void)hipGetLastError(); graph = nullptr; }
+    if (rc == NEPTUNE_HIP_OK && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); exec = nullptr; }
+    if (exec) return true;
+    if (graph) (void)hipGraphDestroy(graph);
+    graph = nullptr;
+    return false;
+  }
+  ~UnitGraph() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+  }
+};
+// Up to `max` units in blocks of check_every.  The first unit runs as plain launches: it validates the request and lets
+// first-use tuning run outside capture.  Then, when at least two more units may follow, ONE capture of unit(); every later
+// unit replays that graph, or, when the capture failed, stays a plain unit().  After each block check(&rr) reads rr back (the
+// block's one synchronise); the loop ends on rr <= tol2.  A unit or a check that refuses ends the call with late(rc).
+// hooks: capturing() before the capture, captured(ok) after it, counted(replayed) after every unit -- the caller's
+// counters, and whatever state of its unit a failed capture must not leave changed.
+template <class Unit, class Check, class Hooks>
+int run_blocks(hipStream_t stream, int64_t max, int64_t check_every, double tol2, int64_t* done_out, double* rr_last, Unit&& unit,
+               Check&& check, Hooks&& hooks) {
+  UnitGraph G;
+  const bool graphs = graph_path_enabled();
+  bool tried = false;
+  int64_t done = 0;
+  while (done < max) {
+    const int64_t block = std::min(check_every, max - done);
+    for (int64_t c = 0; c < block; ++c, ++done) {
+      if (done > 0 && graphs && !tried && max - done >= 2) {
+        tried = true;
+        hooks.capturing();
+        hooks.captured(G.capture(stream, unit));
+      }
+      if (G.exec) {
+        NEPTUNE_HIP_CHECK(hipGraphLaunch(G.exec, stream));
+      } else {
+        const int rc = unit();
+        if (rc != NEPTUNE_HIP_OK) return late(rc);
+      }
+      hooks.counted(G.exec != nullptr);
+      if (done_out) *done_out = done + 1;
+    }
+    double rr = 0.0;
+    const int rc = check(&rr);
+    if (rc != NEPTUNE_HIP_OK) return late(rc);
+    if (rr_last) *rr_last = rr;
+    if (rr <= tol2) break;   // false for a NaN: such a solve runs to `max`
+  }
+  return NEPTUNE_HIP_OK;
+}
+
 // ---------------------------------------------------------------- multigrid-preconditioned conjugate gradients
-// The device block of neptune_hip_mgcg_solve and neptune_hip_mg_smooth_dot: PcgScalars, then rz_0, then the partials of the
-// solver's own kernels; grown on demand, never while a capture is under way.
+// The device block of the MGCG drivers and the kernel-alone sweeps with a dot product: PcgScalars, then rz_0, then the
+// partials of the solver's own kernels; grown on demand, never while a capture is under way.
 void* g_mgcg_ws = nullptr;
 size_t g_mgcg_ws_bytes = 0;
 int64_t g_mgcg_counts[4] = {0, 0, 0, 0};   // plain / graph / fallback iterations, checks of the last mgcg_solve
@@ -590,8 +671,11 @@ bool grow_mgcg_ws(size_t bytes, void* stream) {
   g_mgcg_ws_bytes = bytes;
   return true;
 }
-
-int64_t grid_blocks(const dim3& g) { return (int64_t)g.x * g.y; }
+// room for `count` partials of `elem` bytes behind the scalars: -> where they start, nullptr when the block cannot grow now
+void* mgcg_partials(int64_t count, size_t elem, void* stream) {
+  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)count * elem, stream)) return nullptr;
+  return static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes;
+}
 
 bool region_is_whole(const neptune_hip_apply_geom_t* g) {
   bool whole = true;
@@ -599,8 +683,7 @@ bool region_is_whole(const neptune_hip_apply_geom_t* g) {
   return whole;
 }
 
-// what neptune_hip_mgcg_solve is once its arguments are checked.  S: the solve over the hierarchy whose level 0 carries
-// (z, r) for (x, b) -- the cycle of the preconditioner --, L0: the caller's level 0.
+// what an MGCG entry hands its driver once the arguments are checked
 struct MgcgArgs {
   neptune_hip_apply_dot_fn fn_dot;
   int sweeps;
@@ -612,253 +695,123 @@ struct MgcgArgs {
   double* rr0;
   double* rr_last;
 };
-// The loop of an MGCG solve once its set-up has run, shared by the one-type and the mixed driver: blocks of check_every
-// iterations, the first one as plain launches, then -- when at least two more may follow -- ONE capture of `iteration` as a
-// linear graph that every later iteration replays; after each block read_rr(first, &rr) reads rr back (the block's one
-// synchronise; `first`: rz_0 into g_mgcg_rz0 as well).  `fused` is the iteration's own flag (whether step 1 is the
-// dot-monitored launch): what refused under capture may well run outside, so a failed capture restores it.
-template <class Iteration, class ReadRr>
-int mgcg_iterations(hipStream_t stream, const MgcgArgs& a, bool& fused, Iteration&& iteration, ReadRr&& read_rr) {
-  double rr = 0.0;
-  struct Graph {    // this call's graph of one iteration
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool fallback = false;
-    ~Graph() {
-      if (exec) (void)hipGraphExecDestroy(exec);
-      if (graph) (void)hipGraphDestroy(graph);
-    }
-  } G;
-  // One iteration as a graph: captured on the stream (nothing runs), instantiated; on any refusal under capture the graph is
-  // discarded and the call goes on with plain launches
-  auto capture = [&]() {
-    if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return; }
-    const bool was_fused = fused;
-    const int rc = iteration();
-    hipGraph_t graph = nullptr;
-    if (hipStreamEndCapture(stream, &graph) != hipSuccess) { (void)hipGetLastError(); graph = nullptr; }
-    if (rc != NEPTUNE_HIP_OK || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      fused = was_fused;   // what refused under capture may well run outside
-      return;
-    }
-    if (hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipGraphDestroy(graph);
-      G.exec = nullptr;
-      fused = was_fused;
-      return;
-    }
-    G.graph = graph;
-    G.fallback = !fused;
-  };
-
-  const bool graphs = graph_path_enabled();
-  bool capture_tried = false, rz0_read = false;
-  int64_t done = 0;
-  while (done < a.max_iters) {
-    const int64_t block = a.check_every < a.max_iters - done ? a.check_every : a.max_iters - done;
-    for (int64_t c = 0; c < block; ++c, ++done) {
-      if (done > 0 && graphs && !capture_tried && a.max_iters - done >= 2) {
-        capture_tried = true;
-        capture();
-      }
-      if (done > 0 && G.exec) {
-        NEPTUNE_HIP_CHECK(hipGraphLaunch(G.exec, stream));
-        ++g_mgcg_counts[1];
-        if (G.fallback) ++g_mgcg_counts[2];
-      } else {
-        const int rc = iteration();
-        if (rc != NEPTUNE_HIP_OK) return late(rc);
-        ++g_mgcg_counts[0];
-        if (!fused) ++g_mgcg_counts[2];
-      }
-      if (a.iters_done) *a.iters_done = done + 1;
-    }
-    read_rr(!rz0_read, &rr);
-    rz0_read = true;
-    ++g_mgcg_counts[3];
-    if (a.rr_last) *a.rr_last = rr;
-    if (rr <= a.tol2) break;   // false for a NaN: such a solve runs to max_iters
-  }
-  return NEPTUNE_HIP_OK;
-}
-
+// The fields of one MGCG solve: conjugate gradients' own in D -- x, b, q of the outer operator, r, p --, level 0 of the
+// preconditioner's cycle in S: minv and (z, r_in) for the cycle's (x, b).  scal, partials: the device block.
+// lines0: level 0 smooths with line stages.
+template <class D, class S>
+struct MgcgFields {
+  int64_t n;
+  D* x;
+  const D* b;
+  D *q, *r, *p;
+  const S* minv;
+  S *r_in, *z;
+  PcgScalars<D>* scal;
+  D* partials;
+  bool lines0;
+};
+// What the two forms of MGCG differ in, a policy each: the element types, whether level 0 may have line stages, the grids of
+// the two flat kernels, and four launches -- init (r = b - q, and what the cycle starts from), update (x, r and the cycle's
+// start after alpha), direction (p = z + beta p) and p_from_z (the first direction).  Level 0's last post-sweep, the fifth
+// launch that differs, is do_smooth_dot with or without the wide sum.
+// One type T: r_in is r.  With line stages on level 0, r is stored without z = minv r.
 template <class T>
-int mgcg_solve_typed(const Solve& S, const neptune_hip_mg_level_t& L0, const MgcgArgs& a) {
-  const hipStream_t stream = S.stream;
-  const MgBox& B0 = S.box[0];
-  const int64_t n = B0.n[0] * B0.n[1] * B0.n[2];
-  T* const x = static_cast<T*>(L0.x);
-  const T* const b = static_cast<const T*>(L0.b);
-  T* const q = static_cast<T*>(L0.q);
-  const T* const minv = static_cast<const T*>(L0.minv);
-  T* const r = static_cast<T*>(a.work[0]);
-  T* const p = static_cast<T*>(a.work[1]);
-  T* const z = static_cast<T*>(a.work[2]);
-  T* const tr = static_cast<T*>(a.trace);
-
-  CgBoxParams P;
-  for (int d = 0; d < 3; ++d) {
-    P.n[d] = B0.n[d];
-    P.lo[d] = B0.lo[d];
-    P.hi[d] = B0.lo[d] + B0.m[d];
+struct MgcgOneType {
+  using D = T;
+  using S = T;
+  using Fields = MgcgFields<T, T>;
+  static constexpr bool kLines0 = true;
+  static FlatGrid update_grid(const Fields& f) {
+    return f.lines0 ? flat_grid(f.n, sizeof(T), {f.p, f.q, f.x, f.r}) : flat_grid(f.n, sizeof(T), {f.p, f.q, f.minv, f.x, f.r, f.z});
   }
-  const int64_t init_chunk = (P.n[2] + 255) / 256;
-  const dim3 init_grid = grid_for_blocks(P.n[0] * P.n[1] * init_chunk);
-  // k0 >= 1: level 0 smooths with line stages: r is stored without z = minv r, the cycle starts with the
-  // apply-free stage and ends with the stage that yields r . z
-  const int k0 = S.stages(0);
-  const neptune_hip_mg_lines_t* const ln0 = k0 ? &S.lines[0] : nullptr;
-  const int dot_axis = k0 ? ln0->axis[0] + 3 - S.rank : 0;
-  const FlatGrid upd = k0 ? flat_grid(n, sizeof(T), {p, q, x, r}) : flat_grid(n, sizeof(T), {p, q, minv, x, r, z}),
-                 dir = flat_grid(n, sizeof(T), {z, p});
-  const RowGrid sd = row_grid(B0);
-  const int64_t dot_blocks = k0 ? grid_blocks(line_grid(B0, dot_axis).grid) : grid_blocks(sd.grid);
-  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, dot_blocks});
-  grow_mgcg_ws(kMgcgScalarBytes + (size_t)most * sizeof(T), (void*)stream);   // no capture is under way: the entry refused one
-  PcgScalars<T>* const scal = static_cast<PcgScalars<T>*>(g_mgcg_ws);
-  T* const rz0_dev = reinterpret_cast<T*>(static_cast<char*>(g_mgcg_ws) + kMgcgRz0Offset);
-  T* const partials = reinterpret_cast<T*>(static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes);
-  auto final_kernel = [&](int64_t count, int stage) {
-    hipLaunchKernelGGL(neptune_mgcg_final<T>, dim3(1), dim3(256), 0, stream, (const T*)partials, count, scal, rz0_dev, tr, a.max_iters, stage);
-  };
-  // `count` device scalars from `dev` after everything queued on the stream: the one synchronise of a block
-  auto read = [&](const T* dev, double* host, const T* dev2 = nullptr, double* host2 = nullptr) {
-    T h = 0, h2 = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, dev, sizeof(T), hipMemcpyDeviceToHost, stream));
-    if (dev2) NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h2, dev2, sizeof(T), hipMemcpyDeviceToHost, stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(stream));
-    *host = (double)h;
-    if (dev2) *host2 = (double)h2;
-  };
-  // the rest of M: everything of the cycle on A z = r after its first pre-sweep (z = minv r, stored with r); its last
-  // post-sweep yields r . z, which `stage` of the bookkeeping kernel takes
-  auto rest_of_cycle = [&](int stage) -> int {
-    int rc = NEPTUNE_HIP_OK;
-    if (k0) {   // the first pre-sweep: stage 0 without an apply, from z = 0; then its other stages
-      rc = do_line_first(S.dtype, B0, dot_axis, r, ln0->lo[0], ln0->inv[0], ln0->up[0], z, stream);
-      for (int st = 1; st < k0 && rc == NEPTUNE_HIP_OK; ++st) rc = S.line_stage(0, st);
-      if (rc != NEPTUNE_HIP_OK) return rc;
-    }
-    rc = S.sweeps(0, a.sweeps - 1);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.apply(0);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.restrict_pair(0);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.cycle(1);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.prolong_pair(0);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.sweeps(0, a.sweeps - 1, true);
-    for (int st = k0 - 1; st >= 1 && rc == NEPTUNE_HIP_OK; --st) rc = S.line_stage(0, st);   // the last post-sweep, down to stage 1
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.apply(0);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    if (k0) {
-      rc = do_line_dot(S.dtype, B0, dot_axis, q, r, ln0->lo[0], ln0->inv[0], ln0->up[0], z, partials, stream);
-      if (rc != NEPTUNE_HIP_OK) return rc;
-    } else {
-      hipLaunchKernelGGL(neptune_mg_smooth_dot<T>, sd.grid, dim3(256), 0, stream, B0, sd.nchunk, (const T*)q, (const T*)r, minv, z, partials);
-    }
-    final_kernel(dot_blocks, stage);
-    return launched();
-  };
+  static FlatGrid direction_grid(const Fields& f) { return flat_grid(f.n, sizeof(T), {f.z, f.p}); }
+  static void init(const Fields& f, const CgBoxParams& P, int64_t nchunk, dim3 grid, hipStream_t s) {
+    if (f.lines0) hipLaunchKernelGGL((neptune_mgcg_init<T, false>), grid, dim3(256), 0, s, P, nchunk, f.b, (const T*)f.q, f.minv, f.r, f.z, f.partials);
+    else hipLaunchKernelGGL(neptune_mgcg_init<T>, grid, dim3(256), 0, s, P, nchunk, f.b, (const T*)f.q, f.minv, f.r, f.z, f.partials);
+  }
+  static void update(const Fields& f, const FlatGrid& g, hipStream_t s) {
+    if (f.lines0)
+      flat_launch(g, s, neptune_mgcg_update<T, true, false>, neptune_mgcg_update<T, false, false>, f.n, f.scal, f.p, f.q, f.minv, f.x, f.r, f.z, f.partials);
+    else flat_launch(g, s, neptune_mgcg_update<T, true>, neptune_mgcg_update<T, false>, f.n, f.scal, f.p, f.q, f.minv, f.x, f.r, f.z, f.partials);
+  }
+  static void direction(const Fields& f, const FlatGrid& g, hipStream_t s) {
+    flat_launch(g, s, neptune_mgcg_direction<T, true>, neptune_mgcg_direction<T, false>, f.n, f.scal, f.z, f.p);
+  }
+  static void p_from_z(const Fields& f, const FlatGrid&, hipStream_t s) {
+    NEPTUNE_HIP_CHECK(hipMemcpyAsync(f.p, f.z, (size_t)f.n * sizeof(T), hipMemcpyDeviceToDevice, s));
+  }
+};
+// Conjugate gradients in f64 around a cycle in f32: r_in = r32, the narrowed residual.  The flat kernels take
+// groups of kMixedGroup cells; level 0 has no line stages (a wide-sum form of the line kernels is not built).
+struct MgcgMixed {
+  using D = double;
+  using S = float;
+  using Fields = MgcgFields<double, float>;
+  static constexpr bool kLines0 = false;
+  static FlatGrid update_grid(const Fields& f) { return flat_grid_group(f.n, kMixedGroup, {f.p, f.q, f.minv, f.x, f.r, f.r_in, f.z}); }
+  static FlatGrid direction_grid(const Fields& f) { return flat_grid_group(f.n, kMixedGroup, {f.z, f.p}); }
+  static void init(const Fields& f, const CgBoxParams& P, int64_t nchunk, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((neptune_mgcg_init_mixed<D, S>), grid, dim3(256), 0, s, P, nchunk, f.b, (const D*)f.q, f.minv, f.r, f.r_in, f.z, f.partials);
+  }
+  static void update(const Fields& f, const FlatGrid& g, hipStream_t s) {
+    flat_launch(g, s, neptune_mgcg_update_mixed<D, S, true>, neptune_mgcg_update_mixed<D, S, false>, f.n, f.scal, f.p, f.q, f.minv, f.x, f.r, f.r_in,
+                f.z, f.partials);
+  }
+  static void direction(const Fields& f, const FlatGrid& g, hipStream_t s) {
+    flat_launch(g, s, neptune_mgcg_direction_mixed<D, S, true>, neptune_mgcg_direction_mixed<D, S, false>, f.n, f.scal, f.z, f.p);
+  }
+  static void p_from_z(const Fields& f, const FlatGrid& g, hipStream_t s) {
+    flat_launch(g, s, neptune_mgcg_direction_mixed<D, S, true, true>, neptune_mgcg_direction_mixed<D, S, false, true>, f.n, f.scal, f.z, f.p);
+  }
+};
 
-  // ---- set-up
-  for (int l = 1; l < S.n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(S.levels[l].x, 0, box_bytes(S.box[l], sizeof(T)), stream));
-  if (!region_is_whole(&L0.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), stream));
-  // with line stages on level 0, z outside Omega_0 is the error equation's rim: zero-filled here, never written again
-  if (k0) NEPTUNE_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)n * sizeof(T), stream));
-  int rc = S.apply_of(0, x);
-  if (rc != NEPTUNE_HIP_OK) return rc;
-  if (k0) hipLaunchKernelGGL((neptune_mgcg_init<T, false>), init_grid, dim3(256), 0, stream, P, init_chunk, b, (const T*)q, minv, r, z, partials);
-  else hipLaunchKernelGGL(neptune_mgcg_init<T>, init_grid, dim3(256), 0, stream, P, init_chunk, b, (const T*)q, minv, r, z, partials);
-  final_kernel(grid_blocks(init_grid), kMgcgStartRr);
-  NEPTUNE_HIP_CHECK(hipGetLastError());
-  double rr = 0.0;
-  read(&scal->rr, &rr);
-  if (a.rr0) *a.rr0 = rr;
-  if (a.rr_last) *a.rr_last = rr;
-  if (rr <= a.tol2 || a.max_iters == 0) return NEPTUNE_HIP_OK;
-  rc = rest_of_cycle(kMgcgStartRz);
-  if (rc != NEPTUNE_HIP_OK) return late(rc);
-  NEPTUNE_HIP_CHECK(hipMemcpyAsync(p, z, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
-
-  // ---- one iteration.  fused: q = A(p) and pq out of one dot-monitored launch; a refusal of that entry
-  // (NEPTUNE_HIP_EUNSUPPORTED, nothing launched) is remembered: a plain launch and neptune_hip_dot from then on
-  bool fused = L0.fn ? a.fn_dot != nullptr : true;
-  auto iteration = [&]() -> int {
-    int rc;
-    if (fused) {
-      const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-      S.inputs(0, p, ins);
-      rc = L0.fn ? a.fn_dot(&L0.g, ins, q, &scal->pq, (void*)stream, S.cfg)
-                 : neptune_hip_apply_builtin_dot(L0.body, &L0.g, ins, q, &scal->pq, (void*)stream, S.cfg);
-      if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
-      else if (rc != NEPTUNE_HIP_OK) return rc;
-    }
-    if (!fused) {
-      rc = S.apply_of(0, p);
-      if (rc != NEPTUNE_HIP_OK) return late(rc);
-      rc = neptune_hip_dot(S.dtype, &L0.g, q, p, &scal->pq, (void*)stream);
-      if (rc != NEPTUNE_HIP_OK) return late(rc);
-    }
-    if (k0) flat_launch(upd, stream, neptune_mgcg_update<T, true, false>, neptune_mgcg_update<T, false, false>, n, scal, p, q, minv, x, r, z, partials);
-    else flat_launch(upd, stream, neptune_mgcg_update<T, true>, neptune_mgcg_update<T, false>, n, scal, p, q, minv, x, r, z, partials);
-    final_kernel((int64_t)upd.blocks, kMgcgRr);
-    rc = rest_of_cycle(kMgcgRz);
-    if (rc != NEPTUNE_HIP_OK) return late(rc);
-    flat_launch(dir, stream, neptune_mgcg_direction<T, true>, neptune_mgcg_direction<T, false>, n, scal, z, p);
-    return launched();
-  };
-
-  return mgcg_iterations(stream, a, fused, iteration, [&](bool first, double* out) {
-    if (first) read(&scal->rr, out, rz0_dev, &g_mgcg_rz0);
-    else read(&scal->rr, out);
-  });
-}
-
-// ---------------------------------------------------------------- mixed precision: CG in D around a cycle in S
-// what neptune_hip_mgcg_solve_mixed is once its arguments are checked.  S: the solve over the inner hierarchy in S, whose
-// level 0 carries (z32, r32) for (x, b); O: the outer operator in D with the caller's x, b and q; a.work = r, p in D; cfg: the
-// outer operator's launch configuration (nullptr unless the caller set anything).  Level 0
-// has no line stages (the entry refused them).
-template <class D, class Sx>
-int mgcg_solve_mixed_typed(const Solve& S, const neptune_hip_mg_level_t& O, const neptune_hip_launch_cfg_t* cfg, const MgcgArgs& a) {
+// An MGCG solve once its arguments are checked.  S: the solve over the preconditioner's hierarchy, whose level 0 carries
+// (z, r_in) for (x, b); O: the outer operator, in D, with the caller's x, b and q (the one-type form: the caller's level 0);
+// ocfg: its launch configuration (nullptr unless the caller set anything); a.work = r, p in D.
+template <class P>
+int mgcg_drive(const Solve& S, const neptune_hip_mg_level_t& O, const neptune_hip_launch_cfg_t* ocfg, const MgcgArgs& a) {
+  using D = typename P::D;
+  using Sx = typename P::S;
+  constexpr int dtype_outer = std::is_same<D, double>::value ? NEPTUNE_HIP_F64 : NEPTUNE_HIP_F32;
   const hipStream_t stream = S.stream;
   const MgBox& B0 = S.box[0];
   const neptune_hip_mg_level_t& F = S.levels[0];
-  const int64_t n = B0.n[0] * B0.n[1] * B0.n[2];
-  D* const x = static_cast<D*>(O.x);
-  const D* const b = static_cast<const D*>(O.b);
-  D* const q = static_cast<D*>(O.q);
-  D* const r = static_cast<D*>(a.work[0]);
-  D* const p = static_cast<D*>(a.work[1]);
+  // k0 >= 1: level 0 smooths with line stages: the cycle starts with the apply-free form of stage 0 and ends
+  // with the form of it that yields r . z
+  const int k0 = P::kLines0 ? S.stages(0) : 0;
+  const int dot_axis = k0 ? S.lines[0].axis[0] + 3 - S.rank : 0;
+  typename P::Fields f;
+  f.n = B0.n[0] * B0.n[1] * B0.n[2];
+  f.x = static_cast<D*>(O.x);
+  f.b = static_cast<const D*>(O.b);
+  f.q = static_cast<D*>(O.q);
+  f.r = static_cast<D*>(a.work[0]);
+  f.p = static_cast<D*>(a.work[1]);
+  f.minv = static_cast<const Sx*>(F.minv);
+  f.r_in = static_cast<Sx*>(F.b);
+  f.z = static_cast<Sx*>(F.x);
+  f.lines0 = k0 > 0;
   D* const tr = static_cast<D*>(a.trace);
-  const Sx* const minv = static_cast<const Sx*>(F.minv);
-  Sx* const r32 = static_cast<Sx*>(F.b);
-  Sx* const z32 = static_cast<Sx*>(F.x);
 
-  CgBoxParams P;
+  CgBoxParams Bp;
   for (int d = 0; d < 3; ++d) {
-    P.n[d] = B0.n[d];
-    P.lo[d] = B0.lo[d];
-    P.hi[d] = B0.lo[d] + B0.m[d];
+    Bp.n[d] = B0.n[d];
+    Bp.lo[d] = B0.lo[d];
+    Bp.hi[d] = B0.lo[d] + B0.m[d];
   }
-  const int64_t init_chunk = (P.n[2] + 255) / 256;
-  const dim3 init_grid = grid_for_blocks(P.n[0] * P.n[1] * init_chunk);
-  const FlatGrid upd = flat_grid_group(n, kMixedGroup, {p, q, minv, x, r, r32, z32}), dir = flat_grid_group(n, kMixedGroup, {z32, p});
+  const int64_t init_chunk = (Bp.n[2] + 255) / 256;
+  const dim3 init_grid = grid_for_blocks(Bp.n[0] * Bp.n[1] * init_chunk);
+  const FlatGrid upd = P::update_grid(f), dir = P::direction_grid(f);
   const RowGrid sd = row_grid(B0);
-  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, grid_blocks(sd.grid)});
-  grow_mgcg_ws(kMgcgScalarBytes + (size_t)most * sizeof(D), (void*)stream);   // no capture is under way: the entry refused one
-  PcgScalars<D>* const scal = static_cast<PcgScalars<D>*>(g_mgcg_ws);
+  const int64_t dot_blocks = k0 ? grid_blocks(line_grid(B0, dot_axis).grid) : grid_blocks(sd.grid);
+  const int64_t most = std::max<int64_t>({grid_blocks(init_grid), (int64_t)upd.blocks, dot_blocks});
+  f.partials = static_cast<D*>(mgcg_partials(most, sizeof(D), (void*)stream));   // no capture is under way: the entry refused one
+  f.scal = static_cast<PcgScalars<D>*>(g_mgcg_ws);
   D* const rz0_dev = reinterpret_cast<D*>(static_cast<char*>(g_mgcg_ws) + kMgcgRz0Offset);
-  D* const partials = reinterpret_cast<D*>(static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes);
   auto final_kernel = [&](int64_t count, int stage) {
-    hipLaunchKernelGGL(neptune_mgcg_final<D>, dim3(1), dim3(256), 0, stream, (const D*)partials, count, scal, rz0_dev, tr, a.max_iters, stage);
+    hipLaunchKernelGGL(neptune_mgcg_final<D>, dim3(1), dim3(256), 0, stream, (const D*)f.partials, count, f.scal, rz0_dev, tr, a.max_iters, stage);
   };
+  // one or two device scalars after everything queued on the stream: the one synchronise of a block
   auto read = [&](const D* dev, double* host, const D* dev2 = nullptr, double* host2 = nullptr) {
     D h = 0, h2 = 0;
     NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, dev, sizeof(D), hipMemcpyDeviceToHost, stream));
@@ -867,7 +820,7 @@ int mgcg_solve_mixed_typed(const Solve& S, const neptune_hip_mg_level_t& O, cons
     *host = (double)h;
     if (dev2) *host2 = (double)h2;
   };
-  // q = A(in0) by the outer operator, a plain launch in D
+  // the outer operator's inputs with `in0` as input 0, and q = A(in0) by it, a plain launch in D
   auto outer_inputs = [&](const void* in0, const void** ins) {
     ins[0] = in0;
     for (int i = 1; i < O.g.num_inputs; ++i) ins[i] = O.in_rest[i - 1];
@@ -875,79 +828,172 @@ int mgcg_solve_mixed_typed(const Solve& S, const neptune_hip_mg_level_t& O, cons
   auto outer_apply = [&](const void* in0) -> int {
     const void* ins[NEPTUNE_HIP_MAX_INPUTS];
     outer_inputs(in0, ins);
-    return O.fn ? O.fn(&O.g, ins, q, (void*)stream, cfg) : neptune_hip_apply_builtin(O.body, &O.g, ins, q, (void*)stream, cfg);
+    return O.fn ? O.fn(&O.g, ins, O.q, (void*)stream, ocfg) : neptune_hip_apply_builtin(O.body, &O.g, ins, O.q, (void*)stream, ocfg);
   };
-  // the rest of M32: the cycle in S on A z32 = r32 after its first pre-sweep (z32 = minv r32, stored with r32); its last
-  // post-sweep yields r32 . z32 in D, which `stage` of the bookkeeping kernel takes
+  // the rest of M: everything of the cycle on A z = r_in after its first pre-sweep (z = minv r_in, stored with r_in; with
+  // line stages: stage 0 without an apply, from z = 0, then the other stages); its last post-sweep yields r_in . z in D,
+  // which `stage` of the bookkeeping kernel takes
   auto rest_of_cycle = [&](int stage) -> int {
-    int rc = S.sweeps(0, a.sweeps - 1);
+    int rc = k0 ? S.line_kernel(0, 0, kMgLineFirst) : NEPTUNE_HIP_OK;
+    for (int st = 1; st < k0 && rc == NEPTUNE_HIP_OK; ++st) rc = S.line_stage(0, st);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.apply(0);
+    rc = S.sweeps(0, a.sweeps - 1);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.restrict_pair(0);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.cycle(1);
-    if (rc != NEPTUNE_HIP_OK) return rc;
-    rc = S.prolong_pair(0);
+    rc = S.coarse_correction(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.sweeps(0, a.sweeps - 1, true);
+    for (int st = k0 - 1; st >= 1 && rc == NEPTUNE_HIP_OK; --st) rc = S.line_stage(0, st);   // the last post-sweep, down to stage 1
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = S.apply(0);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    hipLaunchKernelGGL((neptune_mg_smooth_dot_wide<D, Sx>), sd.grid, dim3(256), 0, stream, B0, sd.nchunk, static_cast<const Sx*>(F.q),
-                       (const Sx*)r32, minv, z32, partials);
-    final_kernel(grid_blocks(sd.grid), stage);
+    if (k0) {
+      rc = S.line_kernel(0, 0, kMgLineDot, f.partials);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+    } else {   // the point sweep that yields r_in . z: in D, the wide sum when the cycle's type is narrower
+      rc = do_smooth_dot(S.dtype, !std::is_same<D, Sx>::value, B0, F.q, F.b, F.minv, F.x, f.partials, stream);
+      if (rc != NEPTUNE_HIP_OK) return rc;
+    }
+    final_kernel(dot_blocks, stage);
     return launched();
   };
 
   // ---- set-up
-  for (int l = 1; l < S.n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(S.levels[l].x, 0, box_bytes(S.box[l], sizeof(Sx)), stream));
-  if (!region_is_whole(&O.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(D), stream));
-  int rc = outer_apply(x);
+  S.zero_coarse();
+  if (!region_is_whole(&O.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(f.q, 0, (size_t)f.n * sizeof(D), stream));
+  // with line stages on level 0, z outside Omega_0 is the error equation's rim: zero-filled here, never written again
+  if (k0) NEPTUNE_HIP_CHECK(hipMemsetAsync(f.z, 0, (size_t)f.n * sizeof(Sx), stream));
+  int rc = outer_apply(f.x);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  hipLaunchKernelGGL((neptune_mgcg_init_mixed<D, Sx>), init_grid, dim3(256), 0, stream, P, init_chunk, b, (const D*)q, minv, r, r32, z32, partials);
+  P::init(f, Bp, init_chunk, init_grid, stream);
   final_kernel(grid_blocks(init_grid), kMgcgStartRr);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   double rr = 0.0;
-  read(&scal->rr, &rr);
+  read(&f.scal->rr, &rr);
   if (a.rr0) *a.rr0 = rr;
   if (a.rr_last) *a.rr_last = rr;
   if (rr <= a.tol2 || a.max_iters == 0) return NEPTUNE_HIP_OK;
   rc = rest_of_cycle(kMgcgStartRz);
   if (rc != NEPTUNE_HIP_OK) return late(rc);
-  flat_launch(dir, stream, neptune_mgcg_direction_mixed<D, Sx, true, true>, neptune_mgcg_direction_mixed<D, Sx, false, true>, n, scal, z32, p);
+  P::p_from_z(f, dir, stream);
 
-  // ---- one iteration; `fused` as in mgcg_solve_typed, on the outer operator
+  // ---- one iteration.  fused: q = A(p) and pq out of one dot-monitored launch; a refusal of that entry
+  // (NEPTUNE_HIP_EUNSUPPORTED, nothing launched) is remembered: a plain launch and neptune_hip_dot from then on
   bool fused = O.fn ? a.fn_dot != nullptr : true;
   auto iteration = [&]() -> int {
     int rc;
     if (fused) {
       const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-      outer_inputs(p, ins);
-      rc = O.fn ? a.fn_dot(&O.g, ins, q, &scal->pq, (void*)stream, cfg)
-                : neptune_hip_apply_builtin_dot(O.body, &O.g, ins, q, &scal->pq, (void*)stream, cfg);
+      outer_inputs(f.p, ins);
+      rc = O.fn ? a.fn_dot(&O.g, ins, O.q, &f.scal->pq, (void*)stream, ocfg)
+                : neptune_hip_apply_builtin_dot(O.body, &O.g, ins, O.q, &f.scal->pq, (void*)stream, ocfg);
       if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
       else if (rc != NEPTUNE_HIP_OK) return rc;
     }
     if (!fused) {
-      rc = outer_apply(p);
+      rc = outer_apply(f.p);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
-      rc = neptune_hip_dot(NEPTUNE_HIP_F64, &O.g, q, p, &scal->pq, (void*)stream);
+      rc = neptune_hip_dot(dtype_outer, &O.g, f.q, f.p, &f.scal->pq, (void*)stream);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
     }
-    flat_launch(upd, stream, neptune_mgcg_update_mixed<D, Sx, true>, neptune_mgcg_update_mixed<D, Sx, false>, n, scal, p, q, minv, x, r, r32, z32,
-                partials);
+    P::update(f, upd, stream);
     final_kernel((int64_t)upd.blocks, kMgcgRr);
     rc = rest_of_cycle(kMgcgRz);
     if (rc != NEPTUNE_HIP_OK) return late(rc);
-    flat_launch(dir, stream, neptune_mgcg_direction_mixed<D, Sx, true>, neptune_mgcg_direction_mixed<D, Sx, false>, n, scal, z32, p);
+    P::direction(f, dir, stream);
     return launched();
   };
+  // the counters, and `fused` across the capture: what refused under capture may well run outside, so a failed capture
+  // restores it; a graph captured without the fused launch counts every replay as a fallback iteration
+  struct Hooks {
+    bool& fused;
+    bool was_fused = false, graph_fallback = false;
+    void capturing() { was_fused = fused; }
+    void captured(bool ok) {
+      if (ok) graph_fallback = !fused;
+      else fused = was_fused;
+    }
+    void counted(bool replayed) {
+      ++g_mgcg_counts[replayed ? 1 : 0];
+      if (replayed ? graph_fallback : !fused) ++g_mgcg_counts[2];
+    }
+  } hooks{fused};
+  bool rz0_read = false;
+  return run_blocks(stream, a.max_iters, a.check_every, a.tol2, a.iters_done, a.rr_last, iteration,
+                    [&](double* out) -> int {   // the first check reads rz_0 as well
+                      if (!rz0_read) read(&f.scal->rr, out, rz0_dev, &g_mgcg_rz0);
+                      else read(&f.scal->rr, out);
+                      rz0_read = true;
+                      ++g_mgcg_counts[3];
+                      return NEPTUNE_HIP_OK;
+                    },
+                    hooks);
+}
 
-  return mgcg_iterations(stream, a, fused, iteration, [&](bool first, double* out) {
-    if (first) read(&scal->rr, out, rz0_dev, &g_mgcg_rz0);
-    else read(&scal->rr, out);
-  });
+// ---------------------------------------------------------------- the kernel-alone entries' shared parts
+// the point sweep with its dot product alone: the sum in `dtype_sum` (dtype itself, or f64 over f32 fields) into *dot_out
+int smooth_dot_alone(int dtype, int dtype_sum, const neptune_hip_apply_geom_t* g, const void* q, const void* b, const void* minv, void* x,
+                     void* dot_out, void* stream) {
+  if (!q || !b || !minv || !x || !dot_out) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B)) return NEPTUNE_HIP_EINVAL;
+  const size_t sum_elem = elem_size(dtype_sum), bytes = box_bytes(B, elem_size(dtype));
+  if (!apart({{x, bytes}, {dot_out, sum_elem, sum_elem}}, {{q, bytes}, {b, bytes}, {minv, bytes}})) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const int64_t blocks = grid_blocks(row_grid(B).grid);
+  void* const partials = mgcg_partials(blocks, sum_elem, stream);
+  if (!partials) return NEPTUNE_HIP_EUNSUPPORTED;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = do_smooth_dot(dtype, dtype_sum != dtype, B, q, b, minv, x, partials, s);
+  return rc != NEPTUNE_HIP_OK ? rc : monitor_final(dtype_sum, partials, blocks, dot_out, s);
+}
+// one line stage alone in the form `mode`: q is null for kMgLineFirst, dot_out for every form but kMgLineDot
+int line_alone(int mode, int dtype, const neptune_hip_apply_geom_t* g, int axis, void* q, const void* b, const void* lo, const void* inv,
+               const void* up, void* x, void* dot_out, void* stream) {
+  const bool dot = mode == kMgLineDot;
+  if ((!q && mode != kMgLineFirst) || !b || !lo || !inv || !up || !x || (!dot_out && dot) || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  MgBox B;
+  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
+  const size_t elem = elem_size(dtype), bytes = box_bytes(B, elem);
+  if (!apart({{x, bytes}, {q, bytes, 1, true}, {dot_out, elem, elem, true}}, {{b, bytes}, {lo, bytes}, {inv, bytes}, {up, bytes}}))
+    return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  const int box_axis = axis + 3 - g->rank;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!dot) return do_line(dtype, mode, B, box_axis, q, b, lo, inv, up, x, nullptr, s);
+  const int64_t blocks = grid_blocks(line_grid(B, box_axis).grid);
+  void* const partials = mgcg_partials(blocks, elem, stream);
+  if (!partials) return NEPTUNE_HIP_EUNSUPPORTED;
+  const int rc = do_line(dtype, mode, B, box_axis, q, b, lo, inv, up, x, partials, s);
+  return rc != NEPTUNE_HIP_OK ? rc : monitor_final(dtype, partials, blocks, dot_out, s);
+}
+// a pair's restriction alone; t: the caller's choice, or nullptr: what the pair's grid kind implies
+int restrict_alone(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
+                   const neptune_hip_mg_transfer_t* t, const void* b_fine, const void* q_fine, double rscale, void* b_coarse, void* x_coarse,
+                   void* stream) {
+  if (!b_fine || !q_fine || !b_coarse || !x_coarse || !known_dtype(dtype) || !isfinite(rscale)) return NEPTUNE_HIP_EINVAL;
+  Pair P;
+  if (!P.nest(g_fine, g_coarse) || (t && !P.rules(*t))) return NEPTUNE_HIP_EINVAL;
+  const size_t fb = box_bytes(P.F, elem_size(dtype)), cb = box_bytes(P.Cb, elem_size(dtype));
+  if (!apart({{b_coarse, cb}, {x_coarse, cb}}, {{b_fine, fb}, {q_fine, fb}})) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  return do_restrict(dtype, P, b_fine, q_fine, rscale, b_coarse, x_coarse, reinterpret_cast<hipStream_t>(stream));
+}
+int prolong_alone(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
+                  const neptune_hip_mg_transfer_t* t, const void* x_coarse, void* x_fine, void* stream) {
+  if (!x_coarse || !x_fine || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  Pair P;
+  if (!P.nest(g_fine, g_coarse) || (t && !P.rules(*t))) return NEPTUNE_HIP_EINVAL;
+  if (!apart({{x_fine, box_bytes(P.F, elem_size(dtype))}}, {{x_coarse, box_bytes(P.Cb, elem_size(dtype))}})) return NEPTUNE_HIP_EINVAL;
+  ensure_init();
+  return do_prolong(dtype, P, x_coarse, x_fine, reinterpret_cast<hipStream_t>(stream));
+}
+
+void mgcg_reset(int64_t* iters_done, double* rr0, double* rr_last) {
+  g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
+  g_mgcg_rz0 = 0.0;
+  if (iters_done) *iters_done = 0;
+  if (rr0) *rr0 = 0.0;
+  if (rr_last) *rr_last = 0.0;
 }
 
 }  // namespace
@@ -956,156 +1002,77 @@ extern "C" {
 
 int neptune_hip_mg_smooth(int dtype, const neptune_hip_apply_geom_t* g, const void* q, const void* b, const void* minv, void* x,
                           void* stream) {
-  if (!g || !q || !b || !minv || !x || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  if (!q || !b || !minv || !x || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
   MgBox B;
   if (!level_box(g, B)) return NEPTUNE_HIP_EINVAL;
   const size_t bytes = box_bytes(B, elem_size(dtype));
-  if (buffers_overlap(x, bytes, q, bytes) || buffers_overlap(x, bytes, b, bytes) || buffers_overlap(x, bytes, minv, bytes)) return NEPTUNE_HIP_EINVAL;
+  if (!apart({{x, bytes}}, {{q, bytes}, {b, bytes}, {minv, bytes}})) return NEPTUNE_HIP_EINVAL;
   ensure_init();
   return do_smooth(dtype, B, q, b, minv, x, reinterpret_cast<hipStream_t>(stream));
 }
 
+int neptune_hip_mg_smooth_dot(int dtype, const neptune_hip_apply_geom_t* g, const void* q, const void* b, const void* minv, void* x,
+                              void* dot_out, void* stream) {
+  if (!known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
+  return smooth_dot_alone(dtype, dtype, g, q, b, minv, x, dot_out, stream);
+}
+
+int neptune_hip_mg_smooth_dot_wide(int dtype, int dtype_sum, const neptune_hip_apply_geom_t* g, const void* q, const void* b,
+                                   const void* minv, void* x, void* dot_out, void* stream) {
+  if (dtype != NEPTUNE_HIP_F32 || dtype_sum != NEPTUNE_HIP_F64) return NEPTUNE_HIP_EINVAL;
+  return smooth_dot_alone(dtype, dtype_sum, g, q, b, minv, x, dot_out, stream);
+}
+
 int neptune_hip_mg_line_smooth(int dtype, const neptune_hip_apply_geom_t* g, int axis, void* q, const void* b, const void* lo,
                                const void* inv, const void* up, void* x, void* stream) {
-  if (!g || !q || !b || !lo || !inv || !up || !x || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  MgBox B;
-  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
-  const size_t bytes = box_bytes(B, elem_size(dtype));
-  for (const void* f : {(const void*)q, b, lo, inv, up})
-    if (buffers_overlap(x, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  for (const void* f : {b, lo, inv, up})
-    if (buffers_overlap(q, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  return do_line(dtype, B, axis + 3 - g->rank, q, b, lo, inv, up, x, reinterpret_cast<hipStream_t>(stream));
+  return line_alone(kMgLinePlain, dtype, g, axis, q, b, lo, inv, up, x, nullptr, stream);
 }
 
 int neptune_hip_mg_line_first(int dtype, const neptune_hip_apply_geom_t* g, int axis, const void* b, const void* lo, const void* inv,
                               const void* up, void* x, void* stream) {
-  if (!g || !b || !lo || !inv || !up || !x || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  MgBox B;
-  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
-  const size_t bytes = box_bytes(B, elem_size(dtype));
-  for (const void* f : {b, lo, inv, up})
-    if (buffers_overlap(x, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  return do_line_first(dtype, B, axis + 3 - g->rank, b, lo, inv, up, x, reinterpret_cast<hipStream_t>(stream));
+  return line_alone(kMgLineFirst, dtype, g, axis, nullptr, b, lo, inv, up, x, nullptr, stream);
 }
 
 int neptune_hip_mg_line_smooth_dot(int dtype, const neptune_hip_apply_geom_t* g, int axis, void* q, const void* b, const void* lo,
                                    const void* inv, const void* up, void* x, void* dot_out, void* stream) {
-  if (!g || !q || !b || !lo || !inv || !up || !x || !dot_out || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  MgBox B;
-  if (!level_box(g, B) || axis < 0 || axis >= g->rank) return NEPTUNE_HIP_EINVAL;
-  const size_t elem = elem_size(dtype), bytes = box_bytes(B, elem);
-  for (const void* f : {(const void*)q, b, lo, inv, up})
-    if (buffers_overlap(x, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  for (const void* f : {b, lo, inv, up})
-    if (buffers_overlap(q, bytes, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  if ((uintptr_t)dot_out % elem != 0) return NEPTUNE_HIP_EINVAL;
-  for (const void* f : {(const void*)q, b, lo, inv, up, (const void*)x})
-    if (buffers_overlap(dot_out, elem, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  const int box_axis = axis + 3 - g->rank;
-  const int64_t blocks = grid_blocks(line_grid(B, box_axis).grid);
-  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)blocks * elem, stream)) return NEPTUNE_HIP_EUNSUPPORTED;
-  void* const partials = static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes;
-  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int rc = do_line_dot(dtype, B, box_axis, q, b, lo, inv, up, x, partials, s);
-  if (rc != NEPTUNE_HIP_OK) return rc;
-  return by_type(dtype,
-                 [&] {
-                   hipLaunchKernelGGL(neptune_monitor_final<double>, dim3(1), dim3(256), 0, s, static_cast<const double*>(partials), blocks,
-                                      static_cast<double*>(dot_out));
-                   return launched();
-                 },
-                 [&] {
-                   hipLaunchKernelGGL(neptune_monitor_final<float>, dim3(1), dim3(256), 0, s, static_cast<const float*>(partials), blocks,
-                                      static_cast<float*>(dot_out));
-                   return launched();
-                 });
+  return line_alone(kMgLineDot, dtype, g, axis, q, b, lo, inv, up, x, dot_out, stream);
 }
 
 int neptune_hip_mg_restrict(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
                             const void* b_fine, const void* q_fine, double rscale, void* b_coarse, void* x_coarse, void* stream) {
-  if (!g_fine || !g_coarse || !b_fine || !q_fine || !b_coarse || !x_coarse || !known_dtype(dtype) || !isfinite(rscale)) return NEPTUNE_HIP_EINVAL;
-  MgBox F, Cb;
-  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
-  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
-  if (!mask) return NEPTUNE_HIP_EINVAL;
-  const size_t fb = box_bytes(F, elem_size(dtype)), cb = box_bytes(Cb, elem_size(dtype));
-  if (buffers_overlap(b_coarse, cb, x_coarse, cb)) return NEPTUNE_HIP_EINVAL;
-  for (const void* w : {(const void*)b_coarse, (const void*)x_coarse})
-    if (buffers_overlap(w, cb, b_fine, fb) || buffers_overlap(w, cb, q_fine, fb)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  return do_restrict(dtype, mask, F, Cb, b_fine, q_fine, rscale, b_coarse, x_coarse, reinterpret_cast<hipStream_t>(stream));
-}
-
-int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
-                               const void* x_coarse, void* x_fine, void* stream) {
-  if (!g_fine || !g_coarse || !x_coarse || !x_fine || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  MgBox F, Cb;
-  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
-  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
-  if (!mask) return NEPTUNE_HIP_EINVAL;
-  if (buffers_overlap(x_fine, box_bytes(F, elem_size(dtype)), x_coarse, box_bytes(Cb, elem_size(dtype)))) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  return do_prolong(dtype, mask, F, Cb, x_coarse, x_fine, reinterpret_cast<hipStream_t>(stream));
-}
-
-int neptune_hip_mg_prolong_add_linear(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
-                                      const neptune_hip_mg_prolong_t* p, const void* x_coarse, void* x_fine, void* stream) {
-  if (!g_fine || !g_coarse || !p || !x_coarse || !x_fine || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  MgBox F, Cb;
-  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
-  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
-  if (!mask) return NEPTUNE_HIP_EINVAL;
-  bool linear = false;
-  MgRim rim;
-  if (!prolong_rules(*p, mask, g_fine->rank, &linear, rim)) return NEPTUNE_HIP_EINVAL;
-  if (buffers_overlap(x_fine, box_bytes(F, elem_size(dtype)), x_coarse, box_bytes(Cb, elem_size(dtype)))) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return linear ? do_prolong_linear(dtype, mask, F, Cb, rim, x_coarse, x_fine, s) : do_prolong(dtype, mask, F, Cb, x_coarse, x_fine, s);
+  return restrict_alone(dtype, g_fine, g_coarse, nullptr, b_fine, q_fine, rscale, b_coarse, x_coarse, stream);
 }
 
 int neptune_hip_mg_restrict_linear(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
                                    const neptune_hip_mg_transfer_t* t, const void* b_fine, const void* q_fine, double rscale, void* b_coarse,
                                    void* x_coarse, void* stream) {
-  if (!g_fine || !g_coarse || !t || !b_fine || !q_fine || !b_coarse || !x_coarse || !known_dtype(dtype) || !isfinite(rscale)) return NEPTUNE_HIP_EINVAL;
-  MgBox F, Cb;
-  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb)) return NEPTUNE_HIP_EINVAL;
-  const int mask = g_fine->rank == g_coarse->rank ? sizes_nest(F, Cb, g_fine->rank) : 0;
-  if (!mask) return NEPTUNE_HIP_EINVAL;
-  bool linear = false, rlinear = false;
-  MgRim rim;
-  if (!transfer_rules(*t, mask, g_fine->rank, &linear, &rlinear, rim)) return NEPTUNE_HIP_EINVAL;
-  const size_t fb = box_bytes(F, elem_size(dtype)), cb = box_bytes(Cb, elem_size(dtype));
-  if (buffers_overlap(b_coarse, cb, x_coarse, cb)) return NEPTUNE_HIP_EINVAL;
-  for (const void* w : {(const void*)b_coarse, (const void*)x_coarse})
-    if (buffers_overlap(w, cb, b_fine, fb) || buffers_overlap(w, cb, q_fine, fb)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return rlinear ? do_restrict_linear(dtype, mask, F, Cb, rim, b_fine, q_fine, rscale, b_coarse, x_coarse, s)
-                 : do_restrict(dtype, mask, F, Cb, b_fine, q_fine, rscale, b_coarse, x_coarse, s);
+  if (!t) return NEPTUNE_HIP_EINVAL;
+  return restrict_alone(dtype, g_fine, g_coarse, t, b_fine, q_fine, rscale, b_coarse, x_coarse, stream);
+}
+
+int neptune_hip_mg_prolong_add(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
+                               const void* x_coarse, void* x_fine, void* stream) {
+  return prolong_alone(dtype, g_fine, g_coarse, nullptr, x_coarse, x_fine, stream);
+}
+
+int neptune_hip_mg_prolong_add_linear(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse,
+                                      const neptune_hip_mg_prolong_t* p, const void* x_coarse, void* x_fine, void* stream) {
+  if (!p) return NEPTUNE_HIP_EINVAL;
+  const neptune_hip_mg_transfer_t t = transfer_of(*p);
+  return prolong_alone(dtype, g_fine, g_coarse, &t, x_coarse, x_fine, stream);
 }
 
 int neptune_hip_mg_coarsened_axes(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse, int* mask_out) {
-  if (!g_fine || !g_coarse || !mask_out) return NEPTUNE_HIP_EINVAL;
-  MgBox F, Cb;
-  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb) || g_fine->rank != g_coarse->rank) return NEPTUNE_HIP_EINVAL;
-  const int mask = sizes_nest(F, Cb, g_fine->rank);
-  if (!mask) return NEPTUNE_HIP_EINVAL;
-  *mask_out = (mask & 7) >> (3 - g_fine->rank);   // the kernels' axes are the dimensions right-aligned
+  Pair P;
+  if (!mask_out || !P.nest(g_fine, g_coarse)) return NEPTUNE_HIP_EINVAL;
+  *mask_out = (P.mask & 7) >> (3 - P.rank);   // the kernels' axes are the dimensions right-aligned
   return NEPTUNE_HIP_OK;
 }
 
 int neptune_hip_mg_halved_axes(const neptune_hip_apply_geom_t* g_fine, const neptune_hip_apply_geom_t* g_coarse, int* mask_out) {
-  if (!g_fine || !g_coarse || !mask_out) return NEPTUNE_HIP_EINVAL;
-  MgBox F, Cb;
-  if (!level_box(g_fine, F) || !level_box(g_coarse, Cb) || g_fine->rank != g_coarse->rank) return NEPTUNE_HIP_EINVAL;
-  const int mask = sizes_nest(F, Cb, g_fine->rank);
-  if (!mask) return NEPTUNE_HIP_EINVAL;
-  *mask_out = (mask & kMgCell) ? (mask & 7) >> (3 - g_fine->rank) : 0;
+  Pair P;
+  if (!mask_out || !P.nest(g_fine, g_coarse)) return NEPTUNE_HIP_EINVAL;
+  *mask_out = (P.mask & kMgCell) ? (P.mask & 7) >> (3 - P.rank) : 0;
   return NEPTUNE_HIP_OK;
 }
 
@@ -1137,14 +1104,7 @@ int neptune_hip_mg_solve_prolong(const neptune_hip_mg_level_t* levels, const nep
   // the same choice per pair with the averaging restriction; an n_levels out of range is refused below whatever the array
   neptune_hip_mg_transfer_t tr[kMaxLevels];
   const bool have = prolong && n_levels >= 1 && n_levels <= kMaxLevels;
-  for (int l = 0; have && l + 1 < n_levels; ++l) {
-    tr[l].prolong = prolong[l].kind;
-    tr[l].restrict_kind = NEPTUNE_HIP_MG_RESTRICT_AVERAGE;
-    for (int d = 0; d < 3; ++d) {
-      tr[l].rim_lo[d] = prolong[l].rim_lo[d];
-      tr[l].rim_hi[d] = prolong[l].rim_hi[d];
-    }
-  }
+  for (int l = 0; have && l + 1 < n_levels; ++l) tr[l] = transfer_of(prolong[l]);
   return neptune_hip_mg_solve_transfer(levels, lines, have ? tr : nullptr, n_levels, dtype, pre, post, coarse_sweeps, max_cycles, check_every,
                                        tol2, rr_checks, stream, cfg, cycles_done, rr0, rr_last);
 }
@@ -1161,7 +1121,6 @@ int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t* levels, const ne
   if (check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
   Solve S;
   if (!S.check(levels, n_levels, dtype, pre, post, coarse_sweeps, cfg, lines, transfer)) return NEPTUNE_HIP_EINVAL;
-  const size_t elem = elem_size(dtype);
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
@@ -1173,110 +1132,29 @@ int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t* levels, const ne
     Scalar() { NEPTUNE_HIP_CHECK(hipMalloc(&p, 8)); }
     ~Scalar() { (void)hipFree(p); }
   } rr_dev;
-  struct Graph {    // this call's graph of one cycle
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    ~Graph() {
-      if (exec) (void)hipGraphExecDestroy(exec);
-      if (graph) (void)hipGraphDestroy(graph);
-    }
-  } G;
 
-  for (int l = 1; l < n_levels; ++l) NEPTUNE_HIP_CHECK(hipMemsetAsync(levels[l].x, 0, box_bytes(S.box[l], elem), S.stream));
+  S.zero_coarse();
   double rr = 0.0;
-  int rc = S.residual(rr_dev.p, &rr);
+  const int rc = S.residual(rr_dev.p, &rr);
   if (rc != NEPTUNE_HIP_OK) return rc;
   if (rr0) *rr0 = rr;
   if (rr_last) *rr_last = rr;
   if (rr <= tol2) return NEPTUNE_HIP_OK;
 
-  const bool graphs = graph_path_enabled();
-  bool capture_tried = false;
-  int64_t done = 0;
-  while (done < max_cycles) {
-    const int64_t block = check_every < max_cycles - done ? check_every : max_cycles - done;
-    for (int64_t c = 0; c < block; ++c, ++done) {
-      // the first cycle plain: it validates the request and lets first-use tuning run outside capture; then, when at least
-      // two more cycles may follow, ONE capture
-      if (done > 0 && graphs && !capture_tried && max_cycles - done >= 2) {
-        capture_tried = true;
-        G.exec = S.capture(&G.graph);
-      }
-      if (done > 0 && G.exec) {
-        NEPTUNE_HIP_CHECK(hipGraphLaunch(G.exec, S.stream));
-        ++g_mg_counts[1];
-      } else {
-        rc = S.cycle(0);
-        if (rc != NEPTUNE_HIP_OK) return late(rc);
-        ++g_mg_counts[0];
-      }
-      if (cycles_done) *cycles_done = done + 1;
-    }
-    rc = S.residual(rr_dev.p, &rr);
-    if (rc != NEPTUNE_HIP_OK) return late(rc);
-    if (rr_checks) rr_checks[g_mg_counts[2]] = rr;
-    ++g_mg_counts[2];
-    if (rr_last) *rr_last = rr;
-    if (rr <= tol2) break;   // false for a NaN: such a solve runs to max_cycles
-  }
-  return NEPTUNE_HIP_OK;
-}
-
-int neptune_hip_mg_smooth_dot(int dtype, const neptune_hip_apply_geom_t* g, const void* q, const void* b, const void* minv, void* x,
-                              void* dot_out, void* stream) {
-  if (!g || !q || !b || !minv || !x || !dot_out || !known_dtype(dtype)) return NEPTUNE_HIP_EINVAL;
-  MgBox B;
-  if (!level_box(g, B)) return NEPTUNE_HIP_EINVAL;
-  const size_t elem = elem_size(dtype), bytes = box_bytes(B, elem);
-  if (buffers_overlap(x, bytes, q, bytes) || buffers_overlap(x, bytes, b, bytes) || buffers_overlap(x, bytes, minv, bytes)) return NEPTUNE_HIP_EINVAL;
-  if ((uintptr_t)dot_out % elem != 0) return NEPTUNE_HIP_EINVAL;
-  for (const void* f : {q, b, minv, (const void*)x})
-    if (buffers_overlap(dot_out, elem, f, bytes)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  const RowGrid r = row_grid(B);
-  const int64_t blocks = grid_blocks(r.grid);
-  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)blocks * elem, stream)) return NEPTUNE_HIP_EUNSUPPORTED;
-  void* const partials = static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes;
-  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return by_type(dtype,
-                 [&] {
-                   hipLaunchKernelGGL(neptune_mg_smooth_dot<double>, r.grid, dim3(256), 0, s, B, r.nchunk, static_cast<const double*>(q),
-                                      static_cast<const double*>(b), static_cast<const double*>(minv), static_cast<double*>(x),
-                                      static_cast<double*>(partials));
-                   hipLaunchKernelGGL(neptune_monitor_final<double>, dim3(1), dim3(256), 0, s, static_cast<const double*>(partials), blocks,
-                                      static_cast<double*>(dot_out));
-                   return launched();
-                 },
-                 [&] {
-                   hipLaunchKernelGGL(neptune_mg_smooth_dot<float>, r.grid, dim3(256), 0, s, B, r.nchunk, static_cast<const float*>(q),
-                                      static_cast<const float*>(b), static_cast<const float*>(minv), static_cast<float*>(x),
-                                      static_cast<float*>(partials));
-                   hipLaunchKernelGGL(neptune_monitor_final<float>, dim3(1), dim3(256), 0, s, static_cast<const float*>(partials), blocks,
-                                      static_cast<float*>(dot_out));
-                   return launched();
-                 });
-}
-
-int neptune_hip_mg_smooth_dot_wide(int dtype, int dtype_sum, const neptune_hip_apply_geom_t* g, const void* q, const void* b,
-                                   const void* minv, void* x, void* dot_out, void* stream) {
-  if (!g || !q || !b || !minv || !x || !dot_out || dtype != NEPTUNE_HIP_F32 || dtype_sum != NEPTUNE_HIP_F64) return NEPTUNE_HIP_EINVAL;
-  MgBox B;
-  if (!level_box(g, B)) return NEPTUNE_HIP_EINVAL;
-  const size_t bytes = box_bytes(B, sizeof(float));
-  if (buffers_overlap(x, bytes, q, bytes) || buffers_overlap(x, bytes, b, bytes) || buffers_overlap(x, bytes, minv, bytes)) return NEPTUNE_HIP_EINVAL;
-  if ((uintptr_t)dot_out % sizeof(double) != 0) return NEPTUNE_HIP_EINVAL;
-  for (const void* f : {q, b, minv, (const void*)x})
-    if (buffers_overlap(dot_out, sizeof(double), f, bytes)) return NEPTUNE_HIP_EINVAL;
-  ensure_init();
-  const RowGrid r = row_grid(B);
-  const int64_t blocks = grid_blocks(r.grid);
-  if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)blocks * sizeof(double), stream)) return NEPTUNE_HIP_EUNSUPPORTED;
-  double* const partials = reinterpret_cast<double*>(static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes);
-  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL((neptune_mg_smooth_dot_wide<double, float>), r.grid, dim3(256), 0, s, B, r.nchunk, static_cast<const float*>(q),
-                     static_cast<const float*>(b), static_cast<const float*>(minv), static_cast<float*>(x), partials);
-  hipLaunchKernelGGL(neptune_monitor_final<double>, dim3(1), dim3(256), 0, s, (const double*)partials, blocks, static_cast<double*>(dot_out));
-  return launched();
+  struct Hooks {
+    void capturing() {}
+    void captured(bool) {}
+    void counted(bool replayed) { ++g_mg_counts[replayed ? 1 : 0]; }
+  };
+  return run_blocks(S.stream, max_cycles, check_every, tol2, cycles_done, rr_last, [&] { return S.cycle(0); },
+                    [&](double* out) -> int {
+                      const int rc = S.residual(rr_dev.p, out);
+                      if (rc != NEPTUNE_HIP_OK) return rc;
+                      if (rr_checks) rr_checks[g_mg_counts[2]] = *out;
+                      ++g_mg_counts[2];
+                      return NEPTUNE_HIP_OK;
+                    },
+                    Hooks());
 }
 
 int neptune_hip_mgcg_solve_mixed(const neptune_hip_mg_level_t* outer, int dtype_outer, neptune_hip_apply_dot_fn fn_dot,
@@ -1294,11 +1172,7 @@ int neptune_hip_mgcg_solve_mixed_transfer(const neptune_hip_mg_level_t* outer, i
                                           int coarse_sweeps, void* const work[2], int64_t max_iters, int64_t check_every, double tol2,
                                           void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
                                           double* rr_last) {
-  g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
-  g_mgcg_rz0 = 0.0;
-  if (iters_done) *iters_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
+  mgcg_reset(iters_done, rr0, rr_last);
   // ---- the refusals, before anything touches the device
   if (dtype_outer != NEPTUNE_HIP_F64 || dtype_inner != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
   if (!outer || n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
@@ -1314,43 +1188,26 @@ int neptune_hip_mgcg_solve_mixed_transfer(const neptune_hip_mg_level_t* outer, i
   if (O.g.num_inputs > 1 && !O.in_rest) return NEPTUNE_HIP_EINVAL;
   for (int i = 1; i < O.g.num_inputs; ++i)
     if (!O.in_rest[i - 1]) return NEPTUNE_HIP_EINVAL;
-  // the fields of both precisions that the solve touches on levels 0 and 1, the trace included: none may meet another (each
-  // inner level's own four were checked against each other and the neighbour's above)
-  struct Span { const void* p; size_t bytes; size_t align; };
+  // the wide fields and the trace may meet neither each other nor an inner field of levels 0 and 1 (each inner level's own
+  // four were checked against each other and the neighbour's above); minv of a level with line stages may be null
   const size_t wide0 = box_bytes(OB, sizeof(double)), narrow0 = box_bytes(S.box[0], sizeof(float)), narrow1 = box_bytes(S.box[1], sizeof(float));
-  const Span spans[14] = {{O.x, wide0, 8},           {O.b, wide0, 8},           {O.q, wide0, 8},           {work[0], wide0, 8},
-                          {work[1], wide0, 8},       {trace, (size_t)(3 * max_iters) * sizeof(double), 8},
-                          {levels[0].x, narrow0, 4}, {levels[0].b, narrow0, 4}, {levels[0].q, narrow0, 4}, {levels[0].minv, narrow0, 4},
-                          {levels[1].x, narrow1, 4}, {levels[1].b, narrow1, 4}, {levels[1].q, narrow1, 4}, {levels[1].minv, narrow1, 4}};
-  for (int i = 0; i < 14; ++i) {
-    const bool optional = i == 5 || i == 9 || i == 13;   // the trace; minv of a level with line stages
-    if (!spans[i].p) {
-      if (optional) continue;
-      return NEPTUNE_HIP_EINVAL;
-    }
-    if ((uintptr_t)spans[i].p % spans[i].align != 0) return NEPTUNE_HIP_EINVAL;
-    for (int o = 0; o < (i < 6 ? i : 6); ++o)   // an inner field against the wide ones and the trace only
-      if (spans[o].p && buffers_overlap(spans[i].p, spans[i].bytes, spans[o].p, spans[o].bytes)) return NEPTUNE_HIP_EINVAL;
-  }
+  const Span wide[6] = {{O.x, wide0, 8},     {O.b, wide0, 8},     {O.q, wide0, 8},
+                        {work[0], wide0, 8}, {work[1], wide0, 8}, {trace, (size_t)(3 * max_iters) * sizeof(double), 8, true}};
+  if (!apart(wide, {{levels[0].x, narrow0, 4}, {levels[0].b, narrow0, 4}, {levels[0].q, narrow0, 4}, {levels[0].minv, narrow0, 4, true},
+                    {levels[1].x, narrow1, 4}, {levels[1].b, narrow1, 4}, {levels[1].q, narrow1, 4}, {levels[1].minv, narrow1, 4, true}}))
+    return NEPTUNE_HIP_EINVAL;
   // line stages on level 0 need a wide-sum form of both code paths of the line kernel: not built yet
   if (S.stages(0) > 0) return NEPTUNE_HIP_EUNSUPPORTED;
-  // the factor fields are read while x, q, r, p and the trace are written: they may meet none of them
-  for (int l = 0; l < n_levels && lines; ++l)
-    for (int st = 0; st < lines[l].n_stages; ++st)
-      for (const void* f : {lines[l].lo[st], lines[l].inv[st], lines[l].up[st]}) {
-        const size_t fb = box_bytes(S.box[l], sizeof(float));
-        for (int o = 0; o < 6; ++o)
-          if (spans[o].p && buffers_overlap(f, fb, spans[o].p, spans[o].bytes)) return NEPTUNE_HIP_EINVAL;
-      }
+  // the factor fields are read while x, q, r, p and the trace are written
+  if (!S.factors_apart(wide)) return NEPTUNE_HIP_EINVAL;
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
   ensure_init();
   SolveStream sc(reinterpret_cast<hipStream_t>(stream));
   S.stream = sc.stream;
-  const neptune_hip_launch_cfg_t* const outer_cfg = (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
   const MgcgArgs a = {fn_dot, sweeps, work, max_iters, check_every, tol2, trace, iters_done, rr0, rr_last};
-  return mgcg_solve_mixed_typed<double, float>(S, O, outer_cfg, a);
+  return mgcg_drive<MgcgMixed>(S, O, set_cfg(cfg), a);
 }
 
 double neptune_hip_mgcg_rz0(void) { return g_mgcg_rz0; }
@@ -1382,41 +1239,19 @@ int neptune_hip_mgcg_solve_transfer(const neptune_hip_mg_level_t* levels, const 
                                     int sweeps, int coarse_sweeps, void* const work[3], int64_t max_iters, int64_t check_every, double tol2,
                                     void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
                                     double* rr_last) {
-  g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
-  g_mgcg_rz0 = 0.0;
-  if (iters_done) *iters_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
+  mgcg_reset(iters_done, rr0, rr_last);
   // ---- the refusals, before anything touches the device
   if (n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
   Solve S;
   if (!S.check(levels, n_levels, dtype, sweeps, sweeps, coarse_sweeps, cfg, lines, transfer, true)) return NEPTUNE_HIP_EINVAL;
-  const size_t elem = elem_size(dtype);
-  const size_t bytes0 = box_bytes(S.box[0], elem), bytes1 = box_bytes(S.box[1], elem), trace_bytes = (size_t)(3 * max_iters) * elem;
-  const void* const fine[4] = {levels[0].x, levels[0].b, levels[0].q, levels[0].minv};
-  const void* const coarse[4] = {levels[1].x, levels[1].b, levels[1].q, levels[1].minv};
-  if (trace && (uintptr_t)trace % elem != 0) return NEPTUNE_HIP_EINVAL;
-  for (int i = 0; i < 3; ++i) {
-    if (!work[i] || (uintptr_t)work[i] % elem != 0) return NEPTUNE_HIP_EINVAL;
-    for (int o = 0; o < i; ++o)
-      if (buffers_overlap(work[i], bytes0, work[o], bytes0)) return NEPTUNE_HIP_EINVAL;
-    for (int o = 0; o < 4; ++o)   // minv of a level with stages may be null
-      if ((fine[o] && buffers_overlap(work[i], bytes0, fine[o], bytes0)) || (coarse[o] && buffers_overlap(work[i], bytes0, coarse[o], bytes1)))
-        return NEPTUNE_HIP_EINVAL;
-    if (trace && buffers_overlap(trace, trace_bytes, work[i], bytes0)) return NEPTUNE_HIP_EINVAL;
-  }
-  for (int o = 0; o < 4 && trace; ++o)
-    if ((fine[o] && buffers_overlap(trace, trace_bytes, fine[o], bytes0)) || (coarse[o] && buffers_overlap(trace, trace_bytes, coarse[o], bytes1)))
-      return NEPTUNE_HIP_EINVAL;
-  // the factor fields are read while r, p, z and the trace are written: they may meet none of them
-  for (int l = 0; l < n_levels && lines; ++l)
-    for (int st = 0; st < lines[l].n_stages; ++st)
-      for (const void* f : {lines[l].lo[st], lines[l].inv[st], lines[l].up[st]}) {
-        const size_t fb = box_bytes(S.box[l], elem);
-        for (int i = 0; i < 3; ++i)
-          if (buffers_overlap(f, fb, work[i], bytes0)) return NEPTUNE_HIP_EINVAL;
-        if (trace && buffers_overlap(f, fb, trace, trace_bytes)) return NEPTUNE_HIP_EINVAL;
-      }
+  // r, p, z and the trace may meet neither each other nor a field of levels 0 and 1; minv of a level with stages may be null
+  const size_t elem = elem_size(dtype), bytes0 = box_bytes(S.box[0], elem), bytes1 = box_bytes(S.box[1], elem);
+  const Span own[4] = {{work[0], bytes0, elem}, {work[1], bytes0, elem}, {work[2], bytes0, elem}, {trace, (size_t)(3 * max_iters) * elem, elem, true}};
+  if (!apart(own, {{levels[0].x, bytes0}, {levels[0].b, bytes0}, {levels[0].q, bytes0}, {levels[0].minv, bytes0, 1, true},
+                   {levels[1].x, bytes1}, {levels[1].b, bytes1}, {levels[1].q, bytes1}, {levels[1].minv, bytes1, 1, true}}))
+    return NEPTUNE_HIP_EINVAL;
+  // the factor fields are read while r, p, z and the trace are written
+  if (!S.factors_apart(own)) return NEPTUNE_HIP_EINVAL;
   // rr is read back after every block: not while the caller's stream is being captured
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
@@ -1430,7 +1265,7 @@ int neptune_hip_mgcg_solve_transfer(const neptune_hip_mg_level_t* levels, const 
   lv[0].b = work[0];
   S.levels = lv;
   const MgcgArgs a = {fn_dot, sweeps, work, max_iters, check_every, tol2, trace, iters_done, rr0, rr_last};
-  return dtype == NEPTUNE_HIP_F64 ? mgcg_solve_typed<double>(S, levels[0], a) : mgcg_solve_typed<float>(S, levels[0], a);
+  return by_type(dtype, [&](auto t) { return mgcg_drive<MgcgOneType<decltype(t)>>(S, levels[0], S.cfg, a); });
 }
 
 }  // extern "C"
