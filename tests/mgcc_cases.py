@@ -1,14 +1,9 @@
-"""The NumPy restatement of multigrid on cell-centred grids, on mg_cases / mgsemi_cases / mgcg_cases.
+"""The problems of multigrid on cell-centred grids.
 
 Between two neighbouring levels a dimension may be HALVED, m_fine = 2 m_coarse: the coarse cell j covers the fine cells 2 j
-and 2 j + 1.  restrict_cell and prolong_add_cell restate the two transfers of include/neptune_hip.h: arithmetic in the
-element type with one `.astype(dt)` per operation, the last dimension first, kept dimensions skipped; there is no rim operand.
-
-A level carries `.axes` as everywhere else; for a cell-centred pair it is a Halved(...) tuple, and this module's restrict /
-prolong_add dispatch on that -- a plain tuple goes to mgsemi_cases' vertex-centred transfers, so a hierarchy may change its
-grid kind from one pair to the next.  The cycle, the solve, the MGCG preconditioner and the replay are mgsemi_cases' own
-functions (numpy_mgcg is mgcg_cases'), re-bound to this module's namespace so that they call the transfers above and each other: nothing of them is
-written twice.  rr terms, expected_stop and tol_between are mg_cases'.
+and 2 j + 1.  A level carries `.axes` as everywhere else; for a cell-centred pair it is a Halved(...) -- a plain tuple is a
+vertex-centred pair, so a hierarchy may change its grid kind from one pair to the next.  The transfers, the cycle, the solve
+and MGCG are mg_restatement's.
 
 Operators: flux_module, the flux form with one face-coefficient field per dimension and an optional diagonal field,
     A(u)_p = sum_d [ c_d[p] (u_p - u_(p - e_d)) + c_d[p + e_d] (u_p - u_(p + e_d)) ]  (+ s[p] u_p),
@@ -16,92 +11,11 @@ c_d[p] the coefficient of the face between cells p - e_d and p.  Neumann faces: 
 faces (the value 0 on the face itself, the ghost cell mirrored): c = 0 there as well and s = 2 per boundary face of the cell.
 The operator is unscaled (h^2 A) with rscale = 4: a level's interior coefficients along dimension d are a weight w_d that
 follows the plan rule of mgsemi_cases (w on a halved dimension, 4 w on a kept one), 1 everywhere under full halving."""
-import types
-
 import numpy as np
 
-import cg_cases as cc
-import mg_cases as mgc
-import mgcg_cases as mg
-import mgsemi_cases as sc
+import mg_restatement as rst
 import monitor_cases as mc
-
-expected_stop = mgc.expected_stop
-tol_between = mgc.tol_between
-
-
-class Halved(tuple):
-    """the dimensions halved between a level and the next one: a cell-centred pair"""
-
-
-# ---------------------------------------------------------------- the two transfers
-def _mean(d, axis):
-    """t = 0.5 * (a[2 j] + a[2 j + 1]) along `axis`: one rounded addition and the exact scaling"""
-    dt = d.dtype.type
-    n = d.shape[axis]
-    assert n % 2 == 0
-    take = lambda start: np.take(d, np.arange(start, n, 2), axis=axis)
-    with np.errstate(invalid="ignore", over="ignore"):
-        s = (take(0) + take(1)).astype(dt)
-        return (dt(0.5) * s).astype(dt)
-
-
-def restrict_cell(b_f, q_f, where_f, rscale, b_c, x_c, where_c, axes):
-    """-> new (b_c, x_c): b_c = rscale * R(b_f - q_f) and x_c = +0 on the coarse Omega, R the mean along `axes`; every other
-    cell keeps its bits; nothing outside where_f is read"""
-    dt = b_f.dtype.type
-    with np.errstate(invalid="ignore", over="ignore"):
-        t = (b_f[where_f] - q_f[where_f]).astype(dt)
-        for axis in reversed(range(t.ndim)):
-            if axis in axes:
-                t = _mean(t, axis)
-        bc, xc = b_c.copy(), x_c.copy()
-        bc[where_c] = (dt(rscale) * t).astype(dt)
-    xc[where_c] = dt(0)
-    return bc, xc
-
-
-def prolong_add_cell(x_c, where_c, x_f, where_f, axes):
-    """-> a new x_f: x_f + P(x_c) on the fine Omega, fine cell i taking e[i / 2] itself along `axes` (no operation); every
-    other cell keeps its bits; nothing outside where_c is read"""
-    dt = x_f.dtype.type
-    e = x_c[where_c]
-    for axis in reversed(range(e.ndim)):
-        if axis in axes:
-            e = np.repeat(e, 2, axis=axis)
-    out = x_f.copy()
-    with np.errstate(invalid="ignore", over="ignore"):
-        out[where_f] = (x_f[where_f] + e).astype(dt)
-    return out
-
-
-def restrict(b_f, q_f, where_f, rscale, b_c, x_c, where_c, axes):
-    fn = restrict_cell if isinstance(axes, Halved) else sc.restrict
-    return fn(b_f, q_f, where_f, rscale, b_c, x_c, where_c, axes)
-
-
-def prolong_add(x_c, where_c, x_f, where_f, axes):
-    fn = prolong_add_cell if isinstance(axes, Halved) else sc.prolong_add
-    return fn(x_c, where_c, x_f, where_f, axes)
-
-
-# ---------------------------------------------------------------- the cycle, the solve, the MGCG preconditioner and replay
-def _rebound(fn):
-    """mgsemi_cases' function on this module's globals: its calls of restrict, prolong_add, cycle, ... resolve here"""
-    out = types.FunctionType(fn.__code__, globals(), fn.__name__, fn.__defaults__)
-    out.__doc__ = fn.__doc__
-    return out
-
-
-cycle = _rebound(sc.cycle)
-run = _rebound(sc.run)
-rr_sequence = _rebound(sc.rr_sequence)
-rest_of_cycle = _rebound(sc.rest_of_cycle)
-precondition = _rebound(sc.precondition)
-setup = _rebound(sc.setup)
-replay = _rebound(sc.replay)
-_sum = mg._sum
-numpy_mgcg = _rebound(mg.numpy_mgcg)        # mgcg_cases' recurrences with numpy's own sums, on this module's preconditioner
+from mg_restatement import Halved
 
 
 # ---------------------------------------------------------------- the flux-form operator
@@ -209,7 +123,7 @@ def halved_steps(omega, axes_per_pair, weights=None):
     for axes in axes_per_pair:
         out.append((m, w, axes))
         w = tuple(v if d in axes else 4.0 * v for d, v in enumerate(w))
-        if isinstance(axes, Halved):
+        if rst.pair_of(axes, len(m)).halved:
             assert all(m[d] % 2 == 0 and m[d] >= 2 for d in axes), (m, axes)
             m = tuple(v // 2 if d in axes else v for d, v in enumerate(m))
         else:
@@ -252,7 +166,7 @@ def flux_levels(steps, damp, dtype=np.float64, faces="neumann", outside0=0.0):
         minv = np.full(shape, outside0 if l == 0 else np.nan, dtype)
         with np.errstate(divide="ignore"):
             minv[where] = (dt(damp) / diag[where]).astype(dt)
-        L = mgc.Level(mgc.Operator(text, *rest), shape, where, minv, dtype)
+        L = rst.Level(rst.Operator(text, *rest), shape, where, minv, dtype)
         L.axes, L.weights = axes, w
         levels.append(L)
         texts.append(text)

@@ -1,20 +1,11 @@
-"""The NumPy restatement of multigrid-preconditioned conjugate gradients (neptune_hip_mgcg_solve), on the
-kernels' restatement of mg_cases (smooth, restrict, prolong_add, Level, Operator) and the trace-replay pattern of pcg_cases.
-
-Everything follows the normative definition in include/neptune_hip.h: arithmetic in the element type with one `.astype(dt)`
-per operation, the operator itself from the oracle.  The preconditioner z = M(r) is one V(sweeps, sweeps) cycle on A z = r
-from z = 0 whose first pre-sweep on level 0 is z = minv_0 * r on EVERY cell of the box (minv_0 is +0 outside Omega) and whose
-last post-sweep also yields r . z over Omega.  The sums (pq, rz, rr) are compared as exact sums of the restatement's own
-terms with the bound 2 (n - 1) eps sum |t_i| two summation orders may differ by; the fields, driven by the device's traced
-scalars, bit for bit."""
+"""The problems of multigrid-preconditioned conjugate gradients (neptune_hip_mgcg_solve): the anisotropic star
+and hierarchies whose level 0 has minv = +0 outside Omega -- the preconditioner's first pre-sweep is z = minv_0 * r on EVERY
+cell of the box.  The preconditioner, the set-up and the replay are mg_restatement's."""
 import numpy as np
 
-import cg_cases as cc
 import mg_cases as mgc
+import mg_restatement as rst
 import monitor_cases as mc
-
-expected_stop = cc.expected_stop        # what the loop's definition gives on an r . r sequence: (iters_done, checks)
-tol_between = mgc.tol_between           # a threshold between two check values a factor >= 4 apart
 
 
 # ---------------------------------------------------------------- the anisotropic star
@@ -74,138 +65,8 @@ def aniso_levels(omega, n_levels, weights, damp, dtype=np.float64, minv_outside=
     for text, (shape, where) in zip(texts, shapes):
         minv = np.full(shape, minv_outside, dtype)
         minv[where] = dt(dt(damp) / dt(2.0 * sum(float(w) for w in weights)))
-        levels.append(mgc.Level(mgc.Operator(text), shape, where, minv, dtype))
+        levels.append(rst.Level(rst.Operator(text), shape, where, minv, dtype))
     return levels, texts
-
-
-# ---------------------------------------------------------------- the preconditioner
-def start(levels, work_fill=np.nan):
-    """the state the set-up leaves before the first cycle: the coarser x zero-filled (whole box), the coarser b and every q
-    holding `work_fill` (what the device's work fields hold before the call)"""
-    for l, L in enumerate(levels):
-        if l > 0:
-            L.x = np.zeros(L.shape, L.dt)
-            L.b = np.full(L.shape, work_fill, L.dt)
-        L.q = np.full(L.shape, work_fill, L.dt)
-
-
-def first_sweep(levels, r):
-    """the cycle's first pre-sweep on level 0, from z = 0 with A(0) = 0: z = minv_0 * r on every cell, one rounding"""
-    L0 = levels[0]
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (L0.minv * r).astype(L0.dt)
-
-
-def rest_of_cycle(levels, r, z, sweeps, coarse_sweeps):
-    """everything of M after its first pre-sweep: level 0 carries (z, r) for (x, b); -> z = M(r), the levels' fields left as
-    the device leaves them"""
-    L0, L1 = levels[0], levels[1]
-    L0.x, L0.b = z, r
-    for _ in range(sweeps - 1):
-        mgc.sweep(L0)
-    L0.q = L0.A(L0.x)
-    L1.b, L1.x = mgc.restrict(L0.b, L0.q, L0.where, L0.rscale, L1.b, L1.x, L1.where)
-    mgc.cycle(levels, 1, sweeps, sweeps, coarse_sweeps)
-    L0.x = mgc.prolong_add(L1.x, L1.where, L0.x, L0.where)
-    for _ in range(sweeps):
-        mgc.sweep(L0)
-    return L0.x
-
-
-def precondition(levels, r, sweeps=2, coarse_sweeps=8):
-    """z = M(r): one V(sweeps, sweeps) cycle of the definition on A_0 z = r from z = 0 (call start(levels) once before)"""
-    assert len(levels) >= 2 and sweeps >= 1
-    return rest_of_cycle(levels, r, first_sweep(levels, r), sweeps, coarse_sweeps)
-
-
-# ---------------------------------------------------------------- the solve
-def setup(levels, x0, b0, sweeps=2, coarse_sweeps=8):
-    """the definition's set-up: -> (x, r, p, z, rr0 as (terms' sum, bound), rz0 likewise)"""
-    L0 = levels[0]
-    start(levels)
-    x = x0.copy()
-    q = L0.A(x)
-    r = np.zeros_like(x)
-    with np.errstate(invalid="ignore", over="ignore"):
-        r[L0.where] = (b0[L0.where] - q[L0.where]).astype(L0.dt)
-    rr0 = cc.dot_terms(r, r, L0.where)
-    z = precondition(levels, r, sweeps, coarse_sweeps)
-    rz0 = cc.dot_terms(r, z, L0.where)
-    return x, r, z.copy(), z, rr0, rz0
-
-
-def _sum(terms: np.ndarray):
-    return terms.dtype.type(np.sum(terms, dtype=terms.dtype))
-
-
-def numpy_mgcg(levels, x0, b0, iters, sweeps=2, coarse_sweeps=8, stop_at=None):
-    """the recurrences of the definition with numpy's own sums: -> the r . r sequence [rr_0, rr_1, ...] (floats), for the stop
-    tests and the convergence checks; stop_at: end early once r . r <= stop_at"""
-    L0 = levels[0]
-    dt, where = L0.dt, L0.where
-    x, r, p, z, _, _ = setup(levels, x0, b0, sweeps, coarse_sweeps)
-    rz = _sum((r[where] * z[where]).astype(dt))
-    seq = [float(_sum((r * r).astype(dt)))]
-    for _ in range(iters):
-        if stop_at is not None and seq[-1] <= stop_at:
-            break
-        q = L0.A(p)
-        pq = _sum((q[where] * p[where]).astype(dt))
-        broken = rz == 0 or pq == 0
-        alpha = dt(0) if broken else dt(rz / pq)
-        x = (x + (alpha * p).astype(dt)).astype(dt)
-        r = (r - (alpha * q).astype(dt)).astype(dt)
-        z = precondition(levels, r, sweeps, coarse_sweeps)
-        rz_new = _sum((r[where] * z[where]).astype(dt))
-        beta = dt(0) if broken else dt(rz_new / rz)
-        p = (z + (beta * p).astype(dt)).astype(dt)
-        rz = rz_new
-        seq.append(float(_sum((r * r).astype(dt))))
-    return seq
-
-
-def replay(levels, x0, b0, rz0, trace, sweeps=2, coarse_sweeps=8):
-    """The definition's recurrences driven by the DEVICE's scalars: iteration k takes alpha_k = rz_k / pq_k and
-    beta_k = rz_(k+1) / rz_k from rz_0 and the trace rows (pq_k, rz_(k+1), rr_(k+1)), each one division in the element type,
-    and q from the oracle's operator.  -> (x, r, p, z, checks, rr0, rz0): checks[k] = the (terms' sum, bound) pairs of pq, rz'
-    and rr' of the replay's own fields, rr0 / rz0 those of the set-up; the levels' x_l, b_l are left in `levels` (level 0's
-    are z and r)."""
-    L0 = levels[0]
-    dt, where = L0.dt, L0.where
-    x, r, p, z, rr0, rz0_ref = setup(levels, x0, b0, sweeps, coarse_sweeps)
-    rz = dt(rz0)
-    checks = []
-    everywhere = tuple(slice(None) for _ in x.shape)
-    for k in range(len(trace)):
-        pq, rz_new = dt(trace[k][0]), dt(trace[k][1])
-        q = L0.A(p)
-        pq_ref = cc.dot_terms(q, p, where)
-        broken = rz == 0 or pq == 0
-        alpha = dt(0) if broken else dt(rz / pq)
-        x = (x + (alpha * p).astype(dt)).astype(dt)
-        r = (r - (alpha * q).astype(dt)).astype(dt)
-        rr_ref = cc.dot_terms(r, r, everywhere)
-        z = precondition(levels, r, sweeps, coarse_sweeps)
-        checks.append((pq_ref, cc.dot_terms(r, z, where), rr_ref))
-        beta = dt(0) if broken else dt(rz_new / rz)
-        p = (z + (beta * p).astype(dt)).astype(dt)
-        rz = rz_new
-    return x, r, p, z, checks, rr0, rz0_ref
-
-
-def dense_preconditioner(levels, sweeps=2, coarse_sweeps=8):
-    """M as a dense matrix over the cells of Omega_0 (C order), built column by column from unit vectors"""
-    L0 = levels[0]
-    n = int(np.prod(L0.m))
-    M = np.empty((n, n), np.float64)
-    start(levels, work_fill=0.0)
-    for j in range(n):
-        e = np.zeros(L0.m, L0.dt)
-        e.flat[j] = 1
-        r = np.zeros(L0.shape, L0.dt)
-        r[L0.where] = e
-        M[:, j] = precondition(levels, r, sweeps, coarse_sweeps)[L0.where].ravel()
-    return M
 
 
 def star_levels(omega, n_levels, dtype, damp, texts=None):

@@ -1,119 +1,12 @@
-"""The NumPy restatement of the linear prolongation on cell-centred pairs, on mgcc_cases.
-
-Along a halved dimension the fine cell i has j = i / 2 and the neighbour n = j - 1 (even i) or j + 1 (odd i):
-    p = 0.75 * e[j],  s = 0.25 * v,  t = p + s,    v = e[n], or outside [0, m_c) the ghost +e[j] (EVEN) / -e[j] (ODD)
-in the element type with one `.astype(dt)` per operation, the last dimension first, kept dimensions skipped.  e is the
-intermediate after the dimensions already done: the ghosts come from padding THAT array with +- its edge, which is what
-include/neptune_hip.h defines.
-
-A level carries `.axes` as everywhere else; a pair that prolongs linearly carries a Linear(axes, rim) -- an
-mgcc_cases.Halved, so the restriction stays mgcc_cases' averaging one -- whose .rim[d] = (low rule, high rule) per field
-dimension.  prolong_add dispatches on that marker and hands everything else to mgcc_cases.prolong_add.  cycle, run and
-rr_sequence are mgsemi_cases' own functions re-bound to this module's namespace, as mgcc_cases re-binds them; lines_run is
-mgfuzz_cases' composed cycle (line stages per level) re-bound the same way.  Nothing of them is written twice."""
-import types
-
+"""The problems of the linear prolongation on cell-centred pairs: a pair that prolongs linearly carries a
+Linear(axes, rim), .rim[d] = (low rule, high rule) per field dimension, EVEN for a Neumann face and ODD for a Dirichlet one;
+operators whose two faces of a dimension may differ.  The transfers and the cycle are mg_restatement's."""
 import numpy as np
 
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcc_cases as cc
-import mgfuzz_cases as fz
-import mgsemi_cases as sc
-from mgcc_cases import Halved
-
-EVEN, ODD = 0, 1            # NEPTUNE_HIP_MG_RIM_EVEN / _ODD
-RULE = {"neumann": EVEN, "dirichlet": ODD}
-expected_stop = mgc.expected_stop
-tol_between = mgc.tol_between
-restrict = cc.restrict      # a Linear is a Halved: the averaging restriction
-
-
-class Linear(Halved):
-    """the dimensions halved between a level and the next one, prolonged linearly; .rim[d] = (low, high) rule of dimension d"""
-
-    def __new__(cls, axes, rim):
-        self = super().__new__(cls, axes)
-        self.rim = tuple((int(lo), int(hi)) for lo, hi in rim)
-        assert all(v in (EVEN, ODD) for pair in self.rim for v in pair)
-        return self
-
-
-def rim_of(faces, rank):
-    """((low, high) rule per dimension) for faces = "neumann" / "dirichlet" or a (low, high) pair of them per dimension"""
-    if isinstance(faces, str):
-        faces = [(faces, faces)] * rank
-    assert len(faces) == rank
-    return tuple((RULE[lo], RULE[hi]) for lo, hi in faces)
-
-
-def complement(rim):
-    return tuple((1 - lo, 1 - hi) for lo, hi in rim)
-
-
-# ---------------------------------------------------------------- the prolongation
-def _linear(e, axis, rule_lo, rule_hi):
-    """m -> 2 m cells along `axis`: fine 2 j takes 0.75 e[j] + 0.25 e[j - 1], fine 2 j + 1 takes 0.75 e[j] + 0.25 e[j + 1], e
-    padded with + (EVEN) or - (ODD) its own edge"""
-    dt = e.dtype.type
-    m = e.shape[axis]
-    take = lambda a, idx: np.take(a, idx, axis=axis)
-    first, last = take(e, [0]), take(e, [m - 1])
-    with np.errstate(invalid="ignore", over="ignore"):
-        padded = np.concatenate([-first if rule_lo == ODD else first, e, -last if rule_hi == ODD else last], axis=axis)
-        p = (dt(0.75) * e).astype(dt)
-        sm = (dt(0.25) * take(padded, np.arange(0, m))).astype(dt)
-        sp = (dt(0.25) * take(padded, np.arange(2, m + 2))).astype(dt)
-        even = (p + sm).astype(dt)
-        odd = (p + sp).astype(dt)
-    shape = list(e.shape)
-    shape[axis] = 2 * m
-    out = np.empty(shape, e.dtype)
-    sl = [slice(None)] * e.ndim
-    sl[axis] = slice(0, None, 2)
-    out[tuple(sl)] = even
-    sl[axis] = slice(1, None, 2)
-    out[tuple(sl)] = odd
-    return out
-
-
-def prolong_add_linear(x_c, where_c, x_f, where_f, axes, rim):
-    """-> a new x_f: x_f + P(x_c) on the fine Omega, P linear along `axes` by the rules rim[d] = (low, high); every other cell
-    keeps its bits; nothing outside where_c is read"""
-    dt = x_f.dtype.type
-    e = x_c[where_c]
-    for axis in reversed(range(e.ndim)):
-        if axis in axes:
-            e = _linear(e, axis, *rim[axis])
-    out = x_f.copy()
-    with np.errstate(invalid="ignore", over="ignore"):
-        out[where_f] = (x_f[where_f] + e).astype(dt)
-    return out
-
-
-def prolong_add(x_c, where_c, x_f, where_f, axes):
-    if isinstance(axes, Linear):
-        return prolong_add_linear(x_c, where_c, x_f, where_f, axes, axes.rim)
-    return cc.prolong_add(x_c, where_c, x_f, where_f, axes)
-
-
-# ---------------------------------------------------------------- the cycle and the solve, re-bound
-def _rebound(fn, namespace=None):
-    out = types.FunctionType(fn.__code__, globals() if namespace is None else namespace, fn.__name__, fn.__defaults__)
-    out.__doc__ = fn.__doc__
-    return out
-
-
-cycle = _rebound(sc.cycle)
-run = _rebound(sc.run)
-rr_sequence = _rebound(sc.rr_sequence)
-
-# mgfuzz_cases' composed cycle (a level may carry .stages) calls cc.restrict / cc.prolong_add: its globals with `cc` = this
-# module's two transfers
-_composed = dict(vars(fz))
-_composed["cc"] = types.SimpleNamespace(restrict=restrict, prolong_add=prolong_add)
-for _name in ("descend", "cycle", "run"):
-    _composed[_name] = _rebound(getattr(fz, _name), _composed)
-lines_run = _composed["run"]
+from mg_restatement import Linear
 
 
 # ---------------------------------------------------------------- hierarchies
@@ -121,7 +14,7 @@ def linear_steps(steps, rim, only=None):
     """mgcc_cases' steps [(extents, weights, axes)] with every Halved pair (or the pairs listed in `only`) made Linear"""
     out = []
     for l, (m, w, axes) in enumerate(steps):
-        if isinstance(axes, Halved) and len(axes) and (only is None or l in only):
+        if rst.pair_of(axes, len(m)).halved and len(axes) and (only is None or l in only):
             axes = Linear(axes, rim)
         out.append((m, w, axes))
     return out
@@ -169,7 +62,7 @@ def flux_levels(steps, damp, dtype=np.float64, faces="neumann"):
         rest, diag = mixed_face_fields(m, dtype, faces, w)
         minv = np.full(shape, 0.0 if l == 0 else np.nan, dtype)
         minv[where] = (dt(damp) / diag[where]).astype(dt)
-        L = mgc.Level(mgc.Operator(text, *rest), shape, where, minv, dtype)
+        L = rst.Level(rst.Operator(text, *rest), shape, where, minv, dtype)
         L.axes, L.weights = axes, w
         levels.append(L)
         texts.append(text)
@@ -244,7 +137,7 @@ def star_levels(steps, damp, dtype=np.float64, faces="dirichlet"):
         text = star_s_module(shape, dtype)
         minv = np.full(shape, 0.0 if l == 0 else np.nan, dtype)
         minv[where] = (dt(damp) / (dt(2 * rank) + s[where]).astype(dt)).astype(dt)
-        L = mgc.Level(mgc.Operator(text, s), shape, where, minv, dtype)
+        L = rst.Level(rst.Operator(text, s), shape, where, minv, dtype)
         L.axes, L.weights = axes, w
         levels.append(L)
         texts.append(text)

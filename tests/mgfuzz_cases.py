@@ -1,21 +1,8 @@
-"""Composed multigrid hierarchies, fuzzed: ONE NumPy restatement of the cycle, the solve, the MGCG
-preconditioner and the replay, composed of the pieces the features' own case modules define, and a seeded generator of
-hierarchies that mix what those modules test one at a time.
+"""Composed multigrid hierarchies, fuzzed: a seeded generator of hierarchies that mix what the features' case
+modules test one at a time, run on mg_restatement.  A level's operator is mg_restatement.OmegaOperator: the oracle's A on
+Omega and +0 on every other cell.
 
-First half -- the restatement.  Nothing of the arithmetic is written again: the transfers are mgcc_cases.restrict /
-prolong_add (they dispatch per pair on Level.axes: an mgcc_cases.Halved goes to the cell-centred pair, a plain tuple to
-mgsemi_cases' vertex-centred one, mg_cases._weigh / _interp underneath), the sweep is mglines_cases.sweep (line_stage on a
-level with stages, mg_cases.smooth on one without, the stages reversed for a post-sweep), the first pre-sweep of the
-preconditioner is mgcglines_cases.first_stage or mgcg_cases.first_sweep, the recurrences are those of mgcg_cases.replay,
-and the mixed form narrows, widens and updates with mgcgmixed_cases.  Only the control flow of include/neptune_hip.h --
-Cycle(l), "the rest of M", the set-up, the iteration -- stands here, once.
-
-A level's operator is OmegaOperator: the oracle's A on Omega and +0 on every other cell.  That is what q holds where the
-solvers read it outside Omega: the MGCG drivers stream q over the whole box, a launch writes Omega (and copies p = +0
-through between the launch region and the module's bounds), and where the region is not the whole box the drivers zero-fill
-q once.  Sweeps, stages and transfers read q on Omega only.
-
-Second half -- the generator.  decode(seed) draws a case from a fixed pool of module templates (TEMPLATES): a template fixes
+decode(seed) draws a case from a fixed pool of module templates (TEMPLATES): a template fixes
 rank, element type, the boxes (unequal rims of 1..3 cells), the modules' bounds and, per pair, the dimensions transferred --
 so also the weights per level, by the plan rule (w on a transferred dimension, 4 w on a kept one).  Everything else is drawn
 and costs no compile: how many of the template's levels are used, Omega inside the bounds (a launch region), and with it the
@@ -26,196 +13,17 @@ import sys
 
 import numpy as np
 
-import cg_cases as cgc
 import helpers
-import mg_cases as mgc
-import mgcc_cases as cc
+import mg_restatement as rst
 import mgcg_cases as mg
-import mgcglines_cases as mlc
 import mgcgmixed_cases as mx
 import mglines_cases as lc
 import monitor_cases as mc
-from mgcc_cases import Halved
+from mg_restatement import Halved
 
 D, S = np.float64, np.float32
 DAMP = 0.8
 
-
-# ================================================================ first half: the composed restatement
-class OmegaOperator:
-    """the oracle's A for one module text, on Omega: q = A(u) on `where`, +0 on every other cell (module docstring)"""
-    _parsed = {}
-
-    def __init__(self, text, where):
-        if text not in self._parsed:
-            self._parsed[text] = mgc.Operator(text)
-        self.A, self.where, self.rest = self._parsed[text], tuple(where), ()
-
-    def __call__(self, u):
-        out = np.zeros_like(u)
-        out[self.where] = self.A(u)[self.where]
-        return out
-
-
-def axes_of(L):
-    """the dimensions transferred between L and the next level: L.axes (a Halved for a cell-centred pair), default all"""
-    return getattr(L, "axes", tuple(range(len(L.shape))))
-
-
-sweep = lc.sweep        # stages 0 .. k-1 (reverse: k-1 .. 0), each after its own apply; without stages mg_cases.sweep
-
-
-def descend(levels, l, pre, post, coarse_sweeps):
-    """q = A(x) and the restriction; Cycle(l + 1); prolongation and correction"""
-    L, nxt = levels[l], levels[l + 1]
-    L.q = L.A(L.x)
-    nxt.b, nxt.x = cc.restrict(L.b, L.q, L.where, L.rscale, nxt.b, nxt.x, nxt.where, axes_of(L))
-    cycle(levels, l + 1, pre, post, coarse_sweeps)
-    L.x = cc.prolong_add(nxt.x, nxt.where, L.x, L.where, axes_of(L))
-
-
-def cycle(levels, l, pre, post, coarse_sweeps):
-    """Cycle(l) of include/neptune_hip.h"""
-    L = levels[l]
-    if l == len(levels) - 1:
-        for _ in range(coarse_sweeps):
-            sweep(L)
-        return
-    for _ in range(pre):
-        sweep(L)
-    descend(levels, l, pre, post, coarse_sweeps)
-    for _ in range(post):
-        sweep(L, reverse=True)
-
-
-def run(levels, x0, b0, cycles, pre=2, post=2, coarse_sweeps=8, check_every=1):
-    """the solve with no tolerance: -> (rr0, [rr after each block]) as (sum, bound) pairs; the fields are left in `levels`"""
-    mgc.start(levels, x0, b0)
-    rr0 = mgc.residual(levels[0])
-    checks, done = [], 0
-    while done < cycles:
-        for _ in range(min(check_every, cycles - done)):
-            cycle(levels, 0, pre, post, coarse_sweeps)
-            done += 1
-        checks.append(mgc.residual(levels[0]))
-    return rr0, checks
-
-
-def first_pre_sweep(levels, r):
-    """level 0's first pre-sweep on (x, b) = (z, r) from z = 0: with stages, stage 0 apply-free and the others plain; without,
-    z = minv_0 * r on every cell"""
-    L0 = levels[0]
-    stages = getattr(L0, "stages", [])
-    L0.b = r
-    if not stages:
-        L0.x = mg.first_sweep(levels, r)
-        return
-    axis, lo, inv, up = stages[0]
-    L0.x = mlc.first_stage(r, lo, inv, up, np.zeros(L0.shape, L0.dt), L0.where, axis)
-    for axis, lo, inv, up in stages[1:]:
-        L0.q = L0.A(L0.x)
-        L0.x = lc.line_stage(L0.q, L0.b, lo, inv, up, L0.x, L0.where, axis)
-
-
-def rest_of_cycle(levels, sweeps, coarse_sweeps):
-    """"the rest of M": everything of the cycle on level 0's (x, b) = (z, r) after its first pre-sweep; -> z"""
-    L0 = levels[0]
-    for _ in range(sweeps - 1):
-        sweep(L0)
-    descend(levels, 0, sweeps, sweeps, coarse_sweeps)
-    for _ in range(sweeps):
-        sweep(L0, reverse=True)
-    return L0.x
-
-
-def precondition(levels, r, sweeps=2, coarse_sweeps=8):
-    """z = M(r): one V(sweeps, sweeps) cycle on A_0 z = r from z = 0 (call mgcg_cases.start(levels) once before)"""
-    assert len(levels) >= 2 and sweeps >= 1
-    first_pre_sweep(levels, r)
-    return rest_of_cycle(levels, sweeps, coarse_sweeps)
-
-
-class State:
-    """the fields of an MGCG run: x, r, p, z (mixed: x, r, p in f64 and r32, z32)"""
-
-
-def setup(problem, x0, b0, sweeps=2, coarse_sweeps=8):
-    """the definition's set-up for a list of levels or an mgcgmixed_cases.Problem: -> (State, rr0, rz0), the two sums as
-    (terms' sum, bound)"""
-    st = State()
-    if isinstance(problem, mx.Problem):
-        st.x, st.r, st.r32, z32, rr0 = mx.store_residual(problem, x0, b0)
-        L0 = problem.levels[0]
-        L0.x, L0.b = z32, st.r32
-        st.z32 = rest_of_cycle(problem.levels, sweeps, coarse_sweeps)
-        st.p = mx.widen(st.z32)
-        return st, rr0, mx.wide_dot_terms(st.r32, st.z32, problem.where)
-    L0 = problem[0]
-    mg.start(problem)
-    st.x = x0.copy()
-    q = L0.A(st.x)
-    st.r = np.zeros_like(st.x)
-    with np.errstate(invalid="ignore", over="ignore"):
-        st.r[L0.where] = (b0[L0.where] - q[L0.where]).astype(L0.dt)
-    rr0 = cgc.dot_terms(st.r, st.r, L0.where)
-    st.z = precondition(problem, st.r, sweeps, coarse_sweeps)
-    st.p = st.z.copy()
-    return st, rr0, cgc.dot_terms(st.r, st.z, L0.where)
-
-
-def _own(terms):
-    """numpy's own sum of the terms in their element type, as mgcg_cases.numpy_mgcg forms its scalars"""
-    return terms.dtype.type(np.sum(terms, dtype=terms.dtype))
-
-
-def replay(problem, x0, b0, rz0=None, trace=None, sweeps=2, coarse_sweeps=8, iters=None):
-    """The recurrences of mgcg_cases.replay / mgcgmixed_cases.replay on the composed preconditioner, driven by the DEVICE's
-    scalars rz0 and trace rows (pq_k, rz_(k+1), rr_(k+1)) -- or, with trace = None, by numpy's own sums for `iters`
-    iterations, as numpy_mgcg.  -> (State, checks, rr0, rz0_ref, scalars): checks[k] = the (terms' sum, bound) pairs of pq,
-    rz' and rr' of the replay's own fields; scalars[k] = (pq, rz', rr', broken) as used; the levels' x_l, b_l are left in the
-    levels."""
-    mixed = isinstance(problem, mx.Problem)
-    A = problem.A if mixed else problem[0].A
-    where = problem.where if mixed else problem[0].where
-    dt = D if mixed else problem[0].dt
-    st, rr0, rz0_ref = setup(problem, x0, b0, sweeps, coarse_sweeps)
-    zr = (lambda: (mx.widen(st.r32[where]) * mx.widen(st.z32[where]))) if mixed else (lambda: (st.r[where] * st.z[where]).astype(dt))
-    rz = dt(rz0) if trace is not None else _own(zr())
-    st.rz0_used = rz
-    checks, scalars = [], []
-    everywhere = tuple(slice(None) for _ in st.x.shape)
-    for k in range(len(trace) if trace is not None else iters):
-        q = A(st.p)
-        pq_ref = cgc.dot_terms(q, st.p, where)
-        pq = dt(trace[k][0]) if trace is not None else _own((q[where] * st.p[where]).astype(dt))
-        broken = rz == 0 or pq == 0
-        alpha = dt(0) if broken else dt(rz / pq)
-        if mixed:
-            st.x, st.r, st.r32, z32 = mx.update(problem, alpha, st.x, st.r, st.p, q)
-            L0 = problem.levels[0]
-            L0.x, L0.b = z32, st.r32
-        else:
-            with np.errstate(invalid="ignore", over="ignore"):
-                st.x = (st.x + (alpha * st.p).astype(dt)).astype(dt)
-                st.r = (st.r - (alpha * q).astype(dt)).astype(dt)
-        rr_ref = cgc.dot_terms(st.r, st.r, everywhere)
-        if mixed:
-            st.z32 = rest_of_cycle(problem.levels, sweeps, coarse_sweeps)
-            rz_ref = mx.wide_dot_terms(st.r32, st.z32, where)
-        else:
-            st.z = precondition(problem, st.r, sweeps, coarse_sweeps)
-            rz_ref = cgc.dot_terms(st.r, st.z, where)
-        checks.append((pq_ref, rz_ref, rr_ref))
-        rz_new = dt(trace[k][1]) if trace is not None else _own(zr())
-        beta = dt(0) if broken else dt(rz_new / rz)
-        with np.errstate(invalid="ignore", over="ignore"):
-            st.p = ((mx.widen(st.z32) if mixed else st.z) + (beta * st.p).astype(dt)).astype(dt)
-        scalars.append((pq, rz_new, _own((st.r * st.r).astype(dt)), bool(broken)))
-        rz = rz_new
-    return st, checks, rr0, rz0_ref, scalars
-
-
-# ================================================================ second half: the seeded generator
 # name: (element type of the hierarchy, [the module's bounds extents per level], [the dimensions transferred per pair],
 #        whether an f64 outer operator of level 0 exists (mixed precision))
 # Transferred extents double from level to level (or double plus one), kept ones stay: Omega, drawn inside the bounds,
@@ -392,7 +200,7 @@ def stage_factors(shape, where, weights, axis, dtype, outside=np.nan):
 
 
 def restatement_levels(case, dtype=None):
-    """the restatement's levels of a case (mg_cases.Level with .axes, .stages, .weights): minv = DAMP / diagonal on Omega; outside
+    """the restatement's levels of a case (mg_restatement.Level with .axes, .stages, .weights): minv = DAMP / diagonal on Omega; outside
     Omega level 0's is +0 for the CG forms (they form minv_0 * r on the whole box) and NaN everywhere else, as the factor fields"""
     dtype = dtype or case["dtype"]
     dt = np.dtype(dtype).type
@@ -402,7 +210,7 @@ def restatement_levels(case, dtype=None):
         zero_outside = l == 0 and case["form"] in ("cg", "cg-lines", "mixed")
         minv = np.full(shape, 0.0 if zero_outside else np.nan, dtype)
         minv[where] = dt(dt(DAMP) / dt(2.0 * sum(w)))
-        L = mgc.Level(OmegaOperator(module_text(name, l, dtype), where), shape, where, minv, dtype)
+        L = rst.Level(rst.OmegaOperator(module_text(name, l, dtype), where), shape, where, minv, dtype)
         L.weights = w
         if l + 1 < case["n_levels"]:
             L.axes = Halved(case["transferred"][l]) if case["kinds"][l] == "H" else tuple(case["transferred"][l])
@@ -431,7 +239,7 @@ def problem_fields(case):
 
 
 class Built:
-    """a case ready to run: .case, .levels (the restatement's; f32 for a mixed case), .problem (what setup / replay take: the
+    """a case ready to run: .case, .levels (the restatement's; f32 for a mixed case), .problem (what mg_restatement.setup / replay take: the
     levels, or an mgcgmixed_cases.Problem around them), .x0, .b"""
 
 
@@ -441,7 +249,7 @@ def build(case):
     B.levels = restatement_levels(case)
     B.problem = B.levels
     if case["form"] == "mixed":
-        B.problem = mx.Problem(OmegaOperator(module_text(case["template"], 0, D), B.levels[0].where), B.levels)
+        B.problem = mx.Problem(rst.OmegaOperator(module_text(case["template"], 0, D), B.levels[0].where), B.levels)
     B.x0, B.b = problem_fields(case)
     return B
 
@@ -449,7 +257,7 @@ def build(case):
 def reference(B):
     """the restatement's solve() run of a built case: -> (rr0, checks); the fields are left in B.levels"""
     c = B.case
-    return run(B.levels, B.x0, B.b, c["n"], c["pre"], c["post"], c["coarse_sweeps"], c["check_every"])
+    return rst.run(B.levels, B.x0, B.b, c["n"], c["pre"], c["post"], c["coarse_sweeps"], c["check_every"])
 
 
 def expected_counts(case):

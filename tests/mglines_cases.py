@@ -1,9 +1,9 @@
-"""The NumPy restatement of multigrid line smoothers: the line stage, the factor recurrence and the sweep
-order, exactly as include/neptune_hip.h defines them -- arithmetic in the element type with one `.astype(dt)` per operation,
-the recurrences marched cell by cell along the line (vectorised across the lines only, which changes no value).  The
-transfers, the cycle skeleton, rr and expected_stop are mg_cases' (mgsemi_cases' transfers where a level carries `.axes`).
+"""The problems of multigrid line smoothers and the factor recurrence of a line stage, exactly as
+include/neptune_hip.h defines it -- arithmetic in the element type with one `.astype(dt)` per operation, marched cell by cell
+along the line (vectorised across the lines only, which changes no value).  The stage itself, the sweep order and the cycle
+are mg_restatement's.
 
-A level is an mg_cases.Level with `.stages`, a list of (axis, lo, inv, up): empty means the point sweep with minv.
+A level is an mg_restatement.Level with `.stages`, a list of (axis, lo, inv, up): empty means the point sweep with minv.
 
 Operators: mg_cases' star for the shape tests (its tridiagonal part along any axis is (-1, 2 rank, -1)), and flux_module,
 the symmetric flux form with two cell coefficient fields whose strong direction varies across the domain:
@@ -13,11 +13,8 @@ with a = eps^(1 - t), c = eps^t, t = j / (n1 - 1) for physical column j: dim 1 i
 import numpy as np
 
 import mg_cases as mgc
-import mgsemi_cases as sc
+import mg_restatement as rst
 import monitor_cases as mc
-
-expected_stop = mgc.expected_stop
-tol_between = mgc.tol_between
 
 
 # ---------------------------------------------------------------- the flux-form operator
@@ -136,91 +133,6 @@ def factors(lower, diag, upper, where, axis, omega, outside=0.0):
     return tuple(out)
 
 
-# ---------------------------------------------------------------- the line stage
-def line_stage(q, b, lo, inv, up, x, where, axis):
-    """one stage from q = A(x): -> a new x; every cell outside Omega keeps its bits.  lo at i = 0, up at i = m - 1 and
-    everything outside Omega are not read."""
-    dt = x.dtype.type
-    view = lambda f: np.moveaxis(f[where], axis, 0)
-    qv, bv, lv, iv, uv, xv = view(q), view(b), view(lo), view(inv), view(up), view(x)
-    m = xv.shape[0]
-    g = [None] * m
-    with np.errstate(invalid="ignore", over="ignore"):
-        for i in range(m):
-            d = (bv[i] - qv[i]).astype(dt)
-            if i == 0:
-                g[0] = (d * iv[0]).astype(dt)
-            else:
-                t = (lv[i] * g[i - 1]).astype(dt)
-                s = (d - t).astype(dt)
-                g[i] = (s * iv[i]).astype(dt)
-        new = np.empty(xv.shape, x.dtype)
-        e = g[m - 1]
-        new[m - 1] = (xv[m - 1] + e).astype(dt)
-        for i in range(m - 2, -1, -1):
-            t = (uv[i] * e).astype(dt)
-            e = (g[i] - t).astype(dt)
-            new[i] = (xv[i] + e).astype(dt)
-    out = x.copy()
-    out[where] = np.moveaxis(new, 0, axis)
-    return out
-
-
-# ---------------------------------------------------------------- the sweep, the cycle and the solve
-def sweep(L, reverse=False):
-    """a level without stages: mg_cases.sweep; with k stages: all k, each after its own apply, in order 0 .. k-1 or reversed"""
-    stages = getattr(L, "stages", [])
-    if not stages:
-        mgc.sweep(L)
-        return
-    for axis, lo, inv, up in (reversed(stages) if reverse else stages):
-        L.q = L.A(L.x)
-        L.x = line_stage(L.q, L.b, lo, inv, up, L.x, L.where, axis)
-
-
-def cycle(levels, l, pre, post, coarse_sweeps):
-    L = levels[l]
-    if l == len(levels) - 1:
-        for _ in range(coarse_sweeps):
-            sweep(L)
-        return
-    for _ in range(pre):
-        sweep(L)
-    L.q = L.A(L.x)
-    nxt = levels[l + 1]
-    axes = getattr(L, "axes", tuple(range(len(L.shape))))
-    nxt.b, nxt.x = sc.restrict(L.b, L.q, L.where, L.rscale, nxt.b, nxt.x, nxt.where, axes)
-    cycle(levels, l + 1, pre, post, coarse_sweeps)
-    L.x = sc.prolong_add(nxt.x, nxt.where, L.x, L.where, axes)
-    for _ in range(post):
-        sweep(L, reverse=True)
-
-
-def run(levels, x0, b0, cycles, pre=2, post=2, coarse_sweeps=8, check_every=1):
-    """mg_cases.run on this module's cycle: -> (rr0, [rr after each block]) as (sum, bound) pairs"""
-    mgc.start(levels, x0, b0)
-    rr0 = mgc.residual(levels[0])
-    checks, done = [], 0
-    while done < cycles:
-        for _ in range(min(check_every, cycles - done)):
-            cycle(levels, 0, pre, post, coarse_sweeps)
-            done += 1
-        checks.append(mgc.residual(levels[0]))
-    return rr0, checks
-
-
-def rr_sequence(levels, x0, b0, cycles, pre=2, post=2, coarse_sweeps=8, stop_at=None):
-    """[rr_0, rr after cycle 1, ...] as floats; stop_at: a factor -- end early once rr <= stop_at * rr_0"""
-    mgc.start(levels, x0, b0)
-    seq = [mgc.residual(levels[0])[0]]
-    for _ in range(cycles):
-        if stop_at is not None and seq[-1] <= stop_at * seq[0]:
-            break
-        cycle(levels, 0, pre, post, coarse_sweeps)
-        seq.append(mgc.residual(levels[0])[0])
-    return seq
-
-
 # ---------------------------------------------------------------- hierarchies
 def star_tridiagonal(shape, where, dtype):
     """the tridiagonal part of mg_cases' star along any axis except for the rim couplings: (-1, 2 rank, -1) on Omega"""
@@ -264,7 +176,7 @@ def flux_levels(stage_axes=(0, 1), n=FLUX_N, damp=FLUX_DAMP, dtype=np.float64, e
         text = flux_module(shape, dtype)
         minv = np.full(shape, outside, dtype)
         minv[where] = (dt(damp) / flux_tridiagonal(a, c, 0)[1][where]).astype(dt)
-        L = mgc.Level(mgc.Operator(text, a, c), shape, where, minv, dtype)
+        L = rst.Level(rst.Operator(text, a, c), shape, where, minv, dtype)
         L.stages = [(ax,) + factors(*flux_tridiagonal(a, c, ax), where, ax, damp, outside) for ax in stage_axes]
         levels.append(L)
         texts.append(text)
@@ -279,3 +191,12 @@ def flux_problem(levels, seed=2024):
     rng = np.random.default_rng(seed)
     b = rng.standard_normal(levels[0].shape).astype(levels[0].dt)
     return np.zeros(levels[0].shape, levels[0].dt), b
+
+
+def stage_applications(levels, sweeps, coarse_sweeps):
+    """how many line stages (or point sweeps) one cycle applies over all levels"""
+    total = 0
+    for l, L in enumerate(levels):
+        k = max(len(getattr(L, "stages", [])), 1)
+        total += k * (coarse_sweeps if l == len(levels) - 1 else 2 * sweeps)
+    return total

@@ -1,12 +1,13 @@
 """neptune_hip_mg_*  without a GPU: the exports and signatures, every refusal on host pointers (the argument
 checks run before the device is touched), the restatement's transfer operators against dense matrices, and the convergence
-preconditions the GPU stop tests rely on -- conditions on the restatement (tests/mg_cases.py), not on the code under test."""
+preconditions the GPU stop tests rely on -- conditions on the restatement (tests/mg_restatement.py), not on the code under test."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import mg_cases as mgc
+import mg_restatement as rst
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
 
@@ -188,27 +189,27 @@ def _dense(f, n_in, n_out):
 
 def test_transfer_operators_on_a_seven_cell_line():
     whole = lambda n: (slice(0, n),)
-    R = _dense(lambda d: mgc.restrict(d, np.zeros(7), whole(7), 1.0, np.full(3, np.nan), np.full(3, np.nan), whole(3))[0], 7, 3)
+    R = _dense(lambda d: rst.restrict(d, np.zeros(7), whole(7), 1.0, np.full(3, np.nan), np.full(3, np.nan), whole(3))[0], 7, 3)
     want = np.zeros((3, 7))
     for j in range(3):
         want[j, 2 * j:2 * j + 3] = (0.25, 0.5, 0.25)
     assert np.array_equal(R, want)
-    P = _dense(lambda e: mgc.prolong_add(e, whole(3), np.zeros(7), whole(7)), 3, 7)
+    P = _dense(lambda e: rst.prolong_add(e, whole(3), np.zeros(7), whole(7)), 3, 7)
     assert np.array_equal(P, 2.0 * R.T)
     # constants are reproduced away from the rim: restriction everywhere (all its operands lie inside), prolongation on
     # every fine cell but the two next to the rim, which interpolate against the rim's zero
     assert np.array_equal(R @ np.ones(7), np.ones(3))
     assert np.array_equal((P @ np.ones(3))[1:-1], np.ones(5)) and P[0, 0] == 0.5 and P[-1, -1] == 0.5
     # restriction writes x = +0 on the coarse Omega and leaves everything outside alone
-    bc, xc = mgc.restrict(np.ones(9), np.zeros(9), (slice(1, 8),), 4.0, np.full(6, 7.0), np.full(6, 7.0), (slice(2, 5),))
+    bc, xc = rst.restrict(np.ones(9), np.zeros(9), (slice(1, 8),), 4.0, np.full(6, 7.0), np.full(6, 7.0), (slice(2, 5),))
     assert np.array_equal(bc, [7, 7, 4, 4, 4, 7]) and np.array_equal(xc, [7, 7, 0, 0, 0, 7])
 
 
 def test_tensor_product_matches_the_axis_by_axis_form():
     rng = np.random.default_rng(5)
     e = rng.standard_normal((1, 3, 7))
-    out = mgc.prolong_add(e, (slice(0, 1), slice(0, 3), slice(0, 7)), np.zeros((3, 7, 15)), (slice(0, 3), slice(0, 7), slice(0, 15)))
-    P = [2.0 * _dense(lambda d, n=n: mgc.restrict(d, np.zeros(2 * n + 1), (slice(0, 2 * n + 1),), 1.0, np.zeros(n), np.zeros(n),
+    out = rst.prolong_add(e, (slice(0, 1), slice(0, 3), slice(0, 7)), np.zeros((3, 7, 15)), (slice(0, 3), slice(0, 7), slice(0, 15)))
+    P = [2.0 * _dense(lambda d, n=n: rst.restrict(d, np.zeros(2 * n + 1), (slice(0, 2 * n + 1),), 1.0, np.zeros(n), np.zeros(n),
                                                  (slice(0, n),))[0], 2 * n + 1, n).T for n in (1, 3, 7)]
     want = np.einsum("ai,bj,ck,ijk->abc", P[0], P[1], P[2], e)
     assert np.allclose(out, want, rtol=1e-14, atol=1e-14)
@@ -231,7 +232,7 @@ def test_rr_falls_by_a_factor_of_four_per_cycle(name, built_libs):
     omega, n_levels, damp, dtype, cycles = CONVERGENCE[name]
     levels, _ = mgc.star_levels(omega, n_levels, dtype, damp)
     x0, b = mgc.problem_fields(levels[0].shape, levels[0].where, dtype)
-    seq = mgc.rr_sequence(levels, x0, b, cycles)
+    seq = rst.rr_sequence(levels, x0, b, cycles)
     print(name, [f"{a / c:.1f}" for a, c in zip(seq, seq[1:])])
     assert len(seq) == cycles + 1
     for a, c in zip(seq, seq[1:]):

@@ -1,5 +1,5 @@
 """The three multigrid kernels alone (neptune_hip_mg_smooth / _restrict / _prolong_add) against the NumPy
-restatement of tests/mg_cases.py: bit for bit on every cell, the untouched cells outside Omega included.
+restatement of tests/mg_restatement.py: bit for bit on every cell, the untouched cells outside Omega included.
 
 Shapes: the smallest at which the kernels can go wrong -- unequal rims, a row that crosses the 256-cell chunk with an odd
 tail, ranks 1 to 3, fields 8 bytes into larger allocations (the unaligned forms), and a coarse grid one cell thick, where
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import helpers
-import mg_cases as mgc
+import mg_restatement as rst
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
 
@@ -86,7 +86,7 @@ def test_smooth(nh, name, dtype, offset):
     x = _field(shape, dtype, 14)
     x[tuple(0 for _ in shape)] = np.nan          # a NaN and a -0 outside Omega keep their bits
     x[tuple(n - 1 for n in shape)] = -0.0
-    want = mgc.smooth(q, b, minv, x, w)
+    want = rst.smooth(q, b, minv, x, w)
     G.fine.minv = _dev(nh, minv, offset)
     xd = _dev(nh, x, offset)
     nh.mg.smooth(G.fine, _dev(nh, q, offset), _dev(nh, b, offset), xd)
@@ -104,7 +104,7 @@ def test_restrict(nh, name, dtype, offset):
     x_c = _field(G.coarse_shape, dtype, 24)
     for a in (b_c, x_c):
         a[tuple(0 for _ in a.shape)] = np.nan
-    want_b, want_x = mgc.restrict(b_f, q_f, G.fw, mgc.RSCALE, b_c, x_c, G.cw)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, rst.RSCALE, b_c, x_c, G.cw)
     bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
@@ -120,7 +120,7 @@ def test_prolong_add(nh, name, dtype, offset):
     x_c = _field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # the coarse rim is +0 whatever the field holds there
     x_f = _field(G.fine_shape, dtype, 32)
     x_f[tuple(0 for _ in x_f.shape)] = np.nan
-    want = mgc.prolong_add(x_c, G.cw, x_f, G.fw)
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw)
     xd = _dev(nh, x_f, offset)
     nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()

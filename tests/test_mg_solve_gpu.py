@@ -17,6 +17,7 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import pcg_cases as pc
 from helpers import bits_equal, mismatch_report
 
@@ -97,7 +98,7 @@ def _reference(P, cycles, check_every=1, n_levels=None, **kw):
     key = (cycles, check_every, n_levels, tuple(sorted(kw.items())))
     if key not in P.runs:
         levels = P.ref[:n_levels] if n_levels else P.ref
-        rr0, checks = mgc.run(levels, P.x0, P.b, cycles, check_every=check_every, **kw)
+        rr0, checks = rst.run(levels, P.x0, P.b, cycles, check_every=check_every, **kw)
         P.runs[key] = (rr0, checks, [L.x.copy() for L in levels], [L.b.copy() for L in levels])
     return P.runs[key]
 
@@ -172,11 +173,11 @@ def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
 def test_stops_where_the_definition_says(nh, name, check_every, between):
     P = _problem(nh, name)
     if "seq" not in P.runs:
-        P.runs["seq"] = mgc.rr_sequence(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
+        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
     seq = P.runs["seq"]
-    tol2 = mgc.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_cycles = len(seq) - 1
-    want_done, want_checks = mgc.expected_stop(seq, check_every, max_cycles, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
     assert want_done == between[1]
     (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
     print(f"{name}: seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
@@ -228,7 +229,7 @@ def test_two_input_operator_with_a_coefficient_per_level(nh):
         for text, (shape, where), wl in zip(P.texts, shapes, w):
             minv = np.full(shape, np.nan, dtype)
             minv[where] = (dtype(0.8) / (dtype(6.0) + wl[where])).astype(dtype)
-            P.ref.append(mgc.Level(mgc.Operator(text, wl), shape, where, minv, dtype))
+            P.ref.append(rst.Level(rst.Operator(text, wl), shape, where, minv, dtype))
         P.entries = [_entry(nh, t) for t in P.texts]
         P.others = [[nh.fields.DeviceField.from_numpy(wl)] for wl in w]
         P.x0, P.b = mgc.problem_fields(shapes[0][0], shapes[0][1], dtype)
@@ -247,8 +248,8 @@ def test_builtin_body_on_level_zero(nh):
     P = Problem()
     P.dtype, P.n_levels = dtype, 2
     A0 = lambda u: helpers.oracle_entry("3d7", u)
-    P.ref = [mgc.Level(A0, shapes[0][0], shapes[0][1], mgc.minv_field(shapes[0][0], shapes[0][1], dtype, 0.125), dtype),
-             mgc.Level(mgc.Operator(nh.texts["builtin"][0]), shapes[1][0], shapes[1][1],
+    P.ref = [rst.Level(A0, shapes[0][0], shapes[0][1], mgc.minv_field(shapes[0][0], shapes[0][1], dtype, 0.125), dtype),
+             rst.Level(rst.Operator(nh.texts["builtin"][0]), shapes[1][0], shapes[1][1],
                        mgc.minv_field(shapes[1][0], shapes[1][1], dtype, 0.8), dtype)]
     P.entries = [nh.capi.BODY_LAP3D7_F64, _entry(nh, nh.texts["builtin"][0])]
     P.others = [[], []]

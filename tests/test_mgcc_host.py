@@ -1,7 +1,7 @@
 """Multigrid on cell-centred grids without a GPU: the exported query neptune_hip_mg_halved_axes, inference and
 refusals on host pointers (the argument checks run before the device is touched), the restatement's transfers as dense
 matrices, the Python layer (coarsen_bounds / coarsening_plan with centring="cell", Hierarchy.halved, the error texts), and
-the convergence and symmetry preconditions the GPU tests rely on -- conditions on the restatement (tests/mgcc_cases.py), not
+the convergence and symmetry preconditions the GPU tests rely on -- conditions on the restatement (tests/mg_restatement.py), not
 on the code under test."""
 import ctypes as C
 
@@ -10,8 +10,9 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcc_cases as cc
-from mgcc_cases import Halved
+from mg_restatement import Halved
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
 
@@ -124,12 +125,12 @@ def test_solve_refuses_a_mixed_pair_on_host_pointers(lib):
 # ---------------------------------------------------------------- the transfers as dense matrices
 def _line_R(n, axes=Halved((0,))):
     where = (slice(0, n),)
-    return cc.dense(lambda e: cc.restrict_cell(e, np.zeros(n), where, 1.0, np.zeros(n // 2), np.zeros(n // 2), (slice(0, n // 2),), axes)[0],
+    return cc.dense(lambda e: rst.restrict(e, np.zeros(n), where, 1.0, np.zeros(n // 2), np.zeros(n // 2), (slice(0, n // 2),), Halved(axes))[0],
                     n, n // 2)
 
 
 def _line_P(n, axes=Halved((0,))):
-    return cc.dense(lambda e: cc.prolong_add_cell(e, (slice(0, n // 2),), np.zeros(n), (slice(0, n),), axes), n // 2, n)
+    return cc.dense(lambda e: rst.prolong_add(e, (slice(0, n // 2),), np.zeros(n), (slice(0, n),), Halved(axes)), n // 2, n)
 
 
 def test_dense_matrices_on_an_8_cell_line():
@@ -152,7 +153,7 @@ def test_tensor_product_against_einsum():
     cw = tuple(slice(l, l + m) for l, m in zip((2, 1, 1), cm))
     axes = Halved((0, 2))
     d = helpers.hash_field(fshape, np.float64, seed=3)
-    got_b, got_x = cc.restrict_cell(d, np.zeros(fshape), fw, 1.0, np.full(cshape, 7.0), np.full(cshape, 7.0), cw, axes)
+    got_b, got_x = rst.restrict(d, np.zeros(fshape), fw, 1.0, np.full(cshape, 7.0), np.full(cshape, 7.0), cw, Halved(axes))
     R0, R2 = _line_R(4), _line_R(8)
     want = np.einsum("ai,ck,ijk->ajc", R0, R2, d[fw])
     assert np.allclose(got_b[cw], want, rtol=4e-16, atol=0) and (got_x[cw] == 0).all()
@@ -160,15 +161,15 @@ def test_tensor_product_against_einsum():
     outside[cw] = False
     assert (got_b[outside] == 7.0).all() and (got_x[outside] == 7.0).all()
     e = helpers.hash_field(cshape, np.float64, seed=4)
-    got = cc.prolong_add_cell(e, cw, np.zeros(fshape), fw, axes)
+    got = rst.prolong_add(e, cw, np.zeros(fshape), fw, Halved(axes))
     P0, P2 = _line_P(4), _line_P(8)
     assert np.array_equal(got[fw], np.einsum("ia,kc,ajc->ijk", P0, P2, e[cw]))
     # P = 2^k R^T as matrices on Omega
     nf, nc = int(np.prod(fm)), int(np.prod(cm))
-    R = cc.dense(lambda v: cc.restrict_cell(v.reshape(fm), np.zeros(fm), tuple(slice(0, m) for m in fm), 1.0, np.zeros(cm), np.zeros(cm),
-                                            tuple(slice(0, m) for m in cm), axes)[0].reshape(-1), nf, nc)
-    P = cc.dense(lambda v: cc.prolong_add_cell(v.reshape(cm), tuple(slice(0, m) for m in cm), np.zeros(fm),
-                                               tuple(slice(0, m) for m in fm), axes).reshape(-1), nc, nf)
+    R = cc.dense(lambda v: rst.restrict(v.reshape(fm), np.zeros(fm), tuple(slice(0, m) for m in fm), 1.0, np.zeros(cm), np.zeros(cm),
+                                            tuple(slice(0, m) for m in cm), Halved(axes))[0].reshape(-1), nf, nc)
+    P = cc.dense(lambda v: rst.prolong_add(v.reshape(cm), tuple(slice(0, m) for m in cm), np.zeros(fm),
+                                               tuple(slice(0, m) for m in fm), Halved(axes)).reshape(-1), nc, nf)
     assert np.array_equal(P, 4.0 * R.T)
     assert np.array_equal(P @ np.ones(nc), np.ones(nf))
 
@@ -177,12 +178,12 @@ def test_the_dispatch_of_the_restatement():
     """a Halved tuple goes to the cell-centred transfers, a plain one to mgsemi_cases': one hierarchy, two grid kinds"""
     d = helpers.hash_field((14,), np.float64, seed=5)
     w14, w7, w3 = (slice(0, 14),), (slice(0, 7),), (slice(0, 3),)
-    b7, _ = cc.restrict(d, np.zeros(14), w14, 1.0, np.zeros(7), np.zeros(7), w7, Halved((0,)))
+    b7, _ = rst.restrict(d, np.zeros(14), w14, 1.0, np.zeros(7), np.zeros(7), w7, Halved((0,)))
     assert np.array_equal(b7, 0.5 * (d[0::2] + d[1::2]))
-    b3, _ = cc.restrict(b7, np.zeros(7), w7, 1.0, np.zeros(3), np.zeros(3), w3, (0,))
+    b3, _ = rst.restrict(b7, np.zeros(7), w7, 1.0, np.zeros(3), np.zeros(3), w3, (0,))
     assert np.allclose(b3, 0.25 * b7[0:5:2] + 0.5 * b7[1:6:2] + 0.25 * b7[2:7:2], rtol=1e-15)
-    assert np.array_equal(cc.prolong_add(b3, w3, np.zeros(7), w7, (0,))[1::2], b3)
-    assert np.array_equal(cc.prolong_add(b7, w7, np.zeros(14), w14, Halved((0,))), np.repeat(b7, 2))
+    assert np.array_equal(rst.prolong_add(b3, w3, np.zeros(7), w7, (0,))[1::2], b3)
+    assert np.array_equal(rst.prolong_add(b7, w7, np.zeros(14), w14, Halved((0,))), np.repeat(b7, 2))
 
 
 # ---------------------------------------------------------------- the Python layer
@@ -283,7 +284,7 @@ def test_the_restatement_converges(omega, faces):
     x0, b = mgc.problem_fields(L0.shape, L0.where, np.float64)
     if faces == "neumann":
         b = cc.compatible(b, L0.where)
-    seq = cc.rr_sequence(levels, x0, b, 6)
+    seq = rst.rr_sequence(levels, x0, b, 6)
     factors = [seq[k] / seq[k + 1] for k in range(6)]
     print(f"{omega} {faces}: " + ", ".join(f"{f:.3g}" for f in factors))
     smallest = CONVERGENCE[(omega, faces)]
@@ -295,17 +296,16 @@ def test_the_restatement_converges(omega, faces):
 def test_the_restated_cycle_is_a_symmetric_positive_preconditioner(faces):
     """z = M(r), one V(2, 2) cycle from z = 0: u . M(v) = v . M(u) to rounding and u . M(u) > 0 on random vectors (mean-free
     ones for Neumann faces, where constants are the operator's null space)"""
-    import mgcg_cases as mg
     levels, _, _ = cc.flux_levels(cc.plan((8, 16)), 0.8, np.float64, faces)
     L0 = levels[0]
-    mg.start(levels)
+    rst.start(levels)
     rng = np.random.default_rng(7)
 
     def vector():
         v = np.zeros(L0.shape)
         v[L0.where] = rng.standard_normal(L0.m)
         return cc.compatible(v, L0.where) if faces == "neumann" else v
-    M = lambda r: cc.precondition(levels, r).copy()
+    M = lambda r: rst.precondition(levels, r).copy()
     for _ in range(4):
         u, v = vector(), vector()
         Mu, Mv = M(u), M(v)

@@ -1,5 +1,5 @@
 """The two transfer kernels on cell-centred level pairs (neptune_hip_mg_restrict / _prolong_add) against the
-NumPy restatement of tests/mgcc_cases.py: each kernel alone, bit for bit on every cell of every field, the untouched cells
+NumPy restatement of tests/mg_restatement.py: each kernel alone, bit for bit on every cell of every field, the untouched cells
 outside Omega included.  On the parent commit every HALVED pair is NEPTUNE_HIP_EINVAL, so every test here fails there.
 
 Shapes: the smallest at which the kernels can go wrong.  Rank 3: fine box 9 x 18 x 268, Omega 6 x 14 x 262 at (1, 2, 3) onto
@@ -24,9 +24,10 @@ import numpy as np
 import pytest
 
 import helpers
-import mgcc_cases as cc
+import mg_restatement as rst
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_restatement import Halved
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +125,7 @@ def test_restrict(nh, name, dtype, offset):
     x_c = _field(G.coarse_shape, dtype, 24, G.cw, inside=np.nan)
     for a in (b_c, x_c):
         a[tuple(0 for _ in a.shape)] = np.nan
-    want_b, want_x = cc.restrict_cell(b_f, q_f, G.fw, 4.0, b_c, x_c, G.cw, G.axes)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, 4.0, b_c, x_c, G.cw, Halved(G.axes))
     bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
@@ -140,7 +141,7 @@ def test_prolong_add(nh, name, dtype, offset):
     x_c = _field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # no coarse cell outside the coarse Omega is read
     x_f = _field(G.fine_shape, dtype, 32)
     x_f[tuple(0 for _ in x_f.shape)] = np.nan
-    want = cc.prolong_add_cell(x_c, G.cw, x_f, G.fw, G.axes)
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Halved(G.axes))
     xd = _dev(nh, x_f, offset)
     nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()
@@ -162,7 +163,7 @@ def test_minus_zero_and_nan_go_through(nh, dtype):
     b_f[:, :, k0 + 10:k0 + 12] = -0.0                         # the fine columns 10, 11 -> the coarse column 5
     b_f[G.fw[0].start + 2, G.fw[1].start + 4, k0 + 261] = np.nan      # fine (2, 4, 261) -> coarse (1, 2, 130)
     zeros, ones = np.zeros(G.coarse_shape, dtype), np.ones(G.coarse_shape, dtype)
-    want_b, _ = cc.restrict_cell(b_f, q_f, G.fw, 1.0, zeros, ones, G.cw, G.axes)
+    want_b, _ = rst.restrict(b_f, q_f, G.fw, 1.0, zeros, ones, G.cw, Halved(G.axes))
     bd, xd = _dev(nh, zeros, 0), _dev(nh, ones, 0)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, 0), _dev(nh, q_f, 0), bd, xd)
     nh.torch.cuda.synchronize()
@@ -173,7 +174,7 @@ def test_minus_zero_and_nan_go_through(nh, dtype):
     assert np.isnan(inner).sum() == 1 and np.isnan(inner[1, 2, 130])
     assert (np.delete(inner, [5, 130], axis=2) == 1).all()
     x_f = np.full(G.fine_shape, -0.0, dtype)
-    want = cc.prolong_add_cell(got, G.cw, x_f, G.fw, G.axes)
+    want = rst.prolong_add(got, G.cw, x_f, G.fw, Halved(G.axes))
     fd = _dev(nh, x_f, 0)
     nh.mg.prolong_add(G.fine, G.coarse, bd, fd)
     nh.torch.cuda.synchronize()

@@ -1,5 +1,5 @@
 """neptune_hip_mg_solve, neptune_hip_mgcg_solve and their line-stage and mixed-precision forms on cell-centred hierarchies
- against the NumPy restatement of tests/mgcc_cases.py.
+ against the NumPy restatement of tests/mg_restatement.py.
 
 No reduction enters a field, so after any number of cycles x_0 and every level's x_l, b_l must equal the restatement's bit
 for bit, whatever the launch path (plain launches or the replayed graph of one cycle); for MGCG the restatement's recurrences
@@ -22,12 +22,12 @@ import numpy as np
 import pytest
 
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcc_cases as cc
 import mgcgmixed_cases as mx
-import mgfuzz_cases as fz
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
-from mgcc_cases import Halved
+from mg_restatement import Halved
 
 pytestmark = pytest.mark.gpu
 
@@ -113,7 +113,7 @@ def _reference(P, cycles, check_every=1):
     """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
     key = (cycles, check_every)
     if key not in P.runs:
-        rr0, checks = cc.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
+        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
         P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
     return P.runs[key]
 
@@ -135,7 +135,7 @@ def _hierarchy(nh, P, lines=None):
     F = nh.fields.DeviceField
     h = nh.mg.Hierarchy(_levels(nh, P, lines))
     assert h.coarsened == [tuple(R.axes) for R in P.ref[:-1]]
-    assert h.halved == [tuple(R.axes) if isinstance(R.axes, Halved) else () for R in P.ref[:-1]]
+    assert h.halved == [tuple(R.axes) if rst.axes_of(R).halved else () for R in P.ref[:-1]]
     nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
     h.q = [nan(f) for f in h.q]
     h.x = [None] + [nan(f) for f in h.x[1:]]
@@ -213,11 +213,11 @@ def test_stops_where_the_definition_says(nh, check_every, between):
     P = _problem(nh, "stop_f64")
     assert [L.m for L in P.ref] == [(32, 32), (16, 16), (8, 8), (4, 4), (2, 2)]
     if "seq" not in P.runs:
-        P.runs["seq"] = cc.rr_sequence(P.ref, P.x0, P.b, 6)
+        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6)
     seq = P.runs["seq"]
-    tol2 = cc.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_cycles = len(seq) - 1
-    want_done, want_checks = cc.expected_stop(seq, check_every, max_cycles, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
     assert want_done == between[1]
     (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
     print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
@@ -240,7 +240,8 @@ def test_mgcg_replay_from_the_traced_scalars_reproduces_every_field(nh, name, it
     # dot-monitored launch may refuse this many-input apply, and the replay from the traced scalars holds either way
     print(f"counts = {counts}")
     assert (counts[0], counts[1], counts[3]) == ((2, 0, 2) if iters == 2 else (1, 4, 5)), counts
-    rx, rr, rp, rz, checks, rr0_ref, rz0_ref = cc.replay(P.ref, P.x0, P.b, rz0, trace)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, rz0, trace)
+    rx, rr, rp, rz = st.x, st.r, st.p, st.z
     print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
     assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, sums in enumerate(checks):
@@ -261,8 +262,8 @@ def test_mgcg_replay_from_the_traced_scalars_reproduces_every_field(nh, name, it
 def _cg_sequence(P):
     """r . r of the restatement's recurrences (numpy's own sums) down to 1e-16 rr_0, computed once: -> (seq, tol2)"""
     if "cg_seq" not in P.runs:
-        rr0 = cc.numpy_mgcg(P.ref, P.x0, P.b, 0)[0]
-        P.runs["cg_seq"] = (cc.numpy_mgcg(P.ref, P.x0, P.b, 20, stop_at=1e-16 * rr0), 1e-16 * rr0)
+        rr0 = rst.numpy_mgcg(P.ref, P.x0, P.b, 0)[0]
+        P.runs["cg_seq"] = (rst.numpy_mgcg(P.ref, P.x0, P.b, 20, stop_at=1e-16 * rr0), 1e-16 * rr0)
     return P.runs["cg_seq"]
 
 
@@ -306,7 +307,7 @@ def test_mixed_precision_smoke(nh):
     # every field against the composed restatement, driven by the device's scalars: f64 recurrences on the f64 operator
     # around the f32 cycle of the halved hierarchy
     R = mx.Problem(P64.ref[0].A, P32.ref)
-    st, sums, rr0_ref, rz0_ref, _ = fz.replay(R, P64.x0, P64.b, rz0, trace)
+    st, sums, rr0_ref, rz0_ref, _ = rst.replay(R, P64.x0, P64.b, rz0, trace)
     assert trace.shape == (done, 3) and abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, row in enumerate(sums):
         for c, (s, bd) in enumerate(row):
@@ -335,7 +336,7 @@ def test_a_line_stage_on_level_one_smoke(nh, monkeypatch):
     stage = (1,) + lc.factors(-c1, diag, -up_coef, R1.where, 1, DAMP)
     R1.stages = [stage]
     try:
-        ref_rr0, ref_checks = fz.run(P.ref, P.x0, P.b, 4)
+        ref_rr0, ref_checks = rst.run(P.ref, P.x0, P.b, 4)
         ref_x, ref_b = [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref]
     finally:
         del R1.stages

@@ -9,6 +9,7 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcg_cases as mg
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
@@ -203,7 +204,7 @@ def test_the_preconditioner_is_symmetric_positive_definite(sweeps, built_libs):
     16 S eps ||M||_2.  Observed: 5.6e-17 (sweeps = 1) and 4.2e-17 (sweeps = 2) against bounds of 1.1e-13 and 1.3e-13;
     ||M||_2 = 2.66 / 2.73; smallest eigenvalue 0.092 / 0.119."""
     levels, _ = mg.star_levels((7, 7), 2, np.float64, 0.8)
-    M = mg.dense_preconditioner(levels, sweeps=sweeps, coarse_sweeps=8)
+    M = rst.dense_preconditioner(levels, sweeps=sweeps, coarse_sweeps=8)
     assert M.shape == (49, 49) and np.isfinite(M).all()
     norm = np.linalg.norm(M, 2)
     stages = 2 * sweeps + 8 + 2
@@ -231,7 +232,7 @@ def test_rr_falls_by_a_factor_of_four_per_iteration(name, built_libs):
     omega, n_levels, damp, dtype, iters = CONVERGENCE[name]
     levels, _ = mg.star_levels(omega, n_levels, dtype, damp)
     x0, b = mgc.problem_fields(levels[0].shape, levels[0].where, dtype)
-    seq = mg.numpy_mgcg(levels, x0, b, iters)
+    seq = rst.numpy_mgcg(levels, x0, b, iters)
     print(name, [f"{a / c:.1f}" for a, c in zip(seq, seq[1:])])
     assert len(seq) == iters + 1
     for a, c in zip(seq, seq[1:]):
@@ -252,9 +253,9 @@ def test_anisotropic_problem_preconditioned_cg_converges_where_cycles_stall(buil
     b = np.zeros(L0.shape)
     b[L0.where] = helpers.hash_field(L0.shape, np.float64, seed=91)[L0.where]
     x0 = np.zeros(L0.shape)
-    seq = mg.numpy_mgcg(levels, x0, b, ANISO_N, stop_at=0.0)
+    seq = rst.numpy_mgcg(levels, x0, b, ANISO_N, stop_at=0.0)
     reached = next((k for k, v in enumerate(seq) if v <= 1e-16 * seq[0]), None)
-    cycles = mgc.rr_sequence(make(), x0, b, 2 * ANISO_N)
+    cycles = rst.rr_sequence(make(), x0, b, 2 * ANISO_N)
     print(f"preconditioned CG: {reached} iterations; V-cycles: rr / rr_0 = {cycles[-1] / cycles[0]:.3e} after {2 * ANISO_N} cycles")
     assert reached is not None and reached <= ANISO_N
     assert min(cycles) > 1e-16 * cycles[0]

@@ -1,5 +1,5 @@
 """neptune_hip_mg_smooth_dot alone against the NumPy restatement: x bit for bit on every cell, the untouched
-cells outside Omega included (mg_cases.smooth), and the sum of b * x_new over Omega within 2 (n - 1) eps sum |t_i| of the
+cells outside Omega included (mg_restatement.smooth), and the sum of b * x_new over Omega within 2 (n - 1) eps sum |t_i| of the
 exact sum of the restatement's own terms (cg_cases.dot_terms).
 
 Shapes: those of tests/test_mg_kernels_gpu.py -- fine box 9 x 18 x 268 with Omega 7 x 15 x 263 at (1, 2, 3): unequal rims, a
@@ -11,7 +11,7 @@ import pytest
 
 import cg_cases as cc
 import helpers
-import mg_cases as mgc
+import mg_restatement as rst
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
 
@@ -71,7 +71,7 @@ def test_smooth_dot(nh, name, dtype, offset):
     x = _field(box, dtype, 14)
     x[tuple(0 for _ in box)] = np.nan          # a NaN and a -0 outside Omega keep their bits
     x[tuple(n - 1 for n in box)] = -0.0
-    want = mgc.smooth(q, b, minv, x, w)
+    want = rst.smooth(q, b, minv, x, w)
     want_sum, bound = cc.dot_terms(b, want, w)
     level = nh.mg.Level(None, nh.fields.DeviceField.from_numpy(np.zeros(box, dtype)), ([s.start for s in w], [s.stop for s in w]))
     level.minv = _dev(nh, minv, offset)

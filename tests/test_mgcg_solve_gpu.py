@@ -1,5 +1,5 @@
 """neptune_hip_mgcg_solve: conjugate gradients preconditioned with one V-cycle, whose fields never leave the
-device, against the NumPy restatement of tests/mgcg_cases.py.
+device, against the NumPy restatement of tests/mg_restatement.py.
 
 The restatement's recurrences driven by the DEVICE's traced scalars (rz_0 and the rows pq_k, rz_(k+1), rr_(k+1)) must
 reproduce x, r, p, z and every level's x_l, b_l bit for bit, whatever the launch path (plain launches or the replayed graph
@@ -17,8 +17,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import cg_cases
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcg_cases as mg
 import pcg_cases as pc
 import solver_trace_cases as stc
@@ -174,7 +176,8 @@ def _check_replay(nh, P, iters, check_every=1, want_counts=None, offset=0, **kw)
     if want_counts is not None:
         assert R.counts == want_counts, R.counts
     sw = {k: v for k, v in kw.items() if k in ("sweeps", "coarse_sweeps")}
-    x, r, p, z, checks, rr0_ref, rz0_ref = mg.replay(P.ref, P.x0, P.b, R.rz0, trace, **sw)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, R.rz0, trace, **sw)
+    x, r, p, z = st.x, st.r, st.p, st.z
     print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
     assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, sums in enumerate(checks):
@@ -237,11 +240,11 @@ def test_fallback_runs_the_same_iteration(nh):
 def test_stops_where_the_definition_says(nh, name, check_every, between):
     P = _problem(nh, name)
     if "seq" not in P.runs:
-        P.runs["seq"] = mg.numpy_mgcg(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
+        P.runs["seq"] = rst.numpy_mgcg(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
     seq = P.runs["seq"]
-    tol2 = mg.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_iters = len(seq) - 1
-    want_done, want_checks = mg.expected_stop(seq, check_every, max_iters, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_iters, tol2)
     assert want_done == between[1]
     R = _solve(nh, P, max_iters, tol2=tol2, check_every=check_every, trace=False)
     done, rr0, rr_last = R.res
@@ -253,7 +256,7 @@ def test_stops_where_the_definition_says(nh, name, check_every, between):
 
 def test_a_converged_start_runs_no_iteration(nh):
     P = _problem(nh, "3d_f64")
-    rr0_ref = mg.cc.dot_terms(P.b, P.b, P.ref[0].where)          # x0 = 0: r = b on Omega
+    rr0_ref = cg_cases.dot_terms(P.b, P.b, P.ref[0].where)          # x0 = 0: r = b on Omega
     R = _solve(nh, P, 5, tol2=2.0 * rr0_ref[0])
     done, rr0, rr_last, trace = R.res
     assert (done, R.counts, R.rz0, trace.shape) == (0, (0, 0, 0, 0), 0.0, (0, 3))
@@ -278,7 +281,7 @@ def test_more_cells_than_lanes_take_the_grid_stride_loops_round_again(nh):
         P = Problem()
         P.dtype, P.texts = np.float64, nh.texts["big"]
         shapes = mgc.level_shapes(BIG_OMEGA, 2, BIG_RIMS)
-        P.ref = [mgc.Level(mgc.Operator(text), shape, where, mgc.minv_field(shape, where, np.float64, 6.0 / 7.0, outside=0.0 if l == 0 else np.nan),
+        P.ref = [rst.Level(rst.Operator(text), shape, where, mgc.minv_field(shape, where, np.float64, 6.0 / 7.0, outside=0.0 if l == 0 else np.nan),
                            np.float64) for l, (text, (shape, where)) in enumerate(zip(P.texts, shapes))]
         P.others = [[], []]
         nh.cache["big"] = _finish(nh, P)
@@ -310,7 +313,7 @@ def test_two_input_operator_with_a_coefficient_per_level(nh):
         for l, (text, (shape, where), wl) in enumerate(zip(P.texts, shapes, w)):
             minv = np.full(shape, 0.0 if l == 0 else np.nan, dtype)
             minv[where] = (dtype(0.8) / (dtype(12.0) + wl[where])).astype(dtype)     # pcg_module's diagonal is 4 rank + w
-            P.ref.append(mgc.Level(mgc.Operator(text, wl), shape, where, minv, dtype))
+            P.ref.append(rst.Level(rst.Operator(text, wl), shape, where, minv, dtype))
         P.others = [[nh.fields.DeviceField.from_numpy(wl)] for wl in w]
         nh.cache["pcg"] = _finish(nh, P)
     P = nh.cache["pcg"]
@@ -326,8 +329,8 @@ def test_builtin_body_on_level_zero(nh):
     P = Problem()
     P.dtype = dtype
     A0 = lambda u: helpers.oracle_entry("3d7", u)
-    P.ref = [mgc.Level(A0, shapes[0][0], shapes[0][1], mgc.minv_field(shapes[0][0], shapes[0][1], dtype, 0.125, outside=0.0), dtype),
-             mgc.Level(mgc.Operator(nh.texts["builtin"][0]), shapes[1][0], shapes[1][1],
+    P.ref = [rst.Level(A0, shapes[0][0], shapes[0][1], mgc.minv_field(shapes[0][0], shapes[0][1], dtype, 0.125, outside=0.0), dtype),
+             rst.Level(rst.Operator(nh.texts["builtin"][0]), shapes[1][0], shapes[1][1],
                        mgc.minv_field(shapes[1][0], shapes[1][1], dtype, 0.8), dtype)]
     P.entries = [nh.capi.BODY_LAP3D7_F64, _entry(nh, nh.texts["builtin"][0], False)]
     P.others = [[], []]

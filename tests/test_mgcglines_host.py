@@ -1,7 +1,7 @@
 """neptune_hip_mgcg_solve_lines, neptune_hip_mg_line_first and neptune_hip_mg_line_smooth_dot without a GPU: the
 exports and signatures, every new refusal on host pointers (the argument checks run before the device is touched), the
 apply-free stage of the restatement against the plain stage on zero fields, the line-smoothed preconditioner as a dense
-matrix, and the convergence the README's claim rests on -- conditions on the restatement (tests/mgcglines_cases.py), not on
+matrix, and the convergence the README's claim rests on -- conditions on the restatement (tests/mg_restatement.py), not on
 the code under test."""
 import ctypes as C
 import inspect
@@ -9,7 +9,7 @@ import inspect
 import numpy as np
 import pytest
 
-import mgcglines_cases as mlc
+import mg_restatement as rst
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
 from neptune_hip import _capi
@@ -270,13 +270,13 @@ def test_first_stage_is_the_plain_stage_on_zero_fields(axis, dtype):
     b[tuple(cut)] = -0.0
     junk = rng.standard_normal(shape).astype(dtype)
     zeros = np.zeros(shape, dtype)
-    want = lc.line_stage(zeros, b, lo, inv, up, zeros, where, axis)
-    got = mlc.first_stage(b, lo, inv, up, zeros, where, axis)
+    want = rst.line_stage(zeros, b, lo, inv, up, zeros, where, axis)
+    got = rst.first_stage(b, lo, inv, up, zeros, where, axis)
     assert bits_equal(got, want), mismatch_report(got, want)
     assert (got[tuple(cut)] == 0).all() and not np.signbit(got[tuple(cut)]).any()      # whole lines of -0: +0 comes out
     assert np.count_nonzero(got[where]) > 0
     # x on Omega is not read, outside Omega it keeps its bits
-    got = mlc.first_stage(b, lo, inv, up, junk, where, axis)
+    got = rst.first_stage(b, lo, inv, up, junk, where, axis)
     assert bits_equal(got[where], want[where])
     outside = np.ones(shape, bool)
     outside[where] = False
@@ -295,10 +295,10 @@ def test_the_line_smoothed_preconditioner_is_symmetric_positive_definite(sweeps,
     ||M||_2 = 71.0 / 75.6; smallest eigenvalue 0.3292 / 0.3335."""
     levels, _, _ = lc.flux_levels((0, 1), n=17)
     assert [L.m for L in levels] == [(15, 15), (7, 7), (3, 3), (1, 1)]
-    M = mlc.dense_preconditioner(levels, sweeps=sweeps, coarse_sweeps=8)
+    M = rst.dense_preconditioner(levels, sweeps=sweeps, coarse_sweeps=8)
     assert M.shape == (225, 225) and np.isfinite(M).all()
     norm = np.linalg.norm(M, 2)
-    S = mlc.stage_applications(levels, sweeps, 8)
+    S = lc.stage_applications(levels, sweeps, 8)
     assert S == 12 * sweeps + 16
     bound = 16.0 * S * 15 * np.finfo(np.float64).eps * norm
     asym = float(np.abs(M - M.T).max())
@@ -322,10 +322,10 @@ def test_line_smoothed_cg_converges_where_the_point_preconditioner_crawls(built_
     levels, _, _ = lc.flux_levels((0, 1))
     x0, b = lc.flux_problem(levels)
     assert levels[0].m == (63, 63)
-    v11 = mlc.numpy_mgcg(levels, x0, b, 16, sweeps=1, stop_at=0.0)
-    v22 = mlc.numpy_mgcg(levels, x0, b, 10, sweeps=2, stop_at=0.0)
+    v11 = rst.numpy_mgcg(levels, x0, b, 16, sweeps=1, stop_at=0.0)
+    v22 = rst.numpy_mgcg(levels, x0, b, 10, sweeps=2, stop_at=0.0)
     point_levels, _, _ = lc.flux_levels((), outside=0.0)
-    point = mlc.numpy_mgcg(point_levels, x0, b, 20, sweeps=2, stop_at=0.0)
+    point = rst.numpy_mgcg(point_levels, x0, b, 20, sweeps=2, stop_at=0.0)
     print(f"stages V(1,1): {_reached(v11)} iterations; V(2,2): {_reached(v22)}; point V(2,2): rr / rr_0 = {min(point) / point[0]:.3e} after 20")
     assert _reached(v11) is not None and _reached(v11) <= 16
     assert _reached(v22) is not None and _reached(v22) <= 10

@@ -1,5 +1,5 @@
 """The two further forms of the line stage's kernel alone (neptune_hip_mg_line_first, neptune_hip_mg_line_smooth_dot; DESIGN
-3.18) against the NumPy restatement of tests/mgcglines_cases.py and tests/mglines_cases.py: bit for bit on every cell of x,
+3.18) against the NumPy restatement of tests/mg_restatement.py: bit for bit on every cell of x,
 the untouched cells outside Omega included, and q outside Omega; *dot_out within cg_cases.dot_terms' bound -- 2 (n - 1) eps
 sum |t_i|, what two summation orders may differ by -- of the exact sum of its own terms b * x_new.
 
@@ -19,7 +19,7 @@ import pytest
 
 import cg_cases as cc
 import helpers
-import mgcglines_cases as mlc
+import mg_restatement as rst
 import mglines_cases as lc
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
@@ -114,7 +114,7 @@ def test_apply_free_stage_matches_the_restatement_and_the_plain_kernel(nh, name,
     where, q, b, x, (lo, inv, up) = _problem(name, axis, dtype)
     x_nan = x.copy()
     x_nan[where] = np.nan                                             # the stage must not read x on Omega
-    want = mlc.first_stage(b, lo, inv, up, x_nan, where, axis)
+    want = rst.first_stage(b, lo, inv, up, x_nan, where, axis)
     assert np.isfinite(want[where]).all()
     dev = lambda a: stc.offset_field(nh, a, 8 // a.itemsize)          # every field 8 bytes into a larger allocation
     level = _level(nh, x.shape, dtype, where)
@@ -135,7 +135,7 @@ def test_apply_free_stage_matches_the_restatement_and_the_plain_kernel(nh, name,
 @pytest.mark.parametrize("name,axis,dtype", RUNS, ids=IDS)
 def test_stage_with_a_sum_matches_the_restatement(nh, name, axis, dtype):
     where, q, b, x, (lo, inv, up) = _problem(name, axis, dtype)
-    want = lc.line_stage(q, b, lo, inv, up, x, where, axis)
+    want = rst.line_stage(q, b, lo, inv, up, x, where, axis)
     assert np.isfinite(want[where]).all()
     total, bound = cc.dot_terms(b, want, where)
     dev = lambda a: stc.offset_field(nh, a, 8 // a.itemsize)

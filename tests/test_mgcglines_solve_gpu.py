@@ -1,5 +1,5 @@
 """neptune_hip_mgcg_solve_lines: conjugate gradients preconditioned with one line-smoothed V-cycle, against the
-NumPy restatement of tests/mgcglines_cases.py.
+NumPy restatement of tests/mg_restatement.py.
 
 The restatement's recurrences driven by the DEVICE's traced scalars (rz_0 and the rows pq_k, rz_(k+1), rr_(k+1)) must
 reproduce x, r, p, z and every coarser level's x_l, b_l bit for bit, whatever the launch path (plain launches or the replayed
@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 import mg_cases as mgc
-import mgcglines_cases as mlc
+import mg_restatement as rst
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
 
@@ -164,7 +164,8 @@ def _check_replay(nh, P, iters, check_every=1, want_counts=None, **kw):
     if want_counts is not None:
         assert R.counts == want_counts, R.counts
     sw = {k: v for k, v in kw.items() if k in ("sweeps", "coarse_sweeps")}
-    x, r, p, z, checks, rr0_ref, rz0_ref = mlc.replay(P.ref, P.x0, P.b, R.rz0, trace, **sw)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, R.rz0, trace, **sw)
+    x, r, p, z = st.x, st.r, st.p, st.z
     print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
     assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, sums in enumerate(checks):
@@ -240,7 +241,8 @@ def test_without_lines_it_is_mgcg_solve(nh):
                         [tr.cpu().numpy(), x.numpy()] + [f.numpy() for f in work + h.x[1:] + h.b[1:]]))
     first = results[0]
     assert first[0][0] == 5 and first[0][3] == (1, 4, 0, 5)
-    x, r, p, z, _, _, _ = mlc.replay(P.ref, P.x0, P.b, first[0][4], first[1][0].reshape(-1, 3))
+    st, _, _, _, _ = rst.replay(P.ref, P.x0, P.b, first[0][4], first[1][0].reshape(-1, 3))
+    x, r, p, z = st.x, st.r, st.p, st.z
     assert bits_equal(first[1][1], x) and bits_equal(first[1][4], z)
     for other in results[1:]:
         assert other[0] == first[0]
@@ -263,11 +265,11 @@ def test_stops_where_the_definition_says_on_the_flux_hierarchy(nh, check_every, 
     P = _problem(nh, "flux")
     assert [L.m for L in P.ref] == [(63, 63), (31, 31), (15, 15), (7, 7), (3, 3), (1, 1)]
     if "seq" not in P.runs:
-        P.runs["seq"] = mlc.numpy_mgcg(P.ref, P.x0, P.b, 6, sweeps=1)
+        P.runs["seq"] = rst.numpy_mgcg(P.ref, P.x0, P.b, 6, sweeps=1)
     seq = P.runs["seq"]
-    tol2 = mlc.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_iters = len(seq) - 1
-    want_done, want_checks = mlc.expected_stop(seq, check_every, max_iters, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_iters, tol2)
     assert want_done == between[1]
     R = _solve(nh, P, max_iters, tol2=tol2, check_every=check_every, trace=False, sweeps=1)
     done, rr0, rr_last = R.res
@@ -296,7 +298,7 @@ def test_the_keyword_through_the_python_layer(nh):
     assert bits_equal(x.numpy(), P.x0)
     done, rr0, rr_last, trace = nh.mg.cg_solve(h, x, b, sweeps=1, max_iters=3, trace=True, lines=True)
     nh.torch.cuda.synchronize()
-    want = mlc.replay(P.ref, P.x0, P.b, nh.mg.cg_rz0(), trace, sweeps=1)[0]
+    want = rst.replay(P.ref, P.x0, P.b, nh.mg.cg_rz0(), trace, sweeps=1)[0].x
     assert done == 3 and bits_equal(x.numpy(), want), mismatch_report(x.numpy(), want)
     # no stages: the keyword changes nothing
     Q = _problem(nh, "3d_f64_point")

@@ -1,12 +1,13 @@
 """neptune_hip_mgcg_solve_mixed and neptune_hip_mg_smooth_dot_wide without a GPU: the exports and signatures,
 the refusals on host pointers (the argument checks run before the device is touched), and what the claim "an f32 cycle costs
-f64 CG no iteration" rests on -- conditions on the restatement (tests/mgcgmixed_cases.py), not on the code under test."""
+f64 CG no iteration" rests on -- conditions on the restatement (tests/mg_restatement.py), not on the code under test."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import helpers
+import mg_restatement as rst
 import mgcg_cases as mg
 import mgcgmixed_cases as mx
 from neptune_hip import _capi
@@ -245,7 +246,7 @@ def test_the_f32_preconditioner_is_symmetric_positive_definite(built_libs):
     S = 2 sweeps + 8 + 2 stages of at most 16 rounded operations per cell, so two entries differ by at most
     16 S eps32 ||M||_2."""
     P, _, _ = mx.star_problem((7, 7), 2, 0.8)
-    M = mg.dense_preconditioner(P.levels, sweeps=2, coarse_sweeps=8)
+    M = rst.dense_preconditioner(P.levels, sweeps=2, coarse_sweeps=8)
     assert M.shape == (49, 49) and np.isfinite(M).all()
     norm = np.linalg.norm(M, 2)
     bound = 16.0 * (2 * 2 + 8 + 2) * float(np.finfo(np.float32).eps) * norm
@@ -279,7 +280,7 @@ ITERATIONS = {
 @pytest.mark.parametrize("name", sorted(ITERATIONS))
 def test_to_1e_24_the_mixed_loop_needs_at_most_one_iteration_more_than_all_f64(name, built_libs):
     """V(2, 2), 8 coarse sweeps, hashed b, x0 = 0, to rr <= 1e-24 rr_0 -- far below anything f32 can express.  The mixed
-    restatement may need at most one iteration more than mgcg_cases.numpy_mgcg in f64 (an independent experiment found equal
+    restatement may need at most one iteration more than mg_restatement.numpy_mgcg in f64 (an independent experiment found equal
     counts on five problems; the margin of one covers a different summation order), and the true residual b - A(x) of the
     mixed x, by the oracle in f64, must lie within a factor 4 of the recurrence's rr."""
     make, most = ITERATIONS[name]
@@ -287,10 +288,11 @@ def test_to_1e_24_the_mixed_loop_needs_at_most_one_iteration_more_than_all_f64(n
     b = np.zeros(P.shape)
     b[P.where] = helpers.hash_field(P.shape, np.float64, seed=91)[P.where]
     x0 = np.zeros(P.shape)
-    rr0 = mg.numpy_mgcg(levels64, x0, b, 0)[0]
+    rr0 = rst.numpy_mgcg(levels64, x0, b, 0)[0]
     stop = 1e-24 * rr0
-    seq64 = mg.numpy_mgcg(levels64, x0, b, most, stop_at=stop)
-    seq, x = mx.numpy_mgcg_mixed(P, x0, b, most, stop_at=stop)
+    seq64 = rst.numpy_mgcg(levels64, x0, b, most, stop_at=stop)
+    st, _, _, _, scalars = rst.replay(P, x0, b, iters=most, stop_at=stop)       # numpy_mgcg, and its x
+    seq, x = [float(st.rr_own)] + [float(s[2]) for s in scalars], st.x
     true = mx.true_residual(P, x, b)
     print(f"{name}: all-f64 {len(seq64) - 1} iterations (rr / rr_0 = {seq64[-1] / rr0:.3e}), mixed {len(seq) - 1} iterations "
           f"(rr / rr_0 = {seq[-1] / rr0:.3e}); true residual of the mixed x {true:.6e} against the recurrence's {seq[-1]:.6e}")

@@ -1,6 +1,6 @@
 """The kernels at the seam of mixed-precision MGCG against the NumPy restatement.
 
-neptune_hip_mg_smooth_dot_wide alone: x bit for bit the f32 sweep's -- the restatement's (mg_cases.smooth) and the device's own
+neptune_hip_mg_smooth_dot_wide alone: x bit for bit the f32 sweep's -- the restatement's (mg_restatement.smooth) and the device's own
 neptune_hip_mg_smooth --, the untouched cells outside Omega included, and the f64 sum of widen(b) * widen(x_new) over Omega
 within 2 (n - 1) eps64 sum |t_i| of the exact sum of the restatement's own terms.  Shapes: Omega = 5 (a row shorter than a
 wave), 9 x 70 (a wave and six lanes) and 3 x 5 x 300 (a row that crosses the 256-cell chunk: two workgroups per row, one with
@@ -19,6 +19,7 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcgmixed_cases as mx
 from helpers import bits_equal, mismatch_report
 
@@ -90,8 +91,8 @@ def test_smooth_dot_wide(nh, name):
     x = _field(box, 14)
     x[tuple(0 for _ in box)] = np.nan          # a NaN and a -0 outside Omega keep their bits
     x[tuple(n - 1 for n in box)] = -0.0
-    want = mgc.smooth(q, b, minv, x, w)
-    want_sum, bound = mx.wide_dot_terms(b, want, w)
+    want = rst.smooth(q, b, minv, x, w)
+    want_sum, bound = rst.wide_dot_terms(b, want, w)
     level = nh.mg.Level(None, F.from_numpy(np.zeros(box, S)), ([s.start for s in w], [s.stop for s in w]))
     level.minv = F.from_numpy(minv)
     # the f32 sweep alone, on the device
@@ -183,12 +184,12 @@ def _setup_problem(nh, name):
     levels = []
     for l, (text, (box, lo, m)) in enumerate(zip(t32, spec)):
         w = _where(lo, m)
-        levels.append(mgc.Level(mgc.Operator(text), box, w, mgc.minv_field(box, w, S, 0.8, outside=0.0 if l == 0 else np.nan), S))
+        levels.append(rst.Level(rst.Operator(text), box, w, mgc.minv_field(box, w, S, 0.8, outside=0.0 if l == 0 else np.nan), S))
     if len(spec[0][0]) == 2:
         levels[0].axes = (1,)
     entry64 = nh.lowering.compile_module(t64, dot_entries=True).dot_entry("entry")
     entries32 = [nh.lowering.compile_module(t).geom_entry("entry") for t in t32]
-    return mx.Problem(mgc.Operator(t64), levels), entry64, entries32
+    return mx.Problem(rst.Operator(t64), levels), entry64, entries32
 
 
 @pytest.mark.parametrize("with_nan", [True, False], ids=["nan", "inf"])
@@ -204,9 +205,9 @@ def test_the_set_up_narrows_as_the_definition_says(nh, name, with_nan):
     inside[1:1 + 2 * len(values):2] = values             # every other cell of Omega from its second on
     b[P.where] = inside.reshape(b[P.where].shape)
     x0 = np.zeros(P.shape, D)
-    x, r, r32, z32, rr0_ref = mx.store_residual(P, x0, b)
+    x, r, r32, z32, rr0_ref = rst.store_residual(P, x0, b)
     # what the issue states of the restatement itself: from x = 0, r is b on Omega
-    assert bits_equal(r[P.where], b[P.where]) and bits_equal(r32[P.where], mx.narrow(b[P.where]))     # narrow is .astype(float32)
+    assert bits_equal(r[P.where], b[P.where]) and bits_equal(r32[P.where], rst.narrow(b[P.where]))     # narrow is .astype(float32)
     assert np.isinf(r32).sum() == 4 and (np.isnan(r32).sum() == 1) == with_nan
     subnormal = (r32 != 0) & (np.abs(r32) < np.finfo(S).tiny)
     assert subnormal.sum() >= 5 and ((z32 != 0) & (np.abs(z32) < np.finfo(S).tiny)).sum() >= 2

@@ -1,5 +1,5 @@
 """neptune_hip_mgcg_solve_mixed: conjugate gradients in f64 around a V-cycle in f32, whose fields never leave
-the device, against the NumPy restatement of tests/mgcgmixed_cases.py.
+the device, against the NumPy restatement of tests/mg_restatement.py.
 
 The restatement's recurrences driven by the DEVICE's traced scalars (rz_0 and the rows pq_k, rz_(k+1), rr_(k+1)) must
 reproduce x, r, p in f64 and r32, z32 and every level's x_l, b_l in f32 bit for bit, whatever the launch path (plain launches
@@ -20,6 +20,7 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import mgcg_cases as mg
 import mgcgmixed_cases as mx
 import mglines_cases as lc
@@ -138,7 +139,7 @@ def _finish(nh, T, texts, rim=False):
 
 def _star_levels(omega, n_levels, damp, rims, texts32):
     shapes = mgc.level_shapes(omega, n_levels, rims)
-    return [mgc.Level(mgc.Operator(text), shape, where, mgc.minv_field(shape, where, S, damp, outside=0.0 if l == 0 else np.nan), S)
+    return [rst.Level(rst.Operator(text), shape, where, mgc.minv_field(shape, where, S, damp, outside=0.0 if l == 0 else np.nan), S)
             for l, (text, (shape, where)) in enumerate(zip(texts32, shapes))]
 
 
@@ -152,7 +153,7 @@ def _case(nh, name, rim=False, stage_on_level_1=False):
         levels = _star_levels(omega, n_levels, damp, rims, t32)
         if stage_on_level_1:
             levels[1].stages = [lc.star_stage(levels[1], 1, damp)]
-        T.P = mx.Problem(mgc.Operator(t64), levels)
+        T.P = mx.Problem(rst.Operator(t64), levels)
         T.entry64, T.entries32 = None, [None] * n_levels
         nh.cache[key] = _finish(nh, T, (t64, t32), rim)
     return nh.cache[key]
@@ -187,7 +188,8 @@ def _check_replay(nh, T, iters, check_every=1, want_counts=None, offset=0, **kw)
         assert R.counts == want_counts, R.counts
     sw = {k: v for k, v in kw.items() if k in ("sweeps", "coarse_sweeps")}
     P = T.P
-    x, r, p, r32, z32, checks, rr0_ref, rz0_ref = mx.replay(P, T.x0, T.b, R.rz0, trace, **sw)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P, T.x0, T.b, R.rz0, trace, **sw)
+    x, r, p, r32, z32 = st.x, st.r, st.p, st.r32, st.z32
     print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
     assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, sums in enumerate(checks):
@@ -247,11 +249,11 @@ def test_fallback_runs_the_same_iteration(nh):
 def test_stops_where_the_definition_says(nh, name, check_every, between):
     T = _case(nh, name)
     if "seq" not in T.runs:
-        T.runs["seq"] = mx.numpy_mgcg_mixed(T.P, T.x0, T.b, 6)[0]
+        T.runs["seq"] = rst.numpy_mgcg(T.P, T.x0, T.b, 6)
     seq = T.runs["seq"]
-    tol2 = mx.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_iters = len(seq) - 1
-    want_done, want_checks = mx.expected_stop(seq, check_every, max_iters, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_iters, tol2)
     assert want_done == between[1]
     R = _solve(nh, T, max_iters, tol2=tol2, check_every=check_every, trace=False)
     done, rr0, rr_last = R.res
@@ -263,7 +265,7 @@ def test_stops_where_the_definition_says(nh, name, check_every, between):
 
 def test_a_converged_start_runs_no_iteration(nh):
     T = _case(nh, "3d")
-    x, r, r32, z32, rr0_ref = mx.store_residual(T.P, T.x0, T.b)
+    x, r, r32, z32, rr0_ref = rst.store_residual(T.P, T.x0, T.b)
     R = _solve(nh, T, 5, tol2=2.0 * rr0_ref[0])
     done, rr0, rr_last, trace = R.res
     assert (done, R.counts, R.rz0, trace.shape) == (0, (0, 0, 0, 0), 0.0, (0, 3))
@@ -298,7 +300,7 @@ def test_more_cells_than_lanes_take_the_grid_stride_loops_round_again(nh):
     if "big" not in nh.cache:
         t64, t32 = nh.texts["big"]
         T = Case()
-        T.P = mx.Problem(mgc.Operator(t64), _star_levels(BIG_OMEGA, 2, 6.0 / 7.0, BIG_RIMS, t32))
+        T.P = mx.Problem(rst.Operator(t64), _star_levels(BIG_OMEGA, 2, 6.0 / 7.0, BIG_RIMS, t32))
         T.entry64, T.entries32 = None, [None, None]
         nh.cache["big"] = _finish(nh, T, (t64, t32))
     _check_replay(nh, nh.cache["big"], 2, check_every=2, offset=1, sweeps=1, coarse_sweeps=2, want_counts=(2, 0, 0, 1))
@@ -329,9 +331,9 @@ def test_two_input_operator_with_a_coefficient_per_level(nh):
         for l, (text, (shape, where), wl) in enumerate(zip(t32, shapes, w)):
             minv = np.full(shape, 0.0 if l == 0 else np.nan, S)
             minv[where] = (S(0.8) / (S(12.0) + wl[where])).astype(S)     # pcg_module's diagonal is 4 rank + w
-            levels.append(mgc.Level(mgc.Operator(text, wl), shape, where, minv, S))
+            levels.append(rst.Level(rst.Operator(text, wl), shape, where, minv, S))
         T = Case()
-        T.P = mx.Problem(mgc.Operator(t64, w64), levels)
+        T.P = mx.Problem(rst.Operator(t64, w64), levels)
         T.entry64, T.entries32 = None, [None, None]
         F = nh.fields.DeviceField
         T.others64, T.others32 = [F.from_numpy(w64)], [[F.from_numpy(wl)] for wl in w]
@@ -346,9 +348,9 @@ def test_builtin_bodies_on_both_level_zeros(nh):
     operators differ -- any f32 operator may precondition; the replay holds bit for bit whatever it is worth"""
     shapes = mgc.level_shapes(BUILTIN_OMEGA, 2)
     T = Case()
-    levels = [mgc.Level(lambda u: helpers.oracle_entry("3d27", u), shapes[0][0], shapes[0][1],
+    levels = [rst.Level(lambda u: helpers.oracle_entry("3d27", u), shapes[0][0], shapes[0][1],
                         mgc.minv_field(shapes[0][0], shapes[0][1], S, 0.125, outside=0.0), S),
-              mgc.Level(mgc.Operator(nh.texts["builtin"][1][1]), shapes[1][0], shapes[1][1], mgc.minv_field(shapes[1][0], shapes[1][1], S, 0.8), S)]
+              rst.Level(rst.Operator(nh.texts["builtin"][1][1]), shapes[1][0], shapes[1][1], mgc.minv_field(shapes[1][0], shapes[1][1], S, 0.8), S)]
     T.P = mx.Problem(lambda u: helpers.oracle_entry("3d7", u), levels)
     T.entry64 = nh.capi.BODY_LAP3D7_F64
     T.entries32 = [nh.capi.BODY_LAP3D27_F32, _entry(nh, nh.texts["builtin"][1][1], False)]
@@ -363,7 +365,7 @@ def test_semi_coarsened_inner_hierarchy(nh):
         steps = sc.with_axes(SEMI[0], SEMI[1], SEMI[2])
         levels, _ = sc.build_levels(steps, 0.8, S)
         T = Case()
-        T.P = mx.Problem(mgc.Operator(t64), levels)
+        T.P = mx.Problem(rst.Operator(t64), levels)
         T.entry64, T.entries32 = None, [None] * len(levels)
         nh.cache["semi"] = _finish(nh, T, (t64, t32))
     T = nh.cache["semi"]
@@ -384,7 +386,7 @@ def test_reaches_a_residual_beyond_f32s_reach(nh):
     """Omega = 31 x 31 to rr <= 1e-24 rr_0 -- a relative residual of 1e-12, which no f32 field can express -- within the
     iteration count the restatement gives"""
     T = _case(nh, "2d")
-    seq, _ = mx.numpy_mgcg_mixed(T.P, T.x0, T.b, 40, stop_at=0.0)
+    seq = rst.numpy_mgcg(T.P, T.x0, T.b, 40, stop_at=0.0)
     want = next(k for k, v in enumerate(seq) if v <= 1e-24 * seq[0])
     R = _solve(nh, T, want, tol2=1e-24 * seq[0], trace=False)
     done, rr0, rr_last = R.res

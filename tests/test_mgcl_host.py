@@ -1,7 +1,7 @@
 """The linear prolongation on cell-centred pairs without a GPU: the two new exports against the header, every
 refusal on host pointers (the argument checks run before the device is touched), the restatement's prolongation as dense
 matrices, the Python layer's errors, and the convergence the GPU tests and DESIGN's table rely on -- conditions on the
-restatement (tests/mgcl_cases.py), not on the code under test.  On the parent commit the library lacks both exports, so the
+restatement (tests/mg_restatement.py), not on the code under test.  On the parent commit the library lacks both exports, so the
 fixture fails and with it every test that takes it."""
 import ctypes as C
 
@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 import helpers
+import mg_restatement as rst
 import mgcc_cases as cc
 import mgcl_cases as cl
-from mgcc_cases import Halved
-from mgcl_cases import EVEN, ODD, Linear
+from mg_restatement import EVEN, Halved, Linear, ODD
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
 
@@ -152,7 +152,7 @@ def test_the_solve_refuses_on_host_pointers(lib):
 # ---------------------------------------------------------------- the prolongation as dense matrices
 def _line_P(n, rule_lo, rule_hi):
     axes = Linear((0,), ((rule_lo, rule_hi),))
-    return cc.dense(lambda e: cl.prolong_add(e, (slice(0, n // 2),), np.zeros(n), (slice(0, n),), axes), n // 2, n)
+    return cc.dense(lambda e: rst.prolong_add(e, (slice(0, n // 2),), np.zeros(n), (slice(0, n),), axes), n // 2, n)
 
 
 @pytest.mark.parametrize("rule_lo,rule_hi", [(EVEN, EVEN), (ODD, ODD), (EVEN, ODD), (ODD, EVEN)])
@@ -180,7 +180,7 @@ def test_dense_matrix_on_an_8_to_16_line(rule_lo, rule_hi):
     if rule_lo == ODD:
         assert (P @ (2.0 * np.arange(8) + 1.0))[0] == 0.5
     # P is not a multiple of the averaging restriction's transpose: the cycle is not a symmetric preconditioner
-    R = cc.dense(lambda e: cc.restrict_cell(e, np.zeros(16), (slice(0, 16),), 1.0, np.zeros(8), np.zeros(8), (slice(0, 8),), Halved((0,)))[0],
+    R = cc.dense(lambda e: rst.restrict(e, np.zeros(16), (slice(0, 16),), 1.0, np.zeros(8), np.zeros(8), (slice(0, 8),), Halved((0,)))[0],
                  16, 8)
     assert not np.array_equal(P, 2.0 * R.T)
 
@@ -202,7 +202,7 @@ def test_tensor_product_against_einsum_on_dyadic_data():
     e = np.full(cshape, np.nan)
     e[cw] = rng.integers(-64, 64, cm) / 8.0                    # dyadic: every product with 3/4, 1/4 and every sum is exact
     x_f = np.full(fshape, 7.0)
-    got = cl.prolong_add(e, cw, x_f, fw, Linear((0, 2), rim))
+    got = rst.prolong_add(e, cw, x_f, fw, Linear((0, 2), rim))
     P0, P2 = _line_P(4, *rim[0]), _line_P(8, *rim[2])
     assert np.array_equal(got[fw], 7.0 + np.einsum("ia,kc,ajc->ijk", P0, P2, e[cw]))
     outside = np.ones(fshape, bool)
@@ -212,7 +212,7 @@ def test_tensor_product_against_einsum_on_dyadic_data():
     # edge rows, (3/4 - 1/4) (3/4 - 1/4) = 1/4 for two ODD faces
     one = np.zeros((2, 2))
     one[0, 0] = 1.0
-    corner = cl.prolong_add(one, (slice(0, 2),) * 2, np.zeros((4, 4)), (slice(0, 4),) * 2, Linear((0, 1), ((ODD, EVEN), (ODD, EVEN))))
+    corner = rst.prolong_add(one, (slice(0, 2),) * 2, np.zeros((4, 4)), (slice(0, 4),) * 2, Linear((0, 1), ((ODD, EVEN), (ODD, EVEN))))
     assert corner[0, 0] == 0.25 and corner[0, 1] == 0.5 * 0.75 and corner[1, 1] == 0.75 * 0.75 and corner[3, 3] == 0.0
 
 
@@ -221,11 +221,11 @@ def test_the_dispatch_of_the_restatement():
     d = helpers.hash_field((14,), np.float64, seed=5)
     w14, w7 = (slice(0, 14),), (slice(0, 7),)
     lin = Linear((0,), ((EVEN, ODD),))
-    assert isinstance(lin, Halved) and lin == (0,) and lin.rim == ((EVEN, ODD),)
-    b7, _ = cl.restrict(d, np.zeros(14), w14, 1.0, np.zeros(7), np.zeros(7), w7, lin)
+    assert lin.halved and lin == (0,) and lin.rim == ((EVEN, ODD),)
+    b7, _ = rst.restrict(d, np.zeros(14), w14, 1.0, np.zeros(7), np.zeros(7), w7, lin)
     assert np.array_equal(b7, 0.5 * (d[0::2] + d[1::2]))
-    assert np.array_equal(cl.prolong_add(b7, w7, np.zeros(14), w14, Halved((0,))), np.repeat(b7, 2))
-    got = cl.prolong_add(b7, w7, np.zeros(14), w14, lin)
+    assert np.array_equal(rst.prolong_add(b7, w7, np.zeros(14), w14, Halved((0,))), np.repeat(b7, 2))
+    got = rst.prolong_add(b7, w7, np.zeros(14), w14, lin)
     assert got[0] == 0.75 * b7[0] + 0.25 * b7[0] and got[13] == 0.75 * b7[6] + 0.25 * -b7[6]
     assert got[5] == 0.75 * b7[2] + 0.25 * b7[3] and got[6] == 0.75 * b7[3] + 0.25 * b7[2]
 
@@ -339,11 +339,11 @@ def _sequence(omega, faces, linear, cycles=8):
     faces = _mixed(len(omega)) if faces == "mixed" else faces
     steps = cc.plan(omega)
     if linear:
-        steps = cl.linear_steps(steps, cl.rim_of(faces, len(omega)))
+        steps = cl.linear_steps(steps, rst.rim_of(faces, len(omega)))
     levels, _, _ = cl.flux_levels(steps, 0.8, np.float64, faces)
     assert levels[-1].m == (2,) * len(omega)
     x0, b = cl.problem(levels, faces)
-    return cl.rr_sequence(levels, x0, b, cycles)
+    return rst.rr_sequence(levels, x0, b, cycles)
 
 
 @pytest.mark.parametrize("omega,faces", list(SMALLEST), ids=[f"{len(o)}d-{f}" for o, f in SMALLEST])

@@ -1,5 +1,5 @@
 """The linear prolongation kernel of a cell-centred pair alone (neptune_hip_mg_prolong_add_linear) against the
-NumPy restatement of tests/mgcl_cases.py: bit for bit on every cell of the fine field, the untouched cells outside Omega
+NumPy restatement of tests/mg_restatement.py: bit for bit on every cell of the fine field, the untouched cells outside Omega
 included.  On the parent commit the library lacks the export, so every test here fails there.
 
 Shapes: those of test_mgcc_kernels_gpu.py -- rank 3, fine box 9 x 18 x 268, Omega 6 x 14 x 262 at (1, 2, 3) onto 3 x 7 x 131 under
@@ -23,11 +23,10 @@ import numpy as np
 import pytest
 
 import helpers
-import mgcc_cases as cc
-import mgcl_cases as cl
+import mg_restatement as rst
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
-from mgcl_cases import EVEN, ODD
+from mg_restatement import EVEN, Halved, Linear, ODD
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +53,7 @@ IDS = lambda runs: [f"{n}-{np.dtype(d).name}" + ("-offset" if o else "") for n, 
 def _rim(name, complemented):
     rank = len(CASES[name][0])
     rim = (PATTERN * 2)[3 - rank + (1 if name == "thin" else 0):][:rank]       # `thin` shifted: another face meets ODD first
-    return cl.complement(rim) if complemented else tuple(rim)
+    return rst.complement(rim) if complemented else tuple(rim)
 
 
 def test_the_cases_reach_every_form():
@@ -138,7 +137,7 @@ def _run(nh, name, dtype, offset, complemented):
     x_c = _field(G.coarse_shape, dtype, 31, G.cw)             # no coarse cell outside the coarse Omega is read
     x_f = _field(G.fine_shape, dtype, 32, G.fw)               # no fine cell outside the fine Omega is written
     assert np.isfinite(x_c[G.cw]).all() and np.signbit(x_c[G.cw][x_c[G.cw] == 0]).any()
-    want = cl.prolong_add_linear(x_c, G.cw, x_f, G.fw, G.axes, rim)
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Linear(G.axes, rim))
     xd = _dev(nh, x_f, offset)
     nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()
@@ -165,7 +164,7 @@ def test_minus_zero_and_the_exact_sign_flip(nh, dtype):
     x_c = np.full(G.coarse_shape, np.nan, dtype)
     x_c[G.cw] = -0.0
     x_f = np.full(G.fine_shape, -0.0, dtype)
-    want = cl.prolong_add_linear(x_c, G.cw, x_f, G.fw, G.axes, rim)
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Linear(G.axes, rim))
     fd = _dev(nh, x_f, 0)
     nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, 0), fd)
     nh.torch.cuda.synchronize()
@@ -200,7 +199,7 @@ def test_kind_constant_and_unread_rules(nh):
     assert lib.neptune_hip_mg_prolong_add_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(p), _dev(nh, x_c, 0).ptr, xd.ptr,
                                                  None) == nh.capi.OK
     nh.torch.cuda.synchronize()
-    want = cc.prolong_add_cell(x_c, G.cw, x_f, G.fw, G.axes)
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Halved(G.axes))
     assert bits_equal(xd.numpy(), want), mismatch_report(xd.numpy(), want)
     p.kind = nh.capi.MG_PROLONG_LINEAR
     p.rim_lo[0], p.rim_hi[0], p.rim_lo[1], p.rim_hi[1] = ODD, EVEN, EVEN, ODD
@@ -208,7 +207,7 @@ def test_kind_constant_and_unread_rules(nh):
     assert lib.neptune_hip_mg_prolong_add_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(p), _dev(nh, x_c, 0).ptr, xd.ptr,
                                                  None) == nh.capi.OK
     nh.torch.cuda.synchronize()
-    want = cl.prolong_add_linear(x_c, G.cw, x_f, G.fw, G.axes, ((ODD, EVEN), (EVEN, ODD)))
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Linear(G.axes, ((ODD, EVEN), (EVEN, ODD))))
     assert bits_equal(xd.numpy(), want), mismatch_report(xd.numpy(), want)
 
 

@@ -3,7 +3,7 @@ of tests/mgcl_cases.py.
 
 No reduction enters a field, so after any number of cycles x_0 and every level's x_l, b_l must equal the restatement's bit
 for bit, whatever the launch path (plain launches or the replayed graph of one cycle).  rr_0 and every rr read after a block
-must lie within 2 (n - 1) eps sum |t_i| of the exact sum of the restatement's own terms (mg_cases' bound).
+must lie within 2 (n - 1) eps sum |t_i| of the exact sum of the restatement's own terms (monitor_cases.reference_sum's bound).
 
 Operators, one lowered module per level: mgcc_cases.flux_module (face coefficients, and a diagonal field where a face is
 Dirichlet), or, where that would take a fifth input -- rank 3 with a Dirichlet face --, mgcl_cases.star_s_module, the same
@@ -20,12 +20,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import mg_restatement as rst
 import mgcc_cases as cc
 import mgcl_cases as cl
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
-from mgcc_cases import Halved
-from mgcl_cases import EVEN, ODD, Linear
+from mg_restatement import EVEN, Halved, ODD
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,7 @@ FACE = {EVEN: "neumann", ODD: "dirichlet"}
 
 
 def _steps(omega, pairs, faces, only=None):
-    return cl.linear_steps(cc.halved_steps(omega, pairs), cl.rim_of(faces, len(omega)), only)
+    return cl.linear_steps(cc.halved_steps(omega, pairs), rst.rim_of(faces, len(omega)), only)
 
 
 # name: (the steps [(extents, weights, axes)], faces, dtype, the operator's form: mgcl_cases.flux_levels or .star_levels)
@@ -47,7 +47,7 @@ PROBLEMS = {
     "first_f64": (_steps((16, 264), [ALL2, ALL2], "dirichlet", only={0}), "dirichlet", np.float64, cl.flux_levels),
     "kept_f64": (_steps((8, 264), [Halved((1,)), ALL2], MIX2), MIX2, np.float64, cl.flux_levels),
     "switch_f64": (_steps((14, 14), [ALL2, (0, 1)], "dirichlet"), "dirichlet", np.float64, cl.flux_levels),
-    "stop_f64": (cl.linear_steps(cc.plan((32, 32, 32)), cl.rim_of("dirichlet", 3)), "dirichlet", np.float64, cl.star_levels),
+    "stop_f64": (cl.linear_steps(cc.plan((32, 32, 32)), rst.rim_of("dirichlet", 3)), "dirichlet", np.float64, cl.star_levels),
 }
 DAMP = 0.8
 
@@ -112,7 +112,7 @@ def _reference(P, cycles, check_every=1):
     """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
     key = (cycles, check_every)
     if key not in P.runs:
-        rr0, checks = cl.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
+        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
         P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
     return P.runs[key]
 
@@ -128,13 +128,13 @@ def _hierarchy(nh, P, lines=None, constant=False):
         others = [F.from_numpy(a) for a in P.rests[l]]
         stages = lines(l, P.entries[l], like, bounds, others) if lines else ()
         setting = {}
-        if isinstance(R.axes, Linear) and not constant:
+        if rst.axes_of(R).prolong == "linear" and not constant:
             setting = dict(prolong="linear", faces=[(FACE[lo], FACE[hi]) for lo, hi in R.axes.rim])
         levels.append(nh.mg.Level(P.entries[l], like, bounds, others=others, minv=F.from_numpy(R.minv), rscale=R.rscale, lines=stages,
                                   **setting))
     h = nh.mg.Hierarchy(levels)
-    assert h.halved == [tuple(R.axes) if isinstance(R.axes, Halved) else () for R in P.ref[:-1]]
-    assert [L.linear for L in h.levels[:-1]] == [isinstance(R.axes, Linear) and not constant for R in P.ref[:-1]]
+    assert h.halved == [tuple(R.axes) if rst.axes_of(R).halved else () for R in P.ref[:-1]]
+    assert [L.linear for L in h.levels[:-1]] == [rst.axes_of(R).prolong == "linear" and not constant for R in P.ref[:-1]]
     nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
     h.q = [nan(f) for f in h.q]
     h.x = [None] + [nan(f) for f in h.x[1:]]
@@ -181,13 +181,13 @@ def test_cycles_match_the_restatement(nh, name, cycles):
     P = _problem(nh, name)
     assert [L.m for L in P.ref] == ([(8, 16, 264), (4, 8, 132), (2, 4, 66)] if name.startswith("3d") else
                                     [(16, 264), (8, 132), (4, 66)])
-    assert all(isinstance(L.axes, Linear) for L in P.ref[:-1])
+    assert all(L.axes.halved and L.axes.prolong == "linear" for L in P.ref[:-1])
     _check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
 
 
 def test_linear_on_the_first_pair_and_constant_on_the_second(nh):
     P = _problem(nh, "first_f64")
-    assert [type(L.axes) for L in P.ref[:-1]] == [Linear, Halved]
+    assert [(rst.axes_of(L).kind, rst.axes_of(L).prolong, rst.axes_of(L).restrict) for L in P.ref[:-1]] == [("halved", "linear", "average"), ("halved", "constant", "average")]
     _check_against_reference(nh, P, 3)
     # and it is neither all-linear nor all-constant
     x_first = _reference(P, 3)[2][0]
@@ -203,7 +203,7 @@ def test_a_halved_plus_kept_pair(nh):
 def test_linear_on_the_halved_pair_of_a_hierarchy_that_changes_its_grid_kind(nh):
     """Omega 14 -> 7 -> 3: the first pair halved and linear, the second vertex-centred"""
     P = _problem(nh, "switch_f64")
-    assert [L.m for L in P.ref] == [(14, 14), (7, 7), (3, 3)] and [type(L.axes) for L in P.ref[:-1]] == [Linear, tuple]
+    assert [L.m for L in P.ref] == [(14, 14), (7, 7), (3, 3)] and [(rst.axes_of(L).kind, rst.axes_of(L).prolong, rst.axes_of(L).restrict) for L in P.ref[:-1]] == [("halved", "linear", "average"), ("coarsened", "constant", "average")]
     _check_against_reference(nh, P, 3)
 
 
@@ -235,7 +235,7 @@ def test_a_line_stage_on_level_one(nh, monkeypatch):
     diag = cc.face_fields(R1.m, P.dtype, P.faces, R1.weights)[1]
     R1.stages = [(1,) + lc.factors(-c1, diag, -up_coef, R1.where, 1, DAMP)]
     try:
-        ref_rr0, ref_checks = cl.lines_run(P.ref, P.x0, P.b, 4)
+        ref_rr0, ref_checks = rst.run(P.ref, P.x0, P.b, 4)
         ref = (ref_rr0, ref_checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
     finally:
         del R1.stages
@@ -315,10 +315,10 @@ def test_stops_where_the_definition_says_and_before_constant_prolongation(nh):
     restatement's expected_stop; with constant prolongation the same hierarchy has not got there two cycles later"""
     P = _problem(nh, "stop_f64")
     assert [L.m for L in P.ref] == [(32,) * 3, (16,) * 3, (8,) * 3, (4,) * 3, (2,) * 3]
-    seq = cl.rr_sequence(P.ref, P.x0, P.b, 7)
-    tol2 = cl.tol_between(seq, 5, 6)
+    seq = rst.rr_sequence(P.ref, P.x0, P.b, 7)
+    tol2 = rst.tol_between(seq, 5, 6)
     max_cycles = len(seq) - 1
-    want_done, want_checks = cl.expected_stop(seq, 1, max_cycles, tol2)
+    want_done, want_checks = rst.expected_stop(seq, 1, max_cycles, tol2)
     assert want_done == 6
     (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2)
     print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")

@@ -1,7 +1,7 @@
 """The transposed linear restriction on cell-centred pairs without a GPU: the four new exports against the
 header, every refusal on host pointers (the argument checks run before the device is touched), the restatement's restriction
 as dense matrices against the transpose of mgcl_cases' prolongation, the symmetry of the restated cycle, the Python layer's
-errors, and the iteration table DESIGN 3.23 records -- conditions on the restatement (tests/mgcs_cases.py), not on the code
+errors, and the iteration table DESIGN 3.23 records -- conditions on the restatement (tests/mg_restatement.py), not on the code
 under test.  On the parent commit the library lacks the exports, so the fixture fails and with it every test that takes it."""
 import ctypes as C
 
@@ -9,12 +9,11 @@ import numpy as np
 import pytest
 
 import helpers
+import mg_restatement as rst
 import mgcc_cases as cc
 import mgcl_cases as cl
 import mgcs_cases as cs
-from mgcc_cases import Halved
-from mgcl_cases import EVEN, ODD
-from mgcs_cases import Transfers
+from mg_restatement import EVEN, Halved, ODD, Transfers
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
 
@@ -240,12 +239,12 @@ def test_the_solves_refuse_on_host_pointers(lib, entry):
 def _line_R(n, rule_lo, rule_hi):
     axes = Transfers((0,), ((rule_lo, rule_hi),))
     w_f, w_c = (slice(0, n),), (slice(0, n // 2),)
-    return cc.dense(lambda e: cs.restrict(e, np.zeros(n), w_f, 1.0, np.zeros(n // 2), np.zeros(n // 2), w_c, axes)[0], n, n // 2)
+    return cc.dense(lambda e: rst.restrict(e, np.zeros(n), w_f, 1.0, np.zeros(n // 2), np.zeros(n // 2), w_c, axes)[0], n, n // 2)
 
 
 def _line_P(n, rule_lo, rule_hi):
-    axes = cl.Linear((0,), ((rule_lo, rule_hi),))
-    return cc.dense(lambda e: cl.prolong_add(e, (slice(0, n // 2),), np.zeros(n), (slice(0, n),), axes), n // 2, n)
+    axes = rst.Linear((0,), ((rule_lo, rule_hi),))
+    return cc.dense(lambda e: rst.prolong_add(e, (slice(0, n // 2),), np.zeros(n), (slice(0, n),), axes), n // 2, n)
 
 
 @pytest.mark.parametrize("rule_lo,rule_hi", RULE_PAIRS)
@@ -294,8 +293,8 @@ def test_transposition_and_tensor_product_on_dyadic_data(fm, axes, rim):
     q[fw] = 0.0
     e = np.zeros(cshape)
     e[cw] = _dyadic(rng, cm)
-    b_c, x_c = cs.restrict(f, q, fw, 1.0, np.full(cshape, 7.0), np.full(cshape, 9.0), cw, marker)
-    Pe = cs.prolong_add(e, cw, np.zeros(fshape), fw, marker)
+    b_c, x_c = rst.restrict(f, q, fw, 1.0, np.full(cshape, 7.0), np.full(cshape, 9.0), cw, marker)
+    Pe = rst.prolong_add(e, cw, np.zeros(fshape), fw, marker)
     assert float(np.sum(Pe[fw] * f[fw])) == 2.0 ** k * float(np.sum(e[cw] * b_c[cw]))
     outside = np.ones(cshape, bool)
     outside[cw] = False
@@ -307,7 +306,7 @@ def test_transposition_and_tensor_product_on_dyadic_data(fm, axes, rim):
         want = np.einsum("ia,jb,kc,abc->ijk", *mats, f[fw])
     assert np.array_equal(b_c[cw], want)
     # rscale enters as one exact scaling here
-    b4, _ = cs.restrict(f, q, fw, 4.0, np.full(cshape, 7.0), np.full(cshape, 9.0), cw, marker)
+    b4, _ = rst.restrict(f, q, fw, 4.0, np.full(cshape, 7.0), np.full(cshape, 9.0), cw, marker)
     assert np.array_equal(b4[cw], 4.0 * want)
 
 
@@ -316,7 +315,7 @@ def test_the_ghost_is_an_exact_sign_flip_and_keeps_minus_zero():
     other coarse cell, the high one with its EVEN ghost -0 included, adds -0 only and stays -0"""
     d = np.full(8, -0.0)
     w8, w4 = (slice(0, 8),), (slice(0, 4),)
-    b, x = cs.restrict(d, np.zeros(8), w8, 1.0, np.ones(4), np.ones(4), w4, Transfers((0,), ((ODD, EVEN),)))
+    b, x = rst.restrict(d, np.zeros(8), w8, 1.0, np.ones(4), np.ones(4), w4, Transfers((0,), ((ODD, EVEN),)))
     assert list(np.signbit(b)) == [False, True, True, True] and (b == 0).all()
     assert (x == 0).all() and not np.signbit(x).any()
     # the corner weight in two dimensions is the product of the two end rows: the ghost of the later dimension is +- the
@@ -324,11 +323,11 @@ def test_the_ghost_is_an_exact_sign_flip_and_keeps_minus_zero():
     one = np.zeros((4, 4))
     one[0, 0] = 1.0
     w44, w22 = (slice(0, 4),) * 2, (slice(0, 2),) * 2
-    corner, _ = cs.restrict(one, np.zeros((4, 4)), w44, 1.0, np.zeros((2, 2)), np.zeros((2, 2)), w22,
+    corner, _ = rst.restrict(one, np.zeros((4, 4)), w44, 1.0, np.zeros((2, 2)), np.zeros((2, 2)), w22,
                             Transfers((0, 1), ((ODD, EVEN), (ODD, EVEN))))
     assert corner[0, 0] == 0.25 * 0.25 and corner[0, 1] == 0.0 and corner[1, 1] == 0.0
     one[0, 0], one[3, 3] = 0.0, 1.0
-    corner, _ = cs.restrict(one, np.zeros((4, 4)), w44, 1.0, np.zeros((2, 2)), np.zeros((2, 2)), w22,
+    corner, _ = rst.restrict(one, np.zeros((4, 4)), w44, 1.0, np.zeros((2, 2)), np.zeros((2, 2)), w22,
                             Transfers((0, 1), ((ODD, EVEN), (ODD, EVEN))))
     assert corner[1, 1] == 0.5 * 0.5
 
@@ -341,21 +340,21 @@ def test_the_dispatch_of_the_restatement():
     args = (d, np.zeros(14), w14, 1.0, np.zeros(7), np.zeros(7), w7)
     avg = 0.5 * (d[0::2] + d[1::2])
     sym = Transfers((0,), rim)
-    assert isinstance(sym, Halved) and sym == (0,) and sym.rim == rim and sym.symmetric
+    assert sym.halved and sym == (0,) and sym.rim == rim and sym.symmetric
     assert not Transfers((0,), rim, "constant", "linear").symmetric and Transfers((0,), rim, "constant", "average").symmetric
-    assert np.array_equal(cs.restrict(*args, Halved((0,)))[0], avg)
-    assert np.array_equal(cs.restrict(*args, cl.Linear((0,), rim))[0], avg)
-    assert np.array_equal(cs.restrict(*args, Transfers((0,), rim, "linear", "average"))[0], avg)
-    got = cs.restrict(*args, sym)[0]
+    assert np.array_equal(rst.restrict(*args, Halved((0,)))[0], avg)
+    assert np.array_equal(rst.restrict(*args, rst.Linear((0,), rim))[0], avg)
+    assert np.array_equal(rst.restrict(*args, Transfers((0,), rim, "linear", "average"))[0], avg)
+    got = rst.restrict(*args, sym)[0]
     assert got[2] == 0.5 * ((0.25 * d[3] + 0.75 * d[4]) + (0.75 * d[5] + 0.25 * d[6]))
     assert got[0] == 0.5 * ((0.25 * d[0] + 0.75 * d[0]) + (0.75 * d[1] + 0.25 * d[2]))
     assert got[6] == 0.5 * ((0.25 * d[11] + 0.75 * d[12]) + (0.75 * d[13] + 0.25 * -d[13]))
-    assert np.array_equal(cs.restrict(*args, Transfers((0,), rim, "constant", "linear"))[0], got)
+    assert np.array_equal(rst.restrict(*args, Transfers((0,), rim, "constant", "linear"))[0], got)
     e = got
-    assert np.array_equal(cs.prolong_add(e, w7, np.zeros(14), w14, Transfers((0,), rim, "constant", "linear")), np.repeat(e, 2))
-    assert np.array_equal(cs.prolong_add(e, w7, np.zeros(14), w14, sym), cl.prolong_add(e, w7, np.zeros(14), w14, cl.Linear((0,), rim)))
-    assert cs.transfer_of(sym, 1) == (1, 1, [EVEN], [ODD]) and cs.transfer_of(Halved((0,)), 2) == (0, 0, [0, 0], [0, 0])
-    assert cs.transfer_of(cl.Linear((0,), rim), 1) == (1, 0, [EVEN], [ODD])
+    assert np.array_equal(rst.prolong_add(e, w7, np.zeros(14), w14, Transfers((0,), rim, "constant", "linear")), np.repeat(e, 2))
+    assert np.array_equal(rst.prolong_add(e, w7, np.zeros(14), w14, sym), rst.prolong_add(e, w7, np.zeros(14), w14, rst.Linear((0,), rim)))
+    assert rst.transfer_of(sym, 1) == (1, 1, [EVEN], [ODD]) and rst.transfer_of(Halved((0,)), 2) == (0, 0, [0, 0], [0, 0])
+    assert rst.transfer_of(rst.Linear((0,), rim), 1) == (1, 0, [EVEN], [ODD])
 
 
 # ---------------------------------------------------------------- the restated cycle is a symmetric positive preconditioner
@@ -375,20 +374,19 @@ def test_the_restated_cycle_is_a_symmetric_positive_preconditioner(faces):
     """z = M(r), one V(2, 2) cycle from z = 0 with the symmetric linear pair on every pair: u . M(v) = v . M(u) to rounding and
     u . M(u) > 0 on random vectors -- the check test_mgcc_host.py makes for the constant pair, with its bound; the
     linear / averaging pair of DESIGN 3.22 misses that bound by orders of magnitude"""
-    import mgcg_cases as mg
     f = _faces(faces, 2)
-    rim = cl.rim_of(f, 2)
+    rim = rst.rim_of(f, 2)
     rng = np.random.default_rng(7)
 
     def asymmetry(steps):
         levels, _, _ = cs.flux_levels(steps, 0.8, np.float64, f)
         L0 = levels[0]
-        mg.start(levels)
+        rst.start(levels)
         worst = 0.0
         for _ in range(4):
             u, v = np.zeros(L0.shape), np.zeros(L0.shape)
             u[L0.where], v[L0.where] = rng.standard_normal(L0.m), rng.standard_normal(L0.m)
-            Mu, Mv = cs.precondition(levels, u).copy(), cs.precondition(levels, v).copy()
+            Mu, Mv = rst.precondition(levels, u).copy(), rst.precondition(levels, v).copy()
             uMv, vMu = float(np.sum(u * Mv)), float(np.sum(v * Mu))
             assert float(np.sum(u * Mu)) > 0 and float(np.sum(v * Mv)) > 0
             worst = max(worst, abs(uMv - vMu) / float(np.sqrt(np.sum(u * u) * np.sum(Mv * Mv))))
@@ -481,7 +479,7 @@ def test_cg_solve_accepts_the_symmetric_pair_and_refuses_the_others(no_device_fi
 
 
 # ---------------------------------------------------------------- the iteration table of DESIGN 3.23
-# cg_solve restated (mgcs_cases.numpy_mgcg: the project's bit-exact cycle, numpy's own sums for the scalars), f64, mgcc_cases'
+# cg_solve restated (mg_restatement.numpy_mgcg: the project's bit-exact cycle, numpy's own sums for the scalars), f64, mgcc_cases'
 # flux-form levels on the plan rule's hierarchy down to extent 2, damped Jacobi with omega = 0.8 in two dimensions and 6 / 7
 # in three, 8 coarse sweeps, x = 0, b hashed: the first iteration with r . r <= 1e-16 rr_0.  "mixed": Dirichlet on the low face
 # of dimension 0 and on the high face of the last dimension, Neumann elsewhere.  The symmetric pair carries the rules matched
@@ -503,7 +501,7 @@ def test_the_iteration_table(omega, faces, sweeps):
     damp = 0.8 if rank == 2 else 6.0 / 7.0
     steps = cc.plan(omega)
     constant = cs.mgcg_iterations(steps, f, damp, sweeps)
-    symmetric = cs.mgcg_iterations(cs.transfer_steps(steps, cl.rim_of(f, rank)), f, damp, sweeps)
+    symmetric = cs.mgcg_iterations(cs.transfer_steps(steps, rst.rim_of(f, rank)), f, damp, sweeps)
     print(f"{omega} {faces} V({sweeps},{sweeps}): constant {constant}, symmetric linear {symmetric}")
     assert (constant, symmetric) == ITERATIONS[(omega, faces, sweeps)]
     assert symmetric <= constant

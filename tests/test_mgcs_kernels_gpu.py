@@ -1,5 +1,5 @@
 """The transposed linear restriction kernel of a cell-centred pair alone (neptune_hip_mg_restrict_linear)
-against the NumPy restatement of tests/mgcs_cases.py: bit for bit on every cell of b_c and x_c, the untouched cells outside the
+against the NumPy restatement of tests/mg_restatement.py: bit for bit on every cell of b_c and x_c, the untouched cells outside the
 coarse Omega included.  On the parent commit the library lacks the export, so every test here fails there.
 
 Shapes: those of test_mgcl_kernels_gpu.py -- rank 3, fine box 9 x 18 x 268, Omega 6 x 14 x 262 at (1, 2, 3) onto 3 x 7 x 131 under
@@ -21,12 +21,10 @@ import numpy as np
 import pytest
 
 import helpers
-import mgcc_cases as cc
-import mgcl_cases as cl
-import mgcs_cases as cs
+import mg_restatement as rst
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
-from mgcl_cases import EVEN, ODD
+from mg_restatement import EVEN, Halved, ODD, Transfers
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +53,7 @@ IDS = lambda runs: [f"{n}-{np.dtype(d).name}" + ("-offset" if o else "") for n, 
 def _rim(name, complemented):
     rank = len(CASES[name][0])
     rim = (PATTERN * 2)[3 - rank + (1 if name == "thin" else 0):][:rank]       # `thin` shifted: another face meets ODD first
-    return cl.complement(rim) if complemented else tuple(rim)
+    return rst.complement(rim) if complemented else tuple(rim)
 
 
 def _coarse(name):
@@ -127,7 +125,7 @@ class Geometry:
         self.cw = tuple(slice(l, l + m) for l, m in zip(clo, cm))
         like = lambda shape: nh.fields.DeviceField.from_numpy(np.zeros(shape, dtype))
         bounds = lambda w: ([s.start for s in w], [s.stop for s in w])
-        setting = {} if rim is None else dict(restrict="linear", faces=cs.faces_of(rim))
+        setting = {} if rim is None else dict(restrict="linear", faces=rst.faces_of(rim))
         # the levels carry geometry only here (entry None: the kernel alone never calls the operator)
         self.fine = nh.mg.Level(None, like(fbox), bounds(self.fw), rscale=RSCALE, **setting)
         self.coarse = nh.mg.Level(None, like(cbox), bounds(self.cw))
@@ -164,7 +162,7 @@ def _run(nh, name, dtype, offset, complemented):
     G = Geometry(nh, name, dtype, rim)
     assert nh.mg.halved_axes(G.fine, G.coarse) == G.axes
     b_f, q_f, b_c, x_c = _inputs(G, dtype)
-    want_b, want_x = cs.restrict_linear(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, G.axes, rim)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, Transfers(G.axes, rim))
     bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
@@ -194,7 +192,7 @@ def test_minus_zero_and_the_exact_sign_flip(nh, dtype):
     b_f, q_f = np.full(G.fine_shape, np.nan, dtype), np.full(G.fine_shape, np.nan, dtype)
     b_f[G.fw], q_f[G.fw] = -0.0, 0.0
     ones = np.ones(G.coarse_shape, dtype)
-    want_b, want_x = cs.restrict_linear(b_f, q_f, G.fw, RSCALE, ones, ones, G.cw, G.axes, rim)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, RSCALE, ones, ones, G.cw, Transfers(G.axes, rim))
     bd, xd = _dev(nh, ones, 0), _dev(nh, ones, 0)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, 0), _dev(nh, q_f, 0), bd, xd)
     nh.torch.cuda.synchronize()
@@ -239,7 +237,7 @@ def test_kind_average_is_the_averaging_restriction(nh, name):
     assert lib.neptune_hip_mg_restrict(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), _dev(nh, b_f, 0).ptr, _dev(nh, q_f, 0).ptr,
                                        RSCALE, b2.ptr, x2.ptr, None) == nh.capi.OK
     nh.torch.cuda.synchronize()
-    want_b, want_x = cc.restrict_cell(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, G.axes)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, Halved(G.axes))
     assert bits_equal(bd.numpy(), b2.numpy()) and bits_equal(xd.numpy(), x2.numpy())
     assert bits_equal(bd.numpy(), want_b), mismatch_report(bd.numpy(), want_b)
     assert bits_equal(xd.numpy(), want_x)
@@ -249,7 +247,7 @@ def test_kind_average_is_the_averaging_restriction(nh, name):
         assert lib.neptune_hip_mg_restrict_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(t), _dev(nh, b_f, 0).ptr,
                                                   _dev(nh, q_f, 0).ptr, RSCALE, bd.ptr, xd.ptr, None) == nh.capi.OK
         nh.torch.cuda.synchronize()
-        want_b, _ = cs.restrict_linear(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, G.axes, ((ODD, EVEN), (EVEN, ODD)))
+        want_b, _ = rst.restrict(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, Transfers(G.axes, ((ODD, EVEN), (EVEN, ODD))))
         assert bits_equal(bd.numpy(), want_b), mismatch_report(bd.numpy(), want_b)
 
 

@@ -6,7 +6,7 @@ No reduction enters a field, so after any number of cycles x_0 and every level's
 for bit, whatever the launch path (plain launches or the replayed graph); for MGCG the restatement's recurrences are driven
 by the device's own scalars (rz_0 and the trace), which then reproduce x, r, p, z and every level's fields bit for bit.  rr_0
 and every rr read after a block must lie within 2 (n - 1) eps sum |t_i| of the exact sum of the restatement's own terms
-(mg_cases' bound), and so must every traced scalar.
+(monitor_cases.reference_sum's bound), and so must every traced scalar.
 
 Operators, one lowered module per level, as in test_mgcl_solve_gpu.py: mgcc_cases.flux_module, or, for rank 3 with a Dirichlet
 face, mgcl_cases.star_s_module; rscale = 4, minv = 0.8 / diagonal on Omega; the work fields hold NaN before every call.
@@ -21,14 +21,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import mg_restatement as rst
 import mgcc_cases as cc
 import mgcgmixed_cases as mx
 import mgcl_cases as cl
 import mgcs_cases as cs
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
-from mgcc_cases import Halved
-from mgcs_cases import Transfers
+from mg_restatement import Halved, Transfers
 
 pytestmark = pytest.mark.gpu
 
@@ -38,11 +38,11 @@ MIX2 = [("dirichlet", "neumann"), ("neumann", "dirichlet")]
 
 
 def _steps(omega, pairs, faces, only=None):
-    return cs.transfer_steps(cc.halved_steps(omega, pairs), cl.rim_of(faces, len(omega)), only=only)
+    return cs.transfer_steps(cc.halved_steps(omega, pairs), rst.rim_of(faces, len(omega)), only=only)
 
 
 def _crossed():
-    rim = cl.rim_of("dirichlet", 2)
+    rim = rst.rim_of("dirichlet", 2)
     (m0, w0, a0), (m1, w1, a1), last = cc.halved_steps((16, 264), [ALL2, ALL2])
     return [(m0, w0, Transfers(a0, rim, "constant", "linear")), (m1, w1, Transfers(a1, rim, "linear", "average")), last]
 
@@ -56,7 +56,7 @@ PROBLEMS = {
     "crossed_f64": (_crossed(), "dirichlet", np.float64, cl.flux_levels),
     "kept_f64": (_steps((8, 264), [Halved((1,)), ALL2], MIX2), MIX2, np.float64, cl.flux_levels),
     "const3d_f64": (cc.halved_steps((8, 16, 264), [ALL3, ALL3]), MIX3, np.float64, cl.star_levels),
-    "stop_f64": (cs.transfer_steps(cc.plan((32, 32, 32)), cl.rim_of("dirichlet", 3)), "dirichlet", np.float64, cl.star_levels),
+    "stop_f64": (cs.transfer_steps(cc.plan((32, 32, 32)), rst.rim_of("dirichlet", 3)), "dirichlet", np.float64, cl.star_levels),
     "stop_const_f64": (cc.plan((32, 32, 32)), "dirichlet", np.float64, cl.star_levels),
 }
 DAMP = 0.8
@@ -128,16 +128,16 @@ def _reference(P, cycles, check_every=1):
     """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
     key = (cycles, check_every)
     if key not in P.runs:
-        rr0, checks = cs.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
+        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
         P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
     return P.runs[key]
 
 
 def _setting(axes):
-    if isinstance(axes, Transfers):
+    if getattr(axes, "rim", None) is not None:           # a pair with its transfers chosen
         out = dict(prolong=axes.prolong, restrict=axes.restrict)
         if axes.prolong == "linear" or axes.restrict == "linear":
-            out["faces"] = cs.faces_of(axes.rim)
+            out["faces"] = rst.faces_of(axes.rim)
         return out
     return {}
 
@@ -159,7 +159,7 @@ def _hierarchy(nh, P, lines=None):
     """a device hierarchy whose work fields hold NaN, every pair of the restatement with its two transfers; -> (h, x, b, [r, p, z])"""
     F = nh.fields.DeviceField
     h = nh.mg.Hierarchy(_levels(nh, P, lines))
-    assert h.halved == [tuple(R.axes) if isinstance(R.axes, Halved) else () for R in P.ref[:-1]]
+    assert h.halved == [tuple(R.axes) if rst.axes_of(R).halved else () for R in P.ref[:-1]]
     assert [(L.linear, L.restrict_linear) for L in h.levels[:-1]] == [
         (getattr(R.axes, "prolong", "") == "linear", getattr(R.axes, "restrict", "") == "linear") for R in P.ref[:-1]]
     nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
@@ -209,13 +209,13 @@ def test_cycles_match_the_restatement(nh, name, cycles):
     P = _problem(nh, name)
     assert [L.m for L in P.ref] == ([(8, 16, 264), (4, 8, 132), (2, 4, 66)] if name.startswith("3d") else
                                     [(16, 264), (8, 132), (4, 66)])
-    assert all(isinstance(L.axes, Transfers) and L.axes.symmetric and L.axes.restrict == "linear" for L in P.ref[:-1])
+    assert all(L.axes.halved and L.axes.symmetric and L.axes.restrict == "linear" for L in P.ref[:-1])
     _check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
 
 
 def test_the_symmetric_pair_first_and_the_constant_pair_second(nh):
     P = _problem(nh, "first_f64")
-    assert [type(L.axes) for L in P.ref[:-1]] == [Transfers, Halved]
+    assert [(rst.axes_of(L).kind, rst.axes_of(L).prolong, rst.axes_of(L).restrict) for L in P.ref[:-1]] == [("halved", "linear", "linear"), ("halved", "constant", "average")]
     _check_against_reference(nh, P, 3)
     assert not bits_equal(_reference(P, 3)[2][0], _reference(_problem(nh, "2d_f64"), 3)[2][0])
 
@@ -267,7 +267,8 @@ def _check_replay(nh, P, iters):
     assert done == iters and trace.shape == (iters, 3)
     print(f"counts = {counts}")
     assert (counts[0], counts[1], counts[3]) == ((iters, 0, iters) if iters <= 2 else (1, iters - 1, iters)), counts
-    rx, rr, rp, rz, checks, rr0_ref, rz0_ref = cs.replay(P.ref, P.x0, P.b, rz0, trace)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, rz0, trace)
+    rx, rr, rp, rz = st.x, st.r, st.p, st.z
     _check_sums(rr0, rz0, trace, rr0_ref, rz0_ref, checks)
     assert rr_last == float(trace[-1][2])
     assert all(float(row[1]) > 0 for row in trace) and rz0 > 0                         # the preconditioner is positive
@@ -307,8 +308,8 @@ def _cg_sequence(P, sweeps):
     """r . r of the restatement's recurrences (numpy's own sums) down to 1e-16 rr_0, computed once: -> (seq, tol2)"""
     key = ("cg_seq", sweeps)
     if key not in P.runs:
-        rr0 = cs.numpy_mgcg(P.ref, P.x0, P.b, 0, sweeps)[0]
-        P.runs[key] = (cs.numpy_mgcg(P.ref, P.x0, P.b, 40, sweeps, stop_at=1e-16 * rr0), 1e-16 * rr0)
+        rr0 = rst.numpy_mgcg(P.ref, P.x0, P.b, 0, sweeps)[0]
+        P.runs[key] = (rst.numpy_mgcg(P.ref, P.x0, P.b, 40, sweeps, stop_at=1e-16 * rr0), 1e-16 * rr0)
     return P.runs[key]
 
 
@@ -344,7 +345,7 @@ def test_mgcg_with_a_line_stage_on_level_one(nh):
     try:
         (done, rr0, rr_last, trace), h, x, work, counts, rz0 = _cg(nh, P, 4, lines, lines=True)
         assert h.has_lines and done == 4 and (counts[0], counts[1], counts[3]) == (1, 3, 4)
-        st, checks, rr0_ref, rz0_ref, _ = cs.composed.replay(P.ref, P.x0, P.b, rz0, trace)
+        st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, rz0, trace)
         _check_sums(rr0, rz0, trace, rr0_ref, rz0_ref, checks)
         for nm, got, want in (("x", x.numpy(), st.x), ("r", work[0].numpy(), st.r), ("p", work[1].numpy(), st.p), ("z", work[2].numpy(), st.z)):
             assert bits_equal(got, want), f"{nm}: " + mismatch_report(got, want)
@@ -352,7 +353,7 @@ def test_mgcg_with_a_line_stage_on_level_one(nh):
     finally:
         del R1.stages
     # the stage changes the bits
-    assert not bits_equal(st.x, cs.replay(P.ref, P.x0, P.b, rz0, trace)[0])
+    assert not bits_equal(st.x, rst.replay(P.ref, P.x0, P.b, rz0, trace)[0].x)
 
 
 def test_mixed_precision_against_the_composed_restatement(nh):
@@ -373,7 +374,7 @@ def test_mixed_precision_against_the_composed_restatement(nh):
     rz0 = nh.mg.cg_rz0()
     assert done == 4 and trace.shape == (4, 3) and rr_last < rr0
     R = mx.Problem(P64.ref[0].A, P32.ref)
-    st, checks, rr0_ref, rz0_ref, _ = cs.composed.replay(R, P64.x0, P64.b, rz0, trace)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(R, P64.x0, P64.b, rz0, trace)
     _check_sums(rr0, rz0, trace, rr0_ref, rz0_ref, checks)
     for nm, got, want in (("x", x.numpy(), st.x), ("r", work[0].numpy(), st.r), ("p", work[1].numpy(), st.p),
                           ("r32", inner.b[0].numpy(), st.r32), ("z32", inner.x[0].numpy(), st.z32)):

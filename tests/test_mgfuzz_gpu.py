@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import helpers
+import mg_restatement as rst
 import mgfuzz_cases as fz
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
@@ -182,7 +183,7 @@ def _check_cg(B, R):
     assert done == c["n"] and trace.shape == (c["n"], 3)
     # R.counts[2], how many iterations took a plain launch and a separate dot product, is the operator's matter
     assert (R.counts[0], R.counts[1], R.counts[3]) == (plain, graph, checks), R.counts
-    st, sums, rr0_ref, rz0_ref, _ = fz.replay(B.problem, B.x0, B.b, R.rz0, trace, c["sweeps"], c["coarse_sweeps"])
+    st, sums, rr0_ref, rz0_ref, _ = rst.replay(B.problem, B.x0, B.b, R.rz0, trace, c["sweeps"], c["coarse_sweeps"])
     print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
     assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, row in enumerate(sums):

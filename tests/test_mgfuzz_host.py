@@ -1,25 +1,20 @@
 """The multigrid fuzz cases (tests/mgfuzz_cases.py) without a GPU.
 
-The composed restatement IS the features' own ones: on each feature's fixed problems its cycle, run and replay reproduce
-bit for bit what mg_cases, mgsemi_cases, mglines_cases, mgcc_cases, mgcg_cases, mgcglines_cases and mgcgmixed_cases produce.
+The one restatement (tests/mg_restatement.py) IS the features' former own copies: on each feature's fixed problems its run,
+its numpy_mgcg and its replay reproduce bit for bit what those copies produced, as tools/record_mg_restatement.py recorded it
+from the last commit that had them (tests/golden/mg_restatement.json); every recorded problem is run.
 What the seed list covers is binding (a seed taken out of SEEDS so that an item goes missing fails here), the restatement of
 every seed stays finite and its conjugate gradients never break down -- a condition on the generator's inputs, so that the
 GPU tests compare meaningful numbers --, and all seeds together stay within the budget of module texts."""
+import json
 import time
 
 import numpy as np
 import pytest
 
-import mg_cases as mgc
-import mgcc_cases as cc
-import mgcg_cases as mg
-import mgcglines_cases as mlc
-import mgcgmixed_cases as mx
+import mg_restatement as rst
 import mgfuzz_cases as fz
-import mglines_cases as lc
-import mgsemi_cases as sc
-from helpers import bits_equal, mismatch_report
-from mgcc_cases import Halved
+import record_mg_restatement as rec
 
 SEEDS = fz.SEEDS
 ORDINARY = [s for s in SEEDS if fz.seed_class(s) != "refused"]
@@ -34,92 +29,51 @@ def wall_time():
     print(f"\ntest_mgfuzz_host.py: {time.perf_counter() - t0:.1f} s")
 
 
-# ---------------------------------------------------------------- the composed restatement is the old ones
-def _same_fields(got_levels, want_levels, names=("x", "b", "q")):
-    for l, (G, W) in enumerate(zip(got_levels, want_levels)):
-        for nm in names:
-            g, w = getattr(G, nm), getattr(W, nm)
-            assert bits_equal(g, w), f"{nm}_{l}: " + mismatch_report(g, w)
+# ---------------------------------------------------------------- the one restatement is the former copies, bit for bit
+@pytest.fixture(scope="module")
+def recorded():
+    """the golden file; every problem in it is one the two tests below run, with the recorder's schedules"""
+    doc = json.loads(rec.GOLDEN.read_text())
+    assert sorted(doc["solves"]) == sorted(rec.SOLVES) and sorted(doc["cgs"]) == sorted(rec.CGS)
+    assert [tuple(s) for s in doc["schedules"]] == list(rec.SCHEDULES)
+    assert (doc["cycles"], doc["iters"], doc["sweeps"], doc["coarse_sweeps"]) == (rec.CYCLES, rec.ITERS, rec.SWEEPS, rec.COARSE_SWEEPS)
+    return doc
 
 
-def _plain_problem(levels, seed=91):
-    return mgc.problem_fields(levels[0].shape, levels[0].where, levels[0].dt, rim=True, seed=seed)
+def _same_record(name, got, want):
+    diffs = rec.differences(got, want)
+    assert not diffs, f"{name}: " + "; ".join(diffs)
 
 
-OLD_SOLVES = {
-    "mg_star": (lambda: mgc.star_levels((15, 31), 3, np.float64, 0.8)[0], mgc.run),
-    "mg_star_f32_rank3": (lambda: mgc.star_levels((7, 7, 15), 2, np.float32, 0.8)[0], mgc.run),
-    "mgsemi_plan": (lambda: sc.plan_levels((15, 31), (1.0, 16.0), 0.8)[0], sc.run),
-    "mglines_star": (lambda: lc.star_levels((7, 15), 3, np.float64, 0.8, [(0, 1), (1,), ()])[0], lc.run),
-    "mglines_flux": (lambda: lc.flux_levels((0, 1), n=17)[0], lc.run),
-    "mgcc_flux": (lambda: cc.flux_levels(cc.halved_steps((8, 16), [Halved((0, 1)), Halved((1,))]), 0.8, np.float64, "dirichlet")[0], cc.run),
-    "mgcc_switch": (lambda: cc.flux_levels(cc.halved_steps((14, 14), [Halved((0, 1)), (0, 1)]), 0.8, np.float32, "dirichlet")[0], cc.run),
-}
+@pytest.mark.parametrize("name", sorted(rec.SOLVES))
+def test_the_restatement_reproduces_the_recorded_cycles(name, recorded):
+    levels = rec.SOLVES[name][0]()
+    x0, b = rec.problem_fields(levels)
+    for k, (pre, post, cs, every) in enumerate(rec.SCHEDULES):
+        rr0, checks = rst.run(levels, x0, b, rec.CYCLES, pre, post, cs, every)
+        _same_record(f"{name}, schedule {k}", rec.solve_record(rr0, checks, levels), recorded["solves"][name][k])
 
 
-@pytest.mark.parametrize("name", sorted(OLD_SOLVES))
-def test_composed_cycle_reproduces_each_features_own(name):
-    make, old_run = OLD_SOLVES[name]
-    want, got = make(), make()
-    x0, b = _plain_problem(want)
-    for pre, post, cs, every in ((2, 2, 8, 1), (1, 2, 3, 2)):
-        want_rr = old_run(want, x0, b, 2, pre, post, cs, every)
-        got_rr = fz.run(got, x0, b, 2, pre, post, cs, every)
-        assert got_rr == want_rr
-        _same_fields(got, want)
-
-
-def _mixed_pair():
-    return mx.star_problem((15, 15), 3, 0.8)[0]
-
-
-OLD_CG = {
-    # name: (make the problem, the feature's numpy_mgcg -> the r . r sequence, the feature's replay -> the fields to compare)
-    "mgcg": (lambda: mg.star_levels((15, 15), 3, np.float64, 0.8)[0], mg.numpy_mgcg, mg.replay),
-    "mgcg_f32": (lambda: mg.star_levels((7, 31), 2, np.float32, 0.8)[0], mg.numpy_mgcg, mg.replay),
-    "mgsemi": (lambda: sc.plan_levels((15, 31), (1.0, 16.0), 0.8)[0], None, sc.replay),
-    "mgcc": (lambda: cc.flux_levels(cc.halved_steps((8, 16), [Halved((0, 1)), Halved((1,))]), 0.8, np.float64, "dirichlet")[0],
-             cc.numpy_mgcg, cc.replay),
-    "mgcglines": (lambda: lc.star_levels((7, 15), 3, np.float64, 0.8, [(0, 1), (1,), ()])[0], mlc.numpy_mgcg, mlc.replay),
-    "mgcglines_point0": (lambda: _point0_levels(), mlc.numpy_mgcg, mlc.replay),
-    "mgcgmixed": (_mixed_pair, lambda *a, **k: mx.numpy_mgcg_mixed(*a, **k)[0], mx.replay),
-}
-
-
-def _point0_levels():
-    levels = lc.star_levels((7, 15), 3, np.float64, 0.8, [(), (0,), (1, 0)])[0]
-    levels[0].minv = mgc.minv_field(levels[0].shape, levels[0].where, np.float64, 0.8, outside=0.0)
-    return levels
-
-
-@pytest.mark.parametrize("name", sorted(OLD_CG))
-def test_composed_replay_reproduces_each_features_own(name):
-    make, old_numpy, old_replay = OLD_CG[name]
-    want, got = make(), make()
-    mixed = isinstance(want, mx.Problem)
-    x0, b = _plain_problem(want.levels if mixed else want)
-    if mixed:
-        x0, b = x0.astype(np.float64), b.astype(np.float64)
-    iters, sweeps, cs = 3, 2, 4
-    # the scalars of the feature's own numpy_mgcg: the composed recurrences with numpy's sums give its r . r sequence ...
-    st, _, _, _, scalars = fz.replay(got, x0, b, sweeps=sweeps, coarse_sweeps=cs, iters=iters)
+@pytest.mark.parametrize("name", sorted(rec.CGS))
+def test_the_restatement_reproduces_the_recorded_replays(name, recorded):
+    want = recorded["cgs"][name]
+    problem = rec.CGS[name][0]()
+    mixed = rst.is_mixed(problem)
+    x0, b = rec.problem_fields(problem)
+    unhex = float.fromhex
+    rz0, trace = unhex(want["rz0_used"]), np.array([[unhex(v) for v in row] for row in want["trace"]])
+    # with numpy's own sums the recurrences give the recorded scalars: the r . r sequence of the former numpy_mgcg ...
+    st, _, _, _, scalars = rst.replay(problem, x0, b, sweeps=rec.SWEEPS, coarse_sweeps=rec.COARSE_SWEEPS, iters=rec.ITERS)
     assert not any(s[3] for s in scalars)
-    if old_numpy is not None:
-        seq = old_numpy(want, x0, b, iters, sweeps, cs)
-        assert [float(s[2]) for s in scalars] == seq[1:]
-    # ... and driven by them both replays agree in every field, every level and every checked sum
-    rz0 = st.rz0_used
-    trace = np.array([[s[0], s[1], s[2]] for s in scalars])
-    out = old_replay(want, x0, b, rz0, trace, sweeps, cs)
-    st, checks, rr0, rz0_ref, _ = fz.replay(got, x0, b, rz0, trace, sweeps, cs)
-    if mixed:
-        fields = zip(("x", "r", "p", "r32", "z32"), (st.x, st.r, st.p, st.r32, st.z32), out[:5])
-    else:
-        fields = zip(("x", "r", "p", "z"), (st.x, st.r, st.p, st.z), out[:4])
-    for nm, g, w in fields:
-        assert bits_equal(g, w), f"{nm}: " + mismatch_report(g, w)
-    assert (checks, rr0, rz0_ref) == tuple(out[-3:])
-    _same_fields((got.levels if mixed else got)[1:], (want.levels if mixed else want)[1:], names=("x", "b"))
+    assert rec.hexes([st.rz0_used, [list(s[:3]) for s in scalars]]) == [want["rz0_used"], want["trace"]], name
+    seq = rst.numpy_mgcg(problem, x0, b, rec.ITERS, rec.SWEEPS, rec.COARSE_SWEEPS)
+    assert seq[1:] == [row[2] for row in trace.tolist()] and (want["numpy_rr0"] is None or seq[0] == unhex(want["numpy_rr0"])), name
+    # ... and driven by them the replay gives the recorded bits in every field, every level and every checked sum
+    st, checks, rr0, rz0_ref, _ = rst.replay(problem, x0, b, rz0, trace, rec.SWEEPS, rec.COARSE_SWEEPS)
+    fields = {nm: getattr(st, nm) for nm in (("x", "r", "p", "r32", "z32") if mixed else ("x", "r", "p", "z"))}
+    got = rec.cg_record(None, fields, checks, rr0, rz0_ref, rec.levels_of(problem))
+    del got["numpy_rr0"]                        # checked above
+    _same_record(name, got, {k: want[k] for k in got})
 
 
 # ---------------------------------------------------------------- what the seed list covers
@@ -318,7 +272,7 @@ def test_the_restatement_of_a_seed_is_finite_and_cg_does_not_break_down(seed):
         assert all(np.isfinite(v[0]) for v in [rr0] + checks)
         assert np.isfinite(B.levels[0].x).all()
     else:
-        st, checks, rr0, rz0_ref, scalars = fz.replay(B.problem, B.x0, B.b, sweeps=c["sweeps"], coarse_sweeps=c["coarse_sweeps"], iters=c["n"])
+        st, checks, rr0, rz0_ref, scalars = rst.replay(B.problem, B.x0, B.b, sweeps=c["sweeps"], coarse_sweeps=c["coarse_sweeps"], iters=c["n"])
         assert st.rz0_used > 0 and all(not broken and pq > 0 and rz > 0 and np.isfinite(rr) for pq, rz, rr, broken in scalars), scalars
         for a in (st.x, st.r, st.p):
             assert np.isfinite(a).all()

@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import mg_cases as mgc
+import mg_restatement as rst
 import mglines_cases as lc
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
@@ -214,7 +214,7 @@ def test_stage_solves_the_tridiagonal_system(m, axis):
     lower, diag, upper = _random_tridiagonal(rng, shape, where, axis)
     lo, inv, up = lc.factors(lower, diag, upper, where, axis, omega)
     q, b, x = (rng.standard_normal(shape) for _ in range(3))
-    got = lc.line_stage(q, b, lo, inv, up, x, where, axis)
+    got = rst.line_stage(q, b, lo, inv, up, x, where, axis)
     outside = np.ones(shape, bool)
     outside[where] = False
     assert np.array_equal(got[outside], x[outside])
@@ -237,8 +237,8 @@ def test_one_cell_lines_are_the_point_sweep_bit_for_bit(dtype):
     shape, where = (4, 9), (slice(2, 3), slice(1, 8))            # m[0] = 1
     q, b, x, minv = (rng.standard_normal(shape).astype(dtype) for _ in range(4))
     nan = np.full(shape, np.nan, dtype)
-    got = lc.line_stage(q, b, nan, minv, nan, x, where, 0)
-    assert got.tobytes() == mgc.smooth(q, b, minv, x, where).tobytes()
+    got = rst.line_stage(q, b, nan, minv, nan, x, where, 0)
+    assert got.tobytes() == rst.smooth(q, b, minv, x, where).tobytes()
     # and the factors of a one-cell line are inv = 1 / (t / omega), lo = up = +0
     dt = np.dtype(dtype).type
     lower, diag, upper = _random_tridiagonal(rng, shape, where, 0, dtype)
@@ -255,7 +255,7 @@ def test_cells_that_are_not_read_leave_the_bits_alone(axis, dtype):
     lower, diag, upper = (f.astype(dtype) for f in _random_tridiagonal(rng, shape, where, axis))
     lo, inv, up = lc.factors(lower, diag, upper, where, axis, 0.8)
     q, b, x = (rng.standard_normal(shape).astype(dtype) for _ in range(3))
-    want = lc.line_stage(q, b, lo, inv, up, x, where, axis)
+    want = rst.line_stage(q, b, lo, inv, up, x, where, axis)
     outside = np.ones(shape, bool)
     outside[where] = False
     first, last = list(where), list(where)
@@ -266,7 +266,7 @@ def test_cells_that_are_not_read_leave_the_bits_alone(axis, dtype):
             f[outside] = poison
         lo2[tuple(first)] = poison
         up2[tuple(last)] = poison
-        got = lc.line_stage(q2, b2, lo2, inv2, up2, x, where, axis)
+        got = rst.line_stage(q2, b2, lo2, inv2, up2, x, where, axis)
         assert got.tobytes() == want.tobytes(), poison
     assert np.isfinite(want).all()
     # the factor recurrence itself reads nothing outside Omega and no rim coupling
@@ -302,7 +302,7 @@ def test_sweep_order_reverses_the_stages_after_the_coarse_correction():
     """pre-sweeps and coarse sweeps run stages 0 .. k-1, post-sweeps k-1 .. 0: recorded on a stub level"""
     calls = []
 
-    class Stub(mgc.Level):
+    class Stub(rst.Level):
         pass
     shape, where = (5, 5), (slice(1, 4), slice(1, 4))
     z = np.zeros(shape)
@@ -310,22 +310,22 @@ def test_sweep_order_reverses_the_stages_after_the_coarse_correction():
     L.x, L.b, L.q = z.copy(), z.copy(), z.copy()
     one = np.ones(shape)
     L.stages = [(0, z, one, z), (1, z, one, z), (0, z, one, z)]
-    real = lc.line_stage
+    real = rst.line_stage
     try:
-        lc.line_stage = lambda q, b, lo, inv, up, x, where, axis: (calls.append(axis), real(q, b, lo, inv, up, x, where, axis))[1]
-        lc.sweep(L)
-        lc.sweep(L, reverse=True)
+        rst.line_stage = lambda q, b, lo, inv, up, x, where, axis: (calls.append(axis), real(q, b, lo, inv, up, x, where, axis))[1]
+        rst.sweep(L)
+        rst.sweep(L, reverse=True)
     finally:
-        lc.line_stage = real
+        rst.line_stage = real
     L.stages = [(0, z, one, z), (1, z, one, z)]
     assert calls == [0, 1, 0, 0, 1, 0]
     calls.clear()
     try:
-        lc.line_stage = lambda q, b, lo, inv, up, x, where, axis: (calls.append(axis), real(q, b, lo, inv, up, x, where, axis))[1]
-        lc.sweep(L)
-        lc.sweep(L, reverse=True)
+        rst.line_stage = lambda q, b, lo, inv, up, x, where, axis: (calls.append(axis), real(q, b, lo, inv, up, x, where, axis))[1]
+        rst.sweep(L)
+        rst.sweep(L, reverse=True)
     finally:
-        lc.line_stage = real
+        rst.line_stage = real
     assert calls == [0, 1, 1, 0]
 
 
@@ -364,7 +364,7 @@ def test_alternating_lines_fall_by_a_factor_of_four_and_arrive(flux):
     """Observed: per-cycle factors of rr 9830.5, 219.5, 161.4, 150.2, 146.7, 145.0, 143.9 (worst of the first six 145.0);
     rr / rr0 = 6.2e-18 after 7 cycles (the unrounded float64 model on another right-hand side: 7 cycles, worst factor 136)."""
     levels, x0, b = flux
-    seq = lc.rr_sequence(levels, x0, b, 14, stop_at=1e-16)
+    seq = rst.rr_sequence(levels, x0, b, 14, stop_at=1e-16)
     factors = [a / c for a, c in zip(seq, seq[1:])]
     print("alternating:", [f"{f:.1f}" for f in factors], f"arrived after {len(seq) - 1} cycles, rr / rr0 = {seq[-1] / seq[0]:.2e}")
     assert len(seq) - 1 >= 6
@@ -378,7 +378,7 @@ def test_point_jacobi_and_single_directions_do_not_arrive(name, axes, built_libs
     """Observed rr / rr0 after 28 cycles: point Jacobi 3.3e-05, lines along dim 0 only 3.4e-07, along dim 1 only 3.2e-05."""
     levels, _, _ = lc.flux_levels(axes)
     x0, b = lc.flux_problem(levels)
-    seq = lc.rr_sequence(levels, x0, b, 28, stop_at=1e-16)
+    seq = rst.rr_sequence(levels, x0, b, 28, stop_at=1e-16)
     print(f"{name}: rr / rr0 = {seq[-1] / seq[0]:.2e} after {len(seq) - 1} cycles")
     assert len(seq) - 1 == 28 and seq[-1] > 1e-16 * seq[0]
     assert math.isfinite(seq[-1])

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import helpers
+import mg_restatement as rst
 import mglines_cases as lc
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
@@ -100,7 +101,7 @@ def _problem(name, axis, dtype):
 @pytest.mark.parametrize("name,axis,dtype", RUNS, ids=IDS)
 def test_line_stage_matches_the_restatement(nh, name, axis, dtype):
     where, q, b, x, (lo, inv, up) = _problem(name, axis, dtype)
-    want = lc.line_stage(q, b, lo, inv, up, x, where, axis)
+    want = rst.line_stage(q, b, lo, inv, up, x, where, axis)
     assert np.isfinite(want[where]).all()
     F = nh.fields.DeviceField
     dev = lambda a: stc.offset_field(nh, a, 8 // a.itemsize)          # every field 8 bytes into a larger allocation
@@ -119,7 +120,6 @@ def test_line_stage_matches_the_restatement(nh, name, axis, dtype):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_one_cell_lines_are_the_point_sweep(nh, dtype):
     """m = 1 along the stage's axis with inv = minv: the bits of neptune_hip_mg_smooth"""
-    import mg_cases as mgc
     for name, axis in (("one-slow", 0), ("one-contig", 2)):
         where, q, b, x, (lo, inv, up) = _problem(name, axis, dtype)
         F = nh.fields.DeviceField
@@ -130,7 +130,7 @@ def test_one_cell_lines_are_the_point_sweep(nh, dtype):
         nh.mg.line_smooth(level, nh.mg.LineStage(axis, F.from_numpy(lo), F.from_numpy(inv), F.from_numpy(up)), F.from_numpy(q),
                           F.from_numpy(b), xl)
         nh.torch.cuda.synchronize()
-        assert bits_equal(xl.numpy(), xs.numpy()) and bits_equal(xs.numpy(), mgc.smooth(q, b, inv, x, where))
+        assert bits_equal(xl.numpy(), xs.numpy()) and bits_equal(xs.numpy(), rst.smooth(q, b, inv, x, where))
 
 
 def test_refusals_on_device_pointers(nh):

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import mg_cases as mgc
+import mg_restatement as rst
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
 
@@ -111,7 +112,7 @@ def _reference(P, cycles, check_every=1):
     """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
     key = (cycles, check_every)
     if key not in P.runs:
-        rr0, checks = lc.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
+        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
         P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
     return P.runs[key]
 
@@ -217,11 +218,11 @@ def test_stops_where_the_definition_says_on_the_flux_hierarchy(nh, check_every, 
     P = _problem(nh, "flux")
     assert [L.m for L in P.ref] == [(63, 63), (31, 31), (15, 15), (7, 7), (3, 3), (1, 1)]
     if "seq" not in P.runs:
-        P.runs["seq"] = lc.rr_sequence(P.ref, P.x0, P.b, 6)
+        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6)
     seq = P.runs["seq"]
-    tol2 = lc.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_cycles = len(seq) - 1
-    want_done, want_checks = lc.expected_stop(seq, check_every, max_cycles, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
     assert want_done == between[1]
     (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
     print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
@@ -296,7 +297,7 @@ def test_levels_with_lines_through_the_python_layer(nh):
     nh.mg.line_smooth(h.levels[0], h.levels[0].lines[1], qd, b, xd)
     nh.torch.cuda.synchronize()
     ax, lo, inv, up = R.stages[1]
-    want = lc.line_stage(q, P.b, lo, inv, up, P.b, R.where, ax)
+    want = rst.line_stage(q, P.b, lo, inv, up, P.b, R.where, ax)
     assert bits_equal(xd.numpy(), want), mismatch_report(xd.numpy(), want)
     # a hierarchy without stages still needs minv, and says so
     bare = nh.mg.Hierarchy([nh.mg.Level(P.entries[0], levels[0].like, _bounds(R), others=levels[0].others)])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import mg_cases as mgc
+import mg_restatement as rst
 import mgsemi_cases as sc
 from neptune_hip import _capi
 from neptune_hip.geometry import make_geom
@@ -209,9 +210,9 @@ def test_all_axes_is_the_full_restatement_bit_for_bit(dtype):
         b, q = (rng.standard_normal(fshape).astype(dtype) for _ in range(2))
         bc, xc, xf = rng.standard_normal(cshape).astype(dtype), rng.standard_normal(cshape).astype(dtype), rng.standard_normal(fshape).astype(dtype)
         axes = tuple(range(len(fine)))
-        got, want = sc.restrict(b, q, fw, 4.0, bc, xc, cw, axes), mgc.restrict(b, q, fw, 4.0, bc, xc, cw)
+        got, want = rst.restrict(b, q, fw, 4.0, bc, xc, cw, axes), rst.restrict(b, q, fw, 4.0, bc, xc, cw)
         assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
-        assert sc.prolong_add(bc, cw, xf, fw, axes).tobytes() == mgc.prolong_add(bc, cw, xf, fw).tobytes()
+        assert rst.prolong_add(bc, cw, xf, fw, axes).tobytes() == rst.prolong_add(bc, cw, xf, fw).tobytes()
 
 
 def _dense(f, shape_in, shape_out):
@@ -226,9 +227,9 @@ def _dense(f, shape_in, shape_out):
 
 def _transfer_matrices(fine, axes):
     coarse = tuple((m - 1) // 2 if d in axes else m for d, m in enumerate(fine))
-    R = _dense(lambda d: sc.restrict(d, np.zeros(fine), _whole(fine), 1.0, np.zeros(coarse), np.zeros(coarse), _whole(coarse), axes)[0],
+    R = _dense(lambda d: rst.restrict(d, np.zeros(fine), _whole(fine), 1.0, np.zeros(coarse), np.zeros(coarse), _whole(coarse), axes)[0],
                fine, coarse)
-    P = _dense(lambda e: sc.prolong_add(e, _whole(coarse), np.zeros(fine), _whole(fine), axes), coarse, fine)
+    P = _dense(lambda e: rst.prolong_add(e, _whole(coarse), np.zeros(fine), _whole(fine), axes), coarse, fine)
     return R, P
 
 
@@ -263,18 +264,18 @@ def test_a_kept_axis_passes_minus_zero_and_nan_through(dtype):
     b[0, :] = -0.0
     b[1, :] = payload
     b[2, :] = (1.0, 2.0, 3.0)
-    bc, _ = sc.restrict(b, np.zeros(fine, dtype), _whole(fine), 1.0, np.ones(coarse, dtype), np.ones(coarse, dtype), _whole(coarse), (1,))
+    bc, _ = rst.restrict(b, np.zeros(fine, dtype), _whole(fine), 1.0, np.ones(coarse, dtype), np.ones(coarse, dtype), _whole(coarse), (1,))
     # along the coarsened axis: 0.25 * -0 + 0.5 * -0 + 0.25 * -0 = -0; the NaN's payload survives the arithmetic of one axis
     assert np.signbit(bc[0, 0]) and bc[0, 0] == 0 and np.isnan(bc[1, 0]) and bc[2, 0] == 2.0 and not np.signbit(bc[3, 0])
     # the kept axis alone: with only axis 0 listed on 3 x 4 -> 1 x 4, the columns do not mix
     b = np.zeros((3, 4), dtype)
     b[:, 0] = -0.0
     b[:, 1] = payload
-    bc, _ = sc.restrict(b, np.zeros((3, 4), dtype), _whole((3, 4)), 1.0, np.ones((1, 4), dtype), np.ones((1, 4), dtype), _whole((1, 4)), (0,))
+    bc, _ = rst.restrict(b, np.zeros((3, 4), dtype), _whole((3, 4)), 1.0, np.ones((1, 4), dtype), np.ones((1, 4), dtype), _whole((1, 4)), (0,))
     assert np.signbit(bc[0, 0]) and np.isnan(bc[0, 1]) and bc[0, 2] == 0 and not np.signbit(bc[0, 2])
     # prolongation: the coarse value itself along the kept axis -- bit for bit on the odd fine cells of the coarsened one
     e = np.array([[-0.0], [payload], [5.0], [0.0]], dtype)
-    out = sc.prolong_add(e, _whole(coarse), np.full(fine, -0.0, dtype), _whole(fine), (1,))
+    out = rst.prolong_add(e, _whole(coarse), np.full(fine, -0.0, dtype), _whole(fine), (1,))
     assert out[:, 1].tobytes() == (np.full(4, -0.0, dtype) + e[:, 0]).astype(dtype).tobytes()
     assert np.signbit(out[0, 1]) and np.isnan(out[1]).all() and np.array_equal(out[2], [2.5, 5.0, 2.5]) and not np.isnan(out[[0, 2, 3]]).any()
 
@@ -301,7 +302,7 @@ def test_plan_hierarchy_of_the_anisotropic_problem(plan_problem):
 
 def test_rr_falls_by_a_factor_of_four_per_cycle_on_the_plan_hierarchy(plan_problem):
     levels, x0, b = plan_problem
-    seq = sc.rr_sequence(levels, x0, b, 6)
+    seq = rst.rr_sequence(levels, x0, b, 6)
     print("semi:", [f"{a / c:.1f}" for a, c in zip(seq, seq[1:])])
     assert len(seq) == 7
     for a, c in zip(seq, seq[1:]):
@@ -310,11 +311,11 @@ def test_rr_falls_by_a_factor_of_four_per_cycle_on_the_plan_hierarchy(plan_probl
 
 def test_plan_hierarchy_arrives_and_full_coarsening_does_not(plan_problem):
     levels, x0, b = plan_problem
-    seq = sc.rr_sequence(levels, x0, b, N_CYCLES, stop_at=1e-16)
+    seq = rst.rr_sequence(levels, x0, b, N_CYCLES, stop_at=1e-16)
     print(f"semi-coarsening: {len(seq) - 1} cycles to rr <= 1e-16 rr0 (recorded {OBSERVED_CYCLES}, N = {N_CYCLES})")
     assert seq[-1] <= 1e-16 * seq[0] and len(seq) - 1 <= N_CYCLES
     full, _ = sc.full_levels(PLAN_OMEGA, PLAN_WEIGHTS, PLAN_DAMP)
     assert [L.m for L in full] == [(63, 63), (31, 31), (15, 15), (7, 7), (3, 3), (1, 1)]
-    fseq = sc.rr_sequence(full, x0, b, 2 * N_CYCLES, stop_at=1e-16)
+    fseq = rst.rr_sequence(full, x0, b, 2 * N_CYCLES, stop_at=1e-16)
     print(f"full coarsening: rr / rr0 = {fseq[-1] / fseq[0]:.3e} after {len(fseq) - 1} cycles; last factor {fseq[-2] / fseq[-1]:.2f}")
     assert len(fseq) - 1 == 2 * N_CYCLES and fseq[-1] > 1e-16 * fseq[0]

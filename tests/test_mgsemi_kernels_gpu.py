@@ -1,5 +1,5 @@
 """The two transfer kernels on semi-coarsened level pairs (neptune_hip_mg_restrict / _prolong_add) against the
-NumPy restatement of tests/mgsemi_cases.py: each kernel alone, bit for bit on every cell, the untouched cells outside Omega
+NumPy restatement of tests/mg_restatement.py: each kernel alone, bit for bit on every cell, the untouched cells outside Omega
 included.
 
 Shapes: the smallest at which the kernels can go wrong.  Rank 3: fine box 9 x 18 x 268 with Omega 7 x 15 x 263 at (1, 2, 3)
@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import helpers
-import mgsemi_cases as sc
+import mg_restatement as rst
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
 
@@ -97,7 +97,7 @@ def test_restrict(nh, name, dtype, offset):
     x_c = _field(G.coarse_shape, dtype, 24, G.cw, inside=np.nan)
     for a in (b_c, x_c):
         a[tuple(0 for _ in a.shape)] = np.nan
-    want_b, want_x = sc.restrict(b_f, q_f, G.fw, 4.0, b_c, x_c, G.cw, G.axes)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, 4.0, b_c, x_c, G.cw, G.axes)
     bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
@@ -113,7 +113,7 @@ def test_prolong_add(nh, name, dtype, offset):
     x_c = _field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # the coarse rim is +0 whatever the field holds there
     x_f = _field(G.fine_shape, dtype, 32)
     x_f[tuple(0 for _ in x_f.shape)] = np.nan
-    want = sc.prolong_add(x_c, G.cw, x_f, G.fw, G.axes)
+    want = rst.prolong_add(x_c, G.cw, x_f, G.fw, G.axes)
     xd = _dev(nh, x_f, offset)
     nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()
@@ -133,7 +133,7 @@ def test_a_kept_axis_hands_minus_zero_and_nan_through(nh, dtype):
     k0, k1 = G.fw[2].start + 5, G.fw[2].start + 260
     b_f[:, :, k0] = -0.0
     b_f[:, :, k1] = np.nan
-    want_b, want_x = sc.restrict(b_f, q_f, G.fw, 1.0, np.zeros(G.coarse_shape, dtype), np.ones(G.coarse_shape, dtype), G.cw, G.axes)
+    want_b, want_x = rst.restrict(b_f, q_f, G.fw, 1.0, np.zeros(G.coarse_shape, dtype), np.ones(G.coarse_shape, dtype), G.cw, G.axes)
     bd, xd = _dev(nh, np.zeros(G.coarse_shape, dtype), 0), _dev(nh, np.ones(G.coarse_shape, dtype), 0)
     nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, 0), _dev(nh, q_f, 0), bd, xd)
     nh.torch.cuda.synchronize()
@@ -143,7 +143,7 @@ def test_a_kept_axis_hands_minus_zero_and_nan_through(nh, dtype):
     assert np.signbit(inner[:, :, 5]).all() and (inner[:, :, 5] == 0).all() and np.isnan(inner[:, :, 260]).all()
     assert np.isnan(inner).sum() == inner[:, :, 260].size and (np.delete(inner, [5, 260], axis=2) == 1).all()
     x_f = np.full(G.fine_shape, -0.0, dtype)
-    want = sc.prolong_add(got, G.cw, x_f, G.fw, G.axes)
+    want = rst.prolong_add(got, G.cw, x_f, G.fw, G.axes)
     fd = _dev(nh, x_f, 0)
     nh.mg.prolong_add(G.fine, G.coarse, bd, fd)
     nh.torch.cuda.synchronize()

@@ -20,6 +20,7 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_restatement as rst
 import mgsemi_cases as sc
 from helpers import bits_equal, mismatch_report
 
@@ -104,7 +105,7 @@ def _reference(P, cycles, check_every=1):
     """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
     key = (cycles, check_every)
     if key not in P.runs:
-        rr0, checks = sc.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
+        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
         P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
     return P.runs[key]
 
@@ -181,11 +182,11 @@ def test_stops_where_the_definition_says_on_the_plan_hierarchy(nh, check_every, 
     P = _problem(nh, "plan_f64")
     assert [L.m for L in P.ref[:5]] == [(63, 63), (63, 31), (63, 15), (63, 7), (31, 3)]
     if "seq" not in P.runs:
-        P.runs["seq"] = sc.rr_sequence(P.ref, P.x0, P.b, 6)
+        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6)
     seq = P.runs["seq"]
-    tol2 = sc.tol_between(seq, *between)
+    tol2 = rst.tol_between(seq, *between)
     max_cycles = len(seq) - 1
-    want_done, want_checks = sc.expected_stop(seq, check_every, max_cycles, tol2)
+    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
     assert want_done == between[1]
     (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
     print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
@@ -205,7 +206,8 @@ def test_mgcg_replay_from_the_traced_scalars_reproduces_every_field(nh, name, it
     counts, rz0 = nh.mg.cg_counts(), nh.mg.cg_rz0()
     assert done == iters and trace.shape == (iters, 3)
     assert counts == ((2, 0, 0, 2) if iters == 2 else (1, 4, 0, 5)), counts
-    rx, rr, rp, rz, checks, rr0_ref, rz0_ref = sc.replay(P.ref, P.x0, P.b, rz0, trace)
+    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, rz0, trace)
+    rx, rr, rp, rz = st.x, st.r, st.p, st.z
     print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
     assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(rz0 - rz0_ref[0]) <= rz0_ref[1]
     for k, sums in enumerate(checks):
@@ -242,13 +244,13 @@ def test_python_wrappers(nh):
     q = helpers.hash_field(R0.shape, P.dtype, seed=5)
     bc, xc = F.from_numpy(np.full(R1.shape, np.nan)), F.from_numpy(np.full(R1.shape, np.nan))
     nh.mg.restrict(h.levels[0], h.levels[1], b, F.from_numpy(q), bc, xc)
-    want_b, want_x = sc.restrict(P.b, q, R0.where, R0.rscale, np.full(R1.shape, np.nan), np.full(R1.shape, np.nan), R1.where, R0.axes)
+    want_b, want_x = rst.restrict(P.b, q, R0.where, R0.rscale, np.full(R1.shape, np.nan), np.full(R1.shape, np.nan), R1.where, R0.axes)
     nh.torch.cuda.synchronize()
     assert bits_equal(bc.numpy(), want_b) and bits_equal(xc.numpy(), want_x)
     xf = F.from_numpy(q)
     nh.mg.prolong_add(h.levels[0], h.levels[1], bc, xf)
     nh.torch.cuda.synchronize()
-    assert bits_equal(xf.numpy(), sc.prolong_add(want_b, R1.where, q, R0.where, R0.axes))
+    assert bits_equal(xf.numpy(), rst.prolong_add(want_b, R1.where, q, R0.where, R0.axes))
     # a hierarchy from coarsening_plan is the restated one
     plan = nh.mg.coarsening_plan((63, 63), (0.03, 1.0))
     assert [(p[0], p[2]) for p in plan] == [(L.m, L.axes) for L in _problem(nh, "plan_f64").ref]
