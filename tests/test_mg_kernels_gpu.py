@@ -8,10 +8,10 @@ outside Omega that the definition says is never read, and minv is NaN outside Om
 import numpy as np
 import pytest
 
-import helpers
+import mg_device
 import mg_restatement as rst
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import dev, field
 
 pytestmark = pytest.mark.gpu
 
@@ -30,66 +30,29 @@ IDS = [f"{n}-{np.dtype(d).name}" + ("-offset" if o else "") for n, d, o in RUNS]
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
-    return ns
+    return mg_device.namespace()
 
 
-class Geometry:
-    def __init__(self, nh, name, dtype):
-        fbox, flo, fm, cbox, clo = CASES[name]
-        cm = tuple((m - 1) // 2 for m in fm)
-        self.fine_shape, self.coarse_shape = fbox, cbox
-        self.fw = tuple(slice(l, l + m) for l, m in zip(flo, fm))
-        self.cw = tuple(slice(l, l + m) for l, m in zip(clo, cm))
-        self.dtype = dtype
-        like = lambda shape: nh.fields.DeviceField.from_numpy(np.zeros(shape, dtype))
-        bounds = lambda w: ([s.start for s in w], [s.stop for s in w])
-        # the levels carry geometry only here (entry None: the kernels alone never call the operator)
-        self.fine = nh.mg.Level(None, like(fbox), bounds(self.fw))
-        self.coarse = nh.mg.Level(None, like(cbox), bounds(self.cw))
-
-
-def _field(shape, dtype, seed, where=None, outside=None):
-    """hashed values with -0 sprinkled in; `outside` (e.g. NaN) on every cell that is not in `where`"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    if outside is not None:
-        keep = a[where].copy()
-        a[...] = outside
-        a[where] = keep
-    return a
-
-
-def _dev(nh, a, offset):
-    elems = offset // a.itemsize
-    return stc.offset_field(nh, a, elems) if offset else nh.fields.DeviceField.from_numpy(a)
+def Geometry(nh, name, dtype):
+    fbox, flo, fm, cbox, clo = CASES[name]
+    cm = tuple((m - 1) // 2 for m in fm)
+    return mg_device.Geometry(nh, (fbox, flo, fm), (cbox, clo, cm), dtype)
 
 
 @pytest.mark.parametrize("name,dtype,offset", RUNS, ids=IDS)
 def test_smooth(nh, name, dtype, offset):
     G = Geometry(nh, name, dtype)
     shape, w = G.fine_shape, G.fw
-    q = _field(shape, dtype, 11, w, np.nan)
-    b = _field(shape, dtype, 12, w, np.nan)
-    minv = _field(shape, dtype, 13, w, np.nan)
-    x = _field(shape, dtype, 14)
+    q = field(shape, dtype, 11, w, np.nan)
+    b = field(shape, dtype, 12, w, np.nan)
+    minv = field(shape, dtype, 13, w, np.nan)
+    x = field(shape, dtype, 14)
     x[tuple(0 for _ in shape)] = np.nan          # a NaN and a -0 outside Omega keep their bits
     x[tuple(n - 1 for n in shape)] = -0.0
     want = rst.smooth(q, b, minv, x, w)
-    G.fine.minv = _dev(nh, minv, offset)
-    xd = _dev(nh, x, offset)
-    nh.mg.smooth(G.fine, _dev(nh, q, offset), _dev(nh, b, offset), xd)
+    G.fine.minv = dev(nh, minv, offset)
+    xd = dev(nh, x, offset)
+    nh.mg.smooth(G.fine, dev(nh, q, offset), dev(nh, b, offset), xd)
     nh.torch.cuda.synchronize()
     got = xd.numpy()
     assert bits_equal(got, want), mismatch_report(got, want)
@@ -98,15 +61,15 @@ def test_smooth(nh, name, dtype, offset):
 @pytest.mark.parametrize("name,dtype,offset", RUNS, ids=IDS)
 def test_restrict(nh, name, dtype, offset):
     G = Geometry(nh, name, dtype)
-    b_f = _field(G.fine_shape, dtype, 21, G.fw, np.nan)       # nothing outside the fine Omega is read
-    q_f = _field(G.fine_shape, dtype, 22, G.fw, np.nan)
-    b_c = _field(G.coarse_shape, dtype, 23)
-    x_c = _field(G.coarse_shape, dtype, 24)
+    b_f = field(G.fine_shape, dtype, 21, G.fw, np.nan)       # nothing outside the fine Omega is read
+    q_f = field(G.fine_shape, dtype, 22, G.fw, np.nan)
+    b_c = field(G.coarse_shape, dtype, 23)
+    x_c = field(G.coarse_shape, dtype, 24)
     for a in (b_c, x_c):
         a[tuple(0 for _ in a.shape)] = np.nan
     want_b, want_x = rst.restrict(b_f, q_f, G.fw, rst.RSCALE, b_c, x_c, G.cw)
-    bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
-    nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
+    bd, xd = dev(nh, b_c, offset), dev(nh, x_c, offset)
+    nh.mg.restrict(G.fine, G.coarse, dev(nh, b_f, offset), dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
     got_b, got_x = bd.numpy(), xd.numpy()
     assert bits_equal(got_b, want_b), mismatch_report(got_b, want_b)
@@ -117,12 +80,12 @@ def test_restrict(nh, name, dtype, offset):
 @pytest.mark.parametrize("name,dtype,offset", RUNS, ids=IDS)
 def test_prolong_add(nh, name, dtype, offset):
     G = Geometry(nh, name, dtype)
-    x_c = _field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # the coarse rim is +0 whatever the field holds there
-    x_f = _field(G.fine_shape, dtype, 32)
+    x_c = field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # the coarse rim is +0 whatever the field holds there
+    x_f = field(G.fine_shape, dtype, 32)
     x_f[tuple(0 for _ in x_f.shape)] = np.nan
     want = rst.prolong_add(x_c, G.cw, x_f, G.fw)
-    xd = _dev(nh, x_f, offset)
-    nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
+    xd = dev(nh, x_f, offset)
+    nh.mg.prolong_add(G.fine, G.coarse, dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()
     got = xd.numpy()
     assert bits_equal(got, want), mismatch_report(got, want)

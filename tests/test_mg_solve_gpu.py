@@ -1,5 +1,5 @@
 """neptune_hip_mg_solve: V-cycles whose fields never leave the device, against the NumPy restatement of
-tests/mg_cases.py.
+tests/mg_restatement.py.
 
 No reduction enters a field, so after any number of cycles x_0 and every level's x_l, b_l must equal the restatement's bit
 for bit, whatever the device's launch path (plain launches or the replayed graph of one cycle).  rr_0 and every rr read
@@ -17,6 +17,7 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_device as mgd
 import mg_restatement as rst
 import pcg_cases as pc
 from helpers import bits_equal, mismatch_report
@@ -46,181 +47,72 @@ def _texts():
 
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"))
     ns.texts = _texts()
-    helpers.prefetch_modules([t for ts in ns.texts.values() for t in ts])      # every module once, side by side
-    ns.entries = {}
-    ns.cache = {}
+    mgd.prefetch([(t, False) for ts in ns.texts.values() for t in ts])      # every module once, side by side
     return ns
 
 
-def _entry(nh, text):
-    if text not in nh.entries:
-        nh.entries[text] = nh.lowering.compile_module(text).geom_entry("entry")
-    return nh.entries[text]
-
-
-class Problem:
-    pass
-
-
 def _problem(nh, name, rim=False):
-    """the compiled operators, the restatement's levels, x0 and b: built once per problem, x0 and b left unchanged"""
-    key = (name, rim)
-    if key not in nh.cache:
-        omega, n_levels, damp, dtype = PROBLEMS[name]
-        P = Problem()
-        P.dtype, P.n_levels = dtype, n_levels
-        P.ref, P.texts = mgc.star_levels(omega, n_levels, dtype, damp, texts=nh.texts[name])
-        P.entries = [_entry(nh, t) for t in P.texts]
-        P.others = [[] for _ in P.texts]
-        P.x0, P.b = mgc.problem_fields(P.ref[0].shape, P.ref[0].where, dtype, rim=rim)
-        for a in (P.x0, P.b):
-            a.setflags(write=False)
-        P.runs = {}
-        nh.cache[key] = P
-    return nh.cache[key]
-
-
-def _reference(P, cycles, check_every=1, n_levels=None, **kw):
-    """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
-    key = (cycles, check_every, n_levels, tuple(sorted(kw.items())))
-    if key not in P.runs:
-        levels = P.ref[:n_levels] if n_levels else P.ref
-        rr0, checks = rst.run(levels, P.x0, P.b, cycles, check_every=check_every, **kw)
-        P.runs[key] = (rr0, checks, [L.x.copy() for L in levels], [L.b.copy() for L in levels])
-    return P.runs[key]
-
-
-def _hierarchy(nh, P, n_levels=None):
-    """a device hierarchy whose work fields hold NaN; -> (h, x, b)"""
-    F = nh.fields.DeviceField
-    levels = []
-    for l, R in enumerate(P.ref[:n_levels] if n_levels else P.ref):
-        like = F.from_numpy(np.zeros(R.shape, P.dtype))
-        bounds = ([s.start for s in R.where], [s.stop for s in R.where])
-        levels.append(nh.mg.Level(P.entries[l], like, bounds, others=P.others[l], minv=F.from_numpy(R.minv), rscale=R.rscale))
-    h = nh.mg.Hierarchy(levels)
-    nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
-    h.q = [nan(f) for f in h.q]
-    h.x = [None] + [nan(f) for f in h.x[1:]]
-    h.b = [None] + [nan(f) for f in h.b[1:]]
-    return h, F.from_numpy(P.x0), F.from_numpy(P.b)
-
-
-def _solve(nh, P, max_cycles, tol2=0.0, check_every=1, n_levels=None, **kw):
-    h, x, b = _hierarchy(nh, P, n_levels)
-    res = nh.mg.solve(h, x, b, max_cycles=max_cycles, tol2=tol2, check_every=check_every, **kw)
-    nh.torch.cuda.synchronize()
-    xs = [x.numpy()] + [f.numpy() for f in h.x[1:]]
-    bs = [b.numpy()] + [f.numpy() for f in h.b[1:]]
-    return res, xs, bs, nh.mg.counts()
-
-
-def _check_against_reference(nh, P, cycles, check_every=1, n_levels=None, want_counts=None, **kw):
-    (done, rr0, rr_last, rr_checks), xs, bs, counts = _solve(nh, P, cycles, check_every=check_every, n_levels=n_levels, **kw)
-    ref_rr0, ref_checks, ref_x, ref_b = _reference(P, cycles, check_every, n_levels, **kw)
-    assert done == cycles and len(rr_checks) == len(ref_checks) == -(-cycles // check_every)
-    if want_counts is not None:
-        assert counts == want_counts, counts
-    print(f"rr0 = {rr0!r} (terms' sum {ref_rr0[0]!r}, bound {ref_rr0[1]:.3e})")
-    assert abs(rr0 - ref_rr0[0]) <= ref_rr0[1]
-    for k, (got, (want, bound)) in enumerate(zip(rr_checks, ref_checks)):
-        print(f"  check {k}: rr = {got!r} (terms' sum {want!r}, bound {bound:.3e})")
-        assert abs(got - want) <= bound
-    assert rr_last == rr_checks[-1]
-    for l, (got, want) in enumerate(zip(xs, ref_x)):
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(bs, ref_b)):
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
-    return xs, bs
+    def build(P):
+        omega, n_levels, damp, P.dtype = PROBLEMS[name]
+        P.ref, P.texts = mgc.star_levels(omega, n_levels, P.dtype, damp, texts=nh.texts[name])
+        P.x0, P.b = mgc.problem_fields(P.ref[0].shape, P.ref[0].where, P.dtype, rim=rim)
+    return mgd.problem(nh, (name, rim), build)
 
 
 @pytest.mark.parametrize("cycles", [2, 5])
 @pytest.mark.parametrize("name", sorted(PROBLEMS))
 def test_cycles_match_the_restatement(nh, name, cycles):
     P = _problem(nh, name)
-    _check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
+    mgd.check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
 
 
 def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
-    P = _problem(nh, "3d_f64")
-    monkeypatch.delenv("NEPTUNE_HIP_MG_GRAPH", raising=False)
-    res_g, xs_g, bs_g, counts_g = _solve(nh, P, 5)
-    monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", "0")          # read at every call
-    res_p, xs_p, bs_p, counts_p = _solve(nh, P, 5)
-    assert counts_g == (1, 4, 5) and counts_p == (5, 0, 5)
-    assert res_g == res_p
-    for a, b in zip(xs_g + bs_g, xs_p + bs_p):
-        assert bits_equal(a, b), mismatch_report(a, b)
-    _, _, ref_x, _ = _reference(P, 5)
-    assert bits_equal(xs_p[0], ref_x[0])
+    mgd.graph_vs_plain(nh, _problem(nh, "3d_f64"), monkeypatch, 5)
 
 
 @pytest.mark.parametrize("name,check_every,between", [("3d_f64", 1, (2, 3)), ("3d_f64", 3, (3, 6)), ("2d_f64", 3, (3, 6)),
                                                       ("3d_f32", 1, (1, 2))])
 def test_stops_where_the_definition_says(nh, name, check_every, between):
     P = _problem(nh, name)
-    if "seq" not in P.runs:
-        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
-    seq = P.runs["seq"]
-    tol2 = rst.tol_between(seq, *between)
-    max_cycles = len(seq) - 1
-    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
-    assert want_done == between[1]
-    (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
-    print(f"{name}: seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
-    assert (done, counts[2], len(rr_checks)) == (want_done, want_checks, want_checks)
-    assert counts[0] + counts[1] == done
-    assert rr_last == rr_checks[-1] <= tol2 and all(v > tol2 for v in rr_checks[:-1])
+    mgd.check_stop(nh, P, check_every, between, cycles=6 if P.dtype == np.float64 else 3, label=f"{name}: ")
 
 
 def test_a_converged_start_runs_no_cycle(nh):
     P = _problem(nh, "3d_f64")
-    ref_rr0 = _reference(P, 2)[0]
-    (done, rr0, rr_last, rr_checks), xs, bs, counts = _solve(nh, P, 5, tol2=2.0 * ref_rr0[0])
+    ref_rr0 = mgd.reference(P, 2)[0]
+    (done, rr0, rr_last, rr_checks), xs, bs, counts = mgd.solve(nh, P, 5, tol2=2.0 * ref_rr0[0])
     assert (done, rr_checks, counts) == (0, [], (0, 0, 0))
     assert rr0 == rr_last and abs(rr0 - ref_rr0[0]) <= ref_rr0[1]
     assert bits_equal(xs[0], P.x0) and bits_equal(bs[0], P.b)
     # max_cycles = 0: rr_0 is still formed
-    (done, rr0_again, _, rr_checks), xs, _, counts = _solve(nh, P, 0)
+    (done, rr0_again, _, rr_checks), xs, _, counts = mgd.solve(nh, P, 0)
     assert (done, rr_checks, counts, rr0_again) == (0, [], (0, 0, 0), rr0) and bits_equal(xs[0], P.x0)
 
 
 def test_one_level_is_smoothing_only(nh):
     P = _problem(nh, "3d_f64")
-    _check_against_reference(nh, P, 2, n_levels=1, coarse_sweeps=3, want_counts=(2, 0, 2))
-    _check_against_reference(nh, P, 4, n_levels=1, coarse_sweeps=3, check_every=3, want_counts=(1, 3, 2))
+    mgd.check_against_reference(nh, P, 2, n_levels=1, coarse_sweeps=3, want_counts=(2, 0, 2))
+    mgd.check_against_reference(nh, P, 4, n_levels=1, coarse_sweeps=3, check_every=3, want_counts=(1, 3, 2))
 
 
 def test_nonzero_dirichlet_rim(nh):
     P = _problem(nh, "3d_f64", rim=True)
-    xs, _ = _check_against_reference(nh, P, 2)
+    xs, _ = mgd.check_against_reference(nh, P, 2)
     outside = np.ones(P.x0.shape, bool)
     outside[P.ref[0].where] = False
     assert np.count_nonzero(P.x0[outside]) > 0 and bits_equal(xs[0][outside], P.x0[outside])
     zero = _problem(nh, "3d_f64")
-    assert not bits_equal(xs[0], _reference(zero, 2)[2][0])        # the rim values did enter, through A(x)
+    assert not bits_equal(xs[0], mgd.reference(zero, 2)[2][0])        # the rim values did enter, through A(x)
 
 
 def test_two_input_operator_with_a_coefficient_per_level(nh):
     """pcg_cases.pcg_module on two levels, w injected to the coarse grid in numpy: in_rest per level"""
-    if "pcg" not in nh.cache:
-        dtype = np.float64
+    def build(P):
+        dtype = P.dtype = np.float64
         shapes = mgc.level_shapes(PCG_OMEGA, 2)
-        P = Problem()
-        P.dtype, P.n_levels, P.texts = dtype, 2, nh.texts["pcg"]
+        P.texts = nh.texts["pcg"]
         w = [pc.w_field(shapes[0][0], dtype, values=(0.0, 1.0, 2.0, 4.0))]
         wc = np.zeros(shapes[1][0], dtype)
         wc[shapes[1][1]] = w[0][shapes[0][1]][1::2, 1::2, 1::2]     # the coarse cell j sits on the fine cell 2 j + 1
@@ -230,14 +122,11 @@ def test_two_input_operator_with_a_coefficient_per_level(nh):
             minv = np.full(shape, np.nan, dtype)
             minv[where] = (dtype(0.8) / (dtype(6.0) + wl[where])).astype(dtype)
             P.ref.append(rst.Level(rst.Operator(text, wl), shape, where, minv, dtype))
-        P.entries = [_entry(nh, t) for t in P.texts]
-        P.others = [[nh.fields.DeviceField.from_numpy(wl)] for wl in w]
+        P.rests = [[nh.fields.DeviceField.from_numpy(wl)] for wl in w]
         P.x0, P.b = mgc.problem_fields(shapes[0][0], shapes[0][1], dtype)
-        P.runs = {}
-        nh.cache["pcg"] = P
-    P = nh.cache["pcg"]
-    _check_against_reference(nh, P, 3, want_counts=(1, 2, 3))
-    rr0, checks, _, _ = _reference(P, 3)
+    P = mgd.problem(nh, "pcg", build)
+    mgd.check_against_reference(nh, P, 3, want_counts=(1, 2, 3))
+    rr0, checks, _, _ = mgd.reference(P, 3)
     assert checks[-1][0] < rr0[0]
 
 
@@ -245,17 +134,15 @@ def test_builtin_body_on_level_zero(nh):
     """level 0 runs the built-in 7-point body (fn = NULL), level 1 a lowered module"""
     dtype = np.float64
     shapes = mgc.level_shapes(BUILTIN_OMEGA, 2)
-    P = Problem()
-    P.dtype, P.n_levels = dtype, 2
+    P = mgd.Problem()
+    P.dtype = dtype
     A0 = lambda u: helpers.oracle_entry("3d7", u)
     P.ref = [rst.Level(A0, shapes[0][0], shapes[0][1], mgc.minv_field(shapes[0][0], shapes[0][1], dtype, 0.125), dtype),
              rst.Level(rst.Operator(nh.texts["builtin"][0]), shapes[1][0], shapes[1][1],
                        mgc.minv_field(shapes[1][0], shapes[1][1], dtype, 0.8), dtype)]
-    P.entries = [nh.capi.BODY_LAP3D7_F64, _entry(nh, nh.texts["builtin"][0])]
-    P.others = [[], []]
+    P.entries = [nh.capi.BODY_LAP3D7_F64, mgd.entry(nh, nh.texts["builtin"][0])]
     P.x0, P.b = mgc.problem_fields(shapes[0][0], shapes[0][1], dtype)
-    P.runs = {}
-    _check_against_reference(nh, P, 3, want_counts=(1, 2, 3))
+    mgd.check_against_reference(nh, mgd.finish(nh, P), 3, want_counts=(1, 2, 3))
 
 
 def test_jacobi_weights(nh):
@@ -274,7 +161,7 @@ def test_jacobi_weights(nh):
     assert bits_equal(w, want), mismatch_report(w, want)
     assert bits_equal(w[R.where], R.minv[R.where])
     # a zero diagonal is refused as apply.jacobi_minv refuses it
-    zero = _entry(nh, nh.texts["zero_diagonal"][0])
+    zero = mgd.entry(nh, nh.texts["zero_diagonal"][0])
     with pytest.raises(ValueError, match="0 or not finite"):
         nh.mg.jacobi_weights(zero, like, bounds)
     # the Python layer names the level and the dimension of a hierarchy that does not nest
@@ -286,7 +173,7 @@ def test_jacobi_weights(nh):
 
 def test_refusals_on_device_pointers(nh):
     P = _problem(nh, "3d_f64")
-    h, x, b = _hierarchy(nh, P)
+    h, x, b, _ = mgd.hierarchy(nh, P)
     E, lib = nh.capi.EINVAL, nh.lib
     x.tensor.fill_(-3.0)
 

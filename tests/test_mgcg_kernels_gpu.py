@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 import cg_cases as cc
-import helpers
+import mg_device
 import mg_restatement as rst
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import dev, field
 
 pytestmark = pytest.mark.gpu
 
@@ -30,55 +30,27 @@ IDS = [f"{n}-{np.dtype(d).name}" + ("-offset" if o else "") for n, d, o in RUNS]
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
-    return ns
-
-
-def _field(shape, dtype, seed, where=None, outside=None):
-    """hashed values with -0 sprinkled in; `outside` (e.g. NaN) on every cell that is not in `where`"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    if outside is not None:
-        keep = a[where].copy()
-        a[...] = outside
-        a[where] = keep
-    return a
-
-
-def _dev(nh, a, offset):
-    elems = offset // a.itemsize
-    return stc.offset_field(nh, a, elems) if offset else nh.fields.DeviceField.from_numpy(a)
+    return mg_device.namespace()
 
 
 @pytest.mark.parametrize("name,dtype,offset", RUNS, ids=IDS)
 def test_smooth_dot(nh, name, dtype, offset):
     box, lo, m = CASES[name]
     w = tuple(slice(l, l + n) for l, n in zip(lo, m))
-    q = _field(box, dtype, 11, w, np.nan)
-    b = _field(box, dtype, 12, w, np.nan)
-    minv = _field(box, dtype, 13, w, np.nan)
-    x = _field(box, dtype, 14)
+    q = field(box, dtype, 11, w, np.nan)
+    b = field(box, dtype, 12, w, np.nan)
+    minv = field(box, dtype, 13, w, np.nan)
+    x = field(box, dtype, 14)
     x[tuple(0 for _ in box)] = np.nan          # a NaN and a -0 outside Omega keep their bits
     x[tuple(n - 1 for n in box)] = -0.0
     want = rst.smooth(q, b, minv, x, w)
     want_sum, bound = cc.dot_terms(b, want, w)
     level = nh.mg.Level(None, nh.fields.DeviceField.from_numpy(np.zeros(box, dtype)), ([s.start for s in w], [s.stop for s in w]))
-    level.minv = _dev(nh, minv, offset)
-    xd = _dev(nh, x, offset)
+    level.minv = dev(nh, minv, offset)
+    xd = dev(nh, x, offset)
     # the sum lands in the second of three elements: its neighbours keep their values
     out = nh.torch.full((3,), -7.0, dtype=xd.tensor.dtype, device="cuda")
-    assert nh.mg.smooth_dot(level, _dev(nh, q, offset), _dev(nh, b, offset), xd, dot_out=out[1:2]) is None
+    assert nh.mg.smooth_dot(level, dev(nh, q, offset), dev(nh, b, offset), xd, dot_out=out[1:2]) is None
     nh.torch.cuda.synchronize()
     got, sums = xd.numpy(), out.cpu().numpy()
     assert bits_equal(got, want), mismatch_report(got, want)
@@ -86,8 +58,8 @@ def test_smooth_dot(nh, name, dtype, offset):
     assert sums[0] == -7.0 and sums[2] == -7.0
     assert np.isfinite(sums[1]) and abs(float(sums[1]) - want_sum) <= bound
     # the blocking form returns the same sum, bit for bit (one fixed tree), from the same start
-    xd2 = _dev(nh, x, offset)
-    again = nh.mg.smooth_dot(level, _dev(nh, q, offset), _dev(nh, b, offset), xd2)
+    xd2 = dev(nh, x, offset)
+    again = nh.mg.smooth_dot(level, dev(nh, q, offset), dev(nh, b, offset), xd2)
     assert again == float(sums[1]) and bits_equal(xd2.numpy(), want)
 
 

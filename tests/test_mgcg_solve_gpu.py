@@ -20,11 +20,11 @@ import pytest
 import cg_cases
 import helpers
 import mg_cases as mgc
+import mg_device as mgd
 import mg_restatement as rst
 import mgcg_cases as mg
 import pcg_cases as pc
-import solver_trace_cases as stc
-from helpers import bits_equal, mismatch_report
+from helpers import bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -53,154 +53,30 @@ def _texts():
     return out
 
 
-def _prefetch(lowering, texts):
-    """helpers.prefetch_modules for this file's modules: level 0's with their dot entries (another cache key), the coarser
-    levels' plain; host threads only, nothing is loaded"""
-    from concurrent.futures import ThreadPoolExecutor
-    jobs = {}
-    for name, ts in texts.items():
-        for l, t in enumerate(ts):
-            jobs[(t, l == 0 and name != "builtin")] = None
-
-    def one(job):
-        try:
-            lowering.compile_module(job[0], load=False, dot_entries=job[1])
-        except Exception:       # noqa: BLE001 - the test that needs this module shows the diagnostic
-            pass
-    with ThreadPoolExecutor(max_workers=12) as pool:
-        list(pool.map(one, jobs))
-
-
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"))
     ns.texts = _texts()
-    _prefetch(lowering, ns.texts)                # every module once, side by side
-    ns.entries = {}
-    ns.cache = {}
+    # every module once, side by side: level 0's with their dot entries ("builtin" lists level 1 alone)
+    mgd.prefetch([(t, l == 0 and name != "builtin") for name, ts in ns.texts.items() for l, t in enumerate(ts)])
     return ns
 
 
-def _entry(nh, text, level0):
-    """level 0's entry carries the dot-monitored launch as well; the coarser levels' are plain geometry-level entries"""
-    key = (text, level0)
-    if key not in nh.entries:
-        nh.entries[key] = (nh.lowering.compile_module(text, dot_entries=True).dot_entry("entry") if level0 else
-                           nh.lowering.compile_module(text).geom_entry("entry"))
-    return nh.entries[key]
-
-
-class Problem:
-    pass
-
-
-def _finish(nh, P, rim=False):
-    P.entries = [_entry(nh, t, l == 0) for l, t in enumerate(P.texts)]
+def _fields(P, rim=False):
     P.x0, P.b = mgc.problem_fields(P.ref[0].shape, P.ref[0].where, P.dtype, rim=rim)
-    for a in (P.x0, P.b):
-        a.setflags(write=False)
-    P.runs = {}
-    return P
 
 
 def _problem(nh, name, rim=False):
-    """the compiled operators, the restatement's levels, x0 and b: built once per problem, x0 and b left unchanged"""
-    key = (name, rim)
-    if key not in nh.cache:
-        omega, n_levels, damp, dtype = PROBLEMS[name]
-        P = Problem()
-        P.dtype = dtype
-        P.ref, P.texts = mg.star_levels(omega, n_levels, dtype, damp, texts=nh.texts[name])
-        P.others = [[] for _ in P.texts]
-        nh.cache[key] = _finish(nh, P, rim)
-    return nh.cache[key]
+    def build(P):
+        omega, n_levels, damp, P.dtype = PROBLEMS[name]
+        P.ref, P.texts = mg.star_levels(omega, n_levels, P.dtype, damp, texts=nh.texts[name])
+        _fields(P, rim)
+    return mgd.problem(nh, (name, rim), build, dots=(0,))
 
 
-def _hierarchy(nh, P, offset=0):
-    """a device hierarchy whose work fields hold NaN; -> (h, x, b, [r, p, z]); offset: level 0's fields and the work fields
-    start that many elements into larger allocations"""
-    F = nh.fields.DeviceField
-    make = (lambda a: stc.offset_field(nh, a, offset)) if offset else F.from_numpy
-    levels = []
-    for l, R in enumerate(P.ref):
-        like = F.from_numpy(np.zeros(R.shape, P.dtype))
-        bounds = ([s.start for s in R.where], [s.stop for s in R.where])
-        minv = make(R.minv) if l == 0 else F.from_numpy(R.minv)
-        levels.append(nh.mg.Level(P.entries[l], like, bounds, others=P.others[l], minv=minv, rscale=R.rscale))
-    h = nh.mg.Hierarchy(levels)
-    nan = lambda f: np.full(f.shape, np.nan, P.dtype)
-    h.q = [make(nan(f)) if l == 0 else F.from_numpy(nan(f)) for l, f in enumerate(h.q)]
-    h.x = [None] + [F.from_numpy(nan(f)) for f in h.x[1:]]
-    h.b = [None] + [F.from_numpy(nan(f)) for f in h.b[1:]]
-    work = [make(nan(h.q[0])) for _ in range(3)]
-    return h, make(P.x0), make(P.b), work
-
-
-class Run:
-    pass
-
-
-def _solve(nh, P, max_iters, tol2=0.0, check_every=1, trace=True, offset=0, b=None, **kw):
-    h, x, bf, work = _hierarchy(nh, P, offset)
-    if b is not None:
-        bf.tensor.copy_(nh.torch.from_numpy(np.ascontiguousarray(b)))
-    res = nh.mg.cg_solve(h, x, bf, max_iters=max_iters, tol2=tol2, check_every=check_every, trace=trace, work=work, **kw)
-    nh.torch.cuda.synchronize()
-    R = Run()
-    R.res, R.x, R.b = res, x.numpy(), bf.numpy()
-    R.r, R.p, R.z = (f.numpy() for f in work)
-    R.xs = [f.numpy() for f in h.x[1:]]
-    R.bs = [f.numpy() for f in h.b[1:]]
-    R.q = [f.numpy() for f in h.q]
-    R.counts, R.rz0 = nh.mg.cg_counts(), nh.mg.cg_rz0()
-    return R
-
-
-def _check_replay(nh, P, iters, check_every=1, want_counts=None, offset=0, **kw):
-    """one traced run of `iters` iterations against the restatement's replay; -> the run"""
-    R = _solve(nh, P, iters, check_every=check_every, offset=offset, **kw)
-    done, rr0, rr_last, trace = R.res
-    assert done == iters and trace.shape == (iters, 3)
-    assert R.counts[0] + R.counts[1] == iters and R.counts[3] == -(-iters // check_every)
-    if want_counts is not None:
-        assert R.counts == want_counts, R.counts
-    sw = {k: v for k, v in kw.items() if k in ("sweeps", "coarse_sweeps")}
-    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, R.rz0, trace, **sw)
-    x, r, p, z = st.x, st.r, st.p, st.z
-    print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
-    assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
-    for k, sums in enumerate(checks):
-        print(f"  k={k}: " + "  ".join(f"{nm} = {trace[k][c]!r} (sum {s!r}, bound {bd:.3e})"
-                                        for c, (nm, (s, bd)) in enumerate(zip(("pq", "rz'", "rr'"), sums))))
-        for c, (s, bd) in enumerate(sums):
-            assert abs(float(trace[k][c]) - s) <= bd
-    assert rr_last == float(trace[-1][2])
-    R.checks = checks
-    for name, got, want in (("x", R.x, x), ("r", R.r, r), ("p", R.p, p), ("z", R.z, z)):
-        assert bits_equal(got, want), f"{name}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(R.xs, [L.x for L in P.ref[1:]]), 1):
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(R.bs, [L.b for L in P.ref[1:]]), 1):
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
-    # cells of x outside Omega are never changed; r, p and z are +0 there; b is the caller's
-    outside = np.ones(P.x0.shape, bool)
-    outside[P.ref[0].where] = False
-    zero = np.zeros(int(outside.sum()), P.dtype)
-    assert bits_equal(R.x[outside], P.x0[outside]) and bits_equal(R.b, P.b)
-    for a in (R.r, R.p, R.z):
-        assert bits_equal(a[outside], zero)
-    return R
+def _check_replay(nh, P, iters, **kw):
+    """mg_device.check_replay, and what the fields hold outside Omega"""
+    return mgd.check_replay(nh, P, iters, outside=True, **kw)
 
 
 @pytest.mark.parametrize("iters", [2, 5])
@@ -215,13 +91,11 @@ def test_replay_from_the_traced_scalars_reproduces_every_field(nh, name, iters):
 def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
     P = _problem(nh, "3d_f64")
     monkeypatch.delenv("NEPTUNE_HIP_MG_GRAPH", raising=False)
-    G = _solve(nh, P, 5)
+    G = mgd.cg(nh, P, 5)
     monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", "0")          # read at every call
     Pl = _check_replay(nh, P, 5, want_counts=(5, 0, 0, 5))
     assert G.counts == (1, 4, 0, 5)
-    assert G.res[:3] == Pl.res[:3] and bits_equal(G.res[3], Pl.res[3]) and G.rz0 == Pl.rz0
-    for a, b in zip([G.x, G.r, G.p, G.z] + G.xs + G.bs, [Pl.x, Pl.r, Pl.p, Pl.z] + Pl.xs + Pl.bs):
-        assert bits_equal(a, b), mismatch_report(a, b)
+    mgd.same_runs(G, Pl)
 
 
 def test_fallback_runs_the_same_iteration(nh):
@@ -239,53 +113,43 @@ def test_fallback_runs_the_same_iteration(nh):
                                                       ("3d_f32", 1, (1, 2))])
 def test_stops_where_the_definition_says(nh, name, check_every, between):
     P = _problem(nh, name)
-    if "seq" not in P.runs:
-        P.runs["seq"] = rst.numpy_mgcg(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
-    seq = P.runs["seq"]
-    tol2 = rst.tol_between(seq, *between)
-    max_iters = len(seq) - 1
-    want_done, want_checks = rst.expected_stop(seq, check_every, max_iters, tol2)
-    assert want_done == between[1]
-    R = _solve(nh, P, max_iters, tol2=tol2, check_every=check_every, trace=False)
-    done, rr0, rr_last = R.res
-    print(f"{name}: seq = {seq}, tol2 = {tol2!r}, done = {done}, rr_last = {rr_last!r}")
-    assert (done, R.counts[3]) == (want_done, want_checks)
-    assert R.counts[0] + R.counts[1] == done
-    assert rr_last <= tol2 < rr0
+    sequence = lambda: rst.numpy_mgcg(P.ref, P.x0, P.b, 6 if P.dtype == np.float64 else 3)
+    seq, tol2, max_iters, want = mgd.stop_schedule(P, sequence, check_every, between)
+    R = mgd.cg(nh, P, max_iters, tol2=tol2, check_every=check_every, trace=False)
+    mgd.check_cg_stop(R, seq, tol2, want, label=f"{name}: ")
 
 
 def test_a_converged_start_runs_no_iteration(nh):
     P = _problem(nh, "3d_f64")
     rr0_ref = cg_cases.dot_terms(P.b, P.b, P.ref[0].where)          # x0 = 0: r = b on Omega
-    R = _solve(nh, P, 5, tol2=2.0 * rr0_ref[0])
+    R = mgd.cg(nh, P, 5, tol2=2.0 * rr0_ref[0])
     done, rr0, rr_last, trace = R.res
     assert (done, R.counts, R.rz0, trace.shape) == (0, (0, 0, 0, 0), 0.0, (0, 3))
     assert rr0 == rr_last and abs(rr0 - rr0_ref[0]) <= rr0_ref[1]
     assert bits_equal(R.x, P.x0) and bits_equal(R.b, P.b)
     # max_iters = 0: rr_0 is still formed
-    R = _solve(nh, P, 0, trace=False)
+    R = mgd.cg(nh, P, 0, trace=False)
     assert R.res == (0, rr0, rr0) and R.counts == (0, 0, 0, 0) and bits_equal(R.x, P.x0)
 
 
 def test_fields_at_an_8_byte_offset_run_the_scalar_kernel_forms(nh):
     """x, b, r, p, z, q_0 and minv_0 one f64 element into larger allocations: not 16-byte aligned, so the grid-stride forms of
     the update and direction kernels run"""
-    _check_replay(nh, _problem(nh, "3d_f64"), 3, check_every=2, offset=1, want_counts=(1, 2, 0, 2))
+    _check_replay(nh, _problem(nh, "3d_f64"), 3, check_every=2, offset=8, want_counts=(1, 2, 0, 2))
 
 
 def test_more_cells_than_lanes_take_the_grid_stride_loops_round_again(nh):
     """2 129 920 cells in fields one element off 16-byte alignment: the scalar forms' grid is capped at 256 * 32 workgroups
     (2 097 152 lanes), so 32 768 lanes make a second trip; unequal rims on level 0.  Two iterations of V(1, 1) with two coarse
     sweeps: a wrong stride, or a cell summed twice, shows in the fields, in rz' and in rr'."""
-    if "big" not in nh.cache:
-        P = Problem()
+    def build(P):
         P.dtype, P.texts = np.float64, nh.texts["big"]
         shapes = mgc.level_shapes(BIG_OMEGA, 2, BIG_RIMS)
         P.ref = [rst.Level(rst.Operator(text), shape, where, mgc.minv_field(shape, where, np.float64, 6.0 / 7.0, outside=0.0 if l == 0 else np.nan),
                            np.float64) for l, (text, (shape, where)) in enumerate(zip(P.texts, shapes))]
-        P.others = [[], []]
-        nh.cache["big"] = _finish(nh, P)
-    _check_replay(nh, nh.cache["big"], 2, check_every=2, offset=1, sweeps=1, coarse_sweeps=2, want_counts=(2, 0, 0, 1))
+        _fields(P)
+    P = mgd.problem(nh, "big", build, dots=(0,))
+    _check_replay(nh, P, 2, check_every=2, offset=8, sweeps=1, coarse_sweeps=2, want_counts=(2, 0, 0, 1))
 
 
 def test_nonzero_dirichlet_rim(nh):
@@ -294,17 +158,16 @@ def test_nonzero_dirichlet_rim(nh):
     outside = np.ones(P.x0.shape, bool)
     outside[P.ref[0].where] = False
     assert np.count_nonzero(P.x0[outside]) > 0 and bits_equal(R.x[outside], P.x0[outside])
-    zero = _solve(nh, _problem(nh, "3d_f64"), 2)
+    zero = mgd.cg(nh, _problem(nh, "3d_f64"), 2)
     assert not bits_equal(R.x, zero.x)        # the rim values did enter, through A(x)
 
 
 def test_two_input_operator_with_a_coefficient_per_level(nh):
     """pcg_cases.pcg_module on two levels, w injected to the coarse grid in numpy: in_rest per level"""
-    if "pcg" not in nh.cache:
-        dtype = np.float64
+    def build(P):
+        dtype = P.dtype = np.float64
         shapes = mgc.level_shapes(PCG_OMEGA, 2)
-        P = Problem()
-        P.dtype, P.texts = dtype, nh.texts["pcg"]
+        P.texts = nh.texts["pcg"]
         w = [pc.w_field(shapes[0][0], dtype, values=(0.0, 1.0, 2.0, 4.0))]
         wc = np.zeros(shapes[1][0], dtype)
         wc[shapes[1][1]] = w[0][shapes[0][1]][1::2, 1::2, 1::2]     # the coarse cell j sits on the fine cell 2 j + 1
@@ -314,9 +177,9 @@ def test_two_input_operator_with_a_coefficient_per_level(nh):
             minv = np.full(shape, 0.0 if l == 0 else np.nan, dtype)
             minv[where] = (dtype(0.8) / (dtype(12.0) + wl[where])).astype(dtype)     # pcg_module's diagonal is 4 rank + w
             P.ref.append(rst.Level(rst.Operator(text, wl), shape, where, minv, dtype))
-        P.others = [[nh.fields.DeviceField.from_numpy(wl)] for wl in w]
-        nh.cache["pcg"] = _finish(nh, P)
-    P = nh.cache["pcg"]
+        P.rests = [[nh.fields.DeviceField.from_numpy(wl)] for wl in w]
+        _fields(P)
+    P = mgd.problem(nh, "pcg", build, dots=(0,))
     R = _check_replay(nh, P, 3, want_counts=(1, 2, 0, 3))
     assert R.res[2] < R.res[1]
 
@@ -326,26 +189,25 @@ def test_builtin_body_on_level_zero(nh):
     a lowered module"""
     dtype = np.float64
     shapes = mgc.level_shapes(BUILTIN_OMEGA, 2)
-    P = Problem()
+    P = mgd.Problem()
     P.dtype = dtype
     A0 = lambda u: helpers.oracle_entry("3d7", u)
     P.ref = [rst.Level(A0, shapes[0][0], shapes[0][1], mgc.minv_field(shapes[0][0], shapes[0][1], dtype, 0.125, outside=0.0), dtype),
              rst.Level(rst.Operator(nh.texts["builtin"][0]), shapes[1][0], shapes[1][1],
                        mgc.minv_field(shapes[1][0], shapes[1][1], dtype, 0.8), dtype)]
-    P.entries = [nh.capi.BODY_LAP3D7_F64, _entry(nh, nh.texts["builtin"][0], False)]
-    P.others = [[], []]
+    P.entries = [nh.capi.BODY_LAP3D7_F64, mgd.entry(nh, nh.texts["builtin"][0])]
     P.x0, P.b = mgc.problem_fields(shapes[0][0], shapes[0][1], dtype)
-    _check_replay(nh, P, 3, want_counts=(1, 2, 0, 3))
+    _check_replay(nh, mgd.finish(nh, P), 3, want_counts=(1, 2, 0, 3))
 
 
 def test_exact_breakdown_leaves_everything_as_it_is(nh):
     P = _problem(nh, "3d_f64", rim=True)
     b = P.ref[0].A(P.x0)                      # b = A(x) exactly: the residual is +0 everywhere on Omega
-    R = _solve(nh, P, 5, b=b)
+    R = mgd.cg(nh, P, 5, b=b)
     assert R.res[:3] == (0, 0.0, 0.0) and R.rz0 == 0.0 and R.counts == (0, 0, 0, 0)
     assert bits_equal(R.x, P.x0)
     # tol2 < 0 forces the iterations to run: alpha = beta = 0, nothing moves, nothing becomes NaN
-    R = _solve(nh, P, 3, tol2=-1.0, b=b)
+    R = mgd.cg(nh, P, 3, tol2=-1.0, b=b)
     done, rr0, rr_last, trace = R.res
     assert (done, rr0, rr_last) == (3, 0.0, 0.0) and R.rz0 == 0.0 and R.counts[0] + R.counts[1] == 3 and R.counts[3] == 3
     assert bits_equal(R.x, P.x0)
@@ -357,8 +219,8 @@ def test_exact_breakdown_leaves_everything_as_it_is(nh):
 
 def test_python_wrapper(nh):
     P = _problem(nh, "3d_f64")
-    h, x, b, _ = _hierarchy(nh, P)
-    ref = _solve(nh, P, 4)
+    h, x, b, _ = mgd.hierarchy(nh, P)
+    ref = mgd.cg(nh, P, 4)
     # its defaults: V(2, 2), 8 coarse sweeps, no trace, work fields of its own, the entry's own dot entry
     res = nh.mg.cg_solve(h, x, b, max_iters=4)
     assert len(res) == 3 and res == ref.res[:3] and bits_equal(x.numpy(), ref.x)
@@ -373,7 +235,7 @@ def test_python_wrapper(nh):
 
 def test_refusals_on_device_pointers(nh):
     P = _problem(nh, "3d_f64")
-    h, x, b, work = _hierarchy(nh, P)
+    h, x, b, work = mgd.hierarchy(nh, P)
     E, lib = nh.capi.EINVAL, nh.lib
     x.tensor.fill_(-3.0)
     for f in work:

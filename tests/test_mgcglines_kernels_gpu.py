@@ -18,11 +18,10 @@ import numpy as np
 import pytest
 
 import cg_cases as cc
-import helpers
+import mg_device
 import mg_restatement as rst
-import mglines_cases as lc
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import level as _level, outside_of as _outside
 
 pytestmark = pytest.mark.gpu
 
@@ -46,67 +45,11 @@ IDS = [f"{n}-axis{a}-{np.dtype(d).name}" for n, a, d in RUNS]
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
-    return ns
-
-
-def _field(shape, dtype, seed, where=None, outside=None):
-    """hashed values with -0 sprinkled in; `outside` (e.g. NaN) on every cell that is not in `where`"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    if outside is not None:
-        keep = a[where].copy()
-        a[...] = outside
-        a[where] = keep
-    return a
-
-
-def _factors(shape, where, axis, dtype, seed):
-    """the restatement's factors of a random diagonally dominant T along `axis`: NaN outside Omega, on lo at i = 0 and on up
-    at i = m - 1"""
-    rng = np.random.default_rng(seed)
-    m = tuple(s.stop - s.start for s in where)
-    lower, diag, upper = (np.zeros(shape, dtype) for _ in range(3))
-    lower[where] = rng.uniform(-1.0, 1.0, m)
-    upper[where] = rng.uniform(-1.0, 1.0, m)
-    diag[where] = rng.uniform(2.5, 4.0, m) * rng.choice([-1.0, 1.0], m)
-    lo, inv, up = lc.factors(lower, diag, upper, where, axis, 0.8, outside=np.nan)
-    first, last = list(where), list(where)
-    first[axis], last[axis] = where[axis].start, where[axis].stop - 1
-    lo[tuple(first)] = np.nan
-    up[tuple(last)] = np.nan
-    return lo, inv, up
+    return mg_device.namespace()
 
 
 def _problem(name, axis, dtype):
-    box, lo_corner, om, _ = CASES[name]
-    where = tuple(slice(l, l + m) for l, m in zip(lo_corner, om))
-    q = _field(box, dtype, 41, where, np.nan)
-    b = _field(box, dtype, 42, where, np.nan)
-    x = _field(box, dtype, 43)
-    x[tuple(0 for _ in box)] = np.nan                                # a cell outside Omega: it keeps its bits
-    return where, q, b, x, _factors(box, where, axis, dtype, 7 + axis)
-
-
-def _level(nh, shape, dtype, where):
-    return nh.mg.Level(None, nh.fields.DeviceField.from_numpy(np.zeros(shape, dtype)), ([s.start for s in where], [s.stop for s in where]))
-
-
-def _outside(shape, where):
-    outside = np.ones(shape, bool)
-    outside[where] = False
-    return outside
+    return mg_device.line_problem(*CASES[name][:3], axis, dtype)
 
 
 @pytest.mark.parametrize("name,axis,dtype", RUNS, ids=IDS)
@@ -116,7 +59,7 @@ def test_apply_free_stage_matches_the_restatement_and_the_plain_kernel(nh, name,
     x_nan[where] = np.nan                                             # the stage must not read x on Omega
     want = rst.first_stage(b, lo, inv, up, x_nan, where, axis)
     assert np.isfinite(want[where]).all()
-    dev = lambda a: stc.offset_field(nh, a, 8 // a.itemsize)          # every field 8 bytes into a larger allocation
+    dev = lambda a: mg_device.dev(nh, a, 8)                           # every field 8 bytes into a larger allocation
     level = _level(nh, x.shape, dtype, where)
     stage = nh.mg.LineStage(axis, dev(lo), dev(inv), dev(up))
     bd, xd = dev(b), dev(x_nan)
@@ -138,7 +81,7 @@ def test_stage_with_a_sum_matches_the_restatement(nh, name, axis, dtype):
     want = rst.line_stage(q, b, lo, inv, up, x, where, axis)
     assert np.isfinite(want[where]).all()
     total, bound = cc.dot_terms(b, want, where)
-    dev = lambda a: stc.offset_field(nh, a, 8 // a.itemsize)
+    dev = lambda a: mg_device.dev(nh, a, 8)
     level = _level(nh, x.shape, dtype, where)
     stage = nh.mg.LineStage(axis, dev(lo), dev(inv), dev(up))
     qd, xd = dev(q), dev(x)

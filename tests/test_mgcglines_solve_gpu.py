@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import mg_cases as mgc
+import mg_device as mgd
 import mg_restatement as rst
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
@@ -39,18 +40,7 @@ PROBLEMS["3d_f64_point"] = ("3d", np.float64, "point")
 
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"))
     ns.built, texts = {}, {}
     for name, (sk, dtype, cfg) in PROBLEMS.items():
         omega, damp = SHAPES[sk]
@@ -61,45 +51,14 @@ def nh(built_libs, tmp_path_factory):
             levels[0].minv = mgc.minv_field(levels[0].shape, levels[0].where, dtype, damp, outside=0.0)
         ns.built[name] = (levels, ts)
     ns.flux = lc.flux_levels((0, 1))
-    _prefetch(lowering, [ts for ts in texts.values()] + [ns.flux[1]])
-    ns.entries, ns.cache = {}, {}
+    # every module once, side by side: level 0's with its dot entry
+    mgd.prefetch([(t, l == 0) for ts in list(texts.values()) + [ns.flux[1]] for l, t in enumerate(ts)])
     return ns
 
 
-def _prefetch(lowering, text_lists):
-    """every module compiled once, side by side (host threads only, nothing is loaded): level 0's with its dot entry"""
-    from concurrent.futures import ThreadPoolExecutor
-    jobs = {}
-    for ts in text_lists:
-        for l, t in enumerate(ts):
-            jobs[(t, l == 0)] = None
-
-    def one(job):
-        try:
-            lowering.compile_module(job[0], load=False, dot_entries=job[1])
-        except Exception:       # noqa: BLE001 - the test that needs this module shows the diagnostic
-            pass
-    with ThreadPoolExecutor(max_workers=12) as pool:
-        list(pool.map(one, jobs))
-
-
-def _entry(nh, text, level0):
-    key = (text, level0)
-    if key not in nh.entries:
-        nh.entries[key] = (nh.lowering.compile_module(text, dot_entries=True).dot_entry("entry") if level0 else
-                           nh.lowering.compile_module(text).geom_entry("entry"))
-    return nh.entries[key]
-
-
-class Problem:
-    pass
-
-
 def _problem(nh, name, rim=False):
-    """the compiled operators, the restatement's levels, x0 and b: built once per problem, x0 and b left unchanged"""
-    key = (name, rim)
-    if key not in nh.cache:
-        P = Problem()
+    """the restatement's own stages on the device, and a level with stages gets no minv"""
+    def build(P):
         if name == "flux":
             P.ref, P.texts, _ = nh.flux
             P.dtype = np.float64
@@ -108,86 +67,22 @@ def _problem(nh, name, rim=False):
             P.dtype = PROBLEMS[name][1]
             P.ref, P.texts = nh.built[name]
             P.x0, P.b = mgc.problem_fields(P.ref[0].shape, P.ref[0].where, P.dtype, rim=rim)
-        P.entries = [_entry(nh, t, l == 0) for l, t in enumerate(P.texts)]
-        for a in (P.x0, P.b):
-            a.setflags(write=False)
-        P.runs = {}
-        nh.cache[key] = P
-    return nh.cache[key]
+        P.rests = [R.A.rest for R in P.ref]
+        P.lines = "stages"
+    return mgd.problem(nh, (name, rim), build, dots=(0,))
 
 
 def _bounds(R):
-    return [s.start for s in R.where], [s.stop for s in R.where]
+    return mgd.bounds(R.where)
 
 
-def _hierarchy(nh, P):
-    """a device hierarchy whose work fields hold NaN; a level with stages gets no minv; -> (h, x, b, [r, p, z])"""
-    F = nh.fields.DeviceField
-    levels = []
-    for l, R in enumerate(P.ref):
-        like = F.from_numpy(np.zeros(R.shape, P.dtype))
-        others = [F.from_numpy(a) for a in R.A.rest]
-        lines = [nh.mg.LineStage(ax, F.from_numpy(lo), F.from_numpy(inv), F.from_numpy(up)) for ax, lo, inv, up in R.stages]
-        levels.append(nh.mg.Level(P.entries[l], like, _bounds(R), others=others, minv=None if lines else F.from_numpy(R.minv),
-                                  rscale=R.rscale, lines=lines))
-    h = nh.mg.Hierarchy(levels)
-    nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
-    h.q = [nan(f) for f in h.q]
-    h.x = [None] + [nan(f) for f in h.x[1:]]
-    h.b = [None] + [nan(f) for f in h.b[1:]]
-    return h, F.from_numpy(P.x0), F.from_numpy(P.b), [nan(h.q[0]) for _ in range(3)]
+def _solve(nh, P, max_iters, **kw):
+    return mgd.cg(nh, P, max_iters, lines=True, **kw)
 
 
-class Run:
-    pass
-
-
-def _solve(nh, P, max_iters, tol2=0.0, check_every=1, trace=True, **kw):
-    h, x, bf, work = _hierarchy(nh, P)
-    res = nh.mg.cg_solve(h, x, bf, max_iters=max_iters, tol2=tol2, check_every=check_every, trace=trace, work=work, lines=True, **kw)
-    nh.torch.cuda.synchronize()
-    R = Run()
-    R.res, R.x, R.b = res, x.numpy(), bf.numpy()
-    R.r, R.p, R.z = (f.numpy() for f in work)
-    R.xs = [f.numpy() for f in h.x[1:]]
-    R.bs = [f.numpy() for f in h.b[1:]]
-    R.counts, R.rz0 = nh.mg.cg_counts(), nh.mg.cg_rz0()
-    return R
-
-
-def _check_replay(nh, P, iters, check_every=1, want_counts=None, **kw):
-    """one traced run of `iters` iterations against the restatement's replay; -> the run"""
-    R = _solve(nh, P, iters, check_every=check_every, **kw)
-    done, rr0, rr_last, trace = R.res
-    assert done == iters and trace.shape == (iters, 3)
-    assert R.counts[0] + R.counts[1] == iters and R.counts[3] == -(-iters // check_every)
-    if want_counts is not None:
-        assert R.counts == want_counts, R.counts
-    sw = {k: v for k, v in kw.items() if k in ("sweeps", "coarse_sweeps")}
-    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, R.rz0, trace, **sw)
-    x, r, p, z = st.x, st.r, st.p, st.z
-    print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
-    assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
-    for k, sums in enumerate(checks):
-        print(f"  k={k}: " + "  ".join(f"{nm} = {trace[k][c]!r} (sum {s!r}, bound {bd:.3e})"
-                                        for c, (nm, (s, bd)) in enumerate(zip(("pq", "rz'", "rr'"), sums))))
-        for c, (s, bd) in enumerate(sums):
-            assert abs(float(trace[k][c]) - s) <= bd
-    assert rr_last == float(trace[-1][2])
-    for name, got, want in (("x", R.x, x), ("r", R.r, r), ("p", R.p, p), ("z", R.z, z)):
-        assert bits_equal(got, want), f"{name}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(R.xs, [L.x for L in P.ref[1:]]), 1):
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(R.bs, [L.b for L in P.ref[1:]]), 1):
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
-    # cells of x outside Omega are never changed; r, p and z are +0 there; b is the caller's
-    outside = np.ones(P.x0.shape, bool)
-    outside[P.ref[0].where] = False
-    zero = np.zeros(int(outside.sum()), P.dtype)
-    assert bits_equal(R.x[outside], P.x0[outside]) and bits_equal(R.b, P.b)
-    for a in (R.r, R.p, R.z):
-        assert bits_equal(a[outside], zero)
-    return R
+def _check_replay(nh, P, iters, **kw):
+    """mg_device.check_replay through cg_solve(lines=True), and what the fields hold outside Omega"""
+    return mgd.check_replay(nh, P, iters, outside=True, lines=True, **kw)
 
 
 @pytest.mark.parametrize("sweeps", [1, 2])
@@ -208,9 +103,7 @@ def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
     monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", "0")          # read at every call
     Pl = _check_replay(nh, P, 5, want_counts=(5, 0, 0, 5))
     assert G.counts == (1, 4, 0, 5)
-    assert G.res[:3] == Pl.res[:3] and bits_equal(G.res[3], Pl.res[3]) and G.rz0 == Pl.rz0
-    for a, b in zip([G.x, G.r, G.p, G.z] + G.xs + G.bs, [Pl.x, Pl.r, Pl.p, Pl.z] + Pl.xs + Pl.bs):
-        assert bits_equal(a, b), mismatch_report(a, b)
+    mgd.same_runs(G, Pl)
 
 
 def test_fallback_runs_the_same_iteration(nh):
@@ -223,7 +116,7 @@ def test_without_lines_it_is_mgcg_solve(nh):
     P = _problem(nh, "3d_f64_point")
     results = []
     for how in ("mgcg_solve", "null", "empty"):
-        h, x, b, work = _hierarchy(nh, P)
+        h, x, b, work = mgd.hierarchy(nh, P)
         arr, keep = h._structs(x, b)
         tr = nh.torch.zeros(15, dtype=nh.torch.float64, device="cuda")
         warr = (C.c_void_p * 3)(*[f.ptr for f in work])
@@ -264,19 +157,9 @@ def test_nonzero_dirichlet_rim(nh):
 def test_stops_where_the_definition_says_on_the_flux_hierarchy(nh, check_every, between):
     P = _problem(nh, "flux")
     assert [L.m for L in P.ref] == [(63, 63), (31, 31), (15, 15), (7, 7), (3, 3), (1, 1)]
-    if "seq" not in P.runs:
-        P.runs["seq"] = rst.numpy_mgcg(P.ref, P.x0, P.b, 6, sweeps=1)
-    seq = P.runs["seq"]
-    tol2 = rst.tol_between(seq, *between)
-    max_iters = len(seq) - 1
-    want_done, want_checks = rst.expected_stop(seq, check_every, max_iters, tol2)
-    assert want_done == between[1]
+    seq, tol2, max_iters, want = mgd.stop_schedule(P, lambda: rst.numpy_mgcg(P.ref, P.x0, P.b, 6, sweeps=1), check_every, between)
     R = _solve(nh, P, max_iters, tol2=tol2, check_every=check_every, trace=False, sweeps=1)
-    done, rr0, rr_last = R.res
-    print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, rr_last = {rr_last!r}")
-    assert (done, R.counts[3]) == (want_done, want_checks)
-    assert R.counts[0] + R.counts[1] == done
-    assert rr_last <= tol2 < rr0
+    mgd.check_cg_stop(R, seq, tol2, want)
 
 
 def test_the_keyword_through_the_python_layer(nh):
@@ -304,7 +187,7 @@ def test_the_keyword_through_the_python_layer(nh):
     Q = _problem(nh, "3d_f64_point")
     runs = []
     for lines in (False, True):
-        hq, xq, bq, work = _hierarchy(nh, Q)
+        hq, xq, bq, work = mgd.hierarchy(nh, Q)
         res = nh.mg.cg_solve(hq, xq, bq, max_iters=3, trace=True, work=work, lines=lines)
         nh.torch.cuda.synchronize()
         runs.append((res[:3], res[3], xq.numpy()))

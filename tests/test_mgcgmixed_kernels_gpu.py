@@ -19,9 +19,11 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_device
 import mg_restatement as rst
 import mgcgmixed_cases as mx
 from helpers import bits_equal, mismatch_report
+from mg_device import where_of as _where
 
 pytestmark = pytest.mark.gpu
 
@@ -40,43 +42,20 @@ SETUPS = {
 }
 
 
-def _where(lo, m):
-    return tuple(slice(l, l + n) for l, n in zip(lo, m))
-
-
 def _text(box, lo, m, dtype):
     return mgc.mc.star_module(box, dtype, bounds=(list(lo), [l + n for l, n in zip(lo, m)]), centre=float(2 * len(box)), side=-1.0)
 
 
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.lowering, ns.mg = torch, _capi, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mg_device.namespace(tmp_path_factory.mktemp("neptune_cache"))
     ns.setups = {}
     return ns
 
 
 def _field(shape, seed, where=None, outside=None):
-    """hashed f32 values with -0 sprinkled in; `outside` (e.g. NaN) on every cell that is not in `where`"""
-    a = helpers.hash_field(shape, S, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    if outside is not None:
-        keep = a[where].copy()
-        a[...] = outside
-        a[where] = keep
-    return a
+    """mg_device.field in f32"""
+    return mg_device.field(shape, S, seed, where, outside)
 
 
 # ---------------------------------------------------------------- neptune_hip_mg_smooth_dot_wide
@@ -172,23 +151,18 @@ def edge_values(with_nan: bool):
 
 def _setup_problem(nh, name):
     """-> (the restatement's Problem, the outer entry, the inner entries): two levels of the star operator"""
-    from concurrent.futures import ThreadPoolExecutor
     spec = SETUPS[name]
     t64 = _text(*spec[0], D)
     t32 = [_text(*lv, S) for lv in spec]
-
-    def one(job):
-        nh.lowering.compile_module(job[0], load=False, dot_entries=job[1])
-    with ThreadPoolExecutor(max_workers=3) as pool:
-        list(pool.map(one, [(t64, True)] + [(t, False) for t in t32]))
+    mg_device.prefetch([(t64, True)] + [(t, False) for t in t32])
     levels = []
     for l, (text, (box, lo, m)) in enumerate(zip(t32, spec)):
         w = _where(lo, m)
         levels.append(rst.Level(rst.Operator(text), box, w, mgc.minv_field(box, w, S, 0.8, outside=0.0 if l == 0 else np.nan), S))
     if len(spec[0][0]) == 2:
         levels[0].axes = (1,)
-    entry64 = nh.lowering.compile_module(t64, dot_entries=True).dot_entry("entry")
-    entries32 = [nh.lowering.compile_module(t).geom_entry("entry") for t in t32]
+    entry64 = mg_device.entry(nh, t64, True)
+    entries32 = [mg_device.entry(nh, t) for t in t32]
     return mx.Problem(rst.Operator(t64), levels), entry64, entries32
 
 

@@ -20,13 +20,14 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_device as mgd
 import mg_restatement as rst
 import mgcg_cases as mg
 import mgcgmixed_cases as mx
 import mglines_cases as lc
 import mgsemi_cases as sc
 import pcg_cases as pc
-from helpers import bits_equal, mismatch_report
+from helpers import bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -70,55 +71,15 @@ def _texts():
     return out
 
 
-def _prefetch(lowering, texts):
-    """every module once, side by side: the f64 ones with their dot entries (another cache key), the f32 ones plain; host
-    threads only, nothing is loaded"""
-    from concurrent.futures import ThreadPoolExecutor
-    jobs = {}
-    for t64, t32 in texts.values():
-        if t64:
-            jobs[(t64, True)] = None
-        for t in t32:
-            if t:
-                jobs[(t, False)] = None
-
-    def one(job):
-        try:
-            lowering.compile_module(job[0], load=False, dot_entries=job[1])
-        except Exception:       # noqa: BLE001 - the test that needs this module shows the diagnostic
-            pass
-    with ThreadPoolExecutor(max_workers=12) as pool:
-        list(pool.map(one, jobs))
-
-
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"))
     ns.texts = _texts()
-    _prefetch(lowering, ns.texts)
-    ns.entries = {}
-    ns.cache = {}
+    # every module once, side by side: the f64 ones with their dot entries (the outer operator's entry carries the
+    # dot-monitored launch as well), the f32 ones plain
+    jobs = [job for t64, t32 in ns.texts.values() for job in [(t64, True)] + [(t, False) for t in t32]]
+    mgd.prefetch([(t, dot) for t, dot in jobs if t])
     return ns
-
-
-def _entry(nh, text, outer):
-    """the outer operator's entry carries the dot-monitored launch as well; the levels' are plain geometry-level entries"""
-    key = (text, outer)
-    if key not in nh.entries:
-        nh.entries[key] = (nh.lowering.compile_module(text, dot_entries=True).dot_entry("entry") if outer else
-                           nh.lowering.compile_module(text).geom_entry("entry"))
-    return nh.entries[key]
 
 
 class Case:
@@ -128,8 +89,8 @@ class Case:
 
 def _finish(nh, T, texts, rim=False):
     if T.entry64 is None:
-        T.entry64 = _entry(nh, texts[0], True)
-    T.entries32 = [e if e is not None else _entry(nh, t, False) for e, t in zip(T.entries32, texts[1])]
+        T.entry64 = mgd.entry(nh, texts[0], True)
+    T.entries32 = [e if e is not None else mgd.entry(nh, t, False) for e, t in zip(T.entries32, texts[1])]
     T.x0, T.b = mgc.problem_fields(T.P.shape, T.P.where, D, rim=rim)
     for a in (T.x0, T.b):
         a.setflags(write=False)
@@ -159,58 +120,21 @@ def _case(nh, name, rim=False, stage_on_level_1=False):
     return nh.cache[key]
 
 
-class Run:
-    pass
-
-
 def _solve(nh, T, max_iters, tol2=0.0, check_every=1, trace=True, offset=0, b=None, **kw):
+    """offset: in elements of each field's own type (mgcgmixed_cases.device_problem)"""
     dev = mx.device_problem(nh, T.P, T.entry64, T.entries32, T.x0, T.b if b is None else b, T.others64, T.others32, offset)
     res = nh.mg.cg_solve_mixed(dev.outer, dev.h, dev.x, dev.b, max_iters=max_iters, tol2=tol2, check_every=check_every, trace=trace,
                                work=dev.work, **kw)
     nh.torch.cuda.synchronize()
-    R = Run()
-    R.res, R.x, R.b = res, dev.x.numpy(), dev.b.numpy()
-    R.r, R.p, R.q = (f.numpy() for f in dev.work)
-    R.r32, R.z32 = dev.h.b[0].numpy(), dev.h.x[0].numpy()
-    R.xs = [f.numpy() for f in dev.h.x[1:]]
-    R.bs = [f.numpy() for f in dev.h.b[1:]]
-    R.counts, R.rz0 = nh.mg.cg_counts(), nh.mg.cg_rz0()
-    return R
+    return mgd.record(nh, res, dev.h, dev.x, dev.b, list(zip("rp", dev.work)) + [("r32", dev.h.b[0]), ("z32", dev.h.x[0])])
 
 
 def _check_replay(nh, T, iters, check_every=1, want_counts=None, offset=0, **kw):
-    """one traced run of `iters` iterations against the restatement's replay; -> the run"""
+    """one traced run of `iters` iterations against the restatement's replay, and what the fields hold outside Omega; -> the run"""
     R = _solve(nh, T, iters, check_every=check_every, offset=offset, **kw)
-    done, rr0, rr_last, trace = R.res
-    assert done == iters and trace.shape == (iters, 3) and trace.dtype == D
-    assert R.counts[0] + R.counts[1] == iters and R.counts[3] == -(-iters // check_every)
-    if want_counts is not None:
-        assert R.counts == want_counts, R.counts
+    assert R.res[3].dtype == D
     sw = {k: v for k, v in kw.items() if k in ("sweeps", "coarse_sweeps")}
-    P = T.P
-    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P, T.x0, T.b, R.rz0, trace, **sw)
-    x, r, p, r32, z32 = st.x, st.r, st.p, st.r32, st.z32
-    print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
-    assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
-    for k, sums in enumerate(checks):
-        print(f"  k={k}: " + "  ".join(f"{nm} = {trace[k][c]!r} (sum {s!r}, bound {bd:.3e})"
-                                        for c, (nm, (s, bd)) in enumerate(zip(("pq", "rz'", "rr'"), sums))))
-        for c, (s, bd) in enumerate(sums):
-            assert abs(float(trace[k][c]) - s) <= bd
-    assert rr_last == float(trace[-1][2])
-    R.checks = checks
-    for name, got, want in (("x", R.x, x), ("r", R.r, r), ("p", R.p, p), ("r32", R.r32, r32), ("z32", R.z32, z32)):
-        assert got.dtype == want.dtype and bits_equal(got, want), f"{name}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(R.xs, [L.x for L in P.levels[1:]]), 1):
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(R.bs, [L.b for L in P.levels[1:]]), 1):
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
-    # cells of x outside Omega are never changed; r, p, r32 and z32 are +0 there; b is the caller's
-    outside = np.ones(P.shape, bool)
-    outside[P.where] = False
-    assert bits_equal(R.x[outside], T.x0[outside]) and bits_equal(R.b, T.b)
-    for a in (R.r, R.p, R.r32, R.z32):
-        assert bits_equal(a[outside], np.zeros(int(outside.sum()), a.dtype))
+    mgd.compare_replay(R, T.P, T.x0, T.b, iters, check_every, want_counts, outside=True, **sw)
     return R
 
 
@@ -229,9 +153,7 @@ def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
     monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", "0")          # read at every call
     Pl = _check_replay(nh, T, 5, want_counts=(5, 0, 0, 5))
     assert G.counts == (1, 4, 0, 5)
-    assert G.res[:3] == Pl.res[:3] and bits_equal(G.res[3], Pl.res[3]) and G.rz0 == Pl.rz0
-    for a, b in zip([G.x, G.r, G.p, G.r32, G.z32] + G.xs + G.bs, [Pl.x, Pl.r, Pl.p, Pl.r32, Pl.z32] + Pl.xs + Pl.bs):
-        assert bits_equal(a, b), mismatch_report(a, b)
+    mgd.same_runs(G, Pl)
 
 
 def test_fallback_runs_the_same_iteration(nh):
@@ -248,19 +170,9 @@ def test_fallback_runs_the_same_iteration(nh):
 @pytest.mark.parametrize("name,check_every,between", [("3d", 1, (2, 3)), ("3d", 3, (3, 6)), ("2d", 3, (3, 6))])
 def test_stops_where_the_definition_says(nh, name, check_every, between):
     T = _case(nh, name)
-    if "seq" not in T.runs:
-        T.runs["seq"] = rst.numpy_mgcg(T.P, T.x0, T.b, 6)
-    seq = T.runs["seq"]
-    tol2 = rst.tol_between(seq, *between)
-    max_iters = len(seq) - 1
-    want_done, want_checks = rst.expected_stop(seq, check_every, max_iters, tol2)
-    assert want_done == between[1]
+    seq, tol2, max_iters, want = mgd.stop_schedule(T, lambda: rst.numpy_mgcg(T.P, T.x0, T.b, 6), check_every, between)
     R = _solve(nh, T, max_iters, tol2=tol2, check_every=check_every, trace=False)
-    done, rr0, rr_last = R.res
-    print(f"{name}: seq = {seq}, tol2 = {tol2!r}, done = {done}, rr_last = {rr_last!r}")
-    assert (done, R.counts[3]) == (want_done, want_checks)
-    assert R.counts[0] + R.counts[1] == done
-    assert rr_last <= tol2 < rr0
+    mgd.check_cg_stop(R, seq, tol2, want, label=f"{name}: ")
 
 
 def test_a_converged_start_runs_no_iteration(nh):
@@ -353,7 +265,7 @@ def test_builtin_bodies_on_both_level_zeros(nh):
               rst.Level(rst.Operator(nh.texts["builtin"][1][1]), shapes[1][0], shapes[1][1], mgc.minv_field(shapes[1][0], shapes[1][1], S, 0.8), S)]
     T.P = mx.Problem(lambda u: helpers.oracle_entry("3d7", u), levels)
     T.entry64 = nh.capi.BODY_LAP3D7_F64
-    T.entries32 = [nh.capi.BODY_LAP3D27_F32, _entry(nh, nh.texts["builtin"][1][1], False)]
+    T.entries32 = [nh.capi.BODY_LAP3D27_F32, mgd.entry(nh, nh.texts["builtin"][1][1], False)]
     T.x0, T.b = mgc.problem_fields(T.P.shape, T.P.where, D)
     _check_replay(nh, T, 3, want_counts=(1, 2, 0, 3))
 

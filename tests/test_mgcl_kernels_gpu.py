@@ -22,10 +22,10 @@ import itertools
 import numpy as np
 import pytest
 
-import helpers
+import mg_device
 import mg_restatement as rst
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import dev
 from mg_restatement import EVEN, Halved, Linear, ODD
 
 pytestmark = pytest.mark.gpu
@@ -81,65 +81,31 @@ def test_the_cases_reach_every_form():
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
-    return ns
+    return mg_device.namespace()
 
 
-FACE = {EVEN: "neumann", ODD: "dirichlet"}
+def Geometry(nh, name, dtype, rim=None):
+    fbox, flo, fm, axes, clo = CASES[name]
+    cm = tuple(m // 2 if d in axes else m for d, m in enumerate(fm))
+    setting = {} if rim is None else dict(prolong="linear", faces=rst.faces_of(rim))
+    return mg_device.Geometry(nh, (fbox, flo, fm), (mg_device.unequal_rims(clo, cm), clo, cm), dtype, axes, **setting)
 
 
-class Geometry:
-    def __init__(self, nh, name, dtype, rim=None):
-        fbox, flo, fm, self.axes, clo = CASES[name]
-        cm = tuple(m // 2 if d in self.axes else m for d, m in enumerate(fm))
-        cbox = tuple(l + m + 1 + d for d, (l, m) in enumerate(zip(clo, cm)))             # unequal rims
-        self.fine_shape, self.coarse_shape = fbox, cbox
-        self.fw = tuple(slice(l, l + m) for l, m in zip(flo, fm))
-        self.cw = tuple(slice(l, l + m) for l, m in zip(clo, cm))
-        like = lambda shape: nh.fields.DeviceField.from_numpy(np.zeros(shape, dtype))
-        bounds = lambda w: ([s.start for s in w], [s.stop for s in w])
-        setting = {} if rim is None else dict(prolong="linear", faces=[(FACE[lo], FACE[hi]) for lo, hi in rim])
-        # the levels carry geometry only here (entry None: the kernel alone never calls the operator)
-        self.fine = nh.mg.Level(None, like(fbox), bounds(self.fw), **setting)
-        self.coarse = nh.mg.Level(None, like(cbox), bounds(self.cw))
-
-
-def _field(shape, dtype, seed, where, outside=np.nan):
-    """hashed values with -0 sprinkled in on `where`, `outside` on every other cell"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    keep = a[where].copy()
-    a[...] = outside
-    a[where] = keep
-    return a
-
-
-def _dev(nh, a, offset):
-    elems = offset // a.itemsize
-    return stc.offset_field(nh, a, elems) if offset else nh.fields.DeviceField.from_numpy(a)
+def field(shape, dtype, seed, where):
+    """hashed values with -0 sprinkled in on `where`, NaN on every other cell"""
+    return mg_device.field(shape, dtype, seed, where, np.nan)
 
 
 def _run(nh, name, dtype, offset, complemented):
     rim = _rim(name, complemented)
     G = Geometry(nh, name, dtype, rim)
     assert nh.mg.halved_axes(G.fine, G.coarse) == G.axes
-    x_c = _field(G.coarse_shape, dtype, 31, G.cw)             # no coarse cell outside the coarse Omega is read
-    x_f = _field(G.fine_shape, dtype, 32, G.fw)               # no fine cell outside the fine Omega is written
+    x_c = field(G.coarse_shape, dtype, 31, G.cw)             # no coarse cell outside the coarse Omega is read
+    x_f = field(G.fine_shape, dtype, 32, G.fw)               # no fine cell outside the fine Omega is written
     assert np.isfinite(x_c[G.cw]).all() and np.signbit(x_c[G.cw][x_c[G.cw] == 0]).any()
     want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Linear(G.axes, rim))
-    xd = _dev(nh, x_f, offset)
-    nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
+    xd = dev(nh, x_f, offset)
+    nh.mg.prolong_add(G.fine, G.coarse, dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()
     got = xd.numpy()
     assert bits_equal(got, want), mismatch_report(got, want)
@@ -165,8 +131,8 @@ def test_minus_zero_and_the_exact_sign_flip(nh, dtype):
     x_c[G.cw] = -0.0
     x_f = np.full(G.fine_shape, -0.0, dtype)
     want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Linear(G.axes, rim))
-    fd = _dev(nh, x_f, 0)
-    nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, 0), fd)
+    fd = dev(nh, x_f, 0)
+    nh.mg.prolong_add(G.fine, G.coarse, dev(nh, x_c, 0), fd)
     nh.torch.cuda.synchronize()
     got = fd.numpy()
     assert bits_equal(got, want), mismatch_report(got, want)
@@ -177,8 +143,8 @@ def test_minus_zero_and_the_exact_sign_flip(nh, dtype):
     assert not np.signbit(inner[on_odd_face]).any() and np.signbit(inner[~on_odd_face]).all()
     x_c[G.cw] = 0.0
     x_c[G.cw[0].start, G.cw[1].start, G.cw[2].start] = 8.0
-    fd = _dev(nh, np.zeros(G.fine_shape, dtype), 0)
-    nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, 0), fd)
+    fd = dev(nh, np.zeros(G.fine_shape, dtype), 0)
+    nh.mg.prolong_add(G.fine, G.coarse, dev(nh, x_c, 0), fd)
     nh.torch.cuda.synchronize()
     inner = fd.numpy()[G.fw]
     assert inner[0, 0, 0] == 1.0 and inner[1, 1, 1] == 8.0 * 0.75 ** 3 and inner[2, 2, 2] == 8.0 * 0.25 ** 3
@@ -190,21 +156,21 @@ def test_kind_constant_and_unread_rules(nh):
     rank-2 pair the rules of dimension 2 are not read"""
     lib, f64 = nh.lib, nh.capi.F64
     G = Geometry(nh, "r2", F64)
-    x_c, x_f = _field(G.coarse_shape, F64, 41, G.cw), _field(G.fine_shape, F64, 42, G.fw)
+    x_c, x_f = field(G.coarse_shape, F64, 41, G.cw), field(G.fine_shape, F64, 42, G.fw)
     p = nh.capi.MgProlong()
     p.kind = nh.capi.MG_PROLONG_CONSTANT
     for d in range(3):
         p.rim_lo[d], p.rim_hi[d] = 9, -9
-    xd = _dev(nh, x_f, 0)
-    assert lib.neptune_hip_mg_prolong_add_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(p), _dev(nh, x_c, 0).ptr, xd.ptr,
+    xd = dev(nh, x_f, 0)
+    assert lib.neptune_hip_mg_prolong_add_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(p), dev(nh, x_c, 0).ptr, xd.ptr,
                                                  None) == nh.capi.OK
     nh.torch.cuda.synchronize()
     want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Halved(G.axes))
     assert bits_equal(xd.numpy(), want), mismatch_report(xd.numpy(), want)
     p.kind = nh.capi.MG_PROLONG_LINEAR
     p.rim_lo[0], p.rim_hi[0], p.rim_lo[1], p.rim_hi[1] = ODD, EVEN, EVEN, ODD
-    xd = _dev(nh, x_f, 0)
-    assert lib.neptune_hip_mg_prolong_add_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(p), _dev(nh, x_c, 0).ptr, xd.ptr,
+    xd = dev(nh, x_f, 0)
+    assert lib.neptune_hip_mg_prolong_add_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(p), dev(nh, x_c, 0).ptr, xd.ptr,
                                                  None) == nh.capi.OK
     nh.torch.cuda.synchronize()
     want = rst.prolong_add(x_c, G.cw, x_f, G.fw, Linear(G.axes, ((ODD, EVEN), (EVEN, ODD))))

@@ -21,9 +21,10 @@ import numpy as np
 import pytest
 
 import helpers
+import mg_device
 import mg_restatement as rst
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import dev
 from mg_restatement import EVEN, Halved, ODD, Transfers
 
 pytestmark = pytest.mark.gpu
@@ -98,58 +99,28 @@ def test_the_cases_reach_every_path():
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
+    ns = mg_device.namespace()
     assert hasattr(ns.lib, "neptune_hip_mg_restrict_linear")
-    ns.lib.neptune_hip_init(0)
     return ns
 
 
 RSCALE = 3.0                                       # not a power of two: the last operation rounds
 
 
-class Geometry:
-    def __init__(self, nh, name, dtype, rim=None):
-        fbox, flo, fm, self.axes, clo = CASES[name]
-        cm = _coarse(name)
-        cbox = tuple(l + m + 1 + d for d, (l, m) in enumerate(zip(clo, cm)))             # unequal rims
-        self.fine_shape, self.coarse_shape = fbox, cbox
-        self.fw = tuple(slice(l, l + m) for l, m in zip(flo, fm))
-        self.cw = tuple(slice(l, l + m) for l, m in zip(clo, cm))
-        like = lambda shape: nh.fields.DeviceField.from_numpy(np.zeros(shape, dtype))
-        bounds = lambda w: ([s.start for s in w], [s.stop for s in w])
-        setting = {} if rim is None else dict(restrict="linear", faces=rst.faces_of(rim))
-        # the levels carry geometry only here (entry None: the kernel alone never calls the operator)
-        self.fine = nh.mg.Level(None, like(fbox), bounds(self.fw), rscale=RSCALE, **setting)
-        self.coarse = nh.mg.Level(None, like(cbox), bounds(self.cw))
+def Geometry(nh, name, dtype, rim=None):
+    fbox, flo, fm, axes, clo = CASES[name]
+    cm = _coarse(name)
+    setting = {} if rim is None else dict(restrict="linear", faces=rst.faces_of(rim))
+    return mg_device.Geometry(nh, (fbox, flo, fm), (mg_device.unequal_rims(clo, cm), clo, cm), dtype, axes, rscale=RSCALE, **setting)
 
 
-def _field(shape, dtype, seed, where, outside=np.nan):
-    """hashed values with -0 sprinkled in on `where`, `outside` on every other cell"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    keep = a[where].copy()
-    a[...] = outside
-    a[where] = keep
-    return a
-
-
-def _dev(nh, a, offset):
-    elems = offset // a.itemsize
-    return stc.offset_field(nh, a, elems) if offset else nh.fields.DeviceField.from_numpy(a)
+def field(shape, dtype, seed, where):
+    """hashed values with -0 sprinkled in on `where`, NaN on every other cell"""
+    return mg_device.field(shape, dtype, seed, where, np.nan)
 
 
 def _inputs(G, dtype):
-    b_f, q_f = _field(G.fine_shape, dtype, 51, G.fw), _field(G.fine_shape, dtype, 52, G.fw)      # NaN outside the fine Omega
+    b_f, q_f = field(G.fine_shape, dtype, 51, G.fw), field(G.fine_shape, dtype, 52, G.fw)      # NaN outside the fine Omega
     b_c, x_c = helpers.hash_field(G.coarse_shape, dtype, seed=53), helpers.hash_field(G.coarse_shape, dtype, seed=54)
     q_f[q_f == 0] = 0.0                                       # q's zeros are +0, so that d = -0 - +0 = -0 where b is -0
     d = b_f[G.fw] - q_f[G.fw]
@@ -163,8 +134,8 @@ def _run(nh, name, dtype, offset, complemented):
     assert nh.mg.halved_axes(G.fine, G.coarse) == G.axes
     b_f, q_f, b_c, x_c = _inputs(G, dtype)
     want_b, want_x = rst.restrict(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, Transfers(G.axes, rim))
-    bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
-    nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
+    bd, xd = dev(nh, b_c, offset), dev(nh, x_c, offset)
+    nh.mg.restrict(G.fine, G.coarse, dev(nh, b_f, offset), dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
     got_b, got_x = bd.numpy(), xd.numpy()
     assert bits_equal(got_b, want_b), mismatch_report(got_b, want_b)
@@ -193,8 +164,8 @@ def test_minus_zero_and_the_exact_sign_flip(nh, dtype):
     b_f[G.fw], q_f[G.fw] = -0.0, 0.0
     ones = np.ones(G.coarse_shape, dtype)
     want_b, want_x = rst.restrict(b_f, q_f, G.fw, RSCALE, ones, ones, G.cw, Transfers(G.axes, rim))
-    bd, xd = _dev(nh, ones, 0), _dev(nh, ones, 0)
-    nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, 0), _dev(nh, q_f, 0), bd, xd)
+    bd, xd = dev(nh, ones, 0), dev(nh, ones, 0)
+    nh.mg.restrict(G.fine, G.coarse, dev(nh, b_f, 0), dev(nh, q_f, 0), bd, xd)
     nh.torch.cuda.synchronize()
     got = bd.numpy()
     assert bits_equal(got, want_b), mismatch_report(got, want_b)
@@ -206,8 +177,8 @@ def test_minus_zero_and_the_exact_sign_flip(nh, dtype):
     assert not np.signbit(inner[on_odd_face]).any() and np.signbit(inner[~on_odd_face]).all()
     b_f[G.fw] = 0.0
     b_f[G.fw[0].start, G.fw[1].start, G.fw[2].start] = 64.0
-    bd = _dev(nh, ones, 0)
-    nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, 0), _dev(nh, q_f, 0), bd, _dev(nh, ones, 0))
+    bd = dev(nh, ones, 0)
+    nh.mg.restrict(G.fine, G.coarse, dev(nh, b_f, 0), dev(nh, q_f, 0), bd, dev(nh, ones, 0))
     nh.torch.cuda.synchronize()
     inner = bd.numpy()[G.cw]
     assert inner[0, 0, 0] == RSCALE * 64.0 * 0.25 ** 3 and (inner.reshape(-1)[1:] == 0).all()
@@ -230,11 +201,11 @@ def test_kind_average_is_the_averaging_restriction(nh, name):
     G = Geometry(nh, name, F64)
     b_f, q_f, b_c, x_c = _inputs(G, F64)
     t = _transfer(nh, nh.capi.MG_PROLONG_CONSTANT, nh.capi.MG_RESTRICT_AVERAGE, (9, 9, 9), (-9, -9, -9))
-    bd, xd = _dev(nh, b_c, 0), _dev(nh, x_c, 0)
-    assert lib.neptune_hip_mg_restrict_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(t), _dev(nh, b_f, 0).ptr,
-                                              _dev(nh, q_f, 0).ptr, RSCALE, bd.ptr, xd.ptr, None) == nh.capi.OK
-    b2, x2 = _dev(nh, b_c, 0), _dev(nh, x_c, 0)
-    assert lib.neptune_hip_mg_restrict(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), _dev(nh, b_f, 0).ptr, _dev(nh, q_f, 0).ptr,
+    bd, xd = dev(nh, b_c, 0), dev(nh, x_c, 0)
+    assert lib.neptune_hip_mg_restrict_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(t), dev(nh, b_f, 0).ptr,
+                                              dev(nh, q_f, 0).ptr, RSCALE, bd.ptr, xd.ptr, None) == nh.capi.OK
+    b2, x2 = dev(nh, b_c, 0), dev(nh, x_c, 0)
+    assert lib.neptune_hip_mg_restrict(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), dev(nh, b_f, 0).ptr, dev(nh, q_f, 0).ptr,
                                        RSCALE, b2.ptr, x2.ptr, None) == nh.capi.OK
     nh.torch.cuda.synchronize()
     want_b, want_x = rst.restrict(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, Halved(G.axes))
@@ -243,9 +214,9 @@ def test_kind_average_is_the_averaging_restriction(nh, name):
     assert bits_equal(xd.numpy(), want_x)
     if len(G.fine_shape) == 2:
         t = _transfer(nh, nh.capi.MG_PROLONG_CONSTANT, nh.capi.MG_RESTRICT_LINEAR, (ODD, EVEN, 9), (EVEN, ODD, -9))
-        bd, xd = _dev(nh, b_c, 0), _dev(nh, x_c, 0)
-        assert lib.neptune_hip_mg_restrict_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(t), _dev(nh, b_f, 0).ptr,
-                                                  _dev(nh, q_f, 0).ptr, RSCALE, bd.ptr, xd.ptr, None) == nh.capi.OK
+        bd, xd = dev(nh, b_c, 0), dev(nh, x_c, 0)
+        assert lib.neptune_hip_mg_restrict_linear(f64, C.byref(G.fine.geom), C.byref(G.coarse.geom), C.byref(t), dev(nh, b_f, 0).ptr,
+                                                  dev(nh, q_f, 0).ptr, RSCALE, bd.ptr, xd.ptr, None) == nh.capi.OK
         nh.torch.cuda.synchronize()
         want_b, _ = rst.restrict(b_f, q_f, G.fw, RSCALE, b_c, x_c, G.cw, Transfers(G.axes, ((ODD, EVEN), (EVEN, ODD))))
         assert bits_equal(bd.numpy(), want_b), mismatch_report(bd.numpy(), want_b)

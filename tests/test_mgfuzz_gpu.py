@@ -8,16 +8,17 @@ a block and every traced scalar must lie within 2 (n - 1) eps sum |t_i| of the e
 (mg_cases.residual, cg_cases.dot_terms, mgcgmixed_cases.wide_dot_terms).  The counts must be those of the launch path, a
 quarter of the seeds run the other path as well and must give identical bits, and the inputs (b, minv, the factor fields)
 must be unchanged.  Every work field holds NaN before the call.  A refused case must raise and leave every field as it was."""
+import copy
 import time
 
 import numpy as np
 import pytest
 
-import helpers
-import mg_restatement as rst
+import mg_device as mgd
 import mgfuzz_cases as fz
 import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import entry as _entry, same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -26,31 +27,12 @@ SEEDS = fz.SEEDS
 
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"))
     jobs = dict.fromkeys(job for seed in SEEDS for job in fz.case_modules(fz.decode(seed)))
     t0 = time.perf_counter()
-    helpers.prefetch_modules([lowering.with_options(text, dot_entries=dot) for text, dot in jobs])
+    mgd.prefetch(jobs)
     print(f"\nprefetched {len(jobs)} modules in {time.perf_counter() - t0:.1f} s")
-    ns.entries = {}
     return ns
-
-
-def _entry(nh, text, dot):
-    if (text, dot) not in nh.entries:
-        nh.entries[(text, dot)] = (nh.lowering.compile_module(text, dot_entries=True).dot_entry("entry") if dot else
-                                   nh.lowering.compile_module(text).geom_entry("entry"))
-    return nh.entries[(text, dot)]
 
 
 class Device:
@@ -102,16 +84,8 @@ def _device(nh, B, stages=None, m0_region=None):
 
 def _hierarchy(nh, B, dev):
     c = B.case
-    F = nh.fields.DeviceField
-    nan = lambda f: np.full(f.shape, np.nan, c["dtype"])
-    h = nh.mg.Hierarchy(dev.levels)
-    off = c["offset"] // np.dtype(c["dtype"]).itemsize
-    first = (lambda a: stc.offset_field(nh, a, off)) if off else F.from_numpy
-    h.q = [first(nan(h.q[0]))] + [F.from_numpy(nan(f)) for f in h.q[1:]]
-    held = first(nan(h.q[0])) if hasattr(dev, "outer") else None            # mixed: z32 and r32 are level 0's x and b
-    h.x = [held] + [F.from_numpy(nan(f)) for f in h.x[1:]]
-    h.b = [first(nan(h.q[0])) if hasattr(dev, "outer") else None] + [F.from_numpy(nan(f)) for f in h.b[1:]]
-    dev.h = h
+    # mixed: z32 and r32 are level 0's x and b
+    dev.h = h = mgd.poison(nh, nh.mg.Hierarchy(dev.levels), c["dtype"], c["offset"], held=hasattr(dev, "outer"))
     if not c.get("why"):
         want_halved = [tuple(a) if k == "H" else () for a, k in zip(c["transferred"], c["kinds"])]
         assert h.coarsened == [tuple(a) for a in c["transferred"]] and h.halved == want_halved
@@ -154,55 +128,28 @@ def _run(nh, B, graph, monkeypatch):
     return R
 
 
-def _same(name, got, want):
-    assert bits_equal(got, want), f"{name}: " + mismatch_report(got, want)
-
-
 def _check_solve(B, R):
     c = B.case
     done, rr0, rr_last, rr_checks = R.res
     ref_rr0, ref_checks = fz.reference(B)
-    assert done == c["n"] and len(rr_checks) == len(ref_checks)
+    assert done == c["n"]
     assert R.counts == fz.expected_counts(c), R.counts
-    print(f"rr0 = {rr0!r} (terms' sum {ref_rr0[0]!r}, bound {ref_rr0[1]:.3e})")
-    assert abs(rr0 - ref_rr0[0]) <= ref_rr0[1]
-    for k, (got, (want, bound)) in enumerate(zip(rr_checks, ref_checks)):
-        print(f"  check {k}: rr = {got!r} (terms' sum {want!r}, bound {bound:.3e})")
-        assert abs(got - want) <= bound
+    # b_0 is an input (_run holds it unchanged): R.bs[0] is None
+    mgd.compare((ref_rr0, ref_checks, [L.x for L in B.levels], [L.b for L in B.levels]), rr0, rr_checks, [R.x] + R.xs[1:], R.bs)
     assert rr_last == rr_checks[-1]
-    _same("x_0", R.x, B.levels[0].x)
-    for l in range(1, c["n_levels"]):
-        _same(f"x_{l}", R.xs[l], B.levels[l].x)
-        _same(f"b_{l}", R.bs[l], B.levels[l].b)
 
 
 def _check_cg(B, R):
     c = B.case
-    done, rr0, rr_last, trace = R.res
-    plain, graph, checks = fz.expected_counts(c)
-    assert done == c["n"] and trace.shape == (c["n"], 3)
-    # R.counts[2], how many iterations took a plain launch and a separate dot product, is the operator's matter
-    assert (R.counts[0], R.counts[1], R.counts[3]) == (plain, graph, checks), R.counts
-    st, sums, rr0_ref, rz0_ref, _ = rst.replay(B.problem, B.x0, B.b, R.rz0, trace, c["sweeps"], c["coarse_sweeps"])
-    print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {R.rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
-    assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(R.rz0 - rz0_ref[0]) <= rz0_ref[1]
-    for k, row in enumerate(sums):
-        print(f"  k={k}: " + "  ".join(f"{nm} = {trace[k][i]!r} (sum {s!r}, bound {bd:.3e})"
-                                        for i, (nm, (s, bd)) in enumerate(zip(("pq", "rz'", "rr'"), row))))
-        for i, (s, bd) in enumerate(row):
-            assert abs(float(trace[k][i]) - s) <= bd
-    assert rr_last == float(trace[-1][2])
-    _same("x", R.x, st.x)
-    _same("r", R.work[0], st.r)
-    _same("p", R.work[1], st.p)
+    V = copy.copy(R)                    # the run as mg_device.compare_replay reads it: named fields, the coarser levels alone
+    V.fields = dict(zip("rp", R.work))
     if c["form"] == "mixed":
-        _same("r32", R.bs[0], st.r32)
-        _same("z32", R.xs[0], st.z32)
+        V.fields.update(r32=R.bs[0], z32=R.xs[0])
     else:
-        _same("z", R.work[2], st.z)
-    for l in range(1, c["n_levels"]):
-        _same(f"x_{l}", R.xs[l], B.levels[l].x)
-        _same(f"b_{l}", R.bs[l], B.levels[l].b)
+        V.fields["z"] = R.work[2]
+    V.xs, V.bs = R.xs[1:], R.bs[1:]
+    mgd.compare_replay(V, B.problem, B.x0, B.b, c["n"], c["check_every"], fz.expected_counts(c), any_fallback=True,
+                       sweeps=c["sweeps"], coarse_sweeps=c["coarse_sweeps"])
 
 
 def _check_refused(nh, B, monkeypatch):

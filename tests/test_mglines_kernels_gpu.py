@@ -1,5 +1,5 @@
 """The line stage's kernels alone (neptune_hip_mg_line_smooth) against the NumPy restatement of
-tests/mglines_cases.py: bit for bit on every cell of x, the untouched cells outside Omega included, and q outside Omega.
+tests/mg_restatement.py: bit for bit on every cell of x, the untouched cells outside Omega included, and q outside Omega.
 
 Shapes: the smallest at which the kernels can go wrong.  Box 9 x 18 x 268 with Omega 7 x 15 x 263 at (1, 2, 3), lines along
 each axis: contiguous-axis lines of 263 cells cross every 32-cell segment boundary and end in a 7-cell tail, there are 105 of
@@ -17,10 +17,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import helpers
+import mg_device
 import mg_restatement as rst
-import mglines_cases as lc
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
 
 pytestmark = pytest.mark.gpu
@@ -45,57 +43,11 @@ IDS = [f"{n}-axis{a}-{np.dtype(d).name}" for n, a, d in RUNS]
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
-    return ns
-
-
-def _field(shape, dtype, seed, where=None, outside=None):
-    """hashed values with -0 sprinkled in; `outside` (e.g. NaN) on every cell that is not in `where`"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    if outside is not None:
-        keep = a[where].copy()
-        a[...] = outside
-        a[where] = keep
-    return a
-
-
-def _factors(shape, where, axis, dtype, seed):
-    """the restatement's factors of a random diagonally dominant T along `axis`: NaN outside Omega, on lo at i = 0 and on up
-    at i = m - 1"""
-    rng = np.random.default_rng(seed)
-    m = tuple(s.stop - s.start for s in where)
-    lower, diag, upper = (np.zeros(shape, dtype) for _ in range(3))
-    lower[where] = rng.uniform(-1.0, 1.0, m)
-    upper[where] = rng.uniform(-1.0, 1.0, m)
-    diag[where] = rng.uniform(2.5, 4.0, m) * rng.choice([-1.0, 1.0], m)
-    lo, inv, up = lc.factors(lower, diag, upper, where, axis, 0.8, outside=np.nan)
-    first, last = list(where), list(where)
-    first[axis], last[axis] = where[axis].start, where[axis].stop - 1
-    lo[tuple(first)] = np.nan
-    up[tuple(last)] = np.nan
-    return lo, inv, up
+    return mg_device.namespace()
 
 
 def _problem(name, axis, dtype):
-    box, lo_corner, om, _ = CASES[name]
-    where = tuple(slice(l, l + m) for l, m in zip(lo_corner, om))
-    q = _field(box, dtype, 41, where, np.nan)
-    b = _field(box, dtype, 42, where, np.nan)
-    x = _field(box, dtype, 43)
-    x[tuple(0 for _ in box)] = np.nan                                # a cell outside Omega: it keeps its bits
-    return where, q, b, x, _factors(box, where, axis, dtype, 7 + axis)
+    return mg_device.line_problem(*CASES[name][:3], axis, dtype)
 
 
 @pytest.mark.parametrize("name,axis,dtype", RUNS, ids=IDS)
@@ -104,7 +56,7 @@ def test_line_stage_matches_the_restatement(nh, name, axis, dtype):
     want = rst.line_stage(q, b, lo, inv, up, x, where, axis)
     assert np.isfinite(want[where]).all()
     F = nh.fields.DeviceField
-    dev = lambda a: stc.offset_field(nh, a, 8 // a.itemsize)          # every field 8 bytes into a larger allocation
+    dev = lambda a: mg_device.dev(nh, a, 8)                           # every field 8 bytes into a larger allocation
     level = nh.mg.Level(None, F.from_numpy(np.zeros(x.shape, dtype)), ([s.start for s in where], [s.stop for s in where]))
     qd, xd = dev(q), dev(x)
     stage = nh.mg.LineStage(axis, dev(lo), dev(inv), dev(up))

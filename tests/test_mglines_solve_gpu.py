@@ -1,5 +1,5 @@
 """neptune_hip_mg_solve_lines and the Python layer around it against the NumPy restatement of
-tests/mglines_cases.py.
+tests/mg_restatement.py.
 
 No reduction enters a field, so after any number of cycles x_0 and every level's x_l, b_l must equal the restatement's bit
 for bit, whatever the launch path (plain launches or the replayed graph of one cycle); rr_0 and every rr read after a block
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import mg_cases as mgc
+import mg_device as mgd
 import mg_restatement as rst
 import mglines_cases as lc
 from helpers import bits_equal, mismatch_report
@@ -39,18 +40,7 @@ PROBLEMS = {
 
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"))
     ns.built = {}
     texts = {}
     for name, (omega, damp, dtype, axes) in PROBLEMS.items():
@@ -59,39 +49,13 @@ def nh(built_libs, tmp_path_factory):
         texts[key] = ns.built[name][1]
     ns.flux = lc.flux_levels((0, 1))
     ns.flux32 = lc.flux_levels((0, 1), n=17, dtype=np.float32)
-    jobs = [t for _, ts in ns.built.values() for t in ts] + ns.flux[1] + ns.flux32[1]
-    _prefetch(lowering, jobs)
-    ns.entries, ns.cache = {}, {}
+    mgd.prefetch([(t, False) for t in [t for _, ts in ns.built.values() for t in ts] + ns.flux[1] + ns.flux32[1]])
     return ns
 
 
-def _prefetch(lowering, texts):
-    """every module compiled once, side by side (host threads only, nothing is loaded)"""
-    from concurrent.futures import ThreadPoolExecutor
-
-    def one(text):
-        try:
-            lowering.compile_module(text, load=False)
-        except Exception:       # noqa: BLE001 - the test that needs this module shows the diagnostic
-            pass
-    with ThreadPoolExecutor(max_workers=12) as pool:
-        list(pool.map(one, dict.fromkeys(texts)))
-
-
-def _entry(nh, text):
-    if text not in nh.entries:
-        nh.entries[text] = nh.lowering.compile_module(text).geom_entry("entry")
-    return nh.entries[text]
-
-
-class Problem:
-    pass
-
-
 def _problem(nh, name):
-    """the compiled operators, the restatement's levels, x0 and b: built once per problem, x0 and b left unchanged"""
-    if name not in nh.cache:
-        P = Problem()
+    """the restatement's own stages on the device, and a level with stages gets no minv"""
+    def build(P):
         if name == "flux":
             P.ref, P.texts, _ = nh.flux
             P.dtype = np.float64
@@ -100,52 +64,13 @@ def _problem(nh, name):
             P.dtype = PROBLEMS[name][2]
             P.ref, P.texts = nh.built[name]
             P.x0, P.b = mgc.problem_fields(P.ref[0].shape, P.ref[0].where, P.dtype)
-        P.entries = [_entry(nh, t) for t in P.texts]
-        for a in (P.x0, P.b):
-            a.setflags(write=False)
-        P.runs = {}
-        nh.cache[name] = P
-    return nh.cache[name]
-
-
-def _reference(P, cycles, check_every=1):
-    """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
-    key = (cycles, check_every)
-    if key not in P.runs:
-        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
-        P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
-    return P.runs[key]
+        P.rests = [R.A.rest for R in P.ref]
+        P.lines = "stages"
+    return mgd.problem(nh, name, build)
 
 
 def _bounds(R):
-    return [s.start for s in R.where], [s.stop for s in R.where]
-
-
-def _hierarchy(nh, P, with_lines=True):
-    """a device hierarchy whose work fields hold NaN; a level with stages gets no minv; -> (h, x, b)"""
-    F = nh.fields.DeviceField
-    levels = []
-    for l, R in enumerate(P.ref):
-        like = F.from_numpy(np.zeros(R.shape, P.dtype))
-        others = [F.from_numpy(a) for a in R.A.rest]
-        lines = [nh.mg.LineStage(ax, F.from_numpy(lo), F.from_numpy(inv), F.from_numpy(up)) for ax, lo, inv, up in R.stages] if with_lines else []
-        levels.append(nh.mg.Level(P.entries[l], like, _bounds(R), others=others, minv=None if lines else F.from_numpy(R.minv),
-                                  rscale=R.rscale, lines=lines))
-    h = nh.mg.Hierarchy(levels)
-    nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
-    h.q = [nan(f) for f in h.q]
-    h.x = [None] + [nan(f) for f in h.x[1:]]
-    h.b = [None] + [nan(f) for f in h.b[1:]]
-    return h, F.from_numpy(P.x0), F.from_numpy(P.b)
-
-
-def _solve(nh, P, max_cycles, tol2=0.0, check_every=1):
-    h, x, b = _hierarchy(nh, P)
-    res = nh.mg.solve(h, x, b, max_cycles=max_cycles, tol2=tol2, check_every=check_every)
-    nh.torch.cuda.synchronize()
-    xs = [x.numpy()] + [f.numpy() for f in h.x[1:]]
-    bs = [b.numpy()] + [f.numpy() for f in h.b[1:]]
-    return res, xs, bs, nh.mg.counts()
+    return mgd.bounds(R.where)
 
 
 @pytest.mark.parametrize("cycles", [2, 5])
@@ -154,34 +79,11 @@ def test_cycles_match_the_restatement(nh, name, cycles):
     P = _problem(nh, name)
     assert [L.m for L in P.ref] == ([(7, 15, 263), (3, 7, 131), (1, 3, 65)] if name.startswith("3d") else [(15, 263), (7, 131), (3, 65)])
     assert [tuple(s[0] for s in L.stages) for L in P.ref] == PROBLEMS[name][3]
-    (done, rr0, rr_last, rr_checks), xs, bs, counts = _solve(nh, P, cycles)
-    ref_rr0, ref_checks, ref_x, ref_b = _reference(P, cycles)
-    assert done == cycles and len(rr_checks) == len(ref_checks) == cycles
-    assert counts == ((2, 0, 2) if cycles == 2 else (1, 4, 5)), counts
-    print(f"rr0 = {rr0!r} (terms' sum {ref_rr0[0]!r}, bound {ref_rr0[1]:.3e})")
-    assert abs(rr0 - ref_rr0[0]) <= ref_rr0[1]
-    for k, (got, (want, bound)) in enumerate(zip(rr_checks, ref_checks)):
-        print(f"  check {k}: rr = {got!r} (terms' sum {want!r}, bound {bound:.3e})")
-        assert abs(got - want) <= bound
-    assert rr_last == rr_checks[-1]
-    for l, (got, want) in enumerate(zip(xs, ref_x)):
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(bs, ref_b)):
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
+    mgd.check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
 
 
 def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
-    P = _problem(nh, "3d_f64_b")
-    monkeypatch.delenv("NEPTUNE_HIP_MG_GRAPH", raising=False)
-    res_g, xs_g, bs_g, counts_g = _solve(nh, P, 5)
-    monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", "0")          # read at every call
-    res_p, xs_p, bs_p, counts_p = _solve(nh, P, 5)
-    assert counts_g == (1, 4, 5) and counts_p == (5, 0, 5)
-    assert res_g == res_p
-    for a, b in zip(xs_g + bs_g, xs_p + bs_p):
-        assert bits_equal(a, b), mismatch_report(a, b)
-    _, _, ref_x, _ = _reference(P, 5)
-    assert bits_equal(xs_p[0], ref_x[0])
+    mgd.graph_vs_plain(nh, _problem(nh, "3d_f64_b"), monkeypatch, 5)
 
 
 def test_without_lines_it_is_mg_solve(nh):
@@ -189,7 +91,7 @@ def test_without_lines_it_is_mg_solve(nh):
     P = _problem(nh, "3d_f64_point")
     results = []
     for how in ("mg_solve", "null", "empty"):
-        h, x, b = _hierarchy(nh, P)
+        h, x, b, _ = mgd.hierarchy(nh, P)
         arr, keep = h._structs(x, b)
         rr = (C.c_double * 5)()
         done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
@@ -204,7 +106,7 @@ def test_without_lines_it_is_mg_solve(nh):
         results.append((done.value, rr0.value, last.value, list(rr), nh.mg.counts(), x.numpy(), [f.numpy() for f in h.x[1:] + h.b[1:]]))
     first = results[0]
     assert first[0] == 5 and first[4] == (1, 4, 5)
-    _, _, ref_x, _ = _reference(P, 5)
+    _, _, ref_x, _ = mgd.reference(P, 5)
     assert bits_equal(first[5], ref_x[0])
     for other in results[1:]:
         assert other[:5] == first[:5]
@@ -217,18 +119,7 @@ def test_without_lines_it_is_mg_solve(nh):
 def test_stops_where_the_definition_says_on_the_flux_hierarchy(nh, check_every, between):
     P = _problem(nh, "flux")
     assert [L.m for L in P.ref] == [(63, 63), (31, 31), (15, 15), (7, 7), (3, 3), (1, 1)]
-    if "seq" not in P.runs:
-        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6)
-    seq = P.runs["seq"]
-    tol2 = rst.tol_between(seq, *between)
-    max_cycles = len(seq) - 1
-    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
-    assert want_done == between[1]
-    (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
-    print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
-    assert (done, counts[2], len(rr_checks)) == (want_done, want_checks, want_checks)
-    assert counts[0] + counts[1] == done
-    assert rr_last == rr_checks[-1] <= tol2 and all(v > tol2 for v in rr_checks[:-1])
+    mgd.check_stop(nh, P, check_every, between)
 
 
 # ---------------------------------------------------------------- the Python layer
@@ -237,7 +128,7 @@ def _flux_level(nh, built, l):
     F = nh.fields.DeviceField
     R = levels[l]
     like = F.from_numpy(np.zeros(R.shape, R.dt))
-    return R, like, [F.from_numpy(a) for a in coefs[l]], _entry(nh, texts[l])
+    return R, like, [F.from_numpy(a) for a in coefs[l]], mgd.entry(nh, texts[l])
 
 
 @pytest.mark.parametrize("l", [0, 3, 5])
@@ -286,7 +177,7 @@ def test_levels_with_lines_through_the_python_layer(nh):
     x, b = F.from_numpy(P.x0), F.from_numpy(P.b)
     done, rr0, rr_last, rr_checks = nh.mg.solve(h, x, b, max_cycles=3)
     nh.torch.cuda.synchronize()
-    _, _, ref_x, _ = _reference(P, 3)
+    _, _, ref_x, _ = mgd.reference(P, 3)
     assert done == 3 and bits_equal(x.numpy(), ref_x[0]), mismatch_report(x.numpy(), ref_x[0])
     with pytest.raises(ValueError, match="line stages"):
         nh.mg.cg_solve(h, x, b, max_iters=2)

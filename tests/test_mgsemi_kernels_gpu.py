@@ -14,10 +14,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import helpers
+import mg_device
 import mg_restatement as rst
-import solver_trace_cases as stc
 from helpers import bits_equal, mismatch_report
+from mg_device import dev, field
 
 pytestmark = pytest.mark.gpu
 
@@ -39,67 +39,28 @@ IDS = [f"{n}-{np.dtype(d).name}" + ("-offset" if o else "") for n, d, o in RUNS]
 
 @pytest.fixture(scope="module")
 def nh(built_libs):
-    import torch
-    assert torch.cuda.is_available()
-    from neptune_hip import _capi, fields, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.fields, ns.mg = torch, _capi, fields, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
-    return ns
+    return mg_device.namespace()
 
 
-class Geometry:
-    def __init__(self, nh, name, dtype):
-        fbox, flo, fm, self.axes, clo = CASES[name]
-        cm = tuple((m - 1) // 2 if d in self.axes else m for d, m in enumerate(fm))
-        cbox = tuple(l + m + 1 + d for d, (l, m) in enumerate(zip(clo, cm)))             # unequal rims
-        self.fine_shape, self.coarse_shape = fbox, cbox
-        self.fw = tuple(slice(l, l + m) for l, m in zip(flo, fm))
-        self.cw = tuple(slice(l, l + m) for l, m in zip(clo, cm))
-        like = lambda shape: nh.fields.DeviceField.from_numpy(np.zeros(shape, dtype))
-        bounds = lambda w: ([s.start for s in w], [s.stop for s in w])
-        # the levels carry geometry only here (entry None: the kernels alone never call the operator)
-        self.fine = nh.mg.Level(None, like(fbox), bounds(self.fw))
-        self.coarse = nh.mg.Level(None, like(cbox), bounds(self.cw))
-
-
-def _field(shape, dtype, seed, where=None, outside=None, inside=None):
-    """hashed values with -0 sprinkled in; `outside` (e.g. NaN) on every cell that is not in `where`, `inside` on those in it"""
-    a = helpers.hash_field(shape, dtype, seed=seed)
-    flat = a.reshape(-1)
-    flat[::7] = -0.0
-    flat[3::11] = 0.0
-    if outside is not None:
-        keep = a[where].copy()
-        a[...] = outside
-        a[where] = keep
-    if inside is not None:
-        a[where] = inside
-    return a
-
-
-def _dev(nh, a, offset):
-    elems = offset // a.itemsize
-    return stc.offset_field(nh, a, elems) if offset else nh.fields.DeviceField.from_numpy(a)
+def Geometry(nh, name, dtype):
+    fbox, flo, fm, axes, clo = CASES[name]
+    cm = tuple((m - 1) // 2 if d in axes else m for d, m in enumerate(fm))
+    return mg_device.Geometry(nh, (fbox, flo, fm), (mg_device.unequal_rims(clo, cm), clo, cm), dtype, axes)
 
 
 @pytest.mark.parametrize("name,dtype,offset", RUNS, ids=IDS)
 def test_restrict(nh, name, dtype, offset):
     G = Geometry(nh, name, dtype)
     assert nh.mg.coarsened_axes(G.fine, G.coarse) == G.axes
-    b_f = _field(G.fine_shape, dtype, 21, G.fw, np.nan)       # nothing outside the fine Omega is read
-    q_f = _field(G.fine_shape, dtype, 22, G.fw, np.nan)
-    b_c = _field(G.coarse_shape, dtype, 23, G.cw, inside=np.nan)      # what the coarse Omega held does not matter
-    x_c = _field(G.coarse_shape, dtype, 24, G.cw, inside=np.nan)
+    b_f = field(G.fine_shape, dtype, 21, G.fw, np.nan)       # nothing outside the fine Omega is read
+    q_f = field(G.fine_shape, dtype, 22, G.fw, np.nan)
+    b_c = field(G.coarse_shape, dtype, 23, G.cw, inside=np.nan)      # what the coarse Omega held does not matter
+    x_c = field(G.coarse_shape, dtype, 24, G.cw, inside=np.nan)
     for a in (b_c, x_c):
         a[tuple(0 for _ in a.shape)] = np.nan
     want_b, want_x = rst.restrict(b_f, q_f, G.fw, 4.0, b_c, x_c, G.cw, G.axes)
-    bd, xd = _dev(nh, b_c, offset), _dev(nh, x_c, offset)
-    nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, offset), _dev(nh, q_f, offset), bd, xd)
+    bd, xd = dev(nh, b_c, offset), dev(nh, x_c, offset)
+    nh.mg.restrict(G.fine, G.coarse, dev(nh, b_f, offset), dev(nh, q_f, offset), bd, xd)
     nh.torch.cuda.synchronize()
     got_b, got_x = bd.numpy(), xd.numpy()
     assert bits_equal(got_b, want_b), mismatch_report(got_b, want_b)
@@ -110,12 +71,12 @@ def test_restrict(nh, name, dtype, offset):
 @pytest.mark.parametrize("name,dtype,offset", RUNS, ids=IDS)
 def test_prolong_add(nh, name, dtype, offset):
     G = Geometry(nh, name, dtype)
-    x_c = _field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # the coarse rim is +0 whatever the field holds there
-    x_f = _field(G.fine_shape, dtype, 32)
+    x_c = field(G.coarse_shape, dtype, 31, G.cw, np.nan)     # the coarse rim is +0 whatever the field holds there
+    x_f = field(G.fine_shape, dtype, 32)
     x_f[tuple(0 for _ in x_f.shape)] = np.nan
     want = rst.prolong_add(x_c, G.cw, x_f, G.fw, G.axes)
-    xd = _dev(nh, x_f, offset)
-    nh.mg.prolong_add(G.fine, G.coarse, _dev(nh, x_c, offset), xd)
+    xd = dev(nh, x_f, offset)
+    nh.mg.prolong_add(G.fine, G.coarse, dev(nh, x_c, offset), xd)
     nh.torch.cuda.synchronize()
     got = xd.numpy()
     assert bits_equal(got, want), mismatch_report(got, want)
@@ -134,8 +95,8 @@ def test_a_kept_axis_hands_minus_zero_and_nan_through(nh, dtype):
     b_f[:, :, k0] = -0.0
     b_f[:, :, k1] = np.nan
     want_b, want_x = rst.restrict(b_f, q_f, G.fw, 1.0, np.zeros(G.coarse_shape, dtype), np.ones(G.coarse_shape, dtype), G.cw, G.axes)
-    bd, xd = _dev(nh, np.zeros(G.coarse_shape, dtype), 0), _dev(nh, np.ones(G.coarse_shape, dtype), 0)
-    nh.mg.restrict(G.fine, G.coarse, _dev(nh, b_f, 0), _dev(nh, q_f, 0), bd, xd)
+    bd, xd = dev(nh, np.zeros(G.coarse_shape, dtype), 0), dev(nh, np.ones(G.coarse_shape, dtype), 0)
+    nh.mg.restrict(G.fine, G.coarse, dev(nh, b_f, 0), dev(nh, q_f, 0), bd, xd)
     nh.torch.cuda.synchronize()
     got = bd.numpy()
     assert bits_equal(got, want_b), mismatch_report(got, want_b)
@@ -144,7 +105,7 @@ def test_a_kept_axis_hands_minus_zero_and_nan_through(nh, dtype):
     assert np.isnan(inner).sum() == inner[:, :, 260].size and (np.delete(inner, [5, 260], axis=2) == 1).all()
     x_f = np.full(G.fine_shape, -0.0, dtype)
     want = rst.prolong_add(got, G.cw, x_f, G.fw, G.axes)
-    fd = _dev(nh, x_f, 0)
+    fd = dev(nh, x_f, 0)
     nh.mg.prolong_add(G.fine, G.coarse, bd, fd)
     nh.torch.cuda.synchronize()
     out = fd.numpy()

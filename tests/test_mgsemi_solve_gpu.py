@@ -1,5 +1,5 @@
 """neptune_hip_mg_solve and neptune_hip_mgcg_solve on semi-coarsened hierarchies against the NumPy restatement
-of tests/mgsemi_cases.py.
+of tests/mg_restatement.py, through the device harness of tests/mg_device.py.
 
 No reduction enters a field, so after any number of cycles x_0 and every level's x_l, b_l must equal the restatement's bit
 for bit, whatever the launch path (plain launches or the replayed graph of one cycle); for MGCG the restatement's recurrences
@@ -20,9 +20,10 @@ import pytest
 
 import helpers
 import mg_cases as mgc
+import mg_device as mgd
 import mg_restatement as rst
 import mgsemi_cases as sc
-from helpers import bits_equal, mismatch_report
+from helpers import bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -40,118 +41,25 @@ def _steps(name):
     return sc.plan(omega, weights) if axes is None else sc.with_axes(omega, weights, axes)
 
 
+def _dots(name):
+    """level 0 compiled with its dot entry: every problem MGCG runs on"""
+    return () if name == "plan_f64" else (0,)
+
+
 @pytest.fixture(scope="module")
 def nh(built_libs, tmp_path_factory):
-    import os
-    import torch
-    assert torch.cuda.is_available()
-    os.environ["NEPTUNE_CACHE_DIR"] = str(tmp_path_factory.mktemp("neptune_cache"))
-    from neptune_hip import _capi, apply, fields, lowering, multigrid
-
-    class NS:
-        pass
-    ns = NS()
-    ns.torch, ns.capi, ns.apply, ns.fields, ns.lowering, ns.mg = torch, _capi, apply, fields, lowering, multigrid
-    ns.lib = _capi.load()
-    ns.lib.neptune_hip_init(0)
+    ns = mgd.namespace(tmp_path_factory.mktemp("neptune_cache"), check=("coarsened",))
     ns.built = {name: sc.build_levels(_steps(name), PROBLEMS[name][3], PROBLEMS[name][4]) for name in PROBLEMS}
-    _prefetch(lowering, [(t, l == 0 and name != "plan_f64") for name, (_, texts) in ns.built.items() for l, t in enumerate(texts)])
-    ns.entries = {}
-    ns.cache = {}
+    mgd.prefetch([(t, l in _dots(name)) for name, (_, texts) in ns.built.items() for l, t in enumerate(texts)])
     return ns
 
 
-def _prefetch(lowering, jobs):
-    """every module compiled once, side by side (host threads only, nothing is loaded); level 0's with their dot entries"""
-    from concurrent.futures import ThreadPoolExecutor
-
-    def one(job):
-        try:
-            lowering.compile_module(job[0], load=False, dot_entries=job[1])
-        except Exception:       # noqa: BLE001 - the test that needs this module shows the diagnostic
-            pass
-    with ThreadPoolExecutor(max_workers=12) as pool:
-        list(pool.map(one, dict.fromkeys(jobs)))
-
-
-def _entry(nh, text, dot):
-    key = (text, dot)
-    if key not in nh.entries:
-        nh.entries[key] = (nh.lowering.compile_module(text, dot_entries=True).dot_entry("entry") if dot else
-                           nh.lowering.compile_module(text).geom_entry("entry"))
-    return nh.entries[key]
-
-
-class Problem:
-    pass
-
-
 def _problem(nh, name):
-    """the compiled operators, the restatement's levels, x0 and b: built once per problem, x0 and b left unchanged"""
-    if name not in nh.cache:
-        P = Problem()
+    def build(P):
         P.dtype = PROBLEMS[name][4]
         P.ref, P.texts = nh.built[name]
-        P.entries = [_entry(nh, t, l == 0 and name != "plan_f64") for l, t in enumerate(P.texts)]
         P.x0, P.b = mgc.problem_fields(P.ref[0].shape, P.ref[0].where, P.dtype)
-        for a in (P.x0, P.b):
-            a.setflags(write=False)
-        P.runs = {}
-        nh.cache[name] = P
-    return nh.cache[name]
-
-
-def _reference(P, cycles, check_every=1):
-    """the restatement's run, computed once per schedule and left unchanged: -> (rr0, checks, [x_l], [b_l])"""
-    key = (cycles, check_every)
-    if key not in P.runs:
-        rr0, checks = rst.run(P.ref, P.x0, P.b, cycles, check_every=check_every)
-        P.runs[key] = (rr0, checks, [L.x.copy() for L in P.ref], [L.b.copy() for L in P.ref])
-    return P.runs[key]
-
-
-def _hierarchy(nh, P):
-    """a device hierarchy whose work fields hold NaN; -> (h, x, b, [r, p, z])"""
-    F = nh.fields.DeviceField
-    levels = []
-    for l, R in enumerate(P.ref):
-        like = F.from_numpy(np.zeros(R.shape, P.dtype))
-        bounds = ([s.start for s in R.where], [s.stop for s in R.where])
-        levels.append(nh.mg.Level(P.entries[l], like, bounds, minv=F.from_numpy(R.minv), rscale=R.rscale))
-    h = nh.mg.Hierarchy(levels)
-    assert h.coarsened == [R.axes for R in P.ref[:-1]]
-    nan = lambda f: F.from_numpy(np.full(f.shape, np.nan, P.dtype))
-    h.q = [nan(f) for f in h.q]
-    h.x = [None] + [nan(f) for f in h.x[1:]]
-    h.b = [None] + [nan(f) for f in h.b[1:]]
-    return h, F.from_numpy(P.x0), F.from_numpy(P.b), [nan(h.q[0]) for _ in range(3)]
-
-
-def _solve(nh, P, max_cycles, tol2=0.0, check_every=1):
-    h, x, b, _ = _hierarchy(nh, P)
-    res = nh.mg.solve(h, x, b, max_cycles=max_cycles, tol2=tol2, check_every=check_every)
-    nh.torch.cuda.synchronize()
-    xs = [x.numpy()] + [f.numpy() for f in h.x[1:]]
-    bs = [b.numpy()] + [f.numpy() for f in h.b[1:]]
-    return res, xs, bs, nh.mg.counts()
-
-
-def _check_against_reference(nh, P, cycles, check_every=1, want_counts=None):
-    (done, rr0, rr_last, rr_checks), xs, bs, counts = _solve(nh, P, cycles, check_every=check_every)
-    ref_rr0, ref_checks, ref_x, ref_b = _reference(P, cycles, check_every)
-    assert done == cycles and len(rr_checks) == len(ref_checks) == -(-cycles // check_every)
-    if want_counts is not None:
-        assert counts == want_counts, counts
-    print(f"rr0 = {rr0!r} (terms' sum {ref_rr0[0]!r}, bound {ref_rr0[1]:.3e})")
-    assert abs(rr0 - ref_rr0[0]) <= ref_rr0[1]
-    for k, (got, (want, bound)) in enumerate(zip(rr_checks, ref_checks)):
-        print(f"  check {k}: rr = {got!r} (terms' sum {want!r}, bound {bound:.3e})")
-        assert abs(got - want) <= bound
-    assert rr_last == rr_checks[-1]
-    for l, (got, want) in enumerate(zip(xs, ref_x)):
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-    for l, (got, want) in enumerate(zip(bs, ref_b)):
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
+    return mgd.problem(nh, name, build, _dots(name))
 
 
 @pytest.mark.parametrize("cycles", [2, 5])
@@ -160,79 +68,35 @@ def test_cycles_match_the_restatement(nh, name, cycles):
     P = _problem(nh, name)
     assert [L.m for L in P.ref] == ([(7, 15, 263), (7, 7, 131), (3, 3, 65), (3, 3, 32)] if name.startswith("3d") else
                                     [(15, 263), (7, 263), (7, 131), (3, 65)])
-    _check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
+    mgd.check_against_reference(nh, P, cycles, want_counts=(2, 0, 2) if cycles == 2 else (1, 4, 5))
 
 
 def test_graph_and_plain_launches_give_identical_bits(nh, monkeypatch):
-    P = _problem(nh, "3d_f64")
-    monkeypatch.delenv("NEPTUNE_HIP_MG_GRAPH", raising=False)
-    res_g, xs_g, bs_g, counts_g = _solve(nh, P, 5)
-    monkeypatch.setenv("NEPTUNE_HIP_MG_GRAPH", "0")          # read at every call
-    res_p, xs_p, bs_p, counts_p = _solve(nh, P, 5)
-    assert counts_g == (1, 4, 5) and counts_p == (5, 0, 5)
-    assert res_g == res_p
-    for a, b in zip(xs_g + bs_g, xs_p + bs_p):
-        assert bits_equal(a, b), mismatch_report(a, b)
-    _, _, ref_x, _ = _reference(P, 5)
-    assert bits_equal(xs_p[0], ref_x[0])
+    mgd.graph_vs_plain(nh, _problem(nh, "3d_f64"), monkeypatch, 5)
 
 
 @pytest.mark.parametrize("check_every,between", [(1, (2, 3)), (3, (3, 6))])
 def test_stops_where_the_definition_says_on_the_plan_hierarchy(nh, check_every, between):
     P = _problem(nh, "plan_f64")
     assert [L.m for L in P.ref[:5]] == [(63, 63), (63, 31), (63, 15), (63, 7), (31, 3)]
-    if "seq" not in P.runs:
-        P.runs["seq"] = rst.rr_sequence(P.ref, P.x0, P.b, 6)
-    seq = P.runs["seq"]
-    tol2 = rst.tol_between(seq, *between)
-    max_cycles = len(seq) - 1
-    want_done, want_checks = rst.expected_stop(seq, check_every, max_cycles, tol2)
-    assert want_done == between[1]
-    (done, rr0, rr_last, rr_checks), _, _, counts = _solve(nh, P, max_cycles, tol2=tol2, check_every=check_every)
-    print(f"seq = {seq}, tol2 = {tol2!r}, done = {done}, checks = {rr_checks}")
-    assert (done, counts[2], len(rr_checks)) == (want_done, want_checks, want_checks)
-    assert counts[0] + counts[1] == done
-    assert rr_last == rr_checks[-1] <= tol2 and all(v > tol2 for v in rr_checks[:-1])
+    mgd.check_stop(nh, P, check_every, between)
 
 
 # ---------------------------------------------------------------- MGCG
 @pytest.mark.parametrize("iters", [2, 5])
 @pytest.mark.parametrize("name", ["3d_f32", "3d_f64"])
 def test_mgcg_replay_from_the_traced_scalars_reproduces_every_field(nh, name, iters):
-    P = _problem(nh, name)
-    h, x, b, work = _hierarchy(nh, P)
-    done, rr0, rr_last, trace = nh.mg.cg_solve(h, x, b, max_iters=iters, trace=True, work=work)
-    nh.torch.cuda.synchronize()
-    counts, rz0 = nh.mg.cg_counts(), nh.mg.cg_rz0()
-    assert done == iters and trace.shape == (iters, 3)
-    assert counts == ((2, 0, 0, 2) if iters == 2 else (1, 4, 0, 5)), counts
-    st, checks, rr0_ref, rz0_ref, _ = rst.replay(P.ref, P.x0, P.b, rz0, trace)
-    rx, rr, rp, rz = st.x, st.r, st.p, st.z
-    print(f"rr0 = {rr0!r} (terms' sum {rr0_ref[0]!r}, bound {rr0_ref[1]:.3e})  rz0 = {rz0!r} (sum {rz0_ref[0]!r}, bound {rz0_ref[1]:.3e})")
-    assert abs(rr0 - rr0_ref[0]) <= rr0_ref[1] and abs(rz0 - rz0_ref[0]) <= rz0_ref[1]
-    for k, sums in enumerate(checks):
-        print(f"  k={k}: " + "  ".join(f"{nm} = {trace[k][c]!r} (sum {s!r}, bound {bd:.3e})"
-                                        for c, (nm, (s, bd)) in enumerate(zip(("pq", "rz'", "rr'"), sums))))
-        for c, (s, bd) in enumerate(sums):
-            assert abs(float(trace[k][c]) - s) <= bd
-    assert rr_last == float(trace[-1][2])
-    for nm, got, want in (("x", x.numpy(), rx), ("r", work[0].numpy(), rr), ("p", work[1].numpy(), rp), ("z", work[2].numpy(), rz)):
-        assert bits_equal(got, want), f"{nm}: " + mismatch_report(got, want)
-    for l in range(1, len(P.ref)):
-        got, want = h.x[l].numpy(), P.ref[l].x
-        assert bits_equal(got, want), f"x_{l}: " + mismatch_report(got, want)
-        got, want = h.b[l].numpy(), P.ref[l].b
-        assert bits_equal(got, want), f"b_{l}: " + mismatch_report(got, want)
+    mgd.check_replay(nh, _problem(nh, name), iters, want_counts=(2, 0, 0, 2) if iters == 2 else (1, 4, 0, 5))
 
 
 # ---------------------------------------------------------------- the Python wrappers
 def test_python_wrappers(nh):
     P = _problem(nh, "3d_f64")
-    h, x, b, _ = _hierarchy(nh, P)
+    h, x, b, _ = mgd.hierarchy(nh, P)
     assert h.coarsened == [(1, 2), (0, 1, 2), (2,)]
     for l, axes in enumerate(h.coarsened):
         assert nh.mg.coarsened_axes(h.levels[l], h.levels[l + 1]) == axes
-        bounds = ([s.start for s in P.ref[l].where], [s.stop for s in P.ref[l].where])
+        bounds = mgd.bounds(P.ref[l].where)
         assert tuple(nh.mg.coarsen_bounds(bounds, axes=axes)) == P.ref[l + 1].m
     with pytest.raises(nh.capi.NeptuneHipError):
         nh.mg.coarsened_axes(h.levels[0], h.levels[0])
