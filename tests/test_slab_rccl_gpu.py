@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers
+from slab_fuzz_cases import loopback   # the local buffer after a loop-back exchange of its r ghost planes per side
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +20,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def cache_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("neptune_cache_slab_c")   # modules compile once for both transports
-
-
-def loopback(local, lo, hi, r, transport):
-    """the local buffer after a loop-back exchange of its r ghost planes per side"""
-    ext = local.copy()
-    if transport == "rccl":
-        ext[:lo], ext[hi:] = local[lo:lo + r], local[hi - r:hi]
-    else:
-        ext[:lo], ext[hi:] = local[hi - r:hi], local[lo:lo + r]
-    return ext
 
 
 @pytest.fixture(scope="module", params=["rccl", "peer"])
