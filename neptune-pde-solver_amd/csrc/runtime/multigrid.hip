@@ -16,7 +16,9 @@
 //
 // Every driver runs its loop on run_blocks: blocks of check_every units (a cycle, an iteration), the first unit as plain
 // launches, then ONE capture of a unit as a linear graph on the call's stream that every later unit replays; the graph is
-// destroyed when the call returns.
+// destroyed when the call returns.  That stream is a StreamScope's (solver_host.hpp): the one bridge stream the step loops and
+// the Krylov solvers use too when the caller passes the legacy default stream.  The capture query, the read-back of device
+// scalars, the outer operator of MGCG and the out-parameters' bookkeeping are that header's as well.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -32,22 +34,13 @@
 #include "../kernels/mg_line_kernels.hpp"
 #include "../kernels/mgcg_kernels.hpp"
 #include "../kernels/mgcg_mixed_kernels.hpp"
+#include "solver_host.hpp"
 
 using namespace neptune_hip;
 
 namespace {
 
 constexpr int kMaxLevels = 16;
-
-// what neptune_hip_rt.hip's ensure_init does (device 0 unless the runtime is up already), through the public API
-void ensure_init() { (void)neptune_hip_cu_count(); }
-
-bool known_dtype(int dtype) { return dtype == NEPTUNE_HIP_F64 || dtype == NEPTUNE_HIP_F32; }
-size_t elem_size(int dtype) { return dtype == NEPTUNE_HIP_F64 ? 8 : 4; }
-// a launch configuration, nullptr unless the caller set anything in it
-const neptune_hip_launch_cfg_t* set_cfg(const neptune_hip_launch_cfg_t* cfg) {
-  return (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
-}
 
 // A level's box and Omega = apply.bounds x launch region on the kernels' three axes (the field's dimensions right-aligned);
 // -> false for a malformed geometry, an input 0 in another box than the result's, or an empty Omega
@@ -375,39 +368,6 @@ int do_line(int dtype, int mode, const MgBox& B, int axis, void* q, const void* 
   });
 }
 
-bool stream_capturing(void* stream) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (stream && hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-  return cs != hipStreamCaptureStatusNone;
-}
-
-// The stream a solve runs on.  The legacy default stream cannot be captured: the solve then runs on an internal stream
-// ordered after everything already queued on the default stream, and the destructor orders the default stream after it.
-hipStream_t g_mg_stream = nullptr;
-hipEvent_t g_mg_ev[2] = {nullptr, nullptr};
-struct SolveStream {
-  hipStream_t stream;
-  const bool bridged;
-  explicit SolveStream(hipStream_t user) : stream(user), bridged(!user) {
-    if (!bridged) return;
-    if (!g_mg_stream) {
-      NEPTUNE_HIP_CHECK(hipStreamCreateWithFlags(&g_mg_stream, hipStreamNonBlocking));
-      NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_mg_ev[0], hipEventDisableTiming));
-      NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_mg_ev[1], hipEventDisableTiming));
-    }
-    NEPTUNE_HIP_CHECK(hipEventRecord(g_mg_ev[0], nullptr));
-    NEPTUNE_HIP_CHECK(hipStreamWaitEvent(g_mg_stream, g_mg_ev[0], 0));
-    stream = g_mg_stream;
-  }
-  ~SolveStream() {
-    if (!bridged) return;
-    NEPTUNE_HIP_CHECK(hipEventRecord(g_mg_ev[1], g_mg_stream));
-    NEPTUNE_HIP_CHECK(hipStreamWaitEvent(nullptr, g_mg_ev[1], 0));
-  }
-  SolveStream(const SolveStream&) = delete;
-  SolveStream& operator=(const SolveStream&) = delete;
-};
-
 int64_t g_mg_counts[3] = {0, 0, 0};   // plain cycles, graph cycles, checks of the last solve
 
 // one solve, its arguments checked
@@ -445,7 +405,7 @@ struct Solve {
       if (!level_box(&L.g, box[l]) || L.g.rank != rank) return false;
       if (!L.fn) {
         if (L.body < 0 || L.body >= NEPTUNE_HIP_BODY_COUNT) return false;
-        if ((L.body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64) != dtype) return false;
+        if (body_dtype(L.body) != dtype) return false;
       }
       if (L.g.num_inputs > 1 && !L.in_rest) return false;
       for (int i = 1; i < L.g.num_inputs; ++i)
@@ -571,18 +531,10 @@ struct Solve {
     if (rc != NEPTUNE_HIP_OK) return rc;
     rc = neptune_hip_update_norm(dtype, &levels[0].g, levels[0].b, levels[0].q, rr_dev, (void*)stream);
     if (rc != NEPTUNE_HIP_OK) return rc;
-    double h64 = 0.0;
-    float h32 = 0.0f;
-    void* h = dtype == NEPTUNE_HIP_F64 ? (void*)&h64 : (void*)&h32;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(h, rr_dev, elem_size(dtype), hipMemcpyDeviceToHost, stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(stream));
-    *rr = dtype == NEPTUNE_HIP_F64 ? h64 : (double)h32;
+    read_scalars(dtype, stream, rr_dev, 1, rr);
     return NEPTUNE_HIP_OK;
   }
 };
-
-// a late refusal: after the first launch of a cycle the fields have moved
-int late(int rc) { return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc; }
 
 bool graph_path_enabled() {
   const char* e = getenv("NEPTUNE_HIP_MG_GRAPH");
@@ -675,12 +627,6 @@ bool grow_mgcg_ws(size_t bytes, void* stream) {
 void* mgcg_partials(int64_t count, size_t elem, void* stream) {
   if (!grow_mgcg_ws(kMgcgScalarBytes + (size_t)count * elem, stream)) return nullptr;
   return static_cast<char*>(g_mgcg_ws) + kMgcgScalarBytes;
-}
-
-bool region_is_whole(const neptune_hip_apply_geom_t* g) {
-  bool whole = true;
-  for (int d = 0; d < g->rank; ++d) whole = whole && g->region_lb[d] <= 0 && g->region_ub[d] >= g->out_ub[d] - g->out_lb[d];
-  return whole;
 }
 
 // what an MGCG entry hands its driver once the arguments are checked
@@ -811,25 +757,8 @@ int mgcg_drive(const Solve& S, const neptune_hip_mg_level_t& O, const neptune_hi
   auto final_kernel = [&](int64_t count, int stage) {
     hipLaunchKernelGGL(neptune_mgcg_final<D>, dim3(1), dim3(256), 0, stream, (const D*)f.partials, count, f.scal, rz0_dev, tr, a.max_iters, stage);
   };
-  // one or two device scalars after everything queued on the stream: the one synchronise of a block
-  auto read = [&](const D* dev, double* host, const D* dev2 = nullptr, double* host2 = nullptr) {
-    D h = 0, h2 = 0;
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, dev, sizeof(D), hipMemcpyDeviceToHost, stream));
-    if (dev2) NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h2, dev2, sizeof(D), hipMemcpyDeviceToHost, stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(stream));
-    *host = (double)h;
-    if (dev2) *host2 = (double)h2;
-  };
-  // the outer operator's inputs with `in0` as input 0, and q = A(in0) by it, a plain launch in D
-  auto outer_inputs = [&](const void* in0, const void** ins) {
-    ins[0] = in0;
-    for (int i = 1; i < O.g.num_inputs; ++i) ins[i] = O.in_rest[i - 1];
-  };
-  auto outer_apply = [&](const void* in0) -> int {
-    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    outer_inputs(in0, ins);
-    return O.fn ? O.fn(&O.g, ins, O.q, (void*)stream, ocfg) : neptune_hip_apply_builtin(O.body, &O.g, ins, O.q, (void*)stream, ocfg);
-  };
+  // the outer operator: q = A(in0) in D, plainly or through the dot-monitored entry
+  const OuterOperator A = {O.fn, a.fn_dot, O.body, &O.g, O.in_rest, ocfg, stream};
   // the rest of M: everything of the cycle on A z = r_in after its first pre-sweep (z = minv r_in, stored with r_in; with
   // line stages: stage 0 without an apply, from z = 0, then the other stages); its last post-sweep yields r_in . z in D,
   // which `stage` of the bookkeeping kernel takes
@@ -862,35 +791,30 @@ int mgcg_drive(const Solve& S, const neptune_hip_mg_level_t& O, const neptune_hi
   if (!region_is_whole(&O.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(f.q, 0, (size_t)f.n * sizeof(D), stream));
   // with line stages on level 0, z outside Omega_0 is the error equation's rim: zero-filled here, never written again
   if (k0) NEPTUNE_HIP_CHECK(hipMemsetAsync(f.z, 0, (size_t)f.n * sizeof(Sx), stream));
-  int rc = outer_apply(f.x);
+  int rc = A.apply(f.x, f.q);
   if (rc != NEPTUNE_HIP_OK) return rc;
   P::init(f, Bp, init_chunk, init_grid, stream);
   final_kernel(grid_blocks(init_grid), kMgcgStartRr);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   double rr = 0.0;
-  read(&f.scal->rr, &rr);
-  if (a.rr0) *a.rr0 = rr;
-  if (a.rr_last) *a.rr_last = rr;
-  if (rr <= a.tol2 || a.max_iters == 0) return NEPTUNE_HIP_OK;
+  read_scalars(stream, &f.scal->rr, 1, &rr);
+  if (done_after_setup(rr, a.tol2, a.max_iters, a.rr0, a.rr_last)) return NEPTUNE_HIP_OK;
   rc = rest_of_cycle(kMgcgStartRz);
   if (rc != NEPTUNE_HIP_OK) return late(rc);
   P::p_from_z(f, dir, stream);
 
   // ---- one iteration.  fused: q = A(p) and pq out of one dot-monitored launch; a refusal of that entry
   // (NEPTUNE_HIP_EUNSUPPORTED, nothing launched) is remembered: a plain launch and neptune_hip_dot from then on
-  bool fused = O.fn ? a.fn_dot != nullptr : true;
+  bool fused = A.has_dot();
   auto iteration = [&]() -> int {
     int rc;
     if (fused) {
-      const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-      outer_inputs(f.p, ins);
-      rc = O.fn ? a.fn_dot(&O.g, ins, O.q, &f.scal->pq, (void*)stream, ocfg)
-                : neptune_hip_apply_builtin_dot(O.body, &O.g, ins, O.q, &f.scal->pq, (void*)stream, ocfg);
+      rc = A.apply_dot(f.p, f.q, &f.scal->pq);
       if (rc == NEPTUNE_HIP_EUNSUPPORTED) fused = false;
       else if (rc != NEPTUNE_HIP_OK) return rc;
     }
     if (!fused) {
-      rc = outer_apply(f.p);
+      rc = A.apply(f.p, f.q);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
       rc = neptune_hip_dot(dtype_outer, &O.g, f.q, f.p, &f.scal->pq, (void*)stream);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
@@ -920,8 +844,8 @@ int mgcg_drive(const Solve& S, const neptune_hip_mg_level_t& O, const neptune_hi
   bool rz0_read = false;
   return run_blocks(stream, a.max_iters, a.check_every, a.tol2, a.iters_done, a.rr_last, iteration,
                     [&](double* out) -> int {   // the first check reads rz_0 as well
-                      if (!rz0_read) read(&f.scal->rr, out, rz0_dev, &g_mgcg_rz0);
-                      else read(&f.scal->rr, out);
+                      if (!rz0_read) read_scalars(stream, &f.scal->rr, out, (const D*)rz0_dev, &g_mgcg_rz0);
+                      else read_scalars(stream, &f.scal->rr, 1, out);
                       rz0_read = true;
                       ++g_mgcg_counts[3];
                       return NEPTUNE_HIP_OK;
@@ -988,12 +912,10 @@ int prolong_alone(int dtype, const neptune_hip_apply_geom_t* g_fine, const neptu
   return do_prolong(dtype, P, x_coarse, x_fine, reinterpret_cast<hipStream_t>(stream));
 }
 
-void mgcg_reset(int64_t* iters_done, double* rr0, double* rr_last) {
+// MGCG's own part of what an entry resets before anything is checked
+void mgcg_reset() {
   g_mgcg_counts[0] = g_mgcg_counts[1] = g_mgcg_counts[2] = g_mgcg_counts[3] = 0;
   g_mgcg_rz0 = 0.0;
-  if (iters_done) *iters_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
 }
 
 }  // namespace
@@ -1114,9 +1036,7 @@ int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t* levels, const ne
                                   int64_t max_cycles, int64_t check_every, double tol2, double* rr_checks, void* stream,
                                   const neptune_hip_launch_cfg_t* cfg, int64_t* cycles_done, double* rr0, double* rr_last) {
   g_mg_counts[0] = g_mg_counts[1] = g_mg_counts[2] = 0;
-  if (cycles_done) *cycles_done = 0;
-  if (rr0) *rr0 = 0.0;
-  if (rr_last) *rr_last = 0.0;
+  reset_solver_outputs(cycles_done, rr0, rr_last);
   // ---- the refusals, before anything touches the device
   if (check_every < 1 || max_cycles < 0) return NEPTUNE_HIP_EINVAL;
   Solve S;
@@ -1125,7 +1045,7 @@ int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t* levels, const ne
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
   ensure_init();
-  SolveStream sc(reinterpret_cast<hipStream_t>(stream));
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
   S.stream = sc.stream;
   struct Scalar {   // one device T for r . r, this call's
     void* p = nullptr;
@@ -1137,9 +1057,7 @@ int neptune_hip_mg_solve_transfer(const neptune_hip_mg_level_t* levels, const ne
   double rr = 0.0;
   const int rc = S.residual(rr_dev.p, &rr);
   if (rc != NEPTUNE_HIP_OK) return rc;
-  if (rr0) *rr0 = rr;
-  if (rr_last) *rr_last = rr;
-  if (rr <= tol2) return NEPTUNE_HIP_OK;
+  if (done_after_setup(rr, tol2, max_cycles, rr0, rr_last)) return NEPTUNE_HIP_OK;
 
   struct Hooks {
     void capturing() {}
@@ -1172,7 +1090,8 @@ int neptune_hip_mgcg_solve_mixed_transfer(const neptune_hip_mg_level_t* outer, i
                                           int coarse_sweeps, void* const work[2], int64_t max_iters, int64_t check_every, double tol2,
                                           void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
                                           double* rr_last) {
-  mgcg_reset(iters_done, rr0, rr_last);
+  mgcg_reset();
+  reset_solver_outputs(iters_done, rr0, rr_last);
   // ---- the refusals, before anything touches the device
   if (dtype_outer != NEPTUNE_HIP_F64 || dtype_inner != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
   if (!outer || n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
@@ -1204,7 +1123,7 @@ int neptune_hip_mgcg_solve_mixed_transfer(const neptune_hip_mg_level_t* outer, i
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
   ensure_init();
-  SolveStream sc(reinterpret_cast<hipStream_t>(stream));
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
   S.stream = sc.stream;
   const MgcgArgs a = {fn_dot, sweeps, work, max_iters, check_every, tol2, trace, iters_done, rr0, rr_last};
   return mgcg_drive<MgcgMixed>(S, O, set_cfg(cfg), a);
@@ -1239,7 +1158,8 @@ int neptune_hip_mgcg_solve_transfer(const neptune_hip_mg_level_t* levels, const 
                                     int sweeps, int coarse_sweeps, void* const work[3], int64_t max_iters, int64_t check_every, double tol2,
                                     void* trace, void* stream, const neptune_hip_launch_cfg_t* cfg, int64_t* iters_done, double* rr0,
                                     double* rr_last) {
-  mgcg_reset(iters_done, rr0, rr_last);
+  mgcg_reset();
+  reset_solver_outputs(iters_done, rr0, rr_last);
   // ---- the refusals, before anything touches the device
   if (n_levels < 2 || sweeps < 1 || check_every < 1 || max_iters < 0 || !work) return NEPTUNE_HIP_EINVAL;
   Solve S;
@@ -1256,7 +1176,7 @@ int neptune_hip_mgcg_solve_transfer(const neptune_hip_mg_level_t* levels, const 
   if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
 
   ensure_init();
-  SolveStream sc(reinterpret_cast<hipStream_t>(stream));
+  StreamScope sc(reinterpret_cast<hipStream_t>(stream));
   S.stream = sc.stream;
   // the preconditioner's hierarchy: level 0 carries (z, r) for (x, b)
   neptune_hip_mg_level_t lv[kMaxLevels];

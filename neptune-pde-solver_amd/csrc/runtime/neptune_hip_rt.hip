@@ -22,6 +22,7 @@
 #include "../kernels/reduce_launch.hpp"
 #include "../kernels/util_kernels.hpp"
 #include "rt_bodies.hpp"
+#include "solver_host.hpp"   // ensure_init and step_loop_destroy_graphs (declared there), stream_capturing
 
 using namespace neptune_hip;
 
@@ -51,12 +52,6 @@ RuntimeState& rt() {
 [[noreturn]] void die(const char* what) {
   fprintf(stderr, "[NeptuneRT][HIP] %s\n", what);
   abort();
-}
-
-void ensure_init() {
-  RuntimeState& s = rt();
-  if (s.inited) return;
-  neptune_hip_init(s.device < 0 ? 0 : s.device);
 }
 
 inline hipStream_t as_stream(void* p) { return reinterpret_cast<hipStream_t>(p); }
@@ -310,10 +305,11 @@ int reduce_kind(int kind, bool raw, const ReducePlan& pl, const void* src, doubl
 }
 }  // namespace
 
-// step_loop.hip: destroys the cached graphs of the step loops (declared here rather than in a header: the headers of this
-// directory are hashed into NEPTUNE_HIP_BUILD_ID)
-namespace neptune_hip {
-__attribute__((visibility("hidden"))) void step_loop_destroy_graphs();
+// solver_host.hpp: the runtime is up from here on -- on device 0 unless neptune_hip_init has chosen another
+void neptune_hip::ensure_init() {
+  RuntimeState& s = rt();
+  if (s.inited) return;
+  neptune_hip_init(s.device < 0 ? 0 : s.device);
 }
 
 extern "C" {
@@ -592,9 +588,7 @@ void* neptune_hip_monitor_workspace(size_t bytes, void* stream) {
   std::lock_guard<std::mutex> lk(s.mu);
   if (bytes <= s.monitor_bytes) return s.monitor_ws;
   // growing frees the old block, which waits for the launches that may still write it: not inside a stream capture
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(as_stream(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-  if (cs != hipStreamCaptureStatusNone) return nullptr;
+  if (stream_capturing(stream)) return nullptr;
   size_t want = s.monitor_bytes ? s.monitor_bytes : (size_t)1 << 16;
   while (want < bytes) want *= 2;
   if (s.monitor_ws) NEPTUNE_HIP_CHECK(hipFree(s.monitor_ws));

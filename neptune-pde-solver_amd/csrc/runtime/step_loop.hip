@@ -1,10 +1,11 @@
-// step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (stream scope, graph cache, replay,
-// grouping choice) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
+// step_loop.hip -- include/neptune_hip.h: the hipGraph step loops.  One replay engine (graph cache, replay, grouping choice,
+// on the stream scope of solver_host.hpp) that knows nothing about ping-pong or leapfrog, and the three loops built on it:
 // neptune_hip_step_loop_chain (one-level schemes, two fields), neptune_hip_step_loop_leapfrog (two-level schemes, three or
 // four fields) and neptune_hip_step_loop_system (a group of sibling applies: two SETS of fields); and the Krylov solvers
 // neptune_hip_cg_solve / neptune_hip_pcg_solve / neptune_hip_bicgstab_solve, whose iteration the same engine replays: ONE
-// host schedule (SolverFrame: the operator's launches, the key, blocks of iterations, the read-back, the counters), and per
-// solver its set-up and its iteration.  Its own translation unit (builds in seconds, linked into libneptune_hip.so): host
+// host schedule (SolverFrame: the key, blocks of iterations, the counters), and per solver its set-up and its iteration.
+// What multigrid.hip needs as well -- the stream scope, the capture query, the operator's launches, the read-back, the
+// out-parameters -- is solver_host.hpp's.  Its own translation unit (builds in seconds, linked into libneptune_hip.so): host
 // code that launches applies through the public C API, plus the solvers' few vector kernels (krylov_kernels.hpp).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -16,13 +17,11 @@
 #include "../../../include/neptune_hip.h"
 #include "../kernels/apply_launch.hpp"   // NEPTUNE_HIP_CHECK, tune_mode (no apply kernel is instantiated here)
 #include "../kernels/krylov_kernels.hpp"
+#include "solver_host.hpp"
 
 using namespace neptune_hip;
 
 namespace {
-
-// what neptune_hip_rt.hip's ensure_init does (device 0 unless the runtime is up already), through the public API
-void ensure_init() { (void)neptune_hip_cu_count(); }
 
 // ---------------------------------------------------------------- what a loop is: the key of both caches
 using group_fn = void (*)();   // an entry of a larger grouping, untyped: the caches only compare it
@@ -55,10 +54,6 @@ void init_key(LoopKey& k, neptune_hip_apply_fn fn, int body, const neptune_hip_a
   if (cfg) k.cfg = *cfg; else k.cfg.variant = -1;
   k.stream = stream;
 }
-// the cfg to launch with: nullptr unless the caller set anything
-const neptune_hip_launch_cfg_t* set_cfg(const neptune_hip_launch_cfg_t* cfg) {
-  return (cfg && (cfg->kernel || cfg->variant >= 0 || cfg->chunk || cfg->flags)) ? cfg : nullptr;
-}
 const neptune_hip_launch_cfg_t* loop_cfg(const LoopKey& k) { return set_cfg(&k.cfg); }
 // the inputs of one launch: the state in fields[cur], a two-level scheme's previous state in fields[prev] (-1: none), the rest
 // riding along unchanged
@@ -67,42 +62,6 @@ void loop_inputs(const LoopKey& k, const void** ins, int cur, int prev) {
   ins[0] = k.fields[cur];
   if (prev >= 0) ins[1] = k.fields[prev];
 }
-
-// ---------------------------------------------------------------- stream scope
-hipStream_t g_loop_stream = nullptr;   // stands in for the legacy default stream, which cannot be captured
-hipEvent_t g_loop_ev[2] = {nullptr, nullptr};
-
-// The stream a loop body runs on, and whether the caller is capturing it.  The legacy default stream cannot be captured: the
-// loop then runs on an internal stream ordered after everything already queued on the default stream, and the destructor
-// orders the default stream after the loop -- on every exit path.
-struct StreamScope {
-  hipStream_t stream;
-  bool capturing;
-  const bool bridged;
-  explicit StreamScope(hipStream_t user) : stream(user), bridged(!user) {
-    if (bridged) {
-      if (!g_loop_stream) {
-        NEPTUNE_HIP_CHECK(hipStreamCreateWithFlags(&g_loop_stream, hipStreamNonBlocking));
-        NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[0], hipEventDisableTiming));
-        NEPTUNE_HIP_CHECK(hipEventCreateWithFlags(&g_loop_ev[1], hipEventDisableTiming));
-      }
-      NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[0], nullptr));
-      NEPTUNE_HIP_CHECK(hipStreamWaitEvent(g_loop_stream, g_loop_ev[0], 0));
-      stream = g_loop_stream;
-    }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    capturing = cs != hipStreamCaptureStatusNone;
-  }
-  ~StreamScope() {
-    if (bridged) {
-      NEPTUNE_HIP_CHECK(hipEventRecord(g_loop_ev[1], g_loop_stream));
-      NEPTUNE_HIP_CHECK(hipStreamWaitEvent(nullptr, g_loop_ev[1], 0));
-    }
-  }
-  StreamScope(const StreamScope&) = delete;
-  StreamScope& operator=(const StreamScope&) = delete;
-};
 
 // ---------------------------------------------------------------- graph cache
 struct LoopGraph {
@@ -362,8 +321,8 @@ int one_level_loop(const StreamScope& sc, neptune_hip_apply_fn fn, neptune_hip_a
 }  // namespace
 
 namespace neptune_hip {
-// for neptune_hip_finalize (declared in neptune_hip_rt.hip; not exported)
-__attribute__((visibility("hidden"))) void step_loop_destroy_graphs() {
+// for neptune_hip_finalize (solver_host.hpp; not exported)
+void step_loop_destroy_graphs() {
   std::lock_guard<std::mutex> lk(g_loop_mu);
   for (auto& e : g_loops) {
     destroy_graph(e);
@@ -424,18 +383,10 @@ int neptune_hip_step_loop_until(neptune_hip_apply_fn fn, neptune_hip_apply_norm_
   if (!g || !fields || !fields[0] || !fields[1] || fields[0] == fields[1] || max_steps < 0 || check_every < 1) return NEPTUNE_HIP_EINVAL;
   if (g->num_inputs < 1 || g->num_inputs > NEPTUNE_HIP_MAX_INPUTS) return NEPTUNE_HIP_EINVAL;
   if (g->num_inputs > 1 && !in) return NEPTUNE_HIP_EINVAL;
-  int dtype = dtype_of_fn;
-  if (!fn) {
-    if (body < 0 || body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
-    dtype = body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64;
-  }
-  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
-  {
-    // the scalar is read back after every block: not while the caller's stream is being captured
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return NEPTUNE_HIP_EINVAL;
-  }
+  int dtype = 0;
+  if (!entry_dtype(fn, body, dtype_of_fn, &dtype)) return NEPTUNE_HIP_EINVAL;
+  // the scalar is read back after every block: not while the caller's stream is being captured
+  if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
   ensure_init();
   if (max_steps == 0) return NEPTUNE_HIP_OK;
   if (!g_until_sum) NEPTUNE_HIP_CHECK(hipMalloc(&g_until_sum, 8));
@@ -479,17 +430,7 @@ int neptune_hip_step_loop_until(neptune_hip_apply_fn fn, neptune_hip_apply_norm_
     cur ^= 1;
     ++done;
     if (steps_done) *steps_done = done;
-    if (dtype == NEPTUNE_HIP_F64) {
-      double h = 0;
-      NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, sum_dev, sizeof(h), hipMemcpyDeviceToHost, sc.stream));
-      NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-      sum = h;
-    } else {
-      float h = 0;
-      NEPTUNE_HIP_CHECK(hipMemcpyAsync(&h, sum_dev, sizeof(h), hipMemcpyDeviceToHost, sc.stream));
-      NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-      sum = (double)h;
-    }
+    read_scalars(dtype, sc.stream, sum_dev, 1, &sum);
     ++g_until_counts[2];
     if (last_sum) *last_sum = sum;
     if (sum <= tol2) break;   // false for a NaN sum: such a loop runs to max_steps
@@ -666,16 +607,6 @@ int64_t solver_box(const neptune_hip_apply_geom_t* g, CgBoxParams& B) {
   axes(hi, B.hi, 1);
   return n;
 }
-// whether the launch region is the whole box (an apply stores nothing outside its launch region)
-bool region_is_whole(const neptune_hip_apply_geom_t* g) {
-  bool whole = true;
-  for (int d = 0; d < g->rank; ++d) whole = whole && g->region_lb[d] <= 0 && g->region_ub[d] >= g->out_ub[d] - g->out_lb[d];
-  return whole;
-}
-
-// a launch's error, or what an iteration answers for it: a refusal after the iteration's first launch is an error
-int late(int rc) { return rc == NEPTUNE_HIP_EUNSUPPORTED ? NEPTUNE_HIP_EINVAL : rc; }
-
 // a solver entry's arguments once they are checked (include/neptune_hip.h); minv: nullptr unless neptune_hip_pcg_solve
 struct SolveArgs {
   neptune_hip_apply_fn fn;
@@ -696,54 +627,25 @@ struct SolveArgs {
   double* rr_last;
 };
 
-// What the host loops of all solvers share: the box and the set-up grid, the operator's launches, the read-back of a device
-// scalar, the common part of the graph key and the schedule -- blocks of check_every iterations, each replayed through the
-// engine, r . r read back after each.  A solver is its set-up, its `iteration` and one call of run().
+// What the host loops of all solvers share: the box and the set-up grid, the operator A (solver_host.hpp), the common part of
+// the graph key and the schedule -- blocks of check_every iterations, each replayed through the engine, r . r read back after
+// each.  A solver is its set-up, its `iteration` and one call of run().
 template <class T>
 struct SolverFrame {
   const StreamScope& sc;
   const SolveArgs& a;
-  const neptune_hip_launch_cfg_t* const c;   // the cfg to launch with
+  const OuterOperator A;
   CgBoxParams B;
   int64_t n, nchunk, init_blocks;
   dim3 init_grid;
   bool fused_ok;   // false once the dot-monitored entry has refused this geometry
 
-  SolverFrame(const StreamScope& sc_, const SolveArgs& a_) : sc(sc_), a(a_), c(set_cfg(a_.cfg)), fused_ok(a_.fn ? a_.fn_dot != nullptr : true) {
+  SolverFrame(const StreamScope& sc_, const SolveArgs& a_)
+      : sc(sc_), a(a_), A{a_.fn, a_.fn_dot, a_.body, a_.g, a_.in_rest, set_cfg(a_.cfg), sc_.stream}, fused_ok(A.has_dot()) {
     n = solver_box(a.g, B);
     nchunk = (B.n[2] + 255) / 256;
     init_grid = grid_for_blocks(B.n[0] * B.n[1] * nchunk);
     init_blocks = (int64_t)init_grid.x * init_grid.y;
-  }
-  void inputs(const void** ins, const void* in0) const {
-    ins[0] = in0;
-    for (int i = 1; i < a.g->num_inputs; ++i) ins[i] = a.in_rest[i - 1];
-  }
-  // out = A(in0), a plain launch
-  int apply_plain(const void* in0, void* out) const {
-    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    inputs(ins, in0);
-    return a.fn ? a.fn(a.g, ins, out, (void*)sc.stream, c) : neptune_hip_apply_builtin(a.body, a.g, ins, out, (void*)sc.stream, c);
-  }
-  // out = A(in0) and *dot_dev = out . in0 out of one dot-monitored launch; NEPTUNE_HIP_EUNSUPPORTED: nothing was launched
-  int apply_dot(const void* in0, void* out, T* dot_dev) const {
-    const void* ins[NEPTUNE_HIP_MAX_INPUTS];
-    inputs(ins, in0);
-    return a.fn ? a.fn_dot(a.g, ins, out, dot_dev, (void*)sc.stream, c)
-                : neptune_hip_apply_builtin_dot(a.body, a.g, ins, out, dot_dev, (void*)sc.stream, c);
-  }
-  // `count` consecutive device scalars, after everything queued on the stream
-  void read(const T* dev, int count, double* host) const {
-    T h[2] = {0, 0};
-    NEPTUNE_HIP_CHECK(hipMemcpyAsync(h, dev, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, sc.stream));
-    NEPTUNE_HIP_CHECK(hipStreamSynchronize(sc.stream));
-    for (int i = 0; i < count; ++i) host[i] = (double)h[i];
-  }
-  // rr_0 is known: -> whether there is nothing to iterate
-  bool done_after_setup(double rr) const {
-    if (a.rr0) *a.rr0 = rr;
-    if (a.rr_last) *a.rr_last = rr;
-    return rr <= a.tol2 || a.max_iters == 0;
   }
   // the part of the graph key every solver fills alike; n_out < 0 tells the solvers' keys from every loop's and from each other's
   void init_solver_key(LoopKey& key, int n_out) const {
@@ -780,7 +682,7 @@ struct SolverFrame {
       done += block;
       if (a.iters_done) *a.iters_done = done;
       double rr;
-      read(rr_dev, 1, &rr);
+      read_scalars(sc.stream, rr_dev, 1, &rr);
       ++g_cg_counts[2];
       if (a.rr_last) *a.rr_last = rr;
       if (rr <= a.tol2) break;   // false for a NaN: such a solve runs to max_iters
@@ -819,7 +721,7 @@ int cg_solve_typed(const StreamScope& sc, const SolveArgs& a) {
   // set-up: q = A(x), r = p = b - q on Omega, rr_0.  An apply stores nothing outside its launch region, and the flat update
   // reads q everywhere: where the region is not the whole box, q starts as +0 and stays so out there.
   if (!region_is_whole(a.g)) NEPTUNE_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)n * sizeof(T), sc.stream));
-  const int rc = S.apply_plain(x, q);
+  const int rc = S.A.apply(x, q);
   if (rc != NEPTUNE_HIP_OK) return rc;
   if (minv) hipLaunchKernelGGL(neptune_pcg_init<T>, S.init_grid, dim3(256), 0, sc.stream, S.B, S.nchunk, S.init_blocks, b, (const T*)q, minv, r, p, partials);
   else hipLaunchKernelGGL(neptune_cg_init<T>, S.init_grid, dim3(256), 0, sc.stream, S.B, S.nchunk, b, (const T*)q, r, p, partials);
@@ -827,12 +729,12 @@ int cg_solve_typed(const StreamScope& sc, const SolveArgs& a) {
   NEPTUNE_HIP_CHECK(hipGetLastError());
   double h[2];
   if (minv) {   // rz_0 and rr_0 lie side by side
-    S.read(&pscal->rz, 2, h);
+    read_scalars(sc.stream, &pscal->rz, 2, h);
     g_pcg_rz0 = h[0];
   } else {
-    S.read(&scal->rr, 1, &h[1]);
+    read_scalars(sc.stream, &scal->rr, 1, &h[1]);
   }
-  if (S.done_after_setup(h[1])) return NEPTUNE_HIP_OK;
+  if (done_after_setup(h[1], a.tol2, a.max_iters, a.rr0, a.rr_last)) return NEPTUNE_HIP_OK;
 
   LoopKey key;
   S.init_solver_key(key, -1);
@@ -844,11 +746,11 @@ int cg_solve_typed(const StreamScope& sc, const SolveArgs& a) {
   auto iteration = [&](int kind, int&) -> int {
     int rc;
     if (kind == 1) {
-      rc = S.apply_dot(p, q, pq_dev);
+      rc = S.A.apply_dot(p, q, pq_dev);
       if (rc != NEPTUNE_HIP_OK) return rc;
       key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
     } else {
-      rc = S.apply_plain(p, q);
+      rc = S.A.apply(p, q);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
       rc = neptune_hip_dot(dtype, a.g, q, p, pq_dev, (void*)sc.stream);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
@@ -893,14 +795,14 @@ int bicgstab_solve_typed(const StreamScope& sc, const SolveArgs& a) {
     NEPTUNE_HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(T), sc.stream));
     NEPTUNE_HIP_CHECK(hipMemsetAsync(t, 0, (size_t)n * sizeof(T), sc.stream));
   }
-  int rc = S.apply_plain(x, v);
+  int rc = S.A.apply(x, v);
   if (rc != NEPTUNE_HIP_OK) return rc;
   hipLaunchKernelGGL(neptune_bicg_init<T>, S.init_grid, dim3(256), 0, sc.stream, S.B, S.nchunk, static_cast<const T*>(a.b), (const T*)v, r, rh, p, partials);
   final_kernel(S.init_blocks, kBicgStart);
   NEPTUNE_HIP_CHECK(hipGetLastError());
   double rr;
-  S.read(&scal->rr, 1, &rr);
-  if (S.done_after_setup(rr)) return NEPTUNE_HIP_OK;
+  read_scalars(sc.stream, &scal->rr, 1, &rr);
+  if (done_after_setup(rr, a.tol2, a.max_iters, a.rr0, a.rr_last)) return NEPTUNE_HIP_OK;
 
   LoopKey key;
   S.init_solver_key(key, -2);
@@ -912,7 +814,7 @@ int bicgstab_solve_typed(const StreamScope& sc, const SolveArgs& a) {
   // which every iteration writes again before it reads them): a refusal -- NEPTUNE_HIP_EUNSUPPORTED, nothing launched -- is
   // remembered for the rest of the call, and an acceptance has grown the monitor workspace outside of any capture.
   if (S.fused_ok) {
-    rc = S.apply_dot(r, t, &scal->ts);
+    rc = S.A.apply_dot(r, t, &scal->ts);
     if (rc == NEPTUNE_HIP_EUNSUPPORTED) S.fused_ok = false;
     else if (rc != NEPTUNE_HIP_OK) return rc;
   }
@@ -921,7 +823,7 @@ int bicgstab_solve_typed(const StreamScope& sc, const SolveArgs& a) {
   // of one pass
   auto iteration = [&](int kind, int&) -> int {
     // 1. v = A(p), rv = rh . v, alpha
-    int rc = S.apply_plain(p, v);
+    int rc = S.A.apply(p, v);
     if (rc != NEPTUNE_HIP_OK) return late(rc);
     flat_launch(g_rv, sc.stream, neptune_bicg_rv<T, true>, neptune_bicg_rv<T, false>, n, rh, v, partials);
     final_kernel((int64_t)g_rv.blocks, kBicgRv);
@@ -930,13 +832,13 @@ int bicgstab_solve_typed(const StreamScope& sc, const SolveArgs& a) {
     NEPTUNE_HIP_CHECK(hipGetLastError());
     // 3. t = A(s), ts, tt, omega
     if (kind == 1) {
-      rc = S.apply_dot(r, t, &scal->ts);
+      rc = S.A.apply_dot(r, t, &scal->ts);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
       key.fields_b[1] = neptune_hip_monitor_workspace(0, (void*)sc.stream);   // where that launch's partials live: part of a graph
       flat_launch(g_tt, sc.stream, neptune_bicg_tt<T, true, false>, neptune_bicg_tt<T, false, false>, n, t, t, partials);
       final_kernel((int64_t)g_tt.blocks, kBicgTt);
     } else {
-      rc = S.apply_plain(r, t);
+      rc = S.A.apply(r, t);
       if (rc != NEPTUNE_HIP_OK) return late(rc);
       flat_launch(g_ts, sc.stream, neptune_bicg_tt<T, true, true>, neptune_bicg_tt<T, false, true>, n, t, r, partials);
       final_kernel((int64_t)g_ts.blocks, kBicgTsTt);
@@ -978,13 +880,9 @@ static int solver_args_checked(neptune_hip_apply_fn fn, int body, int dtype_of_f
   // the iteration feeds the result back as input 0: one box for both
   for (int d = 0; d < g->rank; ++d)
     if (g->in_lb[0][d] != g->out_lb[d] || g->in_ub[0][d] != g->out_ub[d]) return NEPTUNE_HIP_EINVAL;
-  int dtype = dtype_of_fn;
-  if (!fn) {
-    if (body < 0 || body >= NEPTUNE_HIP_BODY_COUNT) return NEPTUNE_HIP_EINVAL;
-    dtype = body == NEPTUNE_HIP_BODY_LAP3D27_F32 ? NEPTUNE_HIP_F32 : NEPTUNE_HIP_F64;
-  }
-  if (dtype != NEPTUNE_HIP_F64 && dtype != NEPTUNE_HIP_F32) return NEPTUNE_HIP_EINVAL;
-  const size_t elem = dtype == NEPTUNE_HIP_F64 ? 8 : 4;
+  int dtype = 0;
+  if (!entry_dtype(fn, body, dtype_of_fn, &dtype)) return NEPTUNE_HIP_EINVAL;
+  const size_t elem = elem_size(dtype);
   const size_t bytes = geom_box_bytes(g->out_lb, g->out_ub, g->rank, elem);
   const size_t trace_bytes = (size_t)trace_values * elem;
   for (int a = 0; a < count; ++a) {
@@ -994,12 +892,8 @@ static int solver_args_checked(neptune_hip_apply_fn fn, int body, int dtype_of_f
     if (trace && buffers_overlap(trace, trace_bytes, fields[a], bytes)) return NEPTUNE_HIP_EINVAL;
   }
   if (trace && (uintptr_t)trace % elem != 0) return NEPTUNE_HIP_EINVAL;
-  {
-    // rr is read back after every block: not while the caller's stream is being captured
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return NEPTUNE_HIP_EINVAL;
-  }
+  // rr is read back after every block: not while the caller's stream is being captured
+  if (stream_capturing(stream)) return NEPTUNE_HIP_EINVAL;
   *dtype_out = dtype;
   return NEPTUNE_HIP_OK;
 }
@@ -1010,9 +904,7 @@ static int solver_args_checked(neptune_hip_apply_fn fn, int body, int dtype_of_f
 enum Solver { kSolverCg, kSolverPcg, kSolverBicgstab };
 static int solve_checked(Solver solver, int dtype_of_fn, void* stream, const SolveArgs& a) {
   g_cg_counts[0] = g_cg_counts[1] = g_cg_counts[2] = 0;
-  if (a.iters_done) *a.iters_done = 0;
-  if (a.rr0) *a.rr0 = 0.0;
-  if (a.rr_last) *a.rr_last = 0.0;
+  reset_solver_outputs(a.iters_done, a.rr0, a.rr_last);
   if (!a.work) return NEPTUNE_HIP_EINVAL;
   const int n_work = solver == kSolverBicgstab ? 5 : 3;
   const int cols = solver == kSolverCg ? 2 : solver == kSolverPcg ? 3 : 5;

@@ -194,12 +194,30 @@ def cg_counts():
     return fused.value, fallback.value, checks.value
 
 
+def resolve_dot(who: str, entry, dot):
+    """a solver's `dot` argument -- "auto", "fallback", None or a dot entry -- as the fn_dot pointer to hand the C entry, or
+    None: a plain launch and a separate dot product.  entry: the operator (only a lowered entry can have one to hand over; a
+    built-in body's is the library's own).  who: the caller's name in the error text."""
+    is_entry = hasattr(entry, "fn")
+    if isinstance(dot, str):
+        if dot not in ("auto", "fallback"):
+            raise ValueError(f'{who}: dot is "auto", "fallback", None or a dot entry')
+        dot = entry if (dot == "auto" and is_entry) else None
+    return C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+
+
+def trace_buffer(cols: int, max_iters: int, like_tensor, dtype=None):
+    """a zeroed device tensor for a solver's trace: `cols` values per iteration (never empty), on like_tensor's device and
+    of its element type unless `dtype` says otherwise"""
+    import torch
+    return torch.zeros(cols * max(int(max_iters), 1), dtype=dtype or like_tensor.dtype, device=like_tensor.device)
+
+
 def _krylov_solve(entry, x, b, bounds, max_iters, tol2, check_every, others, trace, dot, cfg, work, region, stream, *,
                   who, symbol, n_work, out_index, cols, extra=()):
     """what cg_solve and bicgstab_solve share: the entries, the geometry (the field work[out_index] receives the operator's
     result), the n_work work fields and the trace of `cols` values per iteration, then the C entry `symbol`(fn, fn_dot, body,
     dtype, g, x, b, *extra, work, ...) and the result tuple.  who: the caller's name in error texts."""
-    import torch
     lib = _capi.load()
     others = list(others)
     if work is None:
@@ -208,12 +226,8 @@ def _krylov_solve(entry, x, b, bounds, max_iters, tol2, check_every, others, tra
     st = current_stream_ptr() if stream is None else stream
     is_entry = hasattr(entry, "fn")
     fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
-    if isinstance(dot, str):
-        if dot not in ("auto", "fallback"):
-            raise ValueError(f'{who}: dot is "auto", "fallback", None or a dot entry')
-        dot = entry if (dot == "auto" and is_entry) else None
-    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
-    tr = torch.zeros(cols * max(max_iters, 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    fn_dot = resolve_dot(who, entry, dot)
+    tr = trace_buffer(cols, max_iters, x.tensor) if trace else None
     warr = (C.c_void_p * n_work)(*[f.ptr for f in work])
     rest = _in_array(others) if others else None
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)

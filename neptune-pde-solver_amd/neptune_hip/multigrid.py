@@ -370,6 +370,20 @@ def face_rules(faces, rank: int, what: str = "prolong"):
     return [_FACE_RULE[f[0]] for f in pairs], [_FACE_RULE[f[1]] for f in pairs]
 
 
+def _fill_level(struct, L: Level, x: DeviceField, b: DeviceField, q: DeviceField, keep: list) -> None:
+    """the operator of level L and its fields x, b, q into one neptune_hip_mg_level_t (all but minv); what must stay alive
+    while the struct is used is appended to `keep`"""
+    is_entry = hasattr(L.entry, "fn")
+    struct.fn = C.cast(L.entry.fn, C.c_void_p) if is_entry else None
+    struct.body = -1 if is_entry else int(L.entry)
+    struct.g = L.geom
+    if L.others:
+        rest = (C.c_void_p * len(L.others))(*[f.ptr for f in L.others])
+        keep.append(rest)
+        struct.in_rest = rest
+    struct.x, struct.b, struct.q, struct.rscale = x.ptr, b.ptr, q.ptr, L.rscale
+
+
 class Hierarchy:
     """the levels of a solve, finest first.  Checks the size relation per dimension -- coarsened, m_l = 2 m_(l+1) + 1, or
     kept, m_l = m_(l+1); at least one coarsened -- (ValueError naming the level and the dimension), one rank and one
@@ -437,19 +451,8 @@ class Hierarchy:
         for l, L in enumerate(self.levels):
             if L.minv is None and not L.lines:
                 raise ValueError(f"multigrid: level {l} has no minv (jacobi_weights) and no line stages")
-            is_entry = hasattr(L.entry, "fn")
-            arr[l].fn = C.cast(L.entry.fn, C.c_void_p) if is_entry else None
-            arr[l].body = -1 if is_entry else int(L.entry)
-            arr[l].g = L.geom
-            if L.others:
-                rest = (C.c_void_p * len(L.others))(*[f.ptr for f in L.others])
-                keep.append(rest)
-                arr[l].in_rest = rest
+            _fill_level(arr[l], L, x if l == 0 else self.x[l], b if l == 0 else self.b[l], self.q[l], keep)
             arr[l].minv = L.minv.ptr if L.minv is not None else None
-            arr[l].x = (x if l == 0 else self.x[l]).ptr
-            arr[l].b = (b if l == 0 else self.b[l]).ptr
-            arr[l].q = self.q[l].ptr
-            arr[l].rscale = L.rscale
         return arr, keep
 
     @property
@@ -574,7 +577,6 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
     r, p, z (allocated here when None).  cfg: the launch configuration of level 0's operator.
     Blocking; -> (iters, rr0, rr_last), and with trace=True a fourth item: a numpy array of shape (iters, 3) holding
     (p . A(p) of iteration k, r . M(r) after it, r . r after it).  cg_counts() tells how the iterations were launched."""
-    import torch
     lib = _capi.load()
     first = h.levels[0].like
     if x.box != first.box or b.box != first.box or x.dtype != h.dtype or b.dtype != h.dtype:
@@ -588,16 +590,10 @@ def cg_solve(h: Hierarchy, x: DeviceField, b: DeviceField, sweeps: int = 2, coar
                          "only (its fused first and last sweeps on level 0): pass lines=True for neptune_hip_mgcg_solve_lines")
     if work is None:
         work = [DeviceField.empty_like(x) for _ in range(3)]
-    entry = h.levels[0].entry
-    is_entry = hasattr(entry, "fn")
-    if isinstance(dot, str):
-        if dot not in ("auto", "fallback"):
-            raise ValueError('multigrid.cg_solve: dot is "auto", "fallback", None or a dot entry')
-        dot = entry if (dot == "auto" and is_entry) else None
-    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    fn_dot = _apply.resolve_dot("multigrid.cg_solve", h.levels[0].entry, dot)
     arr, keep = h._structs(x, b)
     st = current_stream_ptr() if stream is None else stream
-    tr = torch.zeros(3 * max(int(max_iters), 1), dtype=x.tensor.dtype, device=x.tensor.device) if trace else None
+    tr = _apply.trace_buffer(3, max_iters, x.tensor) if trace else None
     warr = (C.c_void_p * 3)(*[f.ptr for f in work])
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
     rest = (fn_dot, sweeps, coarse_sweeps, warr, max_iters, check_every, tol2, tr.data_ptr() if trace else None, st,
@@ -661,25 +657,12 @@ def cg_solve_mixed(outer: Level, inner: Hierarchy, x: DeviceField, b: DeviceFiel
         work.append(DeviceField.empty_like(x))
     if len(work) != 3 or any(f.box != x.box or f.dtype != _capi.F64 for f in work):
         raise ValueError("multigrid.cg_solve_mixed: work is two or three float64 fields like x (r, p[, q])")
-    entry = outer.entry
-    is_entry = hasattr(entry, "fn")
-    if isinstance(dot, str):
-        if dot not in ("auto", "fallback"):
-            raise ValueError('multigrid.cg_solve_mixed: dot is "auto", "fallback", None or a dot entry')
-        dot = entry if (dot == "auto" and is_entry) else None
-    fn_dot = C.cast(dot.fn_dot, C.c_void_p) if (is_entry and dot is not None and dot.fn_dot is not None) else None
+    fn_dot = _apply.resolve_dot("multigrid.cg_solve_mixed", outer.entry, dot)
     arr, keep = inner._structs(inner.x[0], inner.b[0])
     out = (_capi.MgLevel * 1)()
-    out[0].fn = C.cast(entry.fn, C.c_void_p) if is_entry else None
-    out[0].body = -1 if is_entry else int(entry)
-    out[0].g = outer.geom
-    if outer.others:
-        rest_in = (C.c_void_p * len(outer.others))(*[f.ptr for f in outer.others])
-        keep.append(rest_in)
-        out[0].in_rest = rest_in
-    out[0].x, out[0].b, out[0].q, out[0].rscale = x.ptr, b.ptr, work[2].ptr, outer.rscale
+    _fill_level(out[0], outer, x, b, work[2], keep)
     st = current_stream_ptr() if stream is None else stream
-    tr = torch.zeros(3 * max(int(max_iters), 1), dtype=torch.float64, device=x.tensor.device) if trace else None
+    tr = _apply.trace_buffer(3, max_iters, x.tensor, torch.float64) if trace else None
     warr = (C.c_void_p * 2)(work[0].ptr, work[1].ptr)
     done, rr0, last = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
     head = (out, _capi.F64, fn_dot, arr, inner._line_structs() if inner.has_lines else None)
