@@ -159,6 +159,9 @@ typedef struct {
  *    and lets the caller free() them (NeptunePETScRuntime.cpp:219-221).  Device-resident
  *    buffers follow the same callee-allocates / caller-frees rule through
  *    neptune_hip_malloc / neptune_rt_free.
+ *    A lowered function stages every host-memory memref argument through a device copy; host
+ *    arguments that name the identical bytes share that copy (they are one memory, as two device
+ *    arguments at one address are), host arguments that overlap otherwise are refused.
  * ---------------------------------------------------------------------------------- */
 /* Select the HIP device for this process (one process per GPU).  Idempotent. */
 void neptune_hip_init(int device);

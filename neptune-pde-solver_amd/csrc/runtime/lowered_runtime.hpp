@@ -8,7 +8,10 @@
 //   * residency : a memref argument may point to host or to device memory.  Host buffers get a
 //     device shadow (H2D once at entry, D2H at exit if a neptune_ir.store dirtied it), so existing
 //     host drivers and the PETSc MatMult thunk (NeptunePETScRuntime.cpp:182-230) keep working;
-//     device buffers are used in place, which is the fast path (nothing crosses PCIe).
+//     device buffers are used in place, which is the fast path (nothing crosses PCIe).  Host
+//     arguments that name the identical bytes are ONE memory, as they are on the device: they share
+//     one shadow (and its dirty flag), so a store through one name is seen through the other and
+//     copied back once; host arguments that overlap without being identical are refused.
 //   * ownership : an apply result is allocated by the callee and released by the caller
 //     (DataflowLowering.cpp:281; NeptunePETScRuntime.cpp:219-221 `free(yout.allocated)`).  If any
 //     argument was host memory the result is returned in malloc'ed host memory so `free()` works;
@@ -70,6 +73,7 @@ struct Val {
 };
 
 struct HostArg {          // a memref argument that arrived in host memory
+  int arg;                // index of the (first) argument that names it
   void* host;             // first element (aligned + offset)
   void* dev;              // its device shadow
   size_t bytes;
@@ -145,12 +149,29 @@ class Scope {
       v.box.ub[d] = sizes[d];
     }
     char* first = static_cast<char*>(aligned) + offset * esize;
+    const int arg = nbound_++;
     if (neptune_hip_is_device_ptr(first)) {
       v.dev = first;
     } else {
+      const size_t bytes = (size_t)v.count * esize;
+      for (size_t i = 0; i < host_args_.size(); ++i) {
+        const HostArg& o = host_args_[i];
+        if (o.host == first && o.bytes == bytes) {   // the same memory under a second name: one shadow, one dirty flag
+          v.dev = o.dev;
+          v.shadow = (int)i;
+          return v;
+        }
+        if (first < static_cast<char*>(o.host) + o.bytes && static_cast<char*>(o.host) < first + bytes) {
+          char msg[160];
+          snprintf(msg, sizeof msg, "memref arguments %d and %d are host buffers that overlap without being identical "
+                                    "(their shadows on the device would be two memories)", o.arg, arg);
+          die(fn_, msg);
+        }
+      }
       HostArg h;
+      h.arg = arg;
       h.host = first;
-      h.bytes = (size_t)v.count * esize;
+      h.bytes = bytes;
       h.dirty = false;
       h.dev = neptune_hip_pool_alloc(h.bytes);
       owned_.push_back({h.dev, h.bytes});
@@ -271,6 +292,7 @@ class Scope {
     return v.box.same_shape(b);
   }
   const char* fn_;
+  int nbound_ = 0;          // memref arguments bound so far
   void* pending_ = nullptr;
   bool slab_on_ = false;
   int64_t slab_[4] = {0, 0, 0, 0};
